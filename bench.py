@@ -2,10 +2,12 @@
 """Benchmark of the MI355X Spartan proving path (NIZK mode = the headline; SNARK mode, sweep and transports as extras).
 
   python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run, one rank per GPU)
+  python bench.py ... --full                           the extras below too (without it the run only sets up, warms up, times and prints)
+  python bench.py ... --dump-outputs DIR               rank 0 writes the last timed step's proof to DIR/proof.npy (its bytes as float32)
 
 Metric (BASELINE.json, SURVEY.md 8(d)): R1CS constraints proved per second = N_constraints / wall time of NIZK::prove, on the
 synthetic satisfiable 2^20-constraint R1CS; instance, generators (with their window table) and witness resident in HBM before timing.
-A "step" is ONE NIZK::prove of that workload, one proof at a time, exactly as a library caller runs it (armed launches on: the HIP
+A "step" is ONE NIZK::prove of that workload, one proof at a time, exactly as a library caller runs it (armed launches on; with --full the HIP
 events of the timed region bracket only the dominant kernel class, which has no armed launches); W untimed warm-up steps, then exactly
 K timed steps bracketed by barrier + device synchronisation; time = max over ranks; rank 0 prints ONE JSON line.
 
@@ -16,7 +18,7 @@ K timed steps bracketed by barrier + device synchronisation; time = max over ran
           2^20 * K / elapsed of that one sharded proof; "scaling": "strong".  --replicas makes the primary line independent proofs per
           GPU instead (weak scaling).
 
-Extras in the same line (all measured in this run, none of them the headline):
+Extras in the same line, only with --full (all measured in this run, none of them the headline; a plain run reports them as null):
   roofline      N = 1: the kernel class with the largest summed device time of one instrumented proof, over ALL classes; N > 1: the
                 same class as at N = 1 (msm_rows, the witness commitment) with this rank's share of the scalars, so the lines of a
                 scaling run are comparable.  Algorithmic bytes per launch / average launch duration (HIP events on the library's
@@ -34,9 +36,10 @@ Extras in the same line (all measured in this run, none of them the headline):
                 proof compared with the oracle digests committed in tests/golden/snark_proofs.json; CPU oracle on a bounded 2^16 sample
                 (N > 1: one independent SNARK::prove per GPU between barriers — SNARK mode is not sharded — aggregate over the ranks, "scaling": "weak")
   spzk_e2e      the path run.py actually executes: `spzk verify --nizk` on a zkInterface triple of the workload, one process
-Every timed proof is checked: identical bytes across steps (fixed seed), accepted by the verifier, equal to the oracle's committed
+With --full every timed proof is checked: identical bytes across steps (fixed seed), accepted by the verifier, equal to the oracle's committed
 digest for the size; rank 0 also compares a 2^12 proof with the CPU oracle (checker only, outside the timed region) and, when the CPU
-baseline runs the same workload, the full-size proof.
+baseline runs the same workload, the full-size proof.  --full also instruments the run: one untimed proof with per-class kernel timing
+picks the dominant class, and the timed steps bracket that class's launches with HIP events (the roofline figures).
 OTTI_BENCH_REHEARSE=1 puts every rank on GPU 0 with the gloo backend (how the sharded mode is rehearsed on a one-GPU box).
 """
 import argparse
@@ -194,7 +197,12 @@ def main():
     ap.add_argument("--in-flight", type=int, default=0, help="extra figure: proofs in flight per GPU (prover threads).  0 = what this rank's host cores feed "
                     "(2 host threads per prover, at most 6); -1 = skip")
     ap.add_argument("--concurrent", type=int, default=None, help="alias of --in-flight (older command lines)")
+    ap.add_argument("--full", action="store_true", help="also run the extras (instrumented proof and roofline, checks against the verifier and the oracle, CPU "
+                    "baseline, transports, sweep, in-flight, SNARK, spzk_e2e); the --no-* and size options above only apply with it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's proof to DIR/proof.npy (its bytes as float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.concurrent is not None:
         args.in_flight = args.concurrent if args.concurrent != 1 else -1
 
@@ -323,17 +331,19 @@ def main():
         return oa.NIZK.prove_sharded(i_, w_, g_, label, seed) if shard else oa.NIZK.prove(i_, w_, None, g_, label, seed)
 
     proofs = [prove_once() for _ in range(args.warmup)]
-    # one untimed, fully instrumented proof: per-class kernel time -> the dominant kernel class, chosen over ALL classes at N = 1; a
-    # sharded run keeps the N = 1 choice (the witness commitment) so that the roofline of every line of a scaling run is the same kernel
-    oa.stats_enable(True)
-    proofs.append(prove_once())
-    breakdown = oa.stats_read()
-    dom = max(breakdown, key=lambda k: breakdown[k][1])
-    if shard and breakdown.get("msm_rows", (0, 0))[0]:
-        dom = "msm_rows"
-    # timed region: HIP events only around the dominant class (two event records per launch would otherwise tax every round, and a
-    # class with armed launches cannot be timed with them on); everything else runs exactly as a library caller runs it
-    oa.stats_enable(True, only=dom)
+    breakdown, dom = {}, None
+    if args.full:
+        # one untimed, fully instrumented proof: per-class kernel time -> the dominant kernel class, chosen over ALL classes at N = 1; a
+        # sharded run keeps the N = 1 choice (the witness commitment) so that the roofline of every line of a scaling run is the same kernel
+        oa.stats_enable(True)
+        proofs.append(prove_once())
+        breakdown = oa.stats_read()
+        dom = max(breakdown, key=lambda k: breakdown[k][1])
+        if shard and breakdown.get("msm_rows", (0, 0))[0]:
+            dom = "msm_rows"
+        # timed region: HIP events only around the dominant class (two event records per launch would otherwise tax every round, and a
+        # class with armed launches cannot be timed with them on); everything else runs exactly as a library caller runs it
+        oa.stats_enable(True, only=dom)
     armed_on = oa.armed_launches_on()
     barrier()
     t0 = time.perf_counter()
@@ -343,37 +353,43 @@ def main():
         t_step = time.perf_counter()
         p = prove_once()                                       # returns after the library's stream has been synchronised
         step_ms.append(1e3 * (time.perf_counter() - t_step))
-        proofs.append(p)
+        if args.full:
+            proofs.append(p)
         for k, v in p.stage_ms.items():
             stage_acc[k] = stage_acc.get(k, 0.0) + v
     barrier()
     elapsed = time.perf_counter() - t0
-    stats = dict(oa.stats_read())
-    oa.stats_enable(False)
-    madd_peak = oa.madd_peak()                                 # the MSM's ALU roof, measured in this run (after the timed region)
-    frmul_peak = oa.fr_mul_peak()                              # the streaming kernels' second roof: Montgomery products in GF(l) per second
+    final_proof = p.bytes
+    if args.full:
+        stats = dict(oa.stats_read())
+        oa.stats_enable(False)
+        madd_peak = oa.madd_peak()                             # the MSM's ALU roof, measured in this run (after the timed region)
+        frmul_peak = oa.fr_mul_peak()                          # the streaming kernels' second roof: Montgomery products in GF(l) per second
+    elapsed = max_over_ranks(elapsed)
+    if args.dump_outputs and rank == 0:
+        # what a caller of NIZK::prove receives: the proof bytes (deterministic: fixed instance, witness and seed), one float32 per byte
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "proof.npy"), np.frombuffer(final_proof, dtype=np.uint8).astype(np.float32))
 
     # correctness of what was timed
-    digests = {hashlib.sha256(p.bytes).hexdigest() for p in proofs}
-    assert len(digests) == 1, "proofs of the same inputs and seed differ between steps"
-    gold = golden_digest("nizk", n) if (args.dist == "uniform" and (shard or world == 1)) else None
-    digest_ok = None if gold is None else (gold["proof_sha256"] in digests)
-    assert digest_ok is not False, "the timed proof differs from the oracle's committed digest for this size"
-    t_verify_calls = []
-    for _ in range(3):                                       # the first call allocates the verifier's device buffers (kept with the context afterwards)
-        t0 = time.perf_counter()
-        proofs[-1].verify(inst, inputs, gens, label)
-        t_verify_calls.append(time.perf_counter() - t0)
-    t_verify = min(t_verify_calls)
-    elapsed = max_over_ranks(elapsed)
-    if shard:
-        same_on_every_rank(proofs[-1].bytes, "ranks of a sharded proof returned different bytes")
-    final_proof = proofs[-1].bytes
+    digests, digest_ok, t_verify_calls = {hashlib.sha256(final_proof).hexdigest()}, None, []
+    if args.full:
+        digests = {hashlib.sha256(p.bytes).hexdigest() for p in proofs}
+        assert len(digests) == 1, "proofs of the same inputs and seed differ between steps"
+        gold = golden_digest("nizk", n) if (args.dist == "uniform" and (shard or world == 1)) else None
+        digest_ok = None if gold is None else (gold["proof_sha256"] in digests)
+        assert digest_ok is not False, "the timed proof differs from the oracle's committed digest for this size"
+        for _ in range(3):                                   # the first call allocates the verifier's device buffers (kept with the context afterwards)
+            t0 = time.perf_counter()
+            proofs[-1].verify(inst, inputs, gens, label)
+            t_verify_calls.append(time.perf_counter() - t0)
+        if shard:
+            same_on_every_rank(proofs[-1].bytes, "ranks of a sharded proof returned different bytes")
     del proofs
 
     # ---- extra (N > 1): the same sharded proof over the other transport of the per-round sums, in this run
     transports = None
-    if shard and not args.no_transports:
+    if args.full and shard and not args.no_transports:
         ksteps = max(2, min(args.steps, 10))
         transports = {transport: {"ms_per_proof": round(1e3 * elapsed / max(1, args.steps), 3), "steps": args.steps, "primary": True}}
         other = "rccl" if transport == "mailbox" else "mailbox"
@@ -403,7 +419,7 @@ def main():
 
     # ---- extra: B independent proofs in flight per GPU, each prover thread with its own instance, witness and seed
     in_flight = None
-    if conc >= 1:
+    if args.full and conc >= 1:
         isteps = max(2, min(2 * args.steps, 40))              # 40 proofs per thread by default: a tenth of a second of proving said little (the figure moved by 2 x between runs)
         jobs = []
         for t in range(conc):
@@ -451,7 +467,8 @@ def main():
     ms_per_step = 1e3 * elapsed / steps
     value = (world if (world > 1 and not shard) else 1) * n * steps / elapsed
 
-    import orc                                                  # the oracle: checker and cpu_baseline leg only
+    if args.full:
+        import orc                                              # the oracle: checker and cpu_baseline leg only
 
     def cpu_oracle_nizk(cr, cores):
         """one NIZK::prove (+ verify) of the instance by the plain-C oracle on `cores` host threads: (proof, seconds, stage ms, prove + verify ms)"""
@@ -477,7 +494,7 @@ def main():
 
     # ---- extra: the other sizes of BASELINE.json's range, sharded like the headline when N > 1 (collective: every rank takes part)
     sweep = None
-    sweep_sizes = [] if (args.no_sweep or not args.sweep.strip() or args.dist != "uniform" or (world > 1 and not shard)) else \
+    sweep_sizes = [] if (not args.full or args.no_sweep or not args.sweep.strip() or args.dist != "uniform" or (world > 1 and not shard)) else \
         [int(x) for x in args.sweep.split(",") if x.strip() and int(x) != lg]
     if sweep_sizes:
         sweep = {}
@@ -534,7 +551,7 @@ def main():
     # SNARK mode at N > 1: SNARK::prove is not sharded — every GPU proves the same instance on its own (replicas), between barriers; the
     # figure is world x n / (the slowest rank's best proof).  No collective sits inside a try block: a rank that fails still reaches them.
     snark_multi = None
-    if world > 1 and not args.no_snark and (not rehearse or os.environ.get("OTTI_BENCH_REHEARSE_SNARK")):
+    if args.full and world > 1 and not args.no_snark and (not rehearse or os.environ.get("OTTI_BENCH_REHEARSE_SNARK")):
         import torch
         s_err, s_ms, s_dig, s_stage = None, float("inf"), None, None
         try:
@@ -600,14 +617,16 @@ def main():
             dist.destroy_process_group()
         return
 
-    # oracle cross-check of the GPU path (checker only; small size, outside the timed region)
-    rs = oa.synth_r1cs(1 << 12, ni, 1)
-    si = oa.Instance.new(rs["num_cons"], rs["num_vars"], rs["num_inputs"], rs["A"], rs["B"], rs["C"]); sg = oa.NIZKGens.new(1 << 12, 1 << 12, ni)
-    sp = oa.NIZK.prove(si, oa.VarsAssignment.new(rs["vars"]), oa.InputsAssignment.new(rs["inputs"]), sg, label, seed)
-    oi, og = orc.OInstance(1 << 12, 1 << 12, ni, rs["A"], rs["B"], rs["C"]), orc.OGens(1 << 12, 1 << 12, ni)
-    op, _ = orc.nizk_prove(oi, rs["vars"], rs["inputs"], og, label, seed)
-    parity_ok = sp.bytes == op
-    del si, sg, sp
+    parity_ok = None
+    if args.full:
+        # oracle cross-check of the GPU path (checker only; small size, outside the timed region)
+        rs = oa.synth_r1cs(1 << 12, ni, 1)
+        si = oa.Instance.new(rs["num_cons"], rs["num_vars"], rs["num_inputs"], rs["A"], rs["B"], rs["C"]); sg = oa.NIZKGens.new(1 << 12, 1 << 12, ni)
+        sp = oa.NIZK.prove(si, oa.VarsAssignment.new(rs["vars"]), oa.InputsAssignment.new(rs["inputs"]), sg, label, seed)
+        oi, og = orc.OInstance(1 << 12, 1 << 12, ni, rs["A"], rs["B"], rs["C"]), orc.OGens(1 << 12, 1 << 12, ni)
+        op, _ = orc.nizk_prove(oi, rs["vars"], rs["inputs"], og, label, seed)
+        parity_ok = sp.bytes == op
+        del si, sg, sp
 
     def traffic_of(kernel_name, snark_run=False):
         """HBM bytes of the kernel's largest launch from a SEPARATE rocprofv3 --pmc pass kept under profiles/ (never measured in this run)"""
@@ -652,30 +671,32 @@ def main():
                                  "roof no implementation of this formula on these limbs can pass (carry sweeps, additions and the table gather all come on top)"}
         return rf
 
-    roofline = roofline_of(dom, stats, breakdown, lambda c_: class_bytes_per_proof(c_, N, V, nnz), world if shard else 1)
-    if roofline is not None and world > 1:
-        roofline["note"] = "N > 1: fixed to the class that dominates at N = 1 (the witness commitment), priced on this rank's 1/%d share of the scalars" % world
-    # ---- the second roof of the "streaming" classes: they carry 7-13 Montgomery products per 192 bytes, so the multiplier binds before HBM does.
-    # products per proof by the kernels' own arithmetic (k_sumcheck.hip, k_sparse.hip): phase one 7 per pair in the first round and 13 per
-    # quad in the fused fold + sums rounds (10 N in all); phase two 2 per pair, then 6 per quad (8 V over tables of 2 V); the two sparse
-    # products one per non-zero entry (+ 3 per output row for the fused combination); eq tables one per element written
-    products = {"sc_cubic": 10 * N, "sc_quad": 8 * (2 * V) // 2, "spmv": 2 * nnz + 3 * 2 * V, "eq": N + 2 * V}
-    field_mul = {"peak": round(frmul_peak / 1e9, 2), "unit": "G Montgomery products/s", "classes": {},
-                 "note": "peak = otti_bench_fr_mul_peak measured in this run: the nine-limb product of fr9.h (round 4; operands unpacked in registers, two chains per lane, every CU "
-                         "busy): 135 v_mad_u64_u32 + 17 64-bit shifts + 9 v_mul_lo_u32 ('heavy': ~4.3 nominal cycles per wave instruction each) + ~27 masks and moves (~2.4) in one asm block; "
-                         "the 8 x u32 form it replaces (104 multiply-adds + 104 carry adds, 143-147 G/s) is timed beside it by tools/limbbench (profiles/r4_limbbench.txt); "
-                         "classes: products per proof / summed device time of the class in one instrumented proof "
-                         "(most launches of a sum-check are rounds too short to fill the chip, so the whole-proof rate sits far below the roof; profiles/*kbw* has the rates at size)"}
-    for cls, nprod in products.items():
-        if breakdown.get(cls, (0, 0))[0]:
-            rate = nprod / (world if shard else 1) / (breakdown[cls][1] * 1e-3)
-            field_mul["classes"][cls] = {"products_per_proof": int(nprod), "ms_per_proof": round(breakdown[cls][1], 3), "achieved": round(rate / 1e9, 2), "frac": round(rate / frmul_peak, 4),
-                                         "hbm_frac": round(class_bytes_per_proof(cls, N, V, nnz) / (world if shard else 1) / (breakdown[cls][1] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)}
+    roofline, field_mul = None, None
+    if args.full:
+        roofline = roofline_of(dom, stats, breakdown, lambda c_: class_bytes_per_proof(c_, N, V, nnz), world if shard else 1)
+        if roofline is not None and world > 1:
+            roofline["note"] = "N > 1: fixed to the class that dominates at N = 1 (the witness commitment), priced on this rank's 1/%d share of the scalars" % world
+        # ---- the second roof of the "streaming" classes: they carry 7-13 Montgomery products per 192 bytes, so the multiplier binds before HBM does.
+        # products per proof by the kernels' own arithmetic (k_sumcheck.hip, k_sparse.hip): phase one 7 per pair in the first round and 13 per
+        # quad in the fused fold + sums rounds (10 N in all); phase two 2 per pair, then 6 per quad (8 V over tables of 2 V); the two sparse
+        # products one per non-zero entry (+ 3 per output row for the fused combination); eq tables one per element written
+        products = {"sc_cubic": 10 * N, "sc_quad": 8 * (2 * V) // 2, "spmv": 2 * nnz + 3 * 2 * V, "eq": N + 2 * V}
+        field_mul = {"peak": round(frmul_peak / 1e9, 2), "unit": "G Montgomery products/s", "classes": {},
+                     "note": "peak = otti_bench_fr_mul_peak measured in this run: the nine-limb product of fr9.h (round 4; operands unpacked in registers, two chains per lane, every CU "
+                             "busy): 135 v_mad_u64_u32 + 17 64-bit shifts + 9 v_mul_lo_u32 ('heavy': ~4.3 nominal cycles per wave instruction each) + ~27 masks and moves (~2.4) in one asm block; "
+                             "the 8 x u32 form it replaces (104 multiply-adds + 104 carry adds, 143-147 G/s) is timed beside it by tools/limbbench (profiles/r4_limbbench.txt); "
+                             "classes: products per proof / summed device time of the class in one instrumented proof "
+                             "(most launches of a sum-check are rounds too short to fill the chip, so the whole-proof rate sits far below the roof; profiles/*kbw* has the rates at size)"}
+        for cls, nprod in products.items():
+            if breakdown.get(cls, (0, 0))[0]:
+                rate = nprod / (world if shard else 1) / (breakdown[cls][1] * 1e-3)
+                field_mul["classes"][cls] = {"products_per_proof": int(nprod), "ms_per_proof": round(breakdown[cls][1], 3), "achieved": round(rate / 1e9, 2), "frac": round(rate / frmul_peak, 4),
+                                             "hbm_frac": round(class_bytes_per_proof(cls, N, V, nnz) / (world if shard else 1) / (breakdown[cls][1] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)}
     whole = algorithmic_bytes(N, V, nnz)
     proof_gbps = whole / (ms_per_step * 1e-3) / 1e9
 
     cpu_baseline, cpu_e2e_ms = None, None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         cores = cpu_cores
         clg = args.cpu_log2 if args.cpu_log2 is not None else lg
         cr = r if clg == lg else gen(1 << clg, ni, 1)
@@ -698,7 +719,7 @@ def main():
 
     # ---- the one-shot path run.py executes: spzk verify --nizk <three zkif files>, one process
     spzk_e2e = None
-    if not args.no_e2e and world == 1:
+    if args.full and not args.no_e2e and world == 1:
         spzk = os.path.join(ROOT, "otti_amd", "spzk")
         with tempfile.TemporaryDirectory(prefix="otti-bench-") as td:
             pre = os.path.join(td, "w")
@@ -747,7 +768,7 @@ def main():
 
     # ---- SNARK mode (BASELINE.json's metric names it; run.py itself only invokes --nizk): SNARK::encode once, then SNARK::prove of the same workload
     snark = None
-    if not args.no_snark and world == 1:
+    if args.full and not args.no_snark and world == 1:
         slabel = b"snark_example"
         nz = nnz // 3 if args.dist == "uniform" else int(max(r["A"].size, r["B"].size, r["C"].size))
         # the headline's NIZK window table (97 GB) makes room: a SNARK prover holds the two tables of SNARKGens and no third one; with the card to
@@ -840,13 +861,14 @@ def main():
         "snark": snark if world == 1 else snark_multi,
         "spzk_e2e": spzk_e2e,
         "stage_ms": {k: round(v / steps, 3) for k, v in stage_acc.items()},
-        "kernel_ms_per_proof": {k: round(v[1], 3) for k, v in breakdown.items() if v[0]},
-        "kernel_launches_per_proof": {k: v[0] for k, v in breakdown.items() if v[0]},
+        "kernel_ms_per_proof": {k: round(v[1], 3) for k, v in breakdown.items() if v[0]} if args.full else None,
+        "kernel_launches_per_proof": {k: v[0] for k, v in breakdown.items() if v[0]} if args.full else None,
         "whole_proof_algorithmic_GBps": round(proof_gbps, 2), "whole_proof_hbm_frac": round(proof_gbps / (HBM_PEAK_GBPS * (world if shard else 1)), 6),
         "prepare_device_ms": round(1e3 * t_prepare, 1),
         "prepare_device_breakdown_ms": {"window_table_allocations": round(table_alloc_ms, 1), "window_table_upload_and_kernels": round(table_kernels_ms, 1),
                                         "instance_upload_and_csr_build": round(1e3 * t_prepare - table_alloc_ms - table_kernels_ms, 1),
-                                        "note": "hipMalloc of the table (tens of GB: the driver maps and clears the pages) is the part that varies between boxes; the kernels scale with the table"}, "witness_upload_ms": round(1e3 * t_upload, 2), "verify_ms": round(1e3 * t_verify, 2), "verify_first_call_ms": round(1e3 * t_verify_calls[0], 2),
+                                        "note": "hipMalloc of the table (tens of GB: the driver maps and clears the pages) is the part that varies between boxes; the kernels scale with the table"}, "witness_upload_ms": round(1e3 * t_upload, 2), "verify_ms": round(1e3 * min(t_verify_calls), 2) if t_verify_calls else None,
+        "verify_first_call_ms": round(1e3 * t_verify_calls[0], 2) if t_verify_calls else None,
         "proof_bytes": len(final_proof), "proof_sha256": next(iter(digests)), "equals_oracle_digest": digest_ok, "oracle_parity_2^12": parity_ok,
         "wall_s": round(time.perf_counter() - t_start, 1),
     }

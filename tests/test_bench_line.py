@@ -47,7 +47,7 @@ def test_two_rank_rehearsal_of_the_drivers_command(tmp_path):
     env = dict(os.environ); env["OTTI_BENCH_REHEARSE"] = "1"; env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env["OTTI_BENCH_REHEARSE_SNARK"] = "1"; env["OTTI_MSM_TABLE_GB"] = "16"          # the SNARK replicas leg too; two ranks' window tables on ONE card
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29533",
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--log2-constraints", "18", "--sweep", "16", "--in-flight", "-1"]
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--log2-constraints", "18", "--sweep", "16", "--in-flight", "-1"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     line = [ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1]
@@ -67,7 +67,7 @@ def test_sharded_bench_path_over_the_real_rccl_backend_with_a_world_of_one(tmp_p
     env = dict(os.environ)
     env.update({"MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29547", "RANK": "0", "WORLD_SIZE": "1", "LOCAL_RANK": "0", "OTTI_FORCE_DIST": "1", "OTTI_FORCE_SHARD": "1"})
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--log2-constraints", "16", "--sweep", "14", "--in-flight", "-1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "3", "--warmup", "1", "--log2-constraints", "16", "--sweep", "14", "--in-flight", "-1",
            "--no-e2e", "--no-snark"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]

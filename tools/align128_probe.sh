@@ -2,7 +2,7 @@
 # -DOTTI_TABLE_ALIGN128 into _exp128/, see tools/README.md) and bench.py's timed region (20 proofs) runs alternately on both.
 # usage on the GPU box, from the repository root: bash tools/align128_probe.sh
 set -e
-F="--no-snark --no-e2e --no-sweep --in-flight -1 --no-cpu-baseline"
+F="--full --no-snark --no-e2e --no-sweep --in-flight -1 --no-cpu-baseline"
 cp otti_amd/libottispartan.so /tmp/lib96.so
 for rep in 1 2 3; do
   for v in 96 128; do

@@ -1,4 +1,4 @@
-"""Short summary of a bench.py line (file argument or stdin)."""
+"""Short summary of a `bench.py --full` line (file argument or stdin)."""
 import json, sys
 d = json.loads((open(sys.argv[1]) if len(sys.argv) > 1 else sys.stdin).read().strip().splitlines()[-1])
 r = d["roofline"]

@@ -1,5 +1,5 @@
 # the six-proofs-in-flight leg of bench.py: commitment MSMs on the CU-masked stream (default) or not, helper threads per prover, proofs in flight
-F="--steps 20 --warmup 1 --no-snark --no-sweep --no-e2e --no-cpu-baseline"
+F="--full --steps 20 --warmup 1 --no-snark --no-sweep --no-e2e --no-cpu-baseline"
 run() { # label, env assignment(s), in-flight count
   L=$(env $2 python bench.py $F --in-flight $3 2>/dev/null | tail -1)
   echo "$1 (in flight $3): $(echo "$L" | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('single', d['ms_per_step'], 'ms; in_flight', round(d['in_flight']['value']/1e6,1), 'M/s, latency', d['in_flight']['latency_ms_per_proof'])")"

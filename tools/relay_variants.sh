@@ -5,5 +5,5 @@
 for v in "OTTI_RELAY=1" "OTTI_RELAY=0" "OTTI_RELAY=1" "OTTI_RELAY=0"; do
   echo "=== $v"
   env $v OTTI_TRACE=1 python tools/snark_probe.py 20 4 2>&1 | grep "  prove\|pcbatch\|rror" | tail -3 | cut -c1-330
-  env $v python bench.py --no-snark --no-sweep --no-e2e --in-flight -1 --no-cpu-baseline 2>/dev/null | python tools/benchsum.py | head -1
+  env $v python bench.py --full --no-snark --no-sweep --no-e2e --in-flight -1 --no-cpu-baseline 2>/dev/null | python tools/benchsum.py | head -1
 done
