@@ -158,6 +158,15 @@ int32_t otti_device_count(void);
    pseudo-random inputs.  0 = consistent.  Needs no GPU; the prover itself only runs on one, so this is how the CPU test suite
    reaches that code. */
 int32_t otti_host_selftest(uint32_t iterations);
+/* The host's sum of a small MSM's chunk results, as the prover adds the per-workgroup mails of k_msm_small, without a GPU.
+ * otti_host_point_from_uniform: a point from 64 uniform bytes (extended coordinates X, Y, Z, T: 4 x 32 bytes little-endian).
+ * otti_host_point_sum: the compressed sum of n extended points.  path 0: the generic code; 1: as mails (cached form, number and tag) summed
+ * in `parts` ranges with AVX-512 IFMA where the CPU has it; 2: the same with the scalar five-limb additions; 3: as 1 with the last mail
+ * left over from an earlier launch (returns OTTI_ERR_INTERNAL: the sum gives up instead of taking it).
+ * otti_host_point_sum_bench: nanoseconds per mail summed, out[0] IFMA (0 without it), out[1] scalar. */
+int32_t otti_host_point_from_uniform(const uint8_t b64[64], uint8_t out128[128]);
+int32_t otti_host_point_sum(const uint8_t *pts128, size_t n, int32_t path, uint32_t parts, uint8_t out32[32]);
+int32_t otti_host_point_sum_bench(uint32_t n, uint32_t reps, double out[2]);
 /* Measurement aid: nanoseconds per operation of the host primitives on the provers' sequential path, on the calling machine:
  * [0] fixed-base scalar multiplication (8-bit windows), [1] ristretto compression, [2] Keccak-f[1600], [3] transcript append of a point
  * + challenge scalar, [4] GF(l) multiplication, [5] GF(l) inversion, [6] hand-off of an empty task to a helper thread and back,

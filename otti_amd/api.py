@@ -64,6 +64,9 @@ _sig("otti_buf_free", None, _vp)
 _sig("otti_device_count", _i32)
 _sig("otti_host_selftest", _i32, ctypes.c_uint32)
 _sig("otti_host_microbench", _i32, ctypes.POINTER(ctypes.c_double))
+_sig("otti_host_point_from_uniform", _i32, _vp, _vp)
+_sig("otti_host_point_sum", _i32, _vp, _sz, _i32, ctypes.c_uint32, _vp)
+_sig("otti_host_point_sum_bench", _i32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_double))
 _sig("otti_host_tail_bench", _i32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_double))
 _sig("otti_instance_new", _i32, _u64, _u64, _u64, _vp, _sz, _vp, _sz, _vp, _sz, ctypes.POINTER(_vp))
 _sig("otti_instance_free", None, _vp)
@@ -195,6 +198,30 @@ def device_count():
 def host_selftest(iterations=200):
     """host-side fast paths of the prover (five-limb field, fixed-base tables) against the generic code; raises on a mismatch"""
     _check(lib.otti_host_selftest(iterations))
+
+
+def host_point_from_uniform(b64):
+    """a point (extended X, Y, Z, T: 128 bytes) from 64 uniform bytes"""
+    assert len(b64) == 64
+    out = ctypes.create_string_buffer(128)
+    _check(lib.otti_host_point_from_uniform(bytes(b64), out))
+    return out.raw
+
+
+def host_point_sum(pts128, path, parts=1):
+    """compressed sum of extended points (concatenated 128-byte records): path 0 generic code, 1 the prover's chunk-mail sum (IFMA where
+    available), 2 the same in the scalar form, 3 as 1 with a stale last mail (raises)"""
+    n = len(pts128) // 128
+    out = ctypes.create_string_buffer(32)
+    _check(lib.otti_host_point_sum(bytes(pts128), n, path, parts, out))
+    return out.raw
+
+
+def host_point_sum_bench(n=52, reps=2000):
+    """nanoseconds per chunk mail summed on the host: (IFMA or 0, scalar)"""
+    out = (ctypes.c_double * 2)()
+    _check(lib.otti_host_point_sum_bench(n, reps, out))
+    return out[0], out[1]
 
 
 HOST_OPS = ("fixed_base_mul", "compress", "keccak_f1600", "append_point+challenge", "fr_mul", "fr_inv", "helper_thread_handoff",

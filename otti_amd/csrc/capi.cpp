@@ -3,6 +3,7 @@
 #include "shard.h"
 #include "snark.h"
 #include "hosttail.h"
+#include "hostifma.h"
 #include <array>
 #include <atomic>
 #include <chrono>
@@ -181,6 +182,70 @@ int32_t otti_host_tail_bench(uint32_t np, uint32_t nd, uint64_t T, uint32_t thre
         if (!out) throw Error(OTTI_ERR_BAD_ARG, "null out pointer");
         if (np > 12 || nd > 12 || T < 2 || T > 4096 || (T & (T - 1))) throw Error(OTTI_ERR_BAD_ARG, "host tail bench: at most 12 + 12 instances, tables of 2 .. 4096 elements");
         hosttail_bench((int)np, (int)nd, (size_t)T, (int)threads, (int)reps, out);
+        return OTTI_OK;
+    });
+}
+// ---- the host's sum of a small MSM's chunk mails (device.h MsmMail, DevCtx::msm_host_sum), reachable without a GPU
+int32_t otti_host_point_from_uniform(const uint8_t b64[64], uint8_t out128[128]) {
+    return guarded([&] {
+        if (!b64 || !out128) throw Error(OTTI_ERR_BAD_ARG, "null pointer");
+        const Pt p = pt_from_uniform_bytes(b64);
+        memcpy(out128, &p, 128);
+        return OTTI_OK;
+    });
+}
+// the mails the device would write for these extended points (cached form, any representatives < 2^256), number `seq` and its tags
+static std::vector<MsmMail> mails_for(const uint8_t *pts128, size_t n, unsigned long long seq) {
+    std::vector<MsmMail> m(n);
+    for (size_t i = 0; i < n; i++) {
+        Pt p; memcpy(&p, pts128 + 128 * i, 128);
+        memset(&m[i], 0, sizeof(MsmMail));
+        m[i].v[0] = fp_sub(p.Y, p.X); m[i].v[1] = fp_add(p.Y, p.X); m[i].v[2] = fp_mul(p.T, fp_2D()); m[i].v[3] = fp_add(p.Z, p.Z);
+        m[i].seq = seq; m[i].tag = msm_mail_tag(seq, m[i].v);
+    }
+    return m;
+}
+int32_t otti_host_point_sum(const uint8_t *pts128, size_t n, int32_t path, uint32_t parts, uint8_t out32[32]) {
+    return guarded([&] {
+        if ((!pts128 && n) || !out32 || n > 4096 || parts < 1 || parts > 64) throw Error(OTTI_ERR_BAD_ARG, "host point sum: bad arguments");
+        if (path == 0) {                                               // the generic 4 x u64 code of point.h
+            Pt acc = pt_identity();
+            for (size_t i = 0; i < n; i++) { Pt p; memcpy(&p, pts128 + 128 * i, 128); acc = pt_add(acc, p); }
+            pt_encode_ref(out32, acc);
+            return OTTI_OK;
+        }
+        if (path != 1 && path != 2 && path != 3) throw Error(OTTI_ERR_BAD_ARG, "host point sum: path is 0 (generic), 1 (mails, IFMA where available), 2 (mails, scalar), 3 (1 with a stale last mail)");
+        const unsigned long long seq = 0x1234567ull;
+        std::vector<MsmMail> m = mails_for(pts128, n, seq);
+        if (path == 3 && n) m[n - 1].seq = seq - 2;                  // left over from the launch before last on this region
+        // as the prover splits a row: `parts` consecutive ranges, each summed from the identity, then added up
+        PtFe acc = ptfe_identity();
+        for (uint32_t k = 0; k < parts; k++) {
+            const int i0 = (int)(n * k / parts), i1 = (int)(n * (k + 1) / parts);
+            PtFe part = ptfe_identity();
+            if (!msm_mail_sum(m.data(), i0, i1, seq, part, 1000u, path != 2)) return OTTI_ERR_INTERNAL;
+            host_point_add(acc, part, path != 2);
+        }
+        pt_encode_ref(out32, ptfe_to(acc));
+        return OTTI_OK;
+    });
+}
+// nanoseconds per mail of msm_mail_sum over n valid mails in one range: out[0] AVX-512 IFMA (0 without it), out[1] the scalar form
+int32_t otti_host_point_sum_bench(uint32_t n, uint32_t reps, double out[2]) {
+    return guarded([&] {
+        if (!out || n < 1 || n > 4096 || reps < 1) throw Error(OTTI_ERR_BAD_ARG, "host point sum bench: bad arguments");
+        std::vector<uint8_t> pts(128 * (size_t)n);
+        for (uint32_t i = 0; i < n; i++) { uint8_t w[64]; for (int k = 0; k < 64; k++) w[k] = (uint8_t)(i * 131 + k * 7 + 1); const Pt p = pt_from_uniform_bytes(w); memcpy(&pts[128 * (size_t)i], &p, 128); }
+        const std::vector<MsmMail> m = mails_for(pts.data(), n, 5);
+        for (int path = 0; path < 2; path++) {
+            out[path] = 0;
+            if (path == 0 && !host_ifma_available()) continue;
+            PtFe acc = ptfe_identity();
+            (void)msm_mail_sum(m.data(), 0, (int)n, 5, acc, 0u, path == 0);
+            const auto t0 = std::chrono::steady_clock::now();
+            for (uint32_t r = 0; r < reps; r++) { acc = ptfe_identity(); (void)msm_mail_sum(m.data(), 0, (int)n, 5, acc, 0u, path == 0); }
+            out[path] = std::chrono::duration<double, std::nano>(std::chrono::steady_clock::now() - t0).count() / ((double)reps * n);
+        }
         return OTTI_OK;
     });
 }

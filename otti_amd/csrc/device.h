@@ -93,6 +93,22 @@ constexpr size_t kGoCopyStride = 4096;
 // first half is covered by the tag (a fenced mail leaves an older tag behind, whose number does not fit) and must be checked.
 constexpr unsigned long long kLineMark = 0x5a5a5a5aull;
 HD unsigned long long line_tag(unsigned long long seq, const Fr *s3) { return (go_tag(seq, s3, 3) & ~0xffffffffull) | ((seq ^ kLineMark) & 0xffffffffull); }
+// Small fixed-base MSMs whose row sums go to the host (k_msm_small, rows <= 2): every workgroup mails its chunk's sum, in cached form
+// (Y - X, Y + X, 2d T, 2 Z), to a line pair of its own in pinned host memory, written by ONE store instruction (nine lanes x 16 bytes) with
+// no fence; the host adds the chunk sums of a row as they arrive (DevCtx::wait_points).  The number and the tag in the second line make
+// the pair self-validating: tag = go_tag(seq, v, 4), so a pair that is not whole yet, or is left over from an earlier launch, does not fit.
+struct MsmMail { Fp v[4]; unsigned long long seq, tag, pad[14]; };
+static_assert(sizeof(MsmMail) == 256 && offsetof(MsmMail, seq) == 128, "one mail = the cached point in one line, (number, tag) at the start of the next");
+constexpr size_t kMsmMailCap = 512;                          // mails per launch (rows * chunks of a fused launch)
+constexpr int kMsmMailRegions = 4;                           // launches whose mails can be waiting at once (round k read while k + 1 is queued, armed)
+HD unsigned long long msm_mail_tag(unsigned long long seq, const Fp *v4) { return go_tag(seq, reinterpret_cast<const Fr *>(v4), 4); }
+struct PtFe;
+// mails [i0, i1) of m summed into acc (hostifma.h host_sum_cached) once each carries number `want` and a fitting tag; a mail that has not
+// come after max_spins polls (0: no limit) makes it return false with acc holding the sum of those before it
+bool msm_mail_sum(const MsmMail *m, int i0, int i1, unsigned long long want, PtFe &acc, unsigned max_spins, bool allow_ifma);
+// whether mails [0, n) all carry number `want` and a fitting tag (no waiting, no arithmetic)
+bool msm_mails_whole(const MsmMail *m, int n, unsigned long long want);
+struct MsmPending { unsigned long long seq = 0, order = 0; int region = 0; uint32_t rows = 0, nchunks = 0; };
 struct Armed { GoBox *host; GoBox *dev; unsigned long long want, deadline; int relay = 1, pollers = 1; };   // relay 0: the copy's number is polled alone and the values loaded after it (OTTI_RELAY=0; A/B)   // want == 0: not armed (values come as kernel arguments); deadline in 100 MHz ticks
 constexpr unsigned long long kArmDeadlineTicks = 3000000000ull;   // 30 s of s_memrealtime: longer than any host stall the prover's own 20 s result wait tolerates
 constexpr size_t kArmMaxLen = 65536;                         // sum-check tables up to this length fold in <= 64 workgroups: only those launches are armed
@@ -144,6 +160,19 @@ struct DevCtx {
     void wait_points(unsigned long long ticket);              // results of a dev_msm_rows launch: flag wait when fused, else stream sync
     void encode_pending();
     Pt *d_pts_alias = nullptr; DevBuf<unsigned> d_counter2;
+    // chunk mails of the small MSMs summed on the host (MsmMail; OTTI_SMALL_HOST_SUM=0: the last workgroup sums them on the device instead)
+    MsmMail *h_msm_mail = nullptr, *d_msm_mail_alias = nullptr;
+    // Launches whose mails are still to be summed, oldest first (an armed round is queued before its predecessor is read).  Launch k mails
+    // to region k mod kMsmMailRegions; queueing one more than that drops the oldest entry, whose region it reuses.
+    MsmPending msm_pending[kMsmMailRegions]; int msm_pending_n = 0;
+    unsigned long long msm_launches = 0;                      // mailing launches queued on this context (picks the region)
+    unsigned long long msm_read[8] = {0}; int msm_read_next = 0;   // the latest tickets whose sums were read (a repeated wait_points returns at once)
+    unsigned long long msm_order = 0, h_pts_order = 0;      // small-MSM launches in queue order; the latest non-mailing one (its results replace h_pts / h_points)
+    bool small_host_sum() const;
+    void ensure_msm_mail();
+    void msm_queue(unsigned long long seq, uint32_t rows, uint32_t nchunks);   // a mailing launch was queued: its pending entry
+    MsmMail *msm_mail_region(int region) { return h_msm_mail + (size_t)region * kMsmMailCap; }
+    void msm_host_sum(const MsmPending &p);                  // waits for every mail of the launch and leaves its row sums in h_pts[0 .. rows)
     void ensure_points(size_t rows, size_t splits);
 };
 struct RowSumSlot { DevBuf<uint8_t> comp; DevBuf<Niels> pts; DevBuf<Fr> sc; DevBuf<Pt> out; DevBuf<unsigned> bad; bool busy = false; };

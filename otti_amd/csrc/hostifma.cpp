@@ -3,6 +3,7 @@
 // parallel carry pass), sums and differences are brought back under 2^51 + 2^7 by the same pass before they are multiplied.
 #include "hostifma.h"
 #include <stdlib.h>
+#include <functional>
 #if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)       // host pass only (hipcc also walks this file for gfx950)
 #include <immintrin.h>
 
@@ -99,14 +100,14 @@ OTTI_IFMA void vstore_point(PtFe &p, const V5 &a) {
     for (int k = 0; k < 5; k++) _mm256_store_si256((__m256i *)t[k], a.l[k]);
     for (int k = 0; k < 5; k++) { p.X.v[k] = t[k][0]; p.Y.v[k] = t[k][1]; p.T.v[k] = t[k][2]; p.Z.v[k] = t[k][3]; }
 }
-// add-2008-hwcd-3 mixed addition as two 4-way products (lanes X, Y, T, Z in and out)
-OTTI_IFMA V5 vmadd(const V5 &P, const Niels4 &q, bool negate) {
+// add-2008-hwcd-3 addition of a point given by its cached lanes Q = (y-x, y+x, 2dT, 2Z) — a Niels entry is one with 2 on the last
+// lane — as two 4-way products (lanes X, Y, T, Z in and out)
+OTTI_IFMA V5 vadd_cached(const V5 &P, const V5 &Q) {
     const __m256i z = _mm256_setzero_si256();
-    V5 A, B, Q;
+    V5 A, B;
     for (int k = 0; k < 5; k++) {
         A.l[k] = _mm256_permute4x64_epi64(P.l[k], 0xE5);                  // (Y, Y, T, Z)
         B.l[k] = _mm256_permute4x64_epi64(P.l[k], 0x00);                  // (X, X, X, X)
-        Q.l[k] = _mm256_load_si256((const __m256i *)q.v[k]);              // (y-x, y+x, 2dxy, 2)
     }
     const V5 Bn = vneg2p(B);
     V5 U;
@@ -115,11 +116,6 @@ OTTI_IFMA V5 vmadd(const V5 &P, const Niels4 &q, bool negate) {
         U.l[k] = _mm256_add_epi64(A.l[k], t);                             // (Y - X, Y + X, T, Z)
     }
     U = vreduce(U);
-    if (negate) {                                                         // -Q = (y+x, y-x, -2dxy, 2)
-        V5 S; for (int k = 0; k < 5; k++) S.l[k] = _mm256_permute4x64_epi64(Q.l[k], 0xE1);
-        const V5 N = vneg2p(S);
-        for (int k = 0; k < 5; k++) Q.l[k] = _mm256_blend_epi32(S.l[k], N.l[k], 0x30);
-    }
     const V5 V = vmul(U, Q);                                              // (A, B, C, D)
     V5 S1, S2;
     for (int k = 0; k < 5; k++) { S1.l[k] = _mm256_permute4x64_epi64(V.l[k], 0xDD); S2.l[k] = _mm256_permute4x64_epi64(V.l[k], 0x88); }   // (B, D, B, D), (A, C, A, C)
@@ -130,6 +126,17 @@ OTTI_IFMA V5 vmadd(const V5 &P, const Niels4 &q, bool negate) {
         M2.l[k] = _mm256_blend_epi32(_mm256_permute4x64_epi64(sum.l[k], 0xE0), _mm256_permute4x64_epi64(diff.l[k], 0x01), 0x03);   // (F, H, H, G)
     }
     return vmul(vreduce(M1), vreduce(M2));                                // (E F, G H, E H, F G) = (X3, Y3, T3, Z3)
+}
+// mixed addition of a table entry (y-x, y+x, 2dxy, 2), negated on request
+OTTI_IFMA V5 vmadd(const V5 &P, const Niels4 &q, bool negate) {
+    V5 Q;
+    for (int k = 0; k < 5; k++) Q.l[k] = _mm256_load_si256((const __m256i *)q.v[k]);
+    if (negate) {                                                         // -Q = (y+x, y-x, -2dxy, 2)
+        V5 S; for (int k = 0; k < 5; k++) S.l[k] = _mm256_permute4x64_epi64(Q.l[k], 0xE1);
+        const V5 N = vneg2p(S);
+        for (int k = 0; k < 5; k++) Q.l[k] = _mm256_blend_epi32(S.l[k], N.l[k], 0x30);
+    }
+    return vadd_cached(P, Q);
 }
 // 4p - b per limb (b below 2^53 - 76)
 OTTI_IFMA V5 vneg4p(const V5 &b) {
@@ -173,6 +180,55 @@ OTTI_IFMA V5 videntity() {
     return r;
 }
 }  // namespace
+
+// cached lanes (y-x, y+x, 2dT, 2Z) of four loosely reduced Fp in the device's order (Y - X, Y + X, 2d T, 2 Z)
+static void cached_fe_from_fp(CachedFe &c, const Fp *v4) {
+    c.yminusx = fe_from_fp(v4[0]); c.yplusx = fe_from_fp(v4[1]); c.t2d = fe_from_fp(v4[2]); c.z2 = fe_from_fp(v4[3]);
+    canon(c.yminusx); canon(c.yplusx); canon(c.t2d); canon(c.z2);
+}
+OTTI_IFMA_FN static int ifma_sum_cached(PtFe &acc, int n, const std::function<const Fp *(int)> &next) {
+    V5 P = vload_point(acc);
+    int i = 0;
+    for (; i < n; i++) {
+        const Fp *v4 = next(i);
+        if (!v4) break;
+        CachedFe c; cached_fe_from_fp(c, v4);
+        V5 Q;
+        for (int k = 0; k < 5; k++) Q.l[k] = _mm256_set_epi64x((long long)c.z2.v[k], (long long)c.t2d.v[k], (long long)c.yplusx.v[k], (long long)c.yminusx.v[k]);
+        P = vadd_cached(P, Q);
+    }
+    vstore_point(acc, P);
+    return i;
+}
+int host_sum_cached(PtFe &acc, int n, const std::function<const Fp *(int)> &next, bool allow_ifma) {
+    if (allow_ifma && host_ifma_available()) return ifma_sum_cached(acc, n, next);
+    int i = 0;
+    for (; i < n; i++) {
+        const Fp *v4 = next(i);
+        if (!v4) break;
+        CachedFe c; cached_fe_from_fp(c, v4);
+        ptfe_add_cached(acc, c, false);
+    }
+    return i;
+}
+// p += q: the cached lanes of q (Y - X, Y + X, T, Z) x (1, 1, 2d, 2) in one 4-way product, then the addition's two
+OTTI_IFMA_FN void ifma_add(PtFe &p, const PtFe &q) {
+    static const Fe d2 = fe_from_fp(fp_2D());
+    const V5 Qp = vload_point(q);                                        // lanes X, Y, T, Z
+    V5 U, K;
+    const V5 Qn = vneg2p(Qp);
+    for (int k = 0; k < 5; k++) {
+        const __m256i x = _mm256_permute4x64_epi64(Qp.l[k], 0x00), xn = _mm256_permute4x64_epi64(Qn.l[k], 0x00);
+        const __m256i y = _mm256_permute4x64_epi64(Qp.l[k], 0xE5);                      // (Y, Y, T, Z)
+        const __m256i t = _mm256_blend_epi32(_mm256_blend_epi32(_mm256_setzero_si256(), xn, 0x03), x, 0x0C);   // (2p - X, X, 0, 0)
+        U.l[k] = _mm256_add_epi64(y, t);
+        K.l[k] = _mm256_set_epi64x(k == 0 ? 2 : 0, (long long)d2.v[k], k == 0 ? 1 : 0, k == 0 ? 1 : 0);
+    }
+    vstore_point(p, vadd_cached(vload_point(p), vmul(vreduce(U), K)));
+}
+void host_point_add(PtFe &p, const PtFe &q, bool allow_ifma) {
+    if (allow_ifma && host_ifma_available()) ifma_add(p, q); else ptfe_add(p, q);
+}
 
 OTTI_IFMA_FN void ifma_dbl_n(PtFe &p, int n) { V5 P = vload_point(p); for (int i = 0; i < n; i++) P = vdbl(P); vstore_point(p, P); }
 

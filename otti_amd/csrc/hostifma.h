@@ -6,6 +6,7 @@
 // else in the library is built for x86-64-v3.
 #pragma once
 #include "hostfast.h"
+#include <functional>
 
 namespace otti {
 
@@ -27,5 +28,14 @@ void ifma_dbl_n(PtFe &p, int n);                             // p = 2^n p
 // Straus: acc = sum_i s_i P_i, where tabs[8 i + m - 1] = m P_i (m = 1 .. 8, cached form) and digs[i * nwin + w] is signed radix-16
 // digit w of s_i (|digit| <= 8); four doublings per window, windows from nwin - 1 down to 0
 void ifma_straus(PtFe &acc, const Niels4 *tabs, int ntabs, const int *digs, int nwin);
+
+// ---- the chunk sums of the small fixed-base MSMs, added on the host (DevCtx::msm_host_sum)
+// acc += the points given in cached form (Y - X, Y + X, 2d T, 2 Z: four loosely reduced Fp each, the layout k_msm_small mails).
+// next(i) returns point i's coordinates (read out and validated by the caller) or nullptr to stop; returns how many were added.
+// AVX-512 IFMA where available (two 4-way products per point), the five-limb scalar addition otherwise (or when allow_ifma is false).
+int host_sum_cached(PtFe &acc, int n, const std::function<const Fp *(int)> &next, bool allow_ifma = true);
+// p += q, both extended (unified addition; IFMA: q's cached lanes in one 4-way product, then the two of the addition; else ptfe_add)
+void host_point_add(PtFe &p, const PtFe &q, bool allow_ifma = true);
+void ifma_add(PtFe &p, const PtFe &q);
 
 }  // namespace otti

@@ -14,6 +14,7 @@
 //   k_bullet_step        K10 nizk/bullet.rs BulletReductionProof::prove scalar bookkeeping
 #include "kernels_common.h"
 #include "snark_dev.h"
+#include "hostifma.h"
 #include <atomic>
 
 namespace otti {
@@ -239,6 +240,7 @@ void DevCtx::go_abort() {
     __atomic_store_n(&h_go->timed_out, 0ull, __ATOMIC_RELEASE);
     __atomic_store_n(&h_go->seq, go_published, __ATOMIC_RELEASE);
     reset_arrival_counters();                                // the context goes back to the pool clean
+    msm_pending_n = 0;                                       // launches released without running mail nothing
 }
 // An armed grid that was released by an abort or a deadline returns before its arrival count is complete, and a launch that was cut
 // short for any other reason may have counted in part: the next launch on this context must not inherit that.  Stream idle.
@@ -367,13 +369,149 @@ void DevCtx::wait_tail_sums(int n_inst, int W, unsigned long long want, Fr *sums
     wait_tail(n, want);                                       // (throws if the launch gave up or never answers)
     tail_sum_range(h_tail, 0, n, W, want, sums, false);
 }
+// ---- the small MSMs' chunk mails (device.h MsmMail), summed on the host
+bool DevCtx::small_host_sum() const {
+    static const bool env_on = [] { const char *e = getenv("OTTI_SMALL_HOST_SUM"); return !(e && e[0] == '0'); }();
+    return env_on && host_coherent;
+}
+void DevCtx::ensure_msm_mail() {
+    if (h_msm_mail) return;
+    mail_alloc(*this, (void **)&h_msm_mail, (size_t)kMsmMailRegions * kMsmMailCap * sizeof(MsmMail));
+    memset(h_msm_mail, 0, (size_t)kMsmMailRegions * kMsmMailCap * sizeof(MsmMail));
+    OTTI_HIP(hipHostGetDevicePointer((void **)&d_msm_mail_alias, h_msm_mail, 0));
+}
+void DevCtx::msm_queue(unsigned long long seq, uint32_t rows, uint32_t nchunks) {
+    if (msm_pending_n == kMsmMailRegions) {                  // the launch just queued mails over the oldest entry's region: that one can no longer be read
+        for (int i = 1; i < kMsmMailRegions; i++) msm_pending[i - 1] = msm_pending[i];
+        msm_pending_n--;
+    }
+    MsmPending &p = msm_pending[msm_pending_n++];
+    p.seq = seq; p.order = ++msm_order; p.region = (int)(msm_launches++ % kMsmMailRegions); p.rows = rows; p.nchunks = nchunks;
+}
+// the tag test of msm_mail_sum without waiting or adding (an idle stream: what has not come will not)
+static bool msm_mail_ok(const MsmMail *line, unsigned long long want) {
+    const unsigned long long s = __atomic_load_n(&line->seq, __ATOMIC_ACQUIRE), tag = __atomic_load_n(&line->tag, __ATOMIC_ACQUIRE);
+    if (s != want) return false;
+    Fp v[4];
+    for (int c = 0; c < 4; c++) v[c] = line->v[c];
+    return msm_mail_tag(s, v) == tag;
+}
+bool msm_mails_whole(const MsmMail *m, int n, unsigned long long want) {
+    for (int i = 0; i < n; i++) if (!msm_mail_ok(m + i, want)) return false;
+    return true;
+}
+// mails [i0, i1) of one row: wait for each (spins > max_spins: give up and return false; 0 = no limit), check its tag, add it to acc
+bool msm_mail_sum(const MsmMail *m, int i0, int i1, unsigned long long want, PtFe &acc, unsigned max_spins, bool allow_ifma) {
+    bool ok = true;
+    Fp v[4];
+    auto next = [&](int k) -> const Fp * {
+        const MsmMail *line = m + i0 + k;
+#if defined(__x86_64__)
+        if (i0 + k + 4 < i1) { _mm_prefetch((const char *)(line + 4), _MM_HINT_T0); _mm_prefetch((const char *)(line + 4) + 128, _MM_HINT_T0); }
+#endif
+        // the pair came in one store instruction but as two lines nothing orders: read, check the tag, read again until it fits
+        for (unsigned spins = 0;; spins++) {
+            const unsigned long long s = __atomic_load_n(&line->seq, __ATOMIC_ACQUIRE), tag = __atomic_load_n(&line->tag, __ATOMIC_ACQUIRE);
+            if (s == want) {
+                for (int c = 0; c < 4; c++) v[c] = line->v[c];
+                if (msm_mail_tag(s, v) == tag) return v;
+            }
+            if (max_spins && spins > max_spins) { ok = false; return nullptr; }
+#if defined(__x86_64__)
+            _mm_pause();
+#endif
+        }
+    };
+    host_sum_cached(acc, i1 - i0, next, allow_ifma);
+    return ok;
+}
+// Every mail of the launch, summed per row.  A row's chunks are split between the prover thread and its helpers (pool.h: pinned next to
+// it), rows side by side; a helper spins a bounded time only — if one gives up, this thread waits for the launch with wait_ticket's failure
+// handling (an armed launch that gave up, a deadline) and sums everything itself.
+void DevCtx::msm_host_sum(const MsmPending &p) {
+    const MsmMail *m = msm_mail_region(p.region);
+    const int rows = (int)p.rows, nch = (int)p.nchunks;
+    SpinPool &pool = SpinPool::get();
+    // >= 8 mails per thread (a hand-over costs ~50 ns, an addition ~60), at most kMaxSumThreads threads whatever OTTI_HOST_THREADS gives the pool
+    constexpr int kMaxSumThreads = 8;
+    const int per_row = std::max(1, std::min(std::min((pool.workers() + 1) / rows, nch / 8), kMaxSumThreads / rows));
+    const int nt = rows * per_row;
+    PtFe part[kMaxSumThreads];
+    bool ok[kMaxSumThreads];
+    if (nt > 1 && nt <= kMaxSumThreads) {
+        std::function<void()> tasks[kMaxSumThreads];
+        for (int t = 0; t < nt; t++) {
+            const int r = t / per_row, k = t % per_row, i0 = r * nch + nch * k / per_row, i1 = r * nch + nch * (k + 1) / per_row;
+            tasks[t] = [m, i0, i1, &p, &part, &ok, t] { part[t] = ptfe_identity(); ok[t] = msm_mail_sum(m, i0, i1, p.seq, part[t], 2000000u, true); };
+        }
+        pool.parallel(tasks, nt);
+        bool all = true;
+        for (int t = 0; t < nt; t++) all = all && ok[t];
+        if (all) {
+            for (int r = 0; r < rows; r++) {
+                PtFe acc = part[r * per_row];
+                for (int k = 1; k < per_row; k++) host_point_add(acc, part[r * per_row + k]);
+                h_pts[r] = ptfe_to(acc);
+            }
+            return;
+        }
+    }
+    // one thread, unbounded but with the failure handling of wait_ticket
+    const auto t0 = std::chrono::steady_clock::now();
+    for (int r = 0; r < rows; r++) {
+        PtFe acc = ptfe_identity();
+        int done = r * nch;
+        for (unsigned spins = 0; done < (r + 1) * nch; spins++) {
+            PtFe one = ptfe_identity();
+            if (msm_mail_sum(m, done, done + 1, p.seq, one, 1000u, true)) { host_point_add(acc, one); done++; spins = 0; continue; }
+            if ((spins & 0x3f) == 0x3f && __atomic_load_n(&h_go->timed_out, __ATOMIC_ACQUIRE)) {
+                go_abort();
+                throw Error(OTTI_ERR_INTERNAL, "an armed launch gave up waiting for the host (the proving thread was stalled beyond the launch's deadline)");
+            }
+            if ((spins & 0x3ff) == 0x3ff && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) {
+                if (go_published < go_issued) go_abort(); else OTTI_HIP(hipStreamSynchronize(stream));
+                if (!msm_mail_sum(m, done, done + 1, p.seq, one, 1000u, true)) throw Error(OTTI_ERR_INTERNAL, "a small MSM's chunk sums never arrived");
+                host_point_add(acc, one); done++; spins = 0;
+            }
+        }
+        h_pts[r] = ptfe_to(acc);
+    }
+}
 void DevCtx::wait_points(unsigned long long ticket) {
     if (!ticket) { sync(); return; }
+    for (int i = 0; i < msm_pending_n; i++)
+        if (msm_pending[i].seq == ticket) {
+            const MsmPending p = msm_pending[i];
+            for (int j = i + 1; j < msm_pending_n; j++) msm_pending[j - 1] = msm_pending[j];
+            msm_pending_n--;
+            msm_host_sum(p);
+            msm_read[msm_read_next++ & 7] = ticket;
+            pending_host_encode = p.rows;
+            encode_pending();
+            return;
+        }
+    if (small_host_sum()) {
+        // this context's small launches mail (the switch is per process): the ticket's sums were read already — then this returns at once,
+        // as a flag wait on a delivered launch does — or they are gone, and nothing will ever raise a flag for them
+        for (unsigned long long r : msm_read) if (r == ticket) { encode_pending(); return; }
+        throw Error(OTTI_ERR_INTERNAL, "a small MSM's chunk sums were overwritten or released before they were read");
+    }
     wait_ticket(ticket);
     encode_pending();
 }
 void DevCtx::sync() {
     OTTI_HIP(hipStreamSynchronize(stream));
+    if (msm_pending_n) {
+        // the stream is idle: the latest launch's mails are all in (unless it was an armed launch released without running: then nothing is);
+        // its row sums are what h_pts holds after a sync, unless a later launch of another kind left its own there
+        const MsmPending p = msm_pending[msm_pending_n - 1];
+        msm_pending_n = 0;
+        if (p.order > h_pts_order && msm_mails_whole(msm_mail_region(p.region), (int)(p.rows * p.nchunks), p.seq)) {
+            msm_host_sum(p);
+            msm_read[msm_read_next++ & 7] = p.seq;
+            pending_host_encode = p.rows;
+        }
+    }
     encode_pending();
 }
 void DevCtx::encode_pending() {

@@ -28,9 +28,10 @@ struct MsmArgs {
     const Fr *extra_s; uint32_t extra_base[8]; int n_extra;
     uint32_t K[9];                                                  // recoding constant (288 bits)
     Pt *partial;
-    // fused finish (rows <= 2, 1 < nchunks <= 128): the last workgroup to arrive sums every row's partials and mails the extended
-    // row sums to pinned host memory, then raises the host flag — no finish launch, no copy, no stream synchronise
-    int fuse; uint32_t rows; unsigned *counter; Pt *host_pts; unsigned long long *host_flag; unsigned long long seq;
+    // fuse = 1 (rows <= 2, OTTI_SMALL_HOST_SUM=0): the last workgroup to arrive sums every row's partials and mails the extended row
+    // sums to pinned host memory, then raises the host flag — no finish launch, no copy, no stream synchronise.
+    // fuse = 2 (rows <= 2, the default): every workgroup mails its chunk's sum to mail[row * nchunks + chunk] and the host adds them up
+    int fuse; uint32_t rows; unsigned *counter; Pt *host_pts; unsigned long long *host_flag; unsigned long long seq; MsmMail *mail;
     BulletArgs bul;
     Armed go;                                                       // armed bullet round: {u, u_inv, raw(u), raw(u_inv)} arrive through the GoBox
     unsigned long long *stamps;                                     // OTTI_MSM_STAMPS: s_memrealtime (100 MHz) at the phase boundaries of k_msm_small
@@ -181,8 +182,10 @@ template <int kKind> __global__ __launch_bounds__(kBlock) void k_msm_rows(MsmArg
 //   * every addition is quad-parallel (fp10.h): 4 lanes per point, 2-3 multiplication depths per addition instead of 7-9;
 //   * a workgroup (64 quads) takes a SHORT chunk (about two pairs per quad), so the tree starts almost at once; its six levels go
 //     through LDS with one barrier each (every level has its own slots);
-//   * rows of at most two: the last workgroup to arrive (agent-scope counter, sc1 hand-off) sums the chunk results the same way
-//     and mails the extended row sums to pinned host memory — no finish launch, no copy, no stream synchronise;
+//   * rows of at most two: every workgroup mails its chunk result (cached form, number and tag: MsmMail in device.h) to pinned host
+//     memory in one store instruction, and the host adds a row's chunk results up (DevCtx::msm_host_sum) — no second tree on the
+//     device behind an arrival counter, no finish launch, no copy, no stream synchronise.  (OTTI_SMALL_HOST_SUM=0: the last
+//     workgroup to arrive sums the chunk results with the same body and mails the row sums, the form this replaced);
 //   * a bullet round's c_L / c_R is not computed by one workgroup ahead of its MSM: every workgroup takes a slice of the dot product
 //     and adds (its slice) * Q as one more term — the sum over workgroups is c_L * Q; the folded state (a, b, s) for the next
 //     round is written after the workgroup has handed its point over, off the path to the host.
@@ -292,6 +295,45 @@ __global__ __launch_bounds__(kBlock) void k_msm_small(MsmArgs A) {
                 const int sft = top >> (step - n_op + 1);                                // top/2, .., 1, then 0 = hand the segment's sum over
                 const bool out_cached = sft == 0 && !pass && A.fuse;
                 if (sft == 0 && !out_cached) break;
+                if (sft == 0 && A.fuse == 2) {
+                    // the chunk's sum (quad 0) in cached form to the host: lanes 0..7 of wave 0 take 16 bytes each of the four coordinates,
+                    // lane 8 the number and the tag (XOR of the lanes' shares of go_tag), all nine in ONE store instruction, no fence
+                    if (wave == 0) {
+                        const Fp pk = f10_pack(q10_cached(ua, q, d2));
+                        const int src = (lane >> 1) & 3, hi = lane & 1;
+                        uint32_t w4[4];
+#pragma unroll
+                        for (int i = 0; i < 4; i++) {
+                            const uint32_t lo_w = (uint32_t)__shfl((int)pk.v[i], src), hi_w = (uint32_t)__shfl((int)pk.v[4 + i], src);
+                            w4[i] = hi ? hi_w : lo_w;
+                        }
+                        unsigned long long h = 0;
+                        if (lane < 8) {
+#pragma unroll
+                            for (int jj = 0; jj < 2; jj++) {
+                                const unsigned long long wd = (unsigned long long)w4[2 * jj] | ((unsigned long long)w4[2 * jj + 1] << 32);
+                                const int rot = ((4 * src + 2 * hi + jj) * 5 + 1) & 63;
+                                h ^= (wd << rot) | (wd >> ((64 - rot) & 63));
+                            }
+                        }
+#pragma unroll
+                        for (int off = 1; off < 8; off <<= 1) {
+                            const uint32_t hl = (uint32_t)__shfl_xor((int)(uint32_t)h, off), hh = (uint32_t)__shfl_xor((int)(uint32_t)(h >> 32), off);
+                            h ^= (unsigned long long)hl | ((unsigned long long)hh << 32);
+                        }
+                        const unsigned long long tag = (A.seq * 0x9e3779b97f4a7c15ull) ^ (((unsigned long long)(uint32_t)__shfl((int)(uint32_t)h, 0)) |
+                                                                                         ((unsigned long long)(uint32_t)__shfl((int)(uint32_t)(h >> 32), 0) << 32));
+                        if (lane < 9) {
+                            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+                            u32x4 v4;
+                            if (lane < 8) { v4[0] = w4[0]; v4[1] = w4[1]; v4[2] = w4[2]; v4[3] = w4[3]; }
+                            else { v4[0] = (uint32_t)A.seq; v4[1] = (uint32_t)(A.seq >> 32); v4[2] = (uint32_t)tag; v4[3] = (uint32_t)(tag >> 32); }
+                            char *dst = reinterpret_cast<char *>(A.mail + (size_t)row * A.nchunks + chunk_id) + 16 * lane;
+                            asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" :: "v"(dst), "v"(v4) : "memory");
+                        }
+                    }
+                    break;
+                }
                 F10 *const level = seg_tree + (size_t)((sft - 1) * (int)segs + (int)r * (sft - 1)) * 4;
                 if (sft ? ((int)idx >= sft && (int)idx < 2 * sft) : idx == 0) {
                     const F10 cv = q10_cached(ua, q, d2);
@@ -307,6 +349,7 @@ __global__ __launch_bounds__(kBlock) void k_msm_small(MsmArgs A) {
         if (pass == 0) {
             if (stamp0) A.stamps[3] = wall_clock64();
             if (!A.fuse) { if (qid == 0) reinterpret_cast<Fp *>(&A.partial[row * A.nchunks + chunk_id])[q] = f10_pack(acc); break; }
+            if (A.fuse == 2) break;                                                // mailed: the host sums the chunks
             last = arrive_and_check_last(A.counter, gridDim.x * gridDim.y);
             if (!last) break;
             if (A.stamps && threadIdx.x == 0) A.stamps[4] = wall_clock64();
@@ -433,10 +476,12 @@ static unsigned long long msm_launch(DevCtx &c, const DeviceGens &g, const Fr *d
     for (int w = 0; w < g.W; w++) { int bit = g.c - 1 + g.c * w; A.K[bit >> 5] |= 1u << (bit & 31); }
     c.ensure_points(rows, nchunks);
     A.partial = c.msm_partial.p;
-    A.fuse = (!bulk && mode == MSM_COMPRESSED && !addend && rows <= 2 && rows * nchunks <= 512) ? 1 : 0;
+    A.fuse = (!bulk && mode == MSM_COMPRESSED && !addend && rows <= 2 && rows * nchunks <= kMsmMailCap) ? 1 : 0;
+    if (A.fuse && c.small_host_sum()) { A.fuse = 2; c.ensure_msm_mail(); }
     if (bul) A.bul = *bul; else { memset(&A.bul, 0, sizeof A.bul); }
     A.go = Armed{nullptr, nullptr, 0};
     A.rows = (uint32_t)rows; A.counter = c.d_counter2.p; A.host_pts = c.d_pts_alias; A.host_flag = c.d_flag_alias; A.seq = A.fuse ? ++c.seq : 0;
+    A.mail = A.fuse == 2 ? c.d_msm_mail_alias + (size_t)(c.msm_launches % kMsmMailRegions) * kMsmMailCap : nullptr;
     dim3 grid((unsigned)nchunks, (unsigned)rows);
     // OTTI_MSM_STAMPS=1: phase stamps of every fused small launch on stderr (development aid; synchronises the stream)
     static const bool want_stamps = getenv("OTTI_MSM_STAMPS") != nullptr;
@@ -453,7 +498,18 @@ static unsigned long long msm_launch(DevCtx &c, const DeviceGens &g, const Fr *d
         else if (bulk) hipLaunchKernelGGL(k_msm_rows<MSM_BULK>, grid, kBlock, 0, c.stream, A);
         else hipLaunchKernelGGL(k_msm_small, grid, kBlock, 0, c.stream, A);
     }
-    if (A.stamps) {
+    if (A.fuse == 2) c.msm_queue(A.seq, (uint32_t)rows, (uint32_t)nchunks);      // the host sums the mails in wait_points(seq) / sync()
+    if (A.stamps && A.fuse == 2) {
+        OTTI_HIP(hipStreamSynchronize(c.stream));
+        const unsigned long long *t = h_stamps;
+        auto us = [&](int a, int b) { return t[b] >= t[a] ? (double)(t[b] - t[a]) * 0.01 : -1.0; };
+        const auto h0 = std::chrono::steady_clock::now();
+        c.msm_host_sum(c.msm_pending[c.msm_pending_n - 1]);
+        const double host_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - h0).count();
+        fprintf(stderr, "[otti] k_msm_small rows=%zu terms=%zu chunks=%zu bullet=%d host-sum: scalars %.2f | pairs %.2f | tree + mail %.2f | total %.2f us on the device; "
+                        "host sum of %zu mails (all in) %.2f us\n",
+                rows, n_dense + n_extra, nchunks, bul ? 1 : 0, us(0, 1), us(1, 2), us(2, 3), us(0, 3), rows * nchunks, host_us);
+    } else if (A.stamps) {
         OTTI_HIP(hipStreamSynchronize(c.stream));
         const unsigned long long *t = h_stamps;
         auto us = [&](int a, int b) { return t[b] >= t[a] ? (double)(t[b] - t[a]) * 0.01 : -1.0; };
@@ -461,6 +517,7 @@ static unsigned long long msm_launch(DevCtx &c, const DeviceGens &g, const Fr *d
                 rows, n_dense + n_extra, nchunks, bul ? 1 : 0, us(0, 1), us(1, 2), us(2, 3), us(3, 4), us(4, 5), us(5, 6), us(6, 7), us(0, 7));
     }
     if (A.fuse) { c.pending_host_encode = rows; return A.seq; }
+    c.h_pts_order = ++c.msm_order;                          // every branch below replaces what a mailing launch before it left for sync()
     // rows with a single chunk need no finish pass: their partial IS the row sum
     const Pt *finals = c.msm_partial.p;
     if (nchunks > 1) {
