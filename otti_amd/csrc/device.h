@@ -1,4 +1,5 @@
-// Device layer of the proving path: HBM-resident objects and the kernel launch functions (k_*.hip).
+// Device layer of the proving path: HBM-resident objects, the device context with its mailboxes and host waits (k_context.hip, waits.cpp;
+// the mail formats themselves: mail.h) and the kernel launch functions (k_*.hip).
 // Everything runs on one HIP stream owned by DevCtx; results that the Fiat-Shamir transcript needs come back through
 // a small pinned buffer.  No function here falls back to the host: without a gfx950 device they throw Error(OTTI_ERR_NO_DEVICE).
 #pragma once
@@ -6,7 +7,9 @@
 #include <vector>
 #include <functional>
 #include <cstddef>
+#include <chrono>
 #include "spartan.h"
+#include "mail.h"
 
 namespace otti {
 
@@ -72,36 +75,13 @@ struct Mailbox { Fr *partials; unsigned *counter; Fr *host_results; unsigned lon
 // again.  timed_out (written by the DEVICE) sits in a line of its own.
 struct alignas(64) GoBox { unsigned long long seq, tag, pad[2]; Fr v[4]; unsigned long long timed_out, pad2[3]; };
 static_assert(sizeof(GoBox) == 192 && offsetof(GoBox, v) == 32 && offsetof(GoBox, timed_out) == 160, "GoBox layout is read by hand-written loads");
-// the same function on both sides of the bus: every 64-bit word of the n values, rotated by its position, folded into the sequence number
-HD unsigned long long go_tag(unsigned long long seq, const Fr *v, int n) {
-    unsigned long long h = seq * 0x9e3779b97f4a7c15ull;
-    for (int k = 0; k < n; k++)
-        for (int j = 0; j < 4; j++) {
-            const unsigned long long w = (unsigned long long)v[k].v[2 * j] | ((unsigned long long)v[k].v[2 * j + 1] << 32);
-            const int rot = ((4 * k + j) * 5 + 1) & 63;
-            h ^= (w << rot) | (w >> ((64 - rot) & 63));
-        }
-    return h;
-}
 // The leader's copy for the other workgroups exists kGoCopies times, kGoCopyStride bytes apart (different memory channels): with every waiting
 // workgroup polling ONE line, 128 pollers kept a single HBM channel busy enough to double the latency of each poll.  Workgroup b polls copy b mod kGoCopies.
 constexpr int kGoCopies = 8;
 constexpr size_t kGoCopyStride = 4096;
-// The completion flag lives in result slot 3 — with slots 0..2 one 128-byte line: {Fr s[3]; u64 seq; u64 tag; u64 pad[2]}.  A launch whose K <= 3
-// totals go to slot 0 mails that line with ONE store instruction and no fence (Mailbox.line_mail; the persistent tail does the same, snark_dev.h):
-// number and tag travel in one 16-byte store; the low 32 bits of the tag are the number's xor kLineMark, which tells the host that the line's
-// first half is covered by the tag (a fenced mail leaves an older tag behind, whose number does not fit) and must be checked.
-constexpr unsigned long long kLineMark = 0x5a5a5a5aull;
-HD unsigned long long line_tag(unsigned long long seq, const Fr *s3) { return (go_tag(seq, s3, 3) & ~0xffffffffull) | ((seq ^ kLineMark) & 0xffffffffull); }
-// Small fixed-base MSMs whose row sums go to the host (k_msm_small, rows <= 2): every workgroup mails its chunk's sum, in cached form
-// (Y - X, Y + X, 2d T, 2 Z), to a line pair of its own in pinned host memory, written by ONE store instruction (nine lanes x 16 bytes) with
-// no fence; the host adds the chunk sums of a row as they arrive (DevCtx::wait_points).  The number and the tag in the second line make
-// the pair self-validating: tag = go_tag(seq, v, 4), so a pair that is not whole yet, or is left over from an earlier launch, does not fit.
-struct MsmMail { Fp v[4]; unsigned long long seq, tag, pad[14]; };
-static_assert(sizeof(MsmMail) == 256 && offsetof(MsmMail, seq) == 128, "one mail = the cached point in one line, (number, tag) at the start of the next");
+// ---- the small MSMs' chunk mails (mail.h MsmMail), summed on the host; OTTI_SMALL_HOST_SUM=0: the last workgroup sums them on the device instead
 constexpr size_t kMsmMailCap = 512;                          // mails per launch (rows * chunks of a fused launch)
 constexpr int kMsmMailRegions = 4;                           // launches whose mails can be waiting at once (round k read while k + 1 is queued, armed)
-HD unsigned long long msm_mail_tag(unsigned long long seq, const Fp *v4) { return go_tag(seq, reinterpret_cast<const Fr *>(v4), 4); }
 struct PtFe;
 // mails [i0, i1) of m summed into acc (hostifma.h host_sum_cached) once each carries number `want` and a fitting tag; a mail that has not
 // come after max_spins polls (0: no limit) makes it return false with acc holding the sum of those before it
@@ -109,6 +89,23 @@ bool msm_mail_sum(const MsmMail *m, int i0, int i1, unsigned long long want, PtF
 // whether mails [0, n) all carry number `want` and a fitting tag (no waiting, no arithmetic)
 bool msm_mails_whole(const MsmMail *m, int n, unsigned long long want);
 struct MsmPending { unsigned long long seq = 0, order = 0; int region = 0; uint32_t rows = 0, nchunks = 0; };
+struct DevCtx;
+struct MsmMailbox {
+    MsmMail *host = nullptr, *dev = nullptr;                  // pinned, kMsmMailRegions regions of kMsmMailCap mails; the device's address of the same
+    // Launches whose mails are still to be summed, oldest first (an armed round is queued before its predecessor is read).  Launch k mails
+    // to region k mod kMsmMailRegions; queueing one more than that drops the oldest entry, whose region it reuses.
+    MsmPending pending[kMsmMailRegions]; int pending_n = 0;
+    unsigned long long launches = 0;                          // mailing launches queued on this context (picks the region)
+    unsigned long long read[8] = {0}; int read_next = 0;      // the latest tickets whose sums were read (a repeated wait_points returns at once)
+    unsigned long long order = 0, h_pts_order = 0;            // small-MSM launches in queue order; the latest non-mailing one (its results replace h_pts / h_points)
+    bool host_sum(const DevCtx &c) const;                     // this process's small launches mail (the switch, and coherent host memory)
+    void ensure(DevCtx &c);
+    void queue(unsigned long long seq, uint32_t rows, uint32_t nchunks);   // a mailing launch was queued: its pending entry
+    MsmMail *region(int r) const { return host + (size_t)r * kMsmMailCap; }
+};
+// per-workgroup mail lines of the persistent sum-check tail (mail.h TailMail, snark_dev.h), pinned, and the device's address of the same
+struct TailMailbox { TailMail *host = nullptr, *dev = nullptr; void ensure(DevCtx &c); };
+struct WaitLimits;                                           // waits.cpp: cadence, time limit and failure handling of one host wait
 struct Armed { GoBox *host; GoBox *dev; unsigned long long want, deadline; int relay = 1, pollers = 1; };   // relay 0: the copy's number is polled alone and the values loaded after it (OTTI_RELAY=0; A/B)   // want == 0: not armed (values come as kernel arguments); deadline in 100 MHz ticks
 constexpr unsigned long long kArmDeadlineTicks = 3000000000ull;   // 30 s of s_memrealtime: longer than any host stall the prover's own 20 s result wait tolerates
 constexpr size_t kArmMaxLen = 65536;                         // sum-check tables up to this length fold in <= 64 workgroups: only those launches are armed
@@ -133,9 +130,11 @@ struct DevCtx {
     void reset_arrival_counters();                            // after an aborted or timed-out launch: a grid may have left them non-zero (stream must be idle)
     hipEvent_t ev_order = nullptr;                            // orders a caller's stream (otti_kd_*) against this context's own
     std::vector<struct RowSumSlot *> row_slots;               // the verifier's variable-base sums in flight on this context (prover.cpp), buffers kept across proofs
-    struct TailMail *h_tail = nullptr, *d_tail_alias = nullptr;   // per-workgroup mail lines of the persistent sum-check tail (snark_dev.h), pinned
-    void ensure_tail_mail();
-    void wait_tail(int n_groups, unsigned long long seq);     // spin until every line carries seq (same failure handling as wait_ticket)
+    TailMailbox tail_mail;
+    // ---- host waits on device mail (waits.cpp).  The one guarded spin: polls arrived() until it holds; while it does not, fails the way lim says
+    // (an armed launch that gave up; a time limit counted from t0, with release-or-drain) and ends in fail(), which throws
+    template <class Pred, class OnLimit> void spin_until(Pred arrived, const WaitLimits &lim, std::chrono::steady_clock::time_point t0, OnLimit fail);
+    void wait_tail(int n_groups, unsigned long long seq);     // spin until every line carries seq (throws TailTimeout at its own, short limit)
     void wait_tail_sums(int n_inst, int W, unsigned long long seq, Fr *sums);   // the same for a round's mails, summing the W partials of every instance as they arrive
     Armed arm_many(int count);                                // reserves `count` consecutive go() numbers for one persistent launch; .want = the first
     bool armed_ok() const;                                    // off under OTTI_ARMED=0, while kernel classes are being timed (a waiting kernel's duration includes the host), and
@@ -160,18 +159,7 @@ struct DevCtx {
     void wait_points(unsigned long long ticket);              // results of a dev_msm_rows launch: flag wait when fused, else stream sync
     void encode_pending();
     Pt *d_pts_alias = nullptr; DevBuf<unsigned> d_counter2;
-    // chunk mails of the small MSMs summed on the host (MsmMail; OTTI_SMALL_HOST_SUM=0: the last workgroup sums them on the device instead)
-    MsmMail *h_msm_mail = nullptr, *d_msm_mail_alias = nullptr;
-    // Launches whose mails are still to be summed, oldest first (an armed round is queued before its predecessor is read).  Launch k mails
-    // to region k mod kMsmMailRegions; queueing one more than that drops the oldest entry, whose region it reuses.
-    MsmPending msm_pending[kMsmMailRegions]; int msm_pending_n = 0;
-    unsigned long long msm_launches = 0;                      // mailing launches queued on this context (picks the region)
-    unsigned long long msm_read[8] = {0}; int msm_read_next = 0;   // the latest tickets whose sums were read (a repeated wait_points returns at once)
-    unsigned long long msm_order = 0, h_pts_order = 0;      // small-MSM launches in queue order; the latest non-mailing one (its results replace h_pts / h_points)
-    bool small_host_sum() const;
-    void ensure_msm_mail();
-    void msm_queue(unsigned long long seq, uint32_t rows, uint32_t nchunks);   // a mailing launch was queued: its pending entry
-    MsmMail *msm_mail_region(int region) { return h_msm_mail + (size_t)region * kMsmMailCap; }
+    MsmMailbox msm_mail;
     void msm_host_sum(const MsmPending &p);                  // waits for every mail of the launch and leaves its row sums in h_pts[0 .. rows)
     void ensure_points(size_t rows, size_t splits);
 };

@@ -1,5 +1,5 @@
-// gfx950 (MI355X, CDNA4) kernels of the Spartan NIZK proving path (this file: the device context, kernel timing, host waits;
-// kernels live in k_field.hip, k_sparse.hip, k_sumcheck.hip, k_msm.hip).  Wave64; 256 CUs in 8 XCDs; every kernel here is integer
+// gfx950 (MI355X, CDNA4) kernels of the Spartan NIZK proving path (this file: the device context — its pool, streams, mailbox memory,
+// armed-launch bookkeeping — and kernel timing; the host's waits on device mail are in waits.cpp; kernels live in k_field.hip, k_sparse.hip, k_sumcheck.hip, k_msm.hip).  Wave64; 256 CUs in 8 XCDs; every kernel here is integer
 // work on 256-bit field elements (8 x u32 limbs, v_mad_u64_u32 chains) — no MFMA applies.  Streaming kernels (K1-K7, K9)
 // move 32-byte elements with two 16-byte accesses per lane and are HBM-bound; the fixed-base MSM (K8) is integer-ALU-bound.
 //
@@ -14,7 +14,6 @@
 //   k_bullet_step        K10 nizk/bullet.rs BulletReductionProof::prove scalar bookkeeping
 #include "kernels_common.h"
 #include "snark_dev.h"
-#include "hostifma.h"
 #include <atomic>
 
 namespace otti {
@@ -87,7 +86,7 @@ DevCtx &DevCtx::get() {
     host_alloc((void **)&c->h_results, kResultSlots * sizeof(Fr));
     OTTI_HIP(hipHostGetDevicePointer((void **)&c->d_results_alias, c->h_results, 0));
     memset(c->h_results, 0, 4 * sizeof(Fr));
-    c->h_flag = reinterpret_cast<unsigned long long *>(&c->h_results[3]);         // slots 0..2 + the flag: one line (device.h, kLineMark)
+    c->h_flag = reinterpret_cast<unsigned long long *>(&c->h_results[3]);         // slots 0..2 + the flag: one line (mail.h RoundLine)
     c->d_flag_alias = reinterpret_cast<unsigned long long *>(&c->d_results_alias[3]);
     c->d_counter.alloc(1);
     OTTI_HIP(hipMemset(c->d_counter.p, 0, sizeof(unsigned)));
@@ -240,7 +239,7 @@ void DevCtx::go_abort() {
     __atomic_store_n(&h_go->timed_out, 0ull, __ATOMIC_RELEASE);
     __atomic_store_n(&h_go->seq, go_published, __ATOMIC_RELEASE);
     reset_arrival_counters();                                // the context goes back to the pool clean
-    msm_pending_n = 0;                                       // launches released without running mail nothing
+    msm_mail.pending_n = 0;                                  // launches released without running mail nothing
 }
 // An armed grid that was released by an abort or a deadline returns before its arrival count is complete, and a launch that was cut
 // short for any other reason may have counted in part: the next launch on this context must not inherit that.  Stream idle.
@@ -249,280 +248,22 @@ void DevCtx::reset_arrival_counters() {
     if (d_counter2.p) (void)hipMemsetAsync(d_counter2.p, 0, sizeof(unsigned), stream);
     (void)hipStreamSynchronize(stream);
 }
-void DevCtx::wait_ticket(unsigned long long ticket) {
-    volatile unsigned long long *f = h_flag;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned spins = 0;; spins++) {
-        if (*f >= ticket) {
-            // a line mail (device.h kLineMark): number and tag came in one 16-byte store, the sums' first half possibly not yet — read until the tag fits
-            if (*f == ticket && ((f[1] ^ ticket ^ kLineMark) & 0xffffffffull) == 0) {
-                for (unsigned tries = 0;; tries++) {
-                    Fr s3[3]; const unsigned long long tag = __atomic_load_n(&h_flag[1], __ATOMIC_ACQUIRE);
-                    for (int k = 0; k < 3; k++) s3[k] = h_results[k];
-                    if (line_tag(ticket, s3) == tag || *f != ticket) break;
-                    if (tries > 50000000u) throw Error(OTTI_ERR_INTERNAL, "a round's mailed line never became whole");
-#if defined(__x86_64__)
-                    _mm_pause();
-#endif
-                }
-            }
-            return;
-        }
-#if defined(__x86_64__)
-        _mm_pause();
-#endif
-        if ((spins & 0x3ff) == 0x3ff && __atomic_load_n(&h_go->timed_out, __ATOMIC_ACQUIRE)) {
-            // an armed launch gave up waiting for this thread (it was stopped for longer than the launch's deadline): its grid returned
-            // without touching anything, the launches queued behind it are released the same way, and the proof fails cleanly
-            go_abort();
-            throw Error(OTTI_ERR_INTERNAL, "an armed launch gave up waiting for the host (the proving thread was stalled beyond the launch's deadline)");
-        }
-        if ((spins & 0xffff) == 0xffff && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) {
-            if (go_published < go_issued) go_abort();         // release whatever is still armed, drain, clear the arrival counters
-            else { OTTI_HIP(hipStreamSynchronize(stream)); if (*f >= ticket) return; reset_arrival_counters(); }   // surfaces a device fault as an error instead of spinning forever
-            if (*f >= ticket) return;
-            throw Error(OTTI_ERR_INTERNAL, "sum-check round result never arrived");
-        }
-    }
+// ---- the mailboxes' pinned memory (their formats: mail.h; the host's reading of them: waits.cpp)
+void TailMailbox::ensure(DevCtx &c) {
+    if (host) return;
+    mail_alloc(c, (void **)&host, (size_t)kTailMaxGroups * sizeof(TailMail));
+    memset(host, 0, (size_t)kTailMaxGroups * sizeof(TailMail));
+    OTTI_HIP(hipHostGetDevicePointer((void **)&dev, host, 0));
 }
-void DevCtx::ensure_tail_mail() {
-    if (h_tail) return;
-    mail_alloc(*this, (void **)&h_tail, (size_t)kTailMaxGroups * sizeof(TailMail));
-    memset(h_tail, 0, (size_t)kTailMaxGroups * sizeof(TailMail));
-    OTTI_HIP(hipHostGetDevicePointer((void **)&d_tail_alias, h_tail, 0));
-}
-static long tail_timeout_ms() { static const long v = [] { const char *e = getenv("OTTI_TAIL_TIMEOUT_MS"); long x = e ? atol(e) : 0; return x > 0 ? x : 5000L; }(); return v; }
-void DevCtx::wait_tail(int n_groups, unsigned long long want) {
-    const auto t0 = std::chrono::steady_clock::now();
-    int done = 0;                                             // lines [0, done) have arrived
-    for (unsigned spins = 0;; spins++) {
-        while (done < n_groups && __atomic_load_n(&h_tail[done].seq, __ATOMIC_ACQUIRE) >= want) done++;
-        if (done == n_groups) return;
-#if defined(__x86_64__)
-        _mm_pause();
-#endif
-        if ((spins & 0x3ff) == 0x3ff && __atomic_load_n(&h_go->timed_out, __ATOMIC_ACQUIRE)) {
-            go_abort();
-            throw Error(OTTI_ERR_INTERNAL, "the persistent sum-check launch gave up waiting for the host (the proving thread was stalled beyond the launch's deadline)");
-        }
-        // a round of the persistent launch takes tens of microseconds; seconds without every line in mean that part of its grid is not
-        // resident (the workgroups that are wait for the host, the host for all of them): give the launch up — the caller proves again without it
-        if ((spins & 0xffff) == 0xffff && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(tail_timeout_ms())) {
-            if (go_published < go_issued) go_abort(); else { (void)hipStreamSynchronize(stream); reset_arrival_counters(); }
-            throw TailTimeout(OTTI_ERR_INTERNAL, "sum-check round result never arrived (persistent launch: its grid was not resident as a whole)");
-        }
-    }
-}
-// the same wait, adding up the W partial sums of every instance as its lines come in (lines a few ahead are prefetched: each is a fresh
-// cache line the device has just written, and 144 dependent misses in a row would cost more than the round's arithmetic)
-// lines [i0, i1) of a round's mails: wait for each (bounded when `bounded`: a helper thread must not throw) and add the W partials of every instance up
-static bool tail_sum_range(TailMail *h_tail, int i0, int i1, int W, unsigned long long want, Fr *sums, bool bounded) {
-#if defined(__x86_64__)
-    for (int i = i0; i < i1 && i < i0 + 16; i++) { _mm_prefetch((const char *)&h_tail[i], _MM_HINT_T0); _mm_prefetch((const char *)&h_tail[i] + 64, _MM_HINT_T0); }
-#endif
-    for (int i = i0; i < i1; i++) {
-#if defined(__x86_64__)
-        if (i + 16 < i1) { _mm_prefetch((const char *)&h_tail[i + 16], _MM_HINT_T0); _mm_prefetch((const char *)&h_tail[i + 16] + 64, _MM_HINT_T0); }
-#endif
-        if (bounded) {
-            unsigned spins = 0;
-            while (__atomic_load_n(&h_tail[i].seq, __ATOMIC_ACQUIRE) < want) {
-                if (++spins > 2000000u) return false;             // ~ a millisecond or more: the calling thread takes the slow path with its failure handling
-#if defined(__x86_64__)
-                _mm_pause();
-#endif
-            }
-        }
-        // the line came in one store instruction but as two 64-byte halves nothing orders: read, check the tag, read again until it fits (normally at once)
-        Fr part[3];
-        for (unsigned tries = 0;; tries++) {
-            const unsigned long long s = __atomic_load_n(&h_tail[i].seq, __ATOMIC_ACQUIRE), tag = __atomic_load_n(&h_tail[i].tag, __ATOMIC_ACQUIRE);
-            for (int k = 0; k < 3; k++) part[k] = h_tail[i].s[k];
-            if (s == want && go_tag(s, part, 3) == tag) break;
-            if (tries > 4000000u) { if (bounded) return false; throw Error(OTTI_ERR_INTERNAL, "a sum-check round's mail never became whole"); }
-#if defined(__x86_64__)
-            _mm_pause();
-#endif
-        }
-        Fr *acc = sums + 3 * (i / W);
-        if (i % W == 0) { acc[0] = part[0]; acc[1] = part[1]; acc[2] = part[2]; }
-        else { acc[0] = fr_add(acc[0], part[0]); acc[1] = fr_add(acc[1], part[1]); acc[2] = fr_add(acc[2], part[2]); }
-    }
-    return true;
-}
-void DevCtx::wait_tail_sums(int n_inst, int W, unsigned long long want, Fr *sums /* [n_inst][3] */) {
-    const int n = n_inst * W;
-    // 128-144 lines of 3 partial sums: adding them up on one core cost 2.6 us of every round (profiles/r3_tail_stamps.txt); the instances are
-    // independent, so the prover thread's helpers (pool.h: pinned next to it, ~55 ns hand-over) take a share each
-    SpinPool &pool = SpinPool::get();
-    const int nt = (n >= 48 && n_inst >= 2) ? std::min(std::min(4, pool.workers() + 1), n_inst) : 1;
-    if (nt > 1) {
-        bool ok[4] = {true, true, true, true};
-        std::function<void()> tasks[4];
-        for (int t = 0; t < nt; t++) {
-            const int y0 = n_inst * t / nt, y1 = n_inst * (t + 1) / nt;
-            tasks[t] = [this, t, y0, y1, W, want, sums, &ok] { ok[t] = tail_sum_range(h_tail, y0 * W, y1 * W, W, want, sums, true); };
-        }
-        pool.parallel(tasks, nt);
-        if (ok[0] && ok[1] && ok[2] && ok[3]) return;
-    }
-    wait_tail(n, want);                                       // (throws if the launch gave up or never answers)
-    tail_sum_range(h_tail, 0, n, W, want, sums, false);
-}
-// ---- the small MSMs' chunk mails (device.h MsmMail), summed on the host
-bool DevCtx::small_host_sum() const {
+bool MsmMailbox::host_sum(const DevCtx &c) const {
     static const bool env_on = [] { const char *e = getenv("OTTI_SMALL_HOST_SUM"); return !(e && e[0] == '0'); }();
-    return env_on && host_coherent;
+    return env_on && c.host_coherent;
 }
-void DevCtx::ensure_msm_mail() {
-    if (h_msm_mail) return;
-    mail_alloc(*this, (void **)&h_msm_mail, (size_t)kMsmMailRegions * kMsmMailCap * sizeof(MsmMail));
-    memset(h_msm_mail, 0, (size_t)kMsmMailRegions * kMsmMailCap * sizeof(MsmMail));
-    OTTI_HIP(hipHostGetDevicePointer((void **)&d_msm_mail_alias, h_msm_mail, 0));
-}
-void DevCtx::msm_queue(unsigned long long seq, uint32_t rows, uint32_t nchunks) {
-    if (msm_pending_n == kMsmMailRegions) {                  // the launch just queued mails over the oldest entry's region: that one can no longer be read
-        for (int i = 1; i < kMsmMailRegions; i++) msm_pending[i - 1] = msm_pending[i];
-        msm_pending_n--;
-    }
-    MsmPending &p = msm_pending[msm_pending_n++];
-    p.seq = seq; p.order = ++msm_order; p.region = (int)(msm_launches++ % kMsmMailRegions); p.rows = rows; p.nchunks = nchunks;
-}
-// the tag test of msm_mail_sum without waiting or adding (an idle stream: what has not come will not)
-static bool msm_mail_ok(const MsmMail *line, unsigned long long want) {
-    const unsigned long long s = __atomic_load_n(&line->seq, __ATOMIC_ACQUIRE), tag = __atomic_load_n(&line->tag, __ATOMIC_ACQUIRE);
-    if (s != want) return false;
-    Fp v[4];
-    for (int c = 0; c < 4; c++) v[c] = line->v[c];
-    return msm_mail_tag(s, v) == tag;
-}
-bool msm_mails_whole(const MsmMail *m, int n, unsigned long long want) {
-    for (int i = 0; i < n; i++) if (!msm_mail_ok(m + i, want)) return false;
-    return true;
-}
-// mails [i0, i1) of one row: wait for each (spins > max_spins: give up and return false; 0 = no limit), check its tag, add it to acc
-bool msm_mail_sum(const MsmMail *m, int i0, int i1, unsigned long long want, PtFe &acc, unsigned max_spins, bool allow_ifma) {
-    bool ok = true;
-    Fp v[4];
-    auto next = [&](int k) -> const Fp * {
-        const MsmMail *line = m + i0 + k;
-#if defined(__x86_64__)
-        if (i0 + k + 4 < i1) { _mm_prefetch((const char *)(line + 4), _MM_HINT_T0); _mm_prefetch((const char *)(line + 4) + 128, _MM_HINT_T0); }
-#endif
-        // the pair came in one store instruction but as two lines nothing orders: read, check the tag, read again until it fits
-        for (unsigned spins = 0;; spins++) {
-            const unsigned long long s = __atomic_load_n(&line->seq, __ATOMIC_ACQUIRE), tag = __atomic_load_n(&line->tag, __ATOMIC_ACQUIRE);
-            if (s == want) {
-                for (int c = 0; c < 4; c++) v[c] = line->v[c];
-                if (msm_mail_tag(s, v) == tag) return v;
-            }
-            if (max_spins && spins > max_spins) { ok = false; return nullptr; }
-#if defined(__x86_64__)
-            _mm_pause();
-#endif
-        }
-    };
-    host_sum_cached(acc, i1 - i0, next, allow_ifma);
-    return ok;
-}
-// Every mail of the launch, summed per row.  A row's chunks are split between the prover thread and its helpers (pool.h: pinned next to
-// it), rows side by side; a helper spins a bounded time only — if one gives up, this thread waits for the launch with wait_ticket's failure
-// handling (an armed launch that gave up, a deadline) and sums everything itself.
-void DevCtx::msm_host_sum(const MsmPending &p) {
-    const MsmMail *m = msm_mail_region(p.region);
-    const int rows = (int)p.rows, nch = (int)p.nchunks;
-    SpinPool &pool = SpinPool::get();
-    // >= 8 mails per thread (a hand-over costs ~50 ns, an addition ~60), at most kMaxSumThreads threads whatever OTTI_HOST_THREADS gives the pool
-    constexpr int kMaxSumThreads = 8;
-    const int per_row = std::max(1, std::min(std::min((pool.workers() + 1) / rows, nch / 8), kMaxSumThreads / rows));
-    const int nt = rows * per_row;
-    PtFe part[kMaxSumThreads];
-    bool ok[kMaxSumThreads];
-    if (nt > 1 && nt <= kMaxSumThreads) {
-        std::function<void()> tasks[kMaxSumThreads];
-        for (int t = 0; t < nt; t++) {
-            const int r = t / per_row, k = t % per_row, i0 = r * nch + nch * k / per_row, i1 = r * nch + nch * (k + 1) / per_row;
-            tasks[t] = [m, i0, i1, &p, &part, &ok, t] { part[t] = ptfe_identity(); ok[t] = msm_mail_sum(m, i0, i1, p.seq, part[t], 2000000u, true); };
-        }
-        pool.parallel(tasks, nt);
-        bool all = true;
-        for (int t = 0; t < nt; t++) all = all && ok[t];
-        if (all) {
-            for (int r = 0; r < rows; r++) {
-                PtFe acc = part[r * per_row];
-                for (int k = 1; k < per_row; k++) host_point_add(acc, part[r * per_row + k]);
-                h_pts[r] = ptfe_to(acc);
-            }
-            return;
-        }
-    }
-    // one thread, unbounded but with the failure handling of wait_ticket
-    const auto t0 = std::chrono::steady_clock::now();
-    for (int r = 0; r < rows; r++) {
-        PtFe acc = ptfe_identity();
-        int done = r * nch;
-        for (unsigned spins = 0; done < (r + 1) * nch; spins++) {
-            PtFe one = ptfe_identity();
-            if (msm_mail_sum(m, done, done + 1, p.seq, one, 1000u, true)) { host_point_add(acc, one); done++; spins = 0; continue; }
-            if ((spins & 0x3f) == 0x3f && __atomic_load_n(&h_go->timed_out, __ATOMIC_ACQUIRE)) {
-                go_abort();
-                throw Error(OTTI_ERR_INTERNAL, "an armed launch gave up waiting for the host (the proving thread was stalled beyond the launch's deadline)");
-            }
-            if ((spins & 0x3ff) == 0x3ff && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) {
-                if (go_published < go_issued) go_abort(); else OTTI_HIP(hipStreamSynchronize(stream));
-                if (!msm_mail_sum(m, done, done + 1, p.seq, one, 1000u, true)) throw Error(OTTI_ERR_INTERNAL, "a small MSM's chunk sums never arrived");
-                host_point_add(acc, one); done++; spins = 0;
-            }
-        }
-        h_pts[r] = ptfe_to(acc);
-    }
-}
-void DevCtx::wait_points(unsigned long long ticket) {
-    if (!ticket) { sync(); return; }
-    for (int i = 0; i < msm_pending_n; i++)
-        if (msm_pending[i].seq == ticket) {
-            const MsmPending p = msm_pending[i];
-            for (int j = i + 1; j < msm_pending_n; j++) msm_pending[j - 1] = msm_pending[j];
-            msm_pending_n--;
-            msm_host_sum(p);
-            msm_read[msm_read_next++ & 7] = ticket;
-            pending_host_encode = p.rows;
-            encode_pending();
-            return;
-        }
-    if (small_host_sum()) {
-        // this context's small launches mail (the switch is per process): the ticket's sums were read already — then this returns at once,
-        // as a flag wait on a delivered launch does — or they are gone, and nothing will ever raise a flag for them
-        for (unsigned long long r : msm_read) if (r == ticket) { encode_pending(); return; }
-        throw Error(OTTI_ERR_INTERNAL, "a small MSM's chunk sums were overwritten or released before they were read");
-    }
-    wait_ticket(ticket);
-    encode_pending();
-}
-void DevCtx::sync() {
-    OTTI_HIP(hipStreamSynchronize(stream));
-    if (msm_pending_n) {
-        // the stream is idle: the latest launch's mails are all in (unless it was an armed launch released without running: then nothing is);
-        // its row sums are what h_pts holds after a sync, unless a later launch of another kind left its own there
-        const MsmPending p = msm_pending[msm_pending_n - 1];
-        msm_pending_n = 0;
-        if (p.order > h_pts_order && msm_mails_whole(msm_mail_region(p.region), (int)(p.rows * p.nchunks), p.seq)) {
-            msm_host_sum(p);
-            msm_read[msm_read_next++ & 7] = p.seq;
-            pending_host_encode = p.rows;
-        }
-    }
-    encode_pending();
-}
-void DevCtx::encode_pending() {
-    if (pending_host_encode >= 2) {
-        SpinPool &pool = SpinPool::get(); const int nt = std::min<int>(pool.workers() + 1, (int)pending_host_encode);
-        const size_t n = pending_host_encode;
-        std::vector<std::function<void()>> tasks(nt);
-        for (int t = 0; t < nt; t++) tasks[t] = [this, t, nt, n] { for (size_t i = t; i < n; i += nt) pt_encode(h_points + 32 * i, h_pts[i]); };
-        pool.parallel(tasks.data(), nt);
-    } else if (pending_host_encode == 1) pt_encode(h_points, h_pts[0]);
-    pending_host_encode = 0;
+void MsmMailbox::ensure(DevCtx &c) {
+    if (host) return;
+    mail_alloc(c, (void **)&host, (size_t)kMsmMailRegions * kMsmMailCap * sizeof(MsmMail));
+    memset(host, 0, (size_t)kMsmMailRegions * kMsmMailCap * sizeof(MsmMail));
+    OTTI_HIP(hipHostGetDevicePointer((void **)&dev, host, 0));
 }
 
 }  // namespace otti

@@ -182,7 +182,7 @@ template <int kKind> __global__ __launch_bounds__(kBlock) void k_msm_rows(MsmArg
 //   * every addition is quad-parallel (fp10.h): 4 lanes per point, 2-3 multiplication depths per addition instead of 7-9;
 //   * a workgroup (64 quads) takes a SHORT chunk (about two pairs per quad), so the tree starts almost at once; its six levels go
 //     through LDS with one barrier each (every level has its own slots);
-//   * rows of at most two: every workgroup mails its chunk result (cached form, number and tag: MsmMail in device.h) to pinned host
+//   * rows of at most two: every workgroup mails its chunk result (cached form, number and tag: MsmMail in mail.h) to pinned host
 //     memory in one store instruction, and the host adds a row's chunk results up (DevCtx::msm_host_sum) — no second tree on the
 //     device behind an arrival counter, no finish launch, no copy, no stream synchronise.  (OTTI_SMALL_HOST_SUM=0: the last
 //     workgroup to arrive sums the chunk results with the same body and mails the row sums, the form this replaced);
@@ -477,11 +477,11 @@ static unsigned long long msm_launch(DevCtx &c, const DeviceGens &g, const Fr *d
     c.ensure_points(rows, nchunks);
     A.partial = c.msm_partial.p;
     A.fuse = (!bulk && mode == MSM_COMPRESSED && !addend && rows <= 2 && rows * nchunks <= kMsmMailCap) ? 1 : 0;
-    if (A.fuse && c.small_host_sum()) { A.fuse = 2; c.ensure_msm_mail(); }
+    if (A.fuse && c.msm_mail.host_sum(c)) { A.fuse = 2; c.msm_mail.ensure(c); }
     if (bul) A.bul = *bul; else { memset(&A.bul, 0, sizeof A.bul); }
     A.go = Armed{nullptr, nullptr, 0};
     A.rows = (uint32_t)rows; A.counter = c.d_counter2.p; A.host_pts = c.d_pts_alias; A.host_flag = c.d_flag_alias; A.seq = A.fuse ? ++c.seq : 0;
-    A.mail = A.fuse == 2 ? c.d_msm_mail_alias + (size_t)(c.msm_launches % kMsmMailRegions) * kMsmMailCap : nullptr;
+    A.mail = A.fuse == 2 ? c.msm_mail.dev + (size_t)(c.msm_mail.launches % kMsmMailRegions) * kMsmMailCap : nullptr;
     dim3 grid((unsigned)nchunks, (unsigned)rows);
     // OTTI_MSM_STAMPS=1: phase stamps of every fused small launch on stderr (development aid; synchronises the stream)
     static const bool want_stamps = getenv("OTTI_MSM_STAMPS") != nullptr;
@@ -498,13 +498,13 @@ static unsigned long long msm_launch(DevCtx &c, const DeviceGens &g, const Fr *d
         else if (bulk) hipLaunchKernelGGL(k_msm_rows<MSM_BULK>, grid, kBlock, 0, c.stream, A);
         else hipLaunchKernelGGL(k_msm_small, grid, kBlock, 0, c.stream, A);
     }
-    if (A.fuse == 2) c.msm_queue(A.seq, (uint32_t)rows, (uint32_t)nchunks);      // the host sums the mails in wait_points(seq) / sync()
+    if (A.fuse == 2) c.msm_mail.queue(A.seq, (uint32_t)rows, (uint32_t)nchunks);      // the host sums the mails in wait_points(seq) / sync()
     if (A.stamps && A.fuse == 2) {
         OTTI_HIP(hipStreamSynchronize(c.stream));
         const unsigned long long *t = h_stamps;
         auto us = [&](int a, int b) { return t[b] >= t[a] ? (double)(t[b] - t[a]) * 0.01 : -1.0; };
         const auto h0 = std::chrono::steady_clock::now();
-        c.msm_host_sum(c.msm_pending[c.msm_pending_n - 1]);
+        c.msm_host_sum(c.msm_mail.pending[c.msm_mail.pending_n - 1]);
         const double host_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - h0).count();
         fprintf(stderr, "[otti] k_msm_small rows=%zu terms=%zu chunks=%zu bullet=%d host-sum: scalars %.2f | pairs %.2f | tree + mail %.2f | total %.2f us on the device; "
                         "host sum of %zu mails (all in) %.2f us\n",
@@ -517,7 +517,7 @@ static unsigned long long msm_launch(DevCtx &c, const DeviceGens &g, const Fr *d
                 rows, n_dense + n_extra, nchunks, bul ? 1 : 0, us(0, 1), us(1, 2), us(2, 3), us(3, 4), us(4, 5), us(5, 6), us(6, 7), us(0, 7));
     }
     if (A.fuse) { c.pending_host_encode = rows; return A.seq; }
-    c.h_pts_order = ++c.msm_order;                          // every branch below replaces what a mailing launch before it left for sync()
+    c.msm_mail.h_pts_order = ++c.msm_mail.order;                          // every branch below replaces what a mailing launch before it left for sync()
     // rows with a single chunk need no finish pass: their partial IS the row sum
     const Pt *finals = c.msm_partial.p;
     if (nchunks > 1) {

@@ -370,10 +370,10 @@ unsigned long long dev_pc_tail(DevCtx &c, const PcList &L, int W, size_t len0, s
         t_out < (size_t)W || len0 <= t_out || rounds < 1)
         throw Error(OTTI_ERR_INTERNAL, "persistent sum-check tail: bad geometry");
     if (slot + (size_t)3 * L.n * t_out > (size_t)kResultSlots) throw Error(OTTI_ERR_INTERNAL, "sum-check tail does not fit the pinned result buffer");
-    c.ensure_tail_mail();
+    c.tail_mail.ensure(c);
     TailArgs a;
     a.L = L; a.W = W; a.len0 = (uint32_t)len0; a.t_out = (uint32_t)t_out; a.fold_on_load = fold_r ? 1 : 0; a.r = fold_r ? *fold_r : fr_zero(); a.E = E;
-    a.mail = c.d_tail_alias; a.host_out = c.d_results_alias + slot;
+    a.mail = c.tail_mail.dev; a.host_out = c.d_results_alias + slot;
     a.seq0 = c.seq + 1; c.seq += (unsigned long long)rounds + 1;
     a.go = c.arm_many(rounds);
     static const bool test_drop = getenv("OTTI_TEST_TAIL_DROP") != nullptr;

@@ -14,9 +14,7 @@
 #include <mutex>
 #include <thread>
 #include <vector>
-#if defined(__x86_64__)
-#include <immintrin.h>
-#endif
+#include "cpu_relax.h"
 
 namespace otti {
 
@@ -97,7 +95,7 @@ public:
             if (st == 2) break;
             // (a helper that is on its core takes a task within ~50 ns; after a microsecond or two without that, it is not)
             if (st == 1 && idle >= 48) { int exp = 1; if (s.state.compare_exchange_strong(exp, 4, std::memory_order_acq_rel)) { s.fn(); break; } }
-            relax();
+            cpu_relax();
         }
         s.state.store(0, std::memory_order_relaxed);
     }
@@ -119,13 +117,6 @@ private:
     unsigned cores_ = 1; bool fixed_ = false;
     std::mutex mu_; std::condition_variable cv_;
 
-    static void relax() {
-#if defined(__x86_64__)
-        _mm_pause();
-#else
-        std::this_thread::yield();
-#endif
-    }
     SpinPool() {
         // cores this process may use: its affinity mask, shared with the other rank processes of the node (one per GPU)
         unsigned hc = std::thread::hardware_concurrency();
@@ -217,7 +208,7 @@ private:
                 continue;
             }
             if (active_.load(std::memory_order_relaxed) > 0) {
-                if (i < workers()) relax();
+                if (i < workers()) cpu_relax();
                 else std::this_thread::sleep_for(std::chrono::microseconds(20));      // over the budget of a crowded process: leave the core to a prover thread
                 continue;
             }

@@ -4,6 +4,7 @@
 // reading epoch e — so two slot sets are enough and no second barrier is needed.
 #include "shard.h"
 #include "device.h"
+#include "cpu_relax.h"
 #include <rccl/rccl.h>
 #include <dlfcn.h>
 #include <atomic>
@@ -11,7 +12,6 @@
 #include <vector>
 #include <errno.h>
 #include <fcntl.h>
-#include <immintrin.h>
 #include <stdlib.h>
 #include <string.h>
 #include <sys/mman.h>
@@ -32,7 +32,7 @@ struct Deadline {
     std::chrono::steady_clock::time_point end = std::chrono::steady_clock::now() + std::chrono::duration_cast<std::chrono::steady_clock::duration>(std::chrono::duration<double>(timeout_s()));
     unsigned spins = 0;
     void pause(const char *what) {
-        _mm_pause();
+        cpu_relax();
         if ((++spins & 0xfff) == 0 && std::chrono::steady_clock::now() > end) throw Error(OTTI_ERR_INTERNAL, std::string("shard exchange timed out: ") + what);
     }
 };

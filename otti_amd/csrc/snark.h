@@ -6,9 +6,7 @@
 // k_snark.hip; the R1CS satisfiability proof inside it is the same device code as NIZK mode (prover.cpp r1cs_prove_device).
 #pragma once
 #include "spartan.h"
-#if defined(__x86_64__)
-#include <immintrin.h>
-#endif
+#include "cpu_relax.h"
 #include <algorithm>
 #include <vector>
 #include <system_error>
@@ -125,9 +123,7 @@ private:
             size_t i = next_.load(std::memory_order_relaxed);
             if (i < count_.load(std::memory_order_acquire)) { if (next_.compare_exchange_weak(i, i + 1, std::memory_order_acq_rel)) run_one(items_[i]); continue; }
             if (until_empty || closing_.load(std::memory_order_acquire)) { if (next_.load() >= count_.load(std::memory_order_acquire)) return; continue; }
-#if defined(__x86_64__)
-            _mm_pause();
-#endif
+            cpu_relax();
         }
     }
 };

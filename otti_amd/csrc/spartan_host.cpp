@@ -571,9 +571,7 @@ void dotproductlog_verify(const DotProductProofLog &pf, size_t n, const Gens &g,
     };
     auto closing = [=] {
         while (st->done.load(std::memory_order_acquire) < 3) {
-#if defined(__x86_64__)
-            _mm_pause();
-#endif
+            cpu_relax();
         }
         if (st->ok.load(std::memory_order_acquire) < 3) return;            // the job that failed has reported why
         const Pt Gamma_hat = pt_add(st->half[0], st->half[1]);
