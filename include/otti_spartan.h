@@ -60,7 +60,8 @@ int32_t otti_instance_new(uint64_t num_cons, uint64_t num_vars, uint64_t num_inp
 void    otti_instance_free(otti_instance *inst);
 /* padded sizes as seen by the prover (Instance.inst.get_num_cons / get_num_vars / get_num_inputs) */
 int32_t otti_instance_dims(const otti_instance *inst, uint64_t *num_cons, uint64_t *num_vars, uint64_t *num_inputs);
-/* Instance::is_sat(&vars, &inputs) -> Result<bool, R1CSError>  (host check, used by spzk before proving) */
+/* Instance::is_sat(&vars, &inputs) -> Result<bool, R1CSError>.  The HOST form: one thread over host byte arrays, a yes or no.  spzk does
+   not call it; the check on the device, on the assignment already uploaded and with a diagnosis, is otti_witness_check_sat below. */
 int32_t otti_instance_is_sat(const otti_instance *inst, const uint8_t *vars32, size_t nvars, const uint8_t *inputs32, size_t ninputs,
                              int32_t *sat);
 
@@ -95,6 +96,16 @@ int32_t otti_witness_upload(otti_instance *inst, const uint8_t *vars32, size_t n
 void    otti_witness_free(otti_witness *w);
 int32_t otti_nizk_prove_resident(otti_instance *inst, otti_witness *wit, otti_gens *gens, const uint8_t *tlabel, size_t tlabel_len,
                                  const uint8_t *seed32, uint8_t **proof, size_t *proof_len, double *stage_ms);
+/* Instance::is_sat on the assignment resident in HBM, with a diagnosis.  *n_unsat: number of constraints with <A_r,z>·<B_r,z> != <C_r,z>.
+   rows[0 .. min(n_unsat, rows_cap)): the lowest failing row indices, ascending (indices of the caller's constraints; padding rows never fail).
+   abc96 (optional, rows_cap * 96 bytes): canonical <A_r,z>, <B_r,z>, <C_r,z> for each reported row.  kernel_ms optional.
+   One pass of the sparse-product kernels that writes a bit per constraint instead of Az, Bz, Cz; the bitmap only comes back when a row
+   fails.  Reads the handles only: callable from any thread that may prove, concurrently with proofs.  One GPU (a sharded prover checks
+   its replicated witness on its own device).  There is no CPU fallback: OTTI_ERR_NO_DEVICE without a device.
+   OTTI_ERR_BAD_ARG: inst, wit or n_unsat NULL, or rows_cap > 0 with rows NULL.  OTTI_ERR_INVALID_NUM_VARS: the witness was uploaded for
+   an instance of other dimensions. */
+int32_t otti_witness_check_sat(otti_instance *inst, otti_witness *wit, uint64_t *n_unsat,
+                               uint64_t *rows, size_t rows_cap, uint8_t *abc96, float *kernel_ms);
 /* ---- one proof over several GPUs of one node (no reference counterpart: upstream `spzk` is one process
    [REF /root/reference/run.py:52-59]).  One process per GPU.  Every process calls otti_shard_init with the same segment name (a
    fresh, unique name per job: it names a POSIX shared-memory object, removed again once all ranks are attached), its rank and the
@@ -258,6 +269,10 @@ int32_t otti_k_bullet_last_fold(size_t R, const uint8_t *h_u, const uint8_t *h_u
         Montgomery-form elements; h_* = small host arrays (challenges come from the transcript).  Calls that return round sums
         (h_e*) wait for that launch's result; the others only enqueue. ---- */
 int32_t otti_kd_multiply_vec(otti_instance *inst, const void *d_z, void *d_Az, void *d_Bz, void *d_Cz, void *stream);
+/* the same pass as otti_witness_check_sat on a caller's device vector z (2*num_vars Montgomery elements) and stream: d_bits receives
+   ceil(num_cons/64) 64-bit words (bit r & 63 of word r >> 6 set: constraint r fails; every word is written).  h_n_unsat non-NULL: waits and
+   returns the number of failing constraints; NULL: only enqueues. */
+int32_t otti_kd_check_sat(otti_instance *inst, const void *d_z, void *d_bits, uint64_t *h_n_unsat, void *stream);
 int32_t otti_kd_eval_table_sparse(otti_instance *inst, const void *d_eq_rx, const uint8_t *h_rABC, void *d_out, void *stream);
 int32_t otti_kd_eq_evals(const uint8_t *h_r, size_t ell, void *d_out, void *stream);
 int32_t otti_kd_fold_top(void *d_Z, size_t len, const uint8_t *h_r, void *stream);                    /* in place: len -> len/2 */
@@ -291,7 +306,8 @@ int32_t otti_stats_enable(int32_t on);
 /* restrict timing to one class (call after enable): two event records per launch are not free on the latency-bound round loop */
 int32_t otti_stats_select(const char *kernel_class);
 int32_t otti_stats_read(const char *kernel_class, uint64_t *count, double *total_ms);
-/* SNARK mode adds the classes pc_round (rounds of the batched product-circuit sum-checks) prod_layer hash_layer gather dot_many. */
+/* SNARK mode adds the classes pc_round (rounds of the batched product-circuit sum-checks) prod_layer hash_layer gather dot_many; the verifier
+   decode msm_var; otti_witness_check_sat / otti_kd_check_sat sat_check. */
 /* 1 when the calling thread's next proof would use armed launches (kernels queued ahead of their challenge): off under OTTI_ARMED=0,
    while a class with armed kernels (msm_small sc_cubic sc_quad pc_round) is being timed, and with several proofs in flight */
 int32_t otti_armed_launches_on(int32_t *on);

@@ -80,6 +80,7 @@ _sig("otti_nizk_prove", _i32, _vp, _vp, _sz, _vp, _sz, _vp, ctypes.c_char_p, _sz
      ctypes.POINTER(_vp), ctypes.POINTER(_sz), ctypes.POINTER(ctypes.c_double))
 _sig("otti_witness_upload", _i32, _vp, _vp, _sz, _vp, _sz, ctypes.POINTER(_vp))
 _sig("otti_witness_free", None, _vp)
+_sig("otti_witness_check_sat", _i32, _vp, _vp, ctypes.POINTER(_u64), _vp, _sz, _vp, ctypes.POINTER(ctypes.c_float))
 _sig("otti_nizk_prove_resident", _i32, _vp, _vp, _vp, ctypes.c_char_p, _sz, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_sz),
      ctypes.POINTER(ctypes.c_double))
 _sig("otti_shard_init", _i32, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32)
@@ -140,6 +141,7 @@ _sig("otti_k_poly_bound", _i32, _vp, _sz, _sz, _vp, _vp, _fp)
 _sig("otti_k_bullet_round", _i32, _vp, _sz, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _fp)
 _sig("otti_k_bullet_last_fold", _i32, _sz, _vp, _vp, _vp, _vp, _vp)
 _sig("otti_kd_multiply_vec", _i32, _vp, _vp, _vp, _vp, _vp, _vp)
+_sig("otti_kd_check_sat", _i32, _vp, _vp, _vp, ctypes.POINTER(_u64), _vp)
 _sig("otti_kd_eval_table_sparse", _i32, _vp, _vp, _vp, _vp, _vp)
 _sig("otti_kd_eq_evals", _i32, _vp, _sz, _vp, _vp)
 _sig("otti_kd_fold_top", _i32, _vp, _sz, _vp, _vp)
@@ -355,6 +357,20 @@ class NIZKGens:
             self._h = None
 
 
+class SatReport:
+    """What Witness.check_sat found: n_unsat failing constraints, the lowest of them in ``rows`` (uint64, ascending) and, when asked for,
+    ``values[i]`` = canonical <A_r,z>, <B_r,z>, <C_r,z> of rows[i] as (3, 32) little-endian bytes.  True when the assignment satisfies."""
+
+    def __init__(self, n_unsat, rows, values, kernel_ms):
+        self.n_unsat, self.rows, self.values, self.kernel_ms = n_unsat, rows, values, kernel_ms
+
+    def __bool__(self):
+        return self.n_unsat == 0
+
+    def __repr__(self):
+        return f"SatReport(n_unsat={self.n_unsat}, rows={self.rows.tolist()})"
+
+
 class Witness:
     """Assignment resident in HBM (z = vars || 1 || inputs || 0..): upload once, prove many times."""
 
@@ -363,6 +379,15 @@ class Witness:
         h = _vp()
         _check(lib.otti_witness_upload(inst._h, _ptr(v), v.shape[0], _ptr(i), i.shape[0], ctypes.byref(h)))
         self._h = h
+
+    def check_sat(self, inst, max_rows=64, values=True):
+        """Instance::is_sat on the device, on this resident assignment, with the failing constraints named (otti_witness_check_sat)"""
+        n, ms = _u64(), ctypes.c_float()
+        rows = np.zeros(max_rows, dtype=np.uint64)
+        abc = np.zeros((max_rows, 3, 32), dtype=np.uint8) if values else None
+        _check(lib.otti_witness_check_sat(inst._h, self._h, ctypes.byref(n), _ptr(rows), max_rows, _ptr(abc), ctypes.byref(ms)))
+        k = min(n.value, max_rows)
+        return SatReport(n.value, rows[:k].copy(), abc[:k].copy() if values else None, ms.value)
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -611,7 +636,7 @@ def fr_to_ints(a):
 
 
 KERNEL_CLASSES = ("msm_rows", "msm_small", "msm_finish", "sc_cubic", "sc_quad", "spmv", "eq", "reduce", "poly_bound", "bullet", "other",
-                  "pc_round", "prod_layer", "hash_layer", "gather", "dot_many", "decode", "msm_var")
+                  "pc_round", "prod_layer", "hash_layer", "gather", "dot_many", "decode", "msm_var", "sat_check")
 
 
 def stats_enable(on=True, only=None):
@@ -868,6 +893,11 @@ class kernels_dev:
     @staticmethod
     def multiply_vec(inst, z, Az, Bz, Cz, stream=None):
         _check(lib.otti_kd_multiply_vec(inst._h, z.ptr, Az.ptr, Bz.ptr, Cz.ptr, stream))
+
+    @staticmethod
+    def check_sat(inst, z, bits, stream=None):
+        """the satisfiability pass on a device vector z; bits: DeviceArray(ceil(num_cons / 64), 8).  Returns the number of failing constraints."""
+        n = _u64(); _check(lib.otti_kd_check_sat(inst._h, z.ptr, bits.ptr, ctypes.byref(n), stream)); return n.value
 
     @staticmethod
     def eval_table_sparse(inst, eq_rx, rABC, out, stream=None):

@@ -402,6 +402,21 @@ int32_t otti_nizk_prove_resident(otti_instance *inst, otti_witness *wit, otti_ge
         *proof = to_malloc(pf, proof_len); return OTTI_OK;
     });
 }
+// Instance::is_sat on the resident assignment, with a diagnosis (device.h dev_check_sat).  No host fallback: without a device DevCtx::get throws.
+int32_t otti_witness_check_sat(otti_instance *inst, otti_witness *wit, uint64_t *n_unsat, uint64_t *rows, size_t rows_cap, uint8_t *abc96, float *kernel_ms) {
+    return guarded([&] {
+        if (!inst || !wit || !n_unsat || (rows_cap && !rows)) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        Instance &I = *inst->I;
+        if (wit->w->z.n != 2 * I.num_vars) throw Error(OTTI_ERR_INVALID_NUM_VARS, "the witness was uploaded for an instance of other dimensions");
+        DevCtx &c = DevCtx::get(); ensure_instance_device(I);
+        const SatReport rep = dev_check_sat(c, *I.dev, wit->w->z.p, rows_cap, abc96 != nullptr);
+        *n_unsat = rep.n_unsat;
+        for (size_t i = 0; i < rep.rows.size(); i++) rows[i] = rep.rows[i];
+        if (abc96 && !rep.abc96.empty()) memcpy(abc96, rep.abc96.data(), rep.abc96.size());
+        if (kernel_ms) *kernel_ms = rep.kernel_ms;
+        return OTTI_OK;
+    });
+}
 int32_t otti_shard_init(const char *segment_name, uint32_t rank, uint32_t world) {
     return guarded([&] {
         if (!segment_name) throw Error(OTTI_ERR_BAD_ARG, "null argument");
@@ -871,6 +886,15 @@ int32_t otti_kd_multiply_vec(otti_instance *inst, const void *z, void *Az, void 
         dev_spmv3(c, I.dev->by_row, dfr(z), dfr(Az), dfr(Bz), dfr(Cz), false, nullptr); return OTTI_OK;
     });
 }
+int32_t otti_kd_check_sat(otti_instance *inst, const void *z, void *bits, uint64_t *n_unsat, void *stream) {
+    return guarded([&] {
+        if (!inst || !z || !bits) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        DevCtx &c = DevCtx::get(); Instance &I = *inst->I; ensure_instance_device(I); StreamScope ss(c, stream);
+        dev_sat_pass(c, I.dev->by_row, dfr(z), reinterpret_cast<unsigned long long *>(bits));
+        if (n_unsat) *n_unsat = dev_sat_count(c);                 // waits for the pass; without it the call only enqueues
+        return OTTI_OK;
+    });
+}
 int32_t otti_kd_eval_table_sparse(otti_instance *inst, const void *eq_rx, const uint8_t *rABC, void *out, void *stream) {
     return guarded([&] {
         if (!inst || !eq_rx || !rABC || !out) throw Error(OTTI_ERR_BAD_ARG, "null argument");
@@ -943,7 +967,7 @@ int32_t otti_bench_fr_mul_peak(double *products_per_second) {
 
 // ------------------------------------------------------------------------------------------------ kernel timing (HIP events on the library stream)
 static const char *kClassNames[KC_COUNT] = {"msm_rows", "msm_small", "msm_finish", "sc_cubic", "sc_quad", "spmv", "eq", "reduce", "poly_bound", "bullet", "other",
-                                               "pc_round", "prod_layer", "hash_layer", "gather", "dot_many", "decode", "msm_var"};
+                                               "pc_round", "prod_layer", "hash_layer", "gather", "dot_many", "decode", "msm_var", "sat_check"};
 int32_t otti_stats_enable(int32_t on) { KStats::get().on = on != 0; KStats::get().mask = 0xffffffffu; KStats::get().reset(); return OTTI_OK; }
 int32_t otti_stats_select(const char *kernel_class) {
     for (int k = 0; k < KC_COUNT; k++) if (!strcmp(kernel_class, kClassNames[k])) { KStats::get().mask = 1u << k; return OTTI_OK; }

@@ -122,7 +122,9 @@ struct DevCtx {
     Fr *d_results_alias = nullptr;                            // device address of h_results (zero-copy stores)
     unsigned long long *h_flag = nullptr, *d_flag_alias = nullptr, seq = 0;   // host-visible completion flag of the latest mailbox launch
     DevBuf<unsigned> d_counter;                               // arrival counter of the publishing workgroups
-    DevBuf<unsigned long long> d_counts;                      // two 64-bit tallies for the kernels that count (non-canonical / small scalars): no allocation per call
+    DevBuf<unsigned long long> d_counts;                      // two 64-bit tallies for the kernels that count (non-canonical / small scalars / failing constraints): no allocation per call
+    DevBuf<unsigned long long> sat_bits;                      // dev_check_sat: one bit per constraint row (grown on demand, kept across calls)
+    DevBuf<uint32_t> sat_rows; DevBuf<Fr> sat_abc;            // its report kernel's row ids and 3 sums per row (kSatReportRows of them)
     Mailbox next_mailbox(int slot);
     GoBox *h_go = nullptr, *d_go_alias = nullptr; DevBuf<GoBox> d_go; unsigned long long go_issued = 0, go_published = 0;
     unsigned long long arm_deadline = kArmDeadlineTicks;     // of the launches armed from now on (the self-test shortens it)
@@ -173,7 +175,7 @@ constexpr size_t kHostPtsCap = 512;
 // per-kernel-class HIP-event timing on the library's own stream (bench.py's roofline numbers come from here)
 enum KClass { KC_MSM_ROWS = 0, KC_MSM_SMALL, KC_MSM_FINISH, KC_SC_CUBIC, KC_SC_QUAD, KC_SPMV, KC_EQ, KC_REDUCE, KC_BOUND, KC_BULLET, KC_OTHER,
               KC_PC_ROUND, KC_PROD_LAYER, KC_HASH_LAYER, KC_GATHER, KC_DOT_MANY /* SNARK mode (k_snark.hip) */,
-              KC_DECODE, KC_MSM_VAR /* verifier (k_msm.hip) */, KC_COUNT };
+              KC_DECODE, KC_MSM_VAR /* verifier (k_msm.hip) */, KC_SAT_CHECK /* dev_sat_pass (k_sparse.hip) */, KC_COUNT };
 struct KStats {
     bool on = false; unsigned mask = 0xffffffffu;            // bit k set: kernel class k is timed
     std::vector<hipEvent_t> pool; std::vector<int> cls; size_t used = 0;
@@ -233,6 +235,18 @@ void dev_to_canonical(DevCtx &c, const Fr *in, Fr *out, size_t n);
 void dev_fill_zero(DevCtx &c, Fr *p, size_t n);
 // ---- K1 / K6: sparse products.  combine == false: out[k][r] = sum_p val_k[p] * x[idx_k[p]];  true: out[0][r] = sum_k coef[k] * (...)
 void dev_spmv3(DevCtx &c, const DeviceCsrSet &m, const Fr *x, Fr *out0, Fr *out1, Fr *out2, bool combine, const Fr coef[3]);
+// ---- Instance::is_sat on the device (k_sparse.hip): per constraint row r the three sums of dev_spmv3 and <A_r,z> <B_r,z> == <C_r,z>; Az, Bz, Cz
+// are never written.  dev_sat_pass only queues: bits[r >> 6] bit (r & 63) is set for every FAILING row (all (rows + 63) / 64 words are written: no
+// zeroing beforehand), c.d_counts[0] holds their number.  dev_check_sat runs it into the context's own bitmap, reads the count through the pinned
+// result buffer and — only when it is non-zero — downloads the bitmap, lists the lowest min(count, max_rows) failing rows in ascending order
+// and, with_values, recomputes their three sums (canonical little-endian bytes, 96 per row).  Reads z and the instance; writes scratch of the
+// CALLER's context alone, so any thread that may prove may check.
+constexpr int kSatCountSlot = 24;                            // result slot the count is copied to (clear of the rounds' and the instance evaluation's)
+constexpr size_t kSatReportRows = 64;                        // rows per launch of the report kernel (one workgroup each)
+struct SatReport { uint64_t n_unsat = 0; std::vector<uint64_t> rows; std::vector<uint8_t> abc96; float kernel_ms = 0; };
+void dev_sat_pass(DevCtx &c, const DeviceCsrSet &m, const Fr *z, unsigned long long *bits);
+uint64_t dev_sat_count(DevCtx &c);                           // waits for the pass queued last on c.stream and returns its count
+SatReport dev_check_sat(DevCtx &c, DeviceInstance &d, const Fr *z, size_t max_rows, bool with_values);
 // ---- K2: eq tables.  r is a HOST array (challenges come from the transcript)
 void dev_eq_evals(DevCtx &c, const Fr *r_host, size_t ell, Fr *out, Fr *scratch /* >= 3 * 4096 elements; 5 * 4096 for ell = 25 */);
 void dev_eq_evals2(DevCtx &c, const Fr *r0_host, size_t ell0, Fr *out0, const Fr *r1_host, size_t ell1, Fr *out1, Fr *scratch);   // both in one launch when each has at most 13 variables

@@ -112,6 +112,161 @@ void dev_spmv3(DevCtx &c, const DeviceCsrSet &m, const Fr *x, Fr *o0, Fr *o1, Fr
     }
 }
 
+// ------------------------------------------------------------------------------------------------ satisfiability pass (Instance::is_sat on the device)
+// Per constraint row r: a = <A_r,z>, b = <B_r,z>, c = <C_r,z> formed exactly as the products above form them, then a b == c in GF(l).  Az, Bz and
+// Cz are never written: a row's only output is bit (r & 63) of bits[r >> 6], set when the row FAILS, and the failing rows are counted in *count.
+// Forms: z and the coefficients are canonical Montgomery words (< l).  entry_term ends in a conditional subtraction (both of its paths return a
+// word in [0, l)) and fr_add keeps [0, l), so row_dot — and a quad's or a workgroup's sum of such words — is the CANONICAL Montgomery word of the
+// row sum, never a representative in [l, 2l).  fr_mul(aR, bR) is the canonical word of abR.  Equal field elements are therefore equal words and
+// the comparison is a plain word compare.  The verdict depends on the row alone, so every launch geometry gives the same bitmap and count.
+// Bitmap writes: a wave owns whole 64-row words and lane 0 stores each with one ordinary 8-byte store (every word of the bitmap is written,
+// so it needs no zeroing); only the long rows, judged by a later launch, come in with atomicOr.  The count costs one atomicAdd per wave with
+// failures: at most one per wave of the grid when every row fails.
+__device__ __forceinline__ bool row_fails(const Fr &a, const Fr &b, const Fr &c) { return !fr_eq(fr_mul(a, b), c); }
+__device__ __forceinline__ bool row_is_heavy(const DCsr3 &m, size_t r) {
+    return max(m.ptr[0][r + 1] - m.ptr[0][r], max(m.ptr[1][r + 1] - m.ptr[1][r], m.ptr[2][r + 1] - m.ptr[2][r])) > (uint32_t)kHeavyRow;
+}
+// row per lane (k_spmv3_light's layout): a wave's 64 rows are one word, its verdicts one __ballot
+template <bool kSmall> __global__ __launch_bounds__(kBlock) void k_sat_light(DCsr3 m, size_t rows, const Fr *x, unsigned long long *bits, unsigned long long *count) {
+    unsigned long long mine = 0;                                    // failing rows of this wave's words (lane 0)
+    const size_t padded = (rows + 63) & ~(size_t)63;                // grid strides are multiples of 64: a wave enters and leaves the loop as a whole
+    for (size_t r = blockIdx.x * (size_t)blockDim.x + threadIdx.x; r < padded; r += (size_t)gridDim.x * blockDim.x) {
+        bool fail = false;
+        if (r < rows && !row_is_heavy(m, r)) {
+            const Fr a0 = row_dot<kSmall>(m, 0, x, r);
+            const Fr a1 = row_dot<kSmall>(m, 1, x, r);
+            const Fr a2 = row_dot<kSmall>(m, 2, x, r);
+            fail = row_fails(a0, a1, a2);
+        }
+        const unsigned long long word = (unsigned long long)__ballot(fail);
+        if ((threadIdx.x & 63) == 0) { bits[r >> 6] = word; mine += (unsigned long long)__popcll(word); }
+    }
+    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(count, mine);
+}
+// bits 0, 4, 8, .. 60 of a ballot (one lane of each quad) packed into bits 0 .. 15
+__device__ __forceinline__ unsigned long long quad_votes(unsigned long long v) {
+    v &= 0x1111111111111111ull;
+    v = (v | (v >> 3)) & 0x0303030303030303ull;
+    v = (v | (v >> 6)) & 0x000f000f000f000full;
+    v = (v | (v >> 12)) & 0x000000ff000000ffull;
+    return (v | (v >> 24)) & 0xffffull;
+}
+// row per quad (k_spmv3_quad's layout: four lanes walk a row, 16 rows per wave and step).  A wave takes the four steps of one 64-row word in
+// turn.  After quad_sum all four lanes of a quad hold the row's sums: lane q of the quad keeps those of step q, so that after the fourth
+// step each of the 64 lanes holds ONE row of the word (lane L: row 16 (L & 3) + (L >> 2)) and the product a b is formed once per word with
+// every lane busy, not once per step with one lane in four.  The ballot comes in that lane order; lane 0 puts it in row order and stores it.
+// Measured on the compiler-like 2^20 instance (multiply_vec: 0.32 ms): 0.30 ms this way (99 VGPRs, 4 waves per SIMD); 0.335 ms with the
+// product in every step (75 VGPRs) and the same with the sums handed over through LDS instead of kept in registers.
+template <bool kSmall> __global__ __launch_bounds__(kBlock) void k_sat_quad(DCsr3 m, size_t rows, const Fr *x, unsigned long long *bits, unsigned long long *count) {
+    const int q = threadIdx.x & 3, lane = threadIdx.x & 63;
+    const size_t words = (rows + 63) >> 6, nwaves = ((size_t)gridDim.x * blockDim.x) >> 6;
+    unsigned long long mine = 0;
+    for (size_t w = (blockIdx.x * (size_t)blockDim.x + threadIdx.x) >> 6; w < words; w += nwaves) {
+        Fr keep[3] = {fr_zero(), fr_zero(), fr_zero()};            // a padding or long row keeps 0, 0, 0: it passes here
+#pragma unroll 1
+        for (int j = 0; j < 4; j++) {
+            const size_t r = (w << 6) + (size_t)(16 * j + (lane >> 2));
+            Fr a[3] = {fr_zero(), fr_zero(), fr_zero()};
+            if (r < rows && !row_is_heavy(m, r))
+                for (int k = 0; k < 3; k++) {
+                    const uint32_t p1 = m.ptr[k][r + 1];
+                    for (uint32_t p = m.ptr[k][r] + (uint32_t)q; p < p1; p += 4) a[k] = fr_add(a[k], entry_term<kSmall>(m, k, p, x));
+                }
+            for (int k = 0; k < 3; k++) a[k] = quad_sum(a[k]);     // every lane of the wave takes part
+            if (q == j) for (int k = 0; k < 3; k++) keep[k] = a[k];
+        }
+        const unsigned long long v = (unsigned long long)__ballot(row_fails(keep[0], keep[1], keep[2]));
+        if (lane == 0) {
+            const unsigned long long word = quad_votes(v) | (quad_votes(v >> 1) << 16) | (quad_votes(v >> 2) << 32) | (quad_votes(v >> 3) << 48);
+            bits[w] = word; mine += (unsigned long long)__popcll(word);
+        }
+    }
+    if (lane == 0 && mine) atomicAdd(count, mine);
+}
+// the checking form of k_spmv3_heavy_combine: one workgroup per long row adds its segments' partial sums up and sets the row's bit.  Runs after
+// the launch above has stored the row's word (with the bit clear), on the same stream.
+__global__ __launch_bounds__(kBlock) void k_sat_heavy_check(const uint32_t *heavy, const uint32_t *seg_begin, const Fr *partial, unsigned long long *bits, unsigned long long *count) {
+    const size_t h = blockIdx.x;
+    Fr acc[3] = {fr_zero(), fr_zero(), fr_zero()};
+    for (uint32_t s = seg_begin[h] + threadIdx.x; s < seg_begin[h + 1]; s += blockDim.x)
+        for (int k = 0; k < 3; k++) acc[k] = fr_add(acc[k], partial[(size_t)s * 3 + k]);
+    block_reduce<3>(acc);
+    if (threadIdx.x != 0 || !row_fails(acc[0], acc[1], acc[2])) return;
+    const size_t r = heavy[h];
+    atomicOr(&bits[r >> 6], 1ull << (r & 63));
+    atomicAdd(count, 1ull);
+}
+// The report: one workgroup per listed row recomputes the three sums (a row of any length: the workgroup strides over it) and writes them
+// out of Montgomery form, as canonical integers — little-endian words, i.e. the 32 canonical bytes of each.
+template <bool kSmall> __global__ __launch_bounds__(kBlock) void k_sat_report(DCsr3 m, const uint32_t *row_ids, const Fr *x, Fr *out) {
+    const size_t r = row_ids[blockIdx.x];
+    Fr acc[3];
+    for (int k = 0; k < 3; k++) {
+        acc[k] = fr_zero();
+        const uint32_t p1 = m.ptr[k][r + 1];
+        for (uint32_t p = m.ptr[k][r] + threadIdx.x; p < p1; p += blockDim.x) acc[k] = fr_add(acc[k], entry_term<kSmall>(m, k, p, x));
+    }
+    block_reduce<3>(acc);
+    if (threadIdx.x == 0) for (int k = 0; k < 3; k++) out[(size_t)blockIdx.x * 3 + k] = fr_to_raw(acc[k]);
+}
+void dev_sat_pass(DevCtx &c, const DeviceCsrSet &m, const Fr *z, unsigned long long *bits) {
+    unsigned long long *count = c.d_counts.p;
+    OTTI_HIP(hipMemsetAsync(count, 0, sizeof(unsigned long long), c.stream));
+    KScope ks(c, KC_SAT_CHECK);
+    const bool quad = m.avg_row >= 3.0, sm = m.use_small;      // the layouts dev_spmv3 picks, for its reasons
+    if (quad && sm) hipLaunchKernelGGL(k_sat_quad<true>, grid_for(4 * m.rows), kBlock, 0, c.stream, m.view(), m.rows, z, bits, count);
+    else if (quad) hipLaunchKernelGGL(k_sat_quad<false>, grid_for(4 * m.rows), kBlock, 0, c.stream, m.view(), m.rows, z, bits, count);
+    else if (sm) hipLaunchKernelGGL(k_sat_light<true>, grid_for(m.rows), kBlock, 0, c.stream, m.view(), m.rows, z, bits, count);
+    else hipLaunchKernelGGL(k_sat_light<false>, grid_for(m.rows), kBlock, 0, c.stream, m.view(), m.rows, z, bits, count);
+    if (m.n_heavy) {
+        if (c.spmv_partial.n < 3 * m.n_seg) { OTTI_HIP(hipStreamSynchronize(c.stream)); c.spmv_partial.alloc(3 * m.n_seg); }
+        if (sm) hipLaunchKernelGGL(k_spmv3_heavy_seg<true>, (unsigned)m.n_seg, kBlock, 0, c.stream, m.view(), (const uint32_t *)m.seg_row.p, (const uint32_t *)m.seg_no.p, z, c.spmv_partial.p);
+        else hipLaunchKernelGGL(k_spmv3_heavy_seg<false>, (unsigned)m.n_seg, kBlock, 0, c.stream, m.view(), (const uint32_t *)m.seg_row.p, (const uint32_t *)m.seg_no.p, z, c.spmv_partial.p);
+        hipLaunchKernelGGL(k_sat_heavy_check, (unsigned)m.n_heavy, kBlock, 0, c.stream, (const uint32_t *)m.heavy.p, (const uint32_t *)m.seg_begin.p, (const Fr *)c.spmv_partial.p, bits, count);
+    }
+}
+uint64_t dev_sat_count(DevCtx &c) {
+    unsigned long long *h = reinterpret_cast<unsigned long long *>(&c.h_results[kSatCountSlot]);
+    OTTI_HIP(hipMemcpyAsync(h, c.d_counts.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, c.stream));
+    OTTI_HIP(hipStreamSynchronize(c.stream));
+    return (uint64_t)*h;
+}
+SatReport dev_check_sat(DevCtx &c, DeviceInstance &d, const Fr *z, size_t max_rows, bool with_values) {
+    const DeviceCsrSet &m = d.by_row;
+    const size_t words = (m.rows + 63) >> 6;
+    if (c.sat_bits.n < words) { OTTI_HIP(hipStreamSynchronize(c.stream)); c.sat_bits.alloc(words); }
+    SatReport rep;
+    OTTI_HIP(hipEventRecord(c.ev0, c.stream));
+    dev_sat_pass(c, m, z, c.sat_bits.p);
+    OTTI_HIP(hipEventRecord(c.ev1, c.stream));
+    rep.n_unsat = dev_sat_count(c);
+    OTTI_HIP(hipEventElapsedTime(&rep.kernel_ms, c.ev0, c.ev1));
+    const size_t k = (size_t)std::min<uint64_t>(rep.n_unsat, max_rows);
+    if (!k) return rep;
+    std::vector<unsigned long long> bits(words);
+    OTTI_HIP(hipMemcpy(bits.data(), c.sat_bits.p, words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    rep.rows.reserve(k);
+    for (size_t w = 0; w < words && rep.rows.size() < k; w++)
+        for (unsigned long long v = bits[w]; v && rep.rows.size() < k; v &= v - 1) {
+            const size_t r = (w << 6) + (size_t)__builtin_ctzll(v);
+            if (r < m.rows) rep.rows.push_back((uint64_t)r);
+        }
+    if (!with_values) return rep;
+    if (c.sat_rows.n < kSatReportRows) { c.sat_rows.alloc(kSatReportRows); c.sat_abc.alloc(3 * kSatReportRows); }
+    rep.abc96.resize(96 * rep.rows.size());
+    uint32_t ids[kSatReportRows];
+    for (size_t i0 = 0; i0 < rep.rows.size(); i0 += kSatReportRows) {
+        const size_t n = std::min(kSatReportRows, rep.rows.size() - i0);
+        for (size_t i = 0; i < n; i++) ids[i] = (uint32_t)rep.rows[i0 + i];
+        OTTI_HIP(hipMemcpyAsync(c.sat_rows.p, ids, n * sizeof(uint32_t), hipMemcpyHostToDevice, c.stream));
+        if (m.use_small) hipLaunchKernelGGL(k_sat_report<true>, (unsigned)n, kBlock, 0, c.stream, m.view(), (const uint32_t *)c.sat_rows.p, z, c.sat_abc.p);
+        else hipLaunchKernelGGL(k_sat_report<false>, (unsigned)n, kBlock, 0, c.stream, m.view(), (const uint32_t *)c.sat_rows.p, z, c.sat_abc.p);
+        OTTI_HIP(hipMemcpyAsync(rep.abc96.data() + 96 * i0, c.sat_abc.p, 96 * n, hipMemcpyDeviceToHost, c.stream));
+        OTTI_HIP(hipStreamSynchronize(c.stream));              // `ids` and the device buffers are reused by the next batch
+    }
+    return rep;
+}
+
 // ------------------------------------------------------------------------------------------------ CSR copies, built on the device
 // The host keeps the matrices as entry lists in caller order (upstream's Vec<SparseMatEntry>); the two access paths the kernels want
 // (by row for multiply_vec, by column for compute_eval_table_sparse) are counting sorts made here from ONE upload of the lists:

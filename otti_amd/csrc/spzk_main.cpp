@@ -5,7 +5,8 @@
 // Without --nizk the same files go through SNARK mode (upstream spartan-zkinterface's default [RECALL]): SNARK::encode commits to the
 // circuit, SNARK::prove adds the R1CSEvalProof, SNARK::verify checks it against the commitment alone.
 // Additive options: --seed <hex32>, --proof-out <file>, --label <transcript label>, `spzk synth <n> <prefix>` to emit a
-// synthetic zkif triple.
+// synthetic zkif triple; `spzk check` and --check: does the assignment satisfy the circuit, and if not, which constraints fail
+// (otti_witness_check_sat: on the device, on the uploaded assignment; no generators are made for `check`).
 #include <stdio.h>
 #include <thread>
 #include <time.h>
@@ -26,10 +27,13 @@ static int fail(const char *what, int rc) {
     return 1;
 }
 static int usage() {
-    fprintf(stderr, "usage: spzk verify [--nizk] <circuit.zkif> <inputs.inp.zkif> <witness.wit.zkif> [--seed HEX64] [--proof-out FILE] [--label STR]\n"
+    fprintf(stderr, "usage: spzk verify [--nizk] <circuit.zkif> <inputs.inp.zkif> <witness.wit.zkif> [--seed HEX64] [--proof-out FILE] [--label STR] [--check]\n"
                     "            (the reference's invocation: prove, then verify, in one process; without --nizk: SNARK mode)\n"
-                    "       spzk prove  --nizk <circuit.zkif> <inputs.inp.zkif> <witness.wit.zkif> --proof-out FILE [--seed HEX64] [--label STR]\n"
+                    "       spzk prove  --nizk <circuit.zkif> <inputs.inp.zkif> <witness.wit.zkif> --proof-out FILE [--seed HEX64] [--label STR] [--check]\n"
                     "       spzk verify --nizk <circuit.zkif> <inputs.inp.zkif> --proof-in FILE [--label STR]\n"
+                    "       spzk check [--nizk] <circuit.zkif> <inputs.inp.zkif> <witness.wit.zkif>\n"
+                    "            (does the assignment satisfy the circuit? exit 0: yes; 1: no, with the failing constraints; no proof is made)\n"
+                    "            --check: the same test after the upload, before proving; an unsatisfied assignment is reported and not proved\n"
                     "       spzk synth <num_constraints> <out_prefix> [num_inputs] [seed]\n");
     return 2;
 }
@@ -47,6 +51,24 @@ static double ms_since_process_start() {
     return (ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6) - 1e3 * (double)start / (double)sysconf(_SC_CLK_TCK);
 }
 
+// The satisfiability check on the uploaded assignment.  0: satisfied; 1: not (the report is printed); -1: the call itself failed (reported).
+constexpr size_t kCheckRows = 16;                              // failing constraints listed at most
+static void print_hex32(const uint8_t *le) { for (int i = 31; i >= 0; i--) printf("%02x", le[i]); }   // canonical value, most significant digit first
+static int run_check(otti_instance *inst, otti_witness *wit, uint64_t num_cons) {
+    uint64_t n_unsat = 0, rows[kCheckRows]; uint8_t abc[96 * kCheckRows]; float kernel_ms = 0;
+    const double t0 = now_ms();
+    const int rc = otti_witness_check_sat(inst, wit, &n_unsat, rows, kCheckRows, abc, &kernel_ms);
+    if (rc) { fail("check_sat", rc); return -1; }
+    printf("* check_sat %.3f ms\n  * kernel %.3f ms\n", now_ms() - t0, kernel_ms);
+    if (!n_unsat) return 0;
+    printf("Unsatisfied: %llu of %llu constraints\n", (unsigned long long)n_unsat, (unsigned long long)num_cons);
+    for (size_t i = 0; i < kCheckRows && i < n_unsat; i++) {
+        printf("  constraint %llu: A.z=", (unsigned long long)rows[i]); print_hex32(abc + 96 * i);
+        printf(" B.z="); print_hex32(abc + 96 * i + 32); printf(" C.z="); print_hex32(abc + 96 * i + 64); printf("\n");
+    }
+    return 1;
+}
+
 int main(int argc, char **argv) {
     const double t_before_main = ms_since_process_start(), t_main0 = now_ms();
     if (argc < 2) return usage();
@@ -60,14 +82,15 @@ int main(int argc, char **argv) {
         printf("wrote %s.zkif %s.inp.zkif %s.wit.zkif (%llu constraints)\n", p.c_str(), p.c_str(), p.c_str(), (unsigned long long)n);
         return 0;
     }
-    const bool prove_only = !strcmp(argv[1], "prove");
-    if (!prove_only && strcmp(argv[1], "verify")) return usage();
+    const bool prove_only = !strcmp(argv[1], "prove"), check_only = !strcmp(argv[1], "check");
+    if (!prove_only && !check_only && strcmp(argv[1], "verify")) return usage();
     // one proof per process: the generator window table is built and used once, so a narrow window (small table, ~7 ms to build for
     // R = 1024) beats the wide one a long-lived prover process amortises (see prover.cpp device_window_bits); an explicit setting wins
     setenv("OTTI_MSM_WINDOW", "10", 0);
-    bool nizk = false, label_given = false; std::vector<const char *> files; const char *seed_hex = nullptr, *proof_out = nullptr, *proof_in = nullptr, *label = "nizk_example";
+    bool nizk = false, label_given = false, check = false; std::vector<const char *> files; const char *seed_hex = nullptr, *proof_out = nullptr, *proof_in = nullptr, *label = "nizk_example";
     for (int i = 2; i < argc; i++) {
         if (!strcmp(argv[i], "--nizk")) nizk = true;
+        else if (!strcmp(argv[i], "--check")) check = true;
         else if (!strcmp(argv[i], "--seed") && i + 1 < argc) seed_hex = argv[++i];
         else if (!strcmp(argv[i], "--proof-out") && i + 1 < argc) proof_out = argv[++i];
         else if (!strcmp(argv[i], "--proof-in") && i + 1 < argc) proof_in = argv[++i];
@@ -75,6 +98,20 @@ int main(int argc, char **argv) {
         else files.push_back(argv[i]);
     }
     const bool verify_only = proof_in != nullptr;
+    if (check_only) {                                          // load, Instance::new, upload, check: no generators, no window table
+        if (files.size() != 3 || verify_only || proof_out) return usage();
+        otti_r1cs *r = nullptr; int rc = otti_zkif_load(files[0], files[1], files[2], &r); if (rc) return fail("zkif load", rc);
+        otti_instance *inst = nullptr;
+        rc = otti_instance_new(r->num_cons, r->num_vars, r->num_inputs, r->A, r->nA, r->B, r->nB, r->C, r->nC, &inst); if (rc) return fail("Instance::new", rc);
+        rc = otti_prepare_device(inst, nullptr); if (rc) return fail("device setup", rc);
+        otti_witness *wit = nullptr;
+        rc = otti_witness_upload(inst, r->vars32, r->nvars, r->inputs32, r->ninputs, &wit); if (rc) return fail("witness upload", rc);
+        const int sat = run_check(inst, wit, r->num_cons);
+        if (sat == 0) printf("Satisfied\n");
+        fflush(stdout);
+        _exit(sat == 0 ? 0 : 1);                               // as below: skip the HIP runtime's teardown
+    }
+    if (check && verify_only) return usage();                  // a separate verifier has no witness to check
     if (!nizk && (prove_only || verify_only)) { fprintf(stderr, "spzk: separate prove / verify processes are offered in --nizk mode only\n"); return 2; }
     if (!nizk && !label_given) label = "snark_example";
     if (prove_only && (verify_only || !proof_out)) return usage();
@@ -99,6 +136,14 @@ int main(int argc, char **argv) {
     struct GensJoiner { std::thread &t; ~GensJoiner() { if (t.joinable()) t.join(); } } gens_joiner{gens_thread};
     otti_instance *inst = nullptr;
     rc = otti_instance_new(r->num_cons, r->num_vars, r->num_inputs, r->A, r->nA, r->B, r->nB, r->C, r->nC, &inst); if (rc) return fail("Instance::new", rc);
+    otti_witness *wit = nullptr;                               // --check: the assignment is uploaded once, checked, and proved from HBM
+    if (check) {
+        rc = otti_prepare_device(inst, nullptr); if (rc) return fail("device setup", rc);
+        rc = otti_witness_upload(inst, r->vars32, r->nvars, r->inputs32, r->ninputs, &wit); if (rc) return fail("witness upload", rc);
+        const int sat = run_check(inst, wit, r->num_cons);
+        if (sat < 0) return 1;
+        if (sat) { printf("Verification FAILED (unsatisfied assignment)\n"); return 1; }
+    }
     if (!nizk) {                                               // ---- SNARK mode: encode, prove, verify
         const uint64_t nnz = std::max<uint64_t>({(uint64_t)r->nA, (uint64_t)r->nB, (uint64_t)r->nC});
         otti_snark_gens *sg = nullptr; rc = otti_snark_gens_new(r->num_cons, r->num_vars, r->num_inputs, nnz, &sg); if (rc) return fail("SNARKGens::new", rc);
@@ -106,7 +151,8 @@ int main(int argc, char **argv) {
         otti_comp_comm *cc = nullptr; rc = otti_snark_encode(inst, sg, &cc); if (rc) return fail("SNARK::encode", rc);
         double t_encode = now_ms() - t0; t0 = now_ms();
         uint8_t *proof = nullptr; size_t proof_len = 0; double st[10] = {0};
-        rc = otti_snark_prove(inst, cc, r->vars32, r->nvars, r->inputs32, r->ninputs, sg, (const uint8_t *)label, strlen(label), seedp, OTTI_FLAG_GPU, &proof, &proof_len, st);
+        if (wit) rc = otti_snark_prove_resident(inst, cc, wit, sg, (const uint8_t *)label, strlen(label), seedp, &proof, &proof_len, st);
+        else rc = otti_snark_prove(inst, cc, r->vars32, r->nvars, r->inputs32, r->ninputs, sg, (const uint8_t *)label, strlen(label), seedp, OTTI_FLAG_GPU, &proof, &proof_len, st);
         if (rc) return fail("SNARK::prove", rc);
         double t_prove = now_ms() - t0; t0 = now_ms();
         // the verifier's copy of the commitment: its bytes only
@@ -144,8 +190,9 @@ int main(int argc, char **argv) {
         if (fread(proof, 1, proof_len, f) != proof_len) { fclose(f); fprintf(stderr, "spzk: short read on %s\n", proof_in); return 1; }
         fclose(f);
     } else {
-        rc = otti_nizk_prove(inst, r->vars32, r->nvars, r->inputs32, r->ninputs, gens, (const uint8_t *)label, strlen(label), seedp, OTTI_FLAG_GPU, &proof,
-                             &proof_len, st);
+        if (wit) rc = otti_nizk_prove_resident(inst, wit, gens, (const uint8_t *)label, strlen(label), seedp, &proof, &proof_len, st);
+        else rc = otti_nizk_prove(inst, r->vars32, r->nvars, r->inputs32, r->ninputs, gens, (const uint8_t *)label, strlen(label), seedp, OTTI_FLAG_GPU, &proof,
+                                  &proof_len, st);
         if (rc) return fail("NIZK::prove", rc);
         t_prove = now_ms() - t0; t0 = now_ms();
     }
