@@ -67,6 +67,10 @@ static int SNARKGens_new(size_t nc, size_t nv, size_t ni, size_t num_nz_entries,
 /* let (comm, decomm) = SNARK::encode(&inst, &gens); */
 static int SNARK_encode(const Instance *I, const SNARKGens *g, ComputationCommitment *out) { return otti_snark_encode(I->h, g->h, &out->h); }
 static int ComputationCommitment_from_bytes(const uint8_t *b, size_t n, ComputationCommitment *out) { return otti_comp_comm_from_bytes(b, n, &out->h); }
+/* the prover's copy of a stored commitment: the decommitment rebuilt from the instance on the device (verify: commitments recomputed and compared) */
+static int ComputationCommitment_attach(ComputationCommitment *c, const Instance *I, const SNARKGens *g, int verify) { return otti_comp_comm_attach(c->h, I->h, g->h, verify ? OTTI_ATTACH_VERIFY : 0u); }
+/* the sizes a verifier makes its SNARKGens from: SNARKGens_new(dims[0], dims[1], dims[2], dims[3], ..) */
+static int ComputationCommitment_dims(const ComputationCommitment *c, uint64_t dims[4], int32_t *has_decommitment) { return otti_comp_comm_dims(c->h, &dims[0], &dims[1], &dims[2], &dims[3], has_decommitment); }
 /* SNARK::prove(&inst, &comm, &decomm, vars, &inputs, &gens, &mut Transcript::new(label)) */
 static int SNARK_prove(const Instance *I, const ComputationCommitment *comm, const Assignment *vars, const Assignment *inputs, const SNARKGens *g, const char *label,
                        const uint8_t *seed32, SNARK *out) {
@@ -122,6 +126,24 @@ static int snark_main(int argc, char **argv) {
     CHECK(ComputationCommitment_from_bytes(comm_bytes.bytes, comm_bytes.len, &verifier_comm) == 0, "ComputationCommitment from bytes");
     CHECK(SNARK_verify(&proof, &verifier_comm, &inputs, label, &gens) == VERIFY_OK, "SNARK::verify");
     CHECK(SNARK_verify(&proof, &verifier_comm, &inputs, "another label", &gens) != VERIFY_OK, "a different transcript label must not verify");
+    {   /* a verifier needs no circuit for its generators: the commitment's dimensions give the encoder's */
+        uint64_t dims[4]; int32_t has = 1; SNARKGens vg;
+        CHECK(ComputationCommitment_dims(&verifier_comm, dims, &has) == 0 && !has && dims[3] >= nz && dims[3] < 2 * (nz > 1 ? nz : 2), "dimensions of a parsed commitment");
+        CHECK(SNARKGens_new(dims[0], dims[1], dims[2], dims[3], &vg) == 0, "SNARKGens::new from the commitment's dimensions");
+        CHECK(SNARK_verify(&proof, &verifier_comm, &inputs, label, &vg) == VERIFY_OK, "SNARK::verify with generators made from the commitment alone");
+        otti_snark_gens_free(vg.h);
+    }
+    {   /* the prover's copy of a stored commitment: attach rebuilds the decommitment (device needed), after which it proves the same bytes */
+        const int rc = ComputationCommitment_attach(&verifier_comm, &inst, &gens, 1);
+        if (otti_device_count() == 0) CHECK(rc == OTTI_ERR_NO_DEVICE, "attach without a device must return OTTI_ERR_NO_DEVICE");
+        else {
+            SNARK again = {0, 0};
+            CHECK(rc == 0, "ComputationCommitment attach");
+            CHECK(SNARK_prove(&inst, &verifier_comm, &vars, &inputs, &gens, label, seed, &again) == 0, "SNARK::prove from an attached commitment");
+            CHECK(again.len == proof.len && !memcmp(again.bytes, proof.bytes, proof.len), "the attached commitment must give the encoder's proof");
+            otti_buf_free(again.bytes);
+        }
+    }
     {
         SNARK t = {malloc(proof.len), proof.len}; memcpy(t.bytes, proof.bytes, proof.len);
         t.bytes[(2 * proof.len) / 3] ^= 0x40;

@@ -37,6 +37,8 @@ extern "C" {
     fn otti_comp_comm_bytes(comm: *const OttiCompComm, out: *mut *mut u8, len: *mut usize) -> i32;
     fn otti_comp_comm_from_bytes(buf: *const u8, len: usize, out: *mut *mut OttiCompComm) -> i32;
     fn otti_comp_comm_free(comm: *mut OttiCompComm);
+    fn otti_comp_comm_attach(comm: *mut OttiCompComm, inst: *mut OttiInstance, gens: *mut OttiSnarkGens, flags: u32) -> i32;
+    fn otti_comp_comm_dims(comm: *const OttiCompComm, num_cons: *mut u64, num_vars: *mut u64, num_inputs: *mut u64, num_ops: *mut u64, has_decommitment: *mut i32) -> i32;
     fn otti_snark_prove(inst: *mut OttiInstance, comm: *mut OttiCompComm, vars32: *const u8, nvars: usize, inputs32: *const u8, ninputs: usize,
                         gens: *mut OttiSnarkGens, tlabel: *const u8, tlabel_len: usize, seed32: *const u8, flags: u32, proof: *mut *mut u8,
                         proof_len: *mut usize, stage_ms: *mut f64) -> i32;
@@ -209,10 +211,23 @@ impl ComputationCommitment {
         unsafe { otti_buf_free(p as *mut c_void) };
         v
     }
-    /// the verifier's copy (no decommitment: `SNARK::prove` refuses it)
+    /// the verifier's copy (no decommitment: `SNARK::prove` refuses it until `attach` has completed it)
     pub fn from_bytes(bytes: &[u8]) -> Option<ComputationCommitment> {
         let mut h = ptr::null_mut();
         if unsafe { otti_comp_comm_from_bytes(bytes.as_ptr(), bytes.len(), &mut h) } == 0 { Some(ComputationCommitment { h }) } else { None }
+    }
+    /// the prover's copy of a stored commitment: rebuilds the decommitment of `inst` on the device; `verify` recomputes both commitments
+    /// and compares them with the stored points first (OTTI_ATTACH_VERIFY).  Err: the library's status code
+    pub fn attach(&mut self, inst: &Instance, gens: &SNARKGens, verify: bool) -> Result<(), i32> {
+        let rc = unsafe { otti_comp_comm_attach(self.h, inst.h, gens.h, if verify { 1 } else { 0 }) };
+        if rc == 0 { Ok(()) } else { Err(rc) }
+    }
+    /// (num_cons, num_vars, num_inputs, num_ops) — `SNARKGens::new` of these gives the encoder's generators — and whether a decommitment is attached
+    pub fn dims(&self) -> ((usize, usize, usize, usize), bool) {
+        let (mut nc, mut nv, mut ni, mut no, mut has) = (0u64, 0u64, 0u64, 0u64, 0i32);
+        let rc = unsafe { otti_comp_comm_dims(self.h, &mut nc, &mut nv, &mut ni, &mut no, &mut has) };
+        assert_eq!(rc, 0, "otti_comp_comm_dims: {}", last_error());
+        ((nc as usize, nv as usize, ni as usize, no as usize), has != 0)
     }
 }
 

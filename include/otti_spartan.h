@@ -139,7 +139,27 @@ int32_t otti_snark_gens_new(uint64_t num_cons, uint64_t num_vars, uint64_t num_i
 void    otti_snark_gens_free(otti_snark_gens *gens);
 int32_t otti_snark_encode(otti_instance *inst, otti_snark_gens *gens, otti_comp_comm **out);
 int32_t otti_comp_comm_bytes(const otti_comp_comm *comm, uint8_t **out, size_t *len);        /* bincode of the commitment; free with otti_buf_free */
-int32_t otti_comp_comm_from_bytes(const uint8_t *buf, size_t len, otti_comp_comm **out);     /* the verifier's copy (no decommitment) */
+/* A commitment read back from bytes is the verifier's copy: it carries no decommitment.  A prover process that did not run otti_snark_encode
+   itself completes its copy with otti_comp_comm_attach below (the decommitment is never stored: rebuilding it from the instance is a few
+   device passes, no commitment MSM). */
+int32_t otti_comp_comm_from_bytes(const uint8_t *buf, size_t len, otti_comp_comm **out);
+/* Rebuilds the decommitment of `inst` on the device and hangs it on `comm`, after which otti_snark_prove* accept it.
+   flags 0: trust the caller — only the dimensions (num_cons, num_vars, num_inputs, num_ops, num_mem_cells) are compared, OTTI_ERR_BAD_ARG on a
+   mismatch (reported before any device is touched); an instance of the right dimensions but other content then gives proofs the verifier rejects.
+   OTTI_ATTACH_VERIFY: also recomputes comm_ops and comm_mem and compares them with the stored points; a difference returns
+   OTTI_ERR_BAD_ARG (the message names the commitment) and leaves `comm` without decommitment.
+   A commitment that already has its decommitment: OTTI_OK, nothing done.  No device: OTTI_ERR_NO_DEVICE.  One GPU: a sharded prover attaches
+   on every rank, each on its own device. */
+#define OTTI_ATTACH_VERIFY 0x1u
+int32_t otti_comp_comm_attach(otti_comp_comm *comm, otti_instance *inst, otti_snark_gens *gens, uint32_t flags);
+/* The sizes a commitment was made for (any out pointer may be NULL).  A verifier builds its generators from these alone:
+   otti_snark_gens_new(num_cons, num_vars, num_inputs, num_ops, ..) gives the encoder's generators (they depend on log2 of num_ops only,
+   and num_ops = next_pow2 of the encoder's num_nz_entries). */
+int32_t otti_comp_comm_dims(const otti_comp_comm *comm, uint64_t *num_cons, uint64_t *num_vars, uint64_t *num_inputs, uint64_t *num_ops,
+                            int32_t *has_decommitment);
+/* the generator streams as compressed points: which = 0 gens_r1cs_sat, 1 gens_r1cs_eval.  *count receives the stream's length; out32 (room for
+   cap points) may be NULL to ask for the length alone */
+int32_t otti_snark_gens_points(const otti_snark_gens *gens, int32_t which, uint8_t *out32, size_t cap, size_t *count);
 void    otti_comp_comm_free(otti_comp_comm *comm);
 int32_t otti_snark_prove(otti_instance *inst, otti_comp_comm *comm, const uint8_t *vars32, size_t nvars, const uint8_t *inputs32, size_t ninputs,
                          otti_snark_gens *gens, const uint8_t *tlabel, size_t tlabel_len, const uint8_t *seed32, uint32_t flags,
@@ -196,6 +216,9 @@ typedef struct {
     uint8_t *inputs32; size_t ninputs;     /* instance (public input) assignment */
 } otti_r1cs;
 int32_t otti_zkif_load(const char *circuit_path, const char *inputs_path, const char *witness_path, otti_r1cs **out);
+/* the public inputs alone, from the .inp.zkif file (a SNARK verifier that holds the computation commitment has no circuit file): only
+   num_inputs, inputs32 and ninputs are filled */
+int32_t otti_zkif_load_inputs(const char *inputs_path, otti_r1cs **out);
 /* writes the three-file split the reference compiler produces [REF run.py:47-49] from an R1CS in z-order [vars | 1 | inputs] */
 int32_t otti_zkif_write(const otti_r1cs *r, const char *circuit_path, const char *inputs_path, const char *witness_path);
 void    otti_r1cs_free(otti_r1cs *r);
@@ -210,6 +233,9 @@ int32_t otti_synth_r1cs_compiler_like(uint64_t n, uint64_t num_inputs, uint64_t 
         kernel_ms (optional) receives the HIP-event time of the kernel launches alone. ---- */
 /* Fr/Fp/point self-test kernels: out[i] = a[i] * b[i] etc.  op: 0 mul, 1 add, 2 sub */
 int32_t otti_k_fr_op(int32_t op, const uint8_t *h_a, const uint8_t *h_b, uint8_t *h_out, size_t n, float *kernel_ms);
+/* sparse_mlpoly.rs AddrTimestamps::new for one side of the dense representation: h_addr3 = three lists of N addresses below M (k-major); walking them
+   in order over one shared counter array, h_read_ts3[k * N + i] = audit[addr]++ and h_audit[0 .. M) = the counts at the end */
+int32_t otti_k_addr_timestamps(const uint32_t *h_addr3, size_t N, size_t M, uint32_t *h_read_ts3, uint32_t *h_audit, float *kernel_ms);
 /* canonical LE <-> Montgomery on the device */
 int32_t otti_k_fr_from_canonical(const uint8_t *h_in, uint8_t *h_out, size_t n);
 int32_t otti_k_fr_to_canonical(const uint8_t *h_in, uint8_t *h_out, size_t n);

@@ -98,6 +98,9 @@ _sig("otti_snark_encode", _i32, _vp, _vp, ctypes.POINTER(_vp))
 _sig("otti_comp_comm_bytes", _i32, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_sz))
 _sig("otti_comp_comm_from_bytes", _i32, _vp, _sz, ctypes.POINTER(_vp))
 _sig("otti_comp_comm_free", None, _vp)
+_sig("otti_comp_comm_attach", _i32, _vp, _vp, _vp, ctypes.c_uint32)
+_sig("otti_comp_comm_dims", _i32, _vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_i32))
+_sig("otti_snark_gens_points", _i32, _vp, _i32, _vp, _sz, ctypes.POINTER(_sz))
 _sig("otti_snark_prove", _i32, _vp, _vp, _vp, _sz, _vp, _sz, _vp, ctypes.c_char_p, _sz, _vp, ctypes.c_uint32,
      ctypes.POINTER(_vp), ctypes.POINTER(_sz), ctypes.POINTER(ctypes.c_double))
 _sig("otti_snark_prove_resident", _i32, _vp, _vp, _vp, _vp, ctypes.c_char_p, _sz, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_sz), ctypes.POINTER(ctypes.c_double))
@@ -121,6 +124,7 @@ _sig("otti_lanes_unpack", None, _vp, _sz, _vp)
 _fp = ctypes.POINTER(ctypes.c_float)
 _sig("otti_k_fr_op", _i32, _i32, _vp, _vp, _vp, _sz, _fp)
 _sig("otti_k_fr_from_canonical", _i32, _vp, _vp, _sz)
+_sig("otti_k_addr_timestamps", _i32, _vp, _sz, _sz, _vp, _vp, _fp)
 _sig("otti_k_fr_to_canonical", _i32, _vp, _vp, _sz)
 _sig("otti_k_multiply_vec", _i32, _vp, _vp, _vp, _vp, _vp, _fp)
 _sig("otti_k_eval_table_sparse", _i32, _vp, _vp, _vp, _vp, _fp)
@@ -455,6 +459,14 @@ class SNARKGens:
         _check(lib.otti_snark_gens_new(num_cons, num_vars, num_inputs, num_nz_entries, ctypes.byref(h)))
         return cls(h)
 
+    def points(self, which):
+        """the generator stream "sat" (gens_r1cs_sat) or "eval" (gens_r1cs_eval) as an (n, 32) array of compressed points"""
+        w, n = {"sat": 0, "eval": 1}[which], _sz()
+        _check(lib.otti_snark_gens_points(self._h, w, None, 0, ctypes.byref(n)))
+        out = np.zeros((n.value, 32), dtype=np.uint8)
+        _check(lib.otti_snark_gens_points(self._h, w, _ptr(out), n.value, ctypes.byref(n)))
+        return out
+
     def __del__(self):
         if getattr(self, "_h", None):
             lib.otti_snark_gens_free(self._h)
@@ -462,7 +474,8 @@ class SNARKGens:
 
 
 class ComputationCommitment:
-    """SNARK::encode(&inst, &gens) -> (ComputationCommitment, ComputationDecommitment); `from_bytes` gives the verifier's copy"""
+    """SNARK::encode(&inst, &gens) -> (ComputationCommitment, ComputationDecommitment); `from_bytes` gives the verifier's copy, which
+    `attach` completes into a prover's copy (the decommitment is rebuilt from the instance on the device, never stored)"""
 
     def __init__(self, handle):
         self._h = handle
@@ -485,6 +498,26 @@ class ComputationCommitment:
         p, n = _vp(), _sz()
         _check(lib.otti_comp_comm_bytes(self._h, ctypes.byref(p), ctypes.byref(n)))
         return NIZK._take(p, n)
+
+    def attach(self, inst, gens, verify=False):
+        """Rebuild the decommitment of ``inst`` on the device.  ``verify``: also recompute both commitments and compare them with the
+        stored points (raises SpartanError, code -21, on a difference); without it the caller is trusted beyond the dimensions."""
+        _check(lib.otti_comp_comm_attach(self._h, inst._h, gens._h, 1 if verify else 0))
+        return self
+
+    def _dims(self):
+        nc, nv, ni, no, has = _u64(), _u64(), _u64(), _u64(), _i32()
+        _check(lib.otti_comp_comm_dims(self._h, ctypes.byref(nc), ctypes.byref(nv), ctypes.byref(ni), ctypes.byref(no), ctypes.byref(has)))
+        return (nc.value, nv.value, ni.value, no.value), bool(has.value)
+
+    @property
+    def dims(self):
+        """(num_cons, num_vars, num_inputs, num_ops): SNARKGens.new(*dims) gives the encoder's generators"""
+        return self._dims()[0]
+
+    @property
+    def has_decommitment(self):
+        return self._dims()[1]
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -704,6 +737,16 @@ class kernels:
         out, ms = np.zeros_like(a), ctypes.c_float(0)
         _check(lib.otti_k_fr_op({"mul": 0, "add": 1, "sub": 2}[op], _ptr(a), _ptr(b), _ptr(out), a.shape[0], ctypes.byref(ms)))
         return out, ms.value
+
+    @staticmethod
+    def addr_timestamps(addr3, M):
+        """addr3: (3, N) uint32 addresses below M.  Returns (read_ts (3, N) uint32, audit (M,) uint32, kernel ms)"""
+        a = np.ascontiguousarray(addr3, dtype=np.uint32)
+        if a.ndim != 2 or a.shape[0] != 3:
+            raise ValueError("addr3: expected a (3, N) uint32 array")
+        ts, audit, ms = np.zeros_like(a), np.zeros(int(M), dtype=np.uint32), ctypes.c_float(0)
+        _check(lib.otti_k_addr_timestamps(_ptr(a), a.shape[1], int(M), _ptr(ts), _ptr(audit), ctypes.byref(ms)))
+        return ts, audit, ms.value
 
     @staticmethod
     def from_canonical(a):

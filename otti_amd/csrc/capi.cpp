@@ -2,6 +2,7 @@
 #include "device.h"
 #include "shard.h"
 #include "snark.h"
+#include "snark_dev.h"
 #include "hosttail.h"
 #include "hostifma.h"
 #include <array>
@@ -22,6 +23,7 @@ otti_r1cs *otti_r1cs_from(size_t nc, size_t nv, size_t ni, const std::vector<ott
                           const std::vector<otti_entry> &C, const std::vector<uint8_t> &vars, const std::vector<uint8_t> &inputs);
 otti_r1cs *zkif_load_impl(const char *circuit_path, const char *inputs_path, const char *witness_path);
 void zkif_write_impl(const otti_r1cs *r, const char *circuit_path, const char *inputs_path, const char *witness_path);
+otti_r1cs *zkif_load_inputs_impl(const char *inputs_path);
 
 static thread_local std::string g_last_error;
 template <class F> static int32_t guarded(F &&f) {
@@ -508,6 +510,34 @@ int32_t otti_comp_comm_from_bytes(const uint8_t *buf, size_t len, otti_comp_comm
     });
 }
 void otti_comp_comm_free(otti_comp_comm *p) { delete p; }
+int32_t otti_comp_comm_attach(otti_comp_comm *comm, otti_instance *inst, otti_snark_gens *gens, uint32_t flags) {
+    return guarded([&] {
+        if (!comm || !inst || !gens) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (flags & ~(uint32_t)OTTI_ATTACH_VERIFY) throw Error(OTTI_ERR_BAD_ARG, "unknown attach flag");
+        snark_attach_gpu(*inst->I, *comm->c, *gens->g, (flags & OTTI_ATTACH_VERIFY) != 0); return OTTI_OK;
+    });
+}
+int32_t otti_comp_comm_dims(const otti_comp_comm *comm, uint64_t *num_cons, uint64_t *num_vars, uint64_t *num_inputs, uint64_t *num_ops, int32_t *has_decommitment) {
+    return guarded([&] {
+        if (!comm) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        const CompComm &c = *comm->c;
+        if (num_cons) *num_cons = c.num_cons;
+        if (num_vars) *num_vars = c.num_vars;
+        if (num_inputs) *num_inputs = c.num_inputs;
+        if (num_ops) *num_ops = c.num_ops;
+        if (has_decommitment) *has_decommitment = c.dec ? 1 : 0;
+        return OTTI_OK;
+    });
+}
+int32_t otti_snark_gens_points(const otti_snark_gens *gens, int32_t which, uint8_t *out32, size_t cap, size_t *count) {
+    return guarded([&] {
+        if (!gens || (which != 0 && which != 1)) throw Error(OTTI_ERR_BAD_ARG, "null generators, or a stream other than 0 (gens_r1cs_sat) and 1 (gens_r1cs_eval)");
+        const std::vector<Pt> &P = (which ? gens->g->eval : gens->g->sat)->P;
+        if (count) *count = P.size();
+        if (out32) { if (cap < P.size()) throw Error(OTTI_ERR_BAD_ARG, "room for fewer points than the stream has"); for (size_t i = 0; i < P.size(); i++) pt_encode(out32 + 32 * i, P[i]); }
+        return OTTI_OK;
+    });
+}
 int32_t otti_snark_prove(otti_instance *inst, otti_comp_comm *comm, const uint8_t *vars32, size_t nvars, const uint8_t *inputs32, size_t ninputs, otti_snark_gens *gens,
                          const uint8_t *tlabel, size_t tlabel_len, const uint8_t *seed32, uint32_t flags, uint8_t **proof, size_t *proof_len, double *stage_ms) {
     return guarded([&] {
@@ -558,6 +588,9 @@ int32_t otti_snark_verify(const otti_comp_comm *comm, const uint8_t *inputs32, s
 int32_t otti_zkif_load(const char *c, const char *i, const char *w, otti_r1cs **out) {
     return guarded([&] { if (!c || !out) throw Error(OTTI_ERR_BAD_ARG, "null argument"); *out = zkif_load_impl(c, i, w); return OTTI_OK; });
 }
+int32_t otti_zkif_load_inputs(const char *i, otti_r1cs **out) {
+    return guarded([&] { if (!i || !out) throw Error(OTTI_ERR_BAD_ARG, "null argument"); *out = zkif_load_inputs_impl(i); return OTTI_OK; });
+}
 int32_t otti_zkif_write(const otti_r1cs *r, const char *c, const char *i, const char *w) {
     return guarded([&] { if (!r || !c || !i || !w) throw Error(OTTI_ERR_BAD_ARG, "null argument"); zkif_write_impl(r, c, i, w); return OTTI_OK; });
 }
@@ -600,6 +633,23 @@ int32_t otti_k_fr_op(int32_t op, const uint8_t *a, const uint8_t *b, uint8_t *ou
         DevCtx &c = DevCtx::get(); Staged A(c, a, n), B(c, b, n); DevBuf<Fr> O(std::max<size_t>(1, n));
         KTimer t(c, ms); dev_fr_op(c, op, A.d.p, B.d.p, O.p, n); t.stop();
         download(c, out, O.p, n); c.sync(); return OTTI_OK;
+    });
+}
+int32_t otti_k_addr_timestamps(const uint32_t *h_addr3, size_t N, size_t M, uint32_t *h_read_ts3, uint32_t *h_audit, float *ms) {
+    return guarded([&] {
+        if (!h_addr3 || !h_read_ts3 || !h_audit || N < 1 || M < 1 || N > ((size_t)1 << 28) || M > ((size_t)1 << 31)) throw Error(OTTI_ERR_BAD_ARG, "address timestamps: null argument, or N outside 1 .. 2^28, or M outside 1 .. 2^31");
+        AddrTs a; a.sides = 1; a.N = N; a.M = M;
+        for (size_t i = 0; i < 3 * N; i++) if (h_addr3[i] >= M) throw Error(OTTI_ERR_BAD_ARG, "address timestamps: an address is not below M");
+        for (int k = 0; k < 3; k++) { size_t len = N; while (len && h_addr3[k * N + len - 1] == 0) len--; a.len[k] = (uint32_t)len; }   // the closed-form tail: trailing entries at address 0
+        DevCtx &c = DevCtx::get();
+        DevBuf<uint32_t> addr(3 * N), ts(3 * N), audit(M);
+        OTTI_HIP(hipMemcpyAsync(addr.p, h_addr3, 3 * N * 4, hipMemcpyHostToDevice, c.stream));
+        for (int k = 0; k < 3; k++) { a.addr[0][k] = addr.p + k * N; a.ts_u32[0][k] = ts.p + k * N; }
+        a.audit_u32[0] = audit.p;
+        KTimer t(c, ms); dev_addr_timestamps(c, a); t.stop();
+        OTTI_HIP(hipMemcpyAsync(h_read_ts3, ts.p, 3 * N * 4, hipMemcpyDeviceToHost, c.stream));
+        OTTI_HIP(hipMemcpyAsync(h_audit, audit.p, M * 4, hipMemcpyDeviceToHost, c.stream));
+        c.sync(); return OTTI_OK;
     });
 }
 int32_t otti_k_fr_from_canonical(const uint8_t *in, uint8_t *out, size_t n) {

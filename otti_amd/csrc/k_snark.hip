@@ -4,6 +4,7 @@
 // batch (grid.y = instance), so a round of SumcheckInstanceProof::prove_cubic_batched is one launch whatever the batch size.
 //
 // Kernel <-> upstream loop [RECALL; the reference's Spartan/ submodule is empty]:
+//   k_at_*                  sparse_mlpoly.rs AddrTimestamps::new (read_ts, audit_ts: a stable radix sort by address)
 //   k_gather                sparse_mlpoly.rs AddrTimestamps::deref_mem
 //   k_hash_mem / k_hash_ops sparse_mlpoly.rs Layers::build_hash_layer (init / audit, read / write)
 //   k_prod_layer            product_tree.rs ProductCircuit::compute_layer
@@ -30,6 +31,160 @@ __global__ __launch_bounds__(kBlock) void k_u32_to_fr(const uint32_t *in, Fr *ou
 }
 void dev_u32_to_fr(DevCtx &c, const uint32_t *in, Fr *out, size_t n) {
     if (n) hipLaunchKernelGGL(k_u32_to_fr, grid_for(n), kBlock, 0, c.stream, in, out, n);
+}
+
+// ------------------------------------------------------------------------------------------------ timestamps of the dense representation
+// sparse_mlpoly.rs AddrTimestamps::new on the device (snark_dev.h AddrTs): read_ts of an entry = how many entries with the same address come
+// before it in the walk over the three lists, audit_ts = how many there are.  A stable LSD radix sort (8-bit digits) of the entries' walk
+// positions by address makes equal addresses contiguous and keeps the walk order inside them: rank = sorted position - first position of the
+// address.  Every step is a pure function of the lists (the only atomics are a workgroup's LDS digit counts, which commute), so the numbers
+// are the sequential scan's whatever the geometry, and the work is linear in the number of entries whatever their distribution.
+// Only the entries below len[k] are sorted; the padding behind them (address 0) is ranked in closed form (k_at_tail).
+constexpr int kAtItems = 8, kAtTile = kBlock * kAtItems;      // entries of one workgroup's tile: rounds j of kBlock consecutive entries
+struct AtLens { uint32_t off[4], pad_before[4]; };            // off[k]: walk position of matrix k's first sorted entry, off[3] = their number; pad_before[k]: padding entries of the matrices before k, [3] = all
+__device__ __forceinline__ int at_matrix(const AtLens &l, uint32_t g) { return g >= l.off[2] ? 2 : g >= l.off[1] ? 1 : 0; }
+
+__global__ __launch_bounds__(kBlock) void k_at_pack(AddrTs a, AtLens l, uint32_t *keys) {
+    const int side = blockIdx.y; const uint32_t L = l.off[3];
+    for (size_t g = blockIdx.x * (size_t)blockDim.x + threadIdx.x; g < L; g += (size_t)gridDim.x * blockDim.x) {
+        const int k = at_matrix(l, (uint32_t)g);
+        keys[(size_t)side * L + g] = a.addr[side][k][g - l.off[k]];
+    }
+}
+// digit counts of every tile: hist[(side * 256 + digit) * nwg + tile] — scanned in this order, a tile's first output position per digit
+__global__ __launch_bounds__(kBlock) void k_at_hist(const uint32_t *keys, uint32_t L, int shift, uint32_t *hist, uint32_t nwg) {
+    __shared__ uint32_t s_h[256];
+    const int side = blockIdx.y; const uint32_t *k = keys + (size_t)side * L;
+    s_h[threadIdx.x] = 0;
+    __syncthreads();
+    for (int j = 0; j < kAtItems; j++) {
+        const size_t e = (size_t)blockIdx.x * kAtTile + (size_t)j * kBlock + threadIdx.x;
+        if (e < L) atomicAdd(&s_h[(k[e] >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    hist[((size_t)side * 256 + threadIdx.x) * nwg + blockIdx.x] = s_h[threadIdx.x];
+}
+// one stable pass: inside a tile the order is round, wave, lane.  Per round a wave finds, by eight ballots, the lanes that hold the same
+// digit (rank inside the wave = how many of them are below this lane); thread d then turns the waves' counts of digit d into their first positions.
+// kFirst: the entries still sit at their walk positions (no index array yet)
+template <bool kFirst> __global__ __launch_bounds__(kBlock) void k_at_scatter(const uint32_t *key_in, const uint32_t *idx_in, uint32_t *key_out, uint32_t *idx_out, uint32_t L, int shift,
+                                                                              const uint32_t *hist_scanned, uint32_t nwg) {
+    __shared__ uint32_t s_cnt[256], s_wave[kBlock / 64][256];
+    const int side = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    key_in += (size_t)side * L; key_out += (size_t)side * L; idx_out += (size_t)side * L;
+    if (!kFirst) idx_in += (size_t)side * L;
+    const size_t h = ((size_t)side * 256 + threadIdx.x) * nwg + blockIdx.x;
+    s_cnt[threadIdx.x] = (h ? hist_scanned[h - 1] : 0u) - (uint32_t)side * L;      // (the scan runs over both sides: side 1 starts at L)
+    for (int j = 0; j < kAtItems; j++) {
+        const size_t e = (size_t)blockIdx.x * kAtTile + (size_t)j * kBlock + threadIdx.x;
+        const bool valid = e < L;
+        const uint32_t key = valid ? key_in[e] : 0u, d = (key >> shift) & 255u;
+        for (int i = lane; i < 256; i += 64) s_wave[wave][i] = 0;
+        __syncthreads();
+        unsigned long long same = __ballot(valid);
+#pragma unroll
+        for (int b = 0; b < 8; b++) { const unsigned long long bal = __ballot((d >> b) & 1u); same &= ((d >> b) & 1u) ? bal : ~bal; }
+        const uint32_t below = (uint32_t)__popcll(same & ((1ull << lane) - 1ull));
+        if (valid && below == 0) s_wave[wave][d] = (uint32_t)__popcll(same);
+        __syncthreads();
+        { uint32_t run = s_cnt[threadIdx.x]; for (int w = 0; w < kBlock / 64; w++) { const uint32_t t = s_wave[w][threadIdx.x]; s_wave[w][threadIdx.x] = run; run += t; } s_cnt[threadIdx.x] = run; }
+        __syncthreads();
+        if (valid) { const uint32_t pos = s_wave[wave][d] + below; key_out[pos] = key; idx_out[pos] = kFirst ? (uint32_t)e : idx_in[e]; }
+        __syncthreads();
+    }
+}
+// start[address] = sorted position of its first entry (written for the addresses that occur, read for those alone)
+__global__ __launch_bounds__(kBlock) void k_at_heads(const uint32_t *keys, uint32_t L, uint32_t *start, size_t M) {
+    const int side = blockIdx.y; const uint32_t *k = keys + (size_t)side * L;
+    for (size_t p = blockIdx.x * (size_t)blockDim.x + threadIdx.x; p < L; p += (size_t)gridDim.x * blockDim.x)
+        if (p == 0 || k[p - 1] != k[p]) start[(size_t)side * M + k[p]] = (uint32_t)p;
+}
+// the outputs (u32 and / or Montgomery form); the audit arrays were zeroed before.  Address 0 also holds the padding: an entry there comes
+// after the padding of the matrices before its own
+__global__ __launch_bounds__(kBlock) void k_at_ranks(AddrTs a, AtLens l, const uint32_t *keys, const uint32_t *idx, const uint32_t *start) {
+    const int side = blockIdx.y; const uint32_t L = l.off[3];
+    keys += (size_t)side * L; idx += (size_t)side * L; start += (size_t)side * a.M;
+    for (size_t p = blockIdx.x * (size_t)blockDim.x + threadIdx.x; p < L; p += (size_t)gridDim.x * blockDim.x) {
+        const uint32_t key = keys[p], g = idx[p], in_seg = (uint32_t)p - start[key];
+        const int k = at_matrix(l, g); const uint32_t i = g - l.off[k];
+        const uint32_t ts = in_seg + (key == 0 ? l.pad_before[k] : 0u);
+        if (a.ts_u32[side][k]) a.ts_u32[side][k][i] = ts;
+        if (a.ts_fr[side][k]) a.ts_fr[side][k][i] = fr_from_u64((uint64_t)ts);
+        if (p + 1 == L || keys[p + 1] != key) {              // the last entry of its address (address 0 with padding: k_at_tail writes the total)
+            if (a.audit_u32[side]) a.audit_u32[side][key] = in_seg + 1;
+            if (a.audit_fr[side]) a.audit_fr[side][key] = fr_from_u64((uint64_t)in_seg + 1);
+        }
+    }
+}
+// zc[side][k] = sorted entries at address 0 in matrices 0 .. k, zc[side][3] = all of them: address 0 sorts first and its entries keep the walk
+// order, so these are binary searches in the sorted arrays
+__global__ void k_at_zero(AtLens l, const uint32_t *keys, const uint32_t *idx, uint32_t *zc) {
+    const int side = blockIdx.x; const uint32_t L = l.off[3];
+    if (threadIdx.x != 0) return;
+    keys += (size_t)side * L; idx += (size_t)side * L;
+    uint32_t lo = 0, hi = L;
+    while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; if (keys[mid] == 0) lo = mid + 1; else hi = mid; }
+    const uint32_t n0 = lo;
+    for (int k = 0; k < 3; k++) {
+        lo = 0; hi = n0;
+        while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; if (idx[mid] < l.off[k + 1]) lo = mid + 1; else hi = mid; }
+        zc[4 * side + k] = lo;
+    }
+    zc[4 * side + 3] = n0;
+}
+// the padding: entry q of all padding entries in walk order (matrix k, index len[k] + q - pad_before[k]) has seen the sorted entries at
+// address 0 of matrices 0 .. k and the q padding entries before it
+__global__ __launch_bounds__(kBlock) void k_at_tail(AddrTs a, AtLens l, const uint32_t *zc) {
+    const int side = blockIdx.y; const uint32_t P = l.pad_before[3];
+    for (size_t q = blockIdx.x * (size_t)blockDim.x + threadIdx.x; q < P; q += (size_t)gridDim.x * blockDim.x) {
+        const int k = q >= l.pad_before[2] ? 2 : q >= l.pad_before[1] ? 1 : 0;
+        const uint32_t i = (l.off[k + 1] - l.off[k]) + ((uint32_t)q - l.pad_before[k]), ts = zc[4 * side + k] + (uint32_t)q;
+        if (a.ts_u32[side][k]) a.ts_u32[side][k][i] = ts;
+        if (a.ts_fr[side][k]) a.ts_fr[side][k][i] = fr_from_u64((uint64_t)ts);
+        if (q == 0) {
+            const uint32_t total = zc[4 * side + 3] + P;
+            if (a.audit_u32[side]) a.audit_u32[side][0] = total;
+            if (a.audit_fr[side]) a.audit_fr[side][0] = fr_from_u64((uint64_t)total);
+        }
+    }
+}
+void dev_addr_timestamps(DevCtx &c, const AddrTs &a) {
+    if (a.sides < 1 || a.sides > 2 || a.N < 1 || a.M < 1 || a.N > ((size_t)1 << 28) || a.M > ((size_t)1 << 31)) throw Error(OTTI_ERR_BAD_ARG, "address timestamps: 1 or 2 sides, lists of at most 2^28 entries, at most 2^31 addresses");
+    AtLens l; l.off[0] = 0; l.pad_before[0] = 0;
+    for (int k = 0; k < 3; k++) {
+        if (a.len[k] > a.N) throw Error(OTTI_ERR_BAD_ARG, "address timestamps: a list longer than N");
+        l.off[k + 1] = l.off[k] + a.len[k]; l.pad_before[k + 1] = l.pad_before[k] + (uint32_t)(a.N - a.len[k]);
+    }
+    const uint32_t L = l.off[3], P = l.pad_before[3], nwg = (L + kAtTile - 1) / kAtTile;
+    const unsigned sides = (unsigned)a.sides;
+    int passes = 1; while (passes < 4 && (a.M - 1) >> (8 * passes)) passes++;
+    // scratch: two key and two index arrays (ping-pong), first positions per address, digit counts, the zero counts
+    const size_t n_hist = (size_t)sides * 256 * std::max<uint32_t>(nwg, 1);
+    DevBuf<uint32_t> scratch((size_t)sides * (4 * (size_t)L + a.M) + n_hist + 8);
+    uint32_t *key[2] = {scratch.p, scratch.p + (size_t)sides * L}, *idx[2] = {key[1] + (size_t)sides * L, key[1] + 2 * (size_t)sides * L};
+    uint32_t *start = idx[1] + (size_t)sides * L, *hist = start + (size_t)sides * a.M, *zc = hist + n_hist;
+    std::vector<DevBuf<uint32_t>> scan_levels; scan_levels.reserve(4);
+    KScope ks(c, KC_GATHER);
+    for (unsigned s = 0; s < sides; s++) {
+        if (a.audit_u32[s]) OTTI_HIP(hipMemsetAsync(a.audit_u32[s], 0, a.M * sizeof(uint32_t), c.stream));
+        if (a.audit_fr[s]) OTTI_HIP(hipMemsetAsync(a.audit_fr[s], 0, a.M * sizeof(Fr), c.stream));
+    }
+    OTTI_HIP(hipMemsetAsync(zc, 0, 8 * sizeof(uint32_t), c.stream));
+    if (L) {
+        hipLaunchKernelGGL(k_at_pack, dim3(grid_for(L), sides), kBlock, 0, c.stream, a, l, key[0]);
+        int cur = 0;
+        for (int p = 0; p < passes; p++, cur ^= 1) {
+            hipLaunchKernelGGL(k_at_hist, dim3(nwg, sides), kBlock, 0, c.stream, (const uint32_t *)key[cur], L, 8 * p, hist, nwg);
+            scan_inplace(c, hist, n_hist, scan_levels);
+            if (p == 0) hipLaunchKernelGGL(k_at_scatter<true>, dim3(nwg, sides), kBlock, 0, c.stream, (const uint32_t *)key[cur], (const uint32_t *)nullptr, key[cur ^ 1], idx[cur ^ 1], L, 8 * p, (const uint32_t *)hist, nwg);
+            else hipLaunchKernelGGL(k_at_scatter<false>, dim3(nwg, sides), kBlock, 0, c.stream, (const uint32_t *)key[cur], (const uint32_t *)idx[cur], key[cur ^ 1], idx[cur ^ 1], L, 8 * p, (const uint32_t *)hist, nwg);
+        }
+        hipLaunchKernelGGL(k_at_heads, dim3(grid_for(L), sides), kBlock, 0, c.stream, (const uint32_t *)key[cur], L, start, a.M);
+        hipLaunchKernelGGL(k_at_ranks, dim3(grid_for(L), sides), kBlock, 0, c.stream, a, l, (const uint32_t *)key[cur], (const uint32_t *)idx[cur], (const uint32_t *)start);
+        if (P) hipLaunchKernelGGL(k_at_zero, sides, 64, 0, c.stream, l, (const uint32_t *)key[cur], (const uint32_t *)idx[cur], zc);
+    }
+    if (P) hipLaunchKernelGGL(k_at_tail, dim3(grid_for(P), sides), kBlock, 0, c.stream, a, l, (const uint32_t *)zc);
+    OTTI_HIP(hipStreamSynchronize(c.stream));                 // the scratch goes out of scope
 }
 
 // hash(addr, val, ts) - gamma = ts * r^2 + val * r + addr - gamma

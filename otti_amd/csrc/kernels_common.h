@@ -202,6 +202,46 @@ template <int K> __global__ __launch_bounds__(kBlock) void k_reduce_partials(con
     if (threadIdx.x == 0) for (int k = 0; k < K; k++) out[k] = acc[k];
 }
 
+// ------------------------------------------------------------------------------------------------ prefix sums of u32 counts (CSR build, address sort)
+// in-place inclusive scan of u32 counts: every workgroup scans 4096 elements and reports its total; the totals are scanned the same way
+// (recursively: two levels reach 2^24 elements, three 2^36), then added back
+constexpr int kScanItems = 16;
+static __global__ __launch_bounds__(kBlock) void k_scan_blocks(uint32_t *a, size_t n, uint32_t *totals) {
+    __shared__ uint32_t s_wave[kBlock / 64];
+    const size_t base = ((size_t)blockIdx.x * kBlock + threadIdx.x) * kScanItems;
+    uint32_t v[kScanItems], run = 0;
+#pragma unroll
+    for (int i = 0; i < kScanItems; i++) { run += base + i < n ? a[base + i] : 0u; v[i] = run; }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t x = run;
+    for (int off = 1; off < 64; off <<= 1) { const uint32_t y = (uint32_t)__shfl_up((int)x, off, 64); if (lane >= off) x += y; }
+    if (lane == 63) s_wave[wave] = x;
+    __syncthreads();
+    uint32_t before = 0;
+    for (int k = 0; k < wave; k++) before += s_wave[k];
+    const uint32_t excl = before + x - run;
+#pragma unroll
+    for (int i = 0; i < kScanItems; i++) if (base + i < n) a[base + i] = v[i] + excl;
+    if (threadIdx.x == kBlock - 1) totals[blockIdx.x] = before + x;
+}
+static __global__ __launch_bounds__(kBlock) void k_scan_add(uint32_t *a, size_t n, const uint32_t *totals_scanned) {
+    if (blockIdx.x == 0) return;
+    const uint32_t add = totals_scanned[blockIdx.x - 1];
+    const size_t base = ((size_t)blockIdx.x * kBlock + threadIdx.x) * kScanItems;
+#pragma unroll
+    for (int i = 0; i < kScanItems; i++) if (base + i < n) a[base + i] += add;
+}
+static void scan_inplace(DevCtx &c, uint32_t *a, size_t n, std::vector<DevBuf<uint32_t>> &levels, size_t depth = 0) {
+    const size_t per = (size_t)kBlock * kScanItems, nb = (n + per - 1) / per;
+    if (levels.size() <= depth) levels.emplace_back();
+    if (levels[depth].n < nb) { OTTI_HIP(hipStreamSynchronize(c.stream)); levels[depth].alloc(nb); }
+    hipLaunchKernelGGL(k_scan_blocks, (unsigned)nb, kBlock, 0, c.stream, a, n, levels[depth].p);
+    if (nb == 1) return;
+    uint32_t *totals = levels[depth].p;                       // (a deeper level may grow `levels`: take the pointer first)
+    scan_inplace(c, totals, nb, levels, depth + 1);
+    hipLaunchKernelGGL(k_scan_add, (unsigned)nb, kBlock, 0, c.stream, a, n, (const uint32_t *)totals);
+}
+
 // ------------------------------------------------------------------------------------------------ shared by the sum-check kernels
 struct Pair { Fr lo, hi; };
 // entries (i, i + q) of a table of length 4q folded by r (bound_poly_var_top): the pair i of the folded table

@@ -132,6 +132,11 @@ void dotproductlog_verify(const DotProductProofLog &pf, size_t n, const Gens &g,
 // GPU (snark_prover.cpp)
 struct SnarkTimings { double ms[10]; };                      // the six R1CSProof stages, [6] derefs commitment, [7] product circuits, [8] hash layer, [9] total
 std::unique_ptr<CompComm> snark_encode_gpu(Instance &inst, SnarkGens &g);
+// The prover's copy of a commitment that came as bytes: rebuilds the decommitment of `inst` in HBM (the same function SNARK::encode uses) and
+// hangs it on `comm`; no commitment MSM unless verify, which recomputes both commitments and compares them with the stored points (a
+// difference: Error(OTTI_ERR_BAD_ARG), comm stays as it was).  Dimensions are checked before the device is touched; a commitment that
+// already has its decommitment is left alone.
+void snark_attach_gpu(Instance &inst, CompComm &comm, SnarkGens &g, bool verify);
 std::vector<uint8_t> snark_prove_gpu(Instance &inst, CompComm &comm, const uint8_t *vars32, size_t nvars, const std::vector<Fr> &inputs, SnarkGens &g,
                                      const void *tlabel, size_t tlabel_len, const uint8_t *seed32, SnarkTimings *tm);
 struct DeviceWitness;                                        // device.h: the assignment resident in HBM (otti_witness_upload)

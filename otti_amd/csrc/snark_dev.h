@@ -38,6 +38,18 @@ unsigned long long dev_pc_tail(DevCtx &c, const PcList &L, int W, size_t len0, s
 
 void dev_gather(DevCtx &c, const Fr *table, const uint32_t *idx, Fr *out, size_t n);
 void dev_u32_to_fr(DevCtx &c, const uint32_t *in, Fr *out, size_t n);        // out[i] = in[i] as a field element (Montgomery form)
+// ---- sparse_mlpoly.rs AddrTimestamps::new for one side (rows) or both (rows, columns) of the dense representation, in one run of launches.
+// Per side three address lists of N entries with values below M; walking k = 0, 1, 2 and i = 0 .. N - 1 in order over ONE counter array shared by
+// the three lists, read_ts[k][i] = audit[addr[k][i]]++.  Entries at and beyond len[k] (the same on both sides) must be address 0: they are not
+// sorted but ranked in closed form.  Results are those of the sequential walk, bit for bit, for any input (a stable radix sort by address:
+// k_snark.hip).  Outputs as u32 and / or as field elements (Montgomery form), each optional (nullptr).  Returns with the stream idle.
+struct AddrTs {
+    int sides = 1; size_t N = 0, M = 0;
+    const uint32_t *addr[2][3] = {}; uint32_t len[3] = {0, 0, 0};
+    uint32_t *ts_u32[2][3] = {}; Fr *ts_fr[2][3] = {};        // N entries each
+    uint32_t *audit_u32[2] = {}; Fr *audit_fr[2] = {};        // M entries each
+};
+void dev_addr_timestamps(DevCtx &c, const AddrTs &a);
 void dev_hash_mem(DevCtx &c, const Fr *eval_table, const Fr *audit_ts, Fr *out_init, Fr *out_audit, size_t M, const Fr &r, const Fr &gamma, int G = 1, int rk = 0);   // G ranks: this rank's residue class (M / G elements) of the M-element vectors
 void dev_hash_ops(DevCtx &c, const Fr *addr_f, const Fr *deref, const Fr *read_ts, Fr *out_read, Fr *out_write, size_t N, const Fr &r, const Fr &gamma, int G = 1, int rk = 0);
 void dev_prod_layer(DevCtx &c, const LayerList &L, size_t q);

@@ -7,6 +7,9 @@
 // Additive options: --seed <hex32>, --proof-out <file>, --label <transcript label>, `spzk synth <n> <prefix>` to emit a
 // synthetic zkif triple; `spzk check` and --check: does the assignment satisfy the circuit, and if not, which constraints fail
 // (otti_witness_check_sat: on the device, on the uploaded assignment; no generators are made for `check`).
+// SNARK mode across processes: `spzk encode` writes the computation commitment, `spzk prove --comm-in` completes its copy of it
+// (otti_comp_comm_attach) and proves, `spzk verify <inputs> --comm-in --proof-in` checks the proof holding nothing but the commitment
+// and the public inputs — no circuit, no witness, no GPU.
 #include <stdio.h>
 #include <thread>
 #include <time.h>
@@ -31,6 +34,12 @@ static int usage() {
                     "            (the reference's invocation: prove, then verify, in one process; without --nizk: SNARK mode)\n"
                     "       spzk prove  --nizk <circuit.zkif> <inputs.inp.zkif> <witness.wit.zkif> --proof-out FILE [--seed HEX64] [--label STR] [--check]\n"
                     "       spzk verify --nizk <circuit.zkif> <inputs.inp.zkif> --proof-in FILE [--label STR]\n"
+                    "       spzk encode <circuit.zkif> [<inputs.inp.zkif>] --comm-out FILE\n"
+                    "            (SNARK::encode: writes the computation commitment)\n"
+                    "       spzk prove  <circuit.zkif> <inputs.inp.zkif> <witness.wit.zkif> [--comm-in FILE] --proof-out FILE [--seed HEX64] [--label STR] [--check] [--verify-comm]\n"
+                    "            (SNARK::prove from a stored commitment; --verify-comm: recompute it and compare first; without --comm-in: encodes itself)\n"
+                    "       spzk verify <inputs.inp.zkif> --comm-in FILE --proof-in FILE [--label STR]\n"
+                    "            (SNARK::verify from the commitment and the public inputs alone: no circuit, no witness, no GPU)\n"
                     "       spzk check [--nizk] <circuit.zkif> <inputs.inp.zkif> <witness.wit.zkif>\n"
                     "            (does the assignment satisfy the circuit? exit 0: yes; 1: no, with the failing constraints; no proof is made)\n"
                     "            --check: the same test after the upload, before proving; an unsatisfied assignment is reported and not proved\n"
@@ -69,6 +78,93 @@ static int run_check(otti_instance *inst, otti_witness *wit, uint64_t num_cons) 
     return 1;
 }
 
+static bool read_file(const char *path, std::vector<uint8_t> &out) {
+    FILE *f = fopen(path, "rb");
+    if (!f) { fprintf(stderr, "spzk: cannot read %s\n", path); return false; }
+    fseek(f, 0, SEEK_END); const long len = ftell(f); fseek(f, 0, SEEK_SET);
+    out.resize(len > 0 ? (size_t)len : 0);
+    const bool ok = fread(out.data(), 1, out.size(), f) == out.size();
+    fclose(f);
+    if (!ok) fprintf(stderr, "spzk: short read on %s\n", path);
+    return ok;
+}
+static bool write_file(const char *path, const uint8_t *p, size_t n) {
+    FILE *f = fopen(path, "wb");
+    const bool ok = f && fwrite(p, 1, n, f) == n;
+    if (f) fclose(f);
+    if (!ok) fprintf(stderr, "spzk: cannot write %s\n", path);
+    return ok;
+}
+
+// ---- SNARK mode, one role per process.  role 'e': encode, 'p': prove, 'v': verify.  Returns the exit status.
+struct SnarkRoleArgs { char role; std::vector<const char *> files; const char *comm_in, *comm_out, *proof_in, *proof_out, *label; const uint8_t *seed; bool check, verify_comm; };
+static int snark_role(const SnarkRoleArgs &a) {
+    int rc; double t0 = now_ms();
+    if (a.role == 'v') {                                       // the commitment, the public inputs, the proof: nothing else, and no device
+        std::vector<uint8_t> cb, proof;
+        if (!read_file(a.comm_in, cb) || !read_file(a.proof_in, proof)) return 1;
+        otti_comp_comm *cc = nullptr; rc = otti_comp_comm_from_bytes(cb.data(), cb.size(), &cc); if (rc) return fail("commitment parse", rc);
+        otti_r1cs *r = nullptr; rc = otti_zkif_load_inputs(a.files[0], &r); if (rc) return fail("zkif load (inputs)", rc);
+        uint64_t nc, nv, ni, nops; rc = otti_comp_comm_dims(cc, &nc, &nv, &ni, &nops, nullptr); if (rc) return fail("commitment dimensions", rc);
+        otti_snark_gens *sg = nullptr; rc = otti_snark_gens_new(nc, nv, ni, nops, &sg); if (rc) return fail("SNARKGens::new", rc);
+        const double t_setup = now_ms() - t0; t0 = now_ms();
+        rc = otti_snark_verify(cc, r->inputs32, r->ninputs, sg, (const uint8_t *)a.label, strlen(a.label), proof.data(), proof.size());
+        printf("* commitment: %llu constraints, %llu variables, %llu inputs, %llu operations per matrix (%zu bytes)\n* setup (parse, SNARKGens::new) %.3f ms\n* SNARK::verify %.3f ms\n",
+               (unsigned long long)nc, (unsigned long long)nv, (unsigned long long)ni, (unsigned long long)nops, cb.size(), t_setup, now_ms() - t0);
+        if (rc) { char msg[512]; otti_last_error(msg, sizeof msg); printf("Verification FAILED (%d%s%s)\n", rc, msg[0] ? ": " : "", msg); return 1; }
+        printf("Verification successful\n");
+        return 0;
+    }
+    otti_r1cs *r = nullptr;
+    rc = otti_zkif_load(a.files[0], a.files.size() > 1 ? a.files[1] : nullptr, a.role == 'p' ? a.files[2] : nullptr, &r); if (rc) return fail("zkif load", rc);
+    const double t_load = now_ms() - t0; t0 = now_ms();
+    otti_instance *inst = nullptr;
+    rc = otti_instance_new(r->num_cons, r->num_vars, r->num_inputs, r->A, r->nA, r->B, r->nB, r->C, r->nC, &inst); if (rc) return fail("Instance::new", rc);
+    const uint64_t nnz = std::max<uint64_t>({(uint64_t)r->nA, (uint64_t)r->nB, (uint64_t)r->nC});
+    otti_snark_gens *sg = nullptr; rc = otti_snark_gens_new(r->num_cons, r->num_vars, r->num_inputs, nnz, &sg); if (rc) return fail("SNARKGens::new", rc);
+    const double t_setup = now_ms() - t0; t0 = now_ms();
+    uint64_t nc, nv, ni; otti_instance_dims(inst, &nc, &nv, &ni);
+    printf("* instance: %llu constraints (padded %llu), %llu variables (padded %llu), %llu inputs, %llu non-zero entries in the largest matrix\n", (unsigned long long)r->num_cons,
+           (unsigned long long)nc, (unsigned long long)r->num_vars, (unsigned long long)nv, (unsigned long long)ni, (unsigned long long)nnz);
+    printf("* zkif_load %.3f ms\n* setup (Instance::new, SNARKGens::new) %.3f ms\n", t_load, t_setup);
+    otti_comp_comm *cc = nullptr;
+    if (a.comm_in) {                                           // the stored commitment, completed from this process's own instance
+        std::vector<uint8_t> cb;
+        if (!read_file(a.comm_in, cb)) return 1;
+        rc = otti_comp_comm_from_bytes(cb.data(), cb.size(), &cc); if (rc) return fail("commitment parse", rc);
+        rc = otti_comp_comm_attach(cc, inst, sg, a.verify_comm ? OTTI_ATTACH_VERIFY : 0u); if (rc) return fail("commitment attach", rc);
+        printf("* attach%s %.3f ms (computation commitment %zu bytes)\n", a.verify_comm ? " (commitments recomputed and compared)" : "", now_ms() - t0, cb.size());
+    } else {
+        rc = otti_snark_encode(inst, sg, &cc); if (rc) return fail("SNARK::encode", rc);
+        uint8_t *cb = nullptr; size_t cb_len = 0; rc = otti_comp_comm_bytes(cc, &cb, &cb_len); if (rc) return fail("commitment bytes", rc);
+        printf("* SNARK::encode %.3f ms (computation commitment %zu bytes)\n", now_ms() - t0, cb_len);
+        if (a.comm_out && !write_file(a.comm_out, cb, cb_len)) return 1;
+        if (a.comm_out) printf("Commitment written to %s (%zu bytes)\n", a.comm_out, cb_len);
+        otti_buf_free(cb);
+    }
+    if (a.role == 'e') { fflush(stdout); _exit(0); }          // everything is printed and written: skip the HIP runtime's teardown
+    t0 = now_ms();
+    otti_witness *wit = nullptr;
+    if (a.check) {
+        rc = otti_witness_upload(inst, r->vars32, r->nvars, r->inputs32, r->ninputs, &wit); if (rc) return fail("witness upload", rc);
+        const int sat = run_check(inst, wit, r->num_cons);
+        if (sat < 0) return 1;
+        if (sat) { printf("Not proved (unsatisfied assignment)\n"); return 1; }
+        t0 = now_ms();
+    }
+    uint8_t *proof = nullptr; size_t proof_len = 0; double st[10] = {0};
+    if (wit) rc = otti_snark_prove_resident(inst, cc, wit, sg, (const uint8_t *)a.label, strlen(a.label), a.seed, &proof, &proof_len, st);
+    else rc = otti_snark_prove(inst, cc, r->vars32, r->nvars, r->inputs32, r->ninputs, sg, (const uint8_t *)a.label, strlen(a.label), a.seed, OTTI_FLAG_GPU, &proof, &proof_len, st);
+    if (rc) return fail("SNARK::prove", rc);
+    printf("* SNARK::prove %.3f ms\n  * polycommit %.3f ms\n  * multiply_vec %.3f ms\n  * prove_sc_phase_one %.3f ms\n  * eval_table_sparse %.3f ms\n  * prove_sc_phase_two %.3f ms\n"
+           "  * polyeval %.3f ms\n  * R1CSEvalProof: derefs commitment %.3f ms, product circuits %.3f ms, hash layer %.3f ms\n  * len_snark_proof %zu\n",
+           now_ms() - t0, st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8], proof_len);
+    if (!write_file(a.proof_out, proof, proof_len)) return 1;
+    printf("Proof written to %s (%zu bytes)\n", a.proof_out, proof_len);
+    fflush(stdout);
+    _exit(0);
+}
+
 int main(int argc, char **argv) {
     const double t_before_main = ms_since_process_start(), t_main0 = now_ms();
     if (argc < 2) return usage();
@@ -82,24 +178,28 @@ int main(int argc, char **argv) {
         printf("wrote %s.zkif %s.inp.zkif %s.wit.zkif (%llu constraints)\n", p.c_str(), p.c_str(), p.c_str(), (unsigned long long)n);
         return 0;
     }
-    const bool prove_only = !strcmp(argv[1], "prove"), check_only = !strcmp(argv[1], "check");
-    if (!prove_only && !check_only && strcmp(argv[1], "verify")) return usage();
+    const bool prove_only = !strcmp(argv[1], "prove"), check_only = !strcmp(argv[1], "check"), encode_only = !strcmp(argv[1], "encode");
+    if (!prove_only && !check_only && !encode_only && strcmp(argv[1], "verify")) return usage();
     // one proof per process: the generator window table is built and used once, so a narrow window (small table, ~7 ms to build for
     // R = 1024) beats the wide one a long-lived prover process amortises (see prover.cpp device_window_bits); an explicit setting wins
     setenv("OTTI_MSM_WINDOW", "10", 0);
-    bool nizk = false, label_given = false, check = false; std::vector<const char *> files; const char *seed_hex = nullptr, *proof_out = nullptr, *proof_in = nullptr, *label = "nizk_example";
+    bool nizk = false, label_given = false, check = false, verify_comm = false; std::vector<const char *> files;
+    const char *seed_hex = nullptr, *proof_out = nullptr, *proof_in = nullptr, *comm_in = nullptr, *comm_out = nullptr, *label = "nizk_example";
     for (int i = 2; i < argc; i++) {
         if (!strcmp(argv[i], "--nizk")) nizk = true;
         else if (!strcmp(argv[i], "--check")) check = true;
         else if (!strcmp(argv[i], "--seed") && i + 1 < argc) seed_hex = argv[++i];
         else if (!strcmp(argv[i], "--proof-out") && i + 1 < argc) proof_out = argv[++i];
         else if (!strcmp(argv[i], "--proof-in") && i + 1 < argc) proof_in = argv[++i];
+        else if (!strcmp(argv[i], "--comm-in") && i + 1 < argc) comm_in = argv[++i];
+        else if (!strcmp(argv[i], "--comm-out") && i + 1 < argc) comm_out = argv[++i];
+        else if (!strcmp(argv[i], "--verify-comm")) verify_comm = true;
         else if (!strcmp(argv[i], "--label") && i + 1 < argc) { label = argv[++i]; label_given = true; }
         else files.push_back(argv[i]);
     }
     const bool verify_only = proof_in != nullptr;
     if (check_only) {                                          // load, Instance::new, upload, check: no generators, no window table
-        if (files.size() != 3 || verify_only || proof_out) return usage();
+        if (files.size() != 3 || verify_only || proof_out || comm_in || comm_out) return usage();
         otti_r1cs *r = nullptr; int rc = otti_zkif_load(files[0], files[1], files[2], &r); if (rc) return fail("zkif load", rc);
         otti_instance *inst = nullptr;
         rc = otti_instance_new(r->num_cons, r->num_vars, r->num_inputs, r->A, r->nA, r->B, r->nB, r->C, r->nC, &inst); if (rc) return fail("Instance::new", rc);
@@ -112,10 +212,21 @@ int main(int argc, char **argv) {
         _exit(sat == 0 ? 0 : 1);                               // as below: skip the HIP runtime's teardown
     }
     if (check && verify_only) return usage();                  // a separate verifier has no witness to check
-    if (!nizk && (prove_only || verify_only)) { fprintf(stderr, "spzk: separate prove / verify processes are offered in --nizk mode only\n"); return 2; }
+    // the stored computation commitment belongs to SNARK mode; its roles: encode / prove / verify --comm-in --proof-in (snark_role)
+    if (nizk && (encode_only || comm_in || comm_out || verify_comm)) return usage();
+    const bool snark_split = !nizk && (encode_only || prove_only || verify_only);
     if (!nizk && !label_given) label = "snark_example";
     if (prove_only && (verify_only || !proof_out)) return usage();
-    if (verify_only ? (files.size() != 2 && files.size() != 3) : files.size() != 3) return usage();
+    if (snark_split) {
+        if (encode_only && (!comm_out || comm_in || proof_out || verify_only || check || verify_comm || (files.size() != 1 && files.size() != 2))) return usage();
+        if (prove_only && (files.size() != 3 || comm_out || (verify_comm && !comm_in))) return usage();
+        if (verify_only && (!comm_in || comm_out || proof_out || verify_comm || files.size() != 1)) {
+            fprintf(stderr, "spzk: SNARK mode verifies a stored proof against a stored commitment: verify <inputs.inp.zkif> --comm-in FILE --proof-in FILE\n"); return usage();
+        }
+    } else {
+        if (comm_in || comm_out || verify_comm) return usage();
+        if (verify_only ? (files.size() != 2 && files.size() != 3) : files.size() != 3) return usage();
+    }
     uint8_t seed[32]; const uint8_t *seedp = nullptr;
     if (seed_hex) {
         if (strlen(seed_hex) != 64) { fprintf(stderr, "spzk: --seed wants 64 hex digits\n"); return 2; }
@@ -125,6 +236,12 @@ int main(int argc, char **argv) {
     // the HIP runtime takes a noticeable fraction of a second to come up: let it do so while the files are being parsed
     std::thread warm([&] { if (!verify_only && otti_device_count() > 0) (void)otti_prepare_device(nullptr, nullptr); });
     struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{warm};
+    if (snark_split) {
+        SnarkRoleArgs a{encode_only ? 'e' : prove_only ? 'p' : 'v', files, comm_in, comm_out, proof_in, proof_out, label, seedp, check, verify_comm};
+        const int status = snark_role(a);
+        fflush(stdout);
+        return status;
+    }
     double t0 = now_ms();
     otti_r1cs *r = nullptr; int rc = otti_zkif_load(files[0], files[1], verify_only ? nullptr : files[2], &r); if (rc) return fail("zkif load", rc);
     double t_load = now_ms() - t0; t0 = now_ms();

@@ -388,6 +388,25 @@ otti_r1cs *zkif_load_impl(const char *circuit_path, const char *inputs_path, con
     return out;
 }
 
+// the public inputs alone (what a SNARK verifier holding the computation commitment needs): the .inp.zkif header's instance values, in
+// the order the full loader gives them; no circuit, so num_cons / num_vars stay 0 and no id map is built
+otti_r1cs *zkif_load_inputs_impl(const char *inputs_path) {
+    Messages m;
+    FileView f(inputs_path);
+    parse_headers(f, m);
+    if (!m.have_header) throw Error(OTTI_ERR_IO, "zkif: no CircuitHeader message");
+    if (!m.instance.ids.empty() && (!m.instance.has_vals || m.instance.vals.size() != m.instance.ids.size())) throw Error(OTTI_ERR_IO, "zkif: inputs file carries no instance values");
+    otti_r1cs *out = (otti_r1cs *)calloc(1, sizeof *out);
+    if (!out) throw std::bad_alloc();
+    struct Guard { otti_r1cs *r; ~Guard() { if (r) otti_r1cs_free(r); } } guard{out};
+    out->num_inputs = out->ninputs = m.instance.ids.size();
+    out->vars32 = (uint8_t *)calloc(1, 1); out->inputs32 = (uint8_t *)calloc(std::max<size_t>(1, 32 * out->ninputs), 1);
+    if (!out->vars32 || !out->inputs32) throw std::bad_alloc();
+    for (size_t i = 0; i < out->ninputs; i++) memcpy(out->inputs32 + 32 * i, m.instance.vals[i].data(), 32);
+    guard.r = nullptr;
+    return out;
+}
+
 void zkif_write_impl(const otti_r1cs *r, const char *circuit_path, const char *inputs_path, const char *witness_path) {
     // ids: 0 = one, 1..ni = instance variables, ni+1.. = witness variables
     const size_t ni = r->num_inputs, nv = r->num_vars;
