@@ -288,6 +288,37 @@ int32_t otti_k_bullet_round(otti_gens *gens, size_t n_cur, int32_t fold, const u
                             const uint8_t *h_s, const uint8_t *h_blinds2, uint8_t *h_a_out, uint8_t *h_b_out, uint8_t *h_s_out, uint8_t *h_LR64, float *kernel_ms);
 /* the closing fold of the reduction (length 2 -> 1): a, b of 2 elements and s of R are folded in place by (u, u^-1) */
 int32_t otti_k_bullet_last_fold(size_t R, const uint8_t *h_u, const uint8_t *h_uinv, uint8_t *h_a2, uint8_t *h_b2, uint8_t *h_s);
+/* ---- SNARK mode's kernels (R1CSEvalProof: product circuits, their batched sum-check, the hash layer).  A batch of ninst (1 .. 20) instances travels
+        as ONE array per table kind: instance y's table at element y * len.  h_has_C[y] != 0: instance y is a dot-product triple with a third table;
+        h_C holds those third tables alone, in instance order.  0: a product-circuit instance, whose third table is the shared eq table of h_tau. ---- */
+/* one round of the batched cubic sum-check.  h_r == NULL: the sums of tables of length len as they are.  Otherwise the tables are folded by r first
+   (bound_poly_var_top; h_out: the folded A tables, the B tables, the C tables, len / 2 elements each).  h_e: 3 * ninst sums (at 0, 2, 3), without
+   the bound variable's eq factor for product-circuit instances.  Item i of a table is element i * G + rk of the eq table (a rank's residue class of a
+   sharded layer); h_tau holds log2(G * len / 2) variables (len / 4 with a fold). */
+int32_t otti_k_pc_round(const uint8_t *h_A, const uint8_t *h_B, const uint8_t *h_C, const uint8_t *h_has_C, size_t ninst, size_t len, const uint8_t *h_tau,
+                        const uint8_t *h_r, uint32_t G, uint32_t rk, uint8_t *h_out, uint8_t *h_e, float *kernel_ms);
+/* the hand-over of a batch's tables to the host (folded by h_fold_r first unless NULL): h_out[(3 y + t) * n_out ..) = table t of instance y
+   (n_out = len, or len / 2 with a fold; the place of an absent third table is zero) */
+int32_t otti_k_pc_export(const uint8_t *h_A, const uint8_t *h_B, const uint8_t *h_C, const uint8_t *h_has_C, size_t ninst, size_t len, const uint8_t *h_fold_r, uint8_t *h_out);
+/* the persistent launch that plays log2(len0 / t_out) rounds with W workgroups per instance, the host answering round j with h_rs[j]: h_sums =
+   [round][instance][3] sums (the eq table of h_tau, log2(len0) variables, is a real third table here), h_out as otti_k_pc_export with n_out = t_out.
+   h_fold_r: the tables hold 2 * len0 elements and are folded on load.  top != 0: h_tau[0] is applied as one factor above a table of the others. */
+int32_t otti_k_pc_tail(const uint8_t *h_A, const uint8_t *h_B, const uint8_t *h_C, const uint8_t *h_has_C, size_t ninst, size_t len0, uint32_t W, size_t t_out,
+                       const uint8_t *h_tau, const uint8_t *h_rs, const uint8_t *h_fold_r, int32_t top, uint8_t *h_sums, uint8_t *h_out);
+/* ProductCircuit::compute_layer of ninst (1 .. 16) circuits: inputs of 2 q elements each, out_left[i] = left[i] * right[i], out_right[i] = left[q + i] * right[q + i] */
+int32_t otti_k_prod_layer(const uint8_t *h_left, const uint8_t *h_right, size_t ninst, size_t q, uint8_t *h_out_left, uint8_t *h_out_right, float *kernel_ms);
+/* Layers::build_hash_layer: cells (init, audit) and operations (read, write) of n elements hashed with (r, gamma); rank rk of G writes the n / G
+   elements of its residue class (both halves of the vector keep the indices i = rk mod G) */
+int32_t otti_k_hash_mem(const uint8_t *h_eval_table, const uint8_t *h_audit_ts, size_t M, const uint8_t *h_r, const uint8_t *h_gamma, uint32_t G, uint32_t rk,
+                        uint8_t *h_out_init, uint8_t *h_out_audit, float *kernel_ms);
+int32_t otti_k_hash_ops(const uint8_t *h_addr, const uint8_t *h_deref, const uint8_t *h_read_ts, size_t N, const uint8_t *h_r, const uint8_t *h_gamma, uint32_t G, uint32_t rk,
+                        uint8_t *h_out_read, uint8_t *h_out_write, float *kernel_ms);
+/* h_out[y] = <E, P_y> for npoly (1 .. 64) polynomials of n elements; h_out[y] = sum_i A_y[i] B_y[i] C_y[i] for ninst (1 .. 20) triples */
+int32_t otti_k_dot_many(const uint8_t *h_E, const uint8_t *h_Ps, size_t npoly, size_t n, uint8_t *h_out, float *kernel_ms);
+int32_t otti_k_sum3(const uint8_t *h_A, const uint8_t *h_B, const uint8_t *h_C, size_t ninst, size_t n, uint8_t *h_out, float *kernel_ms);
+/* DensePolynomial::bound in chunks of m rows: h_out[c * R + j] = sum_i Lv_rest[i] * Z[(c m + i) * R + j].  *launched = 0 (and h_out untouched) when
+   the geometry is one the launch function declines */
+int32_t otti_k_poly_bound_chunks(const uint8_t *h_Z, size_t L, size_t R, const uint8_t *h_Lv_rest, size_t m, uint8_t *h_out, int32_t *launched, float *kernel_ms);
 
 /* ---- the same kernels on DEVICE pointers and a caller-chosen HIP stream ("host or device pointers + a stream
         handle"): nothing is staged through PCIe, so a kernel can be benchmarked or composed from outside the library.

@@ -144,6 +144,16 @@ _sig("otti_k_sc_cubic3_fold_round", _i32, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp
 _sig("otti_k_poly_bound", _i32, _vp, _sz, _sz, _vp, _vp, _fp)
 _sig("otti_k_bullet_round", _i32, _vp, _sz, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _fp)
 _sig("otti_k_bullet_last_fold", _i32, _sz, _vp, _vp, _vp, _vp, _vp)
+_u32 = ctypes.c_uint32
+_sig("otti_k_pc_round", _i32, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _u32, _u32, _vp, _vp, _fp)
+_sig("otti_k_pc_export", _i32, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp)
+_sig("otti_k_pc_tail", _i32, _vp, _vp, _vp, _vp, _sz, _sz, _u32, _sz, _vp, _vp, _vp, _i32, _vp, _vp)
+_sig("otti_k_prod_layer", _i32, _vp, _vp, _sz, _sz, _vp, _vp, _fp)
+_sig("otti_k_hash_mem", _i32, _vp, _vp, _sz, _vp, _vp, _u32, _u32, _vp, _vp, _fp)
+_sig("otti_k_hash_ops", _i32, _vp, _vp, _vp, _sz, _vp, _vp, _u32, _u32, _vp, _vp, _fp)
+_sig("otti_k_dot_many", _i32, _vp, _vp, _sz, _sz, _vp, _fp)
+_sig("otti_k_sum3", _i32, _vp, _vp, _vp, _sz, _sz, _vp, _fp)
+_sig("otti_k_poly_bound_chunks", _i32, _vp, _sz, _sz, _vp, _sz, _vp, ctypes.POINTER(_i32), _fp)
 _sig("otti_kd_multiply_vec", _i32, _vp, _vp, _vp, _vp, _vp, _vp)
 _sig("otti_kd_check_sat", _i32, _vp, _vp, _vp, ctypes.POINTER(_u64), _vp)
 _sig("otti_kd_eval_table_sparse", _i32, _vp, _vp, _vp, _vp, _vp)
@@ -890,6 +900,136 @@ class kernels:
         a2, b2, s, u, uinv = (_scalars(x, "t").copy() for x in (a2, b2, s, u, uinv))
         _check(lib.otti_k_bullet_last_fold(s.shape[0], _ptr(u), _ptr(uinv), _ptr(a2), _ptr(b2), _ptr(s)))
         return a2[:1], b2[:1], s
+
+    # ---- SNARK mode's kernels (k_snark.hip).  A batch is a list with one (n, 32) table per instance; C[y] is None for a product-circuit instance
+    @staticmethod
+    def _stack(tables, what, n=None):
+        """tables of one length as one contiguous array (the C ABI's layout); unequal lengths are the library's bad-argument error"""
+        ts = [_scalars(t, what) for t in tables]
+        if n is None:
+            n = ts[0].shape[0] if ts else 0
+        if any(t.shape[0] != n for t in ts):
+            raise SpartanError(-21, f"{what}: tables of unequal length")
+        return (np.concatenate(ts) if len(ts) > 1 else ts[0] if ts else np.zeros((0, 32), dtype=np.uint8)), n
+
+    @staticmethod
+    def _batch(A, B, C):
+        if not (len(A) == len(B) == len(C)):
+            raise SpartanError(-21, "a batch needs one A, B and C entry per instance")
+        a, n = kernels._stack(A, "A"); b, _ = kernels._stack(B, "B", n)
+        has_c = np.array([0 if t is None else 1 for t in C], dtype=np.uint8)
+        c, _ = kernels._stack([t for t in C if t is not None], "C", n)
+        return a, b, c, has_c, len(A), n
+
+    @staticmethod
+    def _unbatch(out, has_c, ninst, n_out):
+        """(3 * ninst * n_out) elements laid out [(3 y + t) * n_out ..) -> per instance [A, B, C or None]"""
+        o = out.reshape(ninst, 3, n_out, 32)
+        return [[o[y, 0], o[y, 1], o[y, 2] if has_c[y] else None] for y in range(ninst)]
+
+    @staticmethod
+    def pc_round(A, B, C, tau, r=None, G=1, rk=0):
+        """one round of the batched sum-check (dev_pc_eval, or dev_pc_fold_eval when r is given).  Returns (sums (ninst, 3, 32), folded, ms);
+        folded = (A, B, C) lists of the tables folded by r (None entries where C has none), or None without r"""
+        a, b, c, has_c, ninst, n = kernels._batch(A, B, C)
+        tau = _scalars(tau, "tau"); rr = None if r is None else _scalars(r, "r")
+        items = (n // (2 if rr is None else 4)) * G
+        if ninst and items >= 1 and tau.shape[0] != items.bit_length() - 1:
+            raise SpartanError(-21, "tau: one variable per bit of the eq table's index")
+        h = n // 2; nc = int(has_c.sum())
+        out = np.zeros(((2 * ninst + nc) * h, 32), dtype=np.uint8) if rr is not None else None
+        e = np.zeros((max(ninst, 1), 3, 32), dtype=np.uint8); ms = ctypes.c_float(0)
+        _check(lib.otti_k_pc_round(_ptr(a), _ptr(b), _ptr(c), _ptr(has_c), ninst, n, _ptr(tau), _ptr(rr), G, rk, _ptr(out), _ptr(e), ctypes.byref(ms)))
+        folded = None
+        if rr is not None:
+            o = out.reshape(2 * ninst + nc, h, 32); k = iter(range(2 * ninst, 2 * ninst + nc))
+            folded = ([o[y] for y in range(ninst)], [o[ninst + y] for y in range(ninst)], [o[next(k)] if has_c[y] else None for y in range(ninst)])
+        return e, folded, ms.value
+
+    @staticmethod
+    def pc_export(A, B, C, fold_r=None):
+        """dev_pc_export: per instance [A, B, C or None], folded by fold_r first when given"""
+        a, b, c, has_c, ninst, n = kernels._batch(A, B, C)
+        rr = None if fold_r is None else _scalars(fold_r, "fold_r")
+        n_out = n if rr is None else n // 2
+        out = np.zeros((3 * ninst * n_out, 32), dtype=np.uint8)
+        _check(lib.otti_k_pc_export(_ptr(a), _ptr(b), _ptr(c), _ptr(has_c), ninst, n, _ptr(rr), _ptr(out)))
+        return kernels._unbatch(out, has_c, ninst, n_out)
+
+    @staticmethod
+    def pc_tail(A, B, C, W, t_out, tau, rs, fold_r=None, top=False):
+        """dev_pc_tail with the host's side of its rounds.  Returns (sums (rounds, ninst, 3, 32), tables per instance [A, B, C or None] of t_out elements)"""
+        a, b, c, has_c, ninst, n = kernels._batch(A, B, C)
+        rr = None if fold_r is None else _scalars(fold_r, "fold_r")
+        len0 = n if rr is None else n // 2
+        tau, rs = _scalars(tau, "tau"), _scalars(rs, "rs")
+        W, t_out = int(W), int(t_out)
+        ok = ninst and W > 0 and t_out > 0 and len0 > t_out and len0 & (len0 - 1) == 0 and t_out & (t_out - 1) == 0
+        rounds = (len0.bit_length() - t_out.bit_length()) if ok else 1
+        if ok and (tau.shape[0] != len0.bit_length() - 1 or rs.shape[0] != rounds):
+            raise SpartanError(-21, "tau: log2(len0) variables; rs: one challenge per round")
+        sums = np.zeros((rounds, max(ninst, 1), 3, 32), dtype=np.uint8); out = np.zeros((3 * max(ninst, 1) * t_out, 32), dtype=np.uint8)
+        _check(lib.otti_k_pc_tail(_ptr(a), _ptr(b), _ptr(c), _ptr(has_c), ninst, len0, W, t_out, _ptr(tau), _ptr(rs), _ptr(rr), 1 if top else 0, _ptr(sums), _ptr(out)))
+        return sums, kernels._unbatch(out, has_c, ninst, t_out)
+
+    @staticmethod
+    def prod_layer(in_left, in_right):
+        """dev_prod_layer: per circuit (out_left, out_right), each half as long as the inputs"""
+        if len(in_left) != len(in_right):
+            raise SpartanError(-21, "one left and one right input per circuit")
+        l, n = kernels._stack(in_left, "in_left"); r, _ = kernels._stack(in_right, "in_right", n)
+        if n % 2:
+            raise SpartanError(-21, "a layer's inputs have an even number of elements")
+        k, q = len(in_left), n // 2
+        ol, orr = (np.zeros((max(k * q, 1), 32), dtype=np.uint8) for _ in range(2)); ms = ctypes.c_float(0)
+        _check(lib.otti_k_prod_layer(_ptr(l), _ptr(r), k, q, _ptr(ol), _ptr(orr), ctypes.byref(ms)))
+        return [(ol[y * q:(y + 1) * q], orr[y * q:(y + 1) * q]) for y in range(k)], ms.value
+
+    @staticmethod
+    def hash_mem(eval_table, audit_ts, r, gamma, G=1, rk=0):
+        """dev_hash_mem: (init, audit) hashes of rank rk's residue class (M / G elements each)"""
+        ev, n = kernels._stack([eval_table], "eval_table"); au, _ = kernels._stack([audit_ts], "audit_ts", n)
+        r, gamma = _scalars(r, "r"), _scalars(gamma, "gamma")
+        o = [np.zeros((max(n // G, 1), 32), dtype=np.uint8) for _ in range(2)]; ms = ctypes.c_float(0)
+        _check(lib.otti_k_hash_mem(_ptr(ev), _ptr(au), n, _ptr(r), _ptr(gamma), G, rk, _ptr(o[0]), _ptr(o[1]), ctypes.byref(ms)))
+        return o[0], o[1], ms.value
+
+    @staticmethod
+    def hash_ops(addr, deref, read_ts, r, gamma, G=1, rk=0):
+        """dev_hash_ops: (read, write) hashes of rank rk's residue class (N / G elements each)"""
+        ad, n = kernels._stack([addr], "addr"); de, _ = kernels._stack([deref], "deref", n); ts, _ = kernels._stack([read_ts], "read_ts", n)
+        r, gamma = _scalars(r, "r"), _scalars(gamma, "gamma")
+        o = [np.zeros((max(n // G, 1), 32), dtype=np.uint8) for _ in range(2)]; ms = ctypes.c_float(0)
+        _check(lib.otti_k_hash_ops(_ptr(ad), _ptr(de), _ptr(ts), n, _ptr(r), _ptr(gamma), G, rk, _ptr(o[0]), _ptr(o[1]), ctypes.byref(ms)))
+        return o[0], o[1], ms.value
+
+    @staticmethod
+    def dot_many(E, Ps):
+        """dev_dot_many: <E, P> for every polynomial of the list"""
+        e, n = kernels._stack([E], "E"); p, _ = kernels._stack(Ps, "Ps", n)
+        out = np.zeros((max(len(Ps), 1), 32), dtype=np.uint8); ms = ctypes.c_float(0)
+        _check(lib.otti_k_dot_many(_ptr(e), _ptr(p), len(Ps), n, _ptr(out), ctypes.byref(ms)))
+        return out, ms.value
+
+    @staticmethod
+    def sum3(A, B, C):
+        """dev_sum3: sum_i A[i] B[i] C[i] for every triple of the lists"""
+        if not (len(A) == len(B) == len(C)):
+            raise SpartanError(-21, "one A, B and C table per triple")
+        a, n = kernels._stack(A, "A"); b, _ = kernels._stack(B, "B", n); c, _ = kernels._stack(C, "C", n)
+        out = np.zeros((max(len(A), 1), 32), dtype=np.uint8); ms = ctypes.c_float(0)
+        _check(lib.otti_k_sum3(_ptr(a), _ptr(b), _ptr(c), len(A), n, _ptr(out), ctypes.byref(ms)))
+        return out, ms.value
+
+    @staticmethod
+    def poly_bound_chunks(Z, L, R, Lv_rest):
+        """dev_poly_bound_chunks with m = len(Lv_rest) rows per chunk: (L / m, R, 32), or None when the launch function declines the geometry"""
+        Z, lv = _scalars(Z, "Z"), _scalars(Lv_rest, "Lv_rest"); m = lv.shape[0]
+        if Z.shape[0] != L * R:
+            raise SpartanError(-21, "Z: L * R elements")
+        out = np.zeros((max(L // max(m, 1), 1) * R, 32), dtype=np.uint8); ok = _i32(0); ms = ctypes.c_float(0)
+        _check(lib.otti_k_poly_bound_chunks(_ptr(Z), L, R, _ptr(lv), m, _ptr(out), ctypes.byref(ok), ctypes.byref(ms)))
+        return out.reshape(-1, R, 32) if ok.value else None
 
 
 class DeviceArray:

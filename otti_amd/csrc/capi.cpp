@@ -919,6 +919,165 @@ int32_t otti_k_bullet_last_fold(size_t R, const uint8_t *u, const uint8_t *uinv,
     });
 }
 
+// ---- SNARK mode's kernels (k_snark.hip, snark_dev.h): each entry stages the caller's tables and calls the launch function snark_prover.cpp calls.
+// Lists travel as ONE array: instance y's table at element y * len; third tables only for the instances that have one (has_C[y] != 0), in order.
+extern "C++" {
+namespace {
+constexpr int kKSumSlot = 64, kKTailSlot = 128;              // where the prover puts a round's sums / the handed-over tables (snark_prover.cpp)
+bool pow2(size_t x) { return x && !(x & (x - 1)); }
+struct StagedPc {
+    std::unique_ptr<Staged> a, b, cc; PcList L; size_t nC = 0;
+    StagedPc(DevCtx &c, const uint8_t *A, const uint8_t *B, const uint8_t *C, const uint8_t *has_C, size_t ninst, size_t len) {
+        for (size_t y = 0; y < ninst; y++) nC += has_C[y] ? 1 : 0;
+        a = std::make_unique<Staged>(c, A, ninst * len); b = std::make_unique<Staged>(c, B, ninst * len); cc = std::make_unique<Staged>(c, C, nC * len);
+        L.n = (int)ninst; size_t k = 0;
+        for (size_t y = 0; y < ninst; y++) { L.A[y] = a->d.p + y * len; L.B[y] = b->d.p + y * len; L.C[y] = has_C[y] ? cc->d.p + (k++) * len : nullptr; }
+    }
+};
+void check_pc_list(const uint8_t *A, const uint8_t *B, const uint8_t *C, const uint8_t *has_C, size_t ninst, size_t len) {
+    if (ninst < 1 || ninst > (size_t)kMaxInst) throw Error(OTTI_ERR_BAD_ARG, "a batch has 1 .. kMaxInst instances");
+    if (!A || !B || !has_C) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+    if (!pow2(len)) throw Error(OTTI_ERR_BAD_ARG, "table length must be a power of two");
+    for (size_t y = 0; y < ninst; y++) if (has_C[y] && !C) throw Error(OTTI_ERR_BAD_ARG, "an instance with a third table, but no third tables");
+}
+}  // namespace
+}  // extern "C++"
+
+int32_t otti_k_pc_round(const uint8_t *A, const uint8_t *B, const uint8_t *C, const uint8_t *has_C, size_t ninst, size_t len, const uint8_t *tau, const uint8_t *r,
+                        uint32_t G, uint32_t rk, uint8_t *out, uint8_t *e, float *ms) {
+    return guarded([&] {
+        check_pc_list(A, B, C, has_C, ninst, len);
+        if (!e || (r && !out)) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (len < (r ? 4u : 2u)) throw Error(OTTI_ERR_BAD_ARG, "table length must be >= 2 (>= 4 with a fold)");
+        if (!pow2(G) || rk >= G) throw Error(OTTI_ERR_BAD_ARG, "G must be a power of two and rk below it");
+        const size_t items = len / (r ? 4 : 2), m = ilog2(items * G);               // the eq table covers every rank's items
+        if (m > 25 || (m && !tau)) throw Error(OTTI_ERR_BAD_ARG, "eq table over more than 25 variables, or no tau");
+        DevCtx &c = DevCtx::get(); StagedPc T(c, A, B, C, has_C, ninst, len);
+        std::vector<Fr> t = fr_load_vec(tau, m); EqPyramids py(c, t.data(), m);
+        EqSrc E = py.top(); E.stride = G; E.offset = rk;
+        const Fr rr = r ? fr_load(r) : fr_zero();
+        KTimer tm(c, ms); auto tk = r ? dev_pc_fold_eval(c, T.L, len, &rr, E, kKSumSlot) : dev_pc_eval(c, T.L, len, E, kKSumSlot); tm.stop();
+        if (r) { const size_t h = len / 2; uint8_t *o = out;
+            for (size_t y = 0; y < ninst; y++, o += 32 * h) download(c, o, T.L.A[y], h);
+            for (size_t y = 0; y < ninst; y++, o += 32 * h) download(c, o, T.L.B[y], h);
+            for (size_t y = 0; y < ninst; y++) if (T.L.C[y]) { download(c, o, T.L.C[y], h); o += 32 * h; } }
+        c.sync(); c.wait_ticket(tk); memcpy(e, &c.h_results[kKSumSlot], 96 * ninst); return OTTI_OK;
+    });
+}
+int32_t otti_k_pc_export(const uint8_t *A, const uint8_t *B, const uint8_t *C, const uint8_t *has_C, size_t ninst, size_t len, const uint8_t *fold_r, uint8_t *out) {
+    return guarded([&] {
+        check_pc_list(A, B, C, has_C, ninst, len);
+        if (!out) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (fold_r && len < 2) throw Error(OTTI_ERR_BAD_ARG, "table length must be >= 2 with a fold");
+        const size_t n_out = fold_r ? len / 2 : len;
+        if (kKTailSlot + 3 * ninst * n_out > (size_t)kResultSlots) throw Error(OTTI_ERR_BAD_ARG, "the exported tables do not fit the pinned result buffer");
+        DevCtx &c = DevCtx::get(); StagedPc T(c, A, B, C, has_C, ninst, len);
+        const Fr rr = fold_r ? fr_load(fold_r) : fr_zero();
+        memset(&c.h_results[kKTailSlot], 0, 96 * ninst * n_out);                      // (an absent third table's place is not written)
+        auto tk = dev_pc_export(c, T.L, len, fold_r != nullptr, fold_r ? &rr : nullptr, kKTailSlot);
+        c.wait_ticket(tk); memcpy(out, &c.h_results[kKTailSlot], 96 * ninst * n_out); c.sync(); return OTTI_OK;
+    });
+}
+// the rounds of one persistent launch played as pcbatch_prove plays them: per round the W * ninst mail lines summed per instance, then the challenge
+int32_t otti_k_pc_tail(const uint8_t *A, const uint8_t *B, const uint8_t *C, const uint8_t *has_C, size_t ninst, size_t len0, uint32_t W, size_t t_out,
+                       const uint8_t *tau, const uint8_t *rs, const uint8_t *fold_r, int32_t top, uint8_t *sums, uint8_t *out) {
+    return guarded([&] {
+        check_pc_list(A, B, C, has_C, ninst, len0);
+        if (!tau || !rs || !sums || !out) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (!pow2(W) || !pow2(t_out) || ninst * W > (size_t)kTailMaxGroups || len0 / W > (size_t)kTailCap || t_out < W || len0 <= t_out)
+            throw Error(OTTI_ERR_BAD_ARG, "persistent sum-check tail: W and t_out powers of two, W <= t_out < len0, at most kTailCap elements per workgroup, at most kTailMaxGroups workgroups");
+        if (kKTailSlot + 3 * ninst * t_out > (size_t)kResultSlots) throw Error(OTTI_ERR_BAD_ARG, "the handed-over tables do not fit the pinned result buffer");
+        const size_t nt = ilog2(len0), rounds = nt - ilog2(t_out);
+        DevCtx &c = DevCtx::get();
+        if (!c.armed_ok()) throw Error(OTTI_ERR_BAD_ARG, "armed launches are off: the prover would not launch the persistent tail");
+        if (ninst * W > (size_t)std::min(kTailMaxGroups, c.num_cu)) throw Error(OTTI_ERR_BAD_ARG, "more workgroups than the device has CUs: the grid would not be resident as a whole");
+        StagedPc T(c, A, B, C, has_C, ninst, fold_r ? 2 * len0 : len0);
+        std::vector<Fr> t = fr_load_vec(tau, nt), rr = fr_load_vec(rs, rounds);
+        const size_t mt = top ? nt - 1 : nt;                                            // tabulated variables; top: tau[0] travels as EqSrc.top
+        EqPyramids py(c, t.data() + (top ? 1 : 0), mt);
+        EqSrc E = py.top(); if (top) { E.top_bit = (int)mt; E.top = t[0]; }
+        const Fr fr = fold_r ? fr_load(fold_r) : fr_zero();
+        memset(&c.h_results[kKTailSlot], 0, 96 * ninst * t_out);
+        SpinPool::Session pool_session;
+        struct Release { DevCtx &c; ~Release() { c.go_abort(); } } release{c};          // an exception must not leave the grid waiting for the host
+        const unsigned long long seq0 = dev_pc_tail(c, T.L, (int)W, len0, t_out, fold_r ? &fr : nullptr, E, kKTailSlot);
+        for (size_t j = 0; j < rounds; j++) {
+            Fr s[3 * kMaxInst];
+            c.wait_tail_sums((int)ninst, (int)W, seq0 + j, s);
+            memcpy(sums + 96 * ninst * j, s, 96 * ninst);
+            c.go(&rr[j], 1);
+        }
+        c.wait_tail((int)(ninst * W), seq0 + rounds);
+        memcpy(out, &c.h_results[kKTailSlot], 96 * ninst * t_out);
+        c.sync(); return OTTI_OK;
+    });
+}
+int32_t otti_k_prod_layer(const uint8_t *left, const uint8_t *right, size_t ninst, size_t q, uint8_t *out_left, uint8_t *out_right, float *ms) {
+    return guarded([&] {
+        if (!left || !right || !out_left || !out_right) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (ninst < 1 || ninst > 16 || q < 1) throw Error(OTTI_ERR_BAD_ARG, "a layer has 1 .. 16 circuits of at least one pair");
+        DevCtx &c = DevCtx::get(); Staged l(c, left, ninst * 2 * q), r(c, right, ninst * 2 * q); DevBuf<Fr> ol(ninst * q), orr(ninst * q);
+        LayerList L; L.n = (int)ninst;
+        for (size_t y = 0; y < ninst; y++) { L.in_left[y] = l.d.p + y * 2 * q; L.in_right[y] = r.d.p + y * 2 * q; L.out_left[y] = ol.p + y * q; L.out_right[y] = orr.p + y * q; }
+        KTimer tm(c, ms); dev_prod_layer(c, L, q); tm.stop();
+        download(c, out_left, ol.p, ninst * q); download(c, out_right, orr.p, ninst * q); c.sync(); return OTTI_OK;
+    });
+}
+static void check_shard(size_t n, uint32_t G, uint32_t rk) {
+    if (!pow2(n) || !pow2(G) || rk >= G || n / G < 2) throw Error(OTTI_ERR_BAD_ARG, "hash layer: n and G powers of two, rk < G, at least two elements per rank");
+}
+int32_t otti_k_hash_mem(const uint8_t *eval_table, const uint8_t *audit_ts, size_t M, const uint8_t *r, const uint8_t *gamma, uint32_t G, uint32_t rk,
+                        uint8_t *out_init, uint8_t *out_audit, float *ms) {
+    return guarded([&] {
+        if (!eval_table || !audit_ts || !r || !gamma || !out_init || !out_audit) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        check_shard(M, G, rk);
+        DevCtx &c = DevCtx::get(); Staged ev(c, eval_table, M), au(c, audit_ts, M); const size_t Ml = M / G; DevBuf<Fr> oi(Ml), oa(Ml);
+        KTimer tm(c, ms); dev_hash_mem(c, ev.d.p, au.d.p, oi.p, oa.p, M, fr_load(r), fr_load(gamma), (int)G, (int)rk); tm.stop();
+        download(c, out_init, oi.p, Ml); download(c, out_audit, oa.p, Ml); c.sync(); return OTTI_OK;
+    });
+}
+int32_t otti_k_hash_ops(const uint8_t *addr, const uint8_t *deref, const uint8_t *read_ts, size_t N, const uint8_t *r, const uint8_t *gamma, uint32_t G, uint32_t rk,
+                        uint8_t *out_read, uint8_t *out_write, float *ms) {
+    return guarded([&] {
+        if (!addr || !deref || !read_ts || !r || !gamma || !out_read || !out_write) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        check_shard(N, G, rk);
+        DevCtx &c = DevCtx::get(); Staged ad(c, addr, N), de(c, deref, N), ts(c, read_ts, N); const size_t Nl = N / G; DevBuf<Fr> ord(Nl), owr(Nl);
+        KTimer tm(c, ms); dev_hash_ops(c, ad.d.p, de.d.p, ts.d.p, ord.p, owr.p, N, fr_load(r), fr_load(gamma), (int)G, (int)rk); tm.stop();
+        download(c, out_read, ord.p, Nl); download(c, out_write, owr.p, Nl); c.sync(); return OTTI_OK;
+    });
+}
+int32_t otti_k_dot_many(const uint8_t *E, const uint8_t *Ps, size_t npoly, size_t n, uint8_t *out, float *ms) {
+    return guarded([&] {
+        if (!E || !Ps || !out) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (npoly < 1 || npoly > 64 || n < 1) throw Error(OTTI_ERR_BAD_ARG, "1 .. 64 polynomials of at least one element");
+        DevCtx &c = DevCtx::get(); Staged e(c, E, n), p(c, Ps, npoly * n); DevBuf<Fr> partials((size_t)3 * 2048 + 64);   // as the prover sizes it: 3 sums x at most 2048 workgroups per launch (k_snark.hip many_grid)
+        PtrList L; L.n = (int)npoly; for (size_t y = 0; y < npoly; y++) L.p[y] = p.d.p + y * n;
+        KTimer tm(c, ms); dev_dot_many(c, e.d.p, L, n, partials.p, kKSumSlot); tm.stop();
+        c.sync(); memcpy(out, &c.h_results[kKSumSlot], 32 * npoly); return OTTI_OK;
+    });
+}
+int32_t otti_k_sum3(const uint8_t *A, const uint8_t *B, const uint8_t *C, size_t ninst, size_t n, uint8_t *out, float *ms) {
+    return guarded([&] {
+        if (!A || !B || !C || !out) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (ninst < 1 || ninst > (size_t)kMaxInst || n < 1) throw Error(OTTI_ERR_BAD_ARG, "1 .. kMaxInst triples of at least one element");
+        DevCtx &c = DevCtx::get(); Staged a(c, A, ninst * n), b(c, B, ninst * n), cc(c, C, ninst * n); DevBuf<Fr> partials((size_t)3 * 2048 + 64);   // as the prover sizes it: 3 sums x at most 2048 workgroups per launch (k_snark.hip many_grid)
+        AbcList L; L.n = (int)ninst; for (size_t y = 0; y < ninst; y++) { L.A[y] = a.d.p + y * n; L.B[y] = b.d.p + y * n; L.C[y] = cc.d.p + y * n; }
+        KTimer tm(c, ms); dev_sum3(c, L, n, partials.p, kKSumSlot); tm.stop();
+        c.sync(); memcpy(out, &c.h_results[kKSumSlot], 32 * ninst); return OTTI_OK;
+    });
+}
+int32_t otti_k_poly_bound_chunks(const uint8_t *Z, size_t L, size_t R, const uint8_t *Lv_rest, size_t m, uint8_t *out, int32_t *launched, float *ms) {
+    return guarded([&] {
+        if (!Z || !Lv_rest || !out || !launched) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (!L || !R || !m) throw Error(OTTI_ERR_BAD_ARG, "empty matrix");
+        DevCtx &c = DevCtx::get(); Staged z(c, Z, L * R), lv(c, Lv_rest, m); DevBuf<Fr> o(std::max<size_t>(1, (L / m) * R)), scratch(64 * R);
+        KTimer tm(c, ms); const bool ok = dev_poly_bound_chunks(c, z.d.p, L, R, lv.d.p, m, o.p, scratch.p); tm.stop();
+        *launched = ok ? 1 : 0;
+        if (ok) download(c, out, o.p, (L / m) * R);
+        c.sync(); return OTTI_OK;
+    });
+}
+
 // ---- device pointers + caller's stream
 static const Fr *dfr(const void *p) { return reinterpret_cast<const Fr *>(p); }
 static Fr *dfr(void *p) { return reinterpret_cast<Fr *>(p); }

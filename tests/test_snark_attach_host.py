@@ -46,8 +46,13 @@ def _spzk(*args):
 
 
 def test_new_symbols_are_exported():
-    for name in ("otti_comp_comm_attach", "otti_comp_comm_dims", "otti_k_addr_timestamps", "otti_snark_gens_points", "otti_zkif_load_inputs"):
+    for name in ("otti_comp_comm_attach", "otti_comp_comm_dims", "otti_k_addr_timestamps", "otti_snark_gens_points", "otti_zkif_load_inputs",
+                 "otti_k_pc_round", "otti_k_pc_export", "otti_k_pc_tail", "otti_k_prod_layer", "otti_k_hash_mem", "otti_k_hash_ops", "otti_k_dot_many",
+                 "otti_k_sum3", "otti_k_poly_bound_chunks"):
         assert hasattr(oa.lib, name), name
+    header = open(os.path.join(os.path.dirname(HERE), "include", "otti_spartan.h")).read()
+    for name in ("pc_round", "pc_export", "pc_tail", "prod_layer", "hash_mem", "hash_ops", "dot_many", "sum3", "poly_bound_chunks"):
+        assert callable(getattr(oa.kernels, name)) and f"int32_t otti_k_{name}(" in header, name
     assert callable(oa.ComputationCommitment.attach) and callable(oa.kernels.addr_timestamps)
 
 
@@ -85,6 +90,55 @@ def test_attach_reports_argument_errors_before_touching_a_device(oracle_case):
     with pytest.raises(oa.SpartanError) as ex:                     # the kernel entry checks its lists before the device as well
         oa.kernels.addr_timestamps(np.full((3, 4), 4, dtype=np.uint32), 4)
     assert ex.value.code == BAD_ARG
+
+
+def test_snark_kernel_entries_check_their_arguments_before_touching_a_device():
+    """unequal table lengths, batches of 0 and 21 instances, a table of 3 elements, a tail of 3 workgroups per instance, and the other geometries
+    the launch functions have no answer for: the library's bad-argument error, with or without a device (nothing is launched)"""
+    K = oa.kernels
+    z = lambda n: np.zeros((n, 32), dtype=np.uint8)
+    bad = [
+        lambda: K.pc_round([z(4), z(4)], [z(4), z(2)], [None, None], z(1)),                   # unequal lengths
+        lambda: K.pc_round([z(4)], [z(4)], [z(2)], z(1)),
+        lambda: K.pc_round([], [], [], z(0)),                                                 # ninst = 0
+        lambda: K.pc_round([z(4)] * 21, [z(4)] * 21, [None] * 21, z(1)),                      # ninst = 21
+        lambda: K.pc_round([z(3)], [z(3)], [None], z(0)),                                     # len = 3
+        lambda: K.pc_round([z(2)], [z(2)], [None], z(0), z(1)),                               # a fold needs len >= 4
+        lambda: K.pc_round([z(8)], [z(8)], [None], z(3), None, 3, 0),                         # G = 3
+        lambda: K.pc_round([z(8)], [z(8)], [None], z(3), None, 2, 2),                         # rk = G
+        lambda: K.pc_export([z(4)], [z(2)], [None]),
+        lambda: K.pc_export([], [], []),
+        lambda: K.pc_export([z(4)] * 21, [z(4)] * 21, [None] * 21),
+        lambda: K.pc_export([z(3)], [z(3)], [None]),
+        lambda: K.pc_export([z(256)] * 11, [z(256)] * 11, [z(256)] * 11),                     # more than the result buffer holds
+        lambda: K.pc_tail([z(64)] * 2, [z(64)] * 2, [None] * 2, 3, 4, z(6), z(4)),            # W = 3
+        lambda: K.pc_tail([z(64)], [z(32)], [None], 2, 4, z(6), z(4)),
+        lambda: K.pc_tail([], [], [], 1, 4, z(6), z(4)),
+        lambda: K.pc_tail([z(64)] * 21, [z(64)] * 21, [None] * 21, 1, 4, z(6), z(4)),
+        lambda: K.pc_tail([z(48)], [z(48)], [None], 1, 4, z(5), z(3)),                        # len0 = 48
+        lambda: K.pc_tail([z(64)], [z(64)], [None], 2, 1, z(6), z(6)),                        # t_out < W
+        lambda: K.pc_tail([z(64)], [z(64)], [None], 1, 64, z(6), z(1)),                       # no round to play
+        lambda: K.pc_tail([z(4096)], [z(4096)], [None], 2, 4, z(12), z(10)),                  # 2048 elements per workgroup
+        lambda: K.pc_tail([z(64)] * 18, [z(64)] * 18, [None] * 18, 16, 16, z(6), z(2)),       # 288 workgroups
+        lambda: K.prod_layer([z(4), z(8)], [z(4), z(8)]),
+        lambda: K.prod_layer([z(4)] * 17, [z(4)] * 17),
+        lambda: K.prod_layer([], []),
+        lambda: K.hash_mem(z(8), z(4), z(1), z(1)),
+        lambda: K.hash_mem(z(12), z(12), z(1), z(1)),
+        lambda: K.hash_mem(z(4), z(4), z(1), z(1), 4, 0),                                     # one element per rank
+        lambda: K.hash_ops(z(8), z(8), z(4), z(1), z(1)),
+        lambda: K.hash_ops(z(8), z(8), z(8), z(1), z(1), 2, 2),
+        lambda: K.dot_many(z(4), [z(4), z(2)]),
+        lambda: K.dot_many(z(4), [z(4)] * 65),
+        lambda: K.dot_many(z(4), []),
+        lambda: K.sum3([z(4)], [z(4)], [z(2)]),
+        lambda: K.sum3([z(4)] * 21, [z(4)] * 21, [z(4)] * 21),
+        lambda: K.poly_bound_chunks(z(12), 4, 4, z(2)),
+    ]
+    for k, f in enumerate(bad):
+        with pytest.raises(oa.SpartanError) as ex:
+            f()
+        assert ex.value.code == BAD_ARG, (k, str(ex.value))
 
 
 def test_generators_made_from_dims_alone_equal_the_encoders(oracle_case):
