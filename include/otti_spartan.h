@@ -94,6 +94,38 @@ int32_t otti_nizk_prove(otti_instance *inst, const uint8_t *vars32, size_t nvars
 typedef struct otti_witness otti_witness;
 int32_t otti_witness_upload(otti_instance *inst, const uint8_t *vars32, size_t nvars, const uint8_t *inputs32, size_t ninputs, otti_witness **out);
 void    otti_witness_free(otti_witness *w);
+/* ---- the resident assignment filled from where witnesses live: device memory (a solver's output, an otti_kd_* result), machine integers, and
+   changed in place.  The resulting z is bit for bit what otti_witness_upload builds from the same values (vars || 0.. || 1 || inputs || 0.. in
+   Montgomery form, small_fraction by the same rule: canonical value below 2^128, padding zeros small, a negative I64 not), so every proof from it
+   is byte-identical.  Validation runs on the device: a CANONICAL32 / MONTGOMERY32 element whose raw value is >= l gives OTTI_ERR_INVALID_SCALAR
+   (no witness is returned, *out is untouched; an update leaves the resident vector exactly as it was); the integer formats cannot fail it.
+   Argument errors are reported before any device is touched: OTTI_ERR_BAD_ARG for a null inst / out / wit, a null source with a non-zero count,
+   an unknown format, a non-zero stride_bytes below the element size or not a multiple of 8, a device source that is not 8-byte aligned;
+   OTTI_ERR_INVALID_NUM_VARS for nvars (or first + count) above the padded num_vars; OTTI_ERR_INVALID_NUM_INPUTS; then OTTI_ERR_NO_DEVICE. */
+enum { OTTI_WIT_CANONICAL32 = 0,   /* 32-byte little-endian, must be < l (as otti_witness_upload) */
+       OTTI_WIT_MONTGOMERY32 = 1,  /* the in-HBM layout (value * 2^256 mod l), raw value must be < l: what otti_kd_* kernels write */
+       OTTI_WIT_I64 = 2,           /* signed 64-bit: x >= 0 -> x, x < 0 -> l - |x| (INT64_MIN included) */
+       OTTI_WIT_U64 = 3 };
+/* vars in DEVICE memory.  stride_bytes: distance between elements (0 = packed).
+   stream: the caller's hipStream_t whose queued work produces d_vars (NULL = the calling thread's library stream): the ingest is ordered after
+   what is already queued there (an event recorded on it, which the library's stream waits for).
+   NULL names no stream to wait for: a producer on HIP's null (legacy default) stream cannot be named, so its caller synchronises first
+   (the library's streams are non-blocking and are not ordered against the null stream).
+   Returns after the ingest has finished: d_vars is free again. */
+int32_t otti_witness_from_device(otti_instance *inst, const void *d_vars, size_t nvars, int32_t format, size_t stride_bytes,
+                                 const uint8_t *inputs32, size_t ninputs, void *stream, otti_witness **out);
+/* vars as HOST integers (OTTI_WIT_I64 / OTTI_WIT_U64 only, packed): 8 bytes per variable cross PCIe, widened on the device */
+int32_t otti_witness_upload_ints(otti_instance *inst, const void *vars, size_t nvars, int32_t format,
+                                 const uint8_t *inputs32, size_t ninputs, otti_witness **out);
+/* replaces variables [first, first + count) of a resident witness.  src is host memory (src_on_device = 0) or device memory (then stream as
+   above).  Afterwards small_fraction is right again (one recount pass).  Never while a proof or check with this witness is running.
+   A device source must not overlap the witness's own vector (the d_z of otti_witness_info): elements are read and written by different
+   lanes in no order.  To move a range within z, copy it out first. */
+int32_t otti_witness_update(otti_instance *inst, otti_witness *wit, size_t first, const void *src, size_t count, int32_t format,
+                            size_t stride_bytes, int32_t src_on_device, void *stream);
+/* the resident vector.  d_z holds n = 2 * padded num_vars Montgomery elements, usable with otti_kd_*.
+   small_fraction is the share below 2^128 that picks the commitment's MSM variant.  Any out pointer may be NULL. */
+int32_t otti_witness_info(const otti_witness *wit, const void **d_z, size_t *n, double *small_fraction);
 int32_t otti_nizk_prove_resident(otti_instance *inst, otti_witness *wit, otti_gens *gens, const uint8_t *tlabel, size_t tlabel_len,
                                  const uint8_t *seed32, uint8_t **proof, size_t *proof_len, double *stage_ms);
 /* Instance::is_sat on the assignment resident in HBM, with a diagnosis.  *n_unsat: number of constraints with <A_r,z>·<B_r,z> != <C_r,z>.

@@ -3,6 +3,7 @@
 rust-circ `--action spartan` [REF /root/reference/run.py:147] call."""
 import ctypes
 import os
+import sys
 import numpy as np
 
 L_ORDER = 2 ** 252 + 27742317777372353535851937790883648493
@@ -80,6 +81,10 @@ _sig("otti_nizk_prove", _i32, _vp, _vp, _sz, _vp, _sz, _vp, ctypes.c_char_p, _sz
      ctypes.POINTER(_vp), ctypes.POINTER(_sz), ctypes.POINTER(ctypes.c_double))
 _sig("otti_witness_upload", _i32, _vp, _vp, _sz, _vp, _sz, ctypes.POINTER(_vp))
 _sig("otti_witness_free", None, _vp)
+_sig("otti_witness_from_device", _i32, _vp, _vp, _sz, _i32, _sz, _vp, _sz, _vp, ctypes.POINTER(_vp))
+_sig("otti_witness_upload_ints", _i32, _vp, _vp, _sz, _i32, _vp, _sz, ctypes.POINTER(_vp))
+_sig("otti_witness_update", _i32, _vp, _vp, _sz, _vp, _sz, _i32, _sz, _i32, _vp)
+_sig("otti_witness_info", _i32, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_sz), ctypes.POINTER(ctypes.c_double))
 _sig("otti_witness_check_sat", _i32, _vp, _vp, ctypes.POINTER(_u64), _vp, _sz, _vp, ctypes.POINTER(ctypes.c_float))
 _sig("otti_nizk_prove_resident", _i32, _vp, _vp, _vp, ctypes.c_char_p, _sz, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_sz),
      ctypes.POINTER(ctypes.c_double))
@@ -385,6 +390,46 @@ class SatReport:
         return f"SatReport(n_unsat={self.n_unsat}, rows={self.rows.tolist()})"
 
 
+WIT_CANONICAL32, WIT_MONTGOMERY32, WIT_I64, WIT_U64 = 0, 1, 2, 3   # OTTI_WIT_*
+
+
+def _dev_addr(p):
+    return p.ptr if hasattr(p, "ptr") else p
+
+
+def _int_array(a):
+    a = np.asarray(a)
+    if a.dtype not in (np.int64, np.uint64) or a.ndim != 1:
+        raise ValueError("expected a 1-D numpy array of int64 or uint64")
+    return np.ascontiguousarray(a), WIT_I64 if a.dtype == np.int64 else WIT_U64
+
+
+def _tensor_layout(torch, t):
+    """(format, count, stride_bytes) of a GPU tensor Witness.from_tensor / update take"""
+    if not t.is_cuda:
+        raise ValueError("expected a tensor on the GPU")
+    if t.dtype == torch.int64 and t.dim() == 1:
+        if t.shape[0] > 1 and t.stride(0) < 1:
+            raise ValueError("an int64 tensor needs a positive stride")
+        return WIT_I64, t.shape[0], t.stride(0) * 8 if t.shape[0] > 1 else 0
+    if t.dtype == torch.uint8 and t.dim() == 2 and t.shape[1] == 32 and t.is_contiguous():
+        return WIT_CANONICAL32, t.shape[0], 0
+    raise ValueError("expected a 1-D int64 tensor or a contiguous uint8 tensor of shape (n, 32)")
+
+
+def _torch_stream(torch, t, stream):
+    """the hipStream_t to order an ingest of tensor t after: the given one, else torch's current stream on t's device.  torch's default stream
+    is HIP's null stream, handle 0, which the C ABI reads as "no stream to wait for" and the library's non-blocking stream is not ordered
+    against: its pending work is waited for here, on the host"""
+    if stream is not None:
+        return stream
+    cur = torch.cuda.current_stream(t.device)
+    if not cur.cuda_stream:
+        cur.synchronize()
+        return None
+    return cur.cuda_stream
+
+
 class Witness:
     """Assignment resident in HBM (z = vars || 1 || inputs || 0..): upload once, prove many times."""
 
@@ -393,6 +438,74 @@ class Witness:
         h = _vp()
         _check(lib.otti_witness_upload(inst._h, _ptr(v), v.shape[0], _ptr(i), i.shape[0], ctypes.byref(h)))
         self._h = h
+
+    @classmethod
+    def _adopt(cls, handle):
+        w = cls.__new__(cls)
+        w._h = handle
+        return w
+
+    @classmethod
+    def from_device(cls, inst, ptr, nvars, fmt, inputs, stride_bytes=0, stream=None):
+        """From ``nvars`` elements in device memory at address ``ptr`` (an int or a DeviceArray) in format ``fmt`` (WIT_*), ``stride_bytes`` apart
+        (0: packed); ``stream``: the hipStream_t whose queued work writes them (otti_witness_from_device)."""
+        i = _scalars(inputs.assignment, "inputs")
+        h = _vp()
+        _check(lib.otti_witness_from_device(inst._h, _dev_addr(ptr), nvars, fmt, stride_bytes, _ptr(i), i.shape[0], stream, ctypes.byref(h)))
+        return cls._adopt(h)
+
+    @classmethod
+    def from_ints(cls, inst, array, inputs):
+        """From a host numpy array of int64 (WIT_I64) or uint64 (WIT_U64): 8 bytes per variable cross PCIe (otti_witness_upload_ints)"""
+        a, fmt = _int_array(array)
+        i = _scalars(inputs.assignment, "inputs")
+        h = _vp()
+        _check(lib.otti_witness_upload_ints(inst._h, _ptr(a), a.size, fmt, _ptr(i), i.shape[0], ctypes.byref(h)))
+        return cls._adopt(h)
+
+    @classmethod
+    def from_tensor(cls, inst, tensor, inputs, stream=None):
+        """From a torch tensor on the GPU: 1-D int64 (contiguous or a strided view) as WIT_I64, uint8 of shape (n, 32) as WIT_CANONICAL32.
+        ``stream`` defaults to torch's current stream, whose queued work is waited for on the device; when that is torch's default stream
+        (HIP's null stream, which the C ABI cannot name) it is synchronised on the host instead.  torch has to be imported before otti_amd
+        so that both use one HIP runtime."""
+        import torch
+        fmt, nvars, stride = _tensor_layout(torch, tensor)
+        return cls.from_device(inst, tensor.data_ptr(), nvars, fmt, inputs, stride, _torch_stream(torch, tensor, stream))
+
+    def update(self, inst, first, values, fmt=None, stride_bytes=0, stream=None):
+        """Replace variables [first, first + count) in place (otti_witness_update).  ``values``: a numpy int64 / uint64 array or (n, 32) uint8
+        canonical scalars on the host; a torch GPU tensor (as from_tensor); or ``(address, count)`` of device memory with ``fmt`` given.
+        A scalar >= l raises R1CSError(-5) and leaves the witness as it was."""
+        if isinstance(values, tuple):
+            if fmt is None:
+                raise ValueError("update from a device address needs fmt")
+            src, count, on_device = _dev_addr(values[0]), values[1], 1
+        elif isinstance(values, np.ndarray):
+            if values.dtype in (np.int64, np.uint64):
+                keep, f = _int_array(values)
+                count = keep.size
+            else:
+                keep, f = _scalars(values, "values"), WIT_CANONICAL32
+                count = keep.shape[0]
+            fmt = f if fmt is None else fmt
+            src, on_device, stride_bytes = _ptr(keep), 0, 0
+        else:
+            torch = sys.modules.get("torch")                      # a tensor came in: its module is loaded (torch is imported in from_tensor only)
+            if torch is None or not isinstance(values, torch.Tensor):
+                raise ValueError("values: expected a numpy int64 / uint64 array, an (n, 32) uint8 numpy array, a torch GPU tensor or (address, count)")
+            f, count, stride_bytes = _tensor_layout(torch, values)
+            fmt = f if fmt is None else fmt
+            src, on_device = values.data_ptr(), 1
+            stream = _torch_stream(torch, values, stream)
+        _check(lib.otti_witness_update(inst._h, self._h, first, src, count, fmt, stride_bytes, on_device, stream))
+
+    @property
+    def info(self):
+        """(device address of z, its length n = 2 * padded num_vars Montgomery elements, small_fraction)"""
+        p, n, f = _vp(), _sz(), ctypes.c_double()
+        _check(lib.otti_witness_info(self._h, ctypes.byref(p), ctypes.byref(n), ctypes.byref(f)))
+        return p.value, n.value, f.value
 
     def check_sat(self, inst, max_rows=64, values=True):
         """Instance::is_sat on the device, on this resident assignment, with the failing constraints named (otti_witness_check_sat)"""

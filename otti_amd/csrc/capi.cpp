@@ -394,6 +394,57 @@ int32_t otti_witness_upload(otti_instance *inst, const uint8_t *vars32, size_t n
     });
 }
 void otti_witness_free(otti_witness *w) { delete w; }
+// ---- a witness from device memory, from host integers, and changed in place (device.h WitFormat, k_field.hip k_witness_ingest_from).  Everything
+// that can be said about the arguments alone is said before DevCtx::get() brings a device up.
+static void check_wit_source(const void *src, size_t count, int32_t format, size_t stride_bytes, bool on_device) {
+    if (format < OTTI_WIT_CANONICAL32 || format > OTTI_WIT_U64) throw Error(OTTI_ERR_BAD_ARG, "unknown witness format");
+    if (!src && count) throw Error(OTTI_ERR_BAD_ARG, "null source with a non-zero count");
+    if (stride_bytes && (stride_bytes < wit_elem_bytes(format) || stride_bytes % 8)) throw Error(OTTI_ERR_BAD_ARG, "stride_bytes below the element size or not a multiple of 8");
+    if (on_device && ((uintptr_t)src & 7)) throw Error(OTTI_ERR_BAD_ARG, "a device source must be 8-byte aligned");
+}
+static int32_t witness_from(otti_instance *inst, const void *src, size_t nvars, int32_t format, size_t stride_bytes, bool on_device, const uint8_t *inputs32,
+                            size_t ninputs, void *stream, otti_witness **out) {
+    return guarded([&] {
+        if (!inst || !out || (!inputs32 && ninputs)) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        check_wit_source(src, nvars, format, stride_bytes, on_device);
+        if (nvars > inst->I->num_vars) throw Error(OTTI_ERR_INVALID_NUM_VARS, "more variables than the instance has");
+        if (ninputs != inst->I->num_inputs) throw Error(OTTI_ERR_INVALID_NUM_INPUTS, "wrong number of inputs");
+        std::vector<Fr> inputs = scalars_from_bytes(inputs32, ninputs);
+        auto h = std::make_unique<otti_witness>();
+        h->w = std::make_unique<DeviceWitness>(*inst->I, format, src, nvars, stride_bytes, on_device, (hipStream_t)stream, inputs);
+        *out = h.release(); return OTTI_OK;
+    });
+}
+int32_t otti_witness_from_device(otti_instance *inst, const void *d_vars, size_t nvars, int32_t format, size_t stride_bytes, const uint8_t *inputs32, size_t ninputs,
+                                 void *stream, otti_witness **out) {
+    return witness_from(inst, d_vars, nvars, format, stride_bytes, true, inputs32, ninputs, stream, out);
+}
+int32_t otti_witness_upload_ints(otti_instance *inst, const void *vars, size_t nvars, int32_t format, const uint8_t *inputs32, size_t ninputs, otti_witness **out) {
+    if (format != OTTI_WIT_I64 && format != OTTI_WIT_U64) return guarded([&]() -> int32_t { throw Error(OTTI_ERR_BAD_ARG, "otti_witness_upload_ints takes OTTI_WIT_I64 or OTTI_WIT_U64"); });
+    return witness_from(inst, vars, nvars, format, 0, false, inputs32, ninputs, nullptr, out);
+}
+int32_t otti_witness_update(otti_instance *inst, otti_witness *wit, size_t first, const void *src, size_t count, int32_t format, size_t stride_bytes,
+                            int32_t src_on_device, void *stream) {
+    return guarded([&] {
+        if (!inst || !wit) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        check_wit_source(src, count, format, stride_bytes, src_on_device != 0);
+        const size_t V = inst->I->num_vars;
+        if (first > V || count > V - first) throw Error(OTTI_ERR_INVALID_NUM_VARS, "the range ends beyond the instance's variables");
+        DevCtx::get();                                            // no device: said before the witness handle is looked at
+        if (wit->w->z.n != 2 * V) throw Error(OTTI_ERR_INVALID_NUM_VARS, "the witness was uploaded for an instance of other dimensions");
+        wit->w->update(first, format, src, count, stride_bytes, src_on_device != 0, (hipStream_t)stream);
+        return OTTI_OK;
+    });
+}
+int32_t otti_witness_info(const otti_witness *wit, const void **d_z, size_t *n, double *small_fraction) {
+    return guarded([&] {
+        if (!wit) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (d_z) *d_z = wit->w->z.p;
+        if (n) *n = wit->w->z.n;
+        if (small_fraction) *small_fraction = wit->w->small_fraction;
+        return OTTI_OK;
+    });
+}
 int32_t otti_nizk_prove_resident(otti_instance *inst, otti_witness *wit, otti_gens *gens, const uint8_t *tlabel, size_t tlabel_len,
                                  const uint8_t *seed32, uint8_t **proof, size_t *proof_len, double *stage_ms) {
     return guarded([&] {

@@ -195,7 +195,16 @@ struct DeviceWitness {
     DeviceWitness(const Instance &I, const std::vector<Fr> &vars_padded, const std::vector<Fr> &inputs);
     // straight from the caller's canonical bytes: validation (InvalidScalar) and the conversion to Montgomery form happen on the device
     DeviceWitness(const Instance &I, const uint8_t *vars32, size_t nvars, const std::vector<Fr> &inputs);
+    // from another source (WitFormat): element i at src + i * stride bytes (stride 0: packed), in device memory or, src_on_device false, host
+    // memory (staged as it is: an integer crosses PCIe as 8 bytes and is widened on the device).  producer: the stream whose queued work writes a
+    // device source (nullptr: none to wait for).  Returns once the source is free again.  Same z and small_fraction as the constructor above.
+    DeviceWitness(const Instance &I, int format, const void *src, size_t nvars, size_t stride, bool src_on_device, hipStream_t producer, const std::vector<Fr> &inputs);
+    // variables [first, first + count) replaced likewise.  A scalar >= l throws INVALID_SCALAR and leaves z as it was (the 32-byte formats are
+    // converted into a staging buffer first); afterwards small_fraction is counted again.  Not while a proof or check with this witness runs.
+    void update(size_t first, int format, const void *src, size_t count, size_t stride, bool src_on_device, hipStream_t producer);
 };
+enum WitFormat { WIT_CANONICAL32 = 0, WIT_MONTGOMERY32 = 1, WIT_I64 = 2, WIT_U64 = 3 };   // = OTTI_WIT_* of the C ABI
+inline size_t wit_elem_bytes(int format) { return format == WIT_I64 || format == WIT_U64 ? 8 : 32; }
 void ensure_device_objects(Instance &I, Gens &g);          // lazily built, shared by every prover thread (guarded)
 void ensure_instance_device(Instance &I);
 void ensure_gens_device(Gens &g);
@@ -223,6 +232,8 @@ struct PeBufs { Fr *LZ, *Rv, *a, *s, *b2, *s2, *rows, *extras; };      // R elem
 DotProductProofLog dplog_prove_device(DevCtx &c, const DeviceGens &DG, const Gens &g, const PcView &v, const PeBufs &B, const Fr &LZ_blind, const Fr *y_known,
                                       const Fr &blind_y, CPoint &Cy_out, Transcript &tr, RandomTape &tape);
 size_t dev_witness_ingest(DevCtx &c, Fr *z, size_t n, size_t *n_small = nullptr);   // returns the number of non-canonical scalars (zeroed); n_small: how many are below 2^128
+// the same from device memory in any WitFormat (k_field.hip): element i read at src + i * stride bytes, written to z[dst_off + i]; synchronises
+size_t dev_witness_ingest_from(DevCtx &c, int format, const void *src, size_t stride, size_t n, Fr *z, size_t dst_off, size_t *n_small = nullptr);
 void dev_gather_strided(DevCtx &c, const Fr *in, size_t stride, size_t offset, Fr *out, size_t n);   // out[i] = in[i*stride + offset]
 
 std::shared_ptr<DeviceInstance> upload_instance(const Instance &I);

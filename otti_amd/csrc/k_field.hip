@@ -48,6 +48,67 @@ size_t dev_witness_ingest(DevCtx &c, Fr *z, size_t n, size_t *n_small) {
     if (n_small) *n_small = (size_t)h[1];
     return (size_t)h[0];
 }
+// The same from wherever an assignment lives (device.h WitFormat): element i is read at src + i * stride bytes and lands, in Montgomery
+// form, in z[dst_off + i]; src is device memory that does not overlap z.  counts as above.  Integers are loaded as one 8-byte word and
+// widened (a negative x is l - |x|, so it is never "small"); the 32-byte formats as two 16-byte loads when base and stride allow it
+// (wide), else as four 8-byte ones.  A 32-byte element whose raw value is >= l is counted and stored as zero.
+typedef uint32_t wit_u32x4 __attribute__((ext_vector_type(4)));
+template <int F> __device__ __forceinline__ Fr wit_load(const unsigned char *p, bool wide, bool &neg) {
+    Fr raw; neg = false;
+    if constexpr (F == WIT_I64 || F == WIT_U64) {
+        unsigned long long x = *reinterpret_cast<const unsigned long long *>(p);
+        if (F == WIT_I64 && (long long)x < 0) { neg = true; x = 0ull - x; }      // |INT64_MIN| = 2^63 comes out of the wrap-around as it should
+        raw = fr_zero(); raw.v[0] = (uint32_t)x; raw.v[1] = (uint32_t)(x >> 32);
+    } else if (wide) {
+        const wit_u32x4 lo = *reinterpret_cast<const wit_u32x4 *>(p), hi = *reinterpret_cast<const wit_u32x4 *>(p + 16);
+        for (int k = 0; k < 4; k++) { raw.v[k] = lo[k]; raw.v[4 + k] = hi[k]; }
+    } else {
+        for (int k = 0; k < 4; k++) {
+            const unsigned long long w = *reinterpret_cast<const unsigned long long *>(p + 8 * k);
+            raw.v[2 * k] = (uint32_t)w; raw.v[2 * k + 1] = (uint32_t)(w >> 32);
+        }
+    }
+    return raw;
+}
+template <int F> __global__ __launch_bounds__(kBlock) void k_witness_ingest_from(const unsigned char *src, size_t stride, size_t n, Fr *z, size_t dst_off,
+                                                                               unsigned long long *counts) {
+    unsigned bad = 0, small = 0;
+    const bool wide = (((size_t)src | stride) & 15) == 0;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        bool neg; Fr raw = wit_load<F>(src + i * stride, wide, neg), out;
+        if constexpr (F == WIT_I64 || F == WIT_U64) {
+            if (neg) raw = fr_sub(fr_zero(), raw);                               // l - |x| (on canonical integers the field subtraction is the integer one mod l)
+            else small++;
+            out = fr_mul(raw, fr_R2());
+        } else if (!fr_raw_is_canonical(raw.v)) { out = fr_zero(); bad++; small++; }
+        else if constexpr (F == WIT_CANONICAL32) { out = fr_mul(raw, fr_R2()); small += (raw.v[4] | raw.v[5] | raw.v[6] | raw.v[7]) == 0 ? 1u : 0u; }
+        else { out = raw; const Fr c = fr_to_raw(raw); small += (c.v[4] | c.v[5] | c.v[6] | c.v[7]) == 0 ? 1u : 0u; }
+        z[dst_off + i] = out;
+    }
+    for (int o = 32; o >= 1; o >>= 1) { bad += __shfl_down(bad, o); small += __shfl_down(small, o); }
+    if ((threadIdx.x & 63) == 0) { if (bad) atomicAdd(&counts[0], (unsigned long long)bad); if (small) atomicAdd(&counts[1], (unsigned long long)small); }
+}
+size_t dev_witness_ingest_from(DevCtx &c, int format, const void *src, size_t stride, size_t n, Fr *z, size_t dst_off, size_t *n_small) {
+    if (n_small) *n_small = 0;
+    if (!n) return 0;
+    const unsigned char *s = reinterpret_cast<const unsigned char *>(src);
+    OTTI_HIP(hipMemsetAsync(c.d_counts.p, 0, 2 * sizeof(unsigned long long), c.stream));
+    {
+        KScope ks(c, KC_OTHER);
+        switch (format) {
+        case WIT_CANONICAL32: hipLaunchKernelGGL(k_witness_ingest_from<WIT_CANONICAL32>, grid_for(n), kBlock, 0, c.stream, s, stride, n, z, dst_off, c.d_counts.p); break;
+        case WIT_MONTGOMERY32: hipLaunchKernelGGL(k_witness_ingest_from<WIT_MONTGOMERY32>, grid_for(n), kBlock, 0, c.stream, s, stride, n, z, dst_off, c.d_counts.p); break;
+        case WIT_I64: hipLaunchKernelGGL(k_witness_ingest_from<WIT_I64>, grid_for(n), kBlock, 0, c.stream, s, stride, n, z, dst_off, c.d_counts.p); break;
+        case WIT_U64: hipLaunchKernelGGL(k_witness_ingest_from<WIT_U64>, grid_for(n), kBlock, 0, c.stream, s, stride, n, z, dst_off, c.d_counts.p); break;
+        default: throw Error(OTTI_ERR_BAD_ARG, "unknown witness format");
+        }
+    }
+    unsigned long long h[2] = {0, 0};
+    OTTI_HIP(hipMemcpyAsync(h, c.d_counts.p, sizeof h, hipMemcpyDeviceToHost, c.stream));
+    OTTI_HIP(hipStreamSynchronize(c.stream));
+    if (n_small) *n_small = (size_t)h[1];
+    return (size_t)h[0];
+}
 // Whole-chip throughput of the Montgomery product in GF(l) (operands in registers, every CU busy): what the sum-check, sparse-product
 // and eq kernels are priced against beside the HBM roof — at 7-13 products per 192 bytes they are bounded by the multiplier first.
 __global__ __launch_bounds__(kBlock) void k_fr_mul_peak(Fr *io, int iters) {

@@ -160,6 +160,64 @@ DeviceWitness::DeviceWitness(const Instance &I, const uint8_t *vars32, size_t nv
 }
 
 namespace {
+// Where dev_witness_ingest_from reads a source: a device source as it is, once the context's stream waits for the producer's queued work (an event
+// recorded there, as the otti_kd_* calls order a caller's stream against the context's own); a host source through a staging copy of its span.
+struct WitSource {
+    DevBuf<uint8_t> staged; const void *p = nullptr; size_t stride = 0;
+    WitSource(DevCtx &c, int format, const void *src, size_t n, size_t stride_, bool on_device, hipStream_t producer) {
+        const size_t eb = wit_elem_bytes(format);
+        stride = stride_ ? stride_ : eb; p = src;
+        if (!n) return;
+        if (on_device) {
+            if (producer && producer != c.stream) {
+                if (!c.ev_order) OTTI_HIP(hipEventCreateWithFlags(&c.ev_order, hipEventDisableTiming));
+                OTTI_HIP(hipEventRecord(c.ev_order, producer)); OTTI_HIP(hipStreamWaitEvent(c.stream, c.ev_order, 0));
+            }
+            return;
+        }
+        const size_t span = (n - 1) * stride + eb;
+        staged.alloc(span); p = staged.p;
+        OTTI_HIP(hipMemcpyAsync(staged.p, src, span, hipMemcpyHostToDevice, c.stream));
+    }
+};
+}  // namespace
+
+DeviceWitness::DeviceWitness(const Instance &I, int format, const void *src, size_t nvars, size_t stride, bool src_on_device, hipStream_t producer,
+                             const std::vector<Fr> &inputs_) : inputs(inputs_) {
+    DevCtx &c = DevCtx::get();
+    const size_t V = I.num_vars;
+    if (nvars > V) throw Error(OTTI_ERR_INVALID_NUM_VARS, "more variables than the instance has");
+    if (inputs.size() != I.num_inputs) throw Error(OTTI_ERR_INVALID_NUM_INPUTS, "wrong number of inputs");
+    z.alloc(2 * V);
+    OTTI_HIP(hipMemsetAsync(z.p, 0, 2 * V * sizeof(Fr), c.stream));
+    std::vector<Fr> tail(1 + inputs.size()); tail[0] = fr_one();
+    for (size_t i = 0; i < inputs.size(); i++) tail[1 + i] = inputs[i];
+    OTTI_HIP(hipMemcpyAsync(z.p + V, tail.data(), tail.size() * sizeof(Fr), hipMemcpyHostToDevice, c.stream));
+    WitSource s(c, format, src, nvars, stride, src_on_device, producer);
+    size_t n_small = 0;
+    const size_t bad = dev_witness_ingest_from(c, format, s.p, s.stride, nvars, z.p, 0, &n_small);   // synchronises: `tail`, the staging copy and the caller's buffer are free again
+    if (!nvars) OTTI_HIP(hipStreamSynchronize(c.stream));
+    if (bad) throw Error(OTTI_ERR_INVALID_SCALAR, "non-canonical scalar in assignment");
+    small_fraction = V ? (double)(n_small + (V - nvars)) / (double)V : 0.0;
+}
+
+void DeviceWitness::update(size_t first, int format, const void *src, size_t count, size_t stride, bool src_on_device, hipStream_t producer) {
+    DevCtx &c = DevCtx::get();
+    const size_t V = z.n / 2;
+    if (first > V || count > V - first) throw Error(OTTI_ERR_INVALID_NUM_VARS, "the range ends beyond the instance's variables");
+    if (!count) return;
+    WitSource s(c, format, src, count, stride, src_on_device, producer);
+    DevBuf<Fr> conv;                                              // outlives the copy out of it: freed after dev_small_fraction has synchronised
+    if (format == WIT_I64 || format == WIT_U64) dev_witness_ingest_from(c, format, s.p, s.stride, count, z.p, first);   // every integer is a scalar: straight into place
+    else {
+        conv.alloc(count);                                        // z is written only once the whole range has passed the check
+        if (dev_witness_ingest_from(c, format, s.p, s.stride, count, conv.p, 0)) throw Error(OTTI_ERR_INVALID_SCALAR, "non-canonical scalar in the update: the witness is unchanged");
+        OTTI_HIP(hipMemcpyAsync(z.p + first, conv.p, count * sizeof(Fr), hipMemcpyDeviceToDevice, c.stream));
+    }
+    small_fraction = dev_small_fraction(c, z.p, V);               // one recount over the variables (padding zeros count as small); synchronises
+}
+
+namespace {
 // Everything the rounds of BOTH sum-checks need that depends on the random tape alone, as ONE batched fixed-base MSM: for each round
 // the four points delta_j = commit(d_vec_j, r_delta_j), blinds_poly[j]*h_n, blinds_evals[j]*h_1, r_beta_j*h_1 (extended, not
 // compressed).  Launched right behind the witness commitment (the second sum-check's tape values are read ahead with a
