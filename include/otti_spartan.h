@@ -205,6 +205,27 @@ int32_t otti_snark_prove_resident(otti_instance *inst, otti_comp_comm *comm, ott
    element index (their per-round sums cross the ranks); host rounds and evaluation proofs run on every rank alike */
 int32_t otti_snark_prove_sharded(otti_instance *inst, otti_comp_comm *comm, otti_witness *wit, otti_snark_gens *gens, const uint8_t *tlabel,
                                  size_t tlabel_len, const uint8_t *seed32, uint8_t **proof, size_t *proof_len, double *stage_ms);
+/* ---- kept rows: a resident witness may own the unblinded row sums of its commitment (sum_j z[i * R + j] * G[j] for the L = 2^(ell/2) rows of
+   R = 2^(ell - ell/2) variables, num_vars = 2^ell), which depend on the assignment and the generator points alone.  Opt-in per witness; costs
+   128 * L bytes of HBM.  Both provers use them: otti_nizk_prove_resident and otti_snark_prove_resident (whose satisfiability part commits to the
+   same rows over the same points) then skip the commitment's large MSM launch and only add the blinds; sharded proofs ignore them and compute as
+   without.  Proofs are byte-identical with and without kept rows.
+   otti_witness_keep_rows builds the generators' window table if need be, sums every row now and returns when the sums are resident;
+   _snark takes the SNARK generators' satisfiability stream (the same points for the same sizes: rows kept with either serve both provers).
+   Again with generators of the same points: OTTI_OK, nothing done.  The points, not the table, are what the rows belong to: they stay valid
+   across otti_gens_release_device.  The generators handle given last must outlive the kept rows (otti_witness_drop_rows / otti_witness_free):
+   otti_witness_update sums the rows its range touches again (rows first / R .. (first + count - 1) / R, nothing else) over that handle's table,
+   and a refused update leaves the kept rows, like the vector, as they were.  keep_rows, drop_rows and update never run beside a proof with
+   this witness; proofs only read the rows, so any number of threads may prove from one witness that keeps them.
+   OTTI_ERR_BAD_ARG: a null handle, or generators made for another size than the instance (both before any device is touched); then
+   OTTI_ERR_NO_DEVICE; OTTI_ERR_INVALID_NUM_VARS: the witness was uploaded for an instance of other dimensions. */
+int32_t otti_witness_keep_rows(otti_instance *inst, otti_witness *wit, otti_gens *gens);
+int32_t otti_witness_keep_rows_snark(otti_instance *inst, otti_witness *wit, otti_snark_gens *gens);
+/* frees the kept rows: from then on the witness proves as one that never kept them (none kept: OTTI_OK) */
+int32_t otti_witness_drop_rows(otti_witness *wit);
+/* *kept: 0 or 1; *L, *R: the geometry of the kept rows (0 when none are kept); *rows_resummed: rows summed again by updates since keep_rows.
+   Any out pointer may be NULL.  A null wit is OTTI_ERR_BAD_ARG; without a device no witness exists: OTTI_ERR_NO_DEVICE, wit is not looked at. */
+int32_t otti_witness_rows_info(const otti_witness *wit, int32_t *kept, size_t *L, size_t *R, uint64_t *rows_resummed);
 int32_t otti_snark_verify(const otti_comp_comm *comm, const uint8_t *inputs32, size_t ninputs, const otti_snark_gens *gens,
                           const uint8_t *tlabel, size_t tlabel_len, const uint8_t *proof, size_t proof_len);
 void    otti_buf_free(void *p);

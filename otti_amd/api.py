@@ -85,6 +85,10 @@ _sig("otti_witness_from_device", _i32, _vp, _vp, _sz, _i32, _sz, _vp, _sz, _vp, 
 _sig("otti_witness_upload_ints", _i32, _vp, _vp, _sz, _i32, _vp, _sz, ctypes.POINTER(_vp))
 _sig("otti_witness_update", _i32, _vp, _vp, _sz, _vp, _sz, _i32, _sz, _i32, _vp)
 _sig("otti_witness_info", _i32, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_sz), ctypes.POINTER(ctypes.c_double))
+_sig("otti_witness_keep_rows", _i32, _vp, _vp, _vp)
+_sig("otti_witness_keep_rows_snark", _i32, _vp, _vp, _vp)
+_sig("otti_witness_drop_rows", _i32, _vp)
+_sig("otti_witness_rows_info", _i32, _vp, ctypes.POINTER(_i32), ctypes.POINTER(_sz), ctypes.POINTER(_sz), ctypes.POINTER(_u64))
 _sig("otti_witness_check_sat", _i32, _vp, _vp, ctypes.POINTER(_u64), _vp, _sz, _vp, ctypes.POINTER(ctypes.c_float))
 _sig("otti_nizk_prove_resident", _i32, _vp, _vp, _vp, ctypes.c_char_p, _sz, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_sz),
      ctypes.POINTER(ctypes.c_double))
@@ -506,6 +510,25 @@ class Witness:
         p, n, f = _vp(), _sz(), ctypes.c_double()
         _check(lib.otti_witness_info(self._h, ctypes.byref(p), ctypes.byref(n), ctypes.byref(f)))
         return p.value, n.value, f.value
+
+    def keep_rows(self, inst, gens):
+        """Sum the commitment's unblinded rows now and keep them with the witness (otti_witness_keep_rows[_snark]); ``gens``: NIZKGens or
+        SNARKGens.  Proofs over the same generator points, NIZK and SNARK alike, then skip the commitment's large MSM launch, and ``update`` sums only the
+        rows it touches again.  Proof bytes do not change.  Costs 128 * L bytes of HBM."""
+        f = lib.otti_witness_keep_rows_snark if isinstance(gens, SNARKGens) else lib.otti_witness_keep_rows
+        _check(f(inst._h, self._h, gens._h))
+        self._rows_gens = gens                                    # updates sum rows over this handle's table: it outlives the kept rows
+
+    def drop_rows(self):
+        """Free the kept rows (otti_witness_drop_rows); the witness then proves as one that never kept them"""
+        _check(lib.otti_witness_drop_rows(self._h))
+        self._rows_gens = None
+
+    def rows_info(self):
+        """(kept, L, R, rows_resummed): whether rows are kept, their geometry, and how many rows updates have summed again since keep_rows"""
+        k, L, R, n = _i32(), _sz(), _sz(), _u64()
+        _check(lib.otti_witness_rows_info(self._h, ctypes.byref(k), ctypes.byref(L), ctypes.byref(R), ctypes.byref(n)))
+        return bool(k.value), L.value, R.value, n.value
 
     def check_sat(self, inst, max_rows=64, values=True):
         """Instance::is_sat on the device, on this resident assignment, with the failing constraints named (otti_witness_check_sat)"""

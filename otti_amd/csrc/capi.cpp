@@ -445,6 +445,41 @@ int32_t otti_witness_info(const otti_witness *wit, const void **d_z, size_t *n, 
         return OTTI_OK;
     });
 }
+// ---- kept rows (device.h DeviceWitness::rows_kept).  As with the calls above, the arguments are judged first, a missing device is reported next,
+// and only then is the witness handle looked at (none can exist without a device).
+static int32_t witness_keep_rows(otti_instance *inst, otti_witness *wit, Gens *g) {
+    return guarded([&] {
+        if (!inst || !wit || !g) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        const size_t V = inst->I->num_vars;
+        if (g->num_vars_padded != V) throw Error(OTTI_ERR_BAD_ARG, "generators were made for a different instance size");
+        DevCtx::get();
+        if (wit->w->z.n != 2 * V) throw Error(OTTI_ERR_INVALID_NUM_VARS, "the witness was uploaded for an instance of other dimensions");
+        wit->w->keep_rows(*g);
+        return OTTI_OK;
+    });
+}
+int32_t otti_witness_keep_rows(otti_instance *inst, otti_witness *wit, otti_gens *gens) { return witness_keep_rows(inst, wit, gens ? gens->g.get() : nullptr); }
+int32_t otti_witness_keep_rows_snark(otti_instance *inst, otti_witness *wit, otti_snark_gens *gens) { return witness_keep_rows(inst, wit, gens ? gens->g->sat.get() : nullptr); }
+int32_t otti_witness_drop_rows(otti_witness *wit) {
+    return guarded([&] {
+        if (!wit) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (otti_device_count() < 1) throw Error(OTTI_ERR_NO_DEVICE, "no device: no witness handle can exist");
+        wit->w->drop_rows();
+        return OTTI_OK;
+    });
+}
+int32_t otti_witness_rows_info(const otti_witness *wit, int32_t *kept, size_t *L, size_t *R, uint64_t *rows_resummed) {
+    return guarded([&] {
+        if (!wit) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (otti_device_count() < 1) throw Error(OTTI_ERR_NO_DEVICE, "no device: no witness handle can exist");
+        const DeviceWitness &w = *wit->w;
+        if (kept) *kept = w.rows_kept.p ? 1 : 0;
+        if (L) *L = w.rows_kept.n;
+        if (R) *R = w.rows_R;
+        if (rows_resummed) *rows_resummed = w.rows_resummed;
+        return OTTI_OK;
+    });
+}
 int32_t otti_nizk_prove_resident(otti_instance *inst, otti_witness *wit, otti_gens *gens, const uint8_t *tlabel, size_t tlabel_len,
                                  const uint8_t *seed32, uint8_t **proof, size_t *proof_len, double *stage_ms) {
     return guarded([&] {

@@ -202,6 +202,17 @@ struct DeviceWitness {
     // variables [first, first + count) replaced likewise.  A scalar >= l throws INVALID_SCALAR and leaves z as it was (the 32-byte formats are
     // converted into a staging buffer first); afterwards small_fraction is counted again.  Not while a proof or check with this witness runs.
     void update(size_t first, int format, const void *src, size_t count, size_t stride, bool src_on_device, hipStream_t producer);
+    // ---- kept rows (opt-in): the unblinded row sums of the commitment, sum_j z[i * R + j] * P[j] for the L = V / R rows — the group elements the
+    // proof's MSM_KEEP launch leaves in DevCtx::msm_keep.  They depend on z and on the generator POINTS alone (their stream and R; not on the
+    // window width of the table they were summed with: a table released and rebuilt keeps them valid).  A proof whose generators have these
+    // points reads them as the addend of its blind launch and skips the MSM_KEEP launch; sharded proofs do not look at them.  Written by
+    // keep_rows and update only — both never beside a proof with this witness, so proofs need no lock to read them.
+    DevBuf<Pt> rows_kept; const char *rows_stream = nullptr; size_t rows_R = 0;
+    Gens *rows_gens = nullptr;                                // whose table update() re-sums with (the caller keeps it alive while rows are kept)
+    unsigned long long rows_resummed = 0;                     // rows re-summed by updates since keep_rows
+    bool rows_kept_for(const Gens &g) const;                  // kept, and over g's points
+    void keep_rows(Gens &g);                                  // builds g's table if need be, sums every row, returns when they are resident; again with the same points: nothing
+    void drop_rows();
 };
 enum WitFormat { WIT_CANONICAL32 = 0, WIT_MONTGOMERY32 = 1, WIT_I64 = 2, WIT_U64 = 3 };   // = OTTI_WIT_* of the C ABI
 inline size_t wit_elem_bytes(int format) { return format == WIT_I64 || format == WIT_U64 ? 8 : 32; }
@@ -289,13 +300,15 @@ enum { MSM_COMPRESSED = 0, MSM_RAW = 1, MSM_KEEP = 2 };
 // returns a ticket: c.wait_points(ticket) returns once the compressed points are in c.h_points (ticket 0 = plain stream sync)
 unsigned long long dev_msm_rows(DevCtx &c, const DeviceGens &g, const Fr *dense, size_t stride, size_t n_dense, size_t rows, const Fr *extra_s,
                                 const uint32_t *extra_base_host, size_t n_extra, int mode = MSM_COMPRESSED, const Pt *addend = nullptr,
-                                bool sparse_hint = false);
+                                bool sparse_hint = false, Pt *keep_dst = nullptr, size_t keep_row0 = 0, bool force_bulk = false);
 // sparse_hint: the dense scalars are mostly small numbers (DeviceWitness::small_fraction) — bulk launches then compact the non-zero
 // (term, window) pairs into a work list instead of giving every pair a lane.  Results are identical either way.
 double dev_small_fraction(DevCtx &c, const Fr *z, size_t n);               // share of scalars below 2^128 (synchronises the stream)
 // MSM_RAW: skip compression; after c.sync() the extended row sums are in c.h_pts[0..rows).
 // MSM_KEEP: no output; the row sums stay on the device in c.msm_keep (to be passed as `addend` of a later launch, which then
 // compresses (row sum + addend)).  Lets the host draw the blinds while the device already sums the witness terms.
+// keep_dst (MSM_KEEP only): row i's sum goes to keep_dst[keep_row0 + i] instead, c.msm_keep is left alone (DeviceWitness::rows_kept: `dense`
+// then points at the first of the rows to sum).  force_bulk: the chip-filling kernel whatever the size (a run of re-summed rows).
 // ---- K9: LZ[j] = sum_i Lv[i] * Z[i*R + j]
 void dev_poly_bound(DevCtx &c, const Fr *Z, size_t L, size_t R, const Fr *Lv, Fr *out, Fr *scratch /* >= 64*R */);
 // chunk sums of the same bound over eq(rest) alone (k_sumcheck.hip): out = (L / m) x R; false (nothing launched) when the geometry does not allow it

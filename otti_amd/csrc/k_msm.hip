@@ -407,10 +407,14 @@ __global__ __launch_bounds__(64) void k_encode_points(const Pt *pts, const Pt *a
     if (host32) { uint32_t *h = (uint32_t *)(host32 + 32 * i); for (int k = 0; k < 8; k++) h[k] = w[k]; }
 }
 static unsigned long long msm_launch(DevCtx &c, const DeviceGens &g, const Fr *dense, size_t stride, size_t n_dense, size_t rows, const Fr *extra_s,
-                                     const uint32_t *extra_base, size_t n_extra, int mode, const Pt *addend, const BulletArgs *bul, bool sparse_hint);
+                                     const uint32_t *extra_base, size_t n_extra, int mode, const Pt *addend, const BulletArgs *bul, bool sparse_hint,
+                                     Pt *keep_dst = nullptr, bool force_bulk = false);
 unsigned long long dev_msm_rows(DevCtx &c, const DeviceGens &g, const Fr *dense, size_t stride, size_t n_dense, size_t rows, const Fr *extra_s,
-                                const uint32_t *extra_base, size_t n_extra, int mode, const Pt *addend, bool sparse_hint) {
-    return msm_launch(c, g, dense, stride, n_dense, rows, extra_s, extra_base, n_extra, mode, addend, nullptr, sparse_hint);
+                                const uint32_t *extra_base, size_t n_extra, int mode, const Pt *addend, bool sparse_hint, Pt *keep_dst, size_t keep_row0,
+                                bool force_bulk) {
+    if (keep_dst && mode != MSM_KEEP) throw Error(OTTI_ERR_INTERNAL, "msm: a destination for kept row sums needs MSM_KEEP");
+    return msm_launch(c, g, dense, stride, n_dense, rows, extra_s, extra_base, n_extra, mode, addend, nullptr, sparse_hint,
+                      keep_dst ? keep_dst + keep_row0 : nullptr, force_bulk);
 }
 // share of the n scalars whose canonical value is below 2^128 (what a compiled circuit's witness is mostly made of)
 __global__ __launch_bounds__(kBlock) void k_count_small(const Fr *z, size_t n, unsigned long long *count) {
@@ -438,7 +442,8 @@ unsigned long long dev_bullet_round(DevCtx &c, const DeviceGens &g, size_t R, si
     return msm_launch(c, g, nullptr, 0, R / 2, 2, extra_s, extra_base, 2, MSM_COMPRESSED, nullptr, &U, false);   // R/2 active terms per row
 }
 static unsigned long long msm_launch(DevCtx &c, const DeviceGens &g, const Fr *dense, size_t stride, size_t n_dense, size_t rows, const Fr *extra_s,
-                                     const uint32_t *extra_base, size_t n_extra, int mode, const Pt *addend, const BulletArgs *bul, bool sparse_hint) {
+                                     const uint32_t *extra_base, size_t n_extra, int mode, const Pt *addend, const BulletArgs *bul, bool sparse_hint,
+                                     Pt *keep_dst, bool force_bulk) {
     const bool raw_points = mode == MSM_RAW;
     if (n_extra > 8) throw Error(OTTI_ERR_INTERNAL, "msm: too many extra terms");
     if (!rows) return 0;
@@ -446,7 +451,7 @@ static unsigned long long msm_launch(DevCtx &c, const DeviceGens &g, const Fr *d
     A.table = g.table.p; A.c = g.c; A.W = g.W; A.E = (uint32_t)g.E; A.lanes = kBlock / g.W;
     A.dense = dense; A.stride = stride; A.n_dense = n_dense; A.extra_s = extra_s; A.n_extra = (int)n_extra;
     for (int i = 0; i < 8; i++) A.extra_base[i] = i < (int)n_extra ? extra_base[i] : 0;
-    const bool bulk = rows * n_dense >= ((size_t)1 << 16) && !bul;
+    const bool bulk = (rows * n_dense >= ((size_t)1 << 16) || (force_bulk && n_dense)) && !bul;
     const bool sparse = bulk && sparse_hint && g.W <= 32;
     size_t nchunks;
     if (bulk) {
@@ -526,8 +531,9 @@ static unsigned long long msm_launch(DevCtx &c, const DeviceGens &g, const Fr *d
         finals = c.msm_final.p;
     }
     if (mode == MSM_KEEP) {
-        if (c.msm_keep.n < rows) c.msm_keep.alloc(rows);
-        OTTI_HIP(hipMemcpyAsync(c.msm_keep.p, finals, rows * sizeof(Pt), hipMemcpyDeviceToDevice, c.stream));
+        // (a launch that is not MSM_COMPRESSED never fuses or mails: whichever kernel ran, the row sums are at `finals` here)
+        if (!keep_dst && c.msm_keep.n < rows) c.msm_keep.alloc(rows);
+        OTTI_HIP(hipMemcpyAsync(keep_dst ? keep_dst : c.msm_keep.p, finals, rows * sizeof(Pt), hipMemcpyDeviceToDevice, c.stream));
         c.pending_host_encode = 0;
     } else if (raw_points) {
         if (rows > kHostPtsCap) throw Error(OTTI_ERR_INTERNAL, "msm: too many raw rows");

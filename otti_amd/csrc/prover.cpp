@@ -10,6 +10,7 @@
 #include "pool.h"
 #include "shard.h"
 #include <chrono>
+#include <cstring>
 #include <mutex>
 
 namespace otti {
@@ -201,6 +202,7 @@ DeviceWitness::DeviceWitness(const Instance &I, int format, const void *src, siz
     small_fraction = V ? (double)(n_small + (V - nvars)) / (double)V : 0.0;
 }
 
+static void resum_rows(DevCtx &c, DeviceWitness &w, size_t r0, size_t r1);
 void DeviceWitness::update(size_t first, int format, const void *src, size_t count, size_t stride, bool src_on_device, hipStream_t producer) {
     DevCtx &c = DevCtx::get();
     const size_t V = z.n / 2;
@@ -215,7 +217,37 @@ void DeviceWitness::update(size_t first, int format, const void *src, size_t cou
         OTTI_HIP(hipMemcpyAsync(z.p + first, conv.p, count * sizeof(Fr), hipMemcpyDeviceToDevice, c.stream));
     }
     small_fraction = dev_small_fraction(c, z.p, V);               // one recount over the variables (padding zeros count as small); synchronises
+    // kept rows: z has changed (a refused scalar threw above, with z and the kept rows as they were), so the rows the range touches are summed again
+    if (rows_kept.p) resum_rows(c, *this, first / rows_R, (first + count - 1) / rows_R);
 }
+
+// ---- kept rows.  Rows [r0, r1] of z summed over g's table into their slots of rows_kept, by the launch the proof's own commitment would make for
+// them: up to two rows the latency-bound kernel (as every launch of at most two rows), a longer run one chip-filling launch with the proof's
+// sparse rule.  Returns once they are resident: the next proof may run on another thread's stream.
+static void sum_rows_into(DevCtx &c, DeviceWitness &w, Gens &g, size_t r0, size_t r1, bool whole) {
+    ensure_gens_device(g);
+    const DeviceGens &DG = *g.dev;
+    const size_t R = w.rows_R, n = r1 - r0 + 1;
+    // the whole vector goes the way the proof's MSM_KEEP launch goes (same size rule); a run of dirty rows is bulk from three rows on
+    dev_msm_rows(c, DG, w.z.p + r0 * R, R, R, n, nullptr, nullptr, 0, MSM_KEEP, nullptr, w.small_fraction > kSparseWitness, w.rows_kept.p, r0, !whole && n > 2);
+    OTTI_HIP(hipStreamSynchronize(c.stream));
+}
+static void resum_rows(DevCtx &c, DeviceWitness &w, size_t r0, size_t r1) {
+    // a failure here (the table has to be rebuilt and HBM is short) leaves rows that no longer belong to z: the witness goes back to having none
+    try { sum_rows_into(c, w, *w.rows_gens, r0, r1, false); } catch (...) { w.drop_rows(); throw; }
+    w.rows_resummed += r1 - r0 + 1;
+}
+bool DeviceWitness::rows_kept_for(const Gens &g) const { return rows_kept.p && rows_R == g.R && rows_stream && !strcmp(rows_stream, g.stream); }
+void DeviceWitness::keep_rows(Gens &g) {
+    DevCtx &c = DevCtx::get();
+    const size_t V = z.n / 2;
+    if (g.num_vars_padded != V || !g.R || V % g.R) throw Error(OTTI_ERR_BAD_ARG, "generators were made for a different instance size");
+    if (rows_kept_for(g)) { rows_gens = &g; return; }
+    drop_rows();
+    rows_kept.alloc(V / g.R); rows_stream = g.stream; rows_R = g.R; rows_gens = &g; rows_resummed = 0;
+    try { sum_rows_into(c, *this, g, 0, V / g.R - 1, true); } catch (...) { drop_rows(); throw; }
+}
+void DeviceWitness::drop_rows() { rows_kept.release(); rows_stream = nullptr; rows_R = 0; rows_gens = nullptr; rows_resummed = 0; }
 
 namespace {
 // Everything the rounds of BOTH sum-checks need that depends on the random tape alone, as ONE batched fixed-base MSM: for each round
@@ -463,7 +495,9 @@ void r1cs_prove_device(Instance &I, DeviceWitness &wit, Gens &g, Transcript &tr,
     // ---- polycommit: DensePolynomial::commit (K8).  The witness terms of every row are summed first (no host input needed);
     // meanwhile the host draws the whole random tape (its label sequence is known in advance); the blind terms are added last.
     t0 = now_ms();
-    {
+    // (a witness that keeps its rows for these points has them already: DeviceWitness::rows_kept; a sharded proof sums its block as ever)
+    const bool rows_kept = !sh && wit.rows_kept_for(g);
+    if (!rows_kept) {
         // several proofs in flight in this process: the chip-filling launch goes to the process's CU-masked stream, so that the other
         // proofs' rounds (tens of workgroups each) find CUs whose registers no MSM workgroup holds; ordered against this context's
         // stream by events on both sides
@@ -500,7 +534,7 @@ void r1cs_prove_device(Instance &I, DeviceWitness &wit, Gens &g, Transcript &tr,
     OTTI_HIP(hipMemcpyAsync(S.blinds.p, blinds_vars.data() + rk * Ll, Ll * sizeof(Fr), hipMemcpyHostToDevice, c.stream));
     {
         uint32_t hbase = g.pc_n.h;
-        dev_msm_rows(c, DG, nullptr, 0, 0, Ll, S.blinds.p, &hbase, 1, MSM_COMPRESSED, c.msm_keep.p);
+        dev_msm_rows(c, DG, nullptr, 0, 0, Ll, S.blinds.p, &hbase, 1, MSM_COMPRESSED, rows_kept ? wit.rows_kept.p : c.msm_keep.p);
         // Az, Bz, Cz do not depend on the transcript: queue them behind the commitment so that they run while the host hashes it
         OTTI_HIP(hipEventRecord(c.ev0, c.stream));
         dev_spmv3(c, rows_set, wit.z.p, S.T[1].p, S.T[2].p, S.T[3].p, false, nullptr);

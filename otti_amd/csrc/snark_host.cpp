@@ -22,7 +22,8 @@ std::unique_ptr<SnarkGens> snark_gens_new(size_t num_cons, size_t num_vars, size
     const size_t Rmax = std::max({g->ops.R, g->mem.R, g->derefs.R});
     auto e = std::make_unique<Gens>();
     e->R = Rmax; e->num_vars_padded = 0;
-    e->P = derive_generators("gens_r1cs_eval", Rmax + 2);             // the three generator sets are prefixes of one stream
+    e->stream = "gens_r1cs_eval";
+    e->P = derive_generators(e->stream, Rmax + 2);             // the three generator sets are prefixes of one stream
     e->small_slot.assign(e->P.size(), -1);
     for (const PcSet *s : {&g->ops, &g->mem, &g->derefs})
         for (uint32_t idx : {s->g1, s->h1}) {

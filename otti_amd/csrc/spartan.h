@@ -56,6 +56,7 @@ struct Term { uint32_t base; Fr s; };
 struct GensView { std::vector<uint32_t> G; uint32_t h; };   // indices into P
 struct Gens {
     size_t num_vars_padded = 0, R = 0;
+    const char *stream = "gens_r1cs_sat";                   // label of the SHAKE256 stream P comes from: with R, the identity of the points P[0 .. R)
     std::vector<Pt> P;
     GensView pc_n, pc_1, sc_1, sc_3, sc_4;
     std::vector<int> small_slot;                            // P index -> slot in small_tables, or -1

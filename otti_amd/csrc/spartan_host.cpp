@@ -127,7 +127,7 @@ std::unique_ptr<Gens> gens_new(size_t num_cons, size_t num_vars, size_t num_inpu
     size_t ell = ilog2(nvp);
     size_t R = (size_t)1 << (ell - ell / 2);
     g->num_vars_padded = nvp; g->R = R;
-    g->P = derive_generators("gens_r1cs_sat", std::max(R + 2, (size_t)5));
+    g->P = derive_generators(g->stream, std::max(R + 2, (size_t)5));
     g->pc_n.G.resize(R); std::iota(g->pc_n.G.begin(), g->pc_n.G.end(), 0u); g->pc_n.h = (uint32_t)(R + 1);
     g->pc_1.G = {(uint32_t)R}; g->pc_1.h = (uint32_t)(R + 1);
     g->sc_1 = g->pc_1;
