@@ -1,0 +1,582 @@
+// Kernel-level and device-pointer entries of libottispartan (otti_k_*, otti_kd_*, otti_dev_*, otti_bench_*, otti_stats_*, otti_lanes_*): what the tests and
+// the measurement tools call, one launch function at a time.  The ABI that embedders call is in capi.cpp.
+#include "capi_common.h"
+
+namespace {
+struct Staged {                      // host Montgomery bytes -> device buffer
+    DevBuf<Fr> d;
+    Staged(DevCtx &c, const uint8_t *h, size_t n) : d(std::max<size_t>(1, n)) { if (n) OTTI_HIP(hipMemcpyAsync(d.p, h, n * sizeof(Fr), hipMemcpyHostToDevice, c.stream)); }
+};
+void download(DevCtx &c, uint8_t *h, const Fr *d, size_t n) { if (n) OTTI_HIP(hipMemcpyAsync(h, d, n * sizeof(Fr), hipMemcpyDeviceToHost, c.stream)); }
+struct KTimer {
+    DevCtx &c; float *out;
+    KTimer(DevCtx &c_, float *o) : c(c_), out(o) { if (out) OTTI_HIP(hipEventRecord(c.ev0, c.stream)); }
+    void stop() { if (out) { OTTI_HIP(hipEventRecord(c.ev1, c.stream)); OTTI_HIP(hipEventSynchronize(c.ev1)); OTTI_HIP(hipEventElapsedTime(out, c.ev0, c.ev1)); } }
+};
+// the two eq pyramids over m variables exactly as nizk_prove_resident lays them out (lo: last min(m,12) variables, hi: the ones before)
+struct EqPyramids {
+    DevBuf<Fr> buf; size_t n_lo = 0, n_hi = 0;
+    EqPyramids(DevCtx &c, const Fr *tau, size_t m) : buf(8192 + 16384) {
+        n_lo = std::min<size_t>(m, 12); n_hi = m - n_lo;
+        dev_eq_pyramid2(c, tau + n_hi, n_lo, buf.p, tau, n_hi, n_hi ? buf.p + 8192 : nullptr);
+    }
+    EqSrc top() const {                                      // E over all m variables
+        EqSrc e; const size_t m = n_lo + n_hi;
+        if (m <= n_lo) { e.hi = nullptr; e.lo = buf.p + (((size_t)1 << m) - 1); e.lo_bits = 0; }
+        else { e.hi = buf.p + 8192 + (((size_t)1 << n_hi) - 1); e.lo = buf.p + (((size_t)1 << n_lo) - 1); e.lo_bits = (int)n_lo; }
+        return e;
+    }
+};
+std::vector<Fr> fr_load_vec(const uint8_t *p, size_t n) { std::vector<Fr> v(n + 1); for (size_t i = 0; i < n; i++) v[i] = fr_load(p + 32 * i); return v; }
+// Run the library's launch functions on a caller's stream for the duration of one call.  The launches share the context's scratch
+// (round partials, arrival counters, MSM partials, result slots), so work enqueued on one stream must not overlap work on another:
+// entering, the caller's stream waits for everything the context's own stream has been given; leaving, the context's own stream
+// waits for what was just enqueued — two calls on different caller streams are thereby ordered through the context's stream.
+struct StreamScope {
+    DevCtx &c; hipStream_t old;
+    void order(hipStream_t after, hipStream_t before) {
+        if (!c.ev_order) OTTI_HIP(hipEventCreateWithFlags(&c.ev_order, hipEventDisableTiming));
+        OTTI_HIP(hipEventRecord(c.ev_order, before)); OTTI_HIP(hipStreamWaitEvent(after, c.ev_order, 0));
+    }
+    StreamScope(DevCtx &c_, void *s) : c(c_), old(c_.stream) { if (s && (hipStream_t)s != old) { order((hipStream_t)s, old); c.stream = (hipStream_t)s; } }
+    ~StreamScope() { if (c.stream != old) { hipStream_t mine = c.stream; c.stream = old; try { order(old, mine); } catch (...) {} } }
+};
+bool pow2(size_t x) { return x && !(x & (x - 1)); }
+struct StagedPc {
+    std::unique_ptr<Staged> a, b, cc; PcList L; size_t nC = 0;
+    StagedPc(DevCtx &c, const uint8_t *A, const uint8_t *B, const uint8_t *C, const uint8_t *has_C, size_t ninst, size_t len) {
+        for (size_t y = 0; y < ninst; y++) nC += has_C[y] ? 1 : 0;
+        a = std::make_unique<Staged>(c, A, ninst * len); b = std::make_unique<Staged>(c, B, ninst * len); cc = std::make_unique<Staged>(c, C, nC * len);
+        L.n = (int)ninst; size_t k = 0;
+        for (size_t y = 0; y < ninst; y++) { L.A[y] = a->d.p + y * len; L.B[y] = b->d.p + y * len; L.C[y] = has_C[y] ? cc->d.p + (k++) * len : nullptr; }
+    }
+};
+void check_pc_list(const uint8_t *A, const uint8_t *B, const uint8_t *C, const uint8_t *has_C, size_t ninst, size_t len) {
+    if (ninst < 1 || ninst > (size_t)kMaxInst) throw Error(OTTI_ERR_BAD_ARG, "a batch has 1 .. kMaxInst instances");
+    if (!A || !B || !has_C) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+    if (!pow2(len)) throw Error(OTTI_ERR_BAD_ARG, "table length must be a power of two");
+    for (size_t y = 0; y < ninst; y++) if (has_C[y] && !C) throw Error(OTTI_ERR_BAD_ARG, "an instance with a third table, but no third tables");
+}
+}  // namespace
+
+extern "C" {
+
+int32_t otti_k_fr_op(int32_t op, const uint8_t *a, const uint8_t *b, uint8_t *out, size_t n, float *ms) {
+    return guarded([&] {
+        DevCtx &c = DevCtx::get(); Staged A(c, a, n), B(c, b, n); DevBuf<Fr> O(std::max<size_t>(1, n));
+        KTimer t(c, ms); dev_fr_op(c, op, A.d.p, B.d.p, O.p, n); t.stop();
+        download(c, out, O.p, n); c.sync(); return OTTI_OK;
+    });
+}
+int32_t otti_k_addr_timestamps(const uint32_t *h_addr3, size_t N, size_t M, uint32_t *h_read_ts3, uint32_t *h_audit, float *ms) {
+    return guarded([&] {
+        if (!h_addr3 || !h_read_ts3 || !h_audit || N < 1 || M < 1 || N > ((size_t)1 << 28) || M > ((size_t)1 << 31)) throw Error(OTTI_ERR_BAD_ARG, "address timestamps: null argument, or N outside 1 .. 2^28, or M outside 1 .. 2^31");
+        AddrTs a; a.sides = 1; a.N = N; a.M = M;
+        for (size_t i = 0; i < 3 * N; i++) if (h_addr3[i] >= M) throw Error(OTTI_ERR_BAD_ARG, "address timestamps: an address is not below M");
+        for (int k = 0; k < 3; k++) { size_t len = N; while (len && h_addr3[k * N + len - 1] == 0) len--; a.len[k] = (uint32_t)len; }   // the closed-form tail: trailing entries at address 0
+        DevCtx &c = DevCtx::get();
+        DevBuf<uint32_t> addr(3 * N), ts(3 * N), audit(M);
+        OTTI_HIP(hipMemcpyAsync(addr.p, h_addr3, 3 * N * 4, hipMemcpyHostToDevice, c.stream));
+        for (int k = 0; k < 3; k++) { a.addr[0][k] = addr.p + k * N; a.ts_u32[0][k] = ts.p + k * N; }
+        a.audit_u32[0] = audit.p;
+        KTimer t(c, ms); dev_addr_timestamps(c, a); t.stop();
+        OTTI_HIP(hipMemcpyAsync(h_read_ts3, ts.p, 3 * N * 4, hipMemcpyDeviceToHost, c.stream));
+        OTTI_HIP(hipMemcpyAsync(h_audit, audit.p, M * 4, hipMemcpyDeviceToHost, c.stream));
+        c.sync(); return OTTI_OK;
+    });
+}
+int32_t otti_k_fr_from_canonical(const uint8_t *in, uint8_t *out, size_t n) {
+    return guarded([&] { DevCtx &c = DevCtx::get(); Staged A(c, in, n); dev_from_canonical(c, A.d.p, A.d.p, n); download(c, out, A.d.p, n); c.sync(); return OTTI_OK; });
+}
+int32_t otti_k_fr_to_canonical(const uint8_t *in, uint8_t *out, size_t n) {
+    return guarded([&] { DevCtx &c = DevCtx::get(); Staged A(c, in, n); dev_to_canonical(c, A.d.p, A.d.p, n); download(c, out, A.d.p, n); c.sync(); return OTTI_OK; });
+}
+int32_t otti_k_multiply_vec(otti_instance *inst, const uint8_t *z, uint8_t *Az, uint8_t *Bz, uint8_t *Cz, float *ms) {
+    return guarded([&] {
+        DevCtx &c = DevCtx::get(); Instance &I = *inst->I; ensure_instance_device(I);
+        Staged Z(c, z, 2 * I.num_vars); DevBuf<Fr> a(I.num_cons), b(I.num_cons), d(I.num_cons);
+        KTimer t(c, ms); dev_spmv3(c, I.dev->by_row, Z.d.p, a.p, b.p, d.p, false, nullptr); t.stop();
+        download(c, Az, a.p, I.num_cons); download(c, Bz, b.p, I.num_cons); download(c, Cz, d.p, I.num_cons); c.sync(); return OTTI_OK;
+    });
+}
+int32_t otti_k_eval_table_sparse(otti_instance *inst, const uint8_t *eq_rx, const uint8_t *rABC, uint8_t *out, float *ms) {
+    return guarded([&] {
+        DevCtx &c = DevCtx::get(); Instance &I = *inst->I; ensure_instance_device(I);
+        Staged E(c, eq_rx, I.num_cons); DevBuf<Fr> o(2 * I.num_vars);
+        Fr coef[3] = {fr_load(rABC), fr_load(rABC + 32), fr_load(rABC + 64)};
+        KTimer t(c, ms); dev_spmv3(c, I.dev->by_col, E.d.p, o.p, nullptr, nullptr, true, coef); t.stop();
+        download(c, out, o.p, 2 * I.num_vars); c.sync(); return OTTI_OK;
+    });
+}
+int32_t otti_k_eq_evals(const uint8_t *r, size_t ell, uint8_t *out, float *ms) {
+    return guarded([&] {
+        if (ell > 25) throw Error(OTTI_ERR_BAD_ARG, "ell > 25");
+        DevCtx &c = DevCtx::get(); std::vector<Fr> rr(ell + 1); for (size_t i = 0; i < ell; i++) rr[i] = fr_load(r + 32 * i);
+        size_t n = (size_t)1 << ell; DevBuf<Fr> o(n), s(5 * 4096);
+        KTimer t(c, ms); dev_eq_evals(c, rr.data(), ell, o.p, s.p); t.stop();
+        download(c, out, o.p, n); c.sync(); return OTTI_OK;
+    });
+}
+int32_t otti_k_fold_top(const uint8_t *Z, size_t len, const uint8_t *r, uint8_t *out, float *ms) {
+    return guarded([&] {
+        DevCtx &c = DevCtx::get(); Staged z(c, Z, len);
+        KTimer t(c, ms); dev_fold_top(c, z.d.p, len, fr_load(r)); t.stop();
+        download(c, out, z.d.p, len / 2); c.sync(); return OTTI_OK;
+    });
+}
+int32_t otti_k_fold_bot(const uint8_t *Z, size_t len, const uint8_t *r, uint8_t *out, float *ms) {
+    return guarded([&] {
+        DevCtx &c = DevCtx::get(); Staged z(c, Z, len); DevBuf<Fr> o(std::max<size_t>(1, len / 2));
+        KTimer t(c, ms); dev_fold_bot(c, z.d.p, o.p, len, fr_load(r)); t.stop();
+        download(c, out, o.p, len / 2); c.sync(); return OTTI_OK;
+    });
+}
+int32_t otti_k_sc_cubic_round(const uint8_t *A, const uint8_t *B, const uint8_t *C, const uint8_t *D, size_t len, uint8_t *e3, float *ms) {
+    return guarded([&] {
+        DevCtx &c = DevCtx::get(); Staged a(c, A, len), b(c, B, len), cc(c, C, len), d(c, D, len);
+        KTimer t(c, ms); auto tk = dev_sc_cubic_eval(c, a.d.p, b.d.p, cc.d.p, d.d.p, len, 0); t.stop();
+        c.wait_ticket(tk); memcpy(e3, c.h_results, 96); c.sync(); return OTTI_OK;
+    });
+}
+int32_t otti_k_sc_cubic_fold_round(const uint8_t *A, const uint8_t *B, const uint8_t *C, const uint8_t *D, size_t len, const uint8_t *r,
+                                   uint8_t *out4, uint8_t *e3, float *ms) {
+    return guarded([&] {
+        DevCtx &c = DevCtx::get(); Staged a(c, A, len), b(c, B, len), cc(c, C, len), d(c, D, len);
+        KTimer t(c, ms); auto tk = dev_sc_cubic_fold_eval(c, a.d.p, b.d.p, cc.d.p, d.d.p, len, fr_load(r), 0); t.stop();
+        size_t h = len / 2;
+        download(c, out4, a.d.p, h); download(c, out4 + 32 * h, b.d.p, h); download(c, out4 + 64 * h, cc.d.p, h); download(c, out4 + 96 * h, d.d.p, h);
+        c.sync(); c.wait_ticket(tk); memcpy(e3, c.h_results, 96); return OTTI_OK;
+    });
+}
+int32_t otti_k_sc_quad_round(const uint8_t *A, const uint8_t *B, size_t len, uint8_t *e2, float *ms) {
+    return guarded([&] {
+        DevCtx &c = DevCtx::get(); Staged a(c, A, len), b(c, B, len);
+        KTimer t(c, ms); auto tk = dev_sc_quad_eval(c, a.d.p, b.d.p, len, 0); t.stop();
+        c.wait_ticket(tk); memcpy(e2, c.h_results, 64); c.sync(); return OTTI_OK;
+    });
+}
+int32_t otti_k_sc_quad_fold_round(const uint8_t *A, const uint8_t *B, size_t len, const uint8_t *r, uint8_t *out2, uint8_t *e2, float *ms) {
+    return guarded([&] {
+        DevCtx &c = DevCtx::get(); Staged a(c, A, len), b(c, B, len);
+        KTimer t(c, ms); auto tk = dev_sc_quad_fold_eval(c, a.d.p, b.d.p, len, fr_load(r), 0); t.stop();
+        size_t h = len / 2; download(c, out2, a.d.p, h); download(c, out2 + 32 * h, b.d.p, h);
+        c.sync(); c.wait_ticket(tk); memcpy(e2, c.h_results, 64); return OTTI_OK;
+    });
+}
+// Armed launches (device.h): the same fold + sums round three ways on the caller's tables — plain; armed and released by go() after
+// `hold_us` microseconds of the kernel waiting; armed and ABORTED (the tables must come back untouched and the stream must drain),
+// followed by another armed round that must still work.  out2/e2: the plain launch's folded tables and sums, for the caller's oracle.
+int32_t otti_k_armed_selftest(const uint8_t *A, const uint8_t *B, size_t len, const uint8_t *r, uint32_t hold_us, uint8_t *out2, uint8_t *e2) {
+    return guarded([&] {
+        if (len < 8 || (len & (len - 1))) throw Error(OTTI_ERR_BAD_ARG, "table length must be a power of two >= 8");
+        DevCtx &c = DevCtx::get();
+        const Fr rr = fr_load(r); const size_t h = len / 2;
+        Staged a0(c, A, len), b0(c, B, len), a1(c, A, len), b1(c, B, len);
+        auto tk = dev_sc_quad_fold_eval(c, a0.d.p, b0.d.p, len, rr, 0);
+        c.wait_ticket(tk); Fr e_plain[2] = {c.h_results[0], c.h_results[1]};
+        download(c, out2, a0.d.p, h); download(c, out2 + 32 * h, b0.d.p, h); c.sync(); memcpy(e2, e_plain, 64);
+        // armed, released late
+        tk = dev_sc_quad_fold_eval_armed(c, a1.d.p, b1.d.p, len, 0);
+        { const auto t0 = std::chrono::steady_clock::now(); while (std::chrono::steady_clock::now() - t0 < std::chrono::microseconds(hold_us)) {} }
+        c.go(&rr, 1);
+        c.wait_ticket(tk);
+        if (memcmp(e_plain, c.h_results, 64)) throw Error(OTTI_ERR_INTERNAL, "armed round: sums differ from the plain launch");
+        std::vector<uint8_t> got(64 * h);
+        download(c, got.data(), a1.d.p, h); download(c, got.data() + 32 * h, b1.d.p, h); c.sync();
+        if (memcmp(got.data(), out2, 64 * h)) throw Error(OTTI_ERR_INTERNAL, "armed round: folded tables differ from the plain launch");
+        // armed, aborted: nothing may be written, the stream must drain, the next armed launch must work
+        std::vector<uint8_t> before(32 * h), after(32 * h);
+        download(c, before.data(), a1.d.p, h); c.sync();
+        tk = dev_sc_quad_fold_eval_armed(c, a1.d.p, b1.d.p, h, 0);
+        c.go_abort();
+        download(c, after.data(), a1.d.p, h); c.sync();
+        if (memcmp(before.data(), after.data(), 32 * h)) throw Error(OTTI_ERR_INTERNAL, "aborted armed round wrote to its tables");
+        if (*c.h_flag >= tk) throw Error(OTTI_ERR_INTERNAL, "aborted armed round delivered a result");
+        tk = dev_sc_quad_fold_eval(c, a0.d.p, b0.d.p, h, rr, 0); c.wait_ticket(tk); e_plain[0] = c.h_results[0]; e_plain[1] = c.h_results[1];
+        tk = dev_sc_quad_fold_eval_armed(c, a1.d.p, b1.d.p, h, 0); c.go(&rr, 1); c.wait_ticket(tk);
+        if (memcmp(e_plain, c.h_results, 64)) throw Error(OTTI_ERR_INTERNAL, "armed round after an abort: sums differ from the plain launch");
+        c.sync();
+        // armed, and the host stalls beyond the launch's deadline (shortened to 2 ms here): the leader gives up for the WHOLE grid (nothing
+        // folded, in any workgroup), says so, the host's wait fails at once, and the context is clean for the next round
+        if (len >= 16) {
+            const size_t q = h / 2;                                                      // both table pairs are down to q elements by now
+            download(c, before.data(), a1.d.p, q); c.sync();
+            struct Restore { DevCtx &c; unsigned long long d; ~Restore() { c.arm_deadline = d; } } restore{c, c.arm_deadline};
+            c.arm_deadline = 200000ull;                                                  // 2 ms of the 100 MHz clock
+            tk = dev_sc_quad_fold_eval_armed(c, a1.d.p, b1.d.p, q, 0);
+            { const auto t0 = std::chrono::steady_clock::now(); while (std::chrono::steady_clock::now() - t0 < std::chrono::milliseconds(20)) {} }
+            bool failed = false;
+            try { c.go(&rr, 1); c.wait_ticket(tk); } catch (const Error &) { failed = true; }
+            if (!failed) throw Error(OTTI_ERR_INTERNAL, "armed round past its deadline still delivered a result");
+            c.arm_deadline = restore.d;
+            download(c, after.data(), a1.d.p, q); c.sync();
+            if (memcmp(before.data(), after.data(), 32 * q)) throw Error(OTTI_ERR_INTERNAL, "armed round past its deadline wrote to its tables");
+            unsigned cnt = 1; OTTI_HIP(hipMemcpy(&cnt, c.d_counter.p, sizeof cnt, hipMemcpyDeviceToHost));
+            if (cnt) throw Error(OTTI_ERR_INTERNAL, "arrival counter left non-zero after a timed-out armed round");
+            tk = dev_sc_quad_fold_eval(c, a0.d.p, b0.d.p, q, rr, 0); c.wait_ticket(tk); e_plain[0] = c.h_results[0]; e_plain[1] = c.h_results[1];
+            tk = dev_sc_quad_fold_eval_armed(c, a1.d.p, b1.d.p, q, 0); c.go(&rr, 1); c.wait_ticket(tk);
+            if (memcmp(e_plain, c.h_results, 64)) throw Error(OTTI_ERR_INTERNAL, "armed round after a timed-out one: sums differ from the plain launch");
+            c.sync();
+        }
+        return OTTI_OK;
+    });
+}
+// The verifier's variable-base sum (spartan.h RowSumBeginHook / FinishHook): sum_i s[i] * decode(C[i]) on the device — batch decompression
+// (k_decode_niels), LDS-bucket Pippenger (k_msm_var), window recombination on the host.  No host fallback here: this entry exists to test the device path.
+int32_t otti_k_row_sum(const uint8_t *compressed32, size_t n, const uint8_t *scalars_mont32, uint8_t *out32) {
+    return guarded([&] {
+        if (!compressed32 || !scalars_mont32 || !out32 || n < 256) throw Error(OTTI_ERR_BAD_ARG, "null argument or fewer than 256 points");
+        if (!g_row_sum_begin_hook || !g_row_sum_finish_hook) throw Error(OTTI_ERR_NO_DEVICE, "no device path registered");
+        DevCtx::get();                                             // NoDevice surfaces here rather than as a declined job
+        RowSumJob *job = g_row_sum_begin_hook(reinterpret_cast<const CPoint *>(compressed32), n);
+        if (!job) throw Error(OTTI_ERR_NO_DEVICE, "the device declined the row sum");
+        std::vector<Fr> s(n); memcpy(s.data(), scalars_mont32, 32 * n);
+        Pt sum; const int rc = g_row_sum_finish_hook(job, s.data(), sum);
+        if (rc == OTTI_ERR_VERIFY_DECOMPRESS) throw Error(OTTI_ERR_VERIFY_DECOMPRESS, "a point does not decode");
+        if (rc) throw Error(OTTI_ERR_INTERNAL, "device row sum failed");
+        pt_encode(out32, sum); return OTTI_OK;
+    });
+}
+int32_t otti_k_msm_rows(otti_gens *gens, const uint8_t *Z, size_t L, size_t R, const uint8_t *blinds, uint8_t *out32, float *ms) {
+    return guarded([&] {
+        DevCtx &c = DevCtx::get(); Gens &g = *gens->g;
+        if (R != g.R) throw Error(OTTI_ERR_BAD_ARG, "row length differs from the generator count");
+        ensure_gens_device(g);
+        Staged z(c, Z, L * R), bl(c, blinds, L);
+        uint32_t hb = g.pc_n.h;
+        const bool sparse = dev_small_fraction(c, z.d.p, L * R) > 0.25;                  // the prover takes this from the resident witness
+        KTimer t(c, ms); dev_msm_rows(c, *g.dev, z.d.p, R, R, L, bl.d.p, &hb, 1, MSM_COMPRESSED, nullptr, sparse); t.stop();
+        c.sync(); memcpy(out32, c.h_points, 32 * L); return OTTI_OK;
+    });
+}
+
+// ---- the prover's own kernels for phase one / evaluation proof / bullet reduction
+int32_t otti_k_eq_pyramid(const uint8_t *r, size_t n, uint8_t *out) {
+    return guarded([&] {
+        if (n > 13) throw Error(OTTI_ERR_BAD_ARG, "n > 13");
+        DevCtx &c = DevCtx::get(); std::vector<Fr> rr = fr_load_vec(r, n); const size_t total = ((size_t)2 << n) - 1;
+        DevBuf<Fr> o(total); dev_eq_pyramid(c, rr.data(), n, o.p); download(c, out, o.p, total); c.sync(); return OTTI_OK;
+    });
+}
+int32_t otti_k_sc_cubic3_round(const uint8_t *B, const uint8_t *C, const uint8_t *D, size_t len, const uint8_t *tau, uint8_t *e3, float *ms) {
+    return guarded([&] {
+        if (len < 2 || (len & (len - 1))) throw Error(OTTI_ERR_BAD_ARG, "len must be a power of two >= 2");
+        DevCtx &c = DevCtx::get(); Staged b(c, B, len), cc(c, C, len), d(c, D, len);
+        const size_t m = ilog2(len) - 1; std::vector<Fr> t = fr_load_vec(tau, m); EqPyramids py(c, t.data(), m);
+        KTimer tm(c, ms); auto tk = dev_sc_cubic3_eval(c, b.d.p, cc.d.p, d.d.p, len, py.top(), 0); tm.stop();
+        c.wait_ticket(tk); memcpy(e3, c.h_results, 96); c.sync(); return OTTI_OK;
+    });
+}
+int32_t otti_k_sc_cubic3_fold_round(const uint8_t *B, const uint8_t *C, const uint8_t *D, size_t len, const uint8_t *r, const uint8_t *tau,
+                                    uint8_t *out3, uint8_t *e3, float *ms) {
+    return guarded([&] {
+        if (len < 4 || (len & (len - 1))) throw Error(OTTI_ERR_BAD_ARG, "len must be a power of two >= 4");
+        DevCtx &c = DevCtx::get(); Staged b(c, B, len), cc(c, C, len), d(c, D, len);
+        const size_t m = ilog2(len) - 2; std::vector<Fr> t = fr_load_vec(tau, m); EqPyramids py(c, t.data(), m);
+        KTimer tm(c, ms); auto tk = dev_sc_cubic3_fold_eval(c, b.d.p, cc.d.p, d.d.p, len, fr_load(r), py.top(), 0); tm.stop();
+        const size_t h = len / 2;
+        download(c, out3, b.d.p, h); download(c, out3 + 32 * h, cc.d.p, h); download(c, out3 + 64 * h, d.d.p, h);
+        c.sync(); c.wait_ticket(tk); memcpy(e3, c.h_results, 96); return OTTI_OK;
+    });
+}
+int32_t otti_k_poly_bound(const uint8_t *Z, size_t L, size_t R, const uint8_t *Lv, uint8_t *out, float *ms) {
+    return guarded([&] {
+        if (!L || !R) throw Error(OTTI_ERR_BAD_ARG, "empty matrix");
+        DevCtx &c = DevCtx::get(); Staged z(c, Z, L * R), lv(c, Lv, L); DevBuf<Fr> o(R), scratch(64 * R);
+        KTimer tm(c, ms); dev_poly_bound(c, z.d.p, L, R, lv.d.p, o.p, scratch.p); tm.stop();
+        download(c, out, o.p, R); c.sync(); return OTTI_OK;
+    });
+}
+int32_t otti_k_bullet_round(otti_gens *gens, size_t n_cur, int32_t fold, const uint8_t *u, const uint8_t *uinv, const uint8_t *a, const uint8_t *b,
+                            const uint8_t *s, const uint8_t *blinds2, uint8_t *a_out, uint8_t *b_out, uint8_t *s_out, uint8_t *LR64, float *ms) {
+    return guarded([&] {
+        DevCtx &c = DevCtx::get(); Gens &g = *gens->g; ensure_gens_device(g);
+        const size_t R = g.R;
+        if (n_cur < 2 || n_cur > R || (n_cur & (n_cur - 1))) throw Error(OTTI_ERR_BAD_ARG, "n_cur must be a power of two in [2, R]");
+        const size_t n_in = fold ? 2 * n_cur : n_cur;
+        if (n_in > R) throw Error(OTTI_ERR_BAD_ARG, "folding needs 2 * n_cur <= R");
+        Staged A(c, a, n_in), B(c, b, n_in), S(c, s, R); DevBuf<Fr> Ao(R), Bo(R), So(R), ex(4);
+        Fr exh[4] = {fr_zero(), fr_load(blinds2), fr_zero(), fr_load(blinds2 + 32)};
+        OTTI_HIP(hipMemcpyAsync(ex.p, exh, sizeof exh, hipMemcpyHostToDevice, c.stream));
+        OTTI_HIP(hipMemcpyAsync(So.p, S.d.p, R * sizeof(Fr), hipMemcpyDeviceToDevice, c.stream));   // slots this round does not walk keep their value
+        c.ensure_points(2, 128);
+        const uint32_t qh[2] = {g.pc_1.G[0], g.pc_n.h};
+        const Fr uu = fold ? fr_load(u) : fr_zero(), ui = fold ? fr_load(uinv) : fr_zero();
+        KTimer tm(c, ms);
+        auto tk = dev_bullet_round(c, *g.dev, R, n_cur, fold != 0, uu, ui, A.d.p, B.d.p, S.d.p, Ao.p, Bo.p, So.p, ex.p, qh);
+        tm.stop();
+        c.wait_points(tk); memcpy(LR64, c.h_points, 64);
+        download(c, a_out, Ao.p, n_cur); download(c, b_out, Bo.p, n_cur); download(c, s_out, So.p, R); c.sync(); return OTTI_OK;
+    });
+}
+int32_t otti_k_bullet_last_fold(size_t R, const uint8_t *u, const uint8_t *uinv, uint8_t *a2, uint8_t *b2, uint8_t *s) {
+    return guarded([&] {
+        if (R < 2) throw Error(OTTI_ERR_BAD_ARG, "R < 2");
+        DevCtx &c = DevCtx::get(); Staged A(c, a2, 2), B(c, b2, 2), S(c, s, R); DevBuf<Fr> rows(2 * R), ex(4);
+        dev_bullet_step(c, A.d.p, B.d.p, S.d.p, R, 1, true, fr_load(u), fr_load(uinv), rows.p, ex.p);
+        download(c, a2, A.d.p, 1); download(c, b2, B.d.p, 1); download(c, s, S.d.p, R); c.sync(); return OTTI_OK;
+    });
+}
+
+// ---- SNARK mode's kernels (k_snark.hip, snark_dev.h): each entry stages the caller's tables and calls the launch function snark_prover.cpp calls.
+// Lists travel as ONE array: instance y's table at element y * len; third tables only for the instances that have one (has_C[y] != 0), in order.
+int32_t otti_k_pc_round(const uint8_t *A, const uint8_t *B, const uint8_t *C, const uint8_t *has_C, size_t ninst, size_t len, const uint8_t *tau, const uint8_t *r,
+                        uint32_t G, uint32_t rk, uint8_t *out, uint8_t *e, float *ms) {
+    return guarded([&] {
+        check_pc_list(A, B, C, has_C, ninst, len);
+        if (!e || (r && !out)) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (len < (r ? 4u : 2u)) throw Error(OTTI_ERR_BAD_ARG, "table length must be >= 2 (>= 4 with a fold)");
+        if (!pow2(G) || rk >= G) throw Error(OTTI_ERR_BAD_ARG, "G must be a power of two and rk below it");
+        const size_t items = len / (r ? 4 : 2), m = ilog2(items * G);               // the eq table covers every rank's items
+        if (m > 25 || (m && !tau)) throw Error(OTTI_ERR_BAD_ARG, "eq table over more than 25 variables, or no tau");
+        DevCtx &c = DevCtx::get(); StagedPc T(c, A, B, C, has_C, ninst, len);
+        std::vector<Fr> t = fr_load_vec(tau, m); EqPyramids py(c, t.data(), m);
+        EqSrc E = py.top(); E.stride = G; E.offset = rk;
+        const Fr rr = r ? fr_load(r) : fr_zero();
+        KTimer tm(c, ms); auto tk = r ? dev_pc_fold_eval(c, T.L, len, &rr, E, kSumSlot) : dev_pc_eval(c, T.L, len, E, kSumSlot); tm.stop();
+        if (r) { const size_t h = len / 2; uint8_t *o = out;
+            for (size_t y = 0; y < ninst; y++, o += 32 * h) download(c, o, T.L.A[y], h);
+            for (size_t y = 0; y < ninst; y++, o += 32 * h) download(c, o, T.L.B[y], h);
+            for (size_t y = 0; y < ninst; y++) if (T.L.C[y]) { download(c, o, T.L.C[y], h); o += 32 * h; } }
+        c.sync(); c.wait_ticket(tk); memcpy(e, &c.h_results[kSumSlot], 96 * ninst); return OTTI_OK;
+    });
+}
+int32_t otti_k_pc_export(const uint8_t *A, const uint8_t *B, const uint8_t *C, const uint8_t *has_C, size_t ninst, size_t len, const uint8_t *fold_r, uint8_t *out) {
+    return guarded([&] {
+        check_pc_list(A, B, C, has_C, ninst, len);
+        if (!out) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (fold_r && len < 2) throw Error(OTTI_ERR_BAD_ARG, "table length must be >= 2 with a fold");
+        const size_t n_out = fold_r ? len / 2 : len;
+        if (kPcTailSlot + 3 * ninst * n_out > (size_t)kResultSlots) throw Error(OTTI_ERR_BAD_ARG, "the exported tables do not fit the pinned result buffer");
+        DevCtx &c = DevCtx::get(); StagedPc T(c, A, B, C, has_C, ninst, len);
+        const Fr rr = fold_r ? fr_load(fold_r) : fr_zero();
+        memset(&c.h_results[kPcTailSlot], 0, 96 * ninst * n_out);                      // (an absent third table's place is not written)
+        auto tk = dev_pc_export(c, T.L, len, fold_r != nullptr, fold_r ? &rr : nullptr, kPcTailSlot);
+        c.wait_ticket(tk); memcpy(out, &c.h_results[kPcTailSlot], 96 * ninst * n_out); c.sync(); return OTTI_OK;
+    });
+}
+// the rounds of one persistent launch played as pcbatch_prove plays them: per round the W * ninst mail lines summed per instance, then the challenge
+int32_t otti_k_pc_tail(const uint8_t *A, const uint8_t *B, const uint8_t *C, const uint8_t *has_C, size_t ninst, size_t len0, uint32_t W, size_t t_out,
+                       const uint8_t *tau, const uint8_t *rs, const uint8_t *fold_r, int32_t top, uint8_t *sums, uint8_t *out) {
+    return guarded([&] {
+        check_pc_list(A, B, C, has_C, ninst, len0);
+        if (!tau || !rs || !sums || !out) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (!pow2(W) || !pow2(t_out) || ninst * W > (size_t)kTailMaxGroups || len0 / W > (size_t)kTailCap || t_out < W || len0 <= t_out)
+            throw Error(OTTI_ERR_BAD_ARG, "persistent sum-check tail: W and t_out powers of two, W <= t_out < len0, at most kTailCap elements per workgroup, at most kTailMaxGroups workgroups");
+        if (kPcTailSlot + 3 * ninst * t_out > (size_t)kResultSlots) throw Error(OTTI_ERR_BAD_ARG, "the handed-over tables do not fit the pinned result buffer");
+        const size_t nt = ilog2(len0), rounds = nt - ilog2(t_out);
+        DevCtx &c = DevCtx::get();
+        if (!c.armed_ok()) throw Error(OTTI_ERR_BAD_ARG, "armed launches are off: the prover would not launch the persistent tail");
+        if (ninst * W > (size_t)std::min(kTailMaxGroups, c.num_cu)) throw Error(OTTI_ERR_BAD_ARG, "more workgroups than the device has CUs: the grid would not be resident as a whole");
+        StagedPc T(c, A, B, C, has_C, ninst, fold_r ? 2 * len0 : len0);
+        std::vector<Fr> t = fr_load_vec(tau, nt), rr = fr_load_vec(rs, rounds);
+        const size_t mt = top ? nt - 1 : nt;                                            // tabulated variables; top: tau[0] travels as EqSrc.top
+        EqPyramids py(c, t.data() + (top ? 1 : 0), mt);
+        EqSrc E = py.top(); if (top) { E.top_bit = (int)mt; E.top = t[0]; }
+        const Fr fr = fold_r ? fr_load(fold_r) : fr_zero();
+        memset(&c.h_results[kPcTailSlot], 0, 96 * ninst * t_out);
+        SpinPool::Session pool_session;
+        struct Release { DevCtx &c; ~Release() { c.go_abort(); } } release{c};          // an exception must not leave the grid waiting for the host
+        const unsigned long long seq0 = dev_pc_tail(c, T.L, (int)W, len0, t_out, fold_r ? &fr : nullptr, E, kPcTailSlot);
+        for (size_t j = 0; j < rounds; j++) {
+            Fr s[3 * kMaxInst];
+            c.wait_tail_sums((int)ninst, (int)W, seq0 + j, s);
+            memcpy(sums + 96 * ninst * j, s, 96 * ninst);
+            c.go(&rr[j], 1);
+        }
+        c.wait_tail((int)(ninst * W), seq0 + rounds);
+        memcpy(out, &c.h_results[kPcTailSlot], 96 * ninst * t_out);
+        c.sync(); return OTTI_OK;
+    });
+}
+int32_t otti_k_prod_layer(const uint8_t *left, const uint8_t *right, size_t ninst, size_t q, uint8_t *out_left, uint8_t *out_right, float *ms) {
+    return guarded([&] {
+        if (!left || !right || !out_left || !out_right) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (ninst < 1 || ninst > 16 || q < 1) throw Error(OTTI_ERR_BAD_ARG, "a layer has 1 .. 16 circuits of at least one pair");
+        DevCtx &c = DevCtx::get(); Staged l(c, left, ninst * 2 * q), r(c, right, ninst * 2 * q); DevBuf<Fr> ol(ninst * q), orr(ninst * q);
+        LayerList L; L.n = (int)ninst;
+        for (size_t y = 0; y < ninst; y++) { L.in_left[y] = l.d.p + y * 2 * q; L.in_right[y] = r.d.p + y * 2 * q; L.out_left[y] = ol.p + y * q; L.out_right[y] = orr.p + y * q; }
+        KTimer tm(c, ms); dev_prod_layer(c, L, q); tm.stop();
+        download(c, out_left, ol.p, ninst * q); download(c, out_right, orr.p, ninst * q); c.sync(); return OTTI_OK;
+    });
+}
+static void check_shard(size_t n, uint32_t G, uint32_t rk) {
+    if (!pow2(n) || !pow2(G) || rk >= G || n / G < 2) throw Error(OTTI_ERR_BAD_ARG, "hash layer: n and G powers of two, rk < G, at least two elements per rank");
+}
+int32_t otti_k_hash_mem(const uint8_t *eval_table, const uint8_t *audit_ts, size_t M, const uint8_t *r, const uint8_t *gamma, uint32_t G, uint32_t rk,
+                        uint8_t *out_init, uint8_t *out_audit, float *ms) {
+    return guarded([&] {
+        if (!eval_table || !audit_ts || !r || !gamma || !out_init || !out_audit) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        check_shard(M, G, rk);
+        DevCtx &c = DevCtx::get(); Staged ev(c, eval_table, M), au(c, audit_ts, M); const size_t Ml = M / G; DevBuf<Fr> oi(Ml), oa(Ml);
+        KTimer tm(c, ms); dev_hash_mem(c, ev.d.p, au.d.p, oi.p, oa.p, M, fr_load(r), fr_load(gamma), (int)G, (int)rk); tm.stop();
+        download(c, out_init, oi.p, Ml); download(c, out_audit, oa.p, Ml); c.sync(); return OTTI_OK;
+    });
+}
+int32_t otti_k_hash_ops(const uint8_t *addr, const uint8_t *deref, const uint8_t *read_ts, size_t N, const uint8_t *r, const uint8_t *gamma, uint32_t G, uint32_t rk,
+                        uint8_t *out_read, uint8_t *out_write, float *ms) {
+    return guarded([&] {
+        if (!addr || !deref || !read_ts || !r || !gamma || !out_read || !out_write) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        check_shard(N, G, rk);
+        DevCtx &c = DevCtx::get(); Staged ad(c, addr, N), de(c, deref, N), ts(c, read_ts, N); const size_t Nl = N / G; DevBuf<Fr> ord(Nl), owr(Nl);
+        KTimer tm(c, ms); dev_hash_ops(c, ad.d.p, de.d.p, ts.d.p, ord.p, owr.p, N, fr_load(r), fr_load(gamma), (int)G, (int)rk); tm.stop();
+        download(c, out_read, ord.p, Nl); download(c, out_write, owr.p, Nl); c.sync(); return OTTI_OK;
+    });
+}
+int32_t otti_k_dot_many(const uint8_t *E, const uint8_t *Ps, size_t npoly, size_t n, uint8_t *out, float *ms) {
+    return guarded([&] {
+        if (!E || !Ps || !out) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (npoly < 1 || npoly > 64 || n < 1) throw Error(OTTI_ERR_BAD_ARG, "1 .. 64 polynomials of at least one element");
+        DevCtx &c = DevCtx::get(); Staged e(c, E, n), p(c, Ps, npoly * n); DevBuf<Fr> partials(kSnarkPartials);
+        PtrList L; L.n = (int)npoly; for (size_t y = 0; y < npoly; y++) L.p[y] = p.d.p + y * n;
+        KTimer tm(c, ms); dev_dot_many(c, e.d.p, L, n, partials.p, kSumSlot); tm.stop();
+        c.sync(); memcpy(out, &c.h_results[kSumSlot], 32 * npoly); return OTTI_OK;
+    });
+}
+int32_t otti_k_sum3(const uint8_t *A, const uint8_t *B, const uint8_t *C, size_t ninst, size_t n, uint8_t *out, float *ms) {
+    return guarded([&] {
+        if (!A || !B || !C || !out) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (ninst < 1 || ninst > (size_t)kMaxInst || n < 1) throw Error(OTTI_ERR_BAD_ARG, "1 .. kMaxInst triples of at least one element");
+        DevCtx &c = DevCtx::get(); Staged a(c, A, ninst * n), b(c, B, ninst * n), cc(c, C, ninst * n); DevBuf<Fr> partials(kSnarkPartials);
+        AbcList L; L.n = (int)ninst; for (size_t y = 0; y < ninst; y++) { L.A[y] = a.d.p + y * n; L.B[y] = b.d.p + y * n; L.C[y] = cc.d.p + y * n; }
+        KTimer tm(c, ms); dev_sum3(c, L, n, partials.p, kSumSlot); tm.stop();
+        c.sync(); memcpy(out, &c.h_results[kSumSlot], 32 * ninst); return OTTI_OK;
+    });
+}
+int32_t otti_k_poly_bound_chunks(const uint8_t *Z, size_t L, size_t R, const uint8_t *Lv_rest, size_t m, uint8_t *out, int32_t *launched, float *ms) {
+    return guarded([&] {
+        if (!Z || !Lv_rest || !out || !launched) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (!L || !R || !m) throw Error(OTTI_ERR_BAD_ARG, "empty matrix");
+        DevCtx &c = DevCtx::get(); Staged z(c, Z, L * R), lv(c, Lv_rest, m); DevBuf<Fr> o(std::max<size_t>(1, (L / m) * R)), scratch(64 * R);
+        KTimer tm(c, ms); const bool ok = dev_poly_bound_chunks(c, z.d.p, L, R, lv.d.p, m, o.p, scratch.p); tm.stop();
+        *launched = ok ? 1 : 0;
+        if (ok) download(c, out, o.p, (L / m) * R);
+        c.sync(); return OTTI_OK;
+    });
+}
+
+// ---- device pointers + caller's stream
+static const Fr *dfr(const void *p) { return reinterpret_cast<const Fr *>(p); }
+static Fr *dfr(void *p) { return reinterpret_cast<Fr *>(p); }
+int32_t otti_dev_alloc(size_t nbytes, void **out) { return guarded([&] { if (!out) throw Error(OTTI_ERR_BAD_ARG, "null argument"); DevCtx::get(); OTTI_HIP(hipMalloc(out, std::max<size_t>(nbytes, 1))); return OTTI_OK; }); }
+int32_t otti_dev_free(void *d) { return guarded([&] { if (d) OTTI_HIP(hipFree(d)); return OTTI_OK; }); }
+int32_t otti_dev_upload(void *d, const void *h, size_t n) { return guarded([&] { DevCtx::get(); if (n) OTTI_HIP(hipMemcpy(d, h, n, hipMemcpyHostToDevice)); return OTTI_OK; }); }
+int32_t otti_dev_download(void *h, const void *d, size_t n) { return guarded([&] { DevCtx::get(); if (n) OTTI_HIP(hipMemcpy(h, d, n, hipMemcpyDeviceToHost)); return OTTI_OK; }); }
+int32_t otti_dev_stream_create(void **out) { return guarded([&] { if (!out) throw Error(OTTI_ERR_BAD_ARG, "null argument"); DevCtx::get(); hipStream_t s; OTTI_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); *out = (void *)s; return OTTI_OK; }); }
+int32_t otti_dev_stream_sync(void *stream) { return guarded([&] { OTTI_HIP(hipStreamSynchronize((hipStream_t)stream)); return OTTI_OK; }); }
+int32_t otti_dev_stream_destroy(void *stream) { return guarded([&] { if (stream) OTTI_HIP(hipStreamDestroy((hipStream_t)stream)); return OTTI_OK; }); }
+int32_t otti_kd_multiply_vec(otti_instance *inst, const void *z, void *Az, void *Bz, void *Cz, void *stream) {
+    return guarded([&] {
+        if (!inst || !z || !Az || !Bz || !Cz) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        DevCtx &c = DevCtx::get(); Instance &I = *inst->I; ensure_instance_device(I); StreamScope ss(c, stream);
+        dev_spmv3(c, I.dev->by_row, dfr(z), dfr(Az), dfr(Bz), dfr(Cz), false, nullptr); return OTTI_OK;
+    });
+}
+int32_t otti_kd_check_sat(otti_instance *inst, const void *z, void *bits, uint64_t *n_unsat, void *stream) {
+    return guarded([&] {
+        if (!inst || !z || !bits) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        DevCtx &c = DevCtx::get(); Instance &I = *inst->I; ensure_instance_device(I); StreamScope ss(c, stream);
+        dev_sat_pass(c, I.dev->by_row, dfr(z), reinterpret_cast<unsigned long long *>(bits));
+        if (n_unsat) *n_unsat = dev_sat_count(c);                 // waits for the pass; without it the call only enqueues
+        return OTTI_OK;
+    });
+}
+int32_t otti_kd_eval_table_sparse(otti_instance *inst, const void *eq_rx, const uint8_t *rABC, void *out, void *stream) {
+    return guarded([&] {
+        if (!inst || !eq_rx || !rABC || !out) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        DevCtx &c = DevCtx::get(); Instance &I = *inst->I; ensure_instance_device(I); StreamScope ss(c, stream);
+        Fr coef[3] = {fr_load(rABC), fr_load(rABC + 32), fr_load(rABC + 64)};
+        dev_spmv3(c, I.dev->by_col, dfr(eq_rx), dfr(out), nullptr, nullptr, true, coef); return OTTI_OK;
+    });
+}
+int32_t otti_kd_eq_evals(const uint8_t *r, size_t ell, void *out, void *stream) {
+    return guarded([&] {
+        if (ell > 25 || !out) throw Error(OTTI_ERR_BAD_ARG, "ell > 25 or null output");
+        DevCtx &c = DevCtx::get(); StreamScope ss(c, stream); std::vector<Fr> rr = fr_load_vec(r, ell);
+        DevBuf<Fr> s(5 * 4096);
+        dev_eq_evals(c, rr.data(), ell, dfr(out), s.p);
+        OTTI_HIP(hipStreamSynchronize(c.stream));                // the scratch tables are freed on return
+        return OTTI_OK;
+    });
+}
+int32_t otti_kd_fold_top(void *Z, size_t len, const uint8_t *r, void *stream) {
+    return guarded([&] { DevCtx &c = DevCtx::get(); StreamScope ss(c, stream); dev_fold_top(c, dfr(Z), len, fr_load(r)); return OTTI_OK; });
+}
+int32_t otti_kd_fold_bot(const void *Z, void *out, size_t len, const uint8_t *r, void *stream) {
+    return guarded([&] { DevCtx &c = DevCtx::get(); StreamScope ss(c, stream); dev_fold_bot(c, dfr(Z), dfr(out), len, fr_load(r)); return OTTI_OK; });
+}
+int32_t otti_kd_sc_cubic_round(const void *A, const void *B, const void *C, const void *D, size_t len, uint8_t *e3, void *stream) {
+    return guarded([&] {
+        DevCtx &c = DevCtx::get(); StreamScope ss(c, stream);
+        auto tk = dev_sc_cubic_eval(c, dfr(A), dfr(B), dfr(C), dfr(D), len, 0); c.wait_ticket(tk); memcpy(e3, c.h_results, 96); return OTTI_OK;
+    });
+}
+int32_t otti_kd_sc_cubic_fold_round(void *A, void *B, void *C, void *D, size_t len, const uint8_t *r, uint8_t *e3, void *stream) {
+    return guarded([&] {
+        DevCtx &c = DevCtx::get(); StreamScope ss(c, stream);
+        auto tk = dev_sc_cubic_fold_eval(c, dfr(A), dfr(B), dfr(C), dfr(D), len, fr_load(r), 0); c.wait_ticket(tk); memcpy(e3, c.h_results, 96); return OTTI_OK;
+    });
+}
+int32_t otti_kd_sc_quad_round(const void *A, const void *B, size_t len, uint8_t *e2, void *stream) {
+    return guarded([&] {
+        DevCtx &c = DevCtx::get(); StreamScope ss(c, stream);
+        auto tk = dev_sc_quad_eval(c, dfr(A), dfr(B), len, 0); c.wait_ticket(tk); memcpy(e2, c.h_results, 64); return OTTI_OK;
+    });
+}
+int32_t otti_kd_sc_quad_fold_round(void *A, void *B, size_t len, const uint8_t *r, uint8_t *e2, void *stream) {
+    return guarded([&] {
+        DevCtx &c = DevCtx::get(); StreamScope ss(c, stream);
+        auto tk = dev_sc_quad_fold_eval(c, dfr(A), dfr(B), len, fr_load(r), 0); c.wait_ticket(tk); memcpy(e2, c.h_results, 64); return OTTI_OK;
+    });
+}
+int32_t otti_kd_msm_rows(otti_gens *gens, const void *Z, size_t L, size_t R, const void *blinds, void *out32, void *stream) {
+    return guarded([&] {
+        if (!gens || !Z || !blinds || !out32 || !L) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        DevCtx &c = DevCtx::get(); Gens &g = *gens->g;
+        if (R != g.R) throw Error(OTTI_ERR_BAD_ARG, "row length differs from the generator count");
+        ensure_gens_device(g); StreamScope ss(c, stream);
+        uint32_t hb = g.pc_n.h;
+        dev_msm_rows(c, *g.dev, dfr(Z), R, R, L, dfr(blinds), &hb, 1, MSM_COMPRESSED, nullptr, false);
+        if (L > kHostEncodeRows) OTTI_HIP(hipMemcpyAsync(out32, c.d_points.p, 32 * L, hipMemcpyDeviceToDevice, c.stream));
+        else { c.sync(); OTTI_HIP(hipMemcpyAsync(out32, c.h_points, 32 * L, hipMemcpyHostToDevice, c.stream)); OTTI_HIP(hipStreamSynchronize(c.stream)); }
+        return OTTI_OK;
+    });
+}
+
+int32_t otti_bench_madd_peak(double *madds_per_second) {
+    return guarded([&] { if (!madds_per_second) throw Error(OTTI_ERR_BAD_ARG, "null argument"); *madds_per_second = dev_madd_peak(DevCtx::get()); return OTTI_OK; });
+}
+
+int32_t otti_bench_fr_mul_peak(double *products_per_second) {
+    return guarded([&] { if (!products_per_second) throw Error(OTTI_ERR_BAD_ARG, "null argument"); *products_per_second = dev_fr_mul_peak(DevCtx::get()); return OTTI_OK; });
+}
+
+// ------------------------------------------------------------------------------------------------ kernel timing (HIP events on the library stream)
+static const char *kClassNames[KC_COUNT] = {"msm_rows", "msm_small", "msm_finish", "sc_cubic", "sc_quad", "spmv", "eq", "reduce", "poly_bound", "bullet", "other",
+                                               "pc_round", "prod_layer", "hash_layer", "gather", "dot_many", "decode", "msm_var", "sat_check"};
+int32_t otti_stats_enable(int32_t on) { KStats::get().on = on != 0; KStats::get().mask = 0xffffffffu; KStats::get().reset(); return OTTI_OK; }
+int32_t otti_stats_select(const char *kernel_class) {
+    for (int k = 0; k < KC_COUNT; k++) if (!strcmp(kernel_class, kClassNames[k])) { KStats::get().mask = 1u << k; return OTTI_OK; }
+    return OTTI_ERR_BAD_ARG;
+}
+int32_t otti_armed_launches_on(int32_t *on) { return guarded([&] { if (!on) throw Error(OTTI_ERR_BAD_ARG, "null argument"); *on = DevCtx::get().armed_ok() ? 1 : 0; return OTTI_OK; }); }
+int32_t otti_stats_read(const char *kernel_class, uint64_t *count, double *total_ms) {
+    return guarded([&] {
+        KStats &s = KStats::get();
+        if (s.used) { DevCtx::get().sync(); s.flush(); }
+        for (int k = 0; k < KC_COUNT; k++) if (!strcmp(kernel_class, kClassNames[k])) { if (count) *count = s.count[k]; if (total_ms) *total_ms = s.total_ms[k]; return OTTI_OK; }
+        throw Error(OTTI_ERR_BAD_ARG, "unknown kernel class");
+    });
+}
+
+// ------------------------------------------------------------------------------------------------ u64-lane transport of Fr sums
+void otti_lanes_pack(const uint8_t *fr, size_t n, uint64_t *lanes) {
+    for (size_t i = 0; i < n; i++) for (int k = 0; k < 8; k++) { uint32_t w; memcpy(&w, fr + 32 * i + 4 * k, 4); lanes[8 * i + k] = w; }
+}
+void otti_lanes_unpack(const uint64_t *lanes, size_t n, uint8_t *fr) {
+    std::vector<Fr> out(n);
+    lanes_to_fr(lanes, n, out.data());                                  // shard.cpp: carries, then reduction mod l (Montgomery form kept)
+    for (size_t i = 0; i < n; i++) memcpy(fr + 32 * i, out[i].v, 32);
+}
+
+}  // extern "C"

@@ -108,6 +108,7 @@ struct TailMailbox { TailMail *host = nullptr, *dev = nullptr; void ensure(DevCt
 struct WaitLimits;                                           // waits.cpp: cadence, time limit and failure handling of one host wait
 struct Armed { GoBox *host; GoBox *dev; unsigned long long want, deadline; int relay = 1, pollers = 1; };   // relay 0: the copy's number is polled alone and the values loaded after it (OTTI_RELAY=0; A/B)   // want == 0: not armed (values come as kernel arguments); deadline in 100 MHz ticks
 constexpr unsigned long long kArmDeadlineTicks = 3000000000ull;   // 30 s of s_memrealtime: longer than any host stall the prover's own 20 s result wait tolerates
+constexpr int kMaxBlocks = 2048;                             // 8 workgroups per CU; grid-stride beyond that (kernels_common.h grid_for, k_snark.hip many_grid)
 constexpr size_t kArmMaxLen = 65536;                         // sum-check tables up to this length fold in <= 64 workgroups: only those launches are armed
 
 struct DevCtx {

@@ -15,7 +15,6 @@
 namespace otti {
 
 constexpr int kBlock = 256;
-constexpr int kMaxBlocks = 2048;           // 8 workgroups per CU; grid-stride beyond that
 constexpr int kHeavyRow = 64;              // sparse rows longer than this go to the one-workgroup-per-row kernel
 
 static inline int grid_for(size_t n) { size_t b = (n + kBlock - 1) / kBlock; return (int)std::max<size_t>(1, std::min<size_t>(b, kMaxBlocks)); }

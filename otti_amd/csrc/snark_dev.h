@@ -5,6 +5,10 @@
 namespace otti {
 
 constexpr int kMaxInst = 20;                                  // 12 product circuits + 6 dot-product halves in the largest batch
+// Places in the pinned result buffer (c.h_results) and scratch sizes that the prover and the kernel-level test entries must agree on
+constexpr int kSumSlot = 64;                                  // where a round's sums land
+constexpr int kPcTailSlot = 128;                              // where a layer's exported / handed-over tables start
+constexpr size_t kSnarkPartials = (size_t)3 * kMaxBlocks + 64;   // dev_dot_many / dev_sum3 scratch: 3 sums x at most kMaxBlocks workgroups per launch (k_snark.hip many_grid)
 struct AbcList { const Fr *A[kMaxInst], *B[kMaxInst], *C[kMaxInst]; int n; };
 struct PtrList { Fr *p[64]; int n; };
 struct LayerList { const Fr *in_left[16], *in_right[16]; Fr *out_left[16], *out_right[16]; int n; };
@@ -53,7 +57,7 @@ void dev_addr_timestamps(DevCtx &c, const AddrTs &a);
 void dev_hash_mem(DevCtx &c, const Fr *eval_table, const Fr *audit_ts, Fr *out_init, Fr *out_audit, size_t M, const Fr &r, const Fr &gamma, int G = 1, int rk = 0);   // G ranks: this rank's residue class (M / G elements) of the M-element vectors
 void dev_hash_ops(DevCtx &c, const Fr *addr_f, const Fr *deref, const Fr *read_ts, Fr *out_read, Fr *out_write, size_t N, const Fr &r, const Fr &gamma, int G = 1, int rk = 0);
 void dev_prod_layer(DevCtx &c, const LayerList &L, size_t q);
-// partials: >= 3 * kMaxBlocks elements of scratch.  Results arrive in c.h_results[slot ..] once the stream has been synchronised.
+// partials: kSnarkPartials elements of scratch.Results arrive in c.h_results[slot ..] once the stream has been synchronised.
 void dev_pick0(DevCtx &c, const PtrList &L, int slot);
 void dev_dot_many(DevCtx &c, const Fr *E, const PtrList &L, size_t n, Fr *partials, int slot);
 void dev_sum3(DevCtx &c, const AbcList &L, size_t n, Fr *partials, int slot);

@@ -25,7 +25,6 @@
 namespace otti {
 
 static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-constexpr int kSumSlot = 64;                                  // where a round's sums land in the pinned result buffer
 
 // the dense representation of sparse_mlpoly.rs MultiSparseMatPolynomialAsDense, resident in HBM
 struct DeviceDecomm {
@@ -286,7 +285,6 @@ struct DotpTables { Fr *l[6], *r[6], *w[6]; size_t len = 0; int n = 0; };
 // (two L2-resident pyramids of small tables, as phase one of the R1CS proof); the kernel returns S_t = sum_i E_j[i] (A_t B_t)[i] and the
 // host applies c_j * ((1 - rand_j) + t (2 rand_j - 1)).  Once the tables are down to T elements they are exported to pinned memory and
 // the host plays the last rounds itself: a launch + hand-off costs more than the arithmetic of such a round on a host core.
-constexpr int kPcTailSlot = 128;
 constexpr int kPcPreExportEnd = 7400;                       // pre-exported host-only layers end below the hash layer's ahead-of-time results (kHashEvalSlot)
 // sh (sharded SNARK::prove): the tables are this rank's residue classes (Circuits above; D: strided copies); a device round works on them
 // with the eq factor taken at the global index, its sums are added across the ranks (allreduce_fr: 3 elements per instance), and where the
@@ -690,7 +688,7 @@ static std::vector<uint8_t> snark_prove_resident_once(Instance &I, CompComm &com
     SnarkScratch &W = snark_workspace(c);
     struct Ptr { Fr *p; };                                    // (the buffers below used to be DevBufs of this proof; the code keeps reading x.p)
     const Ptr mem_rx{W.get(SS_MEM_RX, M)}, mem_ry{W.get(SS_MEM_RY, M)}, eqs{W.get(SS_EQS, 5 * 4096)}, derefs{W.get(SS_DEREFS, (size_t)8 * N)},
-              partials{W.get(SS_PARTIALS, (size_t)3 * 2048 + 64)};             // 3 sums x at most 2048 workgroups per launch (k_snark.hip many_grid)
+              partials{W.get(SS_PARTIALS, kSnarkPartials)};
     auto drow = [&](int k) { return derefs.p + (size_t)k * N; };
     auto dcol = [&](int k) { return derefs.p + (size_t)(3 + k) * N; };
     const size_t nm = ilog2(M);

@@ -159,6 +159,31 @@ def test_lanes_transport_of_field_sums(rng):
     assert int.from_bytes(oa.lanes_unpack(top)[0].tobytes(), "little") == (8 * (2 ** 256 - 1)) % L
 
 
+def test_last_error_is_one_object_across_the_abi_source_files():
+    """otti_last_error reads what a failing entry of ANY of the library's three C-ABI source files wrote (capi.cpp, capi_host.cpp,
+    capi_kernels.cpp), and a successful guarded call in one of them clears it for all."""
+    import ctypes
+    lib = oa.lib
+
+    def last_error():
+        buf = ctypes.create_string_buffer(512)
+        n = lib.otti_last_error(buf, 512)
+        assert n == len(buf.value)
+        return buf.value.decode()
+
+    BAD_ARG = int(re.search(r"OTTI_ERR_BAD_ARG\s*=\s*(-?\d+)", open(os.path.join(ROOT, "include", "otti_spartan.h")).read()).group(1))
+    assert lib.otti_instance_new(2, 2, 0, None, 0, None, 0, None, 0, None) == BAD_ARG                    # capi.cpp
+    assert last_error() == "null out pointer"
+    out32 = ctypes.create_string_buffer(32)
+    assert lib.otti_host_point_sum(None, 0, 0, 0, out32) == BAD_ARG                                      # capi_host.cpp: parts = 0
+    assert last_error() == "host point sum: bad arguments"
+    assert lib.otti_k_pc_round(None, None, None, None, 0, 2, None, None, 1, 0, None, None, None) == BAD_ARG   # capi_kernels.cpp: ninst = 0, before any device
+    assert last_error() == "a batch has 1 .. kMaxInst instances"
+    out128 = ctypes.create_string_buffer(128)
+    assert lib.otti_host_point_from_uniform(bytes(64), out128) == 0
+    assert last_error() == ""
+
+
 @pytest.mark.skipif(oa.device_count() > 0, reason="only meaningful without a GPU")
 def test_prove_fails_loudly_without_device():
     r = oa.synth_r1cs(8, 2, 1)
