@@ -244,8 +244,8 @@ int32_t otti_k_msm_rows(otti_gens *gens, const uint8_t *Z, size_t L, size_t R, c
         ensure_gens_device(g);
         Staged z(c, Z, L * R), bl(c, blinds, L);
         uint32_t hb = g.pc_n.h;
-        const bool sparse = dev_small_fraction(c, z.d.p, L * R) > 0.25;                  // the prover takes this from the resident witness
-        KTimer t(c, ms); dev_msm_rows(c, *g.dev, z.d.p, R, R, L, bl.d.p, &hb, 1, MSM_COMPRESSED, nullptr, sparse); t.stop();
+        const bool sparse = dev_small_fraction(c, z.d.p, L * R) > kSparseWitness;        // the prover takes this from the resident witness
+        KTimer t(c, ms); dev_msm_rows(c, *g.dev, {.dense = z.d.p, .n_dense = R, .rows = L, .extra_s = bl.d.p, .extra_base = &hb, .n_extra = 1, .sparse = sparse}); t.stop();
         c.sync(); memcpy(out32, c.h_points, 32 * L); return OTTI_OK;
     });
 }
@@ -303,7 +303,8 @@ int32_t otti_k_bullet_round(otti_gens *gens, size_t n_cur, int32_t fold, const u
         const uint32_t qh[2] = {g.pc_1.G[0], g.pc_n.h};
         const Fr uu = fold ? fr_load(u) : fr_zero(), ui = fold ? fr_load(uinv) : fr_zero();
         KTimer tm(c, ms);
-        auto tk = dev_bullet_round(c, *g.dev, R, n_cur, fold != 0, uu, ui, A.d.p, B.d.p, S.d.p, Ao.p, Bo.p, So.p, ex.p, qh);
+        auto tk = dev_bullet_round(c, *g.dev, {.R = R, .n_cur = n_cur, .fold = fold != 0, .u = uu, .u_inv = ui, .a_in = A.d.p, .b_in = B.d.p, .s_in = S.d.p,
+                                               .a_out = Ao.p, .b_out = Bo.p, .s_out = So.p, .extra_s = ex.p, .extra_base = qh});
         tm.stop();
         c.wait_points(tk); memcpy(LR64, c.h_points, 64);
         download(c, a_out, Ao.p, n_cur); download(c, b_out, Bo.p, n_cur); download(c, s_out, So.p, R); c.sync(); return OTTI_OK;
@@ -536,8 +537,8 @@ int32_t otti_kd_msm_rows(otti_gens *gens, const void *Z, size_t L, size_t R, con
         if (R != g.R) throw Error(OTTI_ERR_BAD_ARG, "row length differs from the generator count");
         ensure_gens_device(g); StreamScope ss(c, stream);
         uint32_t hb = g.pc_n.h;
-        dev_msm_rows(c, *g.dev, dfr(Z), R, R, L, dfr(blinds), &hb, 1, MSM_COMPRESSED, nullptr, false);
-        if (L > kHostEncodeRows) OTTI_HIP(hipMemcpyAsync(out32, c.d_points.p, 32 * L, hipMemcpyDeviceToDevice, c.stream));
+        const MsmTicket tk = dev_msm_rows(c, *g.dev, {.dense = dfr(Z), .n_dense = R, .rows = L, .extra_s = dfr(blinds), .extra_base = &hb, .n_extra = 1});
+        if (tk.points_on_device()) OTTI_HIP(hipMemcpyAsync(out32, c.d_points.p, 32 * L, hipMemcpyDeviceToDevice, c.stream));
         else { c.sync(); OTTI_HIP(hipMemcpyAsync(out32, c.h_points, 32 * L, hipMemcpyHostToDevice, c.stream)); OTTI_HIP(hipStreamSynchronize(c.stream)); }
         return OTTI_OK;
     });

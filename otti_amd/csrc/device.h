@@ -10,6 +10,7 @@
 #include <chrono>
 #include "spartan.h"
 #include "mail.h"
+#include "msm_plan.h"
 
 namespace otti {
 
@@ -80,7 +81,6 @@ static_assert(sizeof(GoBox) == 192 && offsetof(GoBox, v) == 32 && offsetof(GoBox
 constexpr int kGoCopies = 8;
 constexpr size_t kGoCopyStride = 4096;
 // ---- the small MSMs' chunk mails (mail.h MsmMail), summed on the host; OTTI_SMALL_HOST_SUM=0: the last workgroup sums them on the device instead
-constexpr size_t kMsmMailCap = 512;                          // mails per launch (rows * chunks of a fused launch)
 constexpr int kMsmMailRegions = 4;                           // launches whose mails can be waiting at once (round k read while k + 1 is queued, armed)
 struct PtFe;
 // mails [i0, i1) of m summed into acc (hostifma.h host_sum_cached) once each carries number `want` and a fitting tag; a mail that has not
@@ -148,7 +148,8 @@ struct DevCtx {
     void wait_ticket(unsigned long long ticket);              // spin until the launch with that sequence number has delivered
     DevBuf<Pt> msm_keep;                                      // row sums parked on the device (MSM_KEEP)
     DevBuf<Pt> msm_partial, msm_final;                        // [rows][chunks] partial sums, [rows] row sums
-    Pt *h_pts = nullptr; size_t pending_host_encode = 0;      // pinned: row sums of small launches, compressed on the host in sync()
+    Pt *h_pts = nullptr;                                      // pinned: row sums of small launches
+    size_t pending_host_encode = 0;                           // how many of them sync() has to compress (the launcher's and the waits' own: k_msm.hip, waits.cpp)
     uint8_t *h_points = nullptr;                              // pinned: compressed points coming back
     uint8_t *d_points_host = nullptr;                         // the device's address of h_points: the encode kernel writes there as well (no copy engine round trip)
     DevBuf<uint8_t> d_points;
@@ -159,7 +160,7 @@ struct DevCtx {
     struct Scratch *scratch = nullptr;                        // the prover's HBM workspace (prover.cpp); travels with the context
     struct SnarkScratch *snark_scratch = nullptr;             // SNARK mode's per-proof buffers (snark_prover.cpp), kept across proofs like the above
     void sync();
-    void wait_points(unsigned long long ticket);              // results of a dev_msm_rows launch: flag wait when fused, else stream sync
+    void wait_points(const MsmTicket &ticket);                // results of a dev_msm_rows / dev_bullet_round launch, by the ticket's route (msm_plan.h)
     void encode_pending();
     Pt *d_pts_alias = nullptr; DevBuf<unsigned> d_counter2;
     MsmMailbox msm_mail;
@@ -170,8 +171,6 @@ struct RowSumSlot { DevBuf<uint8_t> comp; DevBuf<Niels> pts; DevBuf<Fr> sc; DevB
 hipStream_t bulk_masked_stream();                                    // the process's CU-masked stream for chip-filling MSM launches beside latency-bound rounds (k_context.hip); nullptr if there is none
 struct ActiveProof { ActiveProof(); ~ActiveProof(); static int count(); };       // RAII around one prove call: counts the proofs in flight in this process
 constexpr int kResultSlots = 8192;                          // 256 KB pinned: round sums, sum-check tails (SNARK: up to 18 x 3 tables x 128 elements)
-constexpr size_t kHostEncodeRows = 8;
-constexpr size_t kHostPtsCap = 512;
 
 // per-kernel-class HIP-event timing on the library's own stream (bench.py's roofline numbers come from here)
 enum KClass { KC_MSM_ROWS = 0, KC_MSM_SMALL, KC_MSM_FINISH, KC_SC_CUBIC, KC_SC_QUAD, KC_SPMV, KC_EQ, KC_REDUCE, KC_BOUND, KC_BULLET, KC_OTHER,
@@ -295,21 +294,28 @@ unsigned long long dev_sc_quad_fold_eval(DevCtx &c, Fr *A, Fr *B, size_t len, co
 void dev_fold_top(DevCtx &c, Fr *Z, size_t len, const Fr &r);
 void dev_fold_bot(DevCtx &c, const Fr *Z, Fr *out, size_t len, const Fr &r);
 void dev_fetch(DevCtx &c, const Fr *src, int slot, size_t n);              // async copy of n elements into h_results[slot..]
-// ---- K8: fixed-base MSM rows.  Row i: sum_j dense[i*stride + j] * P[j] (j < n_dense) + sum_e extra_s[i*n_extra+e] * P[extra_base[e]]
-// Compressed results land in c.h_points[32*i ..] after c.sync(); they also stay in c.d_points.
-enum { MSM_COMPRESSED = 0, MSM_RAW = 1, MSM_KEEP = 2 };
-// returns a ticket: c.wait_points(ticket) returns once the compressed points are in c.h_points (ticket 0 = plain stream sync)
-unsigned long long dev_msm_rows(DevCtx &c, const DeviceGens &g, const Fr *dense, size_t stride, size_t n_dense, size_t rows, const Fr *extra_s,
-                                const uint32_t *extra_base_host, size_t n_extra, int mode = MSM_COMPRESSED, const Pt *addend = nullptr,
-                                bool sparse_hint = false, Pt *keep_dst = nullptr, size_t keep_row0 = 0, bool force_bulk = false);
-// sparse_hint: the dense scalars are mostly small numbers (DeviceWitness::small_fraction) — bulk launches then compact the non-zero
-// (term, window) pairs into a work list instead of giving every pair a lane.  Results are identical either way.
+// ---- K8: fixed-base MSM rows.  Row i: sum_j dense[i*n_dense + j] * P[j] (j < n_dense) + sum_e extra_s[i*n_extra+e] * P[extra_base[e]]
+// Compressed results land in c.h_points[32*i ..] after c.sync(); those of more than kHostEncodeRows rows, or with an addend, also stay in c.d_points.
+// What to sum, filled with designated initialisers at the call site.  The row stride of `dense` is n_dense.
+struct MsmJob {
+    const Fr *dense = nullptr; size_t n_dense = 0, rows = 0;
+    const Fr *extra_s = nullptr; const uint32_t *extra_base = nullptr /* host */; size_t n_extra = 0;
+    int mode = MSM_COMPRESSED;                                // msm_plan.h
+    const Pt *addend = nullptr;
+    // sparse: the dense scalars are mostly small numbers (more than kSparseWitness of them, DeviceWitness::small_fraction) — bulk launches then
+    // compact the non-zero (term, window) pairs into a work list instead of giving every pair a lane.  Results are identical either way.
+    bool sparse = false;
+    Pt *keep_dst = nullptr; bool force_bulk = false;
+};
+constexpr double kSparseWitness = 0.25;                      // above this share of small scalars a commitment uses the work-list MSM variant
+// returns a ticket: c.wait_points(ticket) returns once the compressed points are in c.h_points
+MsmTicket dev_msm_rows(DevCtx &c, const DeviceGens &g, const MsmJob &job);
 double dev_small_fraction(DevCtx &c, const Fr *z, size_t n);               // share of scalars below 2^128 (synchronises the stream)
 // MSM_RAW: skip compression; after c.sync() the extended row sums are in c.h_pts[0..rows).
 // MSM_KEEP: no output; the row sums stay on the device in c.msm_keep (to be passed as `addend` of a later launch, which then
 // compresses (row sum + addend)).  Lets the host draw the blinds while the device already sums the witness terms.
-// keep_dst (MSM_KEEP only): row i's sum goes to keep_dst[keep_row0 + i] instead, c.msm_keep is left alone (DeviceWitness::rows_kept: `dense`
-// then points at the first of the rows to sum).  force_bulk: the chip-filling kernel whatever the size (a run of re-summed rows).
+// keep_dst (MSM_KEEP only): row i's sum goes to keep_dst[i] instead, c.msm_keep is left alone (DeviceWitness::rows_kept: the caller offsets it
+// to the first of the rows to sum, as it does `dense`).  force_bulk: the chip-filling kernel whatever the size (a run of re-summed rows).
 // ---- K9: LZ[j] = sum_i Lv[i] * Z[i*R + j]
 void dev_poly_bound(DevCtx &c, const Fr *Z, size_t L, size_t R, const Fr *Lv, Fr *out, Fr *scratch /* >= 64*R */);
 // chunk sums of the same bound over eq(rest) alone (k_sumcheck.hip): out = (L / m) x R; false (nothing launched) when the geometry does not allow it
@@ -325,9 +331,12 @@ void dev_bullet_finish(DevCtx &c, Fr *a, Fr *b, Fr *s, size_t R, const Fr &u, co
 // and sums both rows (fused finish; compressed L, R arrive in c.h_points[0..64) after c.wait_points(ticket)).  extra_s: 4 scalars
 // {unused, blind_L, unused, blind_R} (the c_L / c_R terms are computed in the kernel); extra_base: {Q, H}.
 // armed (device.h): u and u_inv are not known yet; the launch takes {u, u_inv, raw(u), raw(u_inv)} from the next c.go()
-unsigned long long dev_bullet_round(DevCtx &c, const DeviceGens &g, size_t R, size_t n_cur, bool fold, const Fr &u, const Fr &u_inv, const Fr *a_in,
-                                    const Fr *b_in, const Fr *s_in, Fr *a_out, Fr *b_out, Fr *s_out, const Fr *extra_s, const uint32_t *extra_base,
-                                    bool armed = false);
+struct BulletRound {
+    size_t R, n_cur; bool fold; Fr u, u_inv;
+    const Fr *a_in, *b_in, *s_in; Fr *a_out, *b_out, *s_out;
+    const Fr *extra_s; const uint32_t *extra_base; bool armed = false;
+};
+MsmTicket dev_bullet_round(DevCtx &c, const DeviceGens &g, const BulletRound &round);
 // ---- verifier: decompression of n ristretto255 points into affine Niels form (bad: count of encodings that do not decode), and the
 // variable-base MSM over them: out[w * splits + s] = sum over the points of split s of digit_w(scalar) * point — window sums the host
 // combines (253 doublings: a sequential chain a host core runs 30 x faster than a GPU lane).  Returns the window width c it used.

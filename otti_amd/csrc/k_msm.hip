@@ -189,8 +189,7 @@ template <int kKind> __global__ __launch_bounds__(kBlock) void k_msm_rows(MsmArg
 //   * a bullet round's c_L / c_R is not computed by one workgroup ahead of its MSM: every workgroup takes a slice of the dot product
 //     and adds (its slice) * Q as one more term — the sum over workgroups is c_L * Q; the folded state (a, b, s) for the next
 //     round is written after the workgroup has handed its point over, off the path to the host.
-constexpr int kSmallChunk = 64;                // terms per workgroup at most (LDS: 36 B each)
-constexpr int kSmallQuads = kBlock / 4;
+static_assert(kBlock == kMsmThreads, "the launch plan (msm_plan.h: kSmallChunk, kSmallQuads) counts the MSM kernels' own threads");
 // the folded a in RAW (non-Montgomery) form: a Montgomery product with one raw operand is raw, so the scalars of L / R and the slices of
 // c_L / c_R come out ready for recoding without a conversion multiplication on the path to the first addition
 __device__ __forceinline__ Fr bullet_fold_a_raw(const BulletArgs &U, size_t x) {
@@ -406,16 +405,6 @@ __global__ __launch_bounds__(64) void k_encode_points(const Pt *pts, const Pt *a
     for (int k = 0; k < 8; k++) o[k] = w[k];
     if (host32) { uint32_t *h = (uint32_t *)(host32 + 32 * i); for (int k = 0; k < 8; k++) h[k] = w[k]; }
 }
-static unsigned long long msm_launch(DevCtx &c, const DeviceGens &g, const Fr *dense, size_t stride, size_t n_dense, size_t rows, const Fr *extra_s,
-                                     const uint32_t *extra_base, size_t n_extra, int mode, const Pt *addend, const BulletArgs *bul, bool sparse_hint,
-                                     Pt *keep_dst = nullptr, bool force_bulk = false);
-unsigned long long dev_msm_rows(DevCtx &c, const DeviceGens &g, const Fr *dense, size_t stride, size_t n_dense, size_t rows, const Fr *extra_s,
-                                const uint32_t *extra_base, size_t n_extra, int mode, const Pt *addend, bool sparse_hint, Pt *keep_dst, size_t keep_row0,
-                                bool force_bulk) {
-    if (keep_dst && mode != MSM_KEEP) throw Error(OTTI_ERR_INTERNAL, "msm: a destination for kept row sums needs MSM_KEEP");
-    return msm_launch(c, g, dense, stride, n_dense, rows, extra_s, extra_base, n_extra, mode, addend, nullptr, sparse_hint,
-                      keep_dst ? keep_dst + keep_row0 : nullptr, force_bulk);
-}
 // share of the n scalars whose canonical value is below 2^128 (what a compiled circuit's witness is mostly made of)
 __global__ __launch_bounds__(kBlock) void k_count_small(const Fr *z, size_t n, unsigned long long *count) {
     unsigned mine = 0;
@@ -435,60 +424,44 @@ double dev_small_fraction(DevCtx &c, const Fr *z, size_t n) {
     OTTI_HIP(hipStreamSynchronize(c.stream));
     return (double)h / (double)n;
 }
-unsigned long long dev_bullet_round(DevCtx &c, const DeviceGens &g, size_t R, size_t n_cur, bool fold, const Fr &u, const Fr &u_inv, const Fr *a_in,
-                                    const Fr *b_in, const Fr *s_in, Fr *a_out, Fr *b_out, Fr *s_out, const Fr *extra_s, const uint32_t *extra_base, bool armed) {
-    BulletArgs U; U.on = armed ? 2 : 1; U.fold = fold ? 1 : 0; U.n = (uint32_t)n_cur; U.a_in = a_in; U.b_in = b_in; U.s_in = s_in;
-    U.a_out = a_out; U.b_out = b_out; U.s_out = s_out; U.u = u; U.uinv = u_inv; U.u_raw = fr_to_raw(u); U.uinv_raw = fr_to_raw(u_inv);
-    return msm_launch(c, g, nullptr, 0, R / 2, 2, extra_s, extra_base, 2, MSM_COMPRESSED, nullptr, &U, false);   // R/2 active terms per row
+// OTTI_MSM_STAMPS=1: phase stamps of every fused small launch on stderr (development aid; synchronises the stream)
+static void msm_report_stamps(DevCtx &c, const unsigned long long *t, const MsmJob &j, const MsmPlan &p, bool bullet) {
+    OTTI_HIP(hipStreamSynchronize(c.stream));
+    auto us = [&](int a, int b) { return t[b] >= t[a] ? (double)(t[b] - t[a]) * 0.01 : -1.0; };
+    const size_t rows = j.rows, terms = j.n_dense + j.n_extra, nchunks = p.nchunks;
+    if (p.route == MsmRoute::mail) {
+        const auto h0 = std::chrono::steady_clock::now();
+        c.msm_host_sum(c.msm_mail.pending[c.msm_mail.pending_n - 1]);
+        const double host_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - h0).count();
+        fprintf(stderr, "[otti] k_msm_small rows=%zu terms=%zu chunks=%zu bullet=%d host-sum: scalars %.2f | pairs %.2f | tree + mail %.2f | total %.2f us on the device; "
+                        "host sum of %zu mails (all in) %.2f us\n",
+                rows, terms, nchunks, bullet ? 1 : 0, us(0, 1), us(1, 2), us(2, 3), us(0, 3), rows * nchunks, host_us);
+    } else
+        fprintf(stderr, "[otti] k_msm_small rows=%zu terms=%zu chunks=%zu bullet=%d: scalars %.2f | pairs %.2f | tree %.2f | (others arrive) %.2f | chunk sums %.2f | row tree %.2f | mail %.2f | total %.2f us\n",
+                rows, terms, nchunks, bullet ? 1 : 0, us(0, 1), us(1, 2), us(2, 3), us(3, 4), us(4, 5), us(5, 6), us(6, 7), us(0, 7));
 }
-static unsigned long long msm_launch(DevCtx &c, const DeviceGens &g, const Fr *dense, size_t stride, size_t n_dense, size_t rows, const Fr *extra_s,
-                                     const uint32_t *extra_base, size_t n_extra, int mode, const Pt *addend, const BulletArgs *bul, bool sparse_hint,
-                                     Pt *keep_dst, bool force_bulk) {
-    const bool raw_points = mode == MSM_RAW;
-    if (n_extra > 8) throw Error(OTTI_ERR_INTERNAL, "msm: too many extra terms");
-    if (!rows) return 0;
+// One launch in four steps: plan it (msm_plan.h), fill the kernel's arguments from the plan and the job, launch, hand the row sums on by route.
+static MsmTicket msm_launch(DevCtx &c, const DeviceGens &g, const MsmJob &j, const BulletArgs *bul) {
+    if (j.n_extra > 8) throw Error(OTTI_ERR_INTERNAL, "msm: too many extra terms");
+    const size_t rows = j.rows;
+    if (!rows) return {};
+    const MsmPlan p = msm_plan({g.c, g.W, rows, j.n_dense, j.n_extra, bul != nullptr, j.mode, j.addend != nullptr, j.sparse, j.force_bulk, c.msm_mail.host_sum(c)});
+    const size_t nchunks = p.nchunks;
+    if (p.route == MsmRoute::raw && rows > kHostPtsCap) throw Error(OTTI_ERR_INTERNAL, "msm: too many raw rows");
     MsmArgs A;
     A.table = g.table.p; A.c = g.c; A.W = g.W; A.E = (uint32_t)g.E; A.lanes = kBlock / g.W;
-    A.dense = dense; A.stride = stride; A.n_dense = n_dense; A.extra_s = extra_s; A.n_extra = (int)n_extra;
-    for (int i = 0; i < 8; i++) A.extra_base[i] = i < (int)n_extra ? extra_base[i] : 0;
-    const bool bulk = (rows * n_dense >= ((size_t)1 << 16) || (force_bulk && n_dense)) && !bul;
-    const bool sparse = bulk && sparse_hint && g.W <= 32;
-    size_t nchunks;
-    if (bulk) {
-        // aim for >= 1024 workgroups (4 per CU) but keep at least one term per term lane and at most kMsmMaxChunk per workgroup;
-        // the sparse variant keeps a (term, window) work list in LDS: (chunk + extras) * W <= kMsmListCap;  W <= 32 there (5-bit window field)
-        nchunks = std::max<size_t>(1, (1024 + rows - 1) / rows);
-        nchunks = std::min(nchunks, std::max<size_t>(1, n_dense / (size_t)A.lanes));
-        const size_t max_chunk = 4096;                        // both bulk kernels walk their chunk in sub-chunks that fit the LDS
-        nchunks = std::max(nchunks, (n_dense + max_chunk - 1) / max_chunk);
-    } else {
-        // latency-bound launches: about two (term, window) pairs per quad (one or two rows) or four (many rows), at most 2048 workgroups
-        // and, when the last workgroup sums the chunk results itself (rows <= 2), at most 256 of them per row
-        // (whole steps: a workgroup's pairs, extras included, should fill its 64 quads k times — the bullet rounds carry one extra
-        // term per workgroup, the slice of c_L / c_R, and two in chunk 0)
-        const size_t steps = rows <= 2 ? 3 : 4, per_wg = steps * (size_t)kSmallQuads / (size_t)g.W, ex_wg = bul ? 2 : n_extra;
-        const size_t terms_wg = per_wg > ex_wg ? per_wg - ex_wg : 1;
-        nchunks = std::max<size_t>(1, (n_dense + terms_wg - 1) / terms_wg);
-        nchunks = std::min(nchunks, rows <= 2 ? (size_t)256 : std::max<size_t>(1, 2048 / rows));
-        nchunks = std::min(nchunks, std::max<size_t>(1, n_dense));
-        nchunks = std::max(nchunks, (n_dense + kSmallChunk - 1) / (size_t)kSmallChunk);
-    }
-    if (!n_dense) nchunks = 1;
-    size_t chunk = n_dense ? (n_dense + nchunks - 1) / nchunks : 1;
-    nchunks = n_dense ? (n_dense + chunk - 1) / chunk : 1;
-    A.chunk = (uint32_t)chunk; A.nchunks = (uint32_t)nchunks;
-    for (int i = 0; i < 9; i++) A.K[i] = 0;
-    for (int w = 0; w < g.W; w++) { int bit = g.c - 1 + g.c * w; A.K[bit >> 5] |= 1u << (bit & 31); }
+    A.dense = j.dense; A.stride = j.n_dense; A.n_dense = j.n_dense; A.extra_s = j.extra_s; A.n_extra = (int)j.n_extra;
+    for (int i = 0; i < 8; i++) A.extra_base[i] = i < (int)j.n_extra ? j.extra_base[i] : 0;
+    A.chunk = (uint32_t)p.chunk; A.nchunks = (uint32_t)nchunks;
+    for (int i = 0; i < 9; i++) A.K[i] = p.K[i];
     c.ensure_points(rows, nchunks);
     A.partial = c.msm_partial.p;
-    A.fuse = (!bulk && mode == MSM_COMPRESSED && !addend && rows <= 2 && rows * nchunks <= kMsmMailCap) ? 1 : 0;
-    if (A.fuse && c.msm_mail.host_sum(c)) { A.fuse = 2; c.msm_mail.ensure(c); }
+    A.fuse = p.fuse;
+    if (p.route == MsmRoute::mail) c.msm_mail.ensure(c);
     if (bul) A.bul = *bul; else { memset(&A.bul, 0, sizeof A.bul); }
     A.go = Armed{nullptr, nullptr, 0};
     A.rows = (uint32_t)rows; A.counter = c.d_counter2.p; A.host_pts = c.d_pts_alias; A.host_flag = c.d_flag_alias; A.seq = A.fuse ? ++c.seq : 0;
     A.mail = A.fuse == 2 ? c.msm_mail.dev + (size_t)(c.msm_mail.launches % kMsmMailRegions) * kMsmMailCap : nullptr;
-    dim3 grid((unsigned)nchunks, (unsigned)rows);
-    // OTTI_MSM_STAMPS=1: phase stamps of every fused small launch on stderr (development aid; synchronises the stream)
     static const bool want_stamps = getenv("OTTI_MSM_STAMPS") != nullptr;
     static thread_local unsigned long long *h_stamps = nullptr, *d_stamps = nullptr;
     A.stamps = nullptr;
@@ -498,31 +471,19 @@ static unsigned long long msm_launch(DevCtx &c, const DeviceGens &g, const Fr *d
     }
     if (bul && bul->on == 2) { A.bul.on = 1; if (!A.stamps) A.go = c.arm(); else throw Error(OTTI_ERR_INTERNAL, "armed launches cannot be stamped"); }
     {
-        KScope ks(c, bulk ? KC_MSM_ROWS : KC_MSM_SMALL);
-        if (sparse) hipLaunchKernelGGL(k_msm_rows<MSM_BULK_SPARSE>, grid, kBlock, 0, c.stream, A);
-        else if (bulk) hipLaunchKernelGGL(k_msm_rows<MSM_BULK>, grid, kBlock, 0, c.stream, A);
+        const dim3 grid((unsigned)nchunks, (unsigned)rows);
+        KScope ks(c, p.kernel == MsmKernel::small ? KC_MSM_SMALL : KC_MSM_ROWS);
+        if (p.kernel == MsmKernel::bulk_sparse) hipLaunchKernelGGL(k_msm_rows<MSM_BULK_SPARSE>, grid, kBlock, 0, c.stream, A);
+        else if (p.kernel == MsmKernel::bulk) hipLaunchKernelGGL(k_msm_rows<MSM_BULK>, grid, kBlock, 0, c.stream, A);
         else hipLaunchKernelGGL(k_msm_small, grid, kBlock, 0, c.stream, A);
     }
-    if (A.fuse == 2) c.msm_mail.queue(A.seq, (uint32_t)rows, (uint32_t)nchunks);      // the host sums the mails in wait_points(seq) / sync()
-    if (A.stamps && A.fuse == 2) {
-        OTTI_HIP(hipStreamSynchronize(c.stream));
-        const unsigned long long *t = h_stamps;
-        auto us = [&](int a, int b) { return t[b] >= t[a] ? (double)(t[b] - t[a]) * 0.01 : -1.0; };
-        const auto h0 = std::chrono::steady_clock::now();
-        c.msm_host_sum(c.msm_mail.pending[c.msm_mail.pending_n - 1]);
-        const double host_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - h0).count();
-        fprintf(stderr, "[otti] k_msm_small rows=%zu terms=%zu chunks=%zu bullet=%d host-sum: scalars %.2f | pairs %.2f | tree + mail %.2f | total %.2f us on the device; "
-                        "host sum of %zu mails (all in) %.2f us\n",
-                rows, n_dense + n_extra, nchunks, bul ? 1 : 0, us(0, 1), us(1, 2), us(2, 3), us(0, 3), rows * nchunks, host_us);
-    } else if (A.stamps) {
-        OTTI_HIP(hipStreamSynchronize(c.stream));
-        const unsigned long long *t = h_stamps;
-        auto us = [&](int a, int b) { return t[b] >= t[a] ? (double)(t[b] - t[a]) * 0.01 : -1.0; };
-        fprintf(stderr, "[otti] k_msm_small rows=%zu terms=%zu chunks=%zu bullet=%d: scalars %.2f | pairs %.2f | tree %.2f | (others arrive) %.2f | chunk sums %.2f | row tree %.2f | mail %.2f | total %.2f us\n",
-                rows, n_dense + n_extra, nchunks, bul ? 1 : 0, us(0, 1), us(1, 2), us(2, 3), us(3, 4), us(4, 5), us(5, 6), us(6, 7), us(0, 7));
-    }
-    if (A.fuse) { c.pending_host_encode = rows; return A.seq; }
-    c.msm_mail.h_pts_order = ++c.msm_mail.order;                          // every branch below replaces what a mailing launch before it left for sync()
+    const MsmTicket ticket{A.seq, (uint32_t)rows, p.route};
+    if (p.route == MsmRoute::mail) c.msm_mail.queue(A.seq, (uint32_t)rows, (uint32_t)nchunks);      // the host sums the mails in wait_points(ticket) / sync()
+    if (A.stamps) msm_report_stamps(c, h_stamps, j, p, bul != nullptr);
+    // what sync() finds to compress in h_pts once the stream is idle, if this launch is still the latest then
+    c.pending_host_encode = p.route == MsmRoute::mail || p.route == MsmRoute::flag || p.route == MsmRoute::host_encode ? rows : 0;
+    if (ticket.delivers_without_sync()) return ticket;
+    c.msm_mail.h_pts_order = ++c.msm_mail.order;                          // every route below replaces what a mailing launch before it left for sync()
     // rows with a single chunk need no finish pass: their partial IS the row sum
     const Pt *finals = c.msm_partial.p;
     if (nchunks > 1) {
@@ -530,26 +491,24 @@ static unsigned long long msm_launch(DevCtx &c, const DeviceGens &g, const Fr *d
         hipLaunchKernelGGL(k_msm_finish, (unsigned)rows, 64, 0, c.stream, (const Pt *)c.msm_partial.p, (uint32_t)nchunks, rows, c.msm_final.p);
         finals = c.msm_final.p;
     }
-    if (mode == MSM_KEEP) {
-        // (a launch that is not MSM_COMPRESSED never fuses or mails: whichever kernel ran, the row sums are at `finals` here)
-        if (!keep_dst && c.msm_keep.n < rows) c.msm_keep.alloc(rows);
-        OTTI_HIP(hipMemcpyAsync(keep_dst ? keep_dst : c.msm_keep.p, finals, rows * sizeof(Pt), hipMemcpyDeviceToDevice, c.stream));
-        c.pending_host_encode = 0;
-    } else if (raw_points) {
-        if (rows > kHostPtsCap) throw Error(OTTI_ERR_INTERNAL, "msm: too many raw rows");
-        OTTI_HIP(hipMemcpyAsync(c.h_pts, finals, rows * sizeof(Pt), hipMemcpyDeviceToHost, c.stream));
-        c.pending_host_encode = 0;
-    } else if (rows > kHostEncodeRows || addend) {
+    if (p.route == MsmRoute::keep) {
+        if (!j.keep_dst && c.msm_keep.n < rows) c.msm_keep.alloc(rows);
+        OTTI_HIP(hipMemcpyAsync(j.keep_dst ? j.keep_dst : c.msm_keep.p, finals, rows * sizeof(Pt), hipMemcpyDeviceToDevice, c.stream));
+    } else if (p.route == MsmRoute::device_encode) {
         KScope ks(c, KC_MSM_FINISH);
-        hipLaunchKernelGGL(k_encode_points, (unsigned)((rows + 63) / 64), 64, 0, c.stream, finals, addend, rows, c.d_points.p, c.d_points_host);
+        hipLaunchKernelGGL(k_encode_points, (unsigned)((rows + 63) / 64), 64, 0, c.stream, finals, j.addend, rows, c.d_points.p, c.d_points_host);
         if (!c.d_points_host) OTTI_HIP(hipMemcpyAsync(c.h_points, c.d_points.p, rows * 32, hipMemcpyDeviceToHost, c.stream));
-        c.pending_host_encode = 0;
-    } else {
-        // a handful of points: the dependent inverse-square-root chain runs ~30x faster on a host core than on one GPU lane
-        OTTI_HIP(hipMemcpyAsync(c.h_pts, finals, rows * sizeof(Pt), hipMemcpyDeviceToHost, c.stream));
-        c.pending_host_encode = rows;
-    }
-    return 0;
+    } else OTTI_HIP(hipMemcpyAsync(c.h_pts, finals, rows * sizeof(Pt), hipMemcpyDeviceToHost, c.stream));      // raw, host_encode
+    return ticket;
+}
+MsmTicket dev_msm_rows(DevCtx &c, const DeviceGens &g, const MsmJob &job) {
+    if (job.keep_dst && job.mode != MSM_KEEP) throw Error(OTTI_ERR_INTERNAL, "msm: a destination for kept row sums needs MSM_KEEP");
+    return msm_launch(c, g, job, nullptr);
+}
+MsmTicket dev_bullet_round(DevCtx &c, const DeviceGens &g, const BulletRound &r) {
+    BulletArgs U; U.on = r.armed ? 2 : 1; U.fold = r.fold ? 1 : 0; U.n = (uint32_t)r.n_cur; U.a_in = r.a_in; U.b_in = r.b_in; U.s_in = r.s_in;
+    U.a_out = r.a_out; U.b_out = r.b_out; U.s_out = r.s_out; U.u = r.u; U.uinv = r.u_inv; U.u_raw = fr_to_raw(r.u); U.uinv_raw = fr_to_raw(r.u_inv);
+    return msm_launch(c, g, {.n_dense = r.R / 2, .rows = 2, .extra_s = r.extra_s, .extra_base = r.extra_base, .n_extra = 2}, &U);   // R/2 active terms per row
 }
 // table build.  Row (base b, window w) holds d * B for d = 1..E with B = 2^(cw) * P[b].  Rows are cut into blocks of T entries:
 // k_table_starts (one thread per row) walks the block starts (kT+1) * B; k_table_fill (one thread per block) fills its T extended
@@ -697,8 +656,7 @@ int dev_msm_var(DevCtx &c, const Niels *pts, const Fr *scalars, size_t n, Pt *ou
     A.c = std::max(5, std::min(9, lg - 2));                    // ~8 points per bucket: 2^(c-1) buckets for `chunk` points
     A.W = 253 / A.c + 1; A.splits = (int)splits; A.pts = pts; A.sc = scalars; A.n = (uint32_t)n; A.chunk = (uint32_t)chunk; A.out = out;
     if ((size_t)A.W * splits > out_cap) throw Error(OTTI_ERR_INTERNAL, "msm_var: result buffer too small");
-    for (int i = 0; i < 9; i++) A.K[i] = 0;
-    for (int w = 0; w < A.W; w++) { int bit = A.c - 1 + A.c * w; A.K[bit >> 5] |= 1u << (bit & 31); }
+    msm_recoding_constant(A.K, A.c, A.W);
     KScope ks(c, KC_MSM_VAR);
     hipLaunchKernelGGL(k_msm_var, dim3((unsigned)A.W, (unsigned)splits), kBlock, 0, c.stream, A);
     if (n_windows) *n_windows = A.W;

@@ -17,7 +17,6 @@ namespace otti {
 
 constexpr size_t kHostTailBits = 5;           // sum-check tables of at most 2^5 elements (all ranks together) are finished on the host
 constexpr int kTailSlot = 64;                 // where their elements land in the pinned result buffer
-constexpr double kSparseWitness = 0.25;       // above this share of small witness values the commitment uses the work-list MSM variant
 
 static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
@@ -70,10 +69,8 @@ static bool fixed_base_msm_on_device(const Gens &g, const Fr *s, size_t n, Pt &o
         DevBuf<Fr> d(n);
         OTTI_HIP(hipMemcpyAsync(d.p, s, n * sizeof(Fr), hipMemcpyHostToDevice, c.stream));
         c.ensure_points(1, std::max<size_t>(1, n / 64));
-        const unsigned long long tk = dev_msm_rows(c, *g.dev, d.p, n, n, 1, nullptr, nullptr, 0, MSM_RAW);
-        if (tk) c.wait_ticket(tk);                               // fused launch: the extended row sum is mailed to pinned memory
-        OTTI_HIP(hipStreamSynchronize(c.stream));
-        c.pending_host_encode = 0;                               // the sum is wanted as a point, not compressed
+        dev_msm_rows(c, *g.dev, {.dense = d.p, .n_dense = n, .rows = 1, .mode = MSM_RAW});
+        OTTI_HIP(hipStreamSynchronize(c.stream));               // an MSM_RAW launch never fuses: the extended row sum is copied to h_pts behind the kernel
         out = c.h_pts[0];
         return true;
     } catch (const Error &) { return false; }
@@ -229,7 +226,8 @@ static void sum_rows_into(DevCtx &c, DeviceWitness &w, Gens &g, size_t r0, size_
     const DeviceGens &DG = *g.dev;
     const size_t R = w.rows_R, n = r1 - r0 + 1;
     // the whole vector goes the way the proof's MSM_KEEP launch goes (same size rule); a run of dirty rows is bulk from three rows on
-    dev_msm_rows(c, DG, w.z.p + r0 * R, R, R, n, nullptr, nullptr, 0, MSM_KEEP, nullptr, w.small_fraction > kSparseWitness, w.rows_kept.p, r0, !whole && n > 2);
+    dev_msm_rows(c, DG, {.dense = w.z.p + r0 * R, .n_dense = R, .rows = n, .mode = MSM_KEEP, .sparse = w.small_fraction > kSparseWitness,
+                         .keep_dst = w.rows_kept.p + r0, .force_bulk = !whole && n > 2});
     OTTI_HIP(hipStreamSynchronize(c.stream));
 }
 static void resum_rows(DevCtx &c, DeviceWitness &w, size_t r0, size_t r1) {
@@ -279,7 +277,7 @@ RoundPointsJob precompute_round_points_launch(DevCtx &c, const DeviceGens &DG, c
             r3[cs[k].h1] = st[k]->pre[j].r_beta;
         }
     OTTI_HIP(hipMemcpyAsync(scratch.p, sc.data(), sc.size() * sizeof(Fr), hipMemcpyHostToDevice, c.stream));
-    dev_msm_rows(c, DG, nullptr, 0, 0, 4 * n, scratch.p, bases.data(), nb, MSM_RAW);
+    dev_msm_rows(c, DG, {.rows = 4 * n, .extra_s = scratch.p, .extra_base = bases.data(), .n_extra = nb, .mode = MSM_RAW});
     OTTI_HIP(hipEventRecord(c.ev1, c.stream));
     job.scalars = std::move(sc);                                      // must outlive the copy queued above
     return job;
@@ -361,13 +359,11 @@ DotProductProofLog dplog_prove_device(DevCtx &c, const DeviceGens &DG, const Gen
     tr.append_protocol_name("dot product proof (log)");
     Fr d = tape.random_scalar("d"), r_delta = tape.random_scalar("r_delta"), r_beta = tape.random_scalar("r_delta");   // sic: upstream reuses the label
     std::vector<Fr> bv1 = tape.random_vector("blinds_vec_1", 2 * lgR), bv2 = tape.random_vector("blinds_vec_2", 2 * lgR);
-    unsigned long long tk_cx = 0;
     {   // Cx = commit(LZ, LZ_blind) over gens_n
         OTTI_HIP(hipMemcpyAsync(B.extras, &LZ_blind, sizeof(Fr), hipMemcpyHostToDevice, c.stream));
         uint32_t hb = v.h_n;
-        tk_cx = dev_msm_rows(c, DG, B.LZ, Rsz, Rsz, 1, B.extras, &hb, 1);
+        c.wait_points(dev_msm_rows(c, DG, {.dense = B.LZ, .n_dense = Rsz, .rows = 1, .extra_s = B.extras, .extra_base = &hb, .n_extra = 1}));
     }
-    c.wait_points(tk_cx);
     const Fr y = y_known ? *y_known : c.h_results[12];
     CPoint Cx = point_at(c, 0);
     tr.append_point("Cx", Cx.b);
@@ -389,17 +385,17 @@ DotProductProofLog dplog_prove_device(DevCtx &c, const DeviceGens &DG, const Gen
     const size_t n_rounds = lgR;
     const bool arm_ok = c.armed_ok() && !getenv("OTTI_MSM_STAMPS");
     struct Release { DevCtx &c; ~Release() { c.go_abort(); } } release{c};
-    std::vector<unsigned long long> tks(n_rounds + 1, 0);
+    std::vector<MsmTicket> tks(n_rounds + 1);
     auto launch_round = [&](size_t k, bool armed) {
         const int in = (int)(k & 1), out = in ^ 1;
-        tks[k] = dev_bullet_round(c, DG, Rsz, Rsz >> k, k != 0, u, ui, abuf[in], bbuf[in], sbuf[in], abuf[out], bbuf[out], sbuf[out], B.extras + 4 * k, qh, armed);
+        tks[k] = dev_bullet_round(c, DG, {.R = Rsz, .n_cur = Rsz >> k, .fold = k != 0, .u = u, .u_inv = ui, .a_in = abuf[in], .b_in = bbuf[in], .s_in = sbuf[in],
+                                          .a_out = abuf[out], .b_out = bbuf[out], .s_out = sbuf[out], .extra_s = B.extras + 4 * k, .extra_base = qh, .armed = armed});
     };
     if (n_rounds) launch_round(0, false);
-    const bool arm = arm_ok && n_rounds > 1 && tks[0] != 0;      // only fused launches (results by mailbox, no stream synchronise behind which an armed kernel would wait for the host)
+    const bool arm = arm_ok && n_rounds > 1 && tks[0].delivers_without_sync();      // only fused launches (results by mailbox, no stream synchronise behind which an armed kernel would wait for the host)
     if (arm) launch_round(1, true);
     size_t round = 0;
     for (; round < n_rounds; round++) {
-        if (arm) c.pending_host_encode = 2;                      // the launch queued ahead has already re-armed the counter once; this round's L and R are still to be compressed
         c.wait_points(tks[round]);
         CPoint Lp = point_at(c, 0), Rp = point_at(c, 1);
         tr.append_point("L", Lp.b); tr.append_point("R", Rp.b);
@@ -416,9 +412,7 @@ DotProductProofLog dplog_prove_device(DevCtx &c, const DeviceGens &DG, const Gen
     // delta = d * g_hat + r_delta * h with g_hat = sum_j s[j] P[j]: the last fold, the folded a and b for the host (slots 13, 14) and d s in one launch
     if (round) dev_bullet_finish(c, afin, bvec, sfin, Rsz, u, ui, d, B.rows, 13);
     else { dev_fetch(c, afin, 13, 1); dev_fetch(c, bvec, 14, 1); dev_scale(c, sfin, d, B.rows, Rsz); }
-    unsigned long long tk_delta;
-    { uint32_t hb = v.h1; tk_delta = dev_msm_rows(c, DG, B.rows, Rsz, Rsz, 1, B.extras + 4 * lgR, &hb, 1); }
-    c.wait_points(tk_delta);
+    { uint32_t hb = v.h1; c.wait_points(dev_msm_rows(c, DG, {.dense = B.rows, .n_dense = Rsz, .rows = 1, .extra_s = B.extras + 4 * lgR, .extra_base = &hb, .n_extra = 1})); }
     const Fr x_hat = c.h_results[13], a_hat = c.h_results[14];
     pf.delta = point_at(c, 0);
     tr.append_point("delta", pf.delta.b);
@@ -505,14 +499,15 @@ void r1cs_prove_device(Instance &I, DeviceWitness &wit, Gens &g, Transcript &tr,
         // figure down was the helper threads' spinning, pool.h — so the mask is opt-in: OTTI_INFLIGHT_MASK=1)
         static const bool mask_env = [] { const char *e = getenv("OTTI_INFLIGHT_MASK"); return e && e[0] == '1'; }();
         hipStream_t bulk = (mask_env && !sh && ActiveProof::count() > 1) ? bulk_masked_stream() : nullptr;
+        const MsmJob witness_rows{.dense = my_rows, .n_dense = Rsz, .rows = Ll, .mode = MSM_KEEP, .sparse = wit.small_fraction > kSparseWitness};
         if (bulk) {
             hipStream_t own = c.stream;
             OTTI_HIP(hipEventRecord(c.ev1, own)); OTTI_HIP(hipStreamWaitEvent(bulk, c.ev1, 0));
             c.stream = bulk;
             struct Restore { DevCtx &c; hipStream_t s; ~Restore() { c.stream = s; } } restore{c, own};
-            dev_msm_rows(c, DG, my_rows, Rsz, Rsz, Ll, nullptr, nullptr, 0, MSM_KEEP, nullptr, wit.small_fraction > kSparseWitness);
+            dev_msm_rows(c, DG, witness_rows);
             OTTI_HIP(hipEventRecord(c.ev1, bulk)); OTTI_HIP(hipStreamWaitEvent(own, c.ev1, 0));
-        } else dev_msm_rows(c, DG, my_rows, Rsz, Rsz, Ll, nullptr, nullptr, 0, MSM_KEEP, nullptr, wit.small_fraction > kSparseWitness);
+        } else dev_msm_rows(c, DG, witness_rows);
     }
     size_t off_sc1 = 0, off_sc2 = 0;                                  // where the two sum-checks' draws sit in the prefetched tape
     {
@@ -534,7 +529,7 @@ void r1cs_prove_device(Instance &I, DeviceWitness &wit, Gens &g, Transcript &tr,
     OTTI_HIP(hipMemcpyAsync(S.blinds.p, blinds_vars.data() + rk * Ll, Ll * sizeof(Fr), hipMemcpyHostToDevice, c.stream));
     {
         uint32_t hbase = g.pc_n.h;
-        dev_msm_rows(c, DG, nullptr, 0, 0, Ll, S.blinds.p, &hbase, 1, MSM_COMPRESSED, rows_kept ? wit.rows_kept.p : c.msm_keep.p);
+        dev_msm_rows(c, DG, {.rows = Ll, .extra_s = S.blinds.p, .extra_base = &hbase, .n_extra = 1, .addend = rows_kept ? wit.rows_kept.p : c.msm_keep.p});
         // Az, Bz, Cz do not depend on the transcript: queue them behind the commitment so that they run while the host hashes it
         OTTI_HIP(hipEventRecord(c.ev0, c.stream));
         dev_spmv3(c, rows_set, wit.z.p, S.T[1].p, S.T[2].p, S.T[3].p, false, nullptr);
@@ -542,7 +537,6 @@ void r1cs_prove_device(Instance &I, DeviceWitness &wit, Gens &g, Transcript &tr,
         { RandomTape::Cursor c1(tape, off_sc1), c2(tape, off_sc2); sumcheck_draw_tape(early1, c1, nrx, 4); sumcheck_draw_tape(early2, c2, nry, 3); }
         round_points = precompute_round_points_launch(c, DG, g, early1, early2, S.pre);
         OTTI_HIP(hipEventSynchronize(c.ev0));
-        c.encode_pending();
         P.comm_vars.resize(Lsz);
         static_assert(sizeof(CPoint) == 32, "CPoint is 32 packed bytes");
         if (sh) sh->allgather(c.h_points, Ll * 32, P.comm_vars.data());       // rank order = row-block order

@@ -48,8 +48,8 @@ namespace {
 // sparse_hint: 1 / 0 = the scalars are / are not mostly small numbers (picks the bulk MSM variant); -1 = look (a pass over Z and a synchronise)
 std::vector<CPoint> commit_poly(DevCtx &c, Gens &gens, const Fr *Z, const PcSet &s, int sparse_hint = -1) {
     ensure_gens_device(gens);
-    const bool sparse = sparse_hint >= 0 ? sparse_hint != 0 : dev_small_fraction(c, Z, s.L * s.R) > 0.25;
-    dev_msm_rows(c, *gens.dev, Z, s.R, s.R, s.L, nullptr, nullptr, 0, MSM_COMPRESSED, nullptr, sparse);
+    const bool sparse = sparse_hint >= 0 ? sparse_hint != 0 : dev_small_fraction(c, Z, s.L * s.R) > kSparseWitness;
+    dev_msm_rows(c, *gens.dev, {.dense = Z, .n_dense = s.R, .rows = s.L, .sparse = sparse});
     c.sync();
     std::vector<CPoint> out(s.L);
     memcpy(out.data(), c.h_points, 32 * s.L);
@@ -622,7 +622,7 @@ struct RowsAhead {
             if (ms) hc.stream = ms;
             const bool trace = getenv("OTTI_TRACE") != nullptr; const double t_go = now_ms();
             OTTI_HIP(hipStreamWaitEvent(hc.stream, ev, 0));
-            dev_msm_rows(hc, *gens.dev, Z, R, R, rows, nullptr, nullptr, 0, MSM_COMPRESSED, nullptr, false);
+            dev_msm_rows(hc, *gens.dev, {.dense = Z, .n_dense = R, .rows = rows});
             const double t_queued = now_ms();
             // (polled, not hipStreamSynchronize: a blocking wait in this thread was seen to hold up the proving thread's launches for as long as it lasted)
             if (!getenv("OTTI_DEREFS_SYNC")) while (hipStreamQuery(hc.stream) == hipErrorNotReady) std::this_thread::sleep_for(std::chrono::microseconds(50));
@@ -746,7 +746,7 @@ static std::vector<uint8_t> snark_prove_resident_once(Instance &I, CompComm &com
     tr.append_protocol_name("Sparse polynomial evaluation proof");
     if (rows_job) {
         // the column half (and nothing for the zero rows: the identity compresses to 32 zero bytes) on this stream, beside what is left of the helper's row half
-        dev_msm_rows(c, *g.eval->dev, derefs.p + (size_t)3 * N, g.derefs.R, g.derefs.R, rows_half, nullptr, nullptr, 0, MSM_COMPRESSED, nullptr, false);
+        dev_msm_rows(c, *g.eval->dev, {.dense = derefs.p + (size_t)3 * N, .n_dense = g.derefs.R, .rows = rows_half});
         c.sync();
         E.comm_derefs.assign(g.derefs.L, CPoint{});
         for (auto &z : E.comm_derefs) memset(z.b, 0, 32);
@@ -764,7 +764,7 @@ static std::vector<uint8_t> snark_prove_resident_once(Instance &I, CompComm &com
         ensure_gens_device(*g.eval);
         std::vector<CPoint> block(per); for (auto &z : block) memset(z.b, 0, 32);
         if (mine) {
-            dev_msm_rows(c, *g.eval->dev, derefs.p + r0 * Rr, Rr, Rr, mine, nullptr, nullptr, 0, MSM_COMPRESSED, nullptr, false);
+            dev_msm_rows(c, *g.eval->dev, {.dense = derefs.p + r0 * Rr, .n_dense = Rr, .rows = mine});
             c.sync();
             memcpy(block[0].b, c.h_points, 32 * mine);
         }

@@ -189,27 +189,26 @@ void DevCtx::msm_host_sum(const MsmPending &p) {
         h_pts[r] = ptfe_to(acc);
     }
 }
-void DevCtx::wait_points(unsigned long long ticket) {
-    if (!ticket) { sync(); return; }
-    MsmMailbox &mb = msm_mail;
-    for (int i = 0; i < mb.pending_n; i++)
-        if (mb.pending[i].seq == ticket) {
-            const MsmPending p = mb.pending[i];
-            for (int j = i + 1; j < mb.pending_n; j++) mb.pending[j - 1] = mb.pending[j];
-            mb.pending_n--;
-            msm_host_sum(p);
-            mb.read[mb.read_next++ & 7] = ticket;
-            pending_host_encode = p.rows;
-            encode_pending();
-            return;
+void DevCtx::wait_points(const MsmTicket &t) {
+    if (!t.delivers_without_sync()) { sync(); return; }      // kept, raw, encoded on the device, or in h_pts for the host to encode: all behind the stream
+    if (t.route == MsmRoute::mail) {
+        MsmMailbox &mb = msm_mail;
+        int i = 0;
+        while (i < mb.pending_n && mb.pending[i].seq != t.seq) i++;
+        if (i == mb.pending_n) {
+            // the ticket's sums were read already — then this returns at once, as a flag wait on a delivered launch does — or they are
+            // gone, and nothing will ever raise a flag for them
+            for (unsigned long long r : mb.read) if (r == t.seq) return;
+            throw Error(OTTI_ERR_INTERNAL, "a small MSM's chunk sums were overwritten or released before they were read");
         }
-    if (mb.host_sum(*this)) {
-        // this context's small launches mail (the switch is per process): the ticket's sums were read already — then this returns at once,
-        // as a flag wait on a delivered launch does — or they are gone, and nothing will ever raise a flag for them
-        for (unsigned long long r : mb.read) if (r == ticket) { encode_pending(); return; }
-        throw Error(OTTI_ERR_INTERNAL, "a small MSM's chunk sums were overwritten or released before they were read");
-    }
-    wait_ticket(ticket);
+        const MsmPending p = mb.pending[i];
+        for (int j = i + 1; j < mb.pending_n; j++) mb.pending[j - 1] = mb.pending[j];
+        mb.pending_n--;
+        msm_host_sum(p);
+        mb.read[mb.read_next++ & 7] = t.seq;
+    } else wait_ticket(t.seq);
+    // the ticket's own rows: a launch queued ahead of this wait (an armed bullet round) has set the count for itself since
+    pending_host_encode = t.rows;
     encode_pending();
 }
 void DevCtx::sync() {

@@ -212,6 +212,31 @@ def test_device_pointer_entry_points_match_the_staged_ones(rng):
         KD.stream_destroy(stream)
 
 
+def test_commitment_on_both_sides_of_every_result_route(rng):
+    """Rows of 16 terms plus a blind, L rows of them: L <= 2 is a fused launch (chunk sums mailed to the host, or the flag), 3 <= L <= 8 comes back
+    as extended points the host compresses, L >= 9 is compressed on the device (msm_plan.h MsmRoute) — through the staged entry, and through the
+    device-pointer entry, which has to fetch the points from wherever the route left them, on the library's stream and on a caller's.
+    (The device-pointer entry only enqueues and the library's stream is a non-blocking one: the staged call behind it on the same thread
+    drains that stream before it returns, a caller's own stream is synchronised by the caller.)"""
+    gens, og = oa.NIZKGens.new(256, 256, 1), orc.OGens(256, 256, 1)
+    R = og.R
+    assert R == 16
+    stream = KD.stream_create()
+    try:
+        for L in (1, 2, 3, 8, 9):
+            Z, bl = orc.rand_fr(rng, L * R), orc.rand_fr(rng, L)
+            want = orc.commit_rows(og, Z, L, R, bl)
+            dZ, dbl, d_lib, d_own = oa.DeviceArray.from_host(Z), oa.DeviceArray.from_host(bl), oa.DeviceArray(L), oa.DeviceArray(L)
+            KD.msm_rows(gens, dZ, L, R, dbl, d_lib, None)
+            assert eq(K.msm_rows(gens, Z, L, R, bl)[0], want), L
+            assert eq(d_lib.to_host(), want), L
+            KD.msm_rows(gens, dZ, L, R, dbl, d_own, stream)
+            KD.stream_sync(stream)
+            assert eq(d_own.to_host(), want), L
+    finally:
+        KD.stream_destroy(stream)
+
+
 # ------------------------------------------------------------------------------------------------ armed launches (device.h)
 @pytest.mark.parametrize("n,hold_us", [(8, 0), (1 << 10, 300), (1 << 16, 2000)])
 def test_armed_round_released_aborted_and_reused(rng, n, hold_us):
