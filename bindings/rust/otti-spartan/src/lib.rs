@@ -17,6 +17,7 @@ pub enum OttiInstance {}
 pub enum OttiGens {}
 pub enum OttiSnarkGens {}
 pub enum OttiCompComm {}
+pub enum OttiWitness {}
 
 extern "C" {
     fn otti_instance_new(num_cons: u64, num_vars: u64, num_inputs: u64, a: *const OttiEntry, na: usize, b: *const OttiEntry, nb: usize,
@@ -30,6 +31,10 @@ extern "C" {
                        stage_ms: *mut f64) -> i32;
     fn otti_nizk_verify(inst: *const OttiInstance, inputs32: *const u8, ninputs: usize, gens: *const OttiGens, tlabel: *const u8,
                         tlabel_len: usize, proof: *const u8, proof_len: usize) -> i32;
+    // a resident witness changed in scattered variables (kept rows are patched, not summed again) and in its public inputs
+    fn otti_witness_scatter(inst: *mut OttiInstance, wit: *mut OttiWitness, idx: *const u64, src: *const core::ffi::c_void, count: usize, format: i32,
+                            stride_bytes: usize, on_device: i32, stream: *mut core::ffi::c_void) -> i32;
+    fn otti_witness_set_inputs(inst: *mut OttiInstance, wit: *mut OttiWitness, inputs32: *const u8, ninputs: usize) -> i32;
     // SNARK mode (upstream spartan-zkinterface without --nizk)
     fn otti_snark_gens_new(num_cons: u64, num_vars: u64, num_inputs: u64, num_nz_entries: u64, out: *mut *mut OttiSnarkGens) -> i32;
     fn otti_snark_gens_free(gens: *mut OttiSnarkGens);

@@ -226,6 +226,33 @@ int32_t otti_witness_drop_rows(otti_witness *wit);
 /* *kept: 0 or 1; *L, *R: the geometry of the kept rows (0 when none are kept); *rows_resummed: rows summed again by updates since keep_rows.
    Any out pointer may be NULL.  A null wit is OTTI_ERR_BAD_ARG; without a device no witness exists: OTTI_ERR_NO_DEVICE, wit is not looked at. */
 int32_t otti_witness_rows_info(const otti_witness *wit, int32_t *kept, size_t *L, size_t *R, uint64_t *rows_resummed);
+/* ---- scatter update: variables idx[0 .. count) of a resident witness replaced by src[0 .. count) (format / stride_bytes as otti_witness_update).
+   For a caller whose step changes scattered variables (the touched coordinates of an iterate, a handful of cells of a compiled witness): one call,
+   whatever rows the indices fall in.  idx: 8-byte unsigned indices, STRICTLY ASCENDING (so none twice), each below the padded num_vars.
+   on_device: idx AND src are both host memory (0) or both device memory (1; then `stream` as in otti_witness_update, and both pointers 8-byte
+   aligned).  Afterwards z is bit for bit what otti_witness_upload builds from the updated values, and small_fraction is counted again in one pass,
+   as by otti_witness_update: equal to a fresh upload's.  Kept rows are not summed again but PATCHED: the commitment is linear, so a changed
+   variable j of row i moves the row's sum by (new - old) * G[j - i R] — one table look-up per window of the fixed-base table, count * W in all,
+   against R * W for summing a row again; rows_resummed of otti_witness_rows_info does not move, and proofs stay byte-identical.
+   Refusals, in this order: OTTI_ERR_BAD_ARG before any device is touched (a null inst / wit, a null idx or src with a non-zero count, an unknown
+   format, a bad stride_bytes, a misaligned device pointer); OTTI_ERR_INVALID_INDEX, also before any device, for count above the padded num_vars
+   and for a HOST index list that is not strictly ascending or has an element >= the padded num_vars (one pass over it); OTTI_ERR_NO_DEVICE;
+   OTTI_ERR_INVALID_NUM_VARS for a witness of other dimensions; then, found on the device, OTTI_ERR_INVALID_INDEX for such a DEVICE index list and
+   after it OTTI_ERR_INVALID_SCALAR for a scalar >= l.  A refused call changes nothing: z, small_fraction, the kept rows and every counter stay as
+   they were.  count == 0: OTTI_OK, nothing done, no counter moved.  Never while a proof or check with this witness is running; a device source
+   must not overlap the witness's own vector.  Sharded provers call it on every rank (their proofs ignore kept rows as before).  If the patch
+   cannot run because the generators' table has to be rebuilt and HBM is short, the error is returned with z updated and the kept rows dropped. */
+int32_t otti_witness_scatter(otti_instance *inst, otti_witness *wit, const uint64_t *idx, const void *src, size_t count,
+                             int32_t format, size_t stride_bytes, int32_t on_device, void *stream);
+/* since the witness was made: scatter calls that changed it, kept rows patched by them (distinct idx / R per call, summed), (index, delta) terms
+   summed into kept rows; the last two move only while rows are kept.  Any out pointer may be NULL.  A null wit is OTTI_ERR_BAD_ARG; without a
+   device no witness exists: OTTI_ERR_NO_DEVICE, wit is not looked at. */
+int32_t otti_witness_scatter_info(const otti_witness *wit, uint64_t *calls, uint64_t *rows_patched, uint64_t *terms_patched);
+/* replaces the public inputs of a resident witness (z[V + 1 .. V + 1 + ninputs), V the padded num_vars, and the host copy the transcript reads).
+   Kept rows cover the variables alone and are untouched, as are small_fraction (it counts the variables) and every counter.
+   OTTI_ERR_BAD_ARG: a null handle, or null inputs32 with ninputs > 0; OTTI_ERR_INVALID_NUM_INPUTS: ninputs differs from the instance's;
+   OTTI_ERR_INVALID_SCALAR: an input >= l (checked on the host: the witness is unchanged) — all before OTTI_ERR_NO_DEVICE.  Same threads rule. */
+int32_t otti_witness_set_inputs(otti_instance *inst, otti_witness *wit, const uint8_t *inputs32, size_t ninputs);
 int32_t otti_snark_verify(const otti_comp_comm *comm, const uint8_t *inputs32, size_t ninputs, const otti_snark_gens *gens,
                           const uint8_t *tlabel, size_t tlabel_len, const uint8_t *proof, size_t proof_len);
 void    otti_buf_free(void *p);
@@ -316,6 +343,10 @@ int32_t otti_k_sc_quad_fold_round(const uint8_t *h_A, const uint8_t *h_B, size_t
  * plain launch's results; any disagreement between the three ways is OTTI_ERR_INTERNAL. */
 int32_t otti_k_armed_selftest(const uint8_t *A, const uint8_t *B, size_t len, const uint8_t *r, uint32_t hold_us, uint8_t *out2, uint8_t *e2);
 int32_t otti_k_msm_rows(otti_gens *gens, const uint8_t *h_Z, size_t L, size_t R, const uint8_t *h_blinds, uint8_t *h_out32, float *kernel_ms);
+/* the kernel that patches kept rows, on L identity points: out[i] = compress(sum over {k : idx[k] in [iR, (i+1)R)} s[k] * P[idx[k] - iR]), i < L <= 4096,
+   R = the generators' row length; idx strictly ascending below L*R (else OTTI_ERR_INVALID_INDEX), s Montgomery.  A row without terms is the identity. */
+int32_t otti_k_msm_scatter_rows(otti_gens *gens, size_t L, const uint64_t *h_idx, const uint8_t *h_s, size_t count,
+                                uint8_t *h_out32, float *kernel_ms);
 /* PolyEvalProof::verify's C_LZ on the device [dense_mlpoly.rs PolyEvalProof::verify -> GroupElement::vartime_multiscalar_mul, RECALL]:
    out = compress(sum_i s[i] * decompress(C[i])), n >= 256 compressed ristretto255 points, scalars in Montgomery form.  Batch decompression,
    LDS-bucket Pippenger, window recombination on the host.  OTTI_ERR_VERIFY_DECOMPRESS if an encoding does not decode. */

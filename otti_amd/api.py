@@ -1,6 +1,7 @@
 """ctypes binding of libottispartan.so — same names, argument meaning and error behaviour as upstream libspartan's
 `src/lib.rs` for the NIZK path [RECALL], which is what `spzk verify --nizk` [REF /root/reference/run.py:58,100] and
 rust-circ `--action spartan` [REF /root/reference/run.py:147] call."""
+import contextlib
 import ctypes
 import os
 import sys
@@ -84,6 +85,9 @@ _sig("otti_witness_free", None, _vp)
 _sig("otti_witness_from_device", _i32, _vp, _vp, _sz, _i32, _sz, _vp, _sz, _vp, ctypes.POINTER(_vp))
 _sig("otti_witness_upload_ints", _i32, _vp, _vp, _sz, _i32, _vp, _sz, ctypes.POINTER(_vp))
 _sig("otti_witness_update", _i32, _vp, _vp, _sz, _vp, _sz, _i32, _sz, _i32, _vp)
+_sig("otti_witness_scatter", _i32, _vp, _vp, _vp, _vp, _sz, _i32, _sz, _i32, _vp)
+_sig("otti_witness_scatter_info", _i32, _vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64))
+_sig("otti_witness_set_inputs", _i32, _vp, _vp, _vp, _sz)
 _sig("otti_witness_info", _i32, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_sz), ctypes.POINTER(ctypes.c_double))
 _sig("otti_witness_keep_rows", _i32, _vp, _vp, _vp)
 _sig("otti_witness_keep_rows_snark", _i32, _vp, _vp, _vp)
@@ -147,6 +151,7 @@ _sig("otti_k_sc_quad_fold_round", _i32, _vp, _vp, _sz, _vp, _vp, _vp, _fp)
 _sig("otti_k_armed_selftest", _i32, _vp, _vp, _sz, _vp, ctypes.c_uint32, _vp, _vp)
 _sig("otti_k_msm_rows", _i32, _vp, _vp, _sz, _sz, _vp, _vp, _fp)
 _sig("otti_k_row_sum", _i32, _vp, _sz, _vp, _vp)
+_sig("otti_k_msm_scatter_rows", _i32, _vp, _sz, _vp, _vp, _sz, _vp, _fp)
 _sig("otti_k_eq_pyramid", _i32, _vp, _sz, _vp)
 _sig("otti_k_sc_cubic3_round", _i32, _vp, _vp, _vp, _sz, _vp, _vp, _fp)
 _sig("otti_k_sc_cubic3_fold_round", _i32, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _fp)
@@ -503,6 +508,74 @@ class Witness:
             src, on_device = values.data_ptr(), 1
             stream = _torch_stream(torch, values, stream)
         _check(lib.otti_witness_update(inst._h, self._h, first, src, count, fmt, stride_bytes, on_device, stream))
+
+    def scatter(self, inst, indices, values, fmt=None, stream=None):
+        """Replace the variables ``indices`` by ``values`` in place (otti_witness_scatter); kept rows are patched by the changes, not summed again.
+        ``indices``: a numpy int64 / uint64 array with ``values`` a numpy int64 / uint64 array or (n, 32) uint8 canonical scalars (``fmt`` names
+        another 32-byte format); or both torch GPU tensors, int64 indices and values as from_tensor takes them.  Indices in any order are sorted
+        here, the values alongside; a duplicate or negative index raises ValueError before the library is called.  A scalar >= l raises
+        R1CSError(-5), an index beyond the variables R1CSError(-6), and either leaves the witness as it was."""
+        if isinstance(indices, np.ndarray) or isinstance(indices, (list, tuple)):
+            idx = np.asarray(indices)
+            if idx.ndim != 1 or idx.dtype not in (np.int64, np.uint64):
+                raise ValueError("indices: expected a 1-D numpy array of int64 or uint64")
+            if idx.dtype == np.int64 and idx.size and int(idx.min()) < 0:
+                raise ValueError("indices: a negative index")
+            idx = idx.astype(np.uint64)
+            if not isinstance(values, np.ndarray):
+                raise ValueError("values: host indices go with a numpy int64 / uint64 array or (n, 32) uint8 canonical scalars")
+            if values.dtype in (np.int64, np.uint64):
+                vals, f = _int_array(values)
+            else:
+                vals, f = _scalars(values, "values"), WIT_CANONICAL32
+            if vals.shape[0] != idx.size:
+                raise ValueError("indices and values differ in length")
+            if idx.size > 1 and not bool(np.all(idx[1:] > idx[:-1])):
+                order = np.argsort(idx, kind="stable")
+                idx, vals = np.ascontiguousarray(idx[order]), np.ascontiguousarray(vals[order])
+                if not bool(np.all(idx[1:] > idx[:-1])):
+                    raise ValueError("indices: an index occurs twice")
+            idx = np.ascontiguousarray(idx)
+            fmt = f if fmt is None else fmt
+            _check(lib.otti_witness_scatter(inst._h, self._h, _ptr(idx), _ptr(vals), idx.size, fmt, 0, 0, None))
+            return
+        torch = sys.modules.get("torch")
+        if torch is None or not isinstance(indices, torch.Tensor) or not isinstance(values, torch.Tensor):
+            raise ValueError("indices / values: expected numpy arrays, or torch GPU tensors for both")
+        if not indices.is_cuda or indices.dtype != torch.int64 or indices.dim() != 1:
+            raise ValueError("indices: expected a 1-D int64 tensor on the GPU")
+        f, count, stride = _tensor_layout(torch, values)
+        if count != indices.shape[0]:
+            raise ValueError("indices and values differ in length")
+        fmt = f if fmt is None else fmt
+        if stream is not None:
+            ctx = torch.cuda.stream(torch.cuda.ExternalStream(stream, device=indices.device))
+        else:
+            ctx = contextlib.nullcontext()
+        with ctx:                                                  # the checks and the sort run where the tensors were produced
+            if count and bool((indices < 0).any()):
+                raise ValueError("indices: a negative index")
+            if count > 1 and not bool((indices[1:] > indices[:-1]).all()):
+                indices, order = torch.sort(indices)
+                values = values.index_select(0, order)
+                stride = 0
+                if bool((indices[1:] == indices[:-1]).any()):
+                    raise ValueError("indices: an index occurs twice")
+            indices = indices.contiguous()
+            stream = _torch_stream(torch, indices, stream)
+        _check(lib.otti_witness_scatter(inst._h, self._h, indices.data_ptr(), values.data_ptr(), count, fmt, stride, 1, stream))
+
+    def scatter_info(self):
+        """(calls, rows_patched, terms_patched): scatter calls that changed the witness, kept rows patched by them, (index, delta) terms summed into kept rows"""
+        a, b, c = _u64(), _u64(), _u64()
+        _check(lib.otti_witness_scatter_info(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        return a.value, b.value, c.value
+
+    def set_inputs(self, inst, inputs):
+        """Replace the public inputs of the resident witness (otti_witness_set_inputs); ``inputs``: InputsAssignment or (n, 32) uint8 canonical
+        scalars.  Kept rows cover the variables alone and stay valid."""
+        i = _scalars(inputs.assignment if hasattr(inputs, "assignment") else inputs, "inputs")
+        _check(lib.otti_witness_set_inputs(inst._h, self._h, _ptr(i), i.shape[0]))
 
     @property
     def info(self):
@@ -981,6 +1054,16 @@ class kernels:
         out = np.zeros(32, dtype=np.uint8)
         _check(lib.otti_k_row_sum(_ptr(C), C.shape[0], _ptr(s), _ptr(out)))
         return out
+
+    @staticmethod
+    def msm_scatter_rows(gens, L, idx, s):
+        """the kernel that patches kept rows, onto L identity points: row i = compress(sum of s[k] * P[idx[k] - i R] over its indices)"""
+        idx = np.ascontiguousarray(idx, dtype=np.uint64)
+        s = _scalars(s, "s")
+        out = np.zeros((L, 32), dtype=np.uint8)
+        ms = kernels._ms()
+        _check(lib.otti_k_msm_scatter_rows(gens._h, L, _ptr(idx), _ptr(s), idx.size, _ptr(out), ctypes.byref(ms)))
+        return out, ms.value
 
     @staticmethod
     def msm_rows(gens, Z, L, R, blinds):

@@ -164,6 +164,49 @@ int32_t otti_witness_update(otti_instance *inst, otti_witness *wit, size_t first
         return OTTI_OK;
     });
 }
+// ---- scatter update (device.h DeviceWitness::scatter).  The order of refusals: the arguments (BAD_ARG), the index list as far as the host can see it
+// (INVALID_INDEX: its length, and a host list itself in one pass), a missing device, the witness's dimensions, and on the device a bad device
+// index list before a scalar >= l.
+int32_t otti_witness_scatter(otti_instance *inst, otti_witness *wit, const uint64_t *idx, const void *src, size_t count, int32_t format, size_t stride_bytes,
+                             int32_t on_device, void *stream) {
+    return guarded([&] {
+        if (!inst || !wit) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        check_wit_source(src, count, format, stride_bytes, on_device != 0);
+        if (!idx && count) throw Error(OTTI_ERR_BAD_ARG, "null index list with a non-zero count");
+        if (on_device && ((uintptr_t)idx & 7)) throw Error(OTTI_ERR_BAD_ARG, "a device index list must be 8-byte aligned");
+        const size_t V = inst->I->num_vars;
+        if (count > V) throw Error(OTTI_ERR_INVALID_INDEX, "more indices than the instance has variables");
+        if (!on_device)
+            for (size_t i = 0; i < count; i++)
+                if (idx[i] >= V || (i && idx[i] <= idx[i - 1])) throw Error(OTTI_ERR_INVALID_INDEX, "the indices are not strictly ascending below the padded num_vars");
+        DevCtx::get();                                            // no device: said before the witness handle is looked at
+        check_witness_dims(wit, *inst->I);
+        wit->w->scatter(idx, format, src, count, stride_bytes, on_device != 0, (hipStream_t)stream);
+        return OTTI_OK;
+    });
+}
+int32_t otti_witness_scatter_info(const otti_witness *wit, uint64_t *calls, uint64_t *rows_patched, uint64_t *terms_patched) {
+    return guarded([&] {
+        if (!wit) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (otti_device_count() < 1) throw Error(OTTI_ERR_NO_DEVICE, "no device: no witness handle can exist");
+        const DeviceWitness &w = *wit->w;
+        if (calls) *calls = w.scatter_calls;
+        if (rows_patched) *rows_patched = w.rows_patched;
+        if (terms_patched) *terms_patched = w.terms_patched;
+        return OTTI_OK;
+    });
+}
+int32_t otti_witness_set_inputs(otti_instance *inst, otti_witness *wit, const uint8_t *inputs32, size_t ninputs) {
+    return guarded([&] {
+        if (!inst || !wit || (!inputs32 && ninputs)) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (ninputs != inst->I->num_inputs) throw Error(OTTI_ERR_INVALID_NUM_INPUTS, "wrong number of inputs");
+        const std::vector<Fr> inputs = scalars_from_bytes(inputs32, ninputs);      // INVALID_SCALAR: a host check, the witness is not touched
+        DevCtx::get();
+        check_witness_dims(wit, *inst->I);
+        wit->w->set_inputs(inputs);
+        return OTTI_OK;
+    });
+}
 int32_t otti_witness_info(const otti_witness *wit, const void **d_z, size_t *n, double *small_fraction) {
     return guarded([&] {
         if (!wit) throw Error(OTTI_ERR_BAD_ARG, "null argument");

@@ -250,6 +250,28 @@ int32_t otti_k_msm_rows(otti_gens *gens, const uint8_t *Z, size_t L, size_t R, c
     });
 }
 
+// (index, scalar) lists summed into L rows over the generators' table (k_msm.hip k_msm_scatter, the kernel that patches a witness's kept rows),
+// here onto L identity points, which are then compressed.  The index list is judged on the host: the kernel takes table columns from it.
+int32_t otti_k_msm_scatter_rows(otti_gens *gens, size_t L, const uint64_t *idx, const uint8_t *s, size_t count, uint8_t *out32, float *ms) {
+    return guarded([&] {
+        if (!gens || !out32 || !L || L > 4096 || (count && (!idx || !s))) throw Error(OTTI_ERR_BAD_ARG, "null argument, or L outside 1 .. 4096");
+        Gens &g = *gens->g;
+        for (size_t i = 0; i < count; i++)
+            if (idx[i] >= L * g.R || (i && idx[i] <= idx[i - 1])) throw Error(OTTI_ERR_INVALID_INDEX, "the indices are not strictly ascending below L * R");
+        DevCtx &c = DevCtx::get();
+        ensure_gens_device(g);
+        Staged sc(c, s, count);
+        DevBuf<uint64_t> d_idx(std::max<size_t>(1, count)); DevBuf<Pt> rows(L); DevBuf<uint8_t> enc(32 * L);
+        const std::vector<Pt> id(L, pt_identity());
+        if (count) OTTI_HIP(hipMemcpyAsync(d_idx.p, idx, count * sizeof(uint64_t), hipMemcpyHostToDevice, c.stream));
+        OTTI_HIP(hipMemcpyAsync(rows.p, id.data(), L * sizeof(Pt), hipMemcpyHostToDevice, c.stream));
+        KTimer t(c, ms); dev_msm_scatter(c, *g.dev, d_idx.p, sc.d.p, count, g.R, rows.p, L); t.stop();
+        dev_encode_points(c, rows.p, L, enc.p);
+        OTTI_HIP(hipMemcpyAsync(out32, enc.p, 32 * L, hipMemcpyDeviceToHost, c.stream));
+        OTTI_HIP(hipStreamSynchronize(c.stream)); return OTTI_OK;
+    });
+}
+
 // ---- the prover's own kernels for phase one / evaluation proof / bullet reduction
 int32_t otti_k_eq_pyramid(const uint8_t *r, size_t n, uint8_t *out) {
     return guarded([&] {

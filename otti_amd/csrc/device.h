@@ -202,6 +202,15 @@ struct DeviceWitness {
     // variables [first, first + count) replaced likewise.  A scalar >= l throws INVALID_SCALAR and leaves z as it was (the 32-byte formats are
     // converted into a staging buffer first); afterwards small_fraction is counted again.  Not while a proof or check with this witness runs.
     void update(size_t first, int format, const void *src, size_t count, size_t stride, bool src_on_device, hipStream_t producer);
+    // variables idx[0 .. count) replaced by src[0 .. count) (idx: 8-byte indices, strictly ascending and below V, in host or device memory as src is).
+    // z and small_fraction come out as update leaves them.  A bad device index list throws INVALID_INDEX, then a scalar >= l INVALID_SCALAR, both
+    // with z, the kept rows and the counters as they were (everything is converted into a staging buffer and judged before z is written).  Kept
+    // rows are PATCHED, not summed again: the commitment is linear, so row i moves by sum (new - old) * P[j - i R] over its changed variables —
+    // W table look-ups per variable (k_msm.hip k_msm_scatter) against R * W for the row's full sum.  Same threads rule as update.
+    void scatter(const uint64_t *idx, int format, const void *src, size_t count, size_t stride, bool on_device, hipStream_t producer);
+    unsigned long long scatter_calls = 0, rows_patched = 0, terms_patched = 0;   // since the witness was made; the last two move only while rows are kept
+    // the public inputs replaced, in z (z[V + 1 ..)) and in `inputs`, which the transcript reads; kept rows cover the variables alone and stay
+    void set_inputs(const std::vector<Fr> &new_inputs);
     // ---- kept rows (opt-in): the unblinded row sums of the commitment, sum_j z[i * R + j] * P[j] for the L = V / R rows — the group elements the
     // proof's MSM_KEEP launch leaves in DevCtx::msm_keep.  They depend on z and on the generator POINTS alone (their stream and R; not on the
     // window width of the table they were summed with: a table released and rebuilt keeps them valid).  A proof whose generators have these
@@ -245,6 +254,12 @@ DotProductProofLog dplog_prove_device(DevCtx &c, const DeviceGens &DG, const Gen
 size_t dev_witness_ingest(DevCtx &c, Fr *z, size_t n, size_t *n_small = nullptr);   // returns the number of non-canonical scalars (zeroed); n_small: how many are below 2^128
 // the same from device memory in any WitFormat (k_field.hip): element i read at src + i * stride bytes, written to z[dst_off + i]; synchronises
 size_t dev_witness_ingest_from(DevCtx &c, int format, const void *src, size_t stride, size_t n, Fr *z, size_t dst_off, size_t *n_small = nullptr);
+// DeviceWitness::scatter's two element-wise launches (k_field.hip).  check: conv[i] = element i of src in Montgomery form (the rules of
+// dev_witness_ingest_from); *bad_scalars counts those >= l, *bad_indices the i with idx[i] >= V or idx[i] <= idx[i - 1]; writes nothing else;
+// synchronises.  apply (V: the length of z's first half, beyond which nothing is stored): z[idx[i]] = conv[i], and with delta given delta[i] = conv[i] - (what z[idx[i]] held); only queues.
+void dev_witness_scatter_check(DevCtx &c, int format, const void *src, size_t stride, const uint64_t *d_idx, size_t n, size_t V, Fr *conv,
+                               size_t *bad_scalars, size_t *bad_indices);
+void dev_witness_scatter_apply(DevCtx &c, const uint64_t *d_idx, const Fr *conv, size_t n, size_t V, Fr *z, Fr *delta);
 void dev_gather_strided(DevCtx &c, const Fr *in, size_t stride, size_t offset, Fr *out, size_t n);   // out[i] = in[i*stride + offset]
 
 std::shared_ptr<DeviceInstance> upload_instance(const Instance &I);
@@ -316,6 +331,12 @@ double dev_small_fraction(DevCtx &c, const Fr *z, size_t n);               // sh
 // compresses (row sum + addend)).  Lets the host draw the blinds while the device already sums the witness terms.
 // keep_dst (MSM_KEEP only): row i's sum goes to keep_dst[i] instead, c.msm_keep is left alone (DeviceWitness::rows_kept: the caller offsets it
 // to the first of the rows to sum, as it does `dense`).  force_bulk: the chip-filling kernel whatever the size (a run of re-summed rows).
+// ---- (index, scalar) lists summed into row sums that stay on the device (k_msm.hip k_msm_scatter; DeviceWitness::scatter):
+// rows[i] += sum over {k : d_idx[k] in [i R, (i + 1) R)} d_s[k] * P[d_idx[k] - i R] for i < L.  d_idx: strictly ascending, below L * R (the
+// CALLER has checked that: the kernel takes a term's table column from it); d_s Montgomery.  One workgroup per row; a row without terms is not
+// touched.  Only queues.
+void dev_msm_scatter(DevCtx &c, const DeviceGens &g, const uint64_t *d_idx, const Fr *d_s, size_t count, size_t R, Pt *rows, size_t L);
+void dev_encode_points(DevCtx &c, const Pt *pts, size_t n, uint8_t *d_out32);      // RFC 9496 encodings of n extended points (only queues)
 // ---- K9: LZ[j] = sum_i Lv[i] * Z[i*R + j]
 void dev_poly_bound(DevCtx &c, const Fr *Z, size_t L, size_t R, const Fr *Lv, Fr *out, Fr *scratch /* >= 64*R */);
 // chunk sums of the same bound over eq(rest) alone (k_sumcheck.hip): out = (L / m) x R; false (nothing launched) when the geometry does not allow it

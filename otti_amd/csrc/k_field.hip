@@ -109,6 +109,66 @@ size_t dev_witness_ingest_from(DevCtx &c, int format, const void *src, size_t st
     if (n_small) *n_small = (size_t)h[1];
     return (size_t)h[0];
 }
+// ---- a scatter update of the resident assignment (DeviceWitness::scatter): element i of the source replaces z[idx[i]].  Two launches, so that a
+// refused list has changed nothing.  The first converts every element into a staging buffer by the rules above and counts what the host refuses:
+// counts[0] scalars >= l, counts[1] indices that are not below V or not above their predecessor (so a list that passes has no index twice).
+template <int F> __global__ __launch_bounds__(kBlock) void k_witness_scatter_check(const unsigned char *src, size_t stride, const unsigned long long *idx, size_t n,
+                                                                                 size_t V, Fr *conv, unsigned long long *counts) {
+    unsigned bad = 0, bad_idx = 0;
+    const bool wide = (((size_t)src | stride) & 15) == 0;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        bool neg; Fr raw = wit_load<F>(src + i * stride, wide, neg), out;
+        if constexpr (F == WIT_I64 || F == WIT_U64) {
+            if (neg) raw = fr_sub(fr_zero(), raw);
+            out = fr_mul(raw, fr_R2());
+        } else if (!fr_raw_is_canonical(raw.v)) { out = fr_zero(); bad++; }
+        else if constexpr (F == WIT_CANONICAL32) out = fr_mul(raw, fr_R2());
+        else out = raw;
+        conv[i] = out;
+        const unsigned long long j = idx[i];
+        if (j >= V || (i > 0 && j <= idx[i - 1])) bad_idx++;
+    }
+    for (int o = 32; o >= 1; o >>= 1) { bad += __shfl_down(bad, o); bad_idx += __shfl_down(bad_idx, o); }
+    if ((threadIdx.x & 63) == 0) { if (bad) atomicAdd(&counts[0], (unsigned long long)bad); if (bad_idx) atomicAdd(&counts[1], (unsigned long long)bad_idx); }
+}
+// The second writes: the indices are distinct and below V (checked above), so no two lanes touch one element of z.  delta (kept rows only):
+// what the element moved by, the scalar of its row's patch.
+__global__ __launch_bounds__(kBlock) void k_witness_scatter_apply(const unsigned long long *idx, const Fr *conv, size_t n, size_t V, Fr *z, Fr *delta) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t j = (size_t)idx[i];
+        if (j >= V) continue;                                                    // a list rewritten since the check: never a store outside z
+        const Fr now = conv[i], old = z[j];
+        z[j] = now;
+        if (delta) delta[i] = fr_sub(now, old);
+    }
+}
+void dev_witness_scatter_check(DevCtx &c, int format, const void *src, size_t stride, const uint64_t *d_idx, size_t n, size_t V, Fr *conv,
+                               size_t *bad_scalars, size_t *bad_indices) {
+    *bad_scalars = *bad_indices = 0;
+    if (!n) return;
+    const unsigned char *s = reinterpret_cast<const unsigned char *>(src);
+    const unsigned long long *ix = reinterpret_cast<const unsigned long long *>(d_idx);
+    OTTI_HIP(hipMemsetAsync(c.d_counts.p, 0, 2 * sizeof(unsigned long long), c.stream));
+    {
+        KScope ks(c, KC_OTHER);
+        switch (format) {
+        case WIT_CANONICAL32: hipLaunchKernelGGL(k_witness_scatter_check<WIT_CANONICAL32>, grid_for(n), kBlock, 0, c.stream, s, stride, ix, n, V, conv, c.d_counts.p); break;
+        case WIT_MONTGOMERY32: hipLaunchKernelGGL(k_witness_scatter_check<WIT_MONTGOMERY32>, grid_for(n), kBlock, 0, c.stream, s, stride, ix, n, V, conv, c.d_counts.p); break;
+        case WIT_I64: hipLaunchKernelGGL(k_witness_scatter_check<WIT_I64>, grid_for(n), kBlock, 0, c.stream, s, stride, ix, n, V, conv, c.d_counts.p); break;
+        case WIT_U64: hipLaunchKernelGGL(k_witness_scatter_check<WIT_U64>, grid_for(n), kBlock, 0, c.stream, s, stride, ix, n, V, conv, c.d_counts.p); break;
+        default: throw Error(OTTI_ERR_BAD_ARG, "unknown witness format");
+        }
+    }
+    unsigned long long h[2] = {0, 0};
+    OTTI_HIP(hipMemcpyAsync(h, c.d_counts.p, sizeof h, hipMemcpyDeviceToHost, c.stream));
+    OTTI_HIP(hipStreamSynchronize(c.stream));
+    *bad_scalars = (size_t)h[0]; *bad_indices = (size_t)h[1];
+}
+void dev_witness_scatter_apply(DevCtx &c, const uint64_t *d_idx, const Fr *conv, size_t n, size_t V, Fr *z, Fr *delta) {
+    if (!n) return;
+    KScope ks(c, KC_OTHER);
+    hipLaunchKernelGGL(k_witness_scatter_apply, grid_for(n), kBlock, 0, c.stream, reinterpret_cast<const unsigned long long *>(d_idx), conv, n, V, z, delta);
+}
 // Whole-chip throughput of the Montgomery product in GF(l) (operands in registers, every CU busy): what the sum-check, sparse-product
 // and eq kernels are priced against beside the HBM roof — at 7-13 products per 192 bytes they are bounded by the multiplier first.
 __global__ __launch_bounds__(kBlock) void k_fr_mul_peak(Fr *io, int iters) {

@@ -174,6 +174,83 @@ template <int kKind> __global__ __launch_bounds__(kBlock) void k_msm_rows(MsmArg
     if (threadIdx.x == 0) A.partial[row * A.nchunks + chunk_id] = p10_pack(acc);
 }
 
+// ------------------------------------------------------------------------------------------------ (index, scalar) lists into kept row sums
+// DeviceWitness::scatter: a resident witness that keeps its commitment's row sums has changed in k scattered variables; row i's sum moves by
+// sum (new - old) * P[j - i R] over its changed variables j.  The list is sorted by index, so a row's terms are ONE run of it: workgroup r finds
+// the run [lo, hi) for [r R, (r + 1) R) by two binary searches (one lane, broadcast through LDS) and leaves at once when it is empty — rows_kept[r]
+// is then neither read nor written.  Otherwise it is k_msm_rows<MSM_BULK> on a gathered row: sub-chunks of kMsmScatterSub terms staged in LDS as
+// recoded deltas plus their table column, thread (term lane, window) adding its table entries into a P9 accumulator that lives across the
+// sub-chunks, one tree, and thread 0 adds the sum to the row.  One workgroup owns a row: no atomics, no hand-off between workgroups.
+// Work: k * W table look-ups for k terms, whatever rows they fall in (a full re-sum of a row is R * W).
+constexpr int kMsmScatterSub = 256;            // terms staged at a time (LDS: 36 B + a 4-byte column each; the tree's 20 KB region holds them)
+struct MsmScatterArgs {
+    const TabEntry *table; int c, W; uint32_t E; int lanes; uint32_t K[9];
+    const unsigned long long *idx; const Fr *s; size_t count, R; Pt *rows;
+};
+__device__ __forceinline__ size_t scatter_lower_bound(const unsigned long long *idx, size_t n, unsigned long long key) {   // first k with idx[k] >= key
+    size_t lo = 0, hi = n;
+    while (lo < hi) { const size_t mid = lo + (hi - lo) / 2; if (idx[mid] < key) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+__global__ __launch_bounds__(kBlock) void k_msm_scatter(MsmScatterArgs A) {
+    constexpr size_t kRawBytes = (size_t)kMsmScatterSub * 9 * sizeof(uint32_t), kTreeBytes = (kBlock / 2) * sizeof(P10);
+    __shared__ __attribute__((aligned(16))) unsigned char s_mem[kRawBytes > kTreeBytes ? kRawBytes : kTreeBytes];
+    __shared__ uint32_t s_col[kMsmScatterSub];
+    __shared__ size_t s_run[2];
+    uint32_t *s_raw = reinterpret_cast<uint32_t *>(s_mem);
+    P10 *sm = reinterpret_cast<P10 *>(s_mem);
+    const size_t row = blockIdx.x;
+    const unsigned long long first = (unsigned long long)row * A.R;
+    if (threadIdx.x == 0) {
+        const size_t lo = scatter_lower_bound(A.idx, A.count, first);
+        s_run[0] = lo; s_run[1] = lo + scatter_lower_bound(A.idx + lo, A.count - lo, first + A.R);
+    }
+    __syncthreads();
+    const size_t lo = s_run[0], hi = s_run[1];
+    if (lo == hi) return;                                        // the whole workgroup: nothing of this row has changed
+    P9 acc9 = p9_identity();
+    const int w = threadIdx.x % A.W, tl = threadIdx.x / A.W;
+    const size_t WE = (size_t)A.W * A.E;
+    for (size_t sub0 = lo; sub0 < hi; sub0 += kMsmScatterSub) {
+        const uint32_t n_tot = (uint32_t)min((size_t)kMsmScatterSub, hi - sub0);
+        if (sub0 != lo) __syncthreads();                         // the previous sub-chunk's scalars have been consumed
+        for (uint32_t t = threadIdx.x; t < n_tot; t += blockDim.x) {
+            recode_scalar(s_raw + t * 9, A.s[sub0 + t], A.K);
+            s_col[t] = (uint32_t)min(A.idx[sub0 + t] - first, (unsigned long long)(A.R - 1));   // below R by the search; the clamp keeps a list changed under the kernel inside the table
+        }
+        __syncthreads();
+        if (tl < A.lanes)
+            for (uint32_t t = tl; t < n_tot; t += A.lanes) {
+                const int d = recoded_digit(s_raw + t * 9, w, A.c);
+                if (d == 0) continue;
+                const uint32_t mag = (uint32_t)(d < 0 ? -d : d);
+                N9 e = n9_unpack(A.table[(size_t)s_col[t] * WE + (size_t)w * A.E + (mag - 1)].n);
+                if (d < 0) e = n9_negate(e);
+                acc9 = p9_madd(acc9, e);
+            }
+    }
+    __syncthreads();                                             // the tree reuses the scalar region: everyone must be done reading it
+    P10 acc = p10_unpack(p9_pack(acc9));
+    const F10 d2 = f10_const(fp_2D());
+    for (int sft = kBlock / 2; sft >= 1; sft >>= 1) {
+        if ((int)threadIdx.x >= sft && (int)threadIdx.x < 2 * sft) sm[threadIdx.x - sft] = acc;
+        __syncthreads();
+        if ((int)threadIdx.x < sft) acc = p10_add(acc, sm[threadIdx.x], d2);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) A.rows[row] = p10_pack(p10_add(acc, p10_unpack(A.rows[row]), d2));
+}
+void dev_msm_scatter(DevCtx &c, const DeviceGens &g, const uint64_t *d_idx, const Fr *d_s, size_t count, size_t R, Pt *rows, size_t L) {
+    if (!count || !L) return;
+    if (!R || R > g.nbases || g.W > kBlock) throw Error(OTTI_ERR_INTERNAL, "msm scatter: the row length exceeds the table");
+    MsmScatterArgs A;
+    A.table = g.table.p; A.c = g.c; A.W = g.W; A.E = (uint32_t)g.E; A.lanes = kBlock / g.W;
+    msm_recoding_constant(A.K, g.c, g.W);
+    A.idx = reinterpret_cast<const unsigned long long *>(d_idx); A.s = d_s; A.count = count; A.R = R; A.rows = rows;
+    KScope ks(c, KC_OTHER);
+    hipLaunchKernelGGL(k_msm_scatter, (unsigned)L, kBlock, 0, c.stream, A);
+}
+
 // ------------------------------------------------------------------------------------------------ the latency-bound launches
 // One or two rows of up to R terms (Cx, the bullet-reduction rounds, delta), or many rows of a handful of terms (blind * h per row
 // commitment, the tape-only points of every sum-check round).  Nothing here is throughput: a 2^20 proof makes 14 such launches one
@@ -404,6 +481,11 @@ __global__ __launch_bounds__(64) void k_encode_points(const Pt *pts, const Pt *a
     uint32_t *o = (uint32_t *)(out32 + 32 * i);
     for (int k = 0; k < 8; k++) o[k] = w[k];
     if (host32) { uint32_t *h = (uint32_t *)(host32 + 32 * i); for (int k = 0; k < 8; k++) h[k] = w[k]; }
+}
+void dev_encode_points(DevCtx &c, const Pt *pts, size_t n, uint8_t *d_out32) {
+    if (!n) return;
+    KScope ks(c, KC_MSM_FINISH);
+    hipLaunchKernelGGL(k_encode_points, (unsigned)((n + 63) / 64), 64, 0, c.stream, pts, (const Pt *)nullptr, n, d_out32, (uint8_t *)nullptr);
 }
 // share of the n scalars whose canonical value is below 2^128 (what a compiled circuit's witness is mostly made of)
 __global__ __launch_bounds__(kBlock) void k_count_small(const Fr *z, size_t n, unsigned long long *count) {

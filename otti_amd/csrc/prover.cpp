@@ -235,6 +235,56 @@ static void resum_rows(DevCtx &c, DeviceWitness &w, size_t r0, size_t r1) {
     try { sum_rows_into(c, w, *w.rows_gens, r0, r1, false); } catch (...) { w.drop_rows(); throw; }
     w.rows_resummed += r1 - r0 + 1;
 }
+// ---- scatter update.  Behind the same staging and producer-stream ordering as update (host indices are staged like host values), three launches:
+// the check (everything converted into `conv`, bad indices and scalars counted: one synchronise, and a refusal has written nothing), the apply
+// (z, and the deltas when rows are kept), and the patch of the kept rows (k_msm.hip k_msm_scatter: count * W table look-ups).
+void DeviceWitness::scatter(const uint64_t *idx, int format, const void *src, size_t count, size_t stride, bool on_device, hipStream_t producer) {
+    DevCtx &c = DevCtx::get();
+    const size_t V = z.n / 2;
+    if (count > V) throw Error(OTTI_ERR_INVALID_INDEX, "more indices than the instance has variables");
+    if (!count) return;
+    WitSource s(c, format, src, count, stride, on_device, producer);      // a device source: the one event orders the producer of both lists
+    DevBuf<uint64_t> idx_staged; const uint64_t *d_idx = idx;
+    if (!on_device) {
+        idx_staged.alloc(count); d_idx = idx_staged.p;
+        OTTI_HIP(hipMemcpyAsync(idx_staged.p, idx, count * sizeof(uint64_t), hipMemcpyHostToDevice, c.stream));
+    }
+    DevBuf<Fr> conv(count), delta;                                // outlive the launches that read them: freed after dev_small_fraction has synchronised
+    const bool patch = rows_kept.p != nullptr;
+    if (patch) delta.alloc(count);
+    size_t bad_scalars = 0, bad_indices = 0;
+    dev_witness_scatter_check(c, format, s.p, s.stride, d_idx, count, V, conv.p, &bad_scalars, &bad_indices);
+    if (bad_indices) throw Error(OTTI_ERR_INVALID_INDEX, "the indices are not strictly ascending below the padded num_vars: the witness is unchanged");
+    if (bad_scalars) throw Error(OTTI_ERR_INVALID_SCALAR, "non-canonical scalar in the scatter: the witness is unchanged");
+    dev_witness_scatter_apply(c, d_idx, conv.p, count, V, z.p, patch ? delta.p : nullptr);
+    std::vector<uint64_t> h_idx;                                  // a device list, read back for the count of rows it touches
+    if (patch) {
+        // z has changed: a patch that cannot run (the table has to be rebuilt and HBM is short) leaves rows that no longer belong to it, as in resum_rows
+        try {
+            ensure_gens_device(*rows_gens);
+            dev_msm_scatter(c, *rows_gens->dev, d_idx, delta.p, count, rows_R, rows_kept.p, rows_kept.n);
+            if (on_device) { h_idx.resize(count); OTTI_HIP(hipMemcpyAsync(h_idx.data(), d_idx, count * sizeof(uint64_t), hipMemcpyDeviceToHost, c.stream)); }
+        } catch (...) { (void)hipStreamSynchronize(c.stream); drop_rows(); throw; }
+    }
+    small_fraction = dev_small_fraction(c, z.p, V);               // counted again as update does, never incrementally; synchronises
+    scatter_calls++;
+    if (patch) {
+        const uint64_t *ix = on_device ? h_idx.data() : idx;
+        unsigned long long rows = 0;
+        for (size_t i = 0; i < count; i++) rows += i == 0 || ix[i] / rows_R != ix[i - 1] / rows_R;
+        rows_patched += rows; terms_patched += count;
+    }
+}
+void DeviceWitness::set_inputs(const std::vector<Fr> &new_inputs) {
+    DevCtx &c = DevCtx::get();
+    if (new_inputs.size() != inputs.size()) throw Error(OTTI_ERR_INVALID_NUM_INPUTS, "wrong number of inputs");
+    const size_t V = z.n / 2;
+    if (!new_inputs.empty()) {
+        OTTI_HIP(hipMemcpyAsync(z.p + V + 1, new_inputs.data(), new_inputs.size() * sizeof(Fr), hipMemcpyHostToDevice, c.stream));
+        OTTI_HIP(hipStreamSynchronize(c.stream));
+    }
+    inputs = new_inputs;
+}
 bool DeviceWitness::rows_kept_for(const Gens &g) const { return rows_kept.p && rows_R == g.R && rows_stream && !strcmp(rows_stream, g.stream); }
 void DeviceWitness::keep_rows(Gens &g) {
     DevCtx &c = DevCtx::get();
