@@ -323,6 +323,12 @@ int32_t otti_k_fr_to_canonical(const uint8_t *h_in, uint8_t *h_out, size_t n);
 int32_t otti_k_multiply_vec(otti_instance *inst, const uint8_t *h_z, uint8_t *h_Az, uint8_t *h_Bz, uint8_t *h_Cz, float *kernel_ms);
 /* compute_eval_table_sparse x3 fused with r_A*A + r_B*B + r_C*C: eq_rx has num_cons entries, out 2*num_vars */
 int32_t otti_k_eval_table_sparse(otti_instance *inst, const uint8_t *h_eq_rx, const uint8_t *h_rABC /* 3 */, uint8_t *h_out, float *kernel_ms);
+/* which of their variants the three sparse passes above and below (multiply_vec / the satisfiability pass: by_col = 0; eval_table_sparse:
+   by_col != 0, rows = 2*num_vars) run on this instance.  quad: a row per four lanes (else per lane); use_small: entries are read through 4-byte
+   small-integer codes; n_heavy rows whose longest list exceeds 64 entries go through n_seg segments of 2048.  Makes the device copy of the
+   instance as those entries do, if it is not there yet, and launches nothing else. */
+typedef struct { uint64_t rows, entries[3], n_heavy, n_seg; int32_t use_small, quad; } otti_device_info;
+int32_t otti_instance_device_info(otti_instance *inst, int32_t by_col, otti_device_info *out);
 /* EqPolynomial::evals */
 int32_t otti_k_eq_evals(const uint8_t *h_r, size_t ell, uint8_t *h_out, float *kernel_ms);
 /* DensePolynomial::bound_poly_var_top / _bot (in place on a staged copy; out has len/2 entries) */

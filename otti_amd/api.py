@@ -54,6 +54,10 @@ class _R1CS(ctypes.Structure):
                 ("vars32", _vp), ("nvars", _sz), ("inputs32", _vp), ("ninputs", _sz)]
 
 
+class _DeviceInfo(ctypes.Structure):
+    _fields_ = [("rows", _u64), ("entries", _u64 * 3), ("n_heavy", _u64), ("n_seg", _u64), ("use_small", _i32), ("quad", _i32)]
+
+
 def _sig(name, res, *args):
     f = getattr(lib, name)
     f.restype = res
@@ -141,6 +145,7 @@ _sig("otti_k_addr_timestamps", _i32, _vp, _sz, _sz, _vp, _vp, _fp)
 _sig("otti_k_fr_to_canonical", _i32, _vp, _vp, _sz)
 _sig("otti_k_multiply_vec", _i32, _vp, _vp, _vp, _vp, _vp, _fp)
 _sig("otti_k_eval_table_sparse", _i32, _vp, _vp, _vp, _vp, _fp)
+_sig("otti_instance_device_info", _i32, _vp, _i32, ctypes.POINTER(_DeviceInfo))
 _sig("otti_k_eq_evals", _i32, _vp, _sz, _vp, _fp)
 _sig("otti_k_fold_top", _i32, _vp, _sz, _vp, _vp, _fp)
 _sig("otti_k_fold_bot", _i32, _vp, _sz, _vp, _vp, _fp)
@@ -302,6 +307,13 @@ class Instance:
 
     def prepare_device(self, gens=None):
         _check(lib.otti_prepare_device(self._h, gens._h if gens is not None else None))
+
+    def device_info(self, by_col=False):
+        """which variants of the sparse kernels run on this instance (otti_instance_device_info): dict of rows, entries (A, B, C), use_small, quad,
+        n_heavy, n_seg for the by-row copy (multiply_vec, check_sat) or the by-column one (eval_table_sparse)"""
+        d = _DeviceInfo()
+        _check(lib.otti_instance_device_info(self._h, 1 if by_col else 0, ctypes.byref(d)))
+        return dict(rows=d.rows, entries=tuple(d.entries), use_small=bool(d.use_small), quad=bool(d.quad), n_heavy=d.n_heavy, n_seg=d.n_seg)
 
     def __del__(self):
         if getattr(self, "_h", None):

@@ -43,6 +43,7 @@ struct DeviceCsrSet {
     DevBuf<uint32_t> seg_row, seg_no, seg_begin;              // their segments (row id, segment number), and each long row's first segment
     size_t rows = 0, n_heavy = 0, n_seg = 0;
     double avg_row = 0.0;                                     // entries per row and matrix: picks the row-per-lane or the row-per-quad kernel
+    bool quad() const { return avg_row >= 3.0; }              // row per quad from three entries per row and matrix on (k_sparse.hip: the launchers' and the report's one rule)
     DCsr3 view() const { DCsr3 v; for (int k = 0; k < 3; k++) { v.ptr[k] = ptr[k].p; v.idx[k] = idx[k].p; v.val[k] = val[k].p; v.small[k] = small[k].p; } return v; }
 };
 struct DeviceInstance { DeviceCsrSet by_row, by_col; size_t nnz = 0; };

@@ -96,7 +96,7 @@ void dev_spmv3(DevCtx &c, const DeviceCsrSet &m, const Fr *x, Fr *o0, Fr *o1, Fr
     KScope ks(c, KC_SPMV);
     // measured on the compiler-like 2^20 instance (4.6 entries per row and matrix): 0.54 -> 0.37 ms; on the uniform one (1 entry) the quad
     // kernel would idle three lanes in four (0.16 -> 0.54 ms)
-    const bool quad = m.avg_row >= 3.0;
+    const bool quad = m.quad();
     const bool sm = m.use_small;
     if (quad && sm) hipLaunchKernelGGL(k_spmv3_quad<true>, grid_for(4 * m.rows), kBlock, 0, c.stream, m.view(), m.rows, x, o0, o1, o2, (int)combine, c0, c1, c2);
     else if (quad) hipLaunchKernelGGL(k_spmv3_quad<false>, grid_for(4 * m.rows), kBlock, 0, c.stream, m.view(), m.rows, x, o0, o1, o2, (int)combine, c0, c1, c2);
@@ -213,7 +213,7 @@ void dev_sat_pass(DevCtx &c, const DeviceCsrSet &m, const Fr *z, unsigned long l
     unsigned long long *count = c.d_counts.p;
     OTTI_HIP(hipMemsetAsync(count, 0, sizeof(unsigned long long), c.stream));
     KScope ks(c, KC_SAT_CHECK);
-    const bool quad = m.avg_row >= 3.0, sm = m.use_small;      // the layouts dev_spmv3 picks, for its reasons
+    const bool quad = m.quad(), sm = m.use_small;      // the layouts dev_spmv3 picks, for its reasons
     if (quad && sm) hipLaunchKernelGGL(k_sat_quad<true>, grid_for(4 * m.rows), kBlock, 0, c.stream, m.view(), m.rows, z, bits, count);
     else if (quad) hipLaunchKernelGGL(k_sat_quad<false>, grid_for(4 * m.rows), kBlock, 0, c.stream, m.view(), m.rows, z, bits, count);
     else if (sm) hipLaunchKernelGGL(k_sat_light<true>, grid_for(m.rows), kBlock, 0, c.stream, m.view(), m.rows, z, bits, count);

@@ -157,10 +157,13 @@ def _rect_case(shape):
     return Case(n * reps, n, ni, rep(A), rep(B), rep(C), vars_, inputs)
 
 
-# The three instances of "both lane layouts and both coefficient paths", reached by construction: the uniform synthetic instance has one entry
-# per row (row per lane), the compiler-like one ~4.6 small-integer entries per row (row per quad, coefficient codes) and one row of more
-# than 64 entries (the segmented path), the hand-built one 4 entries per row with 252-bit coefficients (row per quad, no codes).
+# The three instances of "both lane layouts and both coefficient paths": the uniform synthetic instance has one entry per row, two in three of
+# them small integers (row per lane, coefficient codes), the compiler-like one ~4.6 small-integer entries per row (row per quad, coefficient
+# codes) and rows of more than 64 entries (the segmented path), the hand-built one 4 entries per row with 252-bit coefficients (row per quad,
+# no codes).  That each reaches its kernels is asserted below, through device_info; row per lane without codes is test_gpu_sparse_edges.py's.
 _cache = {}
+_VARIANT = {"uniform": dict(quad=False, use_small=True, heavy=False), "compiler": dict(quad=True, use_small=True, heavy=True),
+            "wide": dict(quad=True, use_small=False, heavy=False)}
 
 
 def _layout_case(name):
@@ -171,6 +174,8 @@ def _layout_case(name):
             _cache[name] = Case.of(oa.synth_r1cs_compiler_like(1 << 16, 10, 5))
         else:
             _cache[name] = Case.of(_wide_r1cs(np.random.default_rng(777)))
+        info, want = _cache[name].inst.device_info(), _VARIANT[name]
+        assert (info["quad"], info["use_small"], info["n_heavy"] > 0) == (want["quad"], want["use_small"], want["heavy"]), (name, info)
     return _cache[name]
 
 

@@ -18,7 +18,7 @@ BAD_ARG, NO_DEVICE = -21, -20
 def test_symbols_exported_and_declared():
     syms = subprocess.check_output(["nm", "-D", "--defined-only", oa.lib_path], text=True)
     header = open(HEADER).read()
-    for name in ("otti_witness_check_sat", "otti_kd_check_sat"):
+    for name in ("otti_witness_check_sat", "otti_kd_check_sat", "otti_instance_device_info"):
         assert re.search(r"\bT %s\b" % name, syms), name
         assert re.search(r"int32_t\s+%s\s*\(" % name, header), name
         assert hasattr(oa.lib, name)
@@ -45,6 +45,10 @@ def test_null_arguments_are_bad_arg_without_a_device():
     assert g(None, fake_wit, fake_wit, ctypes.byref(n), None) == BAD_ARG
     assert g(inst._h, None, fake_wit, ctypes.byref(n), None) == BAD_ARG
     assert g(inst._h, fake_wit, None, ctypes.byref(n), None) == BAD_ARG
+    info = oa.api._DeviceInfo()
+    assert oa.lib.otti_instance_device_info(None, 0, ctypes.byref(info)) == BAD_ARG
+    assert oa.lib.otti_instance_device_info(inst._h, 0, None) == BAD_ARG
+    assert ctypes.sizeof(info) == 56                           # otti_device_info: six uint64_t and two int32_t
 
 
 def test_spzk_usage_lists_check():
@@ -85,3 +89,5 @@ def test_check_sat_has_no_cpu_fallback():
     n = ctypes.c_uint64()
     z = ctypes.c_void_p(64)                                    # the device is asked for before any pointer is used
     assert oa.lib.otti_kd_check_sat(inst._h, z, z, ctypes.byref(n), None) == NO_DEVICE
+    with pytest.raises(oa.NoDeviceError):
+        inst.device_info()
