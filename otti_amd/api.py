@@ -425,6 +425,20 @@ def _int_array(a):
     return np.ascontiguousarray(a), WIT_I64 if a.dtype == np.int64 else WIT_U64
 
 
+def _host_values(a):
+    """(contiguous array, WIT_*) of host values Witness.update / scatter take: int64 / uint64 numbers, else (n, 32) uint8 canonical scalars"""
+    if a.dtype in (np.int64, np.uint64):
+        return _int_array(a)
+    return _scalars(a, "values"), WIT_CANONICAL32
+
+
+def _torch_if(*objs):
+    """the torch module when every one of objs is a torch tensor, else None.  A tensor that came in has its module loaded: torch is never
+    imported here (from_tensor alone does that)"""
+    torch = sys.modules.get("torch")
+    return torch if torch is not None and all(isinstance(o, torch.Tensor) for o in objs) else None
+
+
 def _tensor_layout(torch, t):
     """(format, count, stride_bytes) of a GPU tensor Witness.from_tensor / update take"""
     if not t.is_cuda:
@@ -503,17 +517,13 @@ class Witness:
                 raise ValueError("update from a device address needs fmt")
             src, count, on_device = _dev_addr(values[0]), values[1], 1
         elif isinstance(values, np.ndarray):
-            if values.dtype in (np.int64, np.uint64):
-                keep, f = _int_array(values)
-                count = keep.size
-            else:
-                keep, f = _scalars(values, "values"), WIT_CANONICAL32
-                count = keep.shape[0]
+            keep, f = _host_values(values)
+            count = keep.shape[0]
             fmt = f if fmt is None else fmt
             src, on_device, stride_bytes = _ptr(keep), 0, 0
         else:
-            torch = sys.modules.get("torch")                      # a tensor came in: its module is loaded (torch is imported in from_tensor only)
-            if torch is None or not isinstance(values, torch.Tensor):
+            torch = _torch_if(values)
+            if torch is None:
                 raise ValueError("values: expected a numpy int64 / uint64 array, an (n, 32) uint8 numpy array, a torch GPU tensor or (address, count)")
             f, count, stride_bytes = _tensor_layout(torch, values)
             fmt = f if fmt is None else fmt
@@ -536,10 +546,7 @@ class Witness:
             idx = idx.astype(np.uint64)
             if not isinstance(values, np.ndarray):
                 raise ValueError("values: host indices go with a numpy int64 / uint64 array or (n, 32) uint8 canonical scalars")
-            if values.dtype in (np.int64, np.uint64):
-                vals, f = _int_array(values)
-            else:
-                vals, f = _scalars(values, "values"), WIT_CANONICAL32
+            vals, f = _host_values(values)
             if vals.shape[0] != idx.size:
                 raise ValueError("indices and values differ in length")
             if idx.size > 1 and not bool(np.all(idx[1:] > idx[:-1])):
@@ -551,8 +558,8 @@ class Witness:
             fmt = f if fmt is None else fmt
             _check(lib.otti_witness_scatter(inst._h, self._h, _ptr(idx), _ptr(vals), idx.size, fmt, 0, 0, None))
             return
-        torch = sys.modules.get("torch")
-        if torch is None or not isinstance(indices, torch.Tensor) or not isinstance(values, torch.Tensor):
+        torch = _torch_if(indices, values)
+        if torch is None:
             raise ValueError("indices / values: expected numpy arrays, or torch GPU tensors for both")
         if not indices.is_cuda or indices.dtype != torch.int64 or indices.dim() != 1:
             raise ValueError("indices: expected a 1-D int64 tensor on the GPU")

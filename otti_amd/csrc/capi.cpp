@@ -115,16 +115,8 @@ int32_t otti_nizk_prove(otti_instance *inst, const uint8_t *vars32, size_t nvars
         return emit_proof(pf, tm, proof, proof_len, stage_ms);
     });
 }
-int32_t otti_witness_upload(otti_instance *inst, const uint8_t *vars32, size_t nvars, const uint8_t *inputs32, size_t ninputs, otti_witness **out) {
-    return guarded([&] {
-        if (!inst || !out) throw Error(OTTI_ERR_BAD_ARG, "null argument");
-        if (ninputs != inst->I->num_inputs) throw Error(OTTI_ERR_INVALID_NUM_INPUTS, "wrong number of inputs");
-        std::vector<Fr> inputs = scalars_from_bytes(inputs32, ninputs);
-        return adopt(out, std::make_unique<DeviceWitness>(*inst->I, vars32, nvars, inputs));
-    });
-}
 void otti_witness_free(otti_witness *w) { delete w; }
-// ---- a witness from device memory, from host integers, and changed in place (device.h WitFormat, k_field.hip k_witness_ingest_from).  Everything
+// ---- a witness from host bytes, from device memory, from host integers, and changed in place (device.h WitFormat, k_field.hip k_witness_ingest_from).  Everything
 // that can be said about the arguments alone is said before DevCtx::get() brings a device up.
 static void check_wit_source(const void *src, size_t count, int32_t format, size_t stride_bytes, bool on_device) {
     if (format < OTTI_WIT_CANONICAL32 || format > OTTI_WIT_U64) throw Error(OTTI_ERR_BAD_ARG, "unknown witness format");
@@ -142,6 +134,9 @@ static int32_t witness_from(otti_instance *inst, const void *src, size_t nvars, 
         std::vector<Fr> inputs = scalars_from_bytes(inputs32, ninputs);
         return adopt(out, std::make_unique<DeviceWitness>(*inst->I, format, src, nvars, stride_bytes, on_device, (hipStream_t)stream, inputs));
     });
+}
+int32_t otti_witness_upload(otti_instance *inst, const uint8_t *vars32, size_t nvars, const uint8_t *inputs32, size_t ninputs, otti_witness **out) {
+    return witness_from(inst, vars32, nvars, OTTI_WIT_CANONICAL32, 0, false, inputs32, ninputs, nullptr, out);
 }
 int32_t otti_witness_from_device(otti_instance *inst, const void *d_vars, size_t nvars, int32_t format, size_t stride_bytes, const uint8_t *inputs32, size_t ninputs,
                                  void *stream, otti_witness **out) {

@@ -189,17 +189,19 @@ struct KStats {
 };
 struct KScope { DevCtx &c; int rec; KScope(DevCtx &c_, int k) : c(c_), rec(KStats::get().begin(c_, k)) {} ~KScope() { KStats::get().end(c, rec); } };
 
+enum WitFormat { WIT_CANONICAL32 = 0, WIT_MONTGOMERY32 = 1, WIT_I64 = 2, WIT_U64 = 3 };   // = OTTI_WIT_* of the C ABI
+inline size_t wit_elem_bytes(int format) { return format == WIT_I64 || format == WIT_U64 ? 8 : 32; }
 // witness resident in HBM: z = vars || 1 || inputs || 0..  (2 * num_vars Montgomery-form elements)
 struct DeviceWitness {
     DevBuf<Fr> z; std::vector<Fr> inputs;
     double small_fraction = 0.0;                              // share of the variables below 2^128: picks the MSM variant of the commitment
-    DeviceWitness(const Instance &I, const std::vector<Fr> &vars_padded, const std::vector<Fr> &inputs);
-    // straight from the caller's canonical bytes: validation (InvalidScalar) and the conversion to Montgomery form happen on the device
-    DeviceWitness(const Instance &I, const uint8_t *vars32, size_t nvars, const std::vector<Fr> &inputs);
-    // from another source (WitFormat): element i at src + i * stride bytes (stride 0: packed), in device memory or, src_on_device false, host
-    // memory (staged as it is: an integer crosses PCIe as 8 bytes and is widened on the device).  producer: the stream whose queued work writes a
-    // device source (nullptr: none to wait for).  Returns once the source is free again.  Same z and small_fraction as the constructor above.
+    // from a source in any WitFormat: element i at src + i * stride bytes (stride 0: packed), in device memory or, src_on_device false, host memory
+    // (packed 32-byte words are copied into z and converted in place; anything else is staged as it is: an integer crosses PCIe as 8 bytes and
+    // is widened on the device).  Validation (InvalidScalar) and the conversion to Montgomery form happen on the device.  producer: the stream
+    // whose queued work writes a device source (nullptr: none to wait for).  Returns once the source is free again.
     DeviceWitness(const Instance &I, int format, const void *src, size_t nvars, size_t stride, bool src_on_device, hipStream_t producer, const std::vector<Fr> &inputs);
+    // straight from the caller's canonical bytes on the host: the same path
+    DeviceWitness(const Instance &I, const uint8_t *vars32, size_t nvars, const std::vector<Fr> &inputs) : DeviceWitness(I, WIT_CANONICAL32, vars32, nvars, 0, false, nullptr, inputs) {}
     // variables [first, first + count) replaced likewise.  A scalar >= l throws INVALID_SCALAR and leaves z as it was (the 32-byte formats are
     // converted into a staging buffer first); afterwards small_fraction is counted again.  Not while a proof or check with this witness runs.
     void update(size_t first, int format, const void *src, size_t count, size_t stride, bool src_on_device, hipStream_t producer);
@@ -223,9 +225,11 @@ struct DeviceWitness {
     bool rows_kept_for(const Gens &g) const;                  // kept, and over g's points
     void keep_rows(Gens &g);                                  // builds g's table if need be, sums every row, returns when they are resident; again with the same points: nothing
     void drop_rows();
+private:
+    // the dimension checks, z allocated and zeroed, 1 || inputs queued behind the variables; returns the host copy of that tail, which has to
+    // outlive the next synchronise of c.stream
+    std::vector<Fr> set_up(DevCtx &c, const Instance &I, size_t nvars);
 };
-enum WitFormat { WIT_CANONICAL32 = 0, WIT_MONTGOMERY32 = 1, WIT_I64 = 2, WIT_U64 = 3 };   // = OTTI_WIT_* of the C ABI
-inline size_t wit_elem_bytes(int format) { return format == WIT_I64 || format == WIT_U64 ? 8 : 32; }
 void ensure_device_objects(Instance &I, Gens &g);          // lazily built, shared by every prover thread (guarded)
 void ensure_instance_device(Instance &I);
 void ensure_gens_device(Gens &g);
@@ -252,11 +256,12 @@ std::shared_ptr<DeviceShard> upload_instance_shard(const Instance &I, int rank, 
 struct PeBufs { Fr *LZ, *Rv, *a, *s, *b2, *s2, *rows, *extras; };      // R elements each (rows: 2 R, extras: 4 (log2 R + 1))
 DotProductProofLog dplog_prove_device(DevCtx &c, const DeviceGens &DG, const Gens &g, const PcView &v, const PeBufs &B, const Fr &LZ_blind, const Fr *y_known,
                                       const Fr &blind_y, CPoint &Cy_out, Transcript &tr, RandomTape &tape);
-size_t dev_witness_ingest(DevCtx &c, Fr *z, size_t n, size_t *n_small = nullptr);   // returns the number of non-canonical scalars (zeroed); n_small: how many are below 2^128
-// the same from device memory in any WitFormat (k_field.hip): element i read at src + i * stride bytes, written to z[dst_off + i]; synchronises
+// VarsAssignment::new on the device, from device memory in any WitFormat (k_field.hip): element i read at src + i * stride bytes, written in
+// Montgomery form to z[dst_off + i]; src is either disjoint from the destination or is the destination itself, packed (conversion in place).
+// Returns the number of non-canonical scalars (stored as zero); n_small: how many are below 2^128.  Synchronises.
 size_t dev_witness_ingest_from(DevCtx &c, int format, const void *src, size_t stride, size_t n, Fr *z, size_t dst_off, size_t *n_small = nullptr);
 // DeviceWitness::scatter's two element-wise launches (k_field.hip).  check: conv[i] = element i of src in Montgomery form (the rules of
-// dev_witness_ingest_from); *bad_scalars counts those >= l, *bad_indices the i with idx[i] >= V or idx[i] <= idx[i - 1]; writes nothing else;
+// dev_witness_ingest_from, src disjoint from conv or conv itself, packed); *bad_scalars counts those >= l, *bad_indices the i with idx[i] >= V or idx[i] <= idx[i - 1]; writes nothing else;
 // synchronises.  apply (V: the length of z's first half, beyond which nothing is stored): z[idx[i]] = conv[i], and with delta given delta[i] = conv[i] - (what z[idx[i]] held); only queues.
 void dev_witness_scatter_check(DevCtx &c, int format, const void *src, size_t stride, const uint64_t *d_idx, size_t n, size_t V, Fr *conv,
                                size_t *bad_scalars, size_t *bad_indices);

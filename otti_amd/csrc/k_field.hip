@@ -24,34 +24,12 @@ void dev_fill_zero(DevCtx &c, Fr *p, size_t n) { if (n) OTTI_HIP(hipMemsetAsync(
 void dev_fill_one(DevCtx &c, Fr *p, size_t n) { if (n) hipLaunchKernelGGL(k_fr_fill, grid_for(n), kBlock, 0, c.stream, p, fr_one(), n); }
 void dev_fetch(DevCtx &c, const Fr *src, int slot, size_t n) { OTTI_HIP(hipMemcpyAsync(c.h_results + slot, src, n * sizeof(Fr), hipMemcpyDeviceToHost, c.stream)); }
 
-// VarsAssignment::new on the device: canonical little-endian scalars (the caller's bytes, uploaded as they are) -> Montgomery form in
-// place; values >= l are counted (upstream: R1CSError::InvalidScalar) and left as zero.
-// counts[0]: non-canonical scalars; counts[1]: scalars below 2^128 (the share of small values picks the commitment's MSM variant)
-__global__ __launch_bounds__(kBlock) void k_witness_ingest(Fr *z, size_t n, unsigned long long *counts) {
-    unsigned bad = 0, small = 0;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        Fr raw = z[i];
-        if (fr_raw_is_canonical(raw.v)) { z[i] = fr_mul(raw, fr_R2()); small += (raw.v[4] | raw.v[5] | raw.v[6] | raw.v[7]) == 0 ? 1u : 0u; }
-        else { z[i] = fr_zero(); bad++; small++; }
-    }
-    for (int o = 32; o >= 1; o >>= 1) { bad += __shfl_down(bad, o); small += __shfl_down(small, o); }
-    if ((threadIdx.x & 63) == 0) { if (bad) atomicAdd(&counts[0], (unsigned long long)bad); if (small) atomicAdd(&counts[1], (unsigned long long)small); }
-}
-size_t dev_witness_ingest(DevCtx &c, Fr *z, size_t n, size_t *n_small) {
-    if (n_small) *n_small = 0;
-    if (!n) return 0;
-    OTTI_HIP(hipMemsetAsync(c.d_counts.p, 0, 2 * sizeof(unsigned long long), c.stream));
-    hipLaunchKernelGGL(k_witness_ingest, grid_for(n), kBlock, 0, c.stream, z, n, c.d_counts.p);
-    unsigned long long h[2] = {0, 0};
-    OTTI_HIP(hipMemcpyAsync(h, c.d_counts.p, sizeof h, hipMemcpyDeviceToHost, c.stream));
-    OTTI_HIP(hipStreamSynchronize(c.stream));
-    if (n_small) *n_small = (size_t)h[1];
-    return (size_t)h[0];
-}
-// The same from wherever an assignment lives (device.h WitFormat): element i is read at src + i * stride bytes and lands, in Montgomery
-// form, in z[dst_off + i]; src is device memory that does not overlap z.  counts as above.  Integers are loaded as one 8-byte word and
-// widened (a negative x is l - |x|, so it is never "small"); the 32-byte formats as two 16-byte loads when base and stride allow it
-// (wide), else as four 8-byte ones.  A 32-byte element whose raw value is >= l is counted and stored as zero.
+// VarsAssignment::new on the device, from wherever an assignment lives (device.h WitFormat): element i is read at src + i * stride bytes and
+// lands, in Montgomery form, in z[dst_off + i].  src is device memory that is either disjoint from the destination or is the destination
+// itself, packed (src == z + dst_off, stride 32: the caller's canonical bytes uploaded as they are and converted in place — every lane loads
+// all 32 bytes of its own element before it stores them).  Integers are loaded as one 8-byte word and widened; the 32-byte formats as two
+// 16-byte loads when base and stride allow it (wide), else as four 8-byte ones.
+// counts[0]: non-canonical scalars (upstream: R1CSError::InvalidScalar); counts[1]: scalars below 2^128 (their share picks the commitment's MSM variant)
 typedef uint32_t wit_u32x4 __attribute__((ext_vector_type(4)));
 template <int F> __device__ __forceinline__ Fr wit_load(const unsigned char *p, bool wide, bool &neg) {
     Fr raw; neg = false;
@@ -70,66 +48,77 @@ template <int F> __device__ __forceinline__ Fr wit_load(const unsigned char *p, 
     }
     return raw;
 }
+// THE conversion rule, for every kernel that takes witness elements in: the word wit_load<F> returned -> the Montgomery element.  An integer is
+// always a scalar; a negative one is l - |x| and so never small.  A 32-byte word >= l is refused: stored as zero, and counted as small as well.
+// small: the canonical value is below 2^128 (MONTGOMERY32: judged on fr_to_raw of the word).
+__device__ __forceinline__ bool fr_raw_below_2p128(const Fr &c) { return (c.v[4] | c.v[5] | c.v[6] | c.v[7]) == 0; }
+template <int F> __device__ __forceinline__ Fr wit_convert(Fr raw, bool neg, bool &refused, bool &small) {
+    Fr out; refused = false;
+    if constexpr (F == WIT_I64 || F == WIT_U64) {
+        if (neg) raw = fr_sub(fr_zero(), raw);                                   // l - |x| (on canonical integers the field subtraction is the integer one mod l)
+        small = !neg;
+        out = fr_mul(raw, fr_R2());
+    } else {
+        small = fr_raw_below_2p128(F == WIT_CANONICAL32 ? raw : fr_to_raw(raw));
+        if (!fr_raw_is_canonical(raw.v)) { out = fr_zero(); refused = small = true; }
+        else if constexpr (F == WIT_CANONICAL32) out = fr_mul(raw, fr_R2());
+        else out = raw;
+    }
+    return out;
+}
+// a lane's two tallies summed over its wave and added to counts[0], counts[1]
+__device__ __forceinline__ void wit_tally(unsigned a, unsigned b, unsigned long long *counts) {
+    for (int o = 32; o >= 1; o >>= 1) { a += __shfl_down(a, o); b += __shfl_down(b, o); }
+    if ((threadIdx.x & 63) == 0) { if (a) atomicAdd(&counts[0], (unsigned long long)a); if (b) atomicAdd(&counts[1], (unsigned long long)b); }
+}
 template <int F> __global__ __launch_bounds__(kBlock) void k_witness_ingest_from(const unsigned char *src, size_t stride, size_t n, Fr *z, size_t dst_off,
                                                                                unsigned long long *counts) {
-    unsigned bad = 0, small = 0;
+    unsigned bad = 0, nsmall = 0;
     const bool wide = (((size_t)src | stride) & 15) == 0;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        bool neg; Fr raw = wit_load<F>(src + i * stride, wide, neg), out;
-        if constexpr (F == WIT_I64 || F == WIT_U64) {
-            if (neg) raw = fr_sub(fr_zero(), raw);                               // l - |x| (on canonical integers the field subtraction is the integer one mod l)
-            else small++;
-            out = fr_mul(raw, fr_R2());
-        } else if (!fr_raw_is_canonical(raw.v)) { out = fr_zero(); bad++; small++; }
-        else if constexpr (F == WIT_CANONICAL32) { out = fr_mul(raw, fr_R2()); small += (raw.v[4] | raw.v[5] | raw.v[6] | raw.v[7]) == 0 ? 1u : 0u; }
-        else { out = raw; const Fr c = fr_to_raw(raw); small += (c.v[4] | c.v[5] | c.v[6] | c.v[7]) == 0 ? 1u : 0u; }
-        z[dst_off + i] = out;
+        bool neg, refused, small; const Fr raw = wit_load<F>(src + i * stride, wide, neg);
+        z[dst_off + i] = wit_convert<F>(raw, neg, refused, small);
+        bad += refused; nsmall += small;
     }
-    for (int o = 32; o >= 1; o >>= 1) { bad += __shfl_down(bad, o); small += __shfl_down(small, o); }
-    if ((threadIdx.x & 63) == 0) { if (bad) atomicAdd(&counts[0], (unsigned long long)bad); if (small) atomicAdd(&counts[1], (unsigned long long)small); }
+    wit_tally(bad, nsmall, counts);
+}
+// the runtime format -> the kernels' template argument, as an std::integral_constant
+template <class Fn> static void wit_dispatch(int format, Fn fn) {
+    switch (format) {
+    case WIT_CANONICAL32: return fn(std::integral_constant<int, WIT_CANONICAL32>{});
+    case WIT_MONTGOMERY32: return fn(std::integral_constant<int, WIT_MONTGOMERY32>{});
+    case WIT_I64: return fn(std::integral_constant<int, WIT_I64>{});
+    case WIT_U64: return fn(std::integral_constant<int, WIT_U64>{});
+    default: throw Error(OTTI_ERR_BAD_ARG, "unknown witness format");
+    }
 }
 size_t dev_witness_ingest_from(DevCtx &c, int format, const void *src, size_t stride, size_t n, Fr *z, size_t dst_off, size_t *n_small) {
     if (n_small) *n_small = 0;
     if (!n) return 0;
     const unsigned char *s = reinterpret_cast<const unsigned char *>(src);
-    OTTI_HIP(hipMemsetAsync(c.d_counts.p, 0, 2 * sizeof(unsigned long long), c.stream));
-    {
+    const Tallies t = counted_launch(c, [&](unsigned long long *counts) {
         KScope ks(c, KC_OTHER);
-        switch (format) {
-        case WIT_CANONICAL32: hipLaunchKernelGGL(k_witness_ingest_from<WIT_CANONICAL32>, grid_for(n), kBlock, 0, c.stream, s, stride, n, z, dst_off, c.d_counts.p); break;
-        case WIT_MONTGOMERY32: hipLaunchKernelGGL(k_witness_ingest_from<WIT_MONTGOMERY32>, grid_for(n), kBlock, 0, c.stream, s, stride, n, z, dst_off, c.d_counts.p); break;
-        case WIT_I64: hipLaunchKernelGGL(k_witness_ingest_from<WIT_I64>, grid_for(n), kBlock, 0, c.stream, s, stride, n, z, dst_off, c.d_counts.p); break;
-        case WIT_U64: hipLaunchKernelGGL(k_witness_ingest_from<WIT_U64>, grid_for(n), kBlock, 0, c.stream, s, stride, n, z, dst_off, c.d_counts.p); break;
-        default: throw Error(OTTI_ERR_BAD_ARG, "unknown witness format");
-        }
-    }
-    unsigned long long h[2] = {0, 0};
-    OTTI_HIP(hipMemcpyAsync(h, c.d_counts.p, sizeof h, hipMemcpyDeviceToHost, c.stream));
-    OTTI_HIP(hipStreamSynchronize(c.stream));
-    if (n_small) *n_small = (size_t)h[1];
-    return (size_t)h[0];
+        wit_dispatch(format, [&](auto F) { hipLaunchKernelGGL(k_witness_ingest_from<decltype(F)::value>, grid_for(n), kBlock, 0, c.stream, s, stride, n, z, dst_off, counts); });
+    });
+    if (n_small) *n_small = (size_t)t.second;
+    return (size_t)t.first;
 }
 // ---- a scatter update of the resident assignment (DeviceWitness::scatter): element i of the source replaces z[idx[i]].  Two launches, so that a
-// refused list has changed nothing.  The first converts every element into a staging buffer by the rules above and counts what the host refuses:
-// counts[0] scalars >= l, counts[1] indices that are not below V or not above their predecessor (so a list that passes has no index twice).
+// refused list has changed nothing.  The first converts every element into a staging buffer by the rule above (wit_convert) and counts what the host
+// refuses: counts[0] scalars >= l, counts[1] indices that are not below V or not above their predecessor (so a list that passes has no index twice).
+// As for the ingest, src is either disjoint from conv or is conv itself, packed.
 template <int F> __global__ __launch_bounds__(kBlock) void k_witness_scatter_check(const unsigned char *src, size_t stride, const unsigned long long *idx, size_t n,
                                                                                  size_t V, Fr *conv, unsigned long long *counts) {
     unsigned bad = 0, bad_idx = 0;
     const bool wide = (((size_t)src | stride) & 15) == 0;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        bool neg; Fr raw = wit_load<F>(src + i * stride, wide, neg), out;
-        if constexpr (F == WIT_I64 || F == WIT_U64) {
-            if (neg) raw = fr_sub(fr_zero(), raw);
-            out = fr_mul(raw, fr_R2());
-        } else if (!fr_raw_is_canonical(raw.v)) { out = fr_zero(); bad++; }
-        else if constexpr (F == WIT_CANONICAL32) out = fr_mul(raw, fr_R2());
-        else out = raw;
-        conv[i] = out;
+        bool neg, refused, small; const Fr raw = wit_load<F>(src + i * stride, wide, neg);
+        conv[i] = wit_convert<F>(raw, neg, refused, small);
+        bad += refused;
         const unsigned long long j = idx[i];
         if (j >= V || (i > 0 && j <= idx[i - 1])) bad_idx++;
     }
-    for (int o = 32; o >= 1; o >>= 1) { bad += __shfl_down(bad, o); bad_idx += __shfl_down(bad_idx, o); }
-    if ((threadIdx.x & 63) == 0) { if (bad) atomicAdd(&counts[0], (unsigned long long)bad); if (bad_idx) atomicAdd(&counts[1], (unsigned long long)bad_idx); }
+    wit_tally(bad, bad_idx, counts);
 }
 // The second writes: the indices are distinct and below V (checked above), so no two lanes touch one element of z.  delta (kept rows only):
 // what the element moved by, the scalar of its row's patch.
@@ -148,21 +137,11 @@ void dev_witness_scatter_check(DevCtx &c, int format, const void *src, size_t st
     if (!n) return;
     const unsigned char *s = reinterpret_cast<const unsigned char *>(src);
     const unsigned long long *ix = reinterpret_cast<const unsigned long long *>(d_idx);
-    OTTI_HIP(hipMemsetAsync(c.d_counts.p, 0, 2 * sizeof(unsigned long long), c.stream));
-    {
+    const Tallies t = counted_launch(c, [&](unsigned long long *counts) {
         KScope ks(c, KC_OTHER);
-        switch (format) {
-        case WIT_CANONICAL32: hipLaunchKernelGGL(k_witness_scatter_check<WIT_CANONICAL32>, grid_for(n), kBlock, 0, c.stream, s, stride, ix, n, V, conv, c.d_counts.p); break;
-        case WIT_MONTGOMERY32: hipLaunchKernelGGL(k_witness_scatter_check<WIT_MONTGOMERY32>, grid_for(n), kBlock, 0, c.stream, s, stride, ix, n, V, conv, c.d_counts.p); break;
-        case WIT_I64: hipLaunchKernelGGL(k_witness_scatter_check<WIT_I64>, grid_for(n), kBlock, 0, c.stream, s, stride, ix, n, V, conv, c.d_counts.p); break;
-        case WIT_U64: hipLaunchKernelGGL(k_witness_scatter_check<WIT_U64>, grid_for(n), kBlock, 0, c.stream, s, stride, ix, n, V, conv, c.d_counts.p); break;
-        default: throw Error(OTTI_ERR_BAD_ARG, "unknown witness format");
-        }
-    }
-    unsigned long long h[2] = {0, 0};
-    OTTI_HIP(hipMemcpyAsync(h, c.d_counts.p, sizeof h, hipMemcpyDeviceToHost, c.stream));
-    OTTI_HIP(hipStreamSynchronize(c.stream));
-    *bad_scalars = (size_t)h[0]; *bad_indices = (size_t)h[1];
+        wit_dispatch(format, [&](auto F) { hipLaunchKernelGGL(k_witness_scatter_check<decltype(F)::value>, grid_for(n), kBlock, 0, c.stream, s, stride, ix, n, V, conv, counts); });
+    });
+    *bad_scalars = (size_t)t.first; *bad_indices = (size_t)t.second;
 }
 void dev_witness_scatter_apply(DevCtx &c, const uint64_t *d_idx, const Fr *conv, size_t n, size_t V, Fr *z, Fr *delta) {
     if (!n) return;

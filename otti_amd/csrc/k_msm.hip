@@ -499,12 +499,8 @@ __global__ __launch_bounds__(kBlock) void k_count_small(const Fr *z, size_t n, u
 }
 double dev_small_fraction(DevCtx &c, const Fr *z, size_t n) {
     if (!n) return 0.0;
-    OTTI_HIP(hipMemsetAsync(c.d_counts.p, 0, sizeof(unsigned long long), c.stream));
-    hipLaunchKernelGGL(k_count_small, grid_for(n), kBlock, 0, c.stream, z, n, c.d_counts.p);
-    unsigned long long h = 0;
-    OTTI_HIP(hipMemcpyAsync(&h, c.d_counts.p, sizeof h, hipMemcpyDeviceToHost, c.stream));
-    OTTI_HIP(hipStreamSynchronize(c.stream));
-    return (double)h / (double)n;
+    const Tallies t = counted_launch(c, [&](unsigned long long *count) { hipLaunchKernelGGL(k_count_small, grid_for(n), kBlock, 0, c.stream, z, n, count); });
+    return (double)t.first / (double)n;
 }
 // OTTI_MSM_STAMPS=1: phase stamps of every fused small launch on stderr (development aid; synchronises the stream)
 static void msm_report_stamps(DevCtx &c, const unsigned long long *t, const MsmJob &j, const MsmPlan &p, bool bullet) {

@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <chrono>
 #include <mutex>
+#include <type_traits>
 
 namespace otti {
 
@@ -18,6 +19,19 @@ constexpr int kBlock = 256;
 constexpr int kHeavyRow = 64;              // sparse rows longer than this go to the one-workgroup-per-row kernel
 
 static inline int grid_for(size_t n) { size_t b = (n + kBlock - 1) / kBlock; return (int)std::max<size_t>(1, std::min<size_t>(b, kMaxBlocks)); }
+
+// ------------------------------------------------------------------------------------------------ counted launches
+// The kernels that count (non-canonical / small scalars, bad indices) add to the context's two tallies (DevCtx::d_counts).  One counted launch:
+// both tallies zeroed, launch(counts) queues the kernel on c.stream, both read back through one synchronise.
+struct Tallies { unsigned long long first = 0, second = 0; };
+template <class Launch> static inline Tallies counted_launch(DevCtx &c, Launch launch) {
+    OTTI_HIP(hipMemsetAsync(c.d_counts.p, 0, 2 * sizeof(unsigned long long), c.stream));
+    launch(c.d_counts.p);
+    unsigned long long h[2] = {0, 0};
+    OTTI_HIP(hipMemcpyAsync(h, c.d_counts.p, sizeof h, hipMemcpyDeviceToHost, c.stream));
+    OTTI_HIP(hipStreamSynchronize(c.stream));
+    return {h[0], h[1]};
+}
 
 // ------------------------------------------------------------------------------------------------ inter-workgroup hand-off
 // Publishing a workgroup's partial result to the LAST workgroup of the same launch.  A per-workgroup agent release fence

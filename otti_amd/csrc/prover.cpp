@@ -127,42 +127,14 @@ static const bool g_hook_registered = [] {
     return true;
 }();
 
-DeviceWitness::DeviceWitness(const Instance &I, const std::vector<Fr> &vars_padded, const std::vector<Fr> &inputs_) : inputs(inputs_) {
-    DevCtx &c = DevCtx::get();
-    if (vars_padded.size() != I.num_vars) throw Error(OTTI_ERR_INVALID_NUM_VARS, "witness length != padded num_vars");
-    z.alloc(2 * I.num_vars);
-    // z = vars || 1 || inputs || 0...   (r1csproof.rs: "append input to variables to create a single vector z")
-    std::vector<Fr> tail(I.num_vars, fr_zero());
-    tail[0] = fr_one();
-    for (size_t i = 0; i < inputs.size(); i++) tail[1 + i] = inputs[i];
-    OTTI_HIP(hipMemcpyAsync(z.p, vars_padded.data(), I.num_vars * sizeof(Fr), hipMemcpyHostToDevice, c.stream));
-    OTTI_HIP(hipMemcpyAsync(z.p + I.num_vars, tail.data(), I.num_vars * sizeof(Fr), hipMemcpyHostToDevice, c.stream));
-    c.sync();
-    small_fraction = dev_small_fraction(c, z.p, I.num_vars);
-}
-
-DeviceWitness::DeviceWitness(const Instance &I, const uint8_t *vars32, size_t nvars, const std::vector<Fr> &inputs_) : inputs(inputs_) {
-    DevCtx &c = DevCtx::get();
-    const size_t V = I.num_vars;
-    if (nvars > V) throw Error(OTTI_ERR_INVALID_NUM_VARS, "more variables than the instance has");
-    if (inputs.size() != I.num_inputs) throw Error(OTTI_ERR_INVALID_NUM_INPUTS, "wrong number of inputs");
-    z.alloc(2 * V);
-    OTTI_HIP(hipMemsetAsync(z.p, 0, 2 * V * sizeof(Fr), c.stream));
-    if (nvars) OTTI_HIP(hipMemcpyAsync(z.p, vars32, nvars * 32, hipMemcpyHostToDevice, c.stream));
-    std::vector<Fr> tail(1 + inputs.size()); tail[0] = fr_one();
-    for (size_t i = 0; i < inputs.size(); i++) tail[1 + i] = inputs[i];
-    OTTI_HIP(hipMemcpyAsync(z.p + V, tail.data(), tail.size() * sizeof(Fr), hipMemcpyHostToDevice, c.stream));
-    size_t n_small = 0;
-    if (dev_witness_ingest(c, z.p, nvars, &n_small)) throw Error(OTTI_ERR_INVALID_SCALAR, "non-canonical scalar in assignment");   // synchronises: `tail` and the caller's buffer are free again
-    small_fraction = V ? (double)(n_small + (V - nvars)) / (double)V : 0.0;        // the padding zeros count as small
-}
-
 namespace {
 // Where dev_witness_ingest_from reads a source: a device source as it is, once the context's stream waits for the producer's queued work (an event
-// recorded there, as the otti_kd_* calls order a caller's stream against the context's own); a host source through a staging copy of its span.
+// recorded there, as the otti_kd_* calls order a caller's stream against the context's own); a host source from a copy on the device — packed
+// 32-byte words straight in `dst` when the caller names one (they are converted in place there: no staging allocation), anything else in a
+// staging copy of its span.
 struct WitSource {
     DevBuf<uint8_t> staged; const void *p = nullptr; size_t stride = 0;
-    WitSource(DevCtx &c, int format, const void *src, size_t n, size_t stride_, bool on_device, hipStream_t producer) {
+    WitSource(DevCtx &c, int format, const void *src, size_t n, size_t stride_, bool on_device, hipStream_t producer, Fr *dst) {
         const size_t eb = wit_elem_bytes(format);
         stride = stride_ ? stride_ : eb; p = src;
         if (!n) return;
@@ -174,29 +146,37 @@ struct WitSource {
             return;
         }
         const size_t span = (n - 1) * stride + eb;
-        staged.alloc(span); p = staged.p;
-        OTTI_HIP(hipMemcpyAsync(staged.p, src, span, hipMemcpyHostToDevice, c.stream));
+        if (dst && eb == sizeof(Fr) && stride == eb) p = dst;
+        else { staged.alloc(span); p = staged.p; }
+        OTTI_HIP(hipMemcpyAsync(const_cast<void *>(p), src, span, hipMemcpyHostToDevice, c.stream));
     }
 };
 }  // namespace
 
-DeviceWitness::DeviceWitness(const Instance &I, int format, const void *src, size_t nvars, size_t stride, bool src_on_device, hipStream_t producer,
-                             const std::vector<Fr> &inputs_) : inputs(inputs_) {
-    DevCtx &c = DevCtx::get();
+std::vector<Fr> DeviceWitness::set_up(DevCtx &c, const Instance &I, size_t nvars) {
     const size_t V = I.num_vars;
     if (nvars > V) throw Error(OTTI_ERR_INVALID_NUM_VARS, "more variables than the instance has");
     if (inputs.size() != I.num_inputs) throw Error(OTTI_ERR_INVALID_NUM_INPUTS, "wrong number of inputs");
     z.alloc(2 * V);
     OTTI_HIP(hipMemsetAsync(z.p, 0, 2 * V * sizeof(Fr), c.stream));
+    // z = vars || 1 || inputs || 0...   (r1csproof.rs: "append input to variables to create a single vector z")
     std::vector<Fr> tail(1 + inputs.size()); tail[0] = fr_one();
     for (size_t i = 0; i < inputs.size(); i++) tail[1 + i] = inputs[i];
     OTTI_HIP(hipMemcpyAsync(z.p + V, tail.data(), tail.size() * sizeof(Fr), hipMemcpyHostToDevice, c.stream));
-    WitSource s(c, format, src, nvars, stride, src_on_device, producer);
+    return tail;
+}
+
+DeviceWitness::DeviceWitness(const Instance &I, int format, const void *src, size_t nvars, size_t stride, bool src_on_device, hipStream_t producer,
+                             const std::vector<Fr> &inputs_) : inputs(inputs_) {
+    DevCtx &c = DevCtx::get();
+    const size_t V = I.num_vars;
+    const std::vector<Fr> tail = set_up(c, I, nvars);
+    WitSource s(c, format, src, nvars, stride, src_on_device, producer, z.p);    // a fresh z may be written before the check: a refusal throws it away
     size_t n_small = 0;
     const size_t bad = dev_witness_ingest_from(c, format, s.p, s.stride, nvars, z.p, 0, &n_small);   // synchronises: `tail`, the staging copy and the caller's buffer are free again
     if (!nvars) OTTI_HIP(hipStreamSynchronize(c.stream));
     if (bad) throw Error(OTTI_ERR_INVALID_SCALAR, "non-canonical scalar in assignment");
-    small_fraction = V ? (double)(n_small + (V - nvars)) / (double)V : 0.0;
+    small_fraction = V ? (double)(n_small + (V - nvars)) / (double)V : 0.0;        // the padding zeros count as small
 }
 
 static void resum_rows(DevCtx &c, DeviceWitness &w, size_t r0, size_t r1);
@@ -205,11 +185,13 @@ void DeviceWitness::update(size_t first, int format, const void *src, size_t cou
     const size_t V = z.n / 2;
     if (first > V || count > V - first) throw Error(OTTI_ERR_INVALID_NUM_VARS, "the range ends beyond the instance's variables");
     if (!count) return;
-    WitSource s(c, format, src, count, stride, src_on_device, producer);
-    DevBuf<Fr> conv;                                              // outlives the copy out of it: freed after dev_small_fraction has synchronised
-    if (format == WIT_I64 || format == WIT_U64) dev_witness_ingest_from(c, format, s.p, s.stride, count, z.p, first);   // every integer is a scalar: straight into place
+    // every integer is a scalar: straight into place.  A 32-byte range is converted in `conv` (a packed host one is copied there and converted
+    // in place), and z is written only once the whole range has passed the check
+    const bool ints = format == WIT_I64 || format == WIT_U64;
+    DevBuf<Fr> conv(ints ? 0 : count);                            // outlives the copy out of it: freed after dev_small_fraction has synchronised
+    WitSource s(c, format, src, count, stride, src_on_device, producer, conv.p);
+    if (ints) dev_witness_ingest_from(c, format, s.p, s.stride, count, z.p, first);
     else {
-        conv.alloc(count);                                        // z is written only once the whole range has passed the check
         if (dev_witness_ingest_from(c, format, s.p, s.stride, count, conv.p, 0)) throw Error(OTTI_ERR_INVALID_SCALAR, "non-canonical scalar in the update: the witness is unchanged");
         OTTI_HIP(hipMemcpyAsync(z.p + first, conv.p, count * sizeof(Fr), hipMemcpyDeviceToDevice, c.stream));
     }
@@ -243,13 +225,13 @@ void DeviceWitness::scatter(const uint64_t *idx, int format, const void *src, si
     const size_t V = z.n / 2;
     if (count > V) throw Error(OTTI_ERR_INVALID_INDEX, "more indices than the instance has variables");
     if (!count) return;
-    WitSource s(c, format, src, count, stride, on_device, producer);      // a device source: the one event orders the producer of both lists
+    DevBuf<Fr> conv(count), delta;                                // outlive the launches that read them: freed after dev_small_fraction has synchronised
+    WitSource s(c, format, src, count, stride, on_device, producer, conv.p);   // a device source: the one event orders the producer of both lists
     DevBuf<uint64_t> idx_staged; const uint64_t *d_idx = idx;
     if (!on_device) {
         idx_staged.alloc(count); d_idx = idx_staged.p;
         OTTI_HIP(hipMemcpyAsync(idx_staged.p, idx, count * sizeof(uint64_t), hipMemcpyHostToDevice, c.stream));
     }
-    DevBuf<Fr> conv(count), delta;                                // outlive the launches that read them: freed after dev_small_fraction has synchronised
     const bool patch = rows_kept.p != nullptr;
     if (patch) delta.alloc(count);
     size_t bad_scalars = 0, bad_indices = 0;
@@ -856,12 +838,6 @@ std::vector<uint8_t> nizk_prove_resident(Instance &I, DeviceWitness &wit, Gens &
     KStats::get().flush();
     if (tm) *tm = T;
     return out;
-}
-
-std::vector<uint8_t> nizk_prove_gpu(Instance &I, const std::vector<Fr> &vars_padded, const std::vector<Fr> &inputs, Gens &g,
-                                    const void *tlabel, size_t tlabel_len, const uint8_t *seed32, ProveTimings *tm) {
-    DeviceWitness w(I, vars_padded, inputs);
-    return nizk_prove_resident(I, w, g, tlabel, tlabel_len, seed32, tm);
 }
 
 }  // namespace otti

@@ -151,8 +151,6 @@ int nizk_verify(const Instance &inst, const std::vector<Fr> &inputs, const Gens 
 
 // ---------------------------------------------------------------------------------------------- prover (prover.cpp; GPU)
 struct ProveTimings { double ms[8]; };   // polycommit, multiply_vec, sc_phase_one, eval_table_sparse, sc_phase_two, polyeval, total, (spare)
-std::vector<uint8_t> nizk_prove_gpu(Instance &inst, const std::vector<Fr> &vars_padded, const std::vector<Fr> &inputs, Gens &g,
-                                    const void *tlabel, size_t tlabel_len, const uint8_t *seed32, ProveTimings *tm);
 
 // synthetic satisfiable instance of SURVEY.md section 8(d)
 void synth_r1cs(size_t n, size_t num_inputs, uint64_t seed, std::vector<otti_entry> &A, std::vector<otti_entry> &B,

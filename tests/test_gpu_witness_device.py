@@ -1,9 +1,12 @@
-"""A resident witness filled from device memory, from host integers, and updated in place (otti_witness_from_device, otti_witness_upload_ints,
-otti_witness_update, otti_witness_info) against what a host upload of the same values gives.
+"""A resident witness filled from host bytes, from device memory, from host integers, and updated in place (otti_witness_upload,
+otti_witness_from_device, otti_witness_upload_ints, otti_witness_update, otti_witness_info).
 
-The reference for z is never the code under test: it is the z of `oa.Witness` (otti_witness_upload) built from the values as canonical bytes
-computed with Python integers mod l, or `oa.fr_from_ints` of those integers; whole proofs are compared with the CPU oracle's.  Bit-exact
-throughout: the arithmetic is in GF(l)."""
+The reference for z is Python integers: z[:V + 1 + ni] is `oa.fr_from_ints` (pure Python, x * R mod l) of the values padded with zeros, then 1,
+then the inputs; the rest of z is zero; small_fraction is sum(x % l < 2^128 over the padded values) / V, compared with == (both sides are one
+correctly rounded division of integers below 2^53).  Every source is judged against that, the host upload included: it shares the ingest kernel
+with the other sources, so it is no independent reference.  The comparison with a host upload of the same values stays as a second check (the
+promise of the C ABI is "bit for bit what otti_witness_upload builds").  Whole proofs are compared with the CPU oracle's.  Bit-exact throughout:
+the arithmetic is in GF(l)."""
 import ctypes
 
 import numpy as np
@@ -11,7 +14,8 @@ import pytest
 
 import otti_amd as oa
 import orc
-from witness_tensor_worker import bytes32, int_r1cs
+from witness_cases import Dev, bytes32, z_of
+from witness_tensor_worker import int_r1cs
 
 pytestmark = pytest.mark.gpu
 L = orc.L_ORDER
@@ -35,17 +39,6 @@ def _pinned_window(monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------------ helpers
-class Dev:
-    """raw bytes in device memory"""
-
-    def __init__(self, a):
-        a = np.ascontiguousarray(a)
-        self.arr = oa.DeviceArray(max(a.nbytes, 8), 1)
-        if a.nbytes:
-            assert oa.lib.otti_dev_upload(self.arr.ptr, a.ctypes.data_as(_vp), a.nbytes) == 0
-        self.addr = self.arr.ptr.value
-
-
 def from_dev(inst, a, n, fmt, inputs, offset=0, **kw):
     d = Dev(a)                                                 # alive until the call has returned: the ingest has finished by then
     return oa.Witness.from_device(inst, d.addr + offset, n, fmt, inputs, **kw)
@@ -63,13 +56,6 @@ def bare_instance(nv, ni=2):
     return oa.Instance.new(2, nv, ni, e, e, e), oa.InputsAssignment.new(bytes32([11, L - 3][:ni]))
 
 
-def z_of(wit):
-    p, n, sf = wit.info
-    out = np.zeros((n, 32), dtype=np.uint8)
-    assert oa.lib.otti_dev_download(out.ctypes.data_as(_vp), p, out.nbytes) == 0
-    return out, sf
-
-
 def host_witness(inst, inputs, ints):
     return oa.Witness(inst, oa.VarsAssignment.new(bytes32(ints)), inputs)
 
@@ -81,6 +67,11 @@ def source(fmt, ints):
     if fmt == M32:
         return oa.fr_from_ints([int(x) % L for x in ints])
     return np.array([int(x) for x in ints], dtype=np.int64 if fmt == I64 else np.uint64)
+
+
+def ints_of(a):
+    """the integers of (n, 32) canonical little-endian bytes"""
+    return [int.from_bytes(bytes(row), "little") for row in a]
 
 
 def values_for(fmt, n, rng):
@@ -97,7 +88,26 @@ def values_for(fmt, n, rng):
     return out
 
 
-def assert_same(wit, ref, what):
+INPUTS = [11, L - 3]                                           # bare_instance's
+
+
+def assert_z(wit, ints, what, nv=V, inputs=INPUTS):
+    """z and small_fraction of wit against Python integers: the variables `ints`, padded with zeros to nv"""
+    z, sf = z_of(wit)
+    padded = [int(x) % L for x in ints] + [0] * (nv - len(ints))
+    head = padded + [1] + [int(x) % L for x in inputs]
+    assert z.shape == (2 * nv, 32), what
+    assert np.array_equal(z[:len(head)], oa.fr_from_ints(head)), what
+    assert not z[len(head):].any(), what
+    want = sum(x < 2 ** 128 for x in padded) / nv
+    print(f"{what}: small_fraction {sf} (Python integers {want})")
+    assert sf == want, what
+
+
+def assert_same(wit, ref, what, ints=None, **kw):
+    """the Python integers first (ints=None: the caller anchors z itself), then a host upload of the same values as a second check"""
+    if ints is not None:
+        assert_z(wit, ints, what, **kw)
     (z, sf), (zr, sfr) = z_of(wit), z_of(ref)
     print(f"{what}: small_fraction {sf} (host upload {sfr})")
     assert z.shape == zr.shape and np.array_equal(z, zr), what
@@ -109,22 +119,50 @@ def small():
     return bare_instance(V)
 
 
-# ------------------------------------------------------------------------------------------------ same z as a host upload
+# ------------------------------------------------------------------------------------------------ the host upload, a source like the others
+NVARS = (0, 1, 63, 64, 65, 255, V - 1, V)
+
+
+def test_host_upload_is_the_python_integers(small, rng):
+    inst, inputs = small
+    for nvars in NVARS:
+        ints = values_for(C32, nvars, rng)
+        assert_z(host_witness(inst, inputs, ints), ints, f"host upload nvars={nvars}")
+
+
+def test_host_upload_refuses_scalars_not_below_l(small, rng):
+    inst, inputs = small
+    ip = np.ascontiguousarray(inputs.assignment)
+    for nvars, k in ((V, 0), (V, V - 1), (65, 64)):
+        ints = values_for(C32, nvars, rng)
+        for raw, ok in ((L, False), (L + 1, False), (2 ** 256 - 1, False), (L - 1, True)):
+            src = bytes32(ints)
+            src[k] = np.frombuffer(raw.to_bytes(32, "little"), dtype=np.uint8)
+            out = _vp(SENTINEL)
+            rc = oa.lib.otti_witness_upload(inst._h, src.ctypes.data_as(_vp), nvars, ip.ctypes.data_as(_vp), ip.shape[0], ctypes.byref(out))
+            if not ok:
+                assert rc == INVALID_SCALAR and out.value == SENTINEL, (nvars, k, hex(raw), rc)
+                continue
+            assert rc == 0 and out.value != SENTINEL, (nvars, k, rc)
+            wit = oa.Witness._adopt(out)
+            assert np.array_equal(z_of(wit)[0][k], np.frombuffer((raw * R % L).to_bytes(32, "little"), dtype=np.uint8))
+            assert_z(wit, ints[:k] + [raw] + ints[k + 1:], f"host upload of l - 1 at {k} of {nvars}")
+
+
+# ------------------------------------------------------------------------------------------------ same z as the Python integers and as a host upload
 @pytest.mark.parametrize("name", list(FORMATS))
 def test_same_z_as_host_upload(small, rng, name):
     inst, inputs = small
     fmt = FORMATS[name]
-    for nvars in (0, 1, 63, 64, 65, 255, V - 1, V):
+    for nvars in NVARS:
         ints = values_for(fmt, nvars, rng)
         src = source(fmt, ints)
         ref = host_witness(inst, inputs, ints)
+        assert_z(ref, ints, f"{name} nvars={nvars} host upload")
         d = Dev(src)
-        assert_same(oa.Witness.from_device(inst, d.addr, nvars, fmt, inputs), ref, f"{name} nvars={nvars} from_device")
+        assert_same(oa.Witness.from_device(inst, d.addr, nvars, fmt, inputs), ref, f"{name} nvars={nvars} from_device", ints)
         if fmt in (I64, U64):
-            assert_same(oa.Witness.from_ints(inst, src, inputs), ref, f"{name} nvars={nvars} from_ints")
-        if nvars:
-            ref_ints = (ints + [0] * V)[:V] + [1] + [11, L - 3]
-            assert np.array_equal(z_of(ref)[0][:V + 3], oa.fr_from_ints([x % L for x in ref_ints]))   # the reference is what this file says it is
+            assert_same(oa.Witness.from_ints(inst, src, inputs), ref, f"{name} nvars={nvars} from_ints", ints)
 
 
 def test_grid_stride_loop_at_2p20(rng):
@@ -137,6 +175,10 @@ def test_grid_stride_loop_at_2p20(rng):
     canon[:, :8] = np.where(x < 0, 0, x).astype("<i8").view(np.uint8).reshape(n, 8)
     canon[neg] = bytes32([int(v) for v in x[neg]])
     ref = oa.Witness(inst, oa.VarsAssignment.new(canon), inputs)
+    zr = z_of(ref)[0]                                          # the host upload against Python integers on a sample: the edges of the first pass, every negated index, 4096 more
+    sample = np.unique(np.concatenate([neg, rng.integers(0, n, size=4096)]))
+    assert np.array_equal(zr[sample], oa.fr_from_ints([int(v) for v in x[sample]]))
+    assert np.array_equal(zr[n:n + 3], oa.fr_from_ints([1] + INPUTS)) and not zr[n + 3:].any()
     assert_same(from_dev(inst, x, n, I64, inputs), ref, "2^20 packed i64 from_device")
     assert_same(oa.Witness.from_ints(inst, x, inputs), ref, "2^20 from_ints")
     assert z_of(ref)[1] == (n - len(neg)) / n
@@ -169,25 +211,26 @@ def test_strides(small, rng):
     n = 200
     table = rng.integers(I64_MIN, I64_MAX, size=(n, 3), dtype=np.int64, endpoint=True)       # row-major: column 1 is 24 bytes apart
     d = Dev(table)
-    ref = host_witness(inst, inputs, [int(x) for x in table[:, 1]])
-    assert_same(oa.Witness.from_device(inst, d.addr + 8, n, I64, inputs, stride_bytes=24), ref, "column 1 of (n, 3) int64")
+    col = [int(x) for x in table[:, 1]]
+    ref = host_witness(inst, inputs, col)
+    assert_same(oa.Witness.from_device(inst, d.addr + 8, n, I64, inputs, stride_bytes=24), ref, "column 1 of (n, 3) int64", col)
     ints = values_for(C32, n, rng)
     wide = np.full((n, 64), 0xff, dtype=np.uint8)
     wide[:, :32] = bytes32(ints)
     ref = host_witness(inst, inputs, ints)
-    assert_same(from_dev(inst, wide, n, C32, inputs, stride_bytes=64), ref, "canonical32 stride 64")
+    assert_same(from_dev(inst, wide, n, C32, inputs, stride_bytes=64), ref, "canonical32 stride 64", ints)
     wide40 = np.full((n, 40), 0xff, dtype=np.uint8)              # a stride that rules the 16-byte loads out
     wide40[:, :32] = bytes32(ints)
-    assert_same(from_dev(inst, wide40, n, C32, inputs, stride_bytes=40), ref, "canonical32 stride 40")
+    assert_same(from_dev(inst, wide40, n, C32, inputs, stride_bytes=40), ref, "canonical32 stride 40", ints)
     mont = np.zeros((n, 96), dtype=np.uint8)
     mont[:, :32] = source(M32, ints)
-    assert_same(from_dev(inst, mont, n, M32, inputs, stride_bytes=96), ref, "montgomery32 stride 96")
+    assert_same(from_dev(inst, mont, n, M32, inputs, stride_bytes=96), ref, "montgomery32 stride 96", ints)
     for fmt in (C32, M32, I64, U64):                             # stride 0 is the packed size
         vals = values_for(fmt, n, rng)
         d = Dev(source(fmt, vals))
         packed = 8 if fmt in (I64, U64) else 32
-        assert_same(oa.Witness.from_device(inst, d.addr, n, fmt, inputs, stride_bytes=packed), oa.Witness.from_device(inst, d.addr, n, fmt, inputs, stride_bytes=0), f"stride 0, format {fmt}")
-        assert_same(oa.Witness.from_device(inst, d.addr, n, fmt, inputs), host_witness(inst, inputs, vals), f"packed, format {fmt}")
+        assert_same(oa.Witness.from_device(inst, d.addr, n, fmt, inputs, stride_bytes=packed), oa.Witness.from_device(inst, d.addr, n, fmt, inputs, stride_bytes=0), f"stride 0, format {fmt}", vals)
+        assert_same(oa.Witness.from_device(inst, d.addr, n, fmt, inputs), host_witness(inst, inputs, vals), f"packed, format {fmt}", vals)
 
 
 # ------------------------------------------------------------------------------------------------ validation
@@ -253,7 +296,7 @@ def test_update_equals_a_fresh_upload(small, rng, name, where):
         else:
             update_dev(wit, inst, first, src, count, fmt)
         cur[first:first + count] = [x % L for x in new]
-        assert_same(wit, host_witness(inst, inputs, cur), f"{name} from {where} [{first}, {first + count})")
+        assert_same(wit, host_witness(inst, inputs, cur), f"{name} from {where} [{first}, {first + count})", cur)
 
 
 def test_update_from_a_strided_device_source(small, rng):
@@ -263,7 +306,7 @@ def test_update_from_a_strided_device_source(small, rng):
     table = rng.integers(I64_MIN, I64_MAX, size=(40, 3), dtype=np.int64, endpoint=True)
     update_dev(wit, inst, 100, table, 40, I64, offset=16, stride_bytes=24)
     cur[100:140] = [int(x) % L for x in table[:, 2]]
-    assert_same(wit, host_witness(inst, inputs, cur), "column 2 of (40, 3) int64 into [100, 140)")
+    assert_same(wit, host_witness(inst, inputs, cur), "column 2 of (40, 3) int64 into [100, 140)", cur)
 
 
 @pytest.mark.parametrize("where", ["host", "device"])
@@ -341,7 +384,7 @@ def test_compiler_like_witness_takes_the_sparse_commitment():
     inputs = oa.InputsAssignment.new(r["inputs"])
     wit = from_dev(inst, r["vars"], n, C32, inputs)
     ref = oa.Witness(inst, oa.VarsAssignment.new(r["vars"]), inputs)
-    assert_same(wit, ref, "compiler-like 2^16")
+    assert_same(wit, ref, "compiler-like 2^16", ints_of(r["vars"]), nv=n, inputs=ints_of(r["inputs"]))
     assert wit.info[2] > 0.25
     want, _ = orc.nizk_prove(oinst, r["vars"], r["inputs"], ogens, LABEL, SEED)
     assert oa.NIZK.prove(inst, wit, None, gens, LABEL, SEED).bytes == want
