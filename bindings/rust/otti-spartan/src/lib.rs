@@ -35,6 +35,14 @@ extern "C" {
     fn otti_witness_scatter(inst: *mut OttiInstance, wit: *mut OttiWitness, idx: *const u64, src: *const core::ffi::c_void, count: usize, format: i32,
                             stride_bytes: usize, on_device: i32, stream: *mut core::ffi::c_void) -> i32;
     fn otti_witness_set_inputs(inst: *mut OttiInstance, wit: *mut OttiWitness, inputs32: *const u8, ninputs: usize) -> i32;
+    // a resident witness set from a whole new vector: compared on the device, only the changed elements written, kept rows patched by them
+    // (or the touched rows summed again); the dry form; the counters
+    fn otti_witness_assign(inst: *mut OttiInstance, wit: *mut OttiWitness, first: usize, src: *const core::ffi::c_void, count: usize, format: i32,
+                           stride_bytes: usize, src_on_device: i32, stream: *mut core::ffi::c_void, n_changed: *mut u64) -> i32;
+    fn otti_witness_diff(inst: *mut OttiInstance, wit: *const OttiWitness, first: usize, src: *const core::ffi::c_void, count: usize, format: i32,
+                         stride_bytes: usize, src_on_device: i32, stream: *mut core::ffi::c_void, n_changed: *mut u64, idx: *mut u64,
+                         idx_cap: usize) -> i32;
+    fn otti_witness_assign_info(wit: *const OttiWitness, calls: *mut u64, changed: *mut u64, resums: *mut u64) -> i32;
     // SNARK mode (upstream spartan-zkinterface without --nizk)
     fn otti_snark_gens_new(num_cons: u64, num_vars: u64, num_inputs: u64, num_nz_entries: u64, out: *mut *mut OttiSnarkGens) -> i32;
     fn otti_snark_gens_free(gens: *mut OttiSnarkGens);

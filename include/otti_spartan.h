@@ -248,6 +248,36 @@ int32_t otti_witness_scatter(otti_instance *inst, otti_witness *wit, const uint6
    summed into kept rows; the last two move only while rows are kept.  Any out pointer may be NULL.  A null wit is OTTI_ERR_BAD_ARG; without a
    device no witness exists: OTTI_ERR_NO_DEVICE, wit is not looked at. */
 int32_t otti_witness_scatter_info(const otti_witness *wit, uint64_t *calls, uint64_t *rows_patched, uint64_t *terms_patched);
+/* ---- assign: variables [first, first + count) of a resident witness set from a WHOLE new vector (src, format, stride_bytes, src_on_device and
+   stream as otti_witness_update), of which most elements usually have not moved: what an optimiser, an SGD loop or a re-run compiler emits each
+   step.  The library compares the vector with the resident one on the device, by VALUE (-5 as an integer, l - 5 as canonical bytes and the resident
+   Montgomery word are the same value), writes only the elements that changed and reports their number in *n_changed (may be NULL).  Afterwards z is
+   bit for bit what otti_witness_upload builds from the new values and small_fraction is counted again in one pass: equal to a fresh upload's, so
+   proofs are byte-identical.  Kept rows are brought up to date by the changes alone: PATCHED as otti_witness_scatter patches them by the same
+   (index, new - old) list (rows_patched and terms_patched of otti_witness_scatter_info move as that scatter would move them; its calls do not), or,
+   when so much changed that summing the touched rows again is cheaper (profiles/witness_assign.md; OTTI_ASSIGN_RESUM_SHARE, a share of the touched
+   rows' elements read per call, overrides the rule: 0 always sums again, >= 1 never), rows idx_min / R .. idx_max / R are summed again as
+   otti_witness_update sums them (rows_resummed of otti_witness_rows_info moves by their number).
+   Refusals, in otti_witness_update's order: OTTI_ERR_BAD_ARG before any device is touched (a null inst / wit, a null src with a non-zero count, an
+   unknown format, a bad stride_bytes, a misaligned device pointer); OTTI_ERR_INVALID_NUM_VARS for a range beyond the padded num_vars;
+   OTTI_ERR_NO_DEVICE; OTTI_ERR_INVALID_NUM_VARS for a witness of other dimensions; then, found on the device, OTTI_ERR_INVALID_SCALAR for a scalar
+   >= l.  A refused call changes nothing: z, small_fraction, the kept rows and every counter stay as they were.  count == 0: OTTI_OK, *n_changed = 0,
+   no counter moved; nothing changed: OTTI_OK, *n_changed = 0, nothing written, recounted or launched beyond the comparison.
+   A device source must not overlap the witness's own vector (d_z of otti_witness_info).  Never while a proof or check with this witness is running.
+   Sharded provers call it on every rank (their proofs ignore kept rows as before).  If the kept rows cannot be brought up to date because the
+   generators' table has to be rebuilt and HBM is short, the error is returned with z updated and the kept rows dropped, as by otti_witness_scatter. */
+int32_t otti_witness_assign(otti_instance *inst, otti_witness *wit, size_t first, const void *src, size_t count, int32_t format,
+                            size_t stride_bytes, int32_t src_on_device, void *stream, uint64_t *n_changed);
+/* the dry form of otti_witness_assign: *n_changed = the number of elements it would change, and idx[0 .. min(*n_changed, idx_cap)) the lowest of
+   their indices, ascending (idx_cap == 0: the count alone, idx may be NULL).  Writes nothing to the witness and moves no counter; it only reads the
+   handles, so it may run wherever otti_witness_check_sat may.  Refusals as above, and OTTI_ERR_BAD_ARG also for a null n_changed or idx_cap > 0
+   with a null idx. */
+int32_t otti_witness_diff(otti_instance *inst, const otti_witness *wit, size_t first, const void *src, size_t count, int32_t format,
+                          size_t stride_bytes, int32_t src_on_device, void *stream, uint64_t *n_changed, uint64_t *idx, size_t idx_cap);
+/* since the witness was made: otti_witness_assign calls that were not refused (count > 0), elements they changed, and calls that summed kept rows
+   again instead of patching them.  Any out pointer may be NULL.  A null wit is OTTI_ERR_BAD_ARG; without a device no witness exists:
+   OTTI_ERR_NO_DEVICE, wit is not looked at. */
+int32_t otti_witness_assign_info(const otti_witness *wit, uint64_t *calls, uint64_t *changed, uint64_t *resums);
 /* replaces the public inputs of a resident witness (z[V + 1 .. V + 1 + ninputs), V the padded num_vars, and the host copy the transcript reads).
    Kept rows cover the variables alone and are untouched, as are small_fraction (it counts the variables) and every counter.
    OTTI_ERR_BAD_ARG: a null handle, or null inputs32 with ninputs > 0; OTTI_ERR_INVALID_NUM_INPUTS: ninputs differs from the instance's;
@@ -353,6 +383,12 @@ int32_t otti_k_msm_rows(otti_gens *gens, const uint8_t *h_Z, size_t L, size_t R,
    R = the generators' row length; idx strictly ascending below L*R (else OTTI_ERR_INVALID_INDEX), s Montgomery.  A row without terms is the identity. */
 int32_t otti_k_msm_scatter_rows(otti_gens *gens, size_t L, const uint64_t *h_idx, const uint8_t *h_s, size_t count,
                                 uint8_t *h_out32, float *kernel_ms);
+/* the two passes of otti_witness_assign on a staged vector: h_old = n Montgomery elements, h_src = n elements in `format`, stride_bytes apart
+   (0: packed).  h_new = the vector afterwards; h_idx = the ascending indices of the elements whose value changed and h_delta = new - old for each
+   (room for n each, *n_changed filled); *chunk (may be NULL) = elements per workgroup chunk of the passes.  A scalar >= l: OTTI_ERR_INVALID_SCALAR,
+   outputs untouched. */
+int32_t otti_k_witness_diff(const uint8_t *h_old, size_t n, const void *h_src, int32_t format, size_t stride_bytes, uint8_t *h_new,
+                            uint64_t *h_idx, uint8_t *h_delta, uint64_t *n_changed, uint32_t *chunk, float *kernel_ms);
 /* PolyEvalProof::verify's C_LZ on the device [dense_mlpoly.rs PolyEvalProof::verify -> GroupElement::vartime_multiscalar_mul, RECALL]:
    out = compress(sum_i s[i] * decompress(C[i])), n >= 256 compressed ristretto255 points, scalars in Montgomery form.  Batch decompression,
    LDS-bucket Pippenger, window recombination on the host.  OTTI_ERR_VERIFY_DECOMPRESS if an encoding does not decode. */

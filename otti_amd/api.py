@@ -91,6 +91,9 @@ _sig("otti_witness_upload_ints", _i32, _vp, _vp, _sz, _i32, _vp, _sz, ctypes.POI
 _sig("otti_witness_update", _i32, _vp, _vp, _sz, _vp, _sz, _i32, _sz, _i32, _vp)
 _sig("otti_witness_scatter", _i32, _vp, _vp, _vp, _vp, _sz, _i32, _sz, _i32, _vp)
 _sig("otti_witness_scatter_info", _i32, _vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64))
+_sig("otti_witness_assign", _i32, _vp, _vp, _sz, _vp, _sz, _i32, _sz, _i32, _vp, ctypes.POINTER(_u64))
+_sig("otti_witness_diff", _i32, _vp, _vp, _sz, _vp, _sz, _i32, _sz, _i32, _vp, ctypes.POINTER(_u64), _vp, _sz)
+_sig("otti_witness_assign_info", _i32, _vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64))
 _sig("otti_witness_set_inputs", _i32, _vp, _vp, _vp, _sz)
 _sig("otti_witness_info", _i32, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_sz), ctypes.POINTER(ctypes.c_double))
 _sig("otti_witness_keep_rows", _i32, _vp, _vp, _vp)
@@ -157,6 +160,7 @@ _sig("otti_k_armed_selftest", _i32, _vp, _vp, _sz, _vp, ctypes.c_uint32, _vp, _v
 _sig("otti_k_msm_rows", _i32, _vp, _vp, _sz, _sz, _vp, _vp, _fp)
 _sig("otti_k_row_sum", _i32, _vp, _sz, _vp, _vp)
 _sig("otti_k_msm_scatter_rows", _i32, _vp, _sz, _vp, _vp, _sz, _vp, _fp)
+_sig("otti_k_witness_diff", _i32, _vp, _sz, _vp, _i32, _sz, _vp, _vp, _vp, ctypes.POINTER(_u64), ctypes.POINTER(ctypes.c_uint32), _fp)
 _sig("otti_k_eq_pyramid", _i32, _vp, _sz, _vp)
 _sig("otti_k_sc_cubic3_round", _i32, _vp, _vp, _vp, _sz, _vp, _vp, _fp)
 _sig("otti_k_sc_cubic3_fold_round", _i32, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _fp)
@@ -508,28 +512,51 @@ class Witness:
         fmt, nvars, stride = _tensor_layout(torch, tensor)
         return cls.from_device(inst, tensor.data_ptr(), nvars, fmt, inputs, stride, _torch_stream(torch, tensor, stream))
 
+    def _source(self, values, fmt, stride_bytes, stream, what):
+        """(src, count, fmt, stride_bytes, on_device, stream, keep-alive) of the ``values`` update / assign / diff take"""
+        if isinstance(values, tuple):
+            if fmt is None:
+                raise ValueError(f"{what} from a device address needs fmt")
+            return _dev_addr(values[0]), values[1], fmt, stride_bytes, 1, stream, values
+        if isinstance(values, np.ndarray):
+            keep, f = _host_values(values)
+            return _ptr(keep), keep.shape[0], f if fmt is None else fmt, 0, 0, stream, keep
+        torch = _torch_if(values)
+        if torch is None:
+            raise ValueError("values: expected a numpy int64 / uint64 array, an (n, 32) uint8 numpy array, a torch GPU tensor or (address, count)")
+        f, count, stride_bytes = _tensor_layout(torch, values)
+        return values.data_ptr(), count, f if fmt is None else fmt, stride_bytes, 1, _torch_stream(torch, values, stream), values
+
     def update(self, inst, first, values, fmt=None, stride_bytes=0, stream=None):
         """Replace variables [first, first + count) in place (otti_witness_update).  ``values``: a numpy int64 / uint64 array or (n, 32) uint8
         canonical scalars on the host; a torch GPU tensor (as from_tensor); or ``(address, count)`` of device memory with ``fmt`` given.
         A scalar >= l raises R1CSError(-5) and leaves the witness as it was."""
-        if isinstance(values, tuple):
-            if fmt is None:
-                raise ValueError("update from a device address needs fmt")
-            src, count, on_device = _dev_addr(values[0]), values[1], 1
-        elif isinstance(values, np.ndarray):
-            keep, f = _host_values(values)
-            count = keep.shape[0]
-            fmt = f if fmt is None else fmt
-            src, on_device, stride_bytes = _ptr(keep), 0, 0
-        else:
-            torch = _torch_if(values)
-            if torch is None:
-                raise ValueError("values: expected a numpy int64 / uint64 array, an (n, 32) uint8 numpy array, a torch GPU tensor or (address, count)")
-            f, count, stride_bytes = _tensor_layout(torch, values)
-            fmt = f if fmt is None else fmt
-            src, on_device = values.data_ptr(), 1
-            stream = _torch_stream(torch, values, stream)
+        src, count, fmt, stride_bytes, on_device, stream, _keep = self._source(values, fmt, stride_bytes, stream, "update")
         _check(lib.otti_witness_update(inst._h, self._h, first, src, count, fmt, stride_bytes, on_device, stream))
+
+    def assign(self, inst, values, first=0, fmt=None, stride_bytes=0, stream=None):
+        """Set variables [first, first + count) from a whole new vector of which most elements usually have not moved (otti_witness_assign):
+        the vector is compared with the resident one on the device, by value, only the changed elements are written and kept rows are brought
+        up to date by the changes alone.  ``values`` as update takes them.  Returns the number of changed elements.  A scalar >= l raises
+        R1CSError(-5) and leaves the witness as it was."""
+        src, count, fmt, stride_bytes, on_device, stream, _keep = self._source(values, fmt, stride_bytes, stream, "assign")
+        n = _u64()
+        _check(lib.otti_witness_assign(inst._h, self._h, first, src, count, fmt, stride_bytes, on_device, stream, ctypes.byref(n)))
+        return n.value
+
+    def diff(self, inst, values, first=0, fmt=None, stride_bytes=0, stream=None, max_indices=64):
+        """What assign would change, without changing it (otti_witness_diff): (n_changed, the lowest min(n_changed, max_indices) changed
+        indices as an ascending uint64 array)."""
+        src, count, fmt, stride_bytes, on_device, stream, _keep = self._source(values, fmt, stride_bytes, stream, "diff")
+        n, idx = _u64(), np.zeros(max_indices, dtype=np.uint64)
+        _check(lib.otti_witness_diff(inst._h, self._h, first, src, count, fmt, stride_bytes, on_device, stream, ctypes.byref(n), _ptr(idx), max_indices))
+        return n.value, idx[:min(n.value, max_indices)].copy()
+
+    def assign_info(self):
+        """(calls, changed, resums): assign calls that were not refused, elements they changed, calls that summed kept rows again instead of patching them"""
+        a, b, c = _u64(), _u64(), _u64()
+        _check(lib.otti_witness_assign_info(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        return a.value, b.value, c.value
 
     def scatter(self, inst, indices, values, fmt=None, stream=None):
         """Replace the variables ``indices`` by ``values`` in place (otti_witness_scatter); kept rows are patched by the changes, not summed again.
@@ -1083,6 +1110,21 @@ class kernels:
         ms = kernels._ms()
         _check(lib.otti_k_msm_scatter_rows(gens._h, L, _ptr(idx), _ptr(s), idx.size, _ptr(out), ctypes.byref(ms)))
         return out, ms.value
+
+    @staticmethod
+    def witness_diff(old, src, fmt, stride_bytes=0):
+        """otti_witness_assign's two passes on staged vectors: ``old`` (n, 32) Montgomery words, ``src`` the raw bytes of n elements in ``fmt``,
+        ``stride_bytes`` apart (0: packed).  Returns (the new vector, the ascending changed indices, their deltas new - old, elements per chunk)."""
+        old = _scalars(old, "old")
+        n = old.shape[0]
+        raw = np.ascontiguousarray(src).view(np.uint8).reshape(-1)
+        eb = 8 if fmt in (WIT_I64, WIT_U64) else 32
+        if n and raw.size < (n - 1) * (stride_bytes or eb) + eb:
+            raise ValueError("src is shorter than n elements at this stride")
+        new, idx, delta = np.zeros((n, 32), dtype=np.uint8), np.zeros(n, dtype=np.uint64), np.zeros((n, 32), dtype=np.uint8)
+        k, chunk = _u64(), ctypes.c_uint32()
+        _check(lib.otti_k_witness_diff(_ptr(old), n, _ptr(raw), fmt, stride_bytes, _ptr(new), _ptr(idx), _ptr(delta), ctypes.byref(k), ctypes.byref(chunk), None))
+        return new, idx[:k.value].copy(), delta[:k.value].copy(), chunk.value
 
     @staticmethod
     def msm_rows(gens, Z, L, R, blinds):

@@ -191,6 +191,50 @@ int32_t otti_witness_scatter_info(const otti_witness *wit, uint64_t *calls, uint
         return OTTI_OK;
     });
 }
+// ---- assign and its dry form (device.h DeviceWitness::assign / diff).  The order of refusals is otti_witness_update's, through the same
+// check_wit_source; an empty range is answered before a device is asked for.
+int32_t otti_witness_assign(otti_instance *inst, otti_witness *wit, size_t first, const void *src, size_t count, int32_t format, size_t stride_bytes,
+                            int32_t src_on_device, void *stream, uint64_t *n_changed) {
+    return guarded([&] {
+        if (!inst || !wit) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        check_wit_source(src, count, format, stride_bytes, src_on_device != 0);
+        const size_t V = inst->I->num_vars;
+        if (first > V || count > V - first) throw Error(OTTI_ERR_INVALID_NUM_VARS, "the range ends beyond the instance's variables");
+        if (n_changed) *n_changed = 0;
+        if (!count) return OTTI_OK;
+        DevCtx::get();                                            // no device: said before the witness handle is looked at
+        check_witness_dims(wit, *inst->I);
+        const size_t n = wit->w->assign(first, format, src, count, stride_bytes, src_on_device != 0, (hipStream_t)stream);
+        if (n_changed) *n_changed = n;
+        return OTTI_OK;
+    });
+}
+int32_t otti_witness_diff(otti_instance *inst, const otti_witness *wit, size_t first, const void *src, size_t count, int32_t format, size_t stride_bytes,
+                          int32_t src_on_device, void *stream, uint64_t *n_changed, uint64_t *idx, size_t idx_cap) {
+    return guarded([&] {
+        if (!inst || !wit || !n_changed || (idx_cap && !idx)) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        check_wit_source(src, count, format, stride_bytes, src_on_device != 0);
+        const size_t V = inst->I->num_vars;
+        if (first > V || count > V - first) throw Error(OTTI_ERR_INVALID_NUM_VARS, "the range ends beyond the instance's variables");
+        *n_changed = 0;
+        if (!count) return OTTI_OK;
+        DevCtx::get();
+        check_witness_dims(wit, *inst->I);
+        *n_changed = wit->w->diff(first, format, src, count, stride_bytes, src_on_device != 0, (hipStream_t)stream, idx, idx_cap);
+        return OTTI_OK;
+    });
+}
+int32_t otti_witness_assign_info(const otti_witness *wit, uint64_t *calls, uint64_t *changed, uint64_t *resums) {
+    return guarded([&] {
+        if (!wit) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (otti_device_count() < 1) throw Error(OTTI_ERR_NO_DEVICE, "no device: no witness handle can exist");
+        const DeviceWitness &w = *wit->w;
+        if (calls) *calls = w.assign_calls;
+        if (changed) *changed = w.assign_changed;
+        if (resums) *resums = w.assign_resums;
+        return OTTI_OK;
+    });
+}
 int32_t otti_witness_set_inputs(otti_instance *inst, otti_witness *wit, const uint8_t *inputs32, size_t ninputs) {
     return guarded([&] {
         if (!inst || !wit || (!inputs32 && ninputs)) throw Error(OTTI_ERR_BAD_ARG, "null argument");

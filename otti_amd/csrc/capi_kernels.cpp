@@ -282,6 +282,35 @@ int32_t otti_k_msm_scatter_rows(otti_gens *gens, size_t L, const uint64_t *idx, 
     });
 }
 
+// DeviceWitness::assign's two passes (k_field.hip k_witness_diff_count / _scan / _apply) on a staged vector: the new vector, the ascending list of
+// changed indices and their deltas.  A refused scalar is reported after the count pass, before anything is written or copied back.
+int32_t otti_k_witness_diff(const uint8_t *h_old, size_t n, const void *h_src, int32_t format, size_t stride_bytes, uint8_t *h_new, uint64_t *h_idx,
+                            uint8_t *h_delta, uint64_t *n_changed, uint32_t *chunk, float *ms) {
+    return guarded([&] {
+        if (format < OTTI_WIT_CANONICAL32 || format > OTTI_WIT_U64) throw Error(OTTI_ERR_BAD_ARG, "unknown witness format");
+        const size_t eb = wit_elem_bytes(format), stride = stride_bytes ? stride_bytes : eb;
+        if (stride < eb || stride % 8) throw Error(OTTI_ERR_BAD_ARG, "stride_bytes below the element size or not a multiple of 8");
+        if (!n_changed || (n && (!h_old || !h_src || !h_new || !h_idx || !h_delta))) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (chunk) *chunk = (uint32_t)dev_witness_diff_chunk();
+        if (!n) { *n_changed = 0; return OTTI_OK; }
+        DevCtx &c = DevCtx::get();
+        Staged z(c, h_old, n);
+        const size_t span = (n - 1) * stride + eb;
+        DevBuf<uint8_t> src(span);
+        OTTI_HIP(hipMemcpyAsync(src.p, h_src, span, hipMemcpyHostToDevice, c.stream));
+        KTimer t(c, ms);
+        const WitDiff d = dev_witness_diff_count(c, format, src.p, stride, n, z.d.p);
+        const size_t k = d.n_changed;
+        if (d.bad_scalars) { t.stop(); throw Error(OTTI_ERR_INVALID_SCALAR, "non-canonical scalar in the assignment"); }
+        DevBuf<uint64_t> idx(std::max<size_t>(1, k)); DevBuf<Fr> delta(std::max<size_t>(1, k));
+        dev_witness_diff_apply(c, format, src.p, stride, n, z.d.p, 0, k, idx.p, delta.p, true);
+        t.stop();
+        download(c, h_new, z.d.p, n); download(c, h_delta, delta.p, k);
+        if (k) OTTI_HIP(hipMemcpyAsync(h_idx, idx.p, k * sizeof(uint64_t), hipMemcpyDeviceToHost, c.stream));
+        c.sync(); *n_changed = k; return OTTI_OK;
+    });
+}
+
 // ---- the prover's own kernels for phase one / evaluation proof / bullet reduction
 int32_t otti_k_eq_pyramid(const uint8_t *r, size_t n, uint8_t *out) {
     return guarded([&] {

@@ -127,6 +127,7 @@ struct DevCtx {
     DevBuf<unsigned long long> d_counts;                      // two 64-bit tallies for the kernels that count (non-canonical / small scalars / failing constraints): no allocation per call
     DevBuf<unsigned long long> sat_bits;                      // dev_check_sat: one bit per constraint row (grown on demand, kept across calls)
     DevBuf<uint32_t> sat_rows; DevBuf<Fr> sat_abc;            // its report kernel's row ids and 3 sums per row (kSatReportRows of them)
+    DevBuf<unsigned long long> diff_chunks;                   // dev_witness_diff_count: a small head, changed elements per chunk, then their prefix sums (grown on demand, kept across calls)
     Mailbox next_mailbox(int slot);
     GoBox *h_go = nullptr, *d_go_alias = nullptr; DevBuf<GoBox> d_go; unsigned long long go_issued = 0, go_published = 0;
     unsigned long long arm_deadline = kArmDeadlineTicks;     // of the launches armed from now on (the self-test shortens it)
@@ -212,6 +213,17 @@ struct DeviceWitness {
     // W table look-ups per variable (k_msm.hip k_msm_scatter) against R * W for the row's full sum.  Same threads rule as update.
     void scatter(const uint64_t *idx, int format, const void *src, size_t count, size_t stride, bool on_device, hipStream_t producer);
     unsigned long long scatter_calls = 0, rows_patched = 0, terms_patched = 0;   // since the witness was made; the last two move only while rows are kept
+    // variables [first, first + count) ASSIGNED from a whole new vector of which most elements have not moved (arguments, staging and producer
+    // ordering as update): the source is compared with z on the device, only the changed elements are written, and the return value is their
+    // number.  z and small_fraction come out as update leaves them.  A scalar >= l throws INVALID_SCALAR with z, small_fraction, the kept rows and
+    // every counter as they were (the count pass writes nothing); nothing changed: returns 0, nothing written, recounted or launched after that
+    // pass.  Kept rows are patched by the compacted (index, new - old) list as scatter patches them — or, when at least kAssignResumShare of the
+    // touched rows' elements changed, rows idx_min / R .. idx_max / R are summed again as update sums them.  Same threads rule as update.
+    size_t assign(size_t first, int format, const void *src, size_t count, size_t stride, bool src_on_device, hipStream_t producer);
+    // the dry form: the number of elements assign would change, and the lowest min(that, cap) of their indices, ascending, in idx_out (host).
+    // Writes nothing to the witness and moves no counter: it reads the handle only, so it may run wherever check_sat may.
+    size_t diff(size_t first, int format, const void *src, size_t count, size_t stride, bool src_on_device, hipStream_t producer, uint64_t *idx_out, size_t cap) const;
+    unsigned long long assign_calls = 0, assign_changed = 0, assign_resums = 0;   // assign calls that were not refused, elements they changed, calls that summed rows again
     // the public inputs replaced, in z (z[V + 1 ..)) and in `inputs`, which the transcript reads; kept rows cover the variables alone and stay
     void set_inputs(const std::vector<Fr> &new_inputs);
     // ---- kept rows (opt-in): the unblinded row sums of the commitment, sum_j z[i * R + j] * P[j] for the L = V / R rows — the group elements the
@@ -266,6 +278,17 @@ size_t dev_witness_ingest_from(DevCtx &c, int format, const void *src, size_t st
 void dev_witness_scatter_check(DevCtx &c, int format, const void *src, size_t stride, const uint64_t *d_idx, size_t n, size_t V, Fr *conv,
                                size_t *bad_scalars, size_t *bad_indices);
 void dev_witness_scatter_apply(DevCtx &c, const uint64_t *d_idx, const Fr *conv, size_t n, size_t V, Fr *z, Fr *delta);
+// DeviceWitness::assign / diff's launches (k_field.hip).  z: the resident range's first element.  count: the source elements whose Montgomery form
+// differs from z[i] (their number, the first and the last of them; chunk by chunk into c.diff_chunks, then scanned there) and those >= l; writes
+// nothing else; synchronises.  apply (behind a count over the same arguments): the changed elements once more, in ascending order — for the k-th,
+// k < cap, d_idx[k] = first + i (d_idx given), delta[k] = new - old (delta given), z[i] = new (write_z); never a store beyond slot min(count, cap)
+// or outside the range, whatever has become of the source since; only queues.  rows_touched (behind a count on this context): the rows of R that an
+// ascending device list touches; only queues: *h_rows is filled once c.stream has been synchronised.
+struct WitDiff { size_t n_changed = 0, bad_scalars = 0, lo = 0, hi = 0; };   // lo, hi: positions in the range, meaningful when n_changed > 0
+size_t dev_witness_diff_chunk();                             // elements per workgroup of both passes
+WitDiff dev_witness_diff_count(DevCtx &c, int format, const void *src, size_t stride, size_t n, const Fr *z);
+void dev_witness_diff_apply(DevCtx &c, int format, const void *src, size_t stride, size_t n, Fr *z, size_t first, size_t cap, uint64_t *d_idx, Fr *delta, bool write_z);
+void dev_witness_rows_touched(DevCtx &c, const uint64_t *d_idx, size_t n, size_t R, uint64_t *h_rows);
 void dev_gather_strided(DevCtx &c, const Fr *in, size_t stride, size_t offset, Fr *out, size_t n);   // out[i] = in[i*stride + offset]
 
 std::shared_ptr<DeviceInstance> upload_instance(const Instance &I);

@@ -148,6 +148,157 @@ void dev_witness_scatter_apply(DevCtx &c, const uint64_t *d_idx, const Fr *conv,
     KScope ks(c, KC_OTHER);
     hipLaunchKernelGGL(k_witness_scatter_apply, grid_for(n), kBlock, 0, c.stream, reinterpret_cast<const unsigned long long *>(d_idx), conv, n, V, z, delta);
 }
+// ---- a whole assignment compared with the resident one (DeviceWitness::assign / diff): element i of the source against z[i], both in Montgomery
+// form, so that equal values in other clothes (-5, l - 5 as canonical bytes, the resident word) are equal.  Workgroup c owns the FIXED contiguous
+// chunk [c * kDiffChunk, (c + 1) * kDiffChunk) — no grid stride: the compacted list comes out ascending by construction.  Three launches:
+//   count: chunk_counts[c] = changed elements of chunk c, counts[0] += scalars >= l, ends[0 .. 2) = the first and last changed element (what decides
+//          between patching and re-summing kept rows before anything is written); writes nothing else (a refused vector has changed nothing);
+//   scan:  chunk_counts[0 .. nchunks] becomes its exclusive prefix sum (entry nchunks: the total, also left in counts[1]);
+//   apply: every element converted again (twice the products, against 32 bytes per element of HBM for a staging copy), its rank among the
+//          chunk's changed elements from a wave ballot, a popcount prefix and the waves' counts in LDS, and for a changed element
+//          idx[base + rank] = first + i (idx given), delta[base + rank] = now - old (delta given), z[i] = now (write_z).  Unchanged elements are
+//          not written.  z points at the range's first element here and in the count pass; `first` only names it in the list.
+// A chunk stores into its own slots [base[c], base[c + 1]) alone: a device source rewritten between the launches may change FEWER or MORE elements
+// than were counted — the surplus is left as it was (z too), and slots left over are filled with the chunk's last index and a zero delta, so the
+// list stays ascending (not strictly) and the patch of the kept rows (k_msm_scatter) still moves the rows by exactly what z moved by.
+constexpr int kDiffChunk = 1024;               // elements per workgroup: kDiffChunk / kBlock passes of one element per lane
+static_assert(kDiffChunk % kBlock == 0 && kBlock % 64 == 0, "a chunk is whole passes of whole waves");
+template <int F> __device__ __forceinline__ Fr wit_diff_load(const unsigned char *src, size_t stride, bool wide, size_t i, const Fr *z, bool &changed, bool &refused, Fr &old) {
+    bool neg, small; const Fr raw = wit_load<F>(src + i * stride, wide, neg);
+    const Fr now = wit_convert<F>(raw, neg, refused, small);
+    old = z[i];
+    uint32_t d = 0;
+    for (int k = 0; k < 8; k++) d |= now.v[k] ^ old.v[k];
+    changed = d != 0;
+    return now;
+}
+template <int F> __global__ __launch_bounds__(kBlock) void k_witness_diff_count(const unsigned char *src, size_t stride, size_t n, const Fr *z, unsigned long long *chunk_counts,
+                                                                              unsigned long long *ends, unsigned long long *counts) {
+    __shared__ unsigned s_wave[kBlock / 64];
+    const bool wide = (((size_t)src | stride) & 15) == 0;
+    const size_t i0 = (size_t)blockIdx.x * kDiffChunk + threadIdx.x;
+    unsigned bad = 0, wave_changed = 0;                           // wave_changed, lo and hi are the same in every lane of a wave
+    unsigned long long lo = ~0ull, hi = 0;                        // the wave's first and last changed element
+    for (int pass = 0; pass < kDiffChunk / kBlock; pass++) {
+        const size_t i = i0 + (size_t)pass * kBlock;
+        bool changed = false, refused = false;
+        if (i < n) { Fr old; (void)wit_diff_load<F>(src, stride, wide, i, z, changed, refused, old); }
+        bad += refused;
+        const unsigned long long ballot = __ballot(changed);
+        if (ballot) {
+            const unsigned long long lane0 = i - (threadIdx.x & 63);           // the element of the wave's lane 0 in this pass
+            lo = min(lo, lane0 + (unsigned)(__ffsll((long long)ballot) - 1)); hi = max(hi, lane0 + (unsigned)(63 - __clzll((long long)ballot)));
+            wave_changed += (unsigned)__popcll(ballot);
+        }
+    }
+    if ((threadIdx.x & 63) == 0) {
+        s_wave[threadIdx.x >> 6] = wave_changed;
+        if (wave_changed) { atomicMin(&ends[0], lo); atomicMax(&ends[1], hi); }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) { unsigned t = 0; for (int w = 0; w < kBlock / 64; w++) t += s_wave[w]; chunk_counts[blockIdx.x] = t; }
+    wit_tally(bad, 0, counts);
+}
+// one workgroup: the exclusive prefix sum of v[0 .. n) in place, v[n] = the total = counts[1]
+__global__ __launch_bounds__(kBlock) void k_witness_diff_scan(unsigned long long *v, size_t n, unsigned long long *counts) {
+    __shared__ unsigned long long s_wave[kBlock / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long carry = 0;
+    for (size_t t0 = 0; t0 < n; t0 += kBlock) {
+        const size_t i = t0 + threadIdx.x;
+        const unsigned long long x = i < n ? v[i] : 0;
+        unsigned long long incl = x;                              // inclusive scan over the wave
+        for (int o = 1; o < 64; o <<= 1) { const unsigned long long y = __shfl_up(incl, o); if (lane >= o) incl += y; }
+        if (lane == 63) s_wave[wave] = incl;
+        __syncthreads();
+        unsigned long long before = 0, tile = 0;
+        for (int w = 0; w < kBlock / 64; w++) { const unsigned long long s = s_wave[w]; if (w < wave) before += s; tile += s; }
+        if (i < n) v[i] = carry + before + incl - x;
+        carry += tile;
+        __syncthreads();                                          // s_wave is written again by the next tile
+    }
+    if (threadIdx.x == 0) { v[n] = carry; counts[1] = carry; }
+}
+template <int F> __global__ __launch_bounds__(kBlock) void k_witness_diff_apply(const unsigned char *src, size_t stride, size_t n, Fr *z, size_t first,
+                                                                              const unsigned long long *chunk_base, unsigned long long cap,
+                                                                              unsigned long long *idx, Fr *delta, bool write_z) {
+    __shared__ unsigned s_wave[2][kBlock / 64];
+    const unsigned long long base = chunk_base[blockIdx.x], limit = min(chunk_base[blockIdx.x + 1], cap);   // this chunk's slots, whatever the source says now
+    if (base >= limit) return;                                    // the whole workgroup: nothing of this chunk was counted, or (diff) the list is full before it
+    const bool wide = (((size_t)src | stride) & 15) == 0;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const size_t i0 = (size_t)blockIdx.x * kDiffChunk + threadIdx.x;
+    unsigned long long run = base;                                // the slot of the pass's first changed element
+    for (int pass = 0; pass < kDiffChunk / kBlock; pass++) {
+        const size_t i = i0 + (size_t)pass * kBlock;
+        bool changed = false, refused = false; Fr now, old;
+        if (i < n) now = wit_diff_load<F>(src, stride, wide, i, z, changed, refused, old);
+        changed = changed && !refused;                            // the count pass saw none: a scalar >= l has appeared since, and is left out
+        const unsigned long long ballot = __ballot(changed);
+        if (lane == 0) s_wave[pass & 1][wave] = (unsigned)__popcll(ballot);
+        __syncthreads();                                          // one barrier a pass: the next pass writes the other half of s_wave
+        unsigned before = 0, total = 0;
+        for (int w = 0; w < kBlock / 64; w++) { const unsigned s = s_wave[pass & 1][w]; if (w < wave) before += s; total += s; }
+        const unsigned long long out = run + before + (unsigned)__popcll(ballot & ((1ull << lane) - 1));
+        if (changed && out < limit) {
+            if (idx) idx[out] = (unsigned long long)(first + i);
+            if (delta) delta[out] = fr_sub(now, old);
+            if (write_z) z[i] = now;
+        }
+        run += total;
+    }
+    // fewer changed than counted: the slots left over name the chunk's last element with a zero delta (ascending, and nothing for the patch to add)
+    const size_t last = min((size_t)(blockIdx.x + 1) * kDiffChunk, n) - 1;
+    for (unsigned long long out = run + threadIdx.x; out < limit; out += kBlock) { if (idx) idx[out] = (unsigned long long)(first + last); if (delta) delta[out] = fr_zero(); }
+}
+// c.diff_chunks: [0], [1] the first and last changed element of the latest count pass, [2] dev_witness_rows_touched's tally, [3] unused, then the
+// chunks' counts / prefix sums
+constexpr size_t kDiffHead = 4;
+size_t dev_witness_diff_chunk() { return kDiffChunk; }
+WitDiff dev_witness_diff_count(DevCtx &c, int format, const void *src, size_t stride, size_t n, const Fr *z) {
+    WitDiff d;
+    if (!n) return d;
+    const size_t nchunks = (n + kDiffChunk - 1) / kDiffChunk;
+    if (c.diff_chunks.n < kDiffHead + nchunks + 1) c.diff_chunks.alloc(kDiffHead + nchunks + 1);
+    unsigned long long *head = c.diff_chunks.p, *chunks = head + kDiffHead;
+    const unsigned char *s = reinterpret_cast<const unsigned char *>(src);
+    unsigned long long ends[2] = {0, 0};
+    const Tallies t = counted_launch(c, [&](unsigned long long *counts) {
+        OTTI_HIP(hipMemsetAsync(head, 0xff, sizeof(unsigned long long), c.stream)); OTTI_HIP(hipMemsetAsync(head + 1, 0, sizeof(unsigned long long), c.stream));
+        KScope ks(c, KC_OTHER);
+        wit_dispatch(format, [&](auto F) { hipLaunchKernelGGL(k_witness_diff_count<decltype(F)::value>, (unsigned)nchunks, kBlock, 0, c.stream, s, stride, n, z, chunks, head, counts); });
+        hipLaunchKernelGGL(k_witness_diff_scan, 1, kBlock, 0, c.stream, chunks, nchunks, counts);
+        OTTI_HIP(hipMemcpyAsync(ends, head, sizeof ends, hipMemcpyDeviceToHost, c.stream));
+    });
+    d.bad_scalars = (size_t)t.first; d.n_changed = (size_t)t.second; d.lo = (size_t)ends[0]; d.hi = (size_t)ends[1];
+    return d;
+}
+void dev_witness_diff_apply(DevCtx &c, int format, const void *src, size_t stride, size_t n, Fr *z, size_t first, size_t cap, uint64_t *d_idx, Fr *delta, bool write_z) {
+    if (!n || !cap) return;
+    const size_t nchunks = (n + kDiffChunk - 1) / kDiffChunk;
+    if (c.diff_chunks.n < kDiffHead + nchunks + 1) throw Error(OTTI_ERR_INTERNAL, "witness diff: apply without the count pass before it");
+    const unsigned char *s = reinterpret_cast<const unsigned char *>(src);
+    KScope ks(c, KC_OTHER);
+    wit_dispatch(format, [&](auto F) {
+        hipLaunchKernelGGL(k_witness_diff_apply<decltype(F)::value>, (unsigned)nchunks, kBlock, 0, c.stream, s, stride, n, z, first, c.diff_chunks.p + kDiffHead, (unsigned long long)cap,
+                           reinterpret_cast<unsigned long long *>(d_idx), delta, write_z);
+    });
+}
+// how many rows of R an ascending index list touches: the i whose row differs from their predecessor's, added to *tally
+__global__ __launch_bounds__(kBlock) void k_witness_rows_touched(const unsigned long long *idx, size_t n, size_t R, unsigned long long *tally) {
+    unsigned rows = 0;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) rows += i == 0 || idx[i] / R != idx[i - 1] / R;
+    for (int o = 32; o >= 1; o >>= 1) rows += __shfl_down(rows, o);
+    if ((threadIdx.x & 63) == 0 && rows) atomicAdd(tally, (unsigned long long)rows);
+}
+void dev_witness_rows_touched(DevCtx &c, const uint64_t *d_idx, size_t n, size_t R, uint64_t *h_rows) {
+    *h_rows = 0;
+    if (!n) return;
+    unsigned long long *tally = c.diff_chunks.p + 2;              // the count pass before this list has made the buffer
+    OTTI_HIP(hipMemsetAsync(tally, 0, sizeof(unsigned long long), c.stream));
+    { KScope ks(c, KC_OTHER); hipLaunchKernelGGL(k_witness_rows_touched, grid_for(n), kBlock, 0, c.stream, reinterpret_cast<const unsigned long long *>(d_idx), n, R, tally); }
+    OTTI_HIP(hipMemcpyAsync(h_rows, tally, sizeof(uint64_t), hipMemcpyDeviceToHost, c.stream));
+}
 // Whole-chip throughput of the Montgomery product in GF(l) (operands in registers, every CU busy): what the sum-check, sparse-product
 // and eq kernels are priced against beside the HBM roof — at 7-13 products per 192 bytes they are bounded by the multiplier first.
 __global__ __launch_bounds__(kBlock) void k_fr_mul_peak(Fr *io, int iters) {

@@ -257,6 +257,75 @@ void DeviceWitness::scatter(const uint64_t *idx, int format, const void *src, si
         rows_patched += rows; terms_patched += count;
     }
 }
+// ---- assign: a whole new vector of which most elements have not moved.  Behind the same staging and producer-stream ordering as update (a host
+// source is staged as it is, never converted into a copy: both passes convert on the fly): the count pass (changed elements per chunk, scalars >= l;
+// and the first and last changed element; one synchronise, and a refusal or "nothing changed" ends here with nothing written), the apply pass (z, and
+// for a patch the ascending list of changed indices and their deltas), the kept rows brought up to date — patched by the list as scatter patches them,
+// or, from kAssignResumShare of the touched rows' elements on, rows idx_min / R .. idx_max / R summed again as update sums them — and the recount
+// of small_fraction.
+// The share of touched_rows * R changed elements from which summing the touched rows again replaces the patch (a value >= 1: never).  Measured,
+// profiles/witness_assign.md (tools/witness_assign_probe.py, 2^20, kept rows): the smallest probed share at which a round trip with the patch forced
+// was no longer shorter than one with the re-sum of the same range forced, on the same witness, was 1/2 (at 1/8 the patch still won clearly), for small
+// int64 numbers and for uniform canonical bytes alike.
+constexpr double kAssignResumShare = 0.5;
+// OTTI_ASSIGN_RESUM_SHARE, read per call, overrides it: 0 sums again whenever anything changed, a value >= 1 never does (tests pin both paths with it)
+static double assign_resum_share() {
+    if (const char *e = getenv("OTTI_ASSIGN_RESUM_SHARE")) { char *end = nullptr; const double v = strtod(e, &end); if (end != e && v >= 0) return v; }
+    return kAssignResumShare;
+}
+size_t DeviceWitness::assign(size_t first, int format, const void *src, size_t count, size_t stride, bool src_on_device, hipStream_t producer) {
+    DevCtx &c = DevCtx::get();
+    const size_t V = z.n / 2;
+    if (first > V || count > V - first) throw Error(OTTI_ERR_INVALID_NUM_VARS, "the range ends beyond the instance's variables");
+    if (!count) return 0;
+    WitSource s(c, format, src, count, stride, src_on_device, producer, nullptr);
+    const WitDiff d = dev_witness_diff_count(c, format, s.p, s.stride, count, z.p + first);
+    if (d.bad_scalars) throw Error(OTTI_ERR_INVALID_SCALAR, "non-canonical scalar in the assignment: the witness is unchanged");
+    assign_calls++;
+    const size_t n_changed = d.n_changed;
+    if (!n_changed) return 0;
+    assign_changed += n_changed;
+    // kept rows: patched, or rows r0 .. r1 summed again — known before anything is written, so only a patch pays for the list and the deltas
+    const size_t r0 = rows_kept.p ? (first + d.lo) / rows_R : 0, r1 = rows_kept.p ? (first + d.hi) / rows_R : 0;
+    const double share = assign_resum_share();
+    const bool patch = rows_kept.p && !(share < 1.0 && (double)n_changed >= share * (double)((r1 - r0 + 1) * rows_R));
+    DevBuf<uint64_t> idx; DevBuf<Fr> delta;                       // outlive the launches that read them: freed after dev_small_fraction has synchronised
+    if (patch) { idx.alloc(n_changed); delta.alloc(n_changed); }
+    dev_witness_diff_apply(c, format, s.p, s.stride, count, z.p + first, first, n_changed, idx.p, delta.p, true);
+    uint64_t rows = 0;
+    if (patch) {
+        // z has changed: a patch that cannot run (the table has to be rebuilt and HBM is short) leaves rows that no longer belong to it, as in resum_rows
+        try {
+            ensure_gens_device(*rows_gens);
+            dev_msm_scatter(c, *rows_gens->dev, idx.p, delta.p, n_changed, rows_R, rows_kept.p, rows_kept.n);
+            dev_witness_rows_touched(c, idx.p, n_changed, rows_R, &rows);
+        } catch (...) { (void)hipStreamSynchronize(c.stream); drop_rows(); throw; }
+    }
+    // counted again as update and scatter do; synchronises: the patch is done, `rows` is filled.  A throw on the way must not leave the copy into
+    // `rows`, or the launches that read idx and delta, pending behind this frame
+    try { small_fraction = dev_small_fraction(c, z.p, V); } catch (...) { (void)hipStreamSynchronize(c.stream); throw; }
+    if (patch) { rows_patched += rows; terms_patched += n_changed; }
+    else if (rows_kept.p) { resum_rows(c, *this, r0, r1); assign_resums++; }   // behind the recount, as in update: the launch picks its variant by the new share
+    return n_changed;
+}
+size_t DeviceWitness::diff(size_t first, int format, const void *src, size_t count, size_t stride, bool src_on_device, hipStream_t producer, uint64_t *idx_out,
+                           size_t cap) const {
+    DevCtx &c = DevCtx::get();
+    const size_t V = z.n / 2;
+    if (first > V || count > V - first) throw Error(OTTI_ERR_INVALID_NUM_VARS, "the range ends beyond the instance's variables");
+    if (!count) return 0;
+    WitSource s(c, format, src, count, stride, src_on_device, producer, nullptr);
+    const WitDiff d = dev_witness_diff_count(c, format, s.p, s.stride, count, z.p + first);
+    if (d.bad_scalars) throw Error(OTTI_ERR_INVALID_SCALAR, "non-canonical scalar in the assignment");
+    const size_t n_changed = d.n_changed, k = std::min(n_changed, cap);
+    if (k) {
+        DevBuf<uint64_t> idx(k);
+        dev_witness_diff_apply(c, format, s.p, s.stride, count, z.p + first, first, k, idx.p, nullptr, false);
+        OTTI_HIP(hipMemcpyAsync(idx_out, idx.p, k * sizeof(uint64_t), hipMemcpyDeviceToHost, c.stream));
+        OTTI_HIP(hipStreamSynchronize(c.stream));
+    }
+    return n_changed;
+}
 void DeviceWitness::set_inputs(const std::vector<Fr> &new_inputs) {
     DevCtx &c = DevCtx::get();
     if (new_inputs.size() != inputs.size()) throw Error(OTTI_ERR_INVALID_NUM_INPUTS, "wrong number of inputs");
