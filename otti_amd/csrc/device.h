@@ -11,6 +11,7 @@
 #include "spartan.h"
 #include "mail.h"
 #include "msm_plan.h"
+#include "sc_plan.h"
 
 namespace otti {
 
@@ -335,6 +336,7 @@ unsigned long long dev_sc_cubic3_fold_eval_armed(DevCtx &c, Fr *B, Fr *C, Fr *D,
 unsigned long long dev_sc_quad_fold_eval_armed(DevCtx &c, Fr *A, Fr *B, size_t len, int slot);
 unsigned long long dev_sc_quad_eval(DevCtx &c, const Fr *A, const Fr *B, size_t len, int slot);
 unsigned long long dev_sc_quad_fold_eval(DevCtx &c, Fr *A, Fr *B, size_t len, const Fr &r, int slot);
+const ScCaps &sc_caps(DevCtx &c);                   // what sc_plan() (sc_plan.h) is told about this device: it sets the grid of every launch above
 void dev_fold_top(DevCtx &c, Fr *Z, size_t len, const Fr &r);
 void dev_fold_bot(DevCtx &c, const Fr *Z, Fr *out, size_t len, const Fr &r);
 void dev_fetch(DevCtx &c, const Fr *src, int slot, size_t n);              // async copy of n elements into h_results[slot..]

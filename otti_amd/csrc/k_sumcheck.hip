@@ -99,15 +99,50 @@ template <int K> __device__ __forceinline__ void store_partials(Fr (&acc)[K], Fr
 // What the LAST thread does to the launch's totals before they go to the host: POST_CUBIC3 turns (Q(0), Q(1), leading coefficient) of a
 // quadratic into its values at 0, 2, 3 (the nine-limb kernels below sum the former: linear, so applied once per launch, not per item).
 enum { POST_NONE = 0, POST_CUBIC3 = 1 };
+// block_reduce (kernels_common.h) for the two or three sums of a round, with the sums DEALT OUT over the lanes instead of every lane carrying all K
+// through six steps: the first step (K = 3: the first two) halves what a lane carries — of two lanes that exchange, one keeps the lower slots and
+// receives its partner's, the other the upper ones — so a wave makes 6 (K = 2) or 7 (K = 3) modular additions and 48 / 56 register exchanges where
+// block_reduce makes 6 K and 48 K; the waves' totals then meet in LDS, one lane per sum.  All of it is on a launch's sequential path, once in every
+// launch and once more in the last workgroup of a grid: measured 1.5 - 4 us per launch (profiles/sumcheck_split.md).
+// Sums of canonical elements, canonical after every addition: the totals do not depend on the order.  Thread 0 ends up with them.
+template <int K> __device__ __forceinline__ void block_reduce_dealt(Fr (&acc)[K]) {
+    static_assert(K == 2 || K == 3, "two or three sums");
+    __shared__ Fr sm[K][16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const bool up = (lane & 32) != 0, up2 = (lane & 16) != 0;
+    Fr one;                                                   // this lane's single running sum, of slot `mine`
+    int mine;
+    if constexpr (K == 2) {                                   // lanes 0 .. 31 end up with slot 0, lanes 32 .. 63 with slot 1
+        const Fr got = shfl_xor_fr(up ? acc[0] : acc[1], 32);
+        one = fr_add(up ? acc[1] : acc[0], got); mine = up ? 1 : 0;
+    } else {                                                  // slots (0, 1) below lane 32, (2, none) from it up; then slot k in lanes 16 k .. 16 k + 15
+        const Fr z = fr_zero();
+        const Fr got0 = shfl_xor_fr(up ? acc[0] : acc[2], 32), got1 = shfl_xor_fr(up ? acc[1] : z, 32);
+        const Fr two0 = fr_add(up ? acc[2] : acc[0], got0), two1 = up ? z : fr_add(acc[1], got1);
+        const Fr got = shfl_xor_fr(up2 ? two0 : two1, 16);
+        one = fr_add(up2 ? two1 : two0, got); mine = (up ? 2 : 0) + (up2 ? 1 : 0);
+    }
+#pragma unroll
+    for (int off = K == 2 ? 16 : 8; off >= 1; off >>= 1) one = fr_add(one, shfl_xor_fr(one, off));
+    __syncthreads();                         // protects sm against a previous use
+    if ((lane & (K == 2 ? 31 : 15)) == 0 && mine < K) sm[mine][wave] = one;
+    __syncthreads();
+    if (threadIdx.x < 64) {                  // lane k adds up sum k over the waves; lane 0 collects
+        Fr t = fr_zero();
+        if (lane < K) { t = sm[lane][0]; for (int w = 1; w < nw; w++) t = fr_add(t, sm[lane][w]); }
+#pragma unroll
+        for (int k = 0; k < K; k++) acc[k] = shfl_xor_fr(t, k);   // lane 0 reads lane k
+    }
+}
 template <int K, int kPost = POST_NONE> __device__ __forceinline__ void finish_in_kernel(Fr (&acc)[K], const Mailbox &mb) {
-    block_reduce<K>(acc);
+    block_reduce_dealt<K>(acc);
     if (gridDim.x > 1) {
         if (threadIdx.x == 0) for (int k = 0; k < K; k++) store_words_sc1(&mb.partials[(size_t)blockIdx.x * K + k], acc[k].v, 8);
         if (!arrive_and_check_last(mb.counter, gridDim.x)) return;
         for (int k = 0; k < K; k++) acc[k] = fr_zero();
         for (unsigned b = threadIdx.x; b < gridDim.x; b += blockDim.x)
             for (int k = 0; k < K; k++) { Fr t; load_words_sc1(t.v, &mb.partials[(size_t)b * K + k], 8); acc[k] = fr_add(acc[k], t); }
-        block_reduce<K>(acc);
+        block_reduce_dealt<K>(acc);
     }
     if (mb.line_mail && K <= 3) {
         // the totals, the number and the tag as ONE 128-byte line in one store instruction, no fence (device.h kLineMark; 0.7 us of a round's 15)
@@ -289,17 +324,35 @@ template <int K> static void finish_round(DevCtx &c, int nblocks, int slot) {
     { KScope ks(c, KC_REDUCE); hipLaunchKernelGGL(k_reduce_partials<K>, 1, kBlock, 0, c.stream, (const Fr *)c.partials.p, nblocks, c.results.p + slot); }
     dev_fetch(c, c.results.p + slot, slot, K);
 }
-// 242-VGPR kernels: two workgroups per CU are resident, so 512 workgroups already fill the chip; below ~2^21 elements a wider grid only
-// adds partials for the last workgroup to sum (measured: 2^20 evaluate 47 -> 32 us), above it the extra workgroups hide tail effects.
-static inline int sc_grid(size_t n) { return std::min(grid_for(n), n <= ((size_t)1 << 21) ? 512 : kMaxBlocks); }
+// What sc_plan() is told about this device, once per process: its CUs and how many workgroups of each round kernel are resident at once
+// (the occupancy query, times the CUs).
+template <class Kern> static unsigned resident_workgroups(const DevCtx &c, Kern kern) {
+    int per_cu = 0;
+    OTTI_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kBlock, 0));
+    return (unsigned)std::max(1, per_cu) * (unsigned)std::max(1, c.num_cu);
+}
+const ScCaps &sc_caps(DevCtx &c) {
+    static std::once_flag once; static ScCaps caps;
+    std::call_once(once, [&] {
+        caps.num_cu = (unsigned)std::max(1, c.num_cu);
+        caps.resident[(int)ScKind::cubic3_eval] = resident_workgroups(c, k_sc_cubic3_eval);
+        caps.resident[(int)ScKind::cubic3_fold] = resident_workgroups(c, k_sc_cubic3_fold_eval);
+        caps.resident[(int)ScKind::quad_eval] = resident_workgroups(c, k_sc_quad_eval);
+        caps.resident[(int)ScKind::quad_fold] = resident_workgroups(c, k_sc_quad_fold_eval);
+        caps.resident[(int)ScKind::cubic4_eval] = resident_workgroups(c, k_sc_cubic_eval);
+        caps.resident[(int)ScKind::cubic4_fold] = resident_workgroups(c, k_sc_cubic_fold_eval);
+    });
+    return caps;
+}
+static_assert(kScThreads == kBlock && kScMaxWorkgroups == (unsigned)kMaxBlocks && (size_t)kScArmedWorkgroups * kBlock * 4 == kArmMaxLen, "sc_plan.h restates device.h");
 unsigned long long dev_sc_cubic_eval(DevCtx &c, const Fr *A, const Fr *B, const Fr *C, const Fr *D, size_t len, int slot) {
-    size_t half = len / 2; int g = sc_grid(half); Mailbox mb = c.next_mailbox(slot);
+    size_t half = len / 2; const unsigned g = sc_plan(ScKind::cubic4_eval, len, false, sc_caps(c)).workgroups; Mailbox mb = c.next_mailbox(slot);
     KScope ks(c, KC_SC_CUBIC); hipLaunchKernelGGL(k_sc_cubic_eval, g, kBlock, 0, c.stream, A, B, C, D, half, mb);
     return mb.seq;
 }
 unsigned long long dev_sc_cubic_fold_eval(DevCtx &c, Fr *A, Fr *B, Fr *C, Fr *D, size_t len, const Fr &r, int slot) {
     if (len < 4) throw Error(OTTI_ERR_INTERNAL, "fold_eval needs len >= 4");
-    size_t q = len / 4; int g = sc_grid(q); Mailbox mb = c.next_mailbox(slot);
+    size_t q = len / 4; const unsigned g = sc_plan(ScKind::cubic4_fold, len, false, sc_caps(c)).workgroups; Mailbox mb = c.next_mailbox(slot);
     KScope ks(c, KC_SC_CUBIC); hipLaunchKernelGGL(k_sc_cubic_fold_eval, g, kBlock, 0, c.stream, A, B, C, D, q, r, mb);
     return mb.seq;
 }
@@ -309,29 +362,29 @@ void dev_eq_pyramid2(DevCtx &c, const Fr *r0_host, size_t n0, Fr *out0, const Fr
     launch_eq_tree(c, r0_host, n0, true, out0, r1_host, n1, true, out1);
 }
 unsigned long long dev_sc_cubic3_eval(DevCtx &c, const Fr *B, const Fr *C, const Fr *D, size_t len, const EqSrc &E, int slot) {
-    size_t half = len / 2; int g = sc_grid(half); Mailbox mb = c.next_mailbox(slot);
+    size_t half = len / 2; const unsigned g = sc_plan(ScKind::cubic3_eval, len, false, sc_caps(c)).workgroups; Mailbox mb = c.next_mailbox(slot);
     KScope ks(c, KC_SC_CUBIC); hipLaunchKernelGGL(k_sc_cubic3_eval, g, kBlock, 0, c.stream, B, C, D, half, E, mb);
     return mb.seq;
 }
 static unsigned long long cubic3_fold_eval(DevCtx &c, Fr *B, Fr *C, Fr *D, size_t len, const Fr *r, const EqSrc &E, int slot) {
     if (len < 4) throw Error(OTTI_ERR_INTERNAL, "fold_eval needs len >= 4");
-    size_t q = len / 4; int g = sc_grid(q); Mailbox mb = c.next_mailbox(slot);
+    size_t q = len / 4; const ScPlan p = sc_plan(ScKind::cubic3_fold, len, !r, sc_caps(c)); Mailbox mb = c.next_mailbox(slot);
     const Armed go = r ? Armed{nullptr, nullptr, 0} : c.arm();
-    KScope ks(c, KC_SC_CUBIC); hipLaunchKernelGGL(k_sc_cubic3_fold_eval, g, kBlock, 0, c.stream, B, C, D, q, r ? *r : fr_zero(), E, mb, go);
+    KScope ks(c, KC_SC_CUBIC); hipLaunchKernelGGL(k_sc_cubic3_fold_eval, p.workgroups, kBlock, 0, c.stream, B, C, D, q, r ? *r : fr_zero(), E, mb, go);
     return mb.seq;
 }
 unsigned long long dev_sc_cubic3_fold_eval(DevCtx &c, Fr *B, Fr *C, Fr *D, size_t len, const Fr &r, const EqSrc &E, int slot) { return cubic3_fold_eval(c, B, C, D, len, &r, E, slot); }
 unsigned long long dev_sc_cubic3_fold_eval_armed(DevCtx &c, Fr *B, Fr *C, Fr *D, size_t len, const EqSrc &E, int slot) { return cubic3_fold_eval(c, B, C, D, len, nullptr, E, slot); }
 unsigned long long dev_sc_quad_eval(DevCtx &c, const Fr *A, const Fr *B, size_t len, int slot) {
-    size_t half = len / 2; int g = sc_grid(half); Mailbox mb = c.next_mailbox(slot);
+    size_t half = len / 2; const unsigned g = sc_plan(ScKind::quad_eval, len, false, sc_caps(c)).workgroups; Mailbox mb = c.next_mailbox(slot);
     KScope ks(c, KC_SC_QUAD); hipLaunchKernelGGL(k_sc_quad_eval, g, kBlock, 0, c.stream, A, B, half, mb);
     return mb.seq;
 }
 static unsigned long long quad_fold_eval(DevCtx &c, Fr *A, Fr *B, size_t len, const Fr *r, int slot) {
     if (len < 4) throw Error(OTTI_ERR_INTERNAL, "fold_eval needs len >= 4");
-    size_t q = len / 4; int g = sc_grid(q); Mailbox mb = c.next_mailbox(slot);
+    size_t q = len / 4; const ScPlan p = sc_plan(ScKind::quad_fold, len, !r, sc_caps(c)); Mailbox mb = c.next_mailbox(slot);
     const Armed go = r ? Armed{nullptr, nullptr, 0} : c.arm();
-    KScope ks(c, KC_SC_QUAD); hipLaunchKernelGGL(k_sc_quad_fold_eval, g, kBlock, 0, c.stream, A, B, q, r ? *r : fr_zero(), mb, go);
+    KScope ks(c, KC_SC_QUAD); hipLaunchKernelGGL(k_sc_quad_fold_eval, p.workgroups, kBlock, 0, c.stream, A, B, q, r ? *r : fr_zero(), mb, go);
     return mb.seq;
 }
 unsigned long long dev_sc_quad_fold_eval(DevCtx &c, Fr *A, Fr *B, size_t len, const Fr &r, int slot) { return quad_fold_eval(c, A, B, len, &r, slot); }
