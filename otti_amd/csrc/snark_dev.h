@@ -1,13 +1,13 @@
 // Device-side interface of SNARK mode's kernels (k_snark.hip) for snark_prover.cpp.
 #pragma once
 #include "device.h"
+#include "pc_plan.h"
 
 namespace otti {
 
 constexpr int kMaxInst = 20;                                  // 12 product circuits + 6 dot-product halves in the largest batch
 // Places in the pinned result buffer (c.h_results) and scratch sizes that the prover and the kernel-level test entries must agree on
-constexpr int kSumSlot = 64;                                  // where a round's sums land
-constexpr int kPcTailSlot = 128;                              // where a layer's exported / handed-over tables start
+constexpr int kSumSlot = 64;                                  // where a round's sums land (kPcTailSlot, where a layer's exported tables start: pc_plan.h)
 constexpr size_t kSnarkPartials = (size_t)3 * kMaxBlocks + 64;   // dev_dot_many / dev_sum3 scratch: 3 sums x at most kMaxBlocks workgroups per launch (k_snark.hip many_grid)
 struct AbcList { const Fr *A[kMaxInst], *B[kMaxInst], *C[kMaxInst]; int n; };
 struct PtrList { Fr *p[64]; int n; };
@@ -31,9 +31,8 @@ unsigned long long dev_pc_export(DevCtx &c, const PcList &L, size_t len, bool fo
 // for the challenge (an armed fetch per round: consecutive go() numbers), folds in LDS.  The eq table of a product-circuit instance
 // is materialised in LDS here (a real third table, folded like the others; the host multiplies by the factor accumulated before).
 // No launch, no HBM round trip, no inter-workgroup hand-off per round: a round costs the host's hash plus ~3 us of arithmetic.
-constexpr int kTailCap = 1024, kTailThreads = 1024, kTailMaxGroups = 160;
+constexpr int kTailThreads = 1024;                            // (kTailCap, kTailMaxGroups: pc_plan.h, with the rule that picks W and the first round)
 // The line itself (128 bytes per workgroup, one store instruction, no fence; number and tag): TailMail in mail.h.
-struct TailPlan { int W = 0; size_t k0 = 0; };                         // workgroups per instance; first round played by the tail (== ndev: no tail)
 // rounds played = log2(len0 / t_out) (>= 1).  Round j's partial sums of workgroup (w, y) arrive in c.tail_mail.host[y * W + w] with seq = first_seq + j;
 // after the last fold the tables (t_out elements each) go to c.h_results[slot + (3 y + t) * t_out ..) and every workgroup posts first_seq + rounds.
 // fold_r: the source tables hold 2 * len0 elements and are folded by *fold_r on load (nullptr: they hold len0 elements as they are).

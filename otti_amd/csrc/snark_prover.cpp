@@ -276,6 +276,29 @@ struct Circuits {
 };
 struct DotpTables { Fr *l[6], *r[6], *w[6]; size_t len = 0; int n = 0; };
 
+// The knobs of the layer plan (pc_plan.h).  The OTTI_PC_* switches are read once per process; what the device and the process's state allow, per call.
+PcKnobs pc_knobs(DevCtx &c) {
+    // OTTI_PC_TAIL=0 switches the persistent tail off; OTTI_PC_TAIL_CAP shrinks its per-workgroup capacity (tests: small instances then
+    // also take the route where the tail picks up tables that earlier launches folded in HBM)
+    static const bool tail_env = [] { const char *e = getenv("OTTI_PC_TAIL"); return !(e && e[0] == '0'); }();
+    static const size_t tail_cap = [] { const char *e = getenv("OTTI_PC_TAIL_CAP"); size_t v = e ? (size_t)atoi(e) : 0; return (v >= 2 && v <= (size_t)kTailCap && !(v & (v - 1))) ? v : (size_t)kTailCap; }();
+    static const size_t tail_per_wg = [] { const char *e = getenv("OTTI_PC_TAIL_PER_WG"); size_t v = e ? (size_t)atoi(e) : 0; return (v >= 16 && v <= (size_t)kTailCap && !(v & (v - 1))) ? v : (size_t)128; }();
+    static const size_t lgt_env_many = [] { const char *e = getenv("OTTI_PC_LGT_MANY"); return e ? (size_t)atoi(e) : (size_t)0; }();
+    static const size_t lgt_env_few = [] { const char *e = getenv("OTTI_PC_LGT_FEW"); return e ? (size_t)atoi(e) : (size_t)0; }();
+    static const size_t pc_arm_max = [] { const char *e = getenv("OTTI_PC_ARM_MAX"); return e ? (size_t)atoll(e) : (size_t)1 << 22; }();
+    PcKnobs k;
+    k.tail_cap = tail_cap; k.tail_per_wg = tail_per_wg; k.arm_max = pc_arm_max;
+    const bool fr8 = host_fr8_available();                  // the AVX-512 IFMA host tail: 6 / 7 rounds per layer; the scalar form: 4 / 5 (pc_plan.h)
+    k.lgt_many = lgt_env_many ? lgt_env_many : (fr8 ? 6 : 4); k.lgt_few = lgt_env_few ? lgt_env_few : (fr8 ? 7 : 5);
+    k.arm_ok = c.armed_ok();
+    k.tail_ok = k.arm_ok && tail_env && !g_tail_off.load(std::memory_order_relaxed) && !shard_comm_active();
+    k.tail_groups_max = std::min(kTailMaxGroups, c.num_cu);
+    return k;
+}
+// OTTI_PC_PREEXPORT=0: the layers the host plays alone are exported by a launch at the head of each, not ahead of time (pcbatch_prove)
+bool pc_preexport_env() { static const bool on = [] { const char *e = getenv("OTTI_PC_PREEXPORT"); return !(e && e[0] == '0'); }(); return on; }
+bool pc_trace_env() { static const bool on = getenv("OTTI_TRACE") != nullptr; return on; }
+
 // ProductCircuitEvalProofBatched::prove.  evals: the circuits' outputs (already known to the caller).  The tables are folded in place.
 //
 // One layer = one SumcheckInstanceProof::prove_cubic_batched over (left, right, eq(rand)) of every circuit (+ the dot-product triples at
@@ -285,7 +308,6 @@ struct DotpTables { Fr *l[6], *r[6], *w[6]; size_t len = 0; int n = 0; };
 // (two L2-resident pyramids of small tables, as phase one of the R1CS proof); the kernel returns S_t = sum_i E_j[i] (A_t B_t)[i] and the
 // host applies c_j * ((1 - rand_j) + t (2 rand_j - 1)).  Once the tables are down to T elements they are exported to pinned memory and
 // the host plays the last rounds itself: a launch + hand-off costs more than the arithmetic of such a round on a host core.
-constexpr int kPcPreExportEnd = 7400;                       // pre-exported host-only layers end below the hash layer's ahead-of-time results (kHashEvalSlot)
 // sh (sharded SNARK::prove): the tables are this rank's residue classes (Circuits above; D: strided copies); a device round works on them
 // with the eq factor taken at the global index, its sums are added across the ranks (allreduce_fr: 3 elements per instance), and where the
 // host takes a layer over the ranks' shares of its tables are gathered and interleaved.  Host rounds run on every rank alike.
@@ -298,54 +320,24 @@ ProductCircuitEvalProofBatched pcbatch_prove(DevCtx &c, Circuits &C, const std::
     std::vector<Fr> claims = evals, rand, rprod;
     const Fr one = fr_one();
     struct Release { DevCtx &c; ~Release() { c.go_abort(); } } release{c};      // an exception below must not leave an armed kernel waiting
-    const bool arm_ok = c.armed_ok();
-    // OTTI_PC_TAIL=0 switches the persistent tail off; OTTI_PC_TAIL_CAP shrinks its per-workgroup capacity (tests: small instances then
-    // also take the route where the tail picks up tables that earlier launches folded in HBM)
-    static const bool tail_env = [] { const char *e = getenv("OTTI_PC_TAIL"); return !(e && e[0] == '0'); }();
-    static const size_t tail_cap = [] { const char *e = getenv("OTTI_PC_TAIL_CAP"); size_t v = e ? (size_t)atoi(e) : 0; return (v >= 2 && v <= (size_t)kTailCap && !(v & (v - 1))) ? v : (size_t)kTailCap; }();
-    // elements of a table a workgroup of the tail starts with (it spreads wider only for what does not fit): fewer, busier workgroups mean fewer
-    // mail lines per round for the host to collect — the larger cost (tools/hosttail_variants.sh)
-    static const size_t tail_per_wg = [] { const char *e = getenv("OTTI_PC_TAIL_PER_WG"); size_t v = e ? (size_t)atoi(e) : 0; return (v >= 16 && v <= (size_t)kTailCap && !(v & (v - 1))) ? v : (size_t)128; }();
-    const bool tail_ok = arm_ok && tail_env && !g_tail_off.load(std::memory_order_relaxed) && !shard_comm_active();
-    // its grid (W workgroups per instance, one per CU: 96 KB of LDS each) must be resident as a whole: never more workgroups than the device has CUs
-    const int tail_groups_max = std::min(kTailMaxGroups, c.num_cu);
-    static const size_t lgt_env_many = [] { const char *e = getenv("OTTI_PC_LGT_MANY"); return e ? (size_t)atoi(e) : (size_t)0; }();
-    static const size_t lgt_env_few = [] { const char *e = getenv("OTTI_PC_LGT_FEW"); return e ? (size_t)atoi(e) : (size_t)0; }();
-    static const size_t pc_arm_max = [] { const char *e = getenv("OTTI_PC_ARM_MAX"); return e ? (size_t)atoll(e) : (size_t)1 << 22; }();     // (the sum-check kernels of the R1CS proof arm up to kArmMaxLen; here a round more or less ahead costs nothing else)
+    const PcKnobs knobs = pc_knobs(c);
     SpinPool &pool = SpinPool::get();
     const int host_threads = std::min(8, pool.workers() + 1);
-    // How many of a layer's last rounds the host plays (hosttail.h).  With the AVX-512 IFMA form a host round over tables of 32 / 64 elements costs
-    // less than the 16 us of a round of the persistent launch: the last 6 rounds of the 12- and 18-instance batches (tables of 64), the last 7 of
-    // the 4-instance batches (128); measured 4/5, 5/6, 5/7, 5/8, 6/7: product circuits 9.5, 9.1, 9.15, 9.3, 9.0 ms (tools/hosttail_variants.sh,
-    // profiles/r4_hosttail_variants.txt).  With the scalar form (no such instructions): 4 and 5 as before (5/7 cost 10.9-11.4 ms against 10.7).
-    const bool fr8 = host_fr8_available();
-    const size_t lgt_many = lgt_env_many ? lgt_env_many : (fr8 ? 6 : 4), lgt_few = lgt_env_few ? lgt_env_few : (fr8 ? 7 : 5);
-    static const bool trace = getenv("OTTI_TRACE") != nullptr;
+    const bool trace = pc_trace_env();
     double tr_tail_first_ms = 0, tr_tail_sum_ms = 0, tr_tail_wait_ms = 0, tr_tail_ms = 0, tr_launch_ms = 0, tr_host_ms = 0, tr_layer0_ms = 0; size_t tr_tail_rounds = 0, tr_launch_rounds = 0, tr_host_rounds = 0, tr_tail_layers = 0;
-    // what a layer's rounds are made of, decided from its position alone (so that the NEXT layer's first launches can be issued ahead of time)
-    struct Plan { size_t layer_id = 0, nr = 0, h = 1; bool with_dotp = false, on_device = true; PcList P; int ni = 0; size_t lgT = 0, T = 1, ndev = 0, k0 = 0; int tailW = 1; bool tail = false; };
+    // a layer's tables and, from its shape alone, what its rounds are made of (pc_plan.h)
+    struct Plan : PcLayerPlan { size_t layer_id; int ni; bool with_dotp, on_device; PcList P; };
+    auto shape_of = [&](size_t li_, size_t nr_) {
+        const size_t layer_id = nl - 1 - li_;
+        const bool with_dotp = layer_id == 0 && D && D->n;
+        return PcLayerShape{nr_, np + (with_dotp ? D->n : 0), layer_id < C.nl_dev};      // (sharded: the layers with sides shorter than the number of ranks exist on the host only)
+    };
     auto make_plan = [&](size_t li_, size_t nr_) {
-        Plan p; p.layer_id = nl - 1 - li_; p.nr = nr_; p.h = (size_t)1 << nr_;      // elements per side in this layer, one round per variable
-        p.with_dotp = p.layer_id == 0 && D && D->n;
-        p.on_device = p.layer_id < C.nl_dev;                     // (sharded: the layers with sides shorter than the number of ranks exist on the host only)
+        const PcLayerShape s = shape_of(li_, nr_);
+        Plan p{pc_layer_plan(s, knobs), nl - 1 - li_, s.ni, s.ni > np, s.on_device, {}};
         p.P.n = 0;
         for (int i = 0; i < np; i++) { p.P.A[p.P.n] = p.on_device ? C.left(i, p.layer_id) : nullptr; p.P.B[p.P.n] = p.on_device ? C.right(i, p.layer_id) : nullptr; p.P.C[p.P.n] = nullptr; p.P.n++; }
         if (p.with_dotp) for (int i = 0; i < D->n; i++) { p.P.A[p.P.n] = D->l[i]; p.P.B[p.P.n] = D->r[i]; p.P.C[p.P.n] = D->w[i]; p.P.n++; }
-        p.ni = p.P.n;
-        p.lgT = std::min<size_t>(nr_, p.ni >= 8 ? lgt_many : lgt_few); p.T = (size_t)1 << p.lgT; p.ndev = nr_ - p.lgT;
-        // The persistent tail (k_pc_tail, snark_dev.h): from round k0 on — the first round whose tables fit the LDS of W workgroups per
-        // instance — ONE launch plays every remaining device round.  Only while this is the process's single proof in flight (its grid
-        // must be resident as a whole: the workgroups wait for the host, the host for all of them) and no kernel class it belongs to is
-        // being timed; otherwise, and for the rounds before k0, a launch per round as before.
-        p.k0 = p.ndev; p.tailW = 1;
-        if (p.ndev && tail_ok && p.ni <= tail_groups_max) {
-            int Wmax = 1; while (2 * Wmax * p.ni <= tail_groups_max && (size_t)(2 * Wmax) <= p.T) Wmax *= 2;
-            const size_t cap_all = tail_cap * (size_t)Wmax;
-            p.k0 = 0; while ((p.h >> p.k0) > cap_all) p.k0++;
-            if (p.k0 >= p.ndev) p.k0 = p.ndev;                   // (cannot happen for cap_all >= 2 T; kept for a shrunken test capacity)
-            else { const size_t len0 = p.h >> p.k0; p.tailW = 1; while (p.tailW < Wmax && len0 / (size_t)p.tailW > tail_per_wg) p.tailW *= 2; while (len0 / (size_t)p.tailW > tail_cap) p.tailW *= 2; }
-        }
-        p.tail = p.k0 < p.ndev;
         return p;
     };
     // eq(rand[1..], .) of a layer with nr variables as the round kernels read it: pyramids over the last n_lo of rand[1..] and the n_hi before them
@@ -371,98 +363,97 @@ ProductCircuitEvalProofBatched pcbatch_prove(DevCtx &c, Circuits &C, const std::
     // queued here, each to a place of its own — not one launch and one wait at the head of each layer (layer li has li variables whatever the
     // challenges are).  on_start (the caller's work for a second stream) is queued after them, so that they are not held up behind it.
     // OTTI_PC_PREEXPORT=0: a launch per layer as before.
-    static const bool preexport_env = [] { const char *e = getenv("OTTI_PC_PREEXPORT"); return !(e && e[0] == '0'); }();
     std::vector<unsigned long long> pre_tick(nl, 0); std::vector<int> pre_slot(nl, kPcTailSlot);
-    if (!sh && preexport_env) {
-        size_t at = kPcTailSlot;
+    if (!sh && pc_preexport_env()) {
+        PcPreExport pre;
         for (size_t li = 0; li < nl; li++) {
+            const int slot = pre.take(shape_of(li, li), knobs);
+            if (slot < 0) break;
             const Plan p = make_plan(li, li);
-            const size_t need = (size_t)3 * p.ni * p.h;
-            if (p.ndev || !p.on_device || at + need > (size_t)kPcPreExportEnd) break;
-            pre_slot[li] = (int)at; pre_tick[li] = dev_pc_export(c, p.P, p.h, false, nullptr, (int)at); at += need;
+            pre_slot[li] = slot; pre_tick[li] = dev_pc_export(c, p.P, p.h, false, nullptr, slot);
         }
     }
     if (on_start) (*on_start)();
     for (size_t li = 0; li < nl; li++) {
         const double tr_layer_start = trace ? now_ms() : 0;
-        Plan plan = make_plan(li, rand.size());
-        const size_t layer_id = plan.layer_id, nr = plan.nr, h = plan.h, lgT = plan.lgT, T = plan.T, ndev = plan.ndev, k0 = plan.k0;
-        const bool with_dotp = plan.with_dotp, on_device = plan.on_device, tail = plan.tail;
-        const PcList &P = plan.P; const int ni = plan.ni, tailW = plan.tailW;
-        (void)lgT;
-        if (with_dotp) { if (D->len != h / G) throw Error(OTTI_ERR_INTERNAL, "dot-product circuits do not match the input layer"); claims.insert(claims.end(), dotp_evals.begin(), dotp_evals.end()); }
-        if (sh && ndev && (T < G || !on_device)) throw Error(OTTI_ERR_INTERNAL, "sharded product circuits: more ranks than a host tail has elements");
+        const Plan plan = make_plan(li, rand.size());
+        if (plan.with_dotp) { if (D->len != plan.h / G) throw Error(OTTI_ERR_INTERNAL, "dot-product circuits do not match the input layer"); claims.insert(claims.end(), dotp_evals.begin(), dotp_evals.end()); }
+        if (sh && plan.ndev && (plan.T < G || !plan.on_device)) throw Error(OTTI_ERR_INTERNAL, "sharded product circuits: more ranks than a host tail has elements");
         unsigned long long tail_seq = 0;
         // The layer's FIRST variable is in no pyramid: no round's factor table contains it (round j uses eq over rand[j+1..]), only the persistent
         // tail's own eq table when it starts at round 0 (EqSrc.top) — and rand[0] is the last challenge to be drawn, so without it the pyramids of
         // layer li + 1 (and its first round's kernel, when that is a launch of its own) are issued as soon as layer li's last round challenge is
         // out (below) and run while the host absorbs the layer's claims and draws the next coefficients.
-        if (ndev && !pyr_ahead) launch_pyramids(nr, rand.data() + 1);
+        if (plan.ndev && !pyr_ahead) launch_pyramids(plan.nr, rand.data() + 1);
         pyr_ahead = false;
-        auto eq_src = [&](size_t m) { return eq_src_of(nr, m, nr ? rand.data() : nullptr); };
-        // launch k >= 1 folds by r_{k-1} and yields the sums of round k (k < ndev) or the exported tail (k == ndev).  Armed (device.h), it is
-        // queued one round ahead and starts the moment the host publishes r_{k-1}.
-        auto armed = [&](size_t k) { return arm_ok && k >= 1 && k < k0 + (tail ? 0 : 1) && k <= ndev && (h >> (k - 1)) * (size_t)ni <= pc_arm_max; };   // small grids only (device.h); never the tail's own launch
-        std::vector<unsigned long long> tick(ndev + 2, 0);
-        auto launch_tail = [&](const Fr *r) { tail_seq = dev_pc_tail(c, P, tailW, h >> k0, T, r, eq_src(nr - k0), kPcTailSlot); };
+        auto eq_src = [&](size_t m) { return eq_src_of(plan.nr, m, plan.nr ? rand.data() : nullptr); };
+        auto armed = [&](size_t k) { return plan.armed(k, plan.ni, knobs); };      // launch k is queued a round ahead of its challenge (pc_plan.h)
+        std::vector<unsigned long long> tick(plan.ndev + 2, 0);
+        auto launch_tail = [&](const Fr *r) { tail_seq = dev_pc_tail(c, plan.P, plan.tailW, plan.h >> plan.k0, plan.T, r, eq_src(plan.nr - plan.k0), kPcTailSlot); };
         auto launch_for = [&](size_t k, const Fr *r) {
-            const size_t len_in = (h >> (k - 1)) / G;         // of this rank
-            if (tail && k == k0) { launch_tail(r); return; }
-            tick[k] = k < ndev ? dev_pc_fold_eval(c, P, len_in, r, eq_src(nr - k - 1), kSumSlot) : dev_pc_export(c, P, len_in, true, r, kPcTailSlot);
+            const size_t len_in = (plan.h >> (k - 1)) / G;         // of this rank
+            if (plan.tail && k == plan.k0) { launch_tail(r); return; }
+            tick[k] = k < plan.ndev ? dev_pc_fold_eval(c, plan.P, len_in, r, eq_src(plan.nr - k - 1), kSumSlot) : dev_pc_export(c, plan.P, len_in, true, r, kPcTailSlot);
         };
-        if (tail && k0 == 0) launch_tail(nullptr);
-        else if (ndev) { tick[0] = eval_ahead ? eval_ahead_tick : dev_pc_eval(c, P, h / G, eq_src(nr - 1), kSumSlot); if (armed(1)) launch_for(1, nullptr); }
-        else if (!sh) tick[0] = pre_tick[li] ? pre_tick[li] : dev_pc_export(c, P, h, false, nullptr, kPcTailSlot);     // (sharded: the host-only layers are in C.small already)
-        const int layer_slot = (!ndev && pre_tick[li]) ? pre_slot[li] : kPcTailSlot;      // where this layer's exported tables are
+        if (plan.round(0) == PcRound::tail) launch_tail(nullptr);
+        else if (plan.ndev) { tick[0] = eval_ahead ? eval_ahead_tick : dev_pc_eval(c, plan.P, plan.h / G, eq_src(plan.nr - 1), kSumSlot); if (armed(1)) launch_for(1, nullptr); }
+        else if (!sh) tick[0] = pre_tick[li] ? pre_tick[li] : dev_pc_export(c, plan.P, plan.h, false, nullptr, kPcTailSlot);     // (sharded: the host-only layers are in C.small already)
+        const int layer_slot = (!plan.ndev && pre_tick[li]) ? pre_slot[li] : kPcTailSlot;      // where this layer's exported tables are
         eval_ahead = false;
         std::vector<Fr> coeff = tr.challenge_vector("rand_coeffs_next_layer", claims.size());
         Fr e = fr_zero(); for (size_t k = 0; k < claims.size(); k++) e = fr_add(e, fr_mul(claims[k], coeff[k]));
         LayerProofBatched &L = pf.layers[li];
         rprod.clear();
-        std::vector<std::vector<Fr>> tA(ni), tB(ni), tC(ni); std::vector<Fr> tE; bool tail_built = false;   // host tail: T elements per table
+        std::vector<std::vector<Fr>> tA(plan.ni), tB(plan.ni), tC(plan.ni); std::vector<Fr> tE; bool tail_built = false;   // host tail: T elements per table
         std::unique_ptr<HostTail> host_tail;
         Fr cj = one, cj_tail = one;                         // cj_tail: the eq factor accumulated before the tail took over (its eq table carries the rest)
-        if (trace) { tr_layer0_ms += now_ms() - tr_layer_start; if (tail) tr_tail_layers++; }
-        for (size_t j = 0; j < nr; j++) {                    // SumcheckInstanceProof::prove_cubic_batched
+        if (trace) { tr_layer0_ms += now_ms() - tr_layer_start; if (plan.tail) tr_tail_layers++; }
+        for (size_t j = 0; j < plan.nr; j++) {                    // SumcheckInstanceProof::prove_cubic_batched
             const double tr_round_start = trace ? now_ms() : 0;
             Fr c0 = fr_zero(), c2 = fr_zero(), c3 = fr_zero();
-            if (j < ndev && tail && j >= k0) {
+            const PcRound kind = plan.round(j);
+            switch (kind) {
+            case PcRound::tail: {
                 // a round of the persistent launch: W partial sums per instance, in the workgroups' own mail lines; the eq table is a real
                 // third table there, so the sums already carry the bound variable's factor — only the factor of the rounds before k0 is missing
-                if (j == k0) cj_tail = cj;
+                if (j == plan.k0) cj_tail = cj;
                 Fr inst_sums[3 * kMaxInst];
                 {
                     const double tw = trace ? now_ms() : 0;
-                    if (trace) { c.wait_tail(1, tail_seq + (j - k0)); tr_tail_first_ms += now_ms() - tw; }     // (trace only: when the first line is in)
-                    c.wait_tail_sums(ni, tailW, tail_seq + (j - k0), inst_sums);
+                    if (trace) { c.wait_tail(1, tail_seq + (j - plan.k0)); tr_tail_first_ms += now_ms() - tw; }     // (trace only: when the first line is in)
+                    c.wait_tail_sums(plan.ni, plan.tailW, tail_seq + (j - plan.k0), inst_sums);
                     if (trace) tr_tail_wait_ms += now_ms() - tw;
                 }
                 Fr ps[3], ds[3];                                      // the product instances' sums (they share the eq factor) and the triples', times the coefficients
-                weighted_sums3(inst_sums, coeff.data(), np, ni, ps, ds);
+                weighted_sums3(inst_sums, coeff.data(), np, plan.ni, ps, ds);
                 c0 = fr_add(ds[0], fr_mul(cj_tail, ps[0])); c2 = fr_add(ds[1], fr_mul(cj_tail, ps[1])); c3 = fr_add(ds[2], fr_mul(cj_tail, ps[2]));
                 if (trace) tr_tail_sum_ms += now_ms() - tr_round_start;
-            } else if (j < ndev) {
+                break;
+            }
+            case PcRound::launch: {
                 c.wait_ticket(tick[j]);
-                if (sh) sh->allreduce_fr(&c.h_results[kSumSlot], (size_t)3 * ni);      // this round's sums over the ranks' residue classes (pinned memory: the next launch writes them afresh)
+                if (sh) sh->allreduce_fr(&c.h_results[kSumSlot], (size_t)3 * plan.ni);      // this round's sums over the ranks' residue classes (pinned memory: the next launch writes them afresh)
                 const Fr &tau = rand[j];
                 const Fr w0 = fr_sub(one, tau), dw = fr_sub(fr_add(tau, tau), one), w2 = fr_add(w0, fr_add(dw, dw)), w3 = fr_add(w2, dw);
                 const Fr f0 = fr_mul(cj, w0), f2 = fr_mul(cj, w2), f3 = fr_mul(cj, w3);
                 Fr ps[3], ds[3];                                      // the product circuits share the eq factor
-                weighted_sums3(&c.h_results[kSumSlot], coeff.data(), np, ni, ps, ds);
+                weighted_sums3(&c.h_results[kSumSlot], coeff.data(), np, plan.ni, ps, ds);
                 c0 = fr_add(ds[0], fr_mul(f0, ps[0])); c2 = fr_add(ds[1], fr_mul(f2, ps[1])); c3 = fr_add(ds[2], fr_mul(f3, ps[2]));
-            } else {
+                break;
+            }
+            case PcRound::host: {
                 if (!tail_built) {
                     bool direct = false;
-                    if (sh && ndev == 0) {                          // a layer the host plays alone: in full on every rank already (product circuits only)
-                        if (C.small[layer_id].size() != (size_t)ni || C.small[layer_id][0].first.size() != T) throw Error(OTTI_ERR_INTERNAL, "sharded product circuits: a host-played layer was not gathered (host tail longer than kSmallSide)");
-                        for (int k = 0; k < ni; k++) { tA[k] = C.small[layer_id][k].first; tB[k] = C.small[layer_id][k].second; }
+                    if (sh && plan.ndev == 0) {                          // a layer the host plays alone: in full on every rank already (product circuits only)
+                        if (C.small[plan.layer_id].size() != (size_t)plan.ni || C.small[plan.layer_id][0].first.size() != plan.T) throw Error(OTTI_ERR_INTERNAL, "sharded product circuits: a host-played layer was not gathered (host tail longer than kSmallSide)");
+                        for (int k = 0; k < plan.ni; k++) { tA[k] = C.small[plan.layer_id][k].first; tB[k] = C.small[plan.layer_id][k].second; }
                     } else if (sh) {                                // every rank's share of the exported tables, interleaved: element e of rank r is element e G + r
-                        c.wait_ticket(tick[ndev]);
-                        const size_t Tl = T / G, per = (size_t)3 * ni * Tl;
+                        c.wait_ticket(tick[plan.ndev]);
+                        const size_t Tl = plan.T / G, per = (size_t)3 * plan.ni * Tl;
                         std::vector<Fr> all(per * G);
                         sh->allgather(&c.h_results[kPcTailSlot], per * sizeof(Fr), all.data());
-                        for (int k = 0; k < ni; k++) {
-                            tA[k].resize(T); tB[k].resize(T); if (k >= np) tC[k].resize(T);
+                        for (int k = 0; k < plan.ni; k++) {
+                            tA[k].resize(plan.T); tB[k].resize(plan.T); if (k >= np) tC[k].resize(plan.T);
                             for (size_t r = 0; r < G; r++) for (size_t e = 0; e < Tl; e++) {
                                 const Fr *base = &all[r * per + (size_t)3 * k * Tl];
                                 tA[k][e * G + r] = base[e]; tB[k][e * G + r] = base[Tl + e];
@@ -470,72 +461,72 @@ ProductCircuitEvalProofBatched pcbatch_prove(DevCtx &c, Circuits &C, const std::
                             }
                         }
                     } else {
-                    if (tail) c.wait_tail(ni * tailW, tail_seq + (ndev - k0)); else c.wait_ticket(tick[ndev]);
+                    if (plan.tail) c.wait_tail(plan.ni * plan.tailW, tail_seq + (plan.ndev - plan.k0)); else c.wait_ticket(tick[plan.ndev]);
                     direct = true;                                  // the host tail packs the tables straight out of the pinned buffer the device exported them to
                     }
-                    tE = eq_evals_host(rand.data() + ndev, nr - ndev);
+                    tE = eq_evals_host(rand.data() + plan.ndev, plan.nr - plan.ndev);
                     for (auto &x : tE) x = fr_mul(x, cj);
-                    std::vector<const Fr *> pa(ni), pb(ni), pc(ni);
-                    for (int k = 0; k < ni; k++) {
-                        const Fr *base = &c.h_results[layer_slot + (size_t)3 * k * T];
-                        pa[k] = direct ? base : tA[k].data(); pb[k] = direct ? base + T : tB[k].data(); pc[k] = k < np ? nullptr : direct ? base + 2 * T : tC[k].data();
+                    std::vector<const Fr *> pa(plan.ni), pb(plan.ni), pc(plan.ni);
+                    for (int k = 0; k < plan.ni; k++) {
+                        const Fr *base = &c.h_results[layer_slot + (size_t)3 * k * plan.T];
+                        pa[k] = direct ? base : tA[k].data(); pb[k] = direct ? base + plan.T : tB[k].data(); pc[k] = k < np ? nullptr : direct ? base + 2 * plan.T : tC[k].data();
                     }
-                    host_tail = HostTail::make(np, ni - np, T, pa.data(), pb.data(), pc.data(), tE.data(), coeff.data(), host_threads);   // hosttail.h: AVX-512 IFMA where the CPU has it
+                    host_tail = HostTail::make(np, plan.ni - np, plan.T, pa.data(), pb.data(), pc.data(), tE.data(), coeff.data(), host_threads);   // hosttail.h: AVX-512 IFMA where the CPU has it
                     tail_built = true;
                 }
                 Fr hs[3]; host_tail->sums(hs);
                 c0 = hs[0]; c2 = hs[1]; c3 = hs[2];
+                break;
+            }
             }
             Fr evals4[4] = {c0, fr_sub(e, c0), c2, c3}, poly[4];
             unipoly_from_evals(poly, evals4, 4);
             append_unipoly(tr, poly, 4);
             const Fr r_j = tr.challenge_scalar("challenge_nextround");
             rprod.push_back(r_j);
-            if (j + 1 == nr && li + 1 < nl && j >= ndev) {
+            if (j + 1 == plan.nr && li + 1 < nl && kind == PcRound::host) {
                 // the layer's last challenge: everything the NEXT layer's eq pyramids are made of (its variables 1 .. nr are this layer's challenges; its
                 // variable 0 comes after the claims below and is in no pyramid).  The device is idle — this layer's last rounds are the host's — so
                 // the pyramids, and the next layer's first sums when they are a launch of their own (they read tables and pyramids only), run under
                 // the host's closing work and the next layer's coefficient draws instead of in front of its first round.
-                const Plan nx = make_plan(li + 1, nr + 1);
+                const Plan nx = make_plan(li + 1, plan.nr + 1);
                 if (nx.ndev) {
                     launch_pyramids(nx.nr, rprod.data());
                     pyr_ahead = true;
-                    if (!(nx.tail && nx.k0 == 0) && !(sh && (nx.T < G || !nx.on_device))) {
+                    if (nx.round(0) != PcRound::tail && !(sh && (nx.T < G || !nx.on_device))) {
                         eval_ahead_tick = dev_pc_eval(c, nx.P, nx.h / G, eq_src_of(nx.nr, nx.nr - 1, nullptr), kSumSlot);
                         eval_ahead = true;
                     }
                 }
             }
-            if (j < ndev) {
-                if (tail && j >= k0) c.go(&r_j, 1);              // the persistent launch folds and goes on (or exports, after its last round)
-                else {
-                    if (armed(j + 1)) c.go(&r_j, 1); else launch_for(j + 1, &r_j);
-                    if (armed(j + 2)) launch_for(j + 2, nullptr);
-                }
+            if (kind == PcRound::tail) c.go(&r_j, 1);              // the persistent launch folds and goes on (or exports, after its last round)
+            else if (kind == PcRound::launch) {
+                if (armed(j + 1)) c.go(&r_j, 1); else launch_for(j + 1, &r_j);
+                if (armed(j + 2)) launch_for(j + 2, nullptr);
             }
-            if (j < ndev) cj = fr_mul(cj, fr_add(fr_mul(rand[j], r_j), fr_mul(fr_sub(one, rand[j]), fr_sub(one, r_j))));
+            if (kind != PcRound::host) cj = fr_mul(cj, fr_add(fr_mul(rand[j], r_j), fr_mul(fr_sub(one, rand[j]), fr_sub(one, r_j))));
             else host_tail->fold(r_j);
             e = unipoly_eval(poly, 4, r_j);
             L.coeffs.push_back(poly[0]); L.coeffs.push_back(poly[2]); L.coeffs.push_back(poly[3]);      // UniPoly::compress
             if (trace) {
                 const double dt = now_ms() - tr_round_start;
-                if (j < ndev && tail && j >= k0) { tr_tail_ms += dt; tr_tail_rounds++; } else if (j < ndev) { tr_launch_ms += dt; tr_launch_rounds++; } else { tr_host_ms += dt; tr_host_rounds++; }
+                if (kind == PcRound::tail) { tr_tail_ms += dt; tr_tail_rounds++; } else if (kind == PcRound::launch) { tr_launch_ms += dt; tr_launch_rounds++; } else { tr_host_ms += dt; tr_host_rounds++; }
             }
         }
         if (host_tail) {                                    // the tables' last elements, out of the host tail's own representation
             if (host_tail->len() != 1) throw Error(OTTI_ERR_INTERNAL, "host sum-check tail ended early");
-            for (int k = 0; k < ni; k++) { Fr t3[3]; host_tail->last(k, t3); tA[k].assign(1, t3[0]); tB[k].assign(1, t3[1]); if (k >= np) tC[k].assign(1, t3[2]); }
+            for (int k = 0; k < plan.ni; k++) { Fr t3[3]; host_tail->last(k, t3); tA[k].assign(1, t3[0]); tB[k].assign(1, t3[1]); if (k >= np) tC[k].assign(1, t3[2]); }
         }
         if (!tail_built && sh) {                             // a layer without rounds, sharded: from the host copies
-            for (int k = 0; k < ni; k++) { tA[k].assign(1, C.small[layer_id][k].first[0]); tB[k].assign(1, C.small[layer_id][k].second[0]); }
+            for (int k = 0; k < plan.ni; k++) { tA[k].assign(1, C.small[plan.layer_id][k].first[0]); tB[k].assign(1, C.small[plan.layer_id][k].second[0]); }
         } else if (!tail_built) {                            // a layer without rounds: the tables are single elements
             c.wait_ticket(tick[0]);
-            for (int k = 0; k < ni; k++) { const Fr *base = &c.h_results[layer_slot + (size_t)3 * k * T]; tA[k].assign(base, base + 1); tB[k].assign(base + T, base + T + 1); if (k >= np) tC[k].assign(base + 2 * T, base + 2 * T + 1); }
+            for (int k = 0; k < plan.ni; k++) { const Fr *base = &c.h_results[layer_slot + (size_t)3 * k * plan.T]; tA[k].assign(base, base + 1); tB[k].assign(base + plan.T, base + plan.T + 1); if (k >= np) tC[k].assign(base + 2 * plan.T, base + 2 * plan.T + 1); }
         }
         // the tables' last elements: claims_prod (left, right per circuit; the eq table's is not sent), then the dot-product triples
         L.left.resize(np); L.right.resize(np);
         for (int i = 0; i < np; i++) { L.left[i] = tA[i][0]; L.right[i] = tB[i][0]; tr.append_scalar("claim_prod_left", L.left[i]); tr.append_scalar("claim_prod_right", L.right[i]); }
-        if (with_dotp) for (int i = 0; i < D->n; i++) {
+        if (plan.with_dotp) for (int i = 0; i < D->n; i++) {
             const Fr t[3] = {tA[np + i][0], tB[np + i][0], tC[np + i][0]};
             pf.dotp_left.push_back(t[0]); pf.dotp_right.push_back(t[1]); pf.dotp_weight.push_back(t[2]);
             tr.append_scalar("claim_dotp_left", t[0]); tr.append_scalar("claim_dotp_right", t[1]); tr.append_scalar("claim_dotp_weight", t[2]);
@@ -862,7 +853,6 @@ static std::vector<uint8_t> snark_prove_resident_once(Instance &I, CompComm &com
     const bool hash_fused = hash_fused_env && g.derefs.num_vars == lgN_ + 3 && g.ops.num_vars == lgN_ + 4 && g.derefs.num_vars / 2 > 3 && g.ops.num_vars / 2 > 4 && g.derefs.L * g.derefs.R == 8 * N && g.ops.L * g.ops.R == 16 * N;
     const bool hash_ahead = hash_fused && hash_ahead_env && !sh && c.side_stream();
     Fr *chunks_d = nullptr, *chunks_o = nullptr;
-    constexpr int kHashEvalSlot = kPcPreExportEnd;                        // result slots of the 21 evaluations (clear of the round sums and the exported tails)
     bool hash_evals_queued = false;
     // work queued on the second stream uses this context's buffers: an exception on the way to the hash layer must not let the context go back to the pool under it
     struct SideDrain { DevCtx &c; bool pending = false; ~SideDrain() { if (pending && c.ev_side) (void)hipEventSynchronize(c.ev_side); } } side_drain{c};
