@@ -226,6 +226,36 @@ int32_t otti_witness_drop_rows(otti_witness *wit);
 /* *kept: 0 or 1; *L, *R: the geometry of the kept rows (0 when none are kept); *rows_resummed: rows summed again by updates since keep_rows.
    Any out pointer may be NULL.  A null wit is OTTI_ERR_BAD_ARG; without a device no witness exists: OTTI_ERR_NO_DEVICE, wit is not looked at. */
 int32_t otti_witness_rows_info(const otti_witness *wit, int32_t *kept, size_t *L, size_t *R, uint64_t *rows_resummed);
+/* ---- kept products: a resident witness may own Az, Bz, Cz — the row sums <A_r,z>, <B_r,z>, <C_r,z> of its assignment over ONE instance's matrices
+   (N = padded num_cons Montgomery elements each, bit for bit what otti_k_multiply_vec gives for the resident z) — with the satisfiability verdict
+   of every row (the bitmap of otti_kd_check_sat's layout) and the number of failing rows.  Opt-in per witness; costs 96 * N + N / 8 bytes of HBM.
+   The sums are linear in z, and a changed variable j moves only the rows that have an entry in column j.  So once a mutator has written z it
+   brings the kept products up to date by recomputing the touched rows alone — otti_witness_update by its range, otti_witness_scatter by its index
+   list, otti_witness_assign by the list of elements that changed (nothing changed: nothing launched), otti_witness_set_inputs by the range
+   V + 1 .. V + ninputs (inputs are columns of z too) — or, when at least a share of the N rows is touched, by the full pass again
+   (profiles/witness_products.md; OTTI_PRODUCTS_FULL_SHARE, read per call, overrides the share: 0 always takes the full pass, >= 1 never).
+   otti_nizk_prove_resident and otti_snark_prove_resident over that instance then copy the three vectors instead of forming them, and
+   otti_witness_check_sat answers from the kept count and bitmap without a pass (kernel_ms: the report launches for failing rows, 0 if none).
+   Proofs and reports are byte-identical with and without kept products.  Sharded provers ignore them (their rows are renumbered per rank), and
+   a proof or check with ANOTHER instance computes as without and leaves them alone.
+   otti_witness_keep_products runs the full pass now and returns when the products are resident; again for the same instance: OTTI_OK, nothing done;
+   for another instance: the old products are dropped and new ones formed.  The instance must outlive the kept products
+   (otti_witness_drop_products / otti_witness_free).  A mutator called with another instance than the one the products were kept for returns
+   OTTI_ERR_BAD_ARG and changes nothing; any refused mutator call leaves products, bitmap, count and counters exactly as they were (every refusal is
+   decided before z is written).  keep_products, drop_products and the mutators never run beside a proof or check with this witness; proofs and
+   checks only read, so any number of threads may prove or check from one witness that keeps products.  If a patch cannot run (HBM is short), the
+   error is returned with z updated and the products dropped.
+   OTTI_ERR_BAD_ARG: a null handle, before any device is touched; then OTTI_ERR_NO_DEVICE; OTTI_ERR_INVALID_NUM_VARS: the witness was uploaded for
+   an instance of other dimensions. */
+int32_t otti_witness_keep_products(otti_instance *inst, otti_witness *wit);
+/* frees the kept products: from then on the witness proves, checks and counts as one that never kept them (none kept: OTTI_OK) */
+int32_t otti_witness_drop_products(otti_witness *wit);
+/* *kept: 0 or 1; *n_rows: N (0 when none are kept); *d_Az, *d_Bz, *d_Cz: the kept vectors, device pointers usable with otti_kd_* and
+   otti_dev_download (read only; NULL when none are kept); *n_unsat: the failing rows; since keep_products: *patches that recomputed listed rows,
+   the *rows_recomputed by them, and *full_passes (the first one included).  Any out pointer may be NULL.  A null wit is OTTI_ERR_BAD_ARG; without
+   a device no witness exists: OTTI_ERR_NO_DEVICE, wit is not looked at. */
+int32_t otti_witness_products_info(const otti_witness *wit, int32_t *kept, size_t *n_rows, const void **d_Az, const void **d_Bz, const void **d_Cz,
+                                   uint64_t *n_unsat, uint64_t *patches, uint64_t *rows_recomputed, uint64_t *full_passes);
 /* ---- scatter update: variables idx[0 .. count) of a resident witness replaced by src[0 .. count) (format / stride_bytes as otti_witness_update).
    For a caller whose step changes scattered variables (the touched coordinates of an iterate, a handful of cells of a compiled witness): one call,
    whatever rows the indices fall in.  idx: 8-byte unsigned indices, STRICTLY ASCENDING (so none twice), each below the padded num_vars.
@@ -351,6 +381,14 @@ int32_t otti_k_fr_from_canonical(const uint8_t *h_in, uint8_t *h_out, size_t n);
 int32_t otti_k_fr_to_canonical(const uint8_t *h_in, uint8_t *h_out, size_t n);
 /* R1CSInstance::multiply_vec: z has 2*num_vars entries; outputs num_cons entries each */
 int32_t otti_k_multiply_vec(otti_instance *inst, const uint8_t *h_z, uint8_t *h_Az, uint8_t *h_Bz, uint8_t *h_Cz, float *kernel_ms);
+/* the patch of kept products on a caller's host state.  h_cols: ncols strictly ascending z indices below 2 * padded num_vars (else
+   OTTI_ERR_INVALID_INDEX, judged on the host before anything is staged), or NULL with the range [first, first + count); the io vectors are N
+   Montgomery elements each, io_bits ceil(N / 64) words, *io_unsat the count that goes with them: they are patched for z = h_z_new exactly as a
+   mutator would patch kept products.  h_rows (room for n_rows_cap): the touched rows, ascending; *n_touched their number; *took_full_pass as
+   decided by the rule / OTTI_PRODUCTS_FULL_SHARE. */
+int32_t otti_k_products_patch(otti_instance *inst, const uint8_t *h_z_new, const uint64_t *h_cols, size_t ncols, size_t first, size_t count,
+                              uint8_t *io_Az, uint8_t *io_Bz, uint8_t *io_Cz, uint64_t *io_bits, uint64_t *io_unsat,
+                              uint32_t *h_rows, size_t n_rows_cap, uint64_t *n_touched, int32_t *took_full_pass, float *kernel_ms);
 /* compute_eval_table_sparse x3 fused with r_A*A + r_B*B + r_C*C: eq_rx has num_cons entries, out 2*num_vars */
 int32_t otti_k_eval_table_sparse(otti_instance *inst, const uint8_t *h_eq_rx, const uint8_t *h_rABC /* 3 */, uint8_t *h_out, float *kernel_ms);
 /* which of their variants the three sparse passes above and below (multiply_vec / the satisfiability pass: by_col = 0; eval_table_sparse:

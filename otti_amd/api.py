@@ -100,6 +100,10 @@ _sig("otti_witness_keep_rows", _i32, _vp, _vp, _vp)
 _sig("otti_witness_keep_rows_snark", _i32, _vp, _vp, _vp)
 _sig("otti_witness_drop_rows", _i32, _vp)
 _sig("otti_witness_rows_info", _i32, _vp, ctypes.POINTER(_i32), ctypes.POINTER(_sz), ctypes.POINTER(_sz), ctypes.POINTER(_u64))
+_sig("otti_witness_keep_products", _i32, _vp, _vp)
+_sig("otti_witness_drop_products", _i32, _vp)
+_sig("otti_witness_products_info", _i32, _vp, ctypes.POINTER(_i32), ctypes.POINTER(_sz), ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+     ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64))
 _sig("otti_witness_check_sat", _i32, _vp, _vp, ctypes.POINTER(_u64), _vp, _sz, _vp, ctypes.POINTER(ctypes.c_float))
 _sig("otti_nizk_prove_resident", _i32, _vp, _vp, _vp, ctypes.c_char_p, _sz, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_sz),
      ctypes.POINTER(ctypes.c_double))
@@ -148,6 +152,7 @@ _sig("otti_k_addr_timestamps", _i32, _vp, _sz, _sz, _vp, _vp, _fp)
 _sig("otti_k_fr_to_canonical", _i32, _vp, _vp, _sz)
 _sig("otti_k_multiply_vec", _i32, _vp, _vp, _vp, _vp, _vp, _fp)
 _sig("otti_k_eval_table_sparse", _i32, _vp, _vp, _vp, _vp, _fp)
+_sig("otti_k_products_patch", _i32, _vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, ctypes.POINTER(_u64), _vp, _sz, ctypes.POINTER(_u64), ctypes.POINTER(_i32), _fp)
 _sig("otti_instance_device_info", _i32, _vp, _i32, ctypes.POINTER(_DeviceInfo))
 _sig("otti_k_eq_evals", _i32, _vp, _sz, _vp, _fp)
 _sig("otti_k_fold_top", _i32, _vp, _sz, _vp, _vp, _fp)
@@ -649,6 +654,29 @@ class Witness:
         _check(lib.otti_witness_rows_info(self._h, ctypes.byref(k), ctypes.byref(L), ctypes.byref(R), ctypes.byref(n)))
         return bool(k.value), L.value, R.value, n.value
 
+    def keep_products(self, inst):
+        """Form Az, Bz, Cz, the verdict bitmap and the failing count of this assignment over ``inst`` now and keep them with the witness
+        (otti_witness_keep_products).  Every mutator then recomputes only the rows its changed variables reach; proofs over ``inst`` copy the
+        vectors instead of forming them and check_sat answers without a pass.  Proof bytes do not change.  Costs 96 * N + N / 8 bytes of HBM."""
+        _check(lib.otti_witness_keep_products(inst._h, self._h))
+        self._products_inst = inst                                # the patches read this instance's matrices: it outlives the kept products
+
+    def drop_products(self):
+        """Free the kept products (otti_witness_drop_products); the witness then proves and checks as one that never kept them"""
+        _check(lib.otti_witness_drop_products(self._h))
+        self._products_inst = None
+
+    def products_info(self):
+        """dict(kept, n_rows, d_Az, d_Bz, d_Cz, n_unsat, patches, rows_recomputed, full_passes) (otti_witness_products_info); the three device
+        addresses are read-only and None when nothing is kept"""
+        k, n = _i32(), _sz()
+        a, b, c = _vp(), _vp(), _vp()
+        u, pt, rr, fp = _u64(), _u64(), _u64(), _u64()
+        _check(lib.otti_witness_products_info(self._h, ctypes.byref(k), ctypes.byref(n), ctypes.byref(a), ctypes.byref(b), ctypes.byref(c),
+                                              ctypes.byref(u), ctypes.byref(pt), ctypes.byref(rr), ctypes.byref(fp)))
+        return dict(kept=bool(k.value), n_rows=n.value, d_Az=a.value, d_Bz=b.value, d_Cz=c.value, n_unsat=u.value, patches=pt.value,
+                    rows_recomputed=rr.value, full_passes=fp.value)
+
     def check_sat(self, inst, max_rows=64, values=True):
         """Instance::is_sat on the device, on this resident assignment, with the failing constraints named (otti_witness_check_sat)"""
         n, ms = _u64(), ctypes.c_float()
@@ -1030,6 +1058,24 @@ class kernels:
         o = [np.zeros((nc, 32), dtype=np.uint8) for _ in range(3)]; ms = ctypes.c_float(0)
         _check(lib.otti_k_multiply_vec(inst._h, _ptr(z), _ptr(o[0]), _ptr(o[1]), _ptr(o[2]), ctypes.byref(ms)))
         return o[0], o[1], o[2], ms.value
+
+    @staticmethod
+    def products_patch(inst, z_new, Az, Bz, Cz, bits, n_unsat, cols=None, first=0, count=0):
+        """otti_k_products_patch: the kept-products patch on host state.  Az, Bz, Cz ((N, 32) uint8 Montgomery words) and bits (uint64 words) are
+        copied, patched for ``z_new`` and the changed columns (``cols``: ascending uint64 array; None: the range first, count) and returned:
+        (Az, Bz, Cz, bits, n_unsat, touched rows ascending (uint32), took_full_pass, kernel_ms)"""
+        z = _scalars(z_new, "z"); nc, nv, _ = inst.dims
+        assert z.shape[0] == 2 * nv
+        o = [np.ascontiguousarray(_scalars(x, "products")).copy() for x in (Az, Bz, Cz)]
+        b = np.ascontiguousarray(bits, dtype=np.uint64).copy()
+        assert all(x.shape[0] == nc for x in o) and b.size == (nc + 63) // 64
+        if cols is not None:
+            cols = np.ascontiguousarray(cols, dtype=np.uint64)
+        rows = np.zeros(nc, dtype=np.uint32)
+        u, nt, full, ms = _u64(n_unsat), _u64(), _i32(), ctypes.c_float(0)
+        _check(lib.otti_k_products_patch(inst._h, _ptr(z), _ptr(cols) if cols is not None else None, cols.size if cols is not None else 0, first, count,
+                                         _ptr(o[0]), _ptr(o[1]), _ptr(o[2]), _ptr(b), ctypes.byref(u), _ptr(rows), nc, ctypes.byref(nt), ctypes.byref(full), ctypes.byref(ms)))
+        return o[0], o[1], o[2], b, u.value, rows[:nt.value].copy(), bool(full.value), ms.value
 
     @staticmethod
     def eval_table_sparse(inst, eq_rx, rABC):

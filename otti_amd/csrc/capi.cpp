@@ -124,6 +124,11 @@ static void check_wit_source(const void *src, size_t count, int32_t format, size
     if (stride_bytes && (stride_bytes < wit_elem_bytes(format) || stride_bytes % 8)) throw Error(OTTI_ERR_BAD_ARG, "stride_bytes below the element size or not a multiple of 8");
     if (on_device && ((uintptr_t)src & 7)) throw Error(OTTI_ERR_BAD_ARG, "a device source must be 8-byte aligned");
 }
+// a witness that keeps products (device.h DeviceWitness::prod_abc) is changed through the instance they were formed with, and no other: said before
+// z is written, so the refusal changes nothing
+static void check_products_instance(const otti_witness *wit, const Instance &I) {
+    if (wit->w->prod_inst && wit->w->prod_inst != &I) throw Error(OTTI_ERR_BAD_ARG, "the witness keeps products for another instance: the witness is unchanged");
+}
 static int32_t witness_from(otti_instance *inst, const void *src, size_t nvars, int32_t format, size_t stride_bytes, bool on_device, const uint8_t *inputs32,
                             size_t ninputs, void *stream, otti_witness **out) {
     return guarded([&] {
@@ -155,6 +160,7 @@ int32_t otti_witness_update(otti_instance *inst, otti_witness *wit, size_t first
         if (first > V || count > V - first) throw Error(OTTI_ERR_INVALID_NUM_VARS, "the range ends beyond the instance's variables");
         DevCtx::get();                                            // no device: said before the witness handle is looked at
         check_witness_dims(wit, *inst->I);
+        check_products_instance(wit, *inst->I);
         wit->w->update(first, format, src, count, stride_bytes, src_on_device != 0, (hipStream_t)stream);
         return OTTI_OK;
     });
@@ -176,6 +182,7 @@ int32_t otti_witness_scatter(otti_instance *inst, otti_witness *wit, const uint6
                 if (idx[i] >= V || (i && idx[i] <= idx[i - 1])) throw Error(OTTI_ERR_INVALID_INDEX, "the indices are not strictly ascending below the padded num_vars");
         DevCtx::get();                                            // no device: said before the witness handle is looked at
         check_witness_dims(wit, *inst->I);
+        check_products_instance(wit, *inst->I);
         wit->w->scatter(idx, format, src, count, stride_bytes, on_device != 0, (hipStream_t)stream);
         return OTTI_OK;
     });
@@ -204,6 +211,7 @@ int32_t otti_witness_assign(otti_instance *inst, otti_witness *wit, size_t first
         if (!count) return OTTI_OK;
         DevCtx::get();                                            // no device: said before the witness handle is looked at
         check_witness_dims(wit, *inst->I);
+        check_products_instance(wit, *inst->I);
         const size_t n = wit->w->assign(first, format, src, count, stride_bytes, src_on_device != 0, (hipStream_t)stream);
         if (n_changed) *n_changed = n;
         return OTTI_OK;
@@ -242,6 +250,7 @@ int32_t otti_witness_set_inputs(otti_instance *inst, otti_witness *wit, const ui
         const std::vector<Fr> inputs = scalars_from_bytes(inputs32, ninputs);      // INVALID_SCALAR: a host check, the witness is not touched
         DevCtx::get();
         check_witness_dims(wit, *inst->I);
+        check_products_instance(wit, *inst->I);
         wit->w->set_inputs(inputs);
         return OTTI_OK;
     });
@@ -290,6 +299,42 @@ int32_t otti_witness_rows_info(const otti_witness *wit, int32_t *kept, size_t *L
         return OTTI_OK;
     });
 }
+// ---- kept products (device.h DeviceWitness::prod_abc), in the order of the kept-rows calls: the arguments, a missing device, the witness's dimensions
+int32_t otti_witness_keep_products(otti_instance *inst, otti_witness *wit) {
+    return guarded([&] {
+        if (!inst || !wit) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        DevCtx::get();
+        check_witness_dims(wit, *inst->I);
+        wit->w->keep_products(*inst->I);
+        return OTTI_OK;
+    });
+}
+int32_t otti_witness_drop_products(otti_witness *wit) {
+    return guarded([&] {
+        if (!wit) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (otti_device_count() < 1) throw Error(OTTI_ERR_NO_DEVICE, "no device: no witness handle can exist");
+        wit->w->drop_products();
+        return OTTI_OK;
+    });
+}
+int32_t otti_witness_products_info(const otti_witness *wit, int32_t *kept, size_t *n_rows, const void **d_Az, const void **d_Bz, const void **d_Cz,
+                                   uint64_t *n_unsat, uint64_t *patches, uint64_t *rows_recomputed, uint64_t *full_passes) {
+    return guarded([&] {
+        if (!wit) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (otti_device_count() < 1) throw Error(OTTI_ERR_NO_DEVICE, "no device: no witness handle can exist");
+        const DeviceWitness &w = *wit->w;
+        if (kept) *kept = w.prod_inst ? 1 : 0;
+        if (n_rows) *n_rows = w.prod_abc[0].n;
+        if (d_Az) *d_Az = w.prod_abc[0].p;
+        if (d_Bz) *d_Bz = w.prod_abc[1].p;
+        if (d_Cz) *d_Cz = w.prod_abc[2].p;
+        if (n_unsat) *n_unsat = w.prod_unsat;
+        if (patches) *patches = w.prod_patches;
+        if (rows_recomputed) *rows_recomputed = w.prod_rows_recomputed;
+        if (full_passes) *full_passes = w.prod_full_passes;
+        return OTTI_OK;
+    });
+}
 int32_t otti_nizk_prove_resident(otti_instance *inst, otti_witness *wit, otti_gens *gens, const uint8_t *tlabel, size_t tlabel_len,
                                  const uint8_t *seed32, uint8_t **proof, size_t *proof_len, double *stage_ms) {
     return guarded([&] {
@@ -306,7 +351,10 @@ int32_t otti_witness_check_sat(otti_instance *inst, otti_witness *wit, uint64_t 
         Instance &I = *inst->I;
         check_witness_dims(wit, I);
         DevCtx &c = DevCtx::get(); ensure_instance_device(I);
-        const SatReport rep = dev_check_sat(c, *I.dev, wit->w->z.p, rows_cap, abc96 != nullptr);
+        SatReport rep;
+        // a witness that keeps its products for this instance is answered from their count and bitmap: no pass; failing rows are reported as ever
+        if (wit->w->products_kept_for(I)) { rep.n_unsat = wit->w->prod_unsat; dev_sat_report(c, *I.dev, wit->w->z.p, wit->w->prod_bits.p, rows_cap, abc96 != nullptr, true, rep); }
+        else rep = dev_check_sat(c, *I.dev, wit->w->z.p, rows_cap, abc96 != nullptr);
         *n_unsat = rep.n_unsat;
         for (size_t i = 0; i < rep.rows.size(); i++) rows[i] = rep.rows[i];
         if (abc96 && !rep.abc96.empty()) memcpy(abc96, rep.abc96.data(), rep.abc96.size());

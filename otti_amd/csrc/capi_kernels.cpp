@@ -99,6 +99,37 @@ int32_t otti_k_multiply_vec(otti_instance *inst, const uint8_t *z, uint8_t *Az, 
         download(c, Az, a.p, I.num_cons); download(c, Bz, b.p, I.num_cons); download(c, Cz, d.p, I.num_cons); c.sync(); return OTTI_OK;
     });
 }
+// DeviceWitness::products_changed on a caller's host state: the same dev_products_patch, so a wrong patch points at a kernel and not at a proof
+int32_t otti_k_products_patch(otti_instance *inst, const uint8_t *h_z_new, const uint64_t *h_cols, size_t ncols, size_t first, size_t count,
+                              uint8_t *io_Az, uint8_t *io_Bz, uint8_t *io_Cz, uint64_t *io_bits, uint64_t *io_unsat,
+                              uint32_t *h_rows, size_t n_rows_cap, uint64_t *n_touched, int32_t *took_full_pass, float *kernel_ms) {
+    return guarded([&] {
+        if (!inst || !h_z_new || !io_Az || !io_Bz || !io_Cz || !io_bits || !io_unsat || (n_rows_cap && !h_rows) || (!h_cols && ncols)) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        Instance &I = *inst->I;
+        const size_t V2 = 2 * I.num_vars, N = I.num_cons, words = (N + 63) >> 6;
+        if (h_cols) {
+            for (size_t i = 0; i < ncols; i++)
+                if (h_cols[i] >= V2 || (i && h_cols[i] <= h_cols[i - 1])) throw Error(OTTI_ERR_INVALID_INDEX, "the columns are not strictly ascending below 2 * padded num_vars");
+        } else if (first > V2 || count > V2 - first) throw Error(OTTI_ERR_INVALID_INDEX, "the range ends beyond 2 * padded num_vars");
+        DevCtx &c = DevCtx::get(); ensure_instance_device(I);
+        Staged Z(c, h_z_new, V2), a(c, io_Az, N), b(c, io_Bz, N), d(c, io_Cz, N);
+        DevBuf<unsigned long long> bits(words), unsat(1); DevBuf<uint64_t> cols(std::max<size_t>(1, ncols));
+        OTTI_HIP(hipMemcpyAsync(bits.p, io_bits, words * 8, hipMemcpyHostToDevice, c.stream));
+        OTTI_HIP(hipMemcpyAsync(unsat.p, io_unsat, 8, hipMemcpyHostToDevice, c.stream));
+        if (h_cols && ncols) OTTI_HIP(hipMemcpyAsync(cols.p, h_cols, ncols * 8, hipMemcpyHostToDevice, c.stream));
+        const ProductsPatch p = dev_products_patch(c, *I.dev, Z.d.p, h_cols ? cols.p : nullptr, ncols, first, count, a.d.p, b.d.p, d.d.p, bits.p, unsat.p);
+        download(c, io_Az, a.d.p, N); download(c, io_Bz, b.d.p, N); download(c, io_Cz, d.d.p, N);
+        OTTI_HIP(hipMemcpyAsync(io_bits, bits.p, words * 8, hipMemcpyDeviceToHost, c.stream));
+        const size_t k = std::min(p.n_touched, n_rows_cap);
+        if (k) OTTI_HIP(hipMemcpyAsync(h_rows, c.prod_rows.p, k * 4, hipMemcpyDeviceToHost, c.stream));
+        c.sync();
+        *io_unsat = p.n_unsat;
+        if (n_touched) *n_touched = p.n_touched;
+        if (took_full_pass) *took_full_pass = p.full ? 1 : 0;
+        if (kernel_ms) *kernel_ms = p.kernel_ms;
+        return OTTI_OK;
+    });
+}
 int32_t otti_k_eval_table_sparse(otti_instance *inst, const uint8_t *eq_rx, const uint8_t *rABC, uint8_t *out, float *ms) {
     return guarded([&] {
         DevCtx &c = DevCtx::get(); Instance &I = *inst->I; ensure_instance_device(I);

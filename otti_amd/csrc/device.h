@@ -128,6 +128,9 @@ struct DevCtx {
     DevBuf<unsigned long long> d_counts;                      // two 64-bit tallies for the kernels that count (non-canonical / small scalars / failing constraints): no allocation per call
     DevBuf<unsigned long long> sat_bits;                      // dev_check_sat: one bit per constraint row (grown on demand, kept across calls)
     DevBuf<uint32_t> sat_rows; DevBuf<Fr> sat_abc;            // its report kernel's row ids and 3 sums per row (kSatReportRows of them)
+    DevBuf<unsigned long long> prod_touched;                  // dev_products_patch: one bit per constraint row a changed column reaches, then (prod_cnt) the
+    DevBuf<uint32_t> prod_cnt, prod_rows;                     // words' popcounts scanned in place and the touched rows, ascending (grown on demand, kept across calls)
+    std::vector<DevBuf<uint32_t>> prod_scan;                  // scan_inplace's block totals for that scan
     DevBuf<unsigned long long> diff_chunks;                   // dev_witness_diff_count: a small head, changed elements per chunk, then their prefix sums (grown on demand, kept across calls)
     Mailbox next_mailbox(int slot);
     GoBox *h_go = nullptr, *d_go_alias = nullptr; DevBuf<GoBox> d_go; unsigned long long go_issued = 0, go_published = 0;
@@ -238,6 +241,22 @@ struct DeviceWitness {
     bool rows_kept_for(const Gens &g) const;                  // kept, and over g's points
     void keep_rows(Gens &g);                                  // builds g's table if need be, sums every row, returns when they are resident; again with the same points: nothing
     void drop_rows();
+    // ---- kept products (opt-in): Az, Bz, Cz of this z over ONE instance's matrices (N = padded num_cons canonical Montgomery words each, bit for
+    // bit what dev_spmv3 writes), the verdict bitmap dev_sat_pass writes for it and the number of failing rows.  The sums are linear in z: a changed
+    // variable j moves only the rows with an entry in column j, which the instance's by-column copy lists, so every mutator brings the state up to
+    // date by recomputing those rows alone (dev_products_patch) once z is written.  An unsharded proof over that instance copies the vectors into its
+    // tables instead of forming them (the tables are folded in place: the kept vectors themselves never go to a folding kernel); check_sat answers
+    // from count and bitmap.  Written by keep_products, drop_products and the mutators only — never beside a proof or check with this witness, so
+    // readers need no lock.  The instance must outlive the kept products.
+    DevBuf<Fr> prod_abc[3]; DevBuf<unsigned long long> prod_bits, prod_unsat_dev;
+    Instance *prod_inst = nullptr;                            // whose matrices they were formed with
+    uint64_t prod_unsat = 0;                                  // host copy of *prod_unsat_dev
+    unsigned long long prod_patches = 0, prod_rows_recomputed = 0, prod_full_passes = 0;   // since keep_products: patches that recomputed listed rows, those rows, full passes (the first included)
+    bool products_kept_for(const Instance &I) const { return prod_inst == &I && prod_abc[0].p; }
+    void keep_products(Instance &I);                          // one full pass now; again for the same instance: nothing
+    void drop_products();
+    // z[cols] (d_cols: ascending device list of ncols indices; nullptr: the range [first, first + count)) has been written: bring the products up to date
+    void products_changed(const uint64_t *d_cols, size_t ncols, size_t first, size_t count);
 private:
     // the dimension checks, z allocated and zeroed, 1 || inputs queued behind the variables; returns the host copy of that tail, which has to
     // outlive the next synchronise of c.stream
@@ -314,6 +333,26 @@ struct SatReport { uint64_t n_unsat = 0; std::vector<uint64_t> rows; std::vector
 void dev_sat_pass(DevCtx &c, const DeviceCsrSet &m, const Fr *z, unsigned long long *bits);
 uint64_t dev_sat_count(DevCtx &c);                           // waits for the pass queued last on c.stream and returns its count
 SatReport dev_check_sat(DevCtx &c, DeviceInstance &d, const Fr *z, size_t max_rows, bool with_values);
+// ---- kept products (k_sparse.hip): Az, Bz, Cz (N canonical Montgomery words each), the verdict bitmap of dev_sat_pass's layout and the failing count
+// *d_unsat that go with them are brought up to date for a z of which the listed columns have changed.  Three steps: the by-column lists of the
+// changed columns MARK their rows in c.prod_touched (zeroed first; atomicOr), the bitmap is COMPACTED into the ascending row list c.prod_rows
+// (popcount per word, scan_inplace; the length comes back through the pinned result slot: one synchronise), and the listed rows are RECOMPUTED from
+// the by-row set — sums, verdict bit, and the count moved by the difference.  From full_share * N touched rows on, the full pass runs instead:
+// dev_spmv3 into the vectors, then every verdict from them (dev_products_full).  Every index followed comes from the instance's own CSR copies or
+// from d_cols, which the CALLER has checked (ascending, below 2 * num_vars).  Returns with the stream idle.
+constexpr int kProdCountSlot = 26;                           // result slots 26, 27: the touched count and the failing count
+// The share of the N rows from which the full pass replaces the patch.  Measured, profiles/witness_products.md (tools/witness_products_probe.py, 2^20,
+// device time): the smallest probed share at which the patch was no longer shorter than dev_spmv3 + dev_sat_pass, as the code without kept products
+// runs them, was 0.33 on the uniform instance and 0.57 on the compiler-like one; the lower of the two, rounded down to a power of two (toward the
+// full pass).  OTTI_PRODUCTS_FULL_SHARE, read per call, overrides it: 0 always takes the full pass, a value >= 1 never does.
+constexpr double kProductsFullShare = 0.25;
+double products_full_share();
+struct ProductsPatch { size_t n_touched = 0; bool full = false; uint64_t n_unsat = 0; float kernel_ms = 0; };   // kernel_ms: first launch to last, the host's read of n_touched in between included
+void dev_products_full(DevCtx &c, const DeviceInstance &d, const Fr *z, Fr *Az, Fr *Bz, Fr *Cz, unsigned long long *bits, unsigned long long *d_unsat);   // only queues
+ProductsPatch dev_products_patch(DevCtx &c, const DeviceInstance &d, const Fr *z, const uint64_t *d_cols, size_t ncols, size_t first, size_t count,
+                                 Fr *Az, Fr *Bz, Fr *Cz, unsigned long long *bits, unsigned long long *d_unsat);
+// the failing rows of a bitmap whose count is known, listed and (with_values) recomputed as dev_check_sat reports them; kernel_ms: the report launches
+void dev_sat_report(DevCtx &c, DeviceInstance &d, const Fr *z, const unsigned long long *d_bits, size_t max_rows, bool with_values, bool timed, SatReport &rep);
 // ---- K2: eq tables.  r is a HOST array (challenges come from the transcript)
 void dev_eq_evals(DevCtx &c, const Fr *r_host, size_t ell, Fr *out, Fr *scratch /* >= 3 * 4096 elements; 5 * 4096 for ell = 25 */);
 void dev_eq_evals2(DevCtx &c, const Fr *r0_host, size_t ell0, Fr *out0, const Fr *r1_host, size_t ell1, Fr *out1, Fr *scratch);   // both in one launch when each has at most 13 variables

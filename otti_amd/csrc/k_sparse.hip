@@ -241,17 +241,23 @@ SatReport dev_check_sat(DevCtx &c, DeviceInstance &d, const Fr *z, size_t max_ro
     OTTI_HIP(hipEventRecord(c.ev1, c.stream));
     rep.n_unsat = dev_sat_count(c);
     OTTI_HIP(hipEventElapsedTime(&rep.kernel_ms, c.ev0, c.ev1));
+    dev_sat_report(c, d, z, c.sat_bits.p, max_rows, with_values, false, rep);
+    return rep;
+}
+void dev_sat_report(DevCtx &c, DeviceInstance &d, const Fr *z, const unsigned long long *d_bits, size_t max_rows, bool with_values, bool timed, SatReport &rep) {
+    const DeviceCsrSet &m = d.by_row;
+    const size_t words = (m.rows + 63) >> 6;
     const size_t k = (size_t)std::min<uint64_t>(rep.n_unsat, max_rows);
-    if (!k) return rep;
+    if (!k) return;
     std::vector<unsigned long long> bits(words);
-    OTTI_HIP(hipMemcpy(bits.data(), c.sat_bits.p, words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    OTTI_HIP(hipMemcpy(bits.data(), d_bits, words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     rep.rows.reserve(k);
     for (size_t w = 0; w < words && rep.rows.size() < k; w++)
         for (unsigned long long v = bits[w]; v && rep.rows.size() < k; v &= v - 1) {
             const size_t r = (w << 6) + (size_t)__builtin_ctzll(v);
             if (r < m.rows) rep.rows.push_back((uint64_t)r);
         }
-    if (!with_values) return rep;
+    if (!with_values) return;
     if (c.sat_rows.n < kSatReportRows) { c.sat_rows.alloc(kSatReportRows); c.sat_abc.alloc(3 * kSatReportRows); }
     rep.abc96.resize(96 * rep.rows.size());
     uint32_t ids[kSatReportRows];
@@ -259,12 +265,181 @@ SatReport dev_check_sat(DevCtx &c, DeviceInstance &d, const Fr *z, size_t max_ro
         const size_t n = std::min(kSatReportRows, rep.rows.size() - i0);
         for (size_t i = 0; i < n; i++) ids[i] = (uint32_t)rep.rows[i0 + i];
         OTTI_HIP(hipMemcpyAsync(c.sat_rows.p, ids, n * sizeof(uint32_t), hipMemcpyHostToDevice, c.stream));
+        if (timed) OTTI_HIP(hipEventRecord(c.ev0, c.stream));
         if (m.use_small) hipLaunchKernelGGL(k_sat_report<true>, (unsigned)n, kBlock, 0, c.stream, m.view(), (const uint32_t *)c.sat_rows.p, z, c.sat_abc.p);
         else hipLaunchKernelGGL(k_sat_report<false>, (unsigned)n, kBlock, 0, c.stream, m.view(), (const uint32_t *)c.sat_rows.p, z, c.sat_abc.p);
+        if (timed) OTTI_HIP(hipEventRecord(c.ev1, c.stream));
         OTTI_HIP(hipMemcpyAsync(rep.abc96.data() + 96 * i0, c.sat_abc.p, 96 * n, hipMemcpyDeviceToHost, c.stream));
         OTTI_HIP(hipStreamSynchronize(c.stream));              // `ids` and the device buffers are reused by the next batch
+        if (timed) { float ms = 0; OTTI_HIP(hipEventElapsedTime(&ms, c.ev0, c.ev1)); rep.kernel_ms += ms; }
     }
-    return rep;
+}
+
+// ------------------------------------------------------------------------------------------------ kept products (device.h dev_products_patch)
+// MARK: the by-column lists of the changed columns set their rows' bits in `touched` (zeroed by the launcher).  Column i of the launch is cols[i], or
+// first + i when there is no list.  A short column goes to one lane, or to a quad where the by-column set has the quad layout (the lanes only store:
+// no shuffle, so a wave needs no padding); a column longer than kHeavyRow is left to k_prod_mark_heavy, where a workgroup strides over it.
+template <bool kQuad> __global__ __launch_bounds__(kBlock) void k_prod_mark(DCsr3 m, const uint64_t *cols, size_t first, size_t n, unsigned long long *touched) {
+    constexpr uint32_t kLanes = kQuad ? 4 : 1;
+    const uint32_t q = kQuad ? (threadIdx.x & 3) : 0;
+    for (size_t i = (blockIdx.x * (size_t)blockDim.x + threadIdx.x) / kLanes; i < n; i += ((size_t)gridDim.x * blockDim.x) / kLanes) {
+        const size_t j = cols ? (size_t)cols[i] : first + i;
+        if (row_is_heavy(m, j)) continue;
+        for (int k = 0; k < 3; k++) {
+            const uint32_t p1 = m.ptr[k][j + 1];
+            for (uint32_t p = m.ptr[k][j] + q; p < p1; p += kLanes) { const uint32_t r = m.idx[k][p]; atomicOr(&touched[r >> 6], 1ull << (r & 63)); }
+        }
+    }
+}
+__global__ __launch_bounds__(kBlock) void k_prod_mark_heavy(DCsr3 m, const uint64_t *cols, size_t first, size_t n, unsigned long long *touched) {
+    for (size_t i = blockIdx.x; i < n; i += gridDim.x) {
+        const size_t j = cols ? (size_t)cols[i] : first + i;
+        if (!row_is_heavy(m, j)) continue;
+        for (int k = 0; k < 3; k++) {
+            const uint32_t p1 = m.ptr[k][j + 1];
+            for (uint32_t p = m.ptr[k][j] + threadIdx.x; p < p1; p += blockDim.x) { const uint32_t r = m.idx[k][p]; atomicOr(&touched[r >> 6], 1ull << (r & 63)); }
+        }
+    }
+}
+// COMPACT: a popcount per word, scanned in place (scan_inplace: inclusive), then every word writes its rows behind those of the words before it
+__global__ __launch_bounds__(kBlock) void k_prod_popc(const unsigned long long *touched, size_t words, uint32_t *cnt) {
+    for (size_t w = blockIdx.x * (size_t)blockDim.x + threadIdx.x; w < words; w += (size_t)gridDim.x * blockDim.x) cnt[w] = (uint32_t)__popcll(touched[w]);
+}
+__global__ __launch_bounds__(kBlock) void k_prod_emit(const unsigned long long *touched, const uint32_t *cnt, size_t words, uint32_t *rows) {
+    for (size_t w = blockIdx.x * (size_t)blockDim.x + threadIdx.x; w < words; w += (size_t)gridDim.x * blockDim.x) {
+        unsigned long long v = touched[w];
+        uint32_t o = cnt[w] - (uint32_t)__popcll(v);
+        for (; v; v &= v - 1) rows[o++] = (uint32_t)(w << 6) + (uint32_t)__ffsll((long long)v) - 1u;
+    }
+}
+// RECOMPUTE.  One row's three sums stored, its verdict bit set or cleared; returns the change of the failing count (-1, 0, 1).  Each row is listed
+// once, so no other lane writes this bit: the plain load sees it, and the word is only touched (atomically: its other bits have other writers) when
+// the verdict has moved.
+__device__ __forceinline__ int prod_store_row(size_t r, const Fr &a, const Fr &b, const Fr &cc, Fr *Az, Fr *Bz, Fr *Cz, unsigned long long *bits) {
+    Az[r] = a; Bz[r] = b; Cz[r] = cc;
+    const unsigned long long bit = 1ull << (r & 63);
+    const bool fail = row_fails(a, b, cc), was = (bits[r >> 6] & bit) != 0;
+    if (fail != was) atomicXor(&bits[r >> 6], bit);
+    return (int)fail - (int)was;
+}
+__device__ __forceinline__ void prod_count_move(int mine, unsigned long long *count) {
+    for (int off = 32; off >= 1; off >>= 1) mine += __shfl_xor(mine, off, 64);
+    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(count, (unsigned long long)(long long)mine);      // two's complement: a negative move wraps the 64-bit tally down
+}
+// listed rows up to kHeavyRow entries: a row per lane, or per quad in the by-row set's quad layout (k_spmv3_quad's walk and quad_sum; the list is
+// padded to whole waves so that every lane takes part in the shuffles).  The order of summation is free: every partial sum is the canonical word
+// (comment above row_fails), so the stored words are those k_spmv3_* store.
+template <bool kSmall, bool kQuad> __global__ __launch_bounds__(kBlock) void k_prod_rows(DCsr3 m, const uint32_t *rows, size_t n, const Fr *x, Fr *Az, Fr *Bz, Fr *Cz,
+                                                                                         unsigned long long *bits, unsigned long long *count) {
+    constexpr uint32_t kLanes = kQuad ? 4 : 1;
+    constexpr size_t kPerWave = 64 / kLanes;
+    const uint32_t q = kQuad ? (threadIdx.x & 3) : 0;
+    const size_t padded = (n + kPerWave - 1) & ~(kPerWave - 1);
+    int mine = 0;
+    for (size_t i = (blockIdx.x * (size_t)blockDim.x + threadIdx.x) / kLanes; i < padded; i += ((size_t)gridDim.x * blockDim.x) / kLanes) {
+        const size_t r = i < n ? (size_t)rows[i] : 0;
+        const bool live = i < n && !row_is_heavy(m, r);
+        Fr a[3] = {fr_zero(), fr_zero(), fr_zero()};
+        if (live)
+            for (int k = 0; k < 3; k++) {
+                const uint32_t p1 = m.ptr[k][r + 1];
+                for (uint32_t p = m.ptr[k][r] + q; p < p1; p += kLanes) a[k] = fr_add(a[k], entry_term<kSmall>(m, k, p, x));
+            }
+        if (kQuad) for (int k = 0; k < 3; k++) a[k] = quad_sum(a[k]);
+        if (live && q == 0) mine += prod_store_row(r, a[0], a[1], a[2], Az, Bz, Cz, bits);
+    }
+    prod_count_move(mine, count);
+}
+// the longer ones: a workgroup per row strides over it, as k_sat_report does (launched behind the kernel above, and only for an instance that has such rows)
+template <bool kSmall> __global__ __launch_bounds__(kBlock) void k_prod_rows_heavy(DCsr3 m, const uint32_t *rows, size_t n, const Fr *x, Fr *Az, Fr *Bz, Fr *Cz,
+                                                                                   unsigned long long *bits, unsigned long long *count) {
+    for (size_t i = blockIdx.x; i < n; i += gridDim.x) {
+        const size_t r = rows[i];
+        if (!row_is_heavy(m, r)) continue;                          // (the same for every thread of the workgroup)
+        Fr acc[3];
+        for (int k = 0; k < 3; k++) {
+            acc[k] = fr_zero();
+            const uint32_t p1 = m.ptr[k][r + 1];
+            for (uint32_t p = m.ptr[k][r] + threadIdx.x; p < p1; p += blockDim.x) acc[k] = fr_add(acc[k], entry_term<kSmall>(m, k, p, x));
+        }
+        block_reduce<3>(acc);
+        if (threadIdx.x == 0) { const int d = prod_store_row(r, acc[0], acc[1], acc[2], Az, Bz, Cz, bits); if (d) atomicAdd(count, (unsigned long long)(long long)d); }
+    }
+}
+// the full pass's second half: every verdict from the vectors dev_spmv3 has just written (k_sat_light's bitmap writes: a wave owns whole words)
+__global__ __launch_bounds__(kBlock) void k_prod_verdicts(const Fr *Az, const Fr *Bz, const Fr *Cz, size_t rows, unsigned long long *bits, unsigned long long *count) {
+    unsigned long long mine = 0;
+    const size_t padded = (rows + 63) & ~(size_t)63;
+    for (size_t r = blockIdx.x * (size_t)blockDim.x + threadIdx.x; r < padded; r += (size_t)gridDim.x * blockDim.x) {
+        const bool fail = r < rows && row_fails(Az[r], Bz[r], Cz[r]);
+        const unsigned long long word = (unsigned long long)__ballot(fail);
+        if ((threadIdx.x & 63) == 0) { bits[r >> 6] = word; mine += (unsigned long long)__popcll(word); }
+    }
+    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(count, mine);
+}
+double products_full_share() {
+    if (const char *e = getenv("OTTI_PRODUCTS_FULL_SHARE")) { char *end = nullptr; const double v = strtod(e, &end); if (end != e && v >= 0) return v; }
+    return kProductsFullShare;
+}
+void dev_products_full(DevCtx &c, const DeviceInstance &d, const Fr *z, Fr *Az, Fr *Bz, Fr *Cz, unsigned long long *bits, unsigned long long *d_unsat) {
+    const DeviceCsrSet &m = d.by_row;
+    dev_spmv3(c, m, z, Az, Bz, Cz, false, nullptr);
+    OTTI_HIP(hipMemsetAsync(d_unsat, 0, sizeof(unsigned long long), c.stream));
+    KScope ks(c, KC_SPMV);
+    hipLaunchKernelGGL(k_prod_verdicts, grid_for(m.rows), kBlock, 0, c.stream, (const Fr *)Az, (const Fr *)Bz, (const Fr *)Cz, m.rows, bits, d_unsat);
+}
+ProductsPatch dev_products_patch(DevCtx &c, const DeviceInstance &d, const Fr *z, const uint64_t *d_cols, size_t ncols, size_t first, size_t count,
+                                 Fr *Az, Fr *Bz, Fr *Cz, unsigned long long *bits, unsigned long long *d_unsat) {
+    const DeviceCsrSet &bc = d.by_col, &br = d.by_row;
+    const size_t N = br.rows, words = (N + 63) >> 6, n = d_cols ? ncols : count;
+    if (n > bc.rows || (!d_cols && first > bc.rows - n)) throw Error(OTTI_ERR_BAD_ARG, "products patch: the changed columns end beyond the instance's");
+    if (c.prod_touched.n < words || c.prod_rows.n < N) {
+        OTTI_HIP(hipStreamSynchronize(c.stream));
+        c.prod_touched.alloc(words); c.prod_cnt.alloc(words); c.prod_rows.alloc(N);
+    }
+    ProductsPatch out;
+    unsigned long long *touched = c.prod_touched.p;
+    volatile uint32_t *h_touched = reinterpret_cast<volatile uint32_t *>(&c.h_results[kProdCountSlot]);
+    volatile unsigned long long *h_unsat = reinterpret_cast<volatile unsigned long long *>(&c.h_results[kProdCountSlot + 1]);
+    OTTI_HIP(hipEventRecord(c.ev0, c.stream));                      // kernel_ms: from here to the last launch, the host's look at the count included
+    {
+        KScope ks(c, KC_SPMV);
+        OTTI_HIP(hipMemsetAsync(touched, 0, words * sizeof(unsigned long long), c.stream));
+        if (n) {
+            if (bc.quad()) hipLaunchKernelGGL(k_prod_mark<true>, grid_for(4 * n), kBlock, 0, c.stream, bc.view(), d_cols, first, n, touched);
+            else hipLaunchKernelGGL(k_prod_mark<false>, grid_for(n), kBlock, 0, c.stream, bc.view(), d_cols, first, n, touched);
+            if (bc.n_heavy) hipLaunchKernelGGL(k_prod_mark_heavy, (unsigned)std::min<size_t>(n, kMaxBlocks), kBlock, 0, c.stream, bc.view(), d_cols, first, n, touched);
+        }
+        hipLaunchKernelGGL(k_prod_popc, grid_for(words), kBlock, 0, c.stream, (const unsigned long long *)touched, words, c.prod_cnt.p);
+        scan_inplace(c, c.prod_cnt.p, words, c.prod_scan);
+        hipLaunchKernelGGL(k_prod_emit, grid_for(words), kBlock, 0, c.stream, (const unsigned long long *)touched, (const uint32_t *)c.prod_cnt.p, words, c.prod_rows.p);
+    }
+    OTTI_HIP(hipMemcpyAsync((void *)h_touched, c.prod_cnt.p + (words - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
+    OTTI_HIP(hipStreamSynchronize(c.stream));
+    out.n_touched = (size_t)*h_touched;
+    const double share = products_full_share();
+    out.full = share < 1.0 && (double)out.n_touched >= share * (double)N;
+    if (out.full) dev_products_full(c, d, z, Az, Bz, Cz, bits, d_unsat);
+    else if (out.n_touched) {
+        KScope ks(c, KC_SPMV);
+        const size_t nt = out.n_touched; const uint32_t *rows = c.prod_rows.p;
+        const bool quad = br.quad(), sm = br.use_small;             // the layouts dev_spmv3 picks, for its reasons
+        if (quad && sm) hipLaunchKernelGGL((k_prod_rows<true, true>), grid_for(4 * nt), kBlock, 0, c.stream, br.view(), rows, nt, z, Az, Bz, Cz, bits, d_unsat);
+        else if (quad) hipLaunchKernelGGL((k_prod_rows<false, true>), grid_for(4 * nt), kBlock, 0, c.stream, br.view(), rows, nt, z, Az, Bz, Cz, bits, d_unsat);
+        else if (sm) hipLaunchKernelGGL((k_prod_rows<true, false>), grid_for(nt), kBlock, 0, c.stream, br.view(), rows, nt, z, Az, Bz, Cz, bits, d_unsat);
+        else hipLaunchKernelGGL((k_prod_rows<false, false>), grid_for(nt), kBlock, 0, c.stream, br.view(), rows, nt, z, Az, Bz, Cz, bits, d_unsat);
+        if (br.n_heavy) {
+            const unsigned g = (unsigned)std::min<size_t>(nt, kMaxBlocks);
+            if (sm) hipLaunchKernelGGL(k_prod_rows_heavy<true>, g, kBlock, 0, c.stream, br.view(), rows, nt, z, Az, Bz, Cz, bits, d_unsat);
+            else hipLaunchKernelGGL(k_prod_rows_heavy<false>, g, kBlock, 0, c.stream, br.view(), rows, nt, z, Az, Bz, Cz, bits, d_unsat);
+        }
+    }
+    OTTI_HIP(hipEventRecord(c.ev1, c.stream));
+    OTTI_HIP(hipMemcpyAsync((void *)h_unsat, d_unsat, sizeof(unsigned long long), hipMemcpyDeviceToHost, c.stream));
+    OTTI_HIP(hipStreamSynchronize(c.stream));
+    OTTI_HIP(hipEventElapsedTime(&out.kernel_ms, c.ev0, c.ev1));
+    out.n_unsat = (uint64_t)*h_unsat;
+    return out;
 }
 
 // ------------------------------------------------------------------------------------------------ CSR copies, built on the device

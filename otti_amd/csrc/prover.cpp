@@ -198,6 +198,7 @@ void DeviceWitness::update(size_t first, int format, const void *src, size_t cou
     small_fraction = dev_small_fraction(c, z.p, V);               // one recount over the variables (padding zeros count as small); synchronises
     // kept rows: z has changed (a refused scalar threw above, with z and the kept rows as they were), so the rows the range touches are summed again
     if (rows_kept.p) resum_rows(c, *this, first / rows_R, (first + count - 1) / rows_R);
+    if (prod_inst) products_changed(nullptr, 0, first, count);
 }
 
 // ---- kept rows.  Rows [r0, r1] of z summed over g's table into their slots of rows_kept, by the launch the proof's own commitment would make for
@@ -250,6 +251,7 @@ void DeviceWitness::scatter(const uint64_t *idx, int format, const void *src, si
     }
     small_fraction = dev_small_fraction(c, z.p, V);               // counted again as update does, never incrementally; synchronises
     scatter_calls++;
+    if (prod_inst) products_changed(d_idx, count, 0, 0);          // the list has passed the check above; idx_staged and the caller's list are still alive
     if (patch) {
         const uint64_t *ix = on_device ? h_idx.data() : idx;
         unsigned long long rows = 0;
@@ -291,6 +293,7 @@ size_t DeviceWitness::assign(size_t first, int format, const void *src, size_t c
     const bool patch = rows_kept.p && !(share < 1.0 && (double)n_changed >= share * (double)((r1 - r0 + 1) * rows_R));
     DevBuf<uint64_t> idx; DevBuf<Fr> delta;                       // outlive the launches that read them: freed after dev_small_fraction has synchronised
     if (patch) { idx.alloc(n_changed); delta.alloc(n_changed); }
+    else if (prod_inst) idx.alloc(n_changed);                     // kept products are patched by the list of changed columns, whatever becomes of kept rows
     dev_witness_diff_apply(c, format, s.p, s.stride, count, z.p + first, first, n_changed, idx.p, delta.p, true);
     uint64_t rows = 0;
     if (patch) {
@@ -306,6 +309,7 @@ size_t DeviceWitness::assign(size_t first, int format, const void *src, size_t c
     try { small_fraction = dev_small_fraction(c, z.p, V); } catch (...) { (void)hipStreamSynchronize(c.stream); throw; }
     if (patch) { rows_patched += rows; terms_patched += n_changed; }
     else if (rows_kept.p) { resum_rows(c, *this, r0, r1); assign_resums++; }   // behind the recount, as in update: the launch picks its variant by the new share
+    if (prod_inst) products_changed(idx.p, n_changed, 0, 0);
     return n_changed;
 }
 size_t DeviceWitness::diff(size_t first, int format, const void *src, size_t count, size_t stride, bool src_on_device, hipStream_t producer, uint64_t *idx_out,
@@ -335,6 +339,41 @@ void DeviceWitness::set_inputs(const std::vector<Fr> &new_inputs) {
         OTTI_HIP(hipStreamSynchronize(c.stream));
     }
     inputs = new_inputs;
+    if (prod_inst && !new_inputs.empty()) products_changed(nullptr, 0, V + 1, new_inputs.size());   // inputs are columns of z too
+}
+// ---- kept products (device.h).  keep: the full pass, once; every mutator above calls products_changed once z holds the new values.
+void DeviceWitness::keep_products(Instance &I) {
+    DevCtx &c = DevCtx::get();
+    if (I.num_vars * 2 != z.n) throw Error(OTTI_ERR_INVALID_NUM_VARS, "the witness was uploaded for an instance of other dimensions");
+    if (products_kept_for(I)) return;
+    ensure_instance_device(I);
+    drop_products();
+    const size_t N = I.num_cons;
+    try {
+        for (int k = 0; k < 3; k++) prod_abc[k].alloc(N);
+        prod_bits.alloc((N + 63) >> 6); prod_unsat_dev.alloc(1);
+        prod_inst = &I;
+        dev_products_full(c, *I.dev, z.p, prod_abc[0].p, prod_abc[1].p, prod_abc[2].p, prod_bits.p, prod_unsat_dev.p);
+        unsigned long long n = 0;
+        OTTI_HIP(hipMemcpyAsync(&n, prod_unsat_dev.p, sizeof n, hipMemcpyDeviceToHost, c.stream));
+        OTTI_HIP(hipStreamSynchronize(c.stream));
+        prod_unsat = n; prod_full_passes = 1;
+    } catch (...) { (void)hipStreamSynchronize(c.stream); drop_products(); throw; }
+}
+void DeviceWitness::drop_products() {
+    for (int k = 0; k < 3; k++) prod_abc[k].release();
+    prod_bits.release(); prod_unsat_dev.release();
+    prod_inst = nullptr; prod_unsat = 0; prod_patches = prod_rows_recomputed = prod_full_passes = 0;
+}
+void DeviceWitness::products_changed(const uint64_t *d_cols, size_t ncols, size_t first, size_t count) {
+    DevCtx &c = DevCtx::get();
+    // z has changed: products that cannot be brought up to date no longer belong to it, so the witness goes back to having none (as resum_rows does)
+    try {
+        const ProductsPatch p = dev_products_patch(c, *prod_inst->dev, z.p, d_cols, ncols, first, count, prod_abc[0].p, prod_abc[1].p, prod_abc[2].p, prod_bits.p, prod_unsat_dev.p);
+        prod_unsat = p.n_unsat;
+        if (p.full) prod_full_passes++;
+        else if (p.n_touched) { prod_patches++; prod_rows_recomputed += p.n_touched; }
+    } catch (...) { (void)hipStreamSynchronize(c.stream); drop_products(); throw; }
 }
 bool DeviceWitness::rows_kept_for(const Gens &g) const { return rows_kept.p && rows_R == g.R && rows_stream && !strcmp(rows_stream, g.stream); }
 void DeviceWitness::keep_rows(Gens &g) {
@@ -633,7 +672,11 @@ void r1cs_prove_device(Instance &I, DeviceWitness &wit, Gens &g, Transcript &tr,
         dev_msm_rows(c, DG, {.rows = Ll, .extra_s = S.blinds.p, .extra_base = &hbase, .n_extra = 1, .addend = rows_kept ? wit.rows_kept.p : c.msm_keep.p});
         // Az, Bz, Cz do not depend on the transcript: queue them behind the commitment so that they run while the host hashes it
         OTTI_HIP(hipEventRecord(c.ev0, c.stream));
-        dev_spmv3(c, rows_set, wit.z.p, S.T[1].p, S.T[2].p, S.T[3].p, false, nullptr);
+        // (a witness that keeps its products for this instance has them already, DeviceWitness::prod_abc: copies, since the tables are folded in place;
+        // a sharded proof's rows are renumbered per rank and formed as ever)
+        if (!sh && wit.products_kept_for(I))
+            for (int k = 0; k < 3; k++) OTTI_HIP(hipMemcpyAsync(S.T[1 + k].p, wit.prod_abc[k].p, N * sizeof(Fr), hipMemcpyDeviceToDevice, c.stream));
+        else dev_spmv3(c, rows_set, wit.z.p, S.T[1].p, S.T[2].p, S.T[3].p, false, nullptr);
         // ... and so do the blinding commitments of every sum-check round (tape-only): one batched launch for both sum-checks
         { RandomTape::Cursor c1(tape, off_sc1), c2(tape, off_sc2); sumcheck_draw_tape(early1, c1, nrx, 4); sumcheck_draw_tape(early2, c2, nry, 3); }
         round_points = precompute_round_points_launch(c, DG, g, early1, early2, S.pre);
