@@ -77,6 +77,22 @@ int32_t otti_gens_table_info(const otti_gens *gens, uint32_t *window_bits, uint6
 /* frees the device-side window table (tens of GB); it is built again by the next otti_prepare_device or proof with these generators.
  * For a process that moves between instance sizes: two wide tables do not fit one card.  Not while a proof with them is running. */
 int32_t otti_gens_release_device(otti_gens *gens);
+/* one device table for several generator handles: `gens` drops whatever table it has and from then on uses `donor`'s (shared ownership; a
+ * donor without a table gets one built as otti_prepare_device would build it).  Every NIZKGens takes its points from one stream, P[0 .. R),
+ * P[R], P[R + 1] being stream points 0 .. R + 1, and the table is laid out base by base, so the table of the longer handle holds every entry
+ * a shorter one looks up.  Proof bytes do not depend on the table: a proof, a kernel entry (otti_k_*) and kept rows give the same bytes before
+ * and after.  Afterwards otti_gens_table_info(gens) reports the donor's window width and bytes.  Again with the same donor: OTTI_OK, nothing done.
+ * Refusals, before any device is touched: OTTI_ERR_BAD_ARG for a null handle, for gens == donor, for a donor of another stream label and for a
+ * donor with fewer points than gens needs; then OTTI_ERR_NO_DEVICE.
+ * Release and free: otti_gens_release_device and otti_gens_free on any sharer drop that handle's reference only; the table is freed with
+ * its last reference.  A handle that released (donor or adopter) builds a table of its own the next time it needs one.  A witness's kept rows
+ * belong to the points and stay valid.
+ * Threads: a prepare-class call — single-threaded, and never while a proof with either handle is running.
+ * SNARK generators (otti_snark_gens) share nothing. */
+int32_t otti_gens_adopt_table(otti_gens *gens, otti_gens *donor);
+/* *d_table: the device address of the table these generators use, NULL when there is none; *users: the number of handles holding that
+ * table (0 when there is none).  Either out pointer may be NULL.  Touches no device. */
+int32_t otti_gens_table_users(const otti_gens *gens, uint32_t *users, const void **d_table);
 /* what building the table took, in ms: the HBM allocations (driver work: differs widely between boxes and between a fresh and a used
  * process) and the upload + fill kernels (proportional to the table); zeros before it has been built */
 int32_t otti_gens_build_ms(const otti_gens *gens, double *alloc_ms, double *kernels_ms);

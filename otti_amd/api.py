@@ -140,6 +140,8 @@ _sig("otti_stats_enable", _i32, _i32)
 _sig("otti_stats_select", _i32, ctypes.c_char_p)
 _sig("otti_armed_launches_on", _i32, ctypes.POINTER(_i32))
 _sig("otti_gens_release_device", _i32, _vp)
+_sig("otti_gens_adopt_table", _i32, _vp, _vp)
+_sig("otti_gens_table_users", _i32, _vp, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_void_p))
 _sig("otti_gens_build_ms", _i32, _vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double))
 _sig("otti_bench_fr_mul_peak", _i32, ctypes.POINTER(ctypes.c_double))
 _sig("otti_stats_read", _i32, ctypes.c_char_p, ctypes.POINTER(_u64), ctypes.POINTER(ctypes.c_double))
@@ -394,6 +396,16 @@ class NIZKGens:
     def release_device(self):
         """free the device-side window table (rebuilt by the next prepare_device / proof)"""
         _check(lib.otti_gens_release_device(self._h))
+
+    def adopt_table(self, donor):
+        """drop this handle's device table and share ``donor``'s (built if need be); donor: NIZKGens of the same stream with at least as many points"""
+        _check(lib.otti_gens_adopt_table(self._h, donor._h if donor is not None else None))
+
+    def table_users(self):
+        """(handles holding this handle's device table, its device address); (0, None) when there is none"""
+        n, p = ctypes.c_uint32(), ctypes.c_void_p()
+        _check(lib.otti_gens_table_users(self._h, ctypes.byref(n), ctypes.byref(p)))
+        return n.value, p.value
 
     def points(self, count):
         out = np.zeros((count, 32), dtype=np.uint8)

@@ -83,6 +83,26 @@ int32_t otti_gens_release_device(otti_gens *gens) {
         return OTTI_OK;
     });
 }
+int32_t otti_gens_adopt_table(otti_gens *gens, otti_gens *donor) {
+    return guarded([&] {
+        if (!gens || !donor) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (gens == donor) throw Error(OTTI_ERR_BAD_ARG, "a handle cannot adopt its own table");
+        Gens &g = *gens->g, &d = *donor->g;
+        if (strcmp(g.stream, d.stream)) throw Error(OTTI_ERR_BAD_ARG, "the donor's points come from another generator stream");
+        if (d.P.size() < g.P.size()) throw Error(OTTI_ERR_BAD_ARG, "the donor has fewer points than these generators need");
+        adopt_gens_table(g, d);
+        return OTTI_OK;
+    });
+}
+int32_t otti_gens_table_users(const otti_gens *gens, uint32_t *users, const void **d_table) {
+    return guarded([&] {
+        if (!gens) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        const std::shared_ptr<DeviceGens> &d = gens->g->dev;
+        if (users) *users = d ? (uint32_t)d.use_count() : 0;
+        if (d_table) *d_table = d ? (const void *)d->table.p : nullptr;
+        return OTTI_OK;
+    });
+}
 int32_t otti_gens_points(const otti_gens *gens, uint8_t *out32, size_t count) {
     return guarded([&] {
         if (!gens || count > gens->g->P.size()) throw Error(OTTI_ERR_BAD_ARG, "count exceeds the generator stream");

@@ -59,6 +59,8 @@ struct DeviceGens {
     double build_ms[2] = {0, 0};                            // what building it took: allocations / upload + kernels
     const TabEntry *entry0(size_t base) const { return table.p + base * (size_t)W * E; }
 };
+// nbases is the number of stream points the TABLE covers, not the R + 2 of the Gens a launch is made for: a Gens may hold the table of a longer
+// one of its stream (adopt_gens_table).  Launchers take row lengths and base indices from the Gens and check them against nbases.
 
 // where a sum-check kernel's last workgroup delivers the round's totals (see finish_in_kernel)
 struct Mailbox { Fr *partials; unsigned *counter; Fr *host_results; unsigned long long *host_flag; unsigned long long seq; int slot; int line_mail = 0;
@@ -266,6 +268,7 @@ void ensure_device_objects(Instance &I, Gens &g);          // lazily built, shar
 void ensure_instance_device(Instance &I);
 void ensure_gens_device(Gens &g);
 void release_gens_device(Gens &g);                                     // frees the window table; the next ensure_gens_device rebuilds it
+void adopt_gens_table(Gens &g, Gens &donor);                            // g drops its table and shares donor's (built if need be); prover.cpp
 int device_window_bits(size_t nbases);                   // window width of the fixed-base table (prover.cpp)
 // R1CSInstance::evaluate on the device: (A,B,C)(rx,ry) = <eq(rx), M * eq(ry)> for M in {A,B,C}  (verifier's O(nnz + N + V) work)
 constexpr int kInstEvalSlot = 16;                            // result slots of the instance evaluation (nothing a verifier launches in between writes them)

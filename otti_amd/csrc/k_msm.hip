@@ -521,6 +521,9 @@ static void msm_report_stamps(DevCtx &c, const unsigned long long *t, const MsmJ
 // One launch in four steps: plan it (msm_plan.h), fill the kernel's arguments from the plan and the job, launch, hand the row sums on by route.
 static MsmTicket msm_launch(DevCtx &c, const DeviceGens &g, const MsmJob &j, const BulletArgs *bul) {
     if (j.n_extra > 8) throw Error(OTTI_ERR_INTERNAL, "msm: too many extra terms");
+    // the table may be a longer generator set's (adopt_gens_table): what a launch reads is bounded by the table, not by the caller's R + 2
+    if ((bul ? 2 * j.n_dense : j.n_dense) > g.nbases) throw Error(OTTI_ERR_INTERNAL, "msm: the row length exceeds the table");
+    for (size_t i = 0; i < j.n_extra; i++) if (j.extra_base[i] >= g.nbases) throw Error(OTTI_ERR_INTERNAL, "msm: an extra term's base lies beyond the table");
     const size_t rows = j.rows;
     if (!rows) return {};
     const MsmPlan p = msm_plan({g.c, g.W, rows, j.n_dense, j.n_extra, bul != nullptr, j.mode, j.addend != nullptr, j.sparse, j.force_bulk, c.msm_mail.host_sum(c)});

@@ -60,6 +60,17 @@ void ensure_gens_device(Gens &g) {
 // frees the window table (the next ensure_gens_device builds it again): a caller that needs the HBM for another generator set's table
 void release_gens_device(Gens &g) { std::lock_guard<std::mutex> lk(device_objects_mu()); g.dev.reset(); }
 void ensure_device_objects(Instance &I, Gens &g) { ensure_instance_device(I); ensure_gens_device(g); }
+// g gives up its own table and holds the donor's from here on (Gens::dev is shared ownership: the table goes with its last holder).  Every
+// Gens of one stream label takes stream point j as P[j], and the table is base-major, so a table over more points holds every entry a
+// shorter Gens looks up: same addresses, entry0(base) = table + base * W * E.  The CALLER has compared labels and lengths.  Not beside a
+// proof with either: provers hold `const DeviceGens &` into *g.dev.
+void adopt_gens_table(Gens &g, Gens &donor) {
+    { std::lock_guard<std::mutex> lk(device_objects_mu()); if (g.dev && g.dev == donor.dev) return; }
+    ensure_gens_device(donor);
+    std::lock_guard<std::mutex> lk(device_objects_mu());
+    if (donor.dev->nbases < g.P.size()) throw Error(OTTI_ERR_INTERNAL, "adopt: the donor's table covers fewer points than the adopter has");
+    g.dev = donor.dev;
+}
 
 // the verifiers' fixed-base sums (spartan.h g_fixed_base_msm_hook): one row over the resident table; never builds a table for it
 static bool fixed_base_msm_on_device(const Gens &g, const Fr *s, size_t n, Pt &out) {

@@ -1,51 +1,10 @@
-// spzk — drop-in for the reference's spartan-zkinterface binary.
-//   spzk verify --nizk <X.zkif> <X.inp.zkif> <X.wit.zkif>      [REF /root/reference/run.py:58 (via cargo run), run.py:100 (binary)]
-// Reads the three zkInterface files, builds the R1CS instance, proves it on the MI355X, verifies the proof, prints
-// "Verification successful" plus stage runtimes [REF /root/reference/README.md:46-48], exit status 0 on success.
-// Without --nizk the same files go through SNARK mode (upstream spartan-zkinterface's default [RECALL]): SNARK::encode commits to the
-// circuit, SNARK::prove adds the R1CSEvalProof, SNARK::verify checks it against the commitment alone.
-// Additive options: --seed <hex32>, --proof-out <file>, --label <transcript label>, `spzk synth <n> <prefix>` to emit a
-// synthetic zkif triple; `spzk check` and --check: does the assignment satisfy the circuit, and if not, which constraints fail
-// (otti_witness_check_sat: on the device, on the uploaded assignment; no generators are made for `check`).
-// SNARK mode across processes: `spzk encode` writes the computation commitment, `spzk prove --comm-in` completes its copy of it
-// (otti_comp_comm_attach) and proves, `spzk verify <inputs> --comm-in --proof-in` checks the proof holding nothing but the commitment
-// and the public inputs — no circuit, no witness, no GPU.
-#include <stdio.h>
-#include <thread>
-#include <time.h>
-#include <unistd.h>
+// spzk — the process around one request (spzk_run.cpp has the subcommands), or, as `spzk serve`, around many (spzk_serve.cpp).
 #include <stdlib.h>
 #include <string.h>
-#include <string>
-#include <vector>
-#include <chrono>
-#include <algorithm>
+#include <time.h>
 #include <unistd.h>
-#include "../../include/otti_spartan.h"
-
-static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-static int fail(const char *what, int rc) {
-    char msg[512]; otti_last_error(msg, sizeof msg);
-    fprintf(stderr, "spzk: %s failed (%d): %s\n", what, rc, msg);
-    return 1;
-}
-static int usage() {
-    fprintf(stderr, "usage: spzk verify [--nizk] <circuit.zkif> <inputs.inp.zkif> <witness.wit.zkif> [--seed HEX64] [--proof-out FILE] [--label STR] [--check]\n"
-                    "            (the reference's invocation: prove, then verify, in one process; without --nizk: SNARK mode)\n"
-                    "       spzk prove  --nizk <circuit.zkif> <inputs.inp.zkif> <witness.wit.zkif> --proof-out FILE [--seed HEX64] [--label STR] [--check]\n"
-                    "       spzk verify --nizk <circuit.zkif> <inputs.inp.zkif> --proof-in FILE [--label STR]\n"
-                    "       spzk encode <circuit.zkif> [<inputs.inp.zkif>] --comm-out FILE\n"
-                    "            (SNARK::encode: writes the computation commitment)\n"
-                    "       spzk prove  <circuit.zkif> <inputs.inp.zkif> <witness.wit.zkif> [--comm-in FILE] --proof-out FILE [--seed HEX64] [--label STR] [--check] [--verify-comm]\n"
-                    "            (SNARK::prove from a stored commitment; --verify-comm: recompute it and compare first; without --comm-in: encodes itself)\n"
-                    "       spzk verify <inputs.inp.zkif> --comm-in FILE --proof-in FILE [--label STR]\n"
-                    "            (SNARK::verify from the commitment and the public inputs alone: no circuit, no witness, no GPU)\n"
-                    "       spzk check [--nizk] <circuit.zkif> <inputs.inp.zkif> <witness.wit.zkif>\n"
-                    "            (does the assignment satisfy the circuit? exit 0: yes; 1: no, with the failing constraints; no proof is made)\n"
-                    "            --check: the same test after the upload, before proving; an unsatisfied assignment is reported and not proved\n"
-                    "       spzk synth <num_constraints> <out_prefix> [num_inputs] [seed]\n");
-    return 2;
-}
+#include "spzk_run.h"
+#include "spzk_serve.h"
 
 // milliseconds from the creation of this process (execve) to now: /proc/self/stat's start time (clock ticks since boot) against
 // CLOCK_BOOTTIME — what the dynamic loader spent mapping libamdhip64 and its dependencies before main() ran (10 ms resolution)
@@ -60,283 +19,17 @@ static double ms_since_process_start() {
     return (ts.tv_sec * 1e3 + ts.tv_nsec * 1e-6) - 1e3 * (double)start / (double)sysconf(_SC_CLK_TCK);
 }
 
-// The satisfiability check on the uploaded assignment.  0: satisfied; 1: not (the report is printed); -1: the call itself failed (reported).
-constexpr size_t kCheckRows = 16;                              // failing constraints listed at most
-static void print_hex32(const uint8_t *le) { for (int i = 31; i >= 0; i--) printf("%02x", le[i]); }   // canonical value, most significant digit first
-static int run_check(otti_instance *inst, otti_witness *wit, uint64_t num_cons) {
-    uint64_t n_unsat = 0, rows[kCheckRows]; uint8_t abc[96 * kCheckRows]; float kernel_ms = 0;
-    const double t0 = now_ms();
-    const int rc = otti_witness_check_sat(inst, wit, &n_unsat, rows, kCheckRows, abc, &kernel_ms);
-    if (rc) { fail("check_sat", rc); return -1; }
-    printf("* check_sat %.3f ms\n  * kernel %.3f ms\n", now_ms() - t0, kernel_ms);
-    if (!n_unsat) return 0;
-    printf("Unsatisfied: %llu of %llu constraints\n", (unsigned long long)n_unsat, (unsigned long long)num_cons);
-    for (size_t i = 0; i < kCheckRows && i < n_unsat; i++) {
-        printf("  constraint %llu: A.z=", (unsigned long long)rows[i]); print_hex32(abc + 96 * i);
-        printf(" B.z="); print_hex32(abc + 96 * i + 32); printf(" C.z="); print_hex32(abc + 96 * i + 64); printf("\n");
-    }
-    return 1;
-}
-
-static bool read_file(const char *path, std::vector<uint8_t> &out) {
-    FILE *f = fopen(path, "rb");
-    if (!f) { fprintf(stderr, "spzk: cannot read %s\n", path); return false; }
-    fseek(f, 0, SEEK_END); const long len = ftell(f); fseek(f, 0, SEEK_SET);
-    out.resize(len > 0 ? (size_t)len : 0);
-    const bool ok = fread(out.data(), 1, out.size(), f) == out.size();
-    fclose(f);
-    if (!ok) fprintf(stderr, "spzk: short read on %s\n", path);
-    return ok;
-}
-static bool write_file(const char *path, const uint8_t *p, size_t n) {
-    FILE *f = fopen(path, "wb");
-    const bool ok = f && fwrite(p, 1, n, f) == n;
-    if (f) fclose(f);
-    if (!ok) fprintf(stderr, "spzk: cannot write %s\n", path);
-    return ok;
-}
-
-// ---- SNARK mode, one role per process.  role 'e': encode, 'p': prove, 'v': verify.  Returns the exit status.
-struct SnarkRoleArgs { char role; std::vector<const char *> files; const char *comm_in, *comm_out, *proof_in, *proof_out, *label; const uint8_t *seed; bool check, verify_comm; };
-static int snark_role(const SnarkRoleArgs &a) {
-    int rc; double t0 = now_ms();
-    if (a.role == 'v') {                                       // the commitment, the public inputs, the proof: nothing else, and no device
-        std::vector<uint8_t> cb, proof;
-        if (!read_file(a.comm_in, cb) || !read_file(a.proof_in, proof)) return 1;
-        otti_comp_comm *cc = nullptr; rc = otti_comp_comm_from_bytes(cb.data(), cb.size(), &cc); if (rc) return fail("commitment parse", rc);
-        otti_r1cs *r = nullptr; rc = otti_zkif_load_inputs(a.files[0], &r); if (rc) return fail("zkif load (inputs)", rc);
-        uint64_t nc, nv, ni, nops; rc = otti_comp_comm_dims(cc, &nc, &nv, &ni, &nops, nullptr); if (rc) return fail("commitment dimensions", rc);
-        otti_snark_gens *sg = nullptr; rc = otti_snark_gens_new(nc, nv, ni, nops, &sg); if (rc) return fail("SNARKGens::new", rc);
-        const double t_setup = now_ms() - t0; t0 = now_ms();
-        rc = otti_snark_verify(cc, r->inputs32, r->ninputs, sg, (const uint8_t *)a.label, strlen(a.label), proof.data(), proof.size());
-        printf("* commitment: %llu constraints, %llu variables, %llu inputs, %llu operations per matrix (%zu bytes)\n* setup (parse, SNARKGens::new) %.3f ms\n* SNARK::verify %.3f ms\n",
-               (unsigned long long)nc, (unsigned long long)nv, (unsigned long long)ni, (unsigned long long)nops, cb.size(), t_setup, now_ms() - t0);
-        if (rc) { char msg[512]; otti_last_error(msg, sizeof msg); printf("Verification FAILED (%d%s%s)\n", rc, msg[0] ? ": " : "", msg); return 1; }
-        printf("Verification successful\n");
-        return 0;
-    }
-    otti_r1cs *r = nullptr;
-    rc = otti_zkif_load(a.files[0], a.files.size() > 1 ? a.files[1] : nullptr, a.role == 'p' ? a.files[2] : nullptr, &r); if (rc) return fail("zkif load", rc);
-    const double t_load = now_ms() - t0; t0 = now_ms();
-    otti_instance *inst = nullptr;
-    rc = otti_instance_new(r->num_cons, r->num_vars, r->num_inputs, r->A, r->nA, r->B, r->nB, r->C, r->nC, &inst); if (rc) return fail("Instance::new", rc);
-    const uint64_t nnz = std::max<uint64_t>({(uint64_t)r->nA, (uint64_t)r->nB, (uint64_t)r->nC});
-    otti_snark_gens *sg = nullptr; rc = otti_snark_gens_new(r->num_cons, r->num_vars, r->num_inputs, nnz, &sg); if (rc) return fail("SNARKGens::new", rc);
-    const double t_setup = now_ms() - t0; t0 = now_ms();
-    uint64_t nc, nv, ni; otti_instance_dims(inst, &nc, &nv, &ni);
-    printf("* instance: %llu constraints (padded %llu), %llu variables (padded %llu), %llu inputs, %llu non-zero entries in the largest matrix\n", (unsigned long long)r->num_cons,
-           (unsigned long long)nc, (unsigned long long)r->num_vars, (unsigned long long)nv, (unsigned long long)ni, (unsigned long long)nnz);
-    printf("* zkif_load %.3f ms\n* setup (Instance::new, SNARKGens::new) %.3f ms\n", t_load, t_setup);
-    otti_comp_comm *cc = nullptr;
-    if (a.comm_in) {                                           // the stored commitment, completed from this process's own instance
-        std::vector<uint8_t> cb;
-        if (!read_file(a.comm_in, cb)) return 1;
-        rc = otti_comp_comm_from_bytes(cb.data(), cb.size(), &cc); if (rc) return fail("commitment parse", rc);
-        rc = otti_comp_comm_attach(cc, inst, sg, a.verify_comm ? OTTI_ATTACH_VERIFY : 0u); if (rc) return fail("commitment attach", rc);
-        printf("* attach%s %.3f ms (computation commitment %zu bytes)\n", a.verify_comm ? " (commitments recomputed and compared)" : "", now_ms() - t0, cb.size());
-    } else {
-        rc = otti_snark_encode(inst, sg, &cc); if (rc) return fail("SNARK::encode", rc);
-        uint8_t *cb = nullptr; size_t cb_len = 0; rc = otti_comp_comm_bytes(cc, &cb, &cb_len); if (rc) return fail("commitment bytes", rc);
-        printf("* SNARK::encode %.3f ms (computation commitment %zu bytes)\n", now_ms() - t0, cb_len);
-        if (a.comm_out && !write_file(a.comm_out, cb, cb_len)) return 1;
-        if (a.comm_out) printf("Commitment written to %s (%zu bytes)\n", a.comm_out, cb_len);
-        otti_buf_free(cb);
-    }
-    if (a.role == 'e') { fflush(stdout); _exit(0); }          // everything is printed and written: skip the HIP runtime's teardown
-    t0 = now_ms();
-    otti_witness *wit = nullptr;
-    if (a.check) {
-        rc = otti_witness_upload(inst, r->vars32, r->nvars, r->inputs32, r->ninputs, &wit); if (rc) return fail("witness upload", rc);
-        const int sat = run_check(inst, wit, r->num_cons);
-        if (sat < 0) return 1;
-        if (sat) { printf("Not proved (unsatisfied assignment)\n"); return 1; }
-        t0 = now_ms();
-    }
-    uint8_t *proof = nullptr; size_t proof_len = 0; double st[10] = {0};
-    if (wit) rc = otti_snark_prove_resident(inst, cc, wit, sg, (const uint8_t *)a.label, strlen(a.label), a.seed, &proof, &proof_len, st);
-    else rc = otti_snark_prove(inst, cc, r->vars32, r->nvars, r->inputs32, r->ninputs, sg, (const uint8_t *)a.label, strlen(a.label), a.seed, OTTI_FLAG_GPU, &proof, &proof_len, st);
-    if (rc) return fail("SNARK::prove", rc);
-    printf("* SNARK::prove %.3f ms\n  * polycommit %.3f ms\n  * multiply_vec %.3f ms\n  * prove_sc_phase_one %.3f ms\n  * eval_table_sparse %.3f ms\n  * prove_sc_phase_two %.3f ms\n"
-           "  * polyeval %.3f ms\n  * R1CSEvalProof: derefs commitment %.3f ms, product circuits %.3f ms, hash layer %.3f ms\n  * len_snark_proof %zu\n",
-           now_ms() - t0, st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8], proof_len);
-    if (!write_file(a.proof_out, proof, proof_len)) return 1;
-    printf("Proof written to %s (%zu bytes)\n", a.proof_out, proof_len);
-    fflush(stdout);
-    _exit(0);
-}
+// one proof per process: generators are made for it and belong to it
+struct OneShotGens : GensProvider {
+    int nizk_gens(uint64_t nc, uint64_t nv, uint64_t ni, otti_gens **out) override { return otti_gens_new(nc, nv, ni, out); }
+    int prepare(otti_instance *inst, otti_gens *gens) override { return otti_prepare_device(inst, gens); }
+    int snark_gens(uint64_t nc, uint64_t nv, uint64_t ni, uint64_t nops, otti_snark_gens **out) override { return otti_snark_gens_new(nc, nv, ni, nops, out); }
+};
 
 int main(int argc, char **argv) {
-    const double t_before_main = ms_since_process_start(), t_main0 = now_ms();
-    if (argc < 2) return usage();
-    if (!strcmp(argv[1], "synth")) {
-        if (argc < 4) return usage();
-        uint64_t n = strtoull(argv[2], 0, 0), ni = argc > 4 ? strtoull(argv[4], 0, 0) : 10, seed = argc > 5 ? strtoull(argv[5], 0, 0) : 1;
-        otti_r1cs *r = nullptr; int rc = otti_synth_r1cs(n, ni, seed, &r); if (rc) return fail("synth", rc);
-        std::string p = argv[3];
-        rc = otti_zkif_write(r, (p + ".zkif").c_str(), (p + ".inp.zkif").c_str(), (p + ".wit.zkif").c_str());
-        otti_r1cs_free(r); if (rc) return fail("zkif write", rc);
-        printf("wrote %s.zkif %s.inp.zkif %s.wit.zkif (%llu constraints)\n", p.c_str(), p.c_str(), p.c_str(), (unsigned long long)n);
-        return 0;
-    }
-    const bool prove_only = !strcmp(argv[1], "prove"), check_only = !strcmp(argv[1], "check"), encode_only = !strcmp(argv[1], "encode");
-    if (!prove_only && !check_only && !encode_only && strcmp(argv[1], "verify")) return usage();
-    // one proof per process: the generator window table is built and used once, so a narrow window (small table, ~7 ms to build for
-    // R = 1024) beats the wide one a long-lived prover process amortises (see prover.cpp device_window_bits); an explicit setting wins
-    setenv("OTTI_MSM_WINDOW", "10", 0);
-    bool nizk = false, label_given = false, check = false, verify_comm = false; std::vector<const char *> files;
-    const char *seed_hex = nullptr, *proof_out = nullptr, *proof_in = nullptr, *comm_in = nullptr, *comm_out = nullptr, *label = "nizk_example";
-    for (int i = 2; i < argc; i++) {
-        if (!strcmp(argv[i], "--nizk")) nizk = true;
-        else if (!strcmp(argv[i], "--check")) check = true;
-        else if (!strcmp(argv[i], "--seed") && i + 1 < argc) seed_hex = argv[++i];
-        else if (!strcmp(argv[i], "--proof-out") && i + 1 < argc) proof_out = argv[++i];
-        else if (!strcmp(argv[i], "--proof-in") && i + 1 < argc) proof_in = argv[++i];
-        else if (!strcmp(argv[i], "--comm-in") && i + 1 < argc) comm_in = argv[++i];
-        else if (!strcmp(argv[i], "--comm-out") && i + 1 < argc) comm_out = argv[++i];
-        else if (!strcmp(argv[i], "--verify-comm")) verify_comm = true;
-        else if (!strcmp(argv[i], "--label") && i + 1 < argc) { label = argv[++i]; label_given = true; }
-        else files.push_back(argv[i]);
-    }
-    const bool verify_only = proof_in != nullptr;
-    if (check_only) {                                          // load, Instance::new, upload, check: no generators, no window table
-        if (files.size() != 3 || verify_only || proof_out || comm_in || comm_out) return usage();
-        otti_r1cs *r = nullptr; int rc = otti_zkif_load(files[0], files[1], files[2], &r); if (rc) return fail("zkif load", rc);
-        otti_instance *inst = nullptr;
-        rc = otti_instance_new(r->num_cons, r->num_vars, r->num_inputs, r->A, r->nA, r->B, r->nB, r->C, r->nC, &inst); if (rc) return fail("Instance::new", rc);
-        rc = otti_prepare_device(inst, nullptr); if (rc) return fail("device setup", rc);
-        otti_witness *wit = nullptr;
-        rc = otti_witness_upload(inst, r->vars32, r->nvars, r->inputs32, r->ninputs, &wit); if (rc) return fail("witness upload", rc);
-        const int sat = run_check(inst, wit, r->num_cons);
-        if (sat == 0) printf("Satisfied\n");
-        fflush(stdout);
-        _exit(sat == 0 ? 0 : 1);                               // as below: skip the HIP runtime's teardown
-    }
-    if (check && verify_only) return usage();                  // a separate verifier has no witness to check
-    // the stored computation commitment belongs to SNARK mode; its roles: encode / prove / verify --comm-in --proof-in (snark_role)
-    if (nizk && (encode_only || comm_in || comm_out || verify_comm)) return usage();
-    const bool snark_split = !nizk && (encode_only || prove_only || verify_only);
-    if (!nizk && !label_given) label = "snark_example";
-    if (prove_only && (verify_only || !proof_out)) return usage();
-    if (snark_split) {
-        if (encode_only && (!comm_out || comm_in || proof_out || verify_only || check || verify_comm || (files.size() != 1 && files.size() != 2))) return usage();
-        if (prove_only && (files.size() != 3 || comm_out || (verify_comm && !comm_in))) return usage();
-        if (verify_only && (!comm_in || comm_out || proof_out || verify_comm || files.size() != 1)) {
-            fprintf(stderr, "spzk: SNARK mode verifies a stored proof against a stored commitment: verify <inputs.inp.zkif> --comm-in FILE --proof-in FILE\n"); return usage();
-        }
-    } else {
-        if (comm_in || comm_out || verify_comm) return usage();
-        if (verify_only ? (files.size() != 2 && files.size() != 3) : files.size() != 3) return usage();
-    }
-    uint8_t seed[32]; const uint8_t *seedp = nullptr;
-    if (seed_hex) {
-        if (strlen(seed_hex) != 64) { fprintf(stderr, "spzk: --seed wants 64 hex digits\n"); return 2; }
-        for (int i = 0; i < 32; i++) { unsigned v; if (sscanf(seed_hex + 2 * i, "%2x", &v) != 1) return usage(); seed[i] = (uint8_t)v; }
-        seedp = seed;
-    }
-    // the HIP runtime takes a noticeable fraction of a second to come up: let it do so while the files are being parsed
-    std::thread warm([&] { if (!verify_only && otti_device_count() > 0) (void)otti_prepare_device(nullptr, nullptr); });
-    struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{warm};
-    if (snark_split) {
-        SnarkRoleArgs a{encode_only ? 'e' : prove_only ? 'p' : 'v', files, comm_in, comm_out, proof_in, proof_out, label, seedp, check, verify_comm};
-        const int status = snark_role(a);
-        fflush(stdout);
-        return status;
-    }
-    double t0 = now_ms();
-    otti_r1cs *r = nullptr; int rc = otti_zkif_load(files[0], files[1], verify_only ? nullptr : files[2], &r); if (rc) return fail("zkif load", rc);
-    double t_load = now_ms() - t0; t0 = now_ms();
-    // NIZKGens::new (a thousand hash-to-group maps and the host window tables) depends on the sizes only: it runs next to Instance::new
-    otti_gens *gens_early = nullptr; int gens_rc = 0;
-    std::thread gens_thread;
-    if (nizk) gens_thread = std::thread([&] { gens_rc = otti_gens_new(r->num_cons, r->num_vars, r->num_inputs, &gens_early); });
-    auto gens_rc_wait = [&] { if (gens_thread.joinable()) gens_thread.join(); return gens_rc; };
-    struct GensJoiner { std::thread &t; ~GensJoiner() { if (t.joinable()) t.join(); } } gens_joiner{gens_thread};
-    otti_instance *inst = nullptr;
-    rc = otti_instance_new(r->num_cons, r->num_vars, r->num_inputs, r->A, r->nA, r->B, r->nB, r->C, r->nC, &inst); if (rc) return fail("Instance::new", rc);
-    otti_witness *wit = nullptr;                               // --check: the assignment is uploaded once, checked, and proved from HBM
-    if (check) {
-        rc = otti_prepare_device(inst, nullptr); if (rc) return fail("device setup", rc);
-        rc = otti_witness_upload(inst, r->vars32, r->nvars, r->inputs32, r->ninputs, &wit); if (rc) return fail("witness upload", rc);
-        const int sat = run_check(inst, wit, r->num_cons);
-        if (sat < 0) return 1;
-        if (sat) { printf("Verification FAILED (unsatisfied assignment)\n"); return 1; }
-    }
-    if (!nizk) {                                               // ---- SNARK mode: encode, prove, verify
-        const uint64_t nnz = std::max<uint64_t>({(uint64_t)r->nA, (uint64_t)r->nB, (uint64_t)r->nC});
-        otti_snark_gens *sg = nullptr; rc = otti_snark_gens_new(r->num_cons, r->num_vars, r->num_inputs, nnz, &sg); if (rc) return fail("SNARKGens::new", rc);
-        double t_setup = now_ms() - t0; t0 = now_ms();
-        otti_comp_comm *cc = nullptr; rc = otti_snark_encode(inst, sg, &cc); if (rc) return fail("SNARK::encode", rc);
-        double t_encode = now_ms() - t0; t0 = now_ms();
-        uint8_t *proof = nullptr; size_t proof_len = 0; double st[10] = {0};
-        if (wit) rc = otti_snark_prove_resident(inst, cc, wit, sg, (const uint8_t *)label, strlen(label), seedp, &proof, &proof_len, st);
-        else rc = otti_snark_prove(inst, cc, r->vars32, r->nvars, r->inputs32, r->ninputs, sg, (const uint8_t *)label, strlen(label), seedp, OTTI_FLAG_GPU, &proof, &proof_len, st);
-        if (rc) return fail("SNARK::prove", rc);
-        double t_prove = now_ms() - t0; t0 = now_ms();
-        // the verifier's copy of the commitment: its bytes only
-        uint8_t *cb = nullptr; size_t cb_len = 0; rc = otti_comp_comm_bytes(cc, &cb, &cb_len); if (rc) return fail("commitment bytes", rc);
-        otti_comp_comm *vc = nullptr; rc = otti_comp_comm_from_bytes(cb, cb_len, &vc); if (rc) return fail("commitment parse", rc);
-        rc = otti_snark_verify(vc, r->inputs32, r->ninputs, sg, (const uint8_t *)label, strlen(label), proof, proof_len);
-        double t_verify = now_ms() - t0;
-        uint64_t nc, nv, ni; otti_instance_dims(inst, &nc, &nv, &ni);
-        printf("* instance: %llu constraints (padded %llu), %llu variables (padded %llu), %llu inputs, %llu non-zero entries in the largest matrix\n", (unsigned long long)r->num_cons,
-               (unsigned long long)nc, (unsigned long long)r->num_vars, (unsigned long long)nv, (unsigned long long)ni, (unsigned long long)nnz);
-        printf("* zkif_load %.3f ms\n* setup (Instance::new, SNARKGens::new) %.3f ms\n* SNARK::encode %.3f ms (computation commitment %zu bytes)\n", t_load, t_setup, t_encode, cb_len);
-        printf("* SNARK::prove %.3f ms\n  * polycommit %.3f ms\n  * multiply_vec %.3f ms\n  * prove_sc_phase_one %.3f ms\n  * eval_table_sparse %.3f ms\n  * prove_sc_phase_two %.3f ms\n"
-               "  * polyeval %.3f ms\n  * R1CSEvalProof: derefs commitment %.3f ms, product circuits %.3f ms, hash layer %.3f ms\n  * len_snark_proof %zu\n",
-               t_prove, st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8], proof_len);
-        printf("* SNARK::verify %.3f ms\n", t_verify);
-        int wrc = 0;
-        if (proof_out && !rc) { FILE *f = fopen(proof_out, "wb"); if (!f || fwrite(proof, 1, proof_len, f) != proof_len) { fprintf(stderr, "spzk: cannot write %s\n", proof_out); wrc = 1; } if (f) fclose(f); }
-        otti_buf_free(proof); otti_buf_free(cb); otti_comp_comm_free(vc); otti_comp_comm_free(cc); otti_snark_gens_free(sg); otti_instance_free(inst); otti_r1cs_free(r);
-        if (rc) { printf("Verification FAILED (%d)\n", rc); return 1; }
-        if (wrc) return 1;
-        printf("Verification successful\n");
-        return 0;
-    }
-    otti_gens *gens = nullptr; rc = gens_rc_wait(); if (rc) return fail("NIZKGens::new", rc);
-    gens = gens_early;
-    double t_objs = now_ms() - t0;
-    if (!verify_only) { rc = otti_prepare_device(inst, gens); if (rc) return fail("device setup", rc); }
-    double t_setup = now_ms() - t0; t0 = now_ms();
-    uint8_t *proof = nullptr; size_t proof_len = 0; double st[8] = {0}, t_prove = 0, t_verify = 0;
-    if (verify_only) {
-        FILE *f = fopen(proof_in, "rb");
-        if (!f) { fprintf(stderr, "spzk: cannot read %s\n", proof_in); return 1; }
-        fseek(f, 0, SEEK_END); long len = ftell(f); fseek(f, 0, SEEK_SET);
-        proof = (uint8_t *)malloc(len > 0 ? (size_t)len : 1); proof_len = len > 0 ? (size_t)len : 0;
-        if (fread(proof, 1, proof_len, f) != proof_len) { fclose(f); fprintf(stderr, "spzk: short read on %s\n", proof_in); return 1; }
-        fclose(f);
-    } else {
-        if (wit) rc = otti_nizk_prove_resident(inst, wit, gens, (const uint8_t *)label, strlen(label), seedp, &proof, &proof_len, st);
-        else rc = otti_nizk_prove(inst, r->vars32, r->nvars, r->inputs32, r->ninputs, gens, (const uint8_t *)label, strlen(label), seedp, OTTI_FLAG_GPU, &proof,
-                                  &proof_len, st);
-        if (rc) return fail("NIZK::prove", rc);
-        t_prove = now_ms() - t0; t0 = now_ms();
-    }
-    if (!prove_only) {
-        rc = otti_nizk_verify(inst, r->inputs32, r->ninputs, gens, (const uint8_t *)label, strlen(label), proof, proof_len);
-        t_verify = now_ms() - t0;
-    }
-    uint64_t nc, nv, ni; otti_instance_dims(inst, &nc, &nv, &ni);
-    printf("* instance: %llu constraints (padded %llu), %llu variables (padded %llu), %llu inputs\n", (unsigned long long)r->num_cons, (unsigned long long)nc,
-           (unsigned long long)r->num_vars, (unsigned long long)nv, (unsigned long long)ni);
-    printf("* zkif_load %.3f ms\n* setup (Instance::new, NIZKGens::new, device tables) %.3f ms\n  * host objects %.3f ms\n", t_load, t_setup, t_objs);
-    if (!verify_only)
-        printf("* NIZK::prove %.3f ms\n  * polycommit %.3f ms\n  * multiply_vec %.3f ms\n  * prove_sc_phase_one %.3f ms\n  * eval_table_sparse %.3f ms\n"
-               "  * prove_sc_phase_two %.3f ms\n  * polyeval %.3f ms\n  * len_r1cs_sat_proof %zu\n", t_prove, st[0], st[1], st[2], st[3], st[4], st[5], proof_len);
-    if (!prove_only) printf("* NIZK::verify %.3f ms\n", t_verify);
-    int wrc = 0;
-    if (proof_out && !rc) {
-        FILE *f = fopen(proof_out, "wb");
-        if (!f || fwrite(proof, 1, proof_len, f) != proof_len) { fprintf(stderr, "spzk: cannot write %s\n", proof_out); wrc = 1; }
-        if (f) fclose(f);
-    }
-    // (no frees: the process ends here and hands everything back at once — releasing the device tables one by one costs milliseconds)
-    printf("* process start to main() %.0f ms (the dynamic loader mapping the HIP runtime), main() %.3f ms\n", t_before_main, now_ms() - t_main0);
-    if (rc) { printf("Verification FAILED (%d: %s)\n", rc, rc == OTTI_ERR_VERIFY_DECOMPRESS ? "DecompressionError" : rc == OTTI_ERR_VERIFY_INTERNAL ? "InternalError" : "malformed proof"); return 1; }
-    if (wrc) return 1;
-    if (prove_only) { printf("Proof written to %s (%zu bytes)\n", proof_out, proof_len); fflush(stdout); _exit(0); }
-    printf("Verification successful\n");
-    fflush(stdout);
-    _exit(0);                                                  // everything is printed and written: skip the HIP runtime's teardown
+    const double t_before_main = ms_since_process_start();
+    if (argc >= 2 && !strcmp(argv[1], "serve")) return spzk_serve_main(argc, argv);
+    OneShotGens gens;
+    const RunEnv E{stdout, stderr, nullptr, &gens, false, 0.0, nullptr, t_before_main};
+    return spzk_run(argc, argv, E);
 }
