@@ -16,6 +16,45 @@ static void load_assignment(const Instance &I, const uint8_t *vars32, size_t nva
     inputs = scalars_from_bytes(inputs32, ninputs);
 }
 
+// ---- a witness from host bytes, from device memory, from host integers, and changed in place (device.h WitFormat, k_field.hip k_witness_ingest_from).  Everything
+// that can be said about the arguments alone is said before DevCtx::get() brings a device up.
+static void check_wit_source(const void *src, size_t count, int32_t format, size_t stride_bytes, bool on_device) {
+    if (format < OTTI_WIT_CANONICAL32 || format > OTTI_WIT_U64) throw Error(OTTI_ERR_BAD_ARG, "unknown witness format");
+    if (!src && count) throw Error(OTTI_ERR_BAD_ARG, "null source with a non-zero count");
+    if (stride_bytes && (stride_bytes < wit_elem_bytes(format) || stride_bytes % 8)) throw Error(OTTI_ERR_BAD_ARG, "stride_bytes below the element size or not a multiple of 8");
+    if (on_device && ((uintptr_t)src & 7)) throw Error(OTTI_ERR_BAD_ARG, "a device source must be 8-byte aligned");
+}
+// a witness that keeps products (device.h DeviceWitness::prod_abc) is changed through the instance they were formed with, and no other: said before
+// z is written, so the refusal changes nothing
+static void check_products_instance(const otti_witness *wit, const Instance &I) {
+    if (wit->w->prod_inst && wit->w->prod_inst != &I) throw Error(OTTI_ERR_BAD_ARG, "the witness keeps products for another instance: the witness is unchanged");
+}
+// ---- the entries that change or compare a resident witness.  ONE ladder of refusals, in the order the header states for each of them: a null handle or
+// pointer (BAD_ARG), then `early` — everything the arguments alone say: the source (check_wit_source), the range or the index list as far as the host can
+// see it; it returns false to end the call there with OTTI_OK (an empty range is answered before a device is asked for) — then a missing device, said
+// before the witness handle is looked at, the witness's dimensions, for a mutator the instance its products were kept for, and the body.
+template <class Early, class Body>
+static int32_t witness_entry(otti_instance *inst, const otti_witness *wit, bool pointers_ok, bool mutates, Early early, Body body) {
+    return guarded([&] {
+        if (!inst || !wit || !pointers_ok) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (!early(inst->I->num_vars)) return OTTI_OK;
+        DevCtx::get();
+        check_witness_dims(wit, *inst->I);
+        if (mutates) check_products_instance(wit, *inst->I);
+        body(*wit->w);
+        return OTTI_OK;
+    });
+}
+// the entries that only read a handle or free what it keeps: null, no device (then no witness handle can exist: wit is not looked at), the body
+template <class Body> static int32_t witness_read(const otti_witness *wit, Body body) {
+    return guarded([&] {
+        if (!wit) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (otti_device_count() < 1) throw Error(OTTI_ERR_NO_DEVICE, "no device: no witness handle can exist");
+        body(*wit->w);
+        return OTTI_OK;
+    });
+}
+
 extern "C" {
 
 size_t otti_last_error(char *buf, size_t cap) {
@@ -136,19 +175,6 @@ int32_t otti_nizk_prove(otti_instance *inst, const uint8_t *vars32, size_t nvars
     });
 }
 void otti_witness_free(otti_witness *w) { delete w; }
-// ---- a witness from host bytes, from device memory, from host integers, and changed in place (device.h WitFormat, k_field.hip k_witness_ingest_from).  Everything
-// that can be said about the arguments alone is said before DevCtx::get() brings a device up.
-static void check_wit_source(const void *src, size_t count, int32_t format, size_t stride_bytes, bool on_device) {
-    if (format < OTTI_WIT_CANONICAL32 || format > OTTI_WIT_U64) throw Error(OTTI_ERR_BAD_ARG, "unknown witness format");
-    if (!src && count) throw Error(OTTI_ERR_BAD_ARG, "null source with a non-zero count");
-    if (stride_bytes && (stride_bytes < wit_elem_bytes(format) || stride_bytes % 8)) throw Error(OTTI_ERR_BAD_ARG, "stride_bytes below the element size or not a multiple of 8");
-    if (on_device && ((uintptr_t)src & 7)) throw Error(OTTI_ERR_BAD_ARG, "a device source must be 8-byte aligned");
-}
-// a witness that keeps products (device.h DeviceWitness::prod_abc) is changed through the instance they were formed with, and no other: said before
-// z is written, so the refusal changes nothing
-static void check_products_instance(const otti_witness *wit, const Instance &I) {
-    if (wit->w->prod_inst && wit->w->prod_inst != &I) throw Error(OTTI_ERR_BAD_ARG, "the witness keeps products for another instance: the witness is unchanged");
-}
 static int32_t witness_from(otti_instance *inst, const void *src, size_t nvars, int32_t format, size_t stride_bytes, bool on_device, const uint8_t *inputs32,
                             size_t ninputs, void *stream, otti_witness **out) {
     return guarded([&] {
@@ -173,107 +199,74 @@ int32_t otti_witness_upload_ints(otti_instance *inst, const void *vars, size_t n
 }
 int32_t otti_witness_update(otti_instance *inst, otti_witness *wit, size_t first, const void *src, size_t count, int32_t format, size_t stride_bytes,
                             int32_t src_on_device, void *stream) {
-    return guarded([&] {
-        if (!inst || !wit) throw Error(OTTI_ERR_BAD_ARG, "null argument");
-        check_wit_source(src, count, format, stride_bytes, src_on_device != 0);
-        const size_t V = inst->I->num_vars;
-        if (first > V || count > V - first) throw Error(OTTI_ERR_INVALID_NUM_VARS, "the range ends beyond the instance's variables");
-        DevCtx::get();                                            // no device: said before the witness handle is looked at
-        check_witness_dims(wit, *inst->I);
-        check_products_instance(wit, *inst->I);
-        wit->w->update(first, format, src, count, stride_bytes, src_on_device != 0, (hipStream_t)stream);
-        return OTTI_OK;
-    });
+    return witness_entry(inst, wit, true, true,
+        [&](size_t V) { check_wit_source(src, count, format, stride_bytes, src_on_device != 0); DeviceWitness::check_range(V, first, count); return true; },
+        [&](DeviceWitness &w) { w.update(first, format, src, count, stride_bytes, src_on_device != 0, (hipStream_t)stream); });
 }
-// ---- scatter update (device.h DeviceWitness::scatter).  The order of refusals: the arguments (BAD_ARG), the index list as far as the host can see it
-// (INVALID_INDEX: its length, and a host list itself in one pass), a missing device, the witness's dimensions, and on the device a bad device
-// index list before a scalar >= l.
+// ---- scatter update (device.h DeviceWitness::scatter).  `early`: the arguments (BAD_ARG), then the index list as far as the host can see it (INVALID_INDEX:
+// its length, and a host list itself in one pass); on the device a bad device index list is refused before a scalar >= l.
 int32_t otti_witness_scatter(otti_instance *inst, otti_witness *wit, const uint64_t *idx, const void *src, size_t count, int32_t format, size_t stride_bytes,
                              int32_t on_device, void *stream) {
-    return guarded([&] {
-        if (!inst || !wit) throw Error(OTTI_ERR_BAD_ARG, "null argument");
-        check_wit_source(src, count, format, stride_bytes, on_device != 0);
-        if (!idx && count) throw Error(OTTI_ERR_BAD_ARG, "null index list with a non-zero count");
-        if (on_device && ((uintptr_t)idx & 7)) throw Error(OTTI_ERR_BAD_ARG, "a device index list must be 8-byte aligned");
-        const size_t V = inst->I->num_vars;
-        if (count > V) throw Error(OTTI_ERR_INVALID_INDEX, "more indices than the instance has variables");
-        if (!on_device)
-            for (size_t i = 0; i < count; i++)
-                if (idx[i] >= V || (i && idx[i] <= idx[i - 1])) throw Error(OTTI_ERR_INVALID_INDEX, "the indices are not strictly ascending below the padded num_vars");
-        DevCtx::get();                                            // no device: said before the witness handle is looked at
-        check_witness_dims(wit, *inst->I);
-        check_products_instance(wit, *inst->I);
-        wit->w->scatter(idx, format, src, count, stride_bytes, on_device != 0, (hipStream_t)stream);
-        return OTTI_OK;
-    });
+    return witness_entry(inst, wit, true, true,
+        [&](size_t V) {
+            check_wit_source(src, count, format, stride_bytes, on_device != 0);
+            if (!idx && count) throw Error(OTTI_ERR_BAD_ARG, "null index list with a non-zero count");
+            if (on_device && ((uintptr_t)idx & 7)) throw Error(OTTI_ERR_BAD_ARG, "a device index list must be 8-byte aligned");
+            if (count > V) throw Error(OTTI_ERR_INVALID_INDEX, "more indices than the instance has variables");
+            if (!on_device)
+                for (size_t i = 0; i < count; i++)
+                    if (idx[i] >= V || (i && idx[i] <= idx[i - 1])) throw Error(OTTI_ERR_INVALID_INDEX, "the indices are not strictly ascending below the padded num_vars");
+            return true;
+        },
+        [&](DeviceWitness &w) { w.scatter(idx, format, src, count, stride_bytes, on_device != 0, (hipStream_t)stream); });
 }
 int32_t otti_witness_scatter_info(const otti_witness *wit, uint64_t *calls, uint64_t *rows_patched, uint64_t *terms_patched) {
-    return guarded([&] {
-        if (!wit) throw Error(OTTI_ERR_BAD_ARG, "null argument");
-        if (otti_device_count() < 1) throw Error(OTTI_ERR_NO_DEVICE, "no device: no witness handle can exist");
-        const DeviceWitness &w = *wit->w;
+    return witness_read(wit, [&](const DeviceWitness &w) {
         if (calls) *calls = w.scatter_calls;
         if (rows_patched) *rows_patched = w.rows_patched;
         if (terms_patched) *terms_patched = w.terms_patched;
-        return OTTI_OK;
     });
 }
-// ---- assign and its dry form (device.h DeviceWitness::assign / diff).  The order of refusals is otti_witness_update's, through the same
-// check_wit_source; an empty range is answered before a device is asked for.
+// ---- assign and its dry form (device.h DeviceWitness::assign / diff): otti_witness_update's order of refusals, and an empty range ends in `early`
 int32_t otti_witness_assign(otti_instance *inst, otti_witness *wit, size_t first, const void *src, size_t count, int32_t format, size_t stride_bytes,
                             int32_t src_on_device, void *stream, uint64_t *n_changed) {
-    return guarded([&] {
-        if (!inst || !wit) throw Error(OTTI_ERR_BAD_ARG, "null argument");
-        check_wit_source(src, count, format, stride_bytes, src_on_device != 0);
-        const size_t V = inst->I->num_vars;
-        if (first > V || count > V - first) throw Error(OTTI_ERR_INVALID_NUM_VARS, "the range ends beyond the instance's variables");
-        if (n_changed) *n_changed = 0;
-        if (!count) return OTTI_OK;
-        DevCtx::get();                                            // no device: said before the witness handle is looked at
-        check_witness_dims(wit, *inst->I);
-        check_products_instance(wit, *inst->I);
-        const size_t n = wit->w->assign(first, format, src, count, stride_bytes, src_on_device != 0, (hipStream_t)stream);
-        if (n_changed) *n_changed = n;
-        return OTTI_OK;
-    });
+    return witness_entry(inst, wit, true, true,
+        [&](size_t V) {
+            check_wit_source(src, count, format, stride_bytes, src_on_device != 0); DeviceWitness::check_range(V, first, count);
+            if (n_changed) *n_changed = 0;
+            return count != 0;
+        },
+        [&](DeviceWitness &w) {
+            const size_t n = w.assign(first, format, src, count, stride_bytes, src_on_device != 0, (hipStream_t)stream);
+            if (n_changed) *n_changed = n;
+        });
 }
 int32_t otti_witness_diff(otti_instance *inst, const otti_witness *wit, size_t first, const void *src, size_t count, int32_t format, size_t stride_bytes,
                           int32_t src_on_device, void *stream, uint64_t *n_changed, uint64_t *idx, size_t idx_cap) {
-    return guarded([&] {
-        if (!inst || !wit || !n_changed || (idx_cap && !idx)) throw Error(OTTI_ERR_BAD_ARG, "null argument");
-        check_wit_source(src, count, format, stride_bytes, src_on_device != 0);
-        const size_t V = inst->I->num_vars;
-        if (first > V || count > V - first) throw Error(OTTI_ERR_INVALID_NUM_VARS, "the range ends beyond the instance's variables");
-        *n_changed = 0;
-        if (!count) return OTTI_OK;
-        DevCtx::get();
-        check_witness_dims(wit, *inst->I);
-        *n_changed = wit->w->diff(first, format, src, count, stride_bytes, src_on_device != 0, (hipStream_t)stream, idx, idx_cap);
-        return OTTI_OK;
-    });
+    return witness_entry(inst, wit, n_changed && (idx || !idx_cap), false,
+        [&](size_t V) {
+            check_wit_source(src, count, format, stride_bytes, src_on_device != 0); DeviceWitness::check_range(V, first, count);
+            *n_changed = 0;
+            return count != 0;
+        },
+        [&](const DeviceWitness &w) { *n_changed = w.diff(first, format, src, count, stride_bytes, src_on_device != 0, (hipStream_t)stream, idx, idx_cap); });
 }
 int32_t otti_witness_assign_info(const otti_witness *wit, uint64_t *calls, uint64_t *changed, uint64_t *resums) {
-    return guarded([&] {
-        if (!wit) throw Error(OTTI_ERR_BAD_ARG, "null argument");
-        if (otti_device_count() < 1) throw Error(OTTI_ERR_NO_DEVICE, "no device: no witness handle can exist");
-        const DeviceWitness &w = *wit->w;
+    return witness_read(wit, [&](const DeviceWitness &w) {
         if (calls) *calls = w.assign_calls;
         if (changed) *changed = w.assign_changed;
         if (resums) *resums = w.assign_resums;
-        return OTTI_OK;
     });
 }
 int32_t otti_witness_set_inputs(otti_instance *inst, otti_witness *wit, const uint8_t *inputs32, size_t ninputs) {
-    return guarded([&] {
-        if (!inst || !wit || (!inputs32 && ninputs)) throw Error(OTTI_ERR_BAD_ARG, "null argument");
-        if (ninputs != inst->I->num_inputs) throw Error(OTTI_ERR_INVALID_NUM_INPUTS, "wrong number of inputs");
-        const std::vector<Fr> inputs = scalars_from_bytes(inputs32, ninputs);      // INVALID_SCALAR: a host check, the witness is not touched
-        DevCtx::get();
-        check_witness_dims(wit, *inst->I);
-        check_products_instance(wit, *inst->I);
-        wit->w->set_inputs(inputs);
-        return OTTI_OK;
-    });
+    std::vector<Fr> inputs;
+    return witness_entry(inst, wit, inputs32 || !ninputs, true,
+        [&](size_t) {
+            if (ninputs != inst->I->num_inputs) throw Error(OTTI_ERR_INVALID_NUM_INPUTS, "wrong number of inputs");
+            inputs = scalars_from_bytes(inputs32, ninputs);       // INVALID_SCALAR: a host check, the witness is not touched
+            return true;
+        },
+        [&](DeviceWitness &w) { w.set_inputs(inputs); });
 }
 int32_t otti_witness_info(const otti_witness *wit, const void **d_z, size_t *n, double *small_fraction) {
     return guarded([&] {
@@ -287,62 +280,29 @@ int32_t otti_witness_info(const otti_witness *wit, const void **d_z, size_t *n, 
 // ---- kept rows (device.h DeviceWitness::rows_kept).  As with the calls above, the arguments are judged first, a missing device is reported next,
 // and only then is the witness handle looked at (none can exist without a device).
 static int32_t witness_keep_rows(otti_instance *inst, otti_witness *wit, Gens *g) {
-    return guarded([&] {
-        if (!inst || !wit || !g) throw Error(OTTI_ERR_BAD_ARG, "null argument");
-        const size_t V = inst->I->num_vars;
-        if (g->num_vars_padded != V) throw Error(OTTI_ERR_BAD_ARG, "generators were made for a different instance size");
-        DevCtx::get();
-        check_witness_dims(wit, *inst->I);
-        wit->w->keep_rows(*g);
-        return OTTI_OK;
-    });
+    return witness_entry(inst, wit, g != nullptr, false,
+        [&](size_t V) { if (g->num_vars_padded != V) throw Error(OTTI_ERR_BAD_ARG, "generators were made for a different instance size"); return true; },
+        [&](DeviceWitness &w) { w.keep_rows(*g); });
 }
 int32_t otti_witness_keep_rows(otti_instance *inst, otti_witness *wit, otti_gens *gens) { return witness_keep_rows(inst, wit, gens ? gens->g.get() : nullptr); }
 int32_t otti_witness_keep_rows_snark(otti_instance *inst, otti_witness *wit, otti_snark_gens *gens) { return witness_keep_rows(inst, wit, gens ? gens->g->sat.get() : nullptr); }
-int32_t otti_witness_drop_rows(otti_witness *wit) {
-    return guarded([&] {
-        if (!wit) throw Error(OTTI_ERR_BAD_ARG, "null argument");
-        if (otti_device_count() < 1) throw Error(OTTI_ERR_NO_DEVICE, "no device: no witness handle can exist");
-        wit->w->drop_rows();
-        return OTTI_OK;
-    });
-}
+int32_t otti_witness_drop_rows(otti_witness *wit) { return witness_read(wit, [](DeviceWitness &w) { w.drop_rows(); }); }
 int32_t otti_witness_rows_info(const otti_witness *wit, int32_t *kept, size_t *L, size_t *R, uint64_t *rows_resummed) {
-    return guarded([&] {
-        if (!wit) throw Error(OTTI_ERR_BAD_ARG, "null argument");
-        if (otti_device_count() < 1) throw Error(OTTI_ERR_NO_DEVICE, "no device: no witness handle can exist");
-        const DeviceWitness &w = *wit->w;
+    return witness_read(wit, [&](const DeviceWitness &w) {
         if (kept) *kept = w.rows_kept.p ? 1 : 0;
         if (L) *L = w.rows_kept.n;
         if (R) *R = w.rows_R;
         if (rows_resummed) *rows_resummed = w.rows_resummed;
-        return OTTI_OK;
     });
 }
 // ---- kept products (device.h DeviceWitness::prod_abc), in the order of the kept-rows calls: the arguments, a missing device, the witness's dimensions
 int32_t otti_witness_keep_products(otti_instance *inst, otti_witness *wit) {
-    return guarded([&] {
-        if (!inst || !wit) throw Error(OTTI_ERR_BAD_ARG, "null argument");
-        DevCtx::get();
-        check_witness_dims(wit, *inst->I);
-        wit->w->keep_products(*inst->I);
-        return OTTI_OK;
-    });
+    return witness_entry(inst, wit, true, false, [](size_t) { return true; }, [&](DeviceWitness &w) { w.keep_products(*inst->I); });
 }
-int32_t otti_witness_drop_products(otti_witness *wit) {
-    return guarded([&] {
-        if (!wit) throw Error(OTTI_ERR_BAD_ARG, "null argument");
-        if (otti_device_count() < 1) throw Error(OTTI_ERR_NO_DEVICE, "no device: no witness handle can exist");
-        wit->w->drop_products();
-        return OTTI_OK;
-    });
-}
+int32_t otti_witness_drop_products(otti_witness *wit) { return witness_read(wit, [](DeviceWitness &w) { w.drop_products(); }); }
 int32_t otti_witness_products_info(const otti_witness *wit, int32_t *kept, size_t *n_rows, const void **d_Az, const void **d_Bz, const void **d_Cz,
                                    uint64_t *n_unsat, uint64_t *patches, uint64_t *rows_recomputed, uint64_t *full_passes) {
-    return guarded([&] {
-        if (!wit) throw Error(OTTI_ERR_BAD_ARG, "null argument");
-        if (otti_device_count() < 1) throw Error(OTTI_ERR_NO_DEVICE, "no device: no witness handle can exist");
-        const DeviceWitness &w = *wit->w;
+    return witness_read(wit, [&](const DeviceWitness &w) {
         if (kept) *kept = w.prod_inst ? 1 : 0;
         if (n_rows) *n_rows = w.prod_abc[0].n;
         if (d_Az) *d_Az = w.prod_abc[0].p;
@@ -352,7 +312,6 @@ int32_t otti_witness_products_info(const otti_witness *wit, int32_t *kept, size_
         if (patches) *patches = w.prod_patches;
         if (rows_recomputed) *rows_recomputed = w.prod_rows_recomputed;
         if (full_passes) *full_passes = w.prod_full_passes;
-        return OTTI_OK;
     });
 }
 int32_t otti_nizk_prove_resident(otti_instance *inst, otti_witness *wit, otti_gens *gens, const uint8_t *tlabel, size_t tlabel_len,

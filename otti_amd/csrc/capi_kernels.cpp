@@ -99,7 +99,7 @@ int32_t otti_k_multiply_vec(otti_instance *inst, const uint8_t *z, uint8_t *Az, 
         download(c, Az, a.p, I.num_cons); download(c, Bz, b.p, I.num_cons); download(c, Cz, d.p, I.num_cons); c.sync(); return OTTI_OK;
     });
 }
-// DeviceWitness::products_changed on a caller's host state: the same dev_products_patch, so a wrong patch points at a kernel and not at a proof
+// the kept-products step of DeviceWitness::z_written (witness.cpp) on a caller's host state: the same dev_products_patch, so a wrong patch points at a kernel and not at a proof
 int32_t otti_k_products_patch(otti_instance *inst, const uint8_t *h_z_new, const uint64_t *h_cols, size_t ncols, size_t first, size_t count,
                               uint8_t *io_Az, uint8_t *io_Bz, uint8_t *io_Cz, uint64_t *io_bits, uint64_t *io_unsat,
                               uint32_t *h_rows, size_t n_rows_cap, uint64_t *n_touched, int32_t *took_full_pass, float *kernel_ms) {

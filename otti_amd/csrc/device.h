@@ -238,7 +238,7 @@ struct DeviceWitness {
     // points reads them as the addend of its blind launch and skips the MSM_KEEP launch; sharded proofs do not look at them.  Written by
     // keep_rows and update only — both never beside a proof with this witness, so proofs need no lock to read them.
     DevBuf<Pt> rows_kept; const char *rows_stream = nullptr; size_t rows_R = 0;
-    Gens *rows_gens = nullptr;                                // whose table update() re-sums with (the caller keeps it alive while rows are kept)
+    Gens *rows_gens = nullptr;                                // whose table the mutators re-sum and patch with (the caller keeps it alive while rows are kept)
     unsigned long long rows_resummed = 0;                     // rows re-summed by updates since keep_rows
     bool rows_kept_for(const Gens &g) const;                  // kept, and over g's points
     void keep_rows(Gens &g);                                  // builds g's table if need be, sums every row, returns when they are resident; again with the same points: nothing
@@ -246,7 +246,7 @@ struct DeviceWitness {
     // ---- kept products (opt-in): Az, Bz, Cz of this z over ONE instance's matrices (N = padded num_cons canonical Montgomery words each, bit for
     // bit what dev_spmv3 writes), the verdict bitmap dev_sat_pass writes for it and the number of failing rows.  The sums are linear in z: a changed
     // variable j moves only the rows with an entry in column j, which the instance's by-column copy lists, so every mutator brings the state up to
-    // date by recomputing those rows alone (dev_products_patch) once z is written.  An unsharded proof over that instance copies the vectors into its
+    // date by recomputing those rows alone (dev_products_patch, from z_written) once z is written.  An unsharded proof over that instance copies the vectors into its
     // tables instead of forming them (the tables are folded in place: the kept vectors themselves never go to a folding kernel); check_sat answers
     // from count and bitmap.  Written by keep_products, drop_products and the mutators only — never beside a proof or check with this witness, so
     // readers need no lock.  The instance must outlive the kept products.
@@ -257,9 +257,20 @@ struct DeviceWitness {
     bool products_kept_for(const Instance &I) const { return prod_inst == &I && prod_abc[0].p; }
     void keep_products(Instance &I);                          // one full pass now; again for the same instance: nothing
     void drop_products();
-    // z[cols] (d_cols: ascending device list of ncols indices; nullptr: the range [first, first + count)) has been written: bring the products up to date
-    void products_changed(const uint64_t *d_cols, size_t ncols, size_t first, size_t count);
+    static void check_range(size_t V, size_t first, size_t count);   // INVALID_NUM_VARS unless [first, first + count) lies within V variables
 private:
+    // What a mutator wrote into z: the range [first, first + count), or (d_idx given) an ascending device list of n indices — with, when the caller has
+    // them, new - old of each (a patch of kept rows reads them) and a host copy of the list.
+    struct Written {
+        size_t first = 0, count = 0;
+        const uint64_t *d_idx = nullptr; size_t n = 0;
+        const Fr *delta = nullptr; const uint64_t *h_idx = nullptr;
+        bool counted = false;                                 // the list is a count pass's on this context: dev_witness_rows_touched's tally buffer exists
+        bool vars = true;                                     // variables were written; false: inputs alone, which small_fraction and kept rows do not see
+    };
+    struct RowsPlan { enum How { NONE, PATCH, RESUM } how = NONE; size_t r0 = 0, r1 = 0; };   // what becomes of kept rows; r0 .. r1: the rows a RESUM sums again
+    // the one ending of every mutator, and the one failure rule (witness.cpp): small_fraction, kept rows, kept products, counters
+    void z_written(DevCtx &c, const Written &w, RowsPlan rows);
     // the dimension checks, z allocated and zeroed, 1 || inputs queued behind the variables; returns the host copy of that tail, which has to
     // outlive the next synchronise of c.stream
     std::vector<Fr> set_up(DevCtx &c, const Instance &I, size_t nvars);

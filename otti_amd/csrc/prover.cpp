@@ -139,266 +139,6 @@ static const bool g_hook_registered = [] {
 }();
 
 namespace {
-// Where dev_witness_ingest_from reads a source: a device source as it is, once the context's stream waits for the producer's queued work (an event
-// recorded there, as the otti_kd_* calls order a caller's stream against the context's own); a host source from a copy on the device — packed
-// 32-byte words straight in `dst` when the caller names one (they are converted in place there: no staging allocation), anything else in a
-// staging copy of its span.
-struct WitSource {
-    DevBuf<uint8_t> staged; const void *p = nullptr; size_t stride = 0;
-    WitSource(DevCtx &c, int format, const void *src, size_t n, size_t stride_, bool on_device, hipStream_t producer, Fr *dst) {
-        const size_t eb = wit_elem_bytes(format);
-        stride = stride_ ? stride_ : eb; p = src;
-        if (!n) return;
-        if (on_device) {
-            if (producer && producer != c.stream) {
-                if (!c.ev_order) OTTI_HIP(hipEventCreateWithFlags(&c.ev_order, hipEventDisableTiming));
-                OTTI_HIP(hipEventRecord(c.ev_order, producer)); OTTI_HIP(hipStreamWaitEvent(c.stream, c.ev_order, 0));
-            }
-            return;
-        }
-        const size_t span = (n - 1) * stride + eb;
-        if (dst && eb == sizeof(Fr) && stride == eb) p = dst;
-        else { staged.alloc(span); p = staged.p; }
-        OTTI_HIP(hipMemcpyAsync(const_cast<void *>(p), src, span, hipMemcpyHostToDevice, c.stream));
-    }
-};
-}  // namespace
-
-std::vector<Fr> DeviceWitness::set_up(DevCtx &c, const Instance &I, size_t nvars) {
-    const size_t V = I.num_vars;
-    if (nvars > V) throw Error(OTTI_ERR_INVALID_NUM_VARS, "more variables than the instance has");
-    if (inputs.size() != I.num_inputs) throw Error(OTTI_ERR_INVALID_NUM_INPUTS, "wrong number of inputs");
-    z.alloc(2 * V);
-    OTTI_HIP(hipMemsetAsync(z.p, 0, 2 * V * sizeof(Fr), c.stream));
-    // z = vars || 1 || inputs || 0...   (r1csproof.rs: "append input to variables to create a single vector z")
-    std::vector<Fr> tail(1 + inputs.size()); tail[0] = fr_one();
-    for (size_t i = 0; i < inputs.size(); i++) tail[1 + i] = inputs[i];
-    OTTI_HIP(hipMemcpyAsync(z.p + V, tail.data(), tail.size() * sizeof(Fr), hipMemcpyHostToDevice, c.stream));
-    return tail;
-}
-
-DeviceWitness::DeviceWitness(const Instance &I, int format, const void *src, size_t nvars, size_t stride, bool src_on_device, hipStream_t producer,
-                             const std::vector<Fr> &inputs_) : inputs(inputs_) {
-    DevCtx &c = DevCtx::get();
-    const size_t V = I.num_vars;
-    const std::vector<Fr> tail = set_up(c, I, nvars);
-    WitSource s(c, format, src, nvars, stride, src_on_device, producer, z.p);    // a fresh z may be written before the check: a refusal throws it away
-    size_t n_small = 0;
-    const size_t bad = dev_witness_ingest_from(c, format, s.p, s.stride, nvars, z.p, 0, &n_small);   // synchronises: `tail`, the staging copy and the caller's buffer are free again
-    if (!nvars) OTTI_HIP(hipStreamSynchronize(c.stream));
-    if (bad) throw Error(OTTI_ERR_INVALID_SCALAR, "non-canonical scalar in assignment");
-    small_fraction = V ? (double)(n_small + (V - nvars)) / (double)V : 0.0;        // the padding zeros count as small
-}
-
-static void resum_rows(DevCtx &c, DeviceWitness &w, size_t r0, size_t r1);
-void DeviceWitness::update(size_t first, int format, const void *src, size_t count, size_t stride, bool src_on_device, hipStream_t producer) {
-    DevCtx &c = DevCtx::get();
-    const size_t V = z.n / 2;
-    if (first > V || count > V - first) throw Error(OTTI_ERR_INVALID_NUM_VARS, "the range ends beyond the instance's variables");
-    if (!count) return;
-    // every integer is a scalar: straight into place.  A 32-byte range is converted in `conv` (a packed host one is copied there and converted
-    // in place), and z is written only once the whole range has passed the check
-    const bool ints = format == WIT_I64 || format == WIT_U64;
-    DevBuf<Fr> conv(ints ? 0 : count);                            // outlives the copy out of it: freed after dev_small_fraction has synchronised
-    WitSource s(c, format, src, count, stride, src_on_device, producer, conv.p);
-    if (ints) dev_witness_ingest_from(c, format, s.p, s.stride, count, z.p, first);
-    else {
-        if (dev_witness_ingest_from(c, format, s.p, s.stride, count, conv.p, 0)) throw Error(OTTI_ERR_INVALID_SCALAR, "non-canonical scalar in the update: the witness is unchanged");
-        OTTI_HIP(hipMemcpyAsync(z.p + first, conv.p, count * sizeof(Fr), hipMemcpyDeviceToDevice, c.stream));
-    }
-    small_fraction = dev_small_fraction(c, z.p, V);               // one recount over the variables (padding zeros count as small); synchronises
-    // kept rows: z has changed (a refused scalar threw above, with z and the kept rows as they were), so the rows the range touches are summed again
-    if (rows_kept.p) resum_rows(c, *this, first / rows_R, (first + count - 1) / rows_R);
-    if (prod_inst) products_changed(nullptr, 0, first, count);
-}
-
-// ---- kept rows.  Rows [r0, r1] of z summed over g's table into their slots of rows_kept, by the launch the proof's own commitment would make for
-// them: up to two rows the latency-bound kernel (as every launch of at most two rows), a longer run one chip-filling launch with the proof's
-// sparse rule.  Returns once they are resident: the next proof may run on another thread's stream.
-static void sum_rows_into(DevCtx &c, DeviceWitness &w, Gens &g, size_t r0, size_t r1, bool whole) {
-    ensure_gens_device(g);
-    const DeviceGens &DG = *g.dev;
-    const size_t R = w.rows_R, n = r1 - r0 + 1;
-    // the whole vector goes the way the proof's MSM_KEEP launch goes (same size rule); a run of dirty rows is bulk from three rows on
-    dev_msm_rows(c, DG, {.dense = w.z.p + r0 * R, .n_dense = R, .rows = n, .mode = MSM_KEEP, .sparse = w.small_fraction > kSparseWitness,
-                         .keep_dst = w.rows_kept.p + r0, .force_bulk = !whole && n > 2});
-    OTTI_HIP(hipStreamSynchronize(c.stream));
-}
-static void resum_rows(DevCtx &c, DeviceWitness &w, size_t r0, size_t r1) {
-    // a failure here (the table has to be rebuilt and HBM is short) leaves rows that no longer belong to z: the witness goes back to having none
-    try { sum_rows_into(c, w, *w.rows_gens, r0, r1, false); } catch (...) { w.drop_rows(); throw; }
-    w.rows_resummed += r1 - r0 + 1;
-}
-// ---- scatter update.  Behind the same staging and producer-stream ordering as update (host indices are staged like host values), three launches:
-// the check (everything converted into `conv`, bad indices and scalars counted: one synchronise, and a refusal has written nothing), the apply
-// (z, and the deltas when rows are kept), and the patch of the kept rows (k_msm.hip k_msm_scatter: count * W table look-ups).
-void DeviceWitness::scatter(const uint64_t *idx, int format, const void *src, size_t count, size_t stride, bool on_device, hipStream_t producer) {
-    DevCtx &c = DevCtx::get();
-    const size_t V = z.n / 2;
-    if (count > V) throw Error(OTTI_ERR_INVALID_INDEX, "more indices than the instance has variables");
-    if (!count) return;
-    DevBuf<Fr> conv(count), delta;                                // outlive the launches that read them: freed after dev_small_fraction has synchronised
-    WitSource s(c, format, src, count, stride, on_device, producer, conv.p);   // a device source: the one event orders the producer of both lists
-    DevBuf<uint64_t> idx_staged; const uint64_t *d_idx = idx;
-    if (!on_device) {
-        idx_staged.alloc(count); d_idx = idx_staged.p;
-        OTTI_HIP(hipMemcpyAsync(idx_staged.p, idx, count * sizeof(uint64_t), hipMemcpyHostToDevice, c.stream));
-    }
-    const bool patch = rows_kept.p != nullptr;
-    if (patch) delta.alloc(count);
-    size_t bad_scalars = 0, bad_indices = 0;
-    dev_witness_scatter_check(c, format, s.p, s.stride, d_idx, count, V, conv.p, &bad_scalars, &bad_indices);
-    if (bad_indices) throw Error(OTTI_ERR_INVALID_INDEX, "the indices are not strictly ascending below the padded num_vars: the witness is unchanged");
-    if (bad_scalars) throw Error(OTTI_ERR_INVALID_SCALAR, "non-canonical scalar in the scatter: the witness is unchanged");
-    dev_witness_scatter_apply(c, d_idx, conv.p, count, V, z.p, patch ? delta.p : nullptr);
-    std::vector<uint64_t> h_idx;                                  // a device list, read back for the count of rows it touches
-    if (patch) {
-        // z has changed: a patch that cannot run (the table has to be rebuilt and HBM is short) leaves rows that no longer belong to it, as in resum_rows
-        try {
-            ensure_gens_device(*rows_gens);
-            dev_msm_scatter(c, *rows_gens->dev, d_idx, delta.p, count, rows_R, rows_kept.p, rows_kept.n);
-            if (on_device) { h_idx.resize(count); OTTI_HIP(hipMemcpyAsync(h_idx.data(), d_idx, count * sizeof(uint64_t), hipMemcpyDeviceToHost, c.stream)); }
-        } catch (...) { (void)hipStreamSynchronize(c.stream); drop_rows(); throw; }
-    }
-    small_fraction = dev_small_fraction(c, z.p, V);               // counted again as update does, never incrementally; synchronises
-    scatter_calls++;
-    if (prod_inst) products_changed(d_idx, count, 0, 0);          // the list has passed the check above; idx_staged and the caller's list are still alive
-    if (patch) {
-        const uint64_t *ix = on_device ? h_idx.data() : idx;
-        unsigned long long rows = 0;
-        for (size_t i = 0; i < count; i++) rows += i == 0 || ix[i] / rows_R != ix[i - 1] / rows_R;
-        rows_patched += rows; terms_patched += count;
-    }
-}
-// ---- assign: a whole new vector of which most elements have not moved.  Behind the same staging and producer-stream ordering as update (a host
-// source is staged as it is, never converted into a copy: both passes convert on the fly): the count pass (changed elements per chunk, scalars >= l;
-// and the first and last changed element; one synchronise, and a refusal or "nothing changed" ends here with nothing written), the apply pass (z, and
-// for a patch the ascending list of changed indices and their deltas), the kept rows brought up to date — patched by the list as scatter patches them,
-// or, from kAssignResumShare of the touched rows' elements on, rows idx_min / R .. idx_max / R summed again as update sums them — and the recount
-// of small_fraction.
-// The share of touched_rows * R changed elements from which summing the touched rows again replaces the patch (a value >= 1: never).  Measured,
-// profiles/witness_assign.md (tools/witness_assign_probe.py, 2^20, kept rows): the smallest probed share at which a round trip with the patch forced
-// was no longer shorter than one with the re-sum of the same range forced, on the same witness, was 1/2 (at 1/8 the patch still won clearly), for small
-// int64 numbers and for uniform canonical bytes alike.
-constexpr double kAssignResumShare = 0.5;
-// OTTI_ASSIGN_RESUM_SHARE, read per call, overrides it: 0 sums again whenever anything changed, a value >= 1 never does (tests pin both paths with it)
-static double assign_resum_share() {
-    if (const char *e = getenv("OTTI_ASSIGN_RESUM_SHARE")) { char *end = nullptr; const double v = strtod(e, &end); if (end != e && v >= 0) return v; }
-    return kAssignResumShare;
-}
-size_t DeviceWitness::assign(size_t first, int format, const void *src, size_t count, size_t stride, bool src_on_device, hipStream_t producer) {
-    DevCtx &c = DevCtx::get();
-    const size_t V = z.n / 2;
-    if (first > V || count > V - first) throw Error(OTTI_ERR_INVALID_NUM_VARS, "the range ends beyond the instance's variables");
-    if (!count) return 0;
-    WitSource s(c, format, src, count, stride, src_on_device, producer, nullptr);
-    const WitDiff d = dev_witness_diff_count(c, format, s.p, s.stride, count, z.p + first);
-    if (d.bad_scalars) throw Error(OTTI_ERR_INVALID_SCALAR, "non-canonical scalar in the assignment: the witness is unchanged");
-    assign_calls++;
-    const size_t n_changed = d.n_changed;
-    if (!n_changed) return 0;
-    assign_changed += n_changed;
-    // kept rows: patched, or rows r0 .. r1 summed again — known before anything is written, so only a patch pays for the list and the deltas
-    const size_t r0 = rows_kept.p ? (first + d.lo) / rows_R : 0, r1 = rows_kept.p ? (first + d.hi) / rows_R : 0;
-    const double share = assign_resum_share();
-    const bool patch = rows_kept.p && !(share < 1.0 && (double)n_changed >= share * (double)((r1 - r0 + 1) * rows_R));
-    DevBuf<uint64_t> idx; DevBuf<Fr> delta;                       // outlive the launches that read them: freed after dev_small_fraction has synchronised
-    if (patch) { idx.alloc(n_changed); delta.alloc(n_changed); }
-    else if (prod_inst) idx.alloc(n_changed);                     // kept products are patched by the list of changed columns, whatever becomes of kept rows
-    dev_witness_diff_apply(c, format, s.p, s.stride, count, z.p + first, first, n_changed, idx.p, delta.p, true);
-    uint64_t rows = 0;
-    if (patch) {
-        // z has changed: a patch that cannot run (the table has to be rebuilt and HBM is short) leaves rows that no longer belong to it, as in resum_rows
-        try {
-            ensure_gens_device(*rows_gens);
-            dev_msm_scatter(c, *rows_gens->dev, idx.p, delta.p, n_changed, rows_R, rows_kept.p, rows_kept.n);
-            dev_witness_rows_touched(c, idx.p, n_changed, rows_R, &rows);
-        } catch (...) { (void)hipStreamSynchronize(c.stream); drop_rows(); throw; }
-    }
-    // counted again as update and scatter do; synchronises: the patch is done, `rows` is filled.  A throw on the way must not leave the copy into
-    // `rows`, or the launches that read idx and delta, pending behind this frame
-    try { small_fraction = dev_small_fraction(c, z.p, V); } catch (...) { (void)hipStreamSynchronize(c.stream); throw; }
-    if (patch) { rows_patched += rows; terms_patched += n_changed; }
-    else if (rows_kept.p) { resum_rows(c, *this, r0, r1); assign_resums++; }   // behind the recount, as in update: the launch picks its variant by the new share
-    if (prod_inst) products_changed(idx.p, n_changed, 0, 0);
-    return n_changed;
-}
-size_t DeviceWitness::diff(size_t first, int format, const void *src, size_t count, size_t stride, bool src_on_device, hipStream_t producer, uint64_t *idx_out,
-                           size_t cap) const {
-    DevCtx &c = DevCtx::get();
-    const size_t V = z.n / 2;
-    if (first > V || count > V - first) throw Error(OTTI_ERR_INVALID_NUM_VARS, "the range ends beyond the instance's variables");
-    if (!count) return 0;
-    WitSource s(c, format, src, count, stride, src_on_device, producer, nullptr);
-    const WitDiff d = dev_witness_diff_count(c, format, s.p, s.stride, count, z.p + first);
-    if (d.bad_scalars) throw Error(OTTI_ERR_INVALID_SCALAR, "non-canonical scalar in the assignment");
-    const size_t n_changed = d.n_changed, k = std::min(n_changed, cap);
-    if (k) {
-        DevBuf<uint64_t> idx(k);
-        dev_witness_diff_apply(c, format, s.p, s.stride, count, z.p + first, first, k, idx.p, nullptr, false);
-        OTTI_HIP(hipMemcpyAsync(idx_out, idx.p, k * sizeof(uint64_t), hipMemcpyDeviceToHost, c.stream));
-        OTTI_HIP(hipStreamSynchronize(c.stream));
-    }
-    return n_changed;
-}
-void DeviceWitness::set_inputs(const std::vector<Fr> &new_inputs) {
-    DevCtx &c = DevCtx::get();
-    if (new_inputs.size() != inputs.size()) throw Error(OTTI_ERR_INVALID_NUM_INPUTS, "wrong number of inputs");
-    const size_t V = z.n / 2;
-    if (!new_inputs.empty()) {
-        OTTI_HIP(hipMemcpyAsync(z.p + V + 1, new_inputs.data(), new_inputs.size() * sizeof(Fr), hipMemcpyHostToDevice, c.stream));
-        OTTI_HIP(hipStreamSynchronize(c.stream));
-    }
-    inputs = new_inputs;
-    if (prod_inst && !new_inputs.empty()) products_changed(nullptr, 0, V + 1, new_inputs.size());   // inputs are columns of z too
-}
-// ---- kept products (device.h).  keep: the full pass, once; every mutator above calls products_changed once z holds the new values.
-void DeviceWitness::keep_products(Instance &I) {
-    DevCtx &c = DevCtx::get();
-    if (I.num_vars * 2 != z.n) throw Error(OTTI_ERR_INVALID_NUM_VARS, "the witness was uploaded for an instance of other dimensions");
-    if (products_kept_for(I)) return;
-    ensure_instance_device(I);
-    drop_products();
-    const size_t N = I.num_cons;
-    try {
-        for (int k = 0; k < 3; k++) prod_abc[k].alloc(N);
-        prod_bits.alloc((N + 63) >> 6); prod_unsat_dev.alloc(1);
-        prod_inst = &I;
-        dev_products_full(c, *I.dev, z.p, prod_abc[0].p, prod_abc[1].p, prod_abc[2].p, prod_bits.p, prod_unsat_dev.p);
-        unsigned long long n = 0;
-        OTTI_HIP(hipMemcpyAsync(&n, prod_unsat_dev.p, sizeof n, hipMemcpyDeviceToHost, c.stream));
-        OTTI_HIP(hipStreamSynchronize(c.stream));
-        prod_unsat = n; prod_full_passes = 1;
-    } catch (...) { (void)hipStreamSynchronize(c.stream); drop_products(); throw; }
-}
-void DeviceWitness::drop_products() {
-    for (int k = 0; k < 3; k++) prod_abc[k].release();
-    prod_bits.release(); prod_unsat_dev.release();
-    prod_inst = nullptr; prod_unsat = 0; prod_patches = prod_rows_recomputed = prod_full_passes = 0;
-}
-void DeviceWitness::products_changed(const uint64_t *d_cols, size_t ncols, size_t first, size_t count) {
-    DevCtx &c = DevCtx::get();
-    // z has changed: products that cannot be brought up to date no longer belong to it, so the witness goes back to having none (as resum_rows does)
-    try {
-        const ProductsPatch p = dev_products_patch(c, *prod_inst->dev, z.p, d_cols, ncols, first, count, prod_abc[0].p, prod_abc[1].p, prod_abc[2].p, prod_bits.p, prod_unsat_dev.p);
-        prod_unsat = p.n_unsat;
-        if (p.full) prod_full_passes++;
-        else if (p.n_touched) { prod_patches++; prod_rows_recomputed += p.n_touched; }
-    } catch (...) { (void)hipStreamSynchronize(c.stream); drop_products(); throw; }
-}
-bool DeviceWitness::rows_kept_for(const Gens &g) const { return rows_kept.p && rows_R == g.R && rows_stream && !strcmp(rows_stream, g.stream); }
-void DeviceWitness::keep_rows(Gens &g) {
-    DevCtx &c = DevCtx::get();
-    const size_t V = z.n / 2;
-    if (g.num_vars_padded != V || !g.R || V % g.R) throw Error(OTTI_ERR_BAD_ARG, "generators were made for a different instance size");
-    if (rows_kept_for(g)) { rows_gens = &g; return; }
-    drop_rows();
-    rows_kept.alloc(V / g.R); rows_stream = g.stream; rows_R = g.R; rows_gens = &g; rows_resummed = 0;
-    try { sum_rows_into(c, *this, g, 0, V / g.R - 1, true); } catch (...) { drop_rows(); throw; }
-}
-void DeviceWitness::drop_rows() { rows_kept.release(); rows_stream = nullptr; rows_R = 0; rows_gens = nullptr; rows_resummed = 0; }
-
-namespace {
 // Everything the rounds of BOTH sum-checks need that depends on the random tape alone, as ONE batched fixed-base MSM: for each round
 // the four points delta_j = commit(d_vec_j, r_delta_j), blinds_poly[j]*h_n, blinds_evals[j]*h_1, r_beta_j*h_1 (extended, not
 // compressed).  Launched right behind the witness commitment (the second sum-check's tape values are read ahead with a

@@ -1,5 +1,5 @@
 """What assigning a whole new vector to a resident witness with kept rows costs, by the share of it that changed (profiles/witness_assign.md), and
-from which share on summing the touched rows again is no slower than patching them: the figure behind kAssignResumShare (prover.cpp).
+from which share on summing the touched rows again is no slower than patching them: the figure behind kAssignResumShare (witness.cpp).
 For a size of `--lg`, for an int64 (small numbers) and a canonical-bytes (uniform in GF(l)) device source, in ONE process with one instance and one
 generator table: two vectors in HBM that differ in k uniformly placed elements (other values of the same distribution), k = 0, 2^-16, 2^-10, 2^-6, 2^-3,
 1/2 and 1 of the variables, assigned in turn, alternating inside one loop:
