@@ -378,6 +378,40 @@ int32_t otti_zkif_load_inputs(const char *inputs_path, otti_r1cs **out);
 /* writes the three-file split the reference compiler produces [REF run.py:47-49] from an R1CS in z-order [vars | 1 | inputs] */
 int32_t otti_zkif_write(const otti_r1cs *r, const char *circuit_path, const char *inputs_path, const char *witness_path);
 void    otti_r1cs_free(otti_r1cs *r);
+/* zkInterface files to a ready instance in one call.  *assignment: an otti_r1cs with the dimensions, nA / nB / nC, vars32 and inputs32 filled and
+ * A = B = C = NULL (otti_r1cs_free accepts that); without a witness file nvars = 0, as otti_zkif_load leaves it.
+ *   OTTI_INGEST_HOST:   otti_zkif_load + otti_instance_new.  Needs no device (a verifier process without a GPU).
+ *   OTTI_INGEST_DEVICE: the ConstraintSystem messages are staged through pinned buffers to HBM as they are in the file; kernels walk the FlatBuffers
+ *                       tables there, map variable ids to columns, validate and convert the coefficients and write the entry lists in file order,
+ *                       from which both CSR copies are built as for any instance.  Headers, Witness, Command and unknown messages, the .inp.zkif
+ *                       and the .wit.zkif stay on the host.  The instance comes back with its device copy made and WITHOUT host lists: the first
+ *                       host consumer (otti_instance_is_sat, a verifier without a device evaluation, SNARK encode, a sharded upload,
+ *                       otti_instance_entries) downloads them from the device, once, whichever thread asks.  For that the entry lists stay in HBM
+ *                       beside the CSR copies for the life of the instance: 40 bytes per entry (otti_instance_ingest_info: hbm_entry_bytes).
+ *                       Without a device: OTTI_ERR_NO_DEVICE.  Its own limits, all OTTI_ERR_BAD_ARG: a circuit file of 16 GiB and more or more
+ *                       than 2^30 constraints (said before the file is parsed, so before any defect of it: the host path says "too large"
+ *                       only behind a clean parse), and a matrix of 2^32 entries and more (offsets in a file may alias, so a few MB can hold
+ *                       that many; said behind a malformed table and before any entry is looked at; the host path has no such limit).
+ *   OTTI_INGEST_AUTO:   the device when its runtime is already up in this process (the call never brings one up) and the circuit file's size lies
+ *                       between a cut-over and a budget: OTTI_INGEST_MIN_MB (MiB; default 15: the smallest size probed, profiles/zkif_ingest.md)
+ *                       and OTTI_INGEST_GB (GiB; default 8; 0: never), both read per call.  Otherwise the host.
+ * Both paths make the same instance — the same entries in the same order (a SNARK computation commitment depends on it), the same variants in
+ * otti_instance_device_info — and report the same error for the same files: a parse error first, the first in file order (OTTI_ERR_IO, an undeclared
+ * variable id OTTI_ERR_INVALID_INDEX, a coefficient wider than 32 bytes OTTI_ERR_INVALID_SCALAR), then whatever the
+ * inputs and witness files are refused for, then a coefficient >= l (OTTI_ERR_INVALID_SCALAR).
+ * Before any device is touched: a null circuit_path, inputs_path, inst or assignment, or an unknown mode, is OTTI_ERR_BAD_ARG; a file that cannot
+ * be read OTTI_ERR_IO.  On any error *inst and *assignment are untouched, and after a device-side refusal the context stays usable. */
+enum { OTTI_INGEST_AUTO = 0, OTTI_INGEST_HOST = 1, OTTI_INGEST_DEVICE = 2 };
+int32_t otti_instance_from_zkif(const char *circuit_path, const char *inputs_path, const char *witness_path /* may be NULL */,
+                                int32_t mode, otti_instance **inst, otti_r1cs **assignment);
+/* the entries of A (which = 0), B (1) or C (2) as the caller passed them to otti_instance_new, or as otti_zkif_load gives them for the files an
+ * instance was ingested from: unpadded columns, canonical values, the same order.  *count (optional) receives their number; out (optional: NULL
+ * asks for the count alone, which downloads nothing) needs room for cap >= that many, else OTTI_ERR_BAD_ARG.  Works for every instance. */
+int32_t otti_instance_entries(otti_instance *inst, int32_t which /* 0 A, 1 B, 2 C */, otti_entry *out, size_t cap, size_t *count);
+/* how an instance came to be: on_device = 1 for a device ingest; the circuit file's size (0 for otti_instance_new); the HBM its kept entry lists
+ * take (0 unless on_device); and a device ingest's four laps in ms: host walk + id map, staging + copies, kernels, CSR build.  Any pointer may be NULL. */
+int32_t otti_instance_ingest_info(const otti_instance *inst, int32_t *on_device, uint64_t *circuit_bytes, uint64_t *hbm_entry_bytes,
+                                  double ms[4] /* host walk + id map, staging + copies, kernels, CSR build */);
 /* synthetic satisfiable R1CS: num_cons = num_vars = n, one non-zero per row per matrix */
 int32_t otti_synth_r1cs(uint64_t n, uint64_t num_inputs, uint64_t seed, otti_r1cs **out);
 /* second distribution of SURVEY 8d ("compiler-like"): 90 % of the witness < 2^64, 1..8 non-zeros per row, small signed coefficients,

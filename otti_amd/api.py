@@ -156,6 +156,10 @@ _sig("otti_k_multiply_vec", _i32, _vp, _vp, _vp, _vp, _vp, _fp)
 _sig("otti_k_eval_table_sparse", _i32, _vp, _vp, _vp, _vp, _fp)
 _sig("otti_k_products_patch", _i32, _vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, ctypes.POINTER(_u64), _vp, _sz, ctypes.POINTER(_u64), ctypes.POINTER(_i32), _fp)
 _sig("otti_instance_device_info", _i32, _vp, _i32, ctypes.POINTER(_DeviceInfo))
+_sig("otti_instance_from_zkif", _i32, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, _i32, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.POINTER(_R1CS)))
+_sig("otti_instance_entries", _i32, _vp, _i32, _vp, _sz, ctypes.POINTER(_sz))
+_sig("otti_instance_ingest_info", _i32, _vp, ctypes.POINTER(_i32), ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(ctypes.c_double))
+INGEST_MODES = {"auto": 0, "host": 1, "device": 2}             # OTTI_INGEST_*
 _sig("otti_k_eq_evals", _i32, _vp, _sz, _vp, _fp)
 _sig("otti_k_fold_top", _i32, _vp, _sz, _vp, _vp, _fp)
 _sig("otti_k_fold_bot", _i32, _vp, _sz, _vp, _vp, _fp)
@@ -303,6 +307,33 @@ class Instance:
         _check(lib.otti_instance_new(num_cons, num_vars, num_inputs, _ptr(ents[0]), ents[0].size, _ptr(ents[1]), ents[1].size,
                                      _ptr(ents[2]), ents[2].size, ctypes.byref(h)))
         return cls(h, ents)
+
+    @classmethod
+    def from_zkif(cls, circuit, inputs, witness=None, mode="auto"):
+        """otti_instance_from_zkif: the files to a ready instance in one call.  mode "host" is zkif_load + Instance.new; "device" parses the
+        constraints on the GPU (the host lists exist only once something asks for them); "auto" takes the device when its runtime is up and the
+        file's size allows.  Returns (Instance, assignment): the dict zkif_load returns, with A = B = C = None and their counts in nA, nB, nC."""
+        enc = lambda s: None if s is None else os.fsencode(s)
+        h, rp = _vp(), ctypes.POINTER(_R1CS)()
+        _check(lib.otti_instance_from_zkif(enc(circuit), enc(inputs), enc(witness), INGEST_MODES[mode], ctypes.byref(h), ctypes.byref(rp)))
+        counts = dict(nA=rp.contents.nA, nB=rp.contents.nB, nC=rp.contents.nC)
+        assignment = _r1cs_to_py(rp)
+        assignment.update(A=None, B=None, C=None, **counts)
+        return cls(h, None), assignment
+
+    def entries(self, which):
+        """otti_instance_entries: the entries of A (0), B (1) or C (2) as the caller's — unpadded columns, canonical values, caller / file order"""
+        n = _sz()
+        _check(lib.otti_instance_entries(self._h, which, None, 0, ctypes.byref(n)))
+        a = np.zeros(n.value, dtype=ENTRY_DTYPE)
+        _check(lib.otti_instance_entries(self._h, which, _ptr(a) if n.value else None, n.value, ctypes.byref(n)))
+        return a
+
+    def ingest_info(self):
+        """otti_instance_ingest_info: dict of on_device, circuit_bytes, hbm_entry_bytes and ms (host walk + id map, staging + copies, kernels, CSR build)"""
+        on, cb, hb, ms = _i32(), _u64(), _u64(), (ctypes.c_double * 4)()
+        _check(lib.otti_instance_ingest_info(self._h, ctypes.byref(on), ctypes.byref(cb), ctypes.byref(hb), ms))
+        return dict(on_device=bool(on.value), circuit_bytes=cb.value, hbm_entry_bytes=hb.value, ms=tuple(ms))
 
     @property
     def dims(self):
@@ -912,7 +943,7 @@ def _r1cs_to_py(rp):
     r = rp.contents
 
     def ents(p, n):
-        if not n:
+        if not n or not p:                                     # (an assignment of otti_instance_from_zkif carries counts without lists)
             return np.zeros(0, dtype=ENTRY_DTYPE)
         a = np.empty(n, dtype=ENTRY_DTYPE)                     # one memcpy (np.ctypeslib.as_array builds a ctypes array type per shape: seconds at 2^22)
         ctypes.memmove(a.ctypes.data, ctypes.cast(p, _vp), n * ENTRY_DTYPE.itemsize)

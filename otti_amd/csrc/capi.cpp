@@ -6,6 +6,13 @@ otti_r1cs *otti_r1cs_from(size_t nc, size_t nv, size_t ni, const std::vector<ott
 otti_r1cs *zkif_load_impl(const char *circuit_path, const char *inputs_path, const char *witness_path);
 void zkif_write_impl(const otti_r1cs *r, const char *circuit_path, const char *inputs_path, const char *witness_path);
 otti_r1cs *zkif_load_inputs_impl(const char *inputs_path);
+namespace otti { otti_r1cs *instance_from_zkif_device(const char *circuit_path, const char *inputs_path, const char *witness_path, std::unique_ptr<Instance> &inst); }   // k_ingest.hip
+#include <sys/stat.h>
+#include <unistd.h>
+// otti_instance_from_zkif(OTTI_INGEST_AUTO): the circuit sizes between which the device path is taken (OTTI_INGEST_MIN_MB, OTTI_INGEST_GB override them
+// per call; OTTI_INGEST_GB=0: never).  Where they come from: profiles/zkif_ingest.md.
+constexpr double kIngestMinMB = 15.0;                       // MiB: the smallest probed circuit (2^16 uniform, 15.2 MiB) — the device path's median beat the host path's beyond both spreads at every probed size
+constexpr double kIngestGB = 8.0;                            // image + 40-byte entries + both CSR copies of such a file stay far below one card's HBM
 
 thread_local std::string g_last_error;
 // VarsAssignment::new + pad, InputsAssignment::new
@@ -513,6 +520,75 @@ int32_t otti_zkif_write(const otti_r1cs *r, const char *c, const char *i, const 
     return guarded([&] { if (!r || !c || !i || !w) throw Error(OTTI_ERR_BAD_ARG, "null argument"); zkif_write_impl(r, c, i, w); return OTTI_OK; });
 }
 void otti_r1cs_free(otti_r1cs *r) { if (!r) return; free(r->A); free(r->B); free(r->C); free(r->vars32); free(r->inputs32); free(r); }
+
+// ---- zkInterface files to a ready instance (zkif.h, k_ingest.hip).  Everything the arguments and the files' readability say is said before a
+// device is asked for; the outputs are written last, so any error leaves them as they were.
+int32_t otti_instance_from_zkif(const char *circuit_path, const char *inputs_path, const char *witness_path, int32_t mode, otti_instance **inst,
+                                otti_r1cs **assignment) {
+    return guarded([&] {
+        if (!circuit_path || !inputs_path || !inst || !assignment) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (mode != OTTI_INGEST_AUTO && mode != OTTI_INGEST_HOST && mode != OTTI_INGEST_DEVICE) throw Error(OTTI_ERR_BAD_ARG, "unknown ingest mode");
+        uint64_t circuit_bytes = 0;
+        for (const char *path : {circuit_path, inputs_path, witness_path}) {
+            if (!path) continue;
+            struct stat st;
+            if (access(path, R_OK) != 0 || stat(path, &st) != 0 || !S_ISREG(st.st_mode)) throw Error(OTTI_ERR_IO, std::string("cannot read ") + path);
+            if (path == circuit_path) circuit_bytes = (uint64_t)st.st_size;
+        }
+        bool on_device = mode == OTTI_INGEST_DEVICE;
+        if (on_device && otti_device_count() < 1) throw Error(OTTI_ERR_NO_DEVICE, "OTTI_INGEST_DEVICE without a device");
+        if (mode == OTTI_INGEST_AUTO) {
+            // the device, when its runtime is up in this process already (asking brings nothing up) and the file lies between the cut-over and the budget
+            double min_mb = kIngestMinMB, max_gb = kIngestGB;
+            if (const char *e = getenv("OTTI_INGEST_MIN_MB")) min_mb = atof(e);
+            if (const char *e = getenv("OTTI_INGEST_GB")) max_gb = atof(e);
+            const double bytes = (double)circuit_bytes;
+            on_device = max_gb > 0 && device_runtime_up() && bytes >= min_mb * 1048576.0 && bytes <= max_gb * 1073741824.0;
+        }
+        std::unique_ptr<Instance> I; otti_r1cs *r = nullptr;
+        if (on_device) r = instance_from_zkif_device(circuit_path, inputs_path, witness_path, I);
+        else {
+            r = zkif_load_impl(circuit_path, inputs_path, witness_path);
+            struct Guard { otti_r1cs *r; ~Guard() { if (r) otti_r1cs_free(r); } } guard{r};
+            I = instance_new(r->num_cons, r->num_vars, r->num_inputs, r->A, r->nA, r->B, r->nB, r->C, r->nC);
+            free(r->A); free(r->B); free(r->C); r->A = r->B = r->C = nullptr;        // the counts stay
+            I->circuit_bytes = circuit_bytes;
+            guard.r = nullptr;
+        }
+        *inst = new otti_instance{std::move(I)}; *assignment = r;
+        return OTTI_OK;
+    });
+}
+int32_t otti_instance_entries(otti_instance *inst, int32_t which, otti_entry *out, size_t cap, size_t *count) {
+    return guarded([&] {
+        if (!inst || which < 0 || which > 2 || (!out && !count)) throw Error(OTTI_ERR_BAD_ARG, "null argument, or a matrix other than 0 (A), 1 (B), 2 (C)");
+        const Instance &I = *inst->I;
+        if (count) *count = I.nnz[which];
+        if (!out) return OTTI_OK;
+        if (cap < I.nnz[which]) throw Error(OTTI_ERR_BAD_ARG, "room for fewer entries than the matrix has");
+        const SparseMat &m = I.mat(which);                     // (a device-made instance downloads its lists here, once)
+        const size_t shift = I.num_vars - I.given_vars;
+        for (size_t i = 0; i < m.val.size(); i++) {
+            out[i].row = m.row[i]; out[i].col = m.col[i] >= I.num_vars ? m.col[i] - shift : m.col[i];
+            fr_to_bytes(out[i].val, m.val[i]);
+        }
+        return OTTI_OK;
+    });
+}
+int32_t otti_instance_ingest_info(const otti_instance *inst, int32_t *on_device, uint64_t *circuit_bytes, uint64_t *hbm_entry_bytes, double ms[4]) {
+    return guarded([&] {
+        if (!inst) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        const Instance &I = *inst->I;
+        if (on_device) *on_device = I.ingested_on_device ? 1 : 0;
+        if (circuit_bytes) *circuit_bytes = I.circuit_bytes;
+        if (hbm_entry_bytes) {
+            *hbm_entry_bytes = 0;
+            if (I.ingested_on_device && I.dev) for (int k = 0; k < 3; k++) *hbm_entry_bytes += (uint64_t)I.dev->ent[k].n * 40;
+        }
+        if (ms) for (int k = 0; k < 4; k++) ms[k] = I.ingest_ms[k];
+        return OTTI_OK;
+    });
+}
 static int32_t synth_entry(decltype(synth_r1cs) *synth, uint64_t n, uint64_t min_n, uint64_t ni, uint64_t seed, otti_r1cs **out) {
     return guarded([&] {
         if (!out || n < min_n) throw Error(OTTI_ERR_BAD_ARG, "bad argument");

@@ -144,7 +144,7 @@ int32_t otti_instance_device_info(otti_instance *inst, int32_t by_col, otti_devi
         if (!inst || !out) throw Error(OTTI_ERR_BAD_ARG, "null argument");
         DevCtx::get(); Instance &I = *inst->I; ensure_instance_device(I);
         const DeviceCsrSet &m = by_col ? I.dev->by_col : I.dev->by_row;
-        out->rows = m.rows; for (int k = 0; k < 3; k++) out->entries[k] = I.M[k].val.size();
+        out->rows = m.rows; for (int k = 0; k < 3; k++) out->entries[k] = I.nnz[k];
         out->n_heavy = m.n_heavy; out->n_seg = m.n_seg; out->use_small = m.use_small ? 1 : 0; out->quad = m.quad() ? 1 : 0;
         return OTTI_OK;
     });

@@ -47,7 +47,17 @@ struct DeviceCsrSet {
     bool quad() const { return avg_row >= 3.0; }              // row per quad from three entries per row and matrix on (k_sparse.hip: the launchers' and the report's one rule)
     DCsr3 view() const { DCsr3 v; for (int k = 0; k < 3; k++) { v.ptr[k] = ptr[k].p; v.idx[k] = idx[k].p; v.val[k] = val[k].p; v.small[k] = small[k].p; } return v; }
 };
-struct DeviceInstance { DeviceCsrSet by_row, by_col; size_t nnz = 0; };
+// an entry list in HBM, in caller order: what both CSR copies are built from (k_sparse.hip build_csr_set).  code: the small-integer codes of
+// classify_coefficients, needed while the copies are built only.
+struct DeviceCoo { DevBuf<uint32_t> row, col; DevBuf<Fr> val; DevBuf<int32_t> code; size_t n = 0; };
+// ent[k]: the entry lists themselves, KEPT beside the CSR copies by a device ingest (k_ingest.hip) and by nothing else — they are what
+// Instance::mat() downloads when a host consumer asks for the lists.  Their cost: 40 bytes of HBM per entry (row 4, col 4, val 32) for as long as
+// the instance lives; otti_instance_ingest_info reports it.  An instance uploaded from host lists keeps none (ent[k].n = 0, no buffers).
+struct DeviceInstance { DeviceCsrSet by_row, by_col; size_t nnz = 0; DeviceCoo ent[3]; };
+struct DevCtx;
+bool classify_coefficients(DevCtx &c, DeviceCoo coo[3]);
+void build_csr_set(DevCtx &c, DeviceCsrSet &d, const DeviceCoo coo[3], bool by_col, size_t rows, bool use_small);
+bool device_runtime_up();                                   // a device context exists in this process already (k_context.hip): asking never brings one up
 // Rank k of g holds the constraint rows r = k (mod g) (renumbered r / g, columns untouched: multiply_vec output lands where the
 // low-bit-sharded phase-one tables need it) and, as a second copy, the entries of columns c = k (mod g) (renumbered c / g, rows
 // untouched: compute_eval_table_sparse output lands where the phase-two tables need it).  SURVEY.md 8(e).

@@ -44,6 +44,7 @@ static void mail_alloc(DevCtx &c, void **p, size_t bytes) {
     (void)hipGetLastError(); c.host_coherent = false;
     OTTI_HIP(hipHostMalloc(p, bytes, hipHostMallocDefault));
 }
+bool device_runtime_up() { CtxPool &P = ctx_pool(); std::lock_guard<std::mutex> lk(P.mu); return P.probed && !P.failed; }
 DevCtx &DevCtx::get() {
     thread_local CtxLease lease;
     if (lease.c) return *lease.c;

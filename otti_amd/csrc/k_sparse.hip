@@ -471,7 +471,6 @@ __global__ __launch_bounds__(kBlock) void k_csr_count_heavy(const uint32_t *p0, 
     for (size_t r = blockIdx.x * (size_t)blockDim.x + threadIdx.x; r < rows; r += (size_t)gridDim.x * blockDim.x)
         if (max(p0[r + 1] - p0[r], max(p1[r + 1] - p1[r], p2[r + 1] - p2[r])) > (uint32_t)kHeavyRow) atomicAdd(count, 1u);
 }
-struct DeviceCoo { DevBuf<uint32_t> row, col; DevBuf<Fr> val; DevBuf<int32_t> code; size_t n = 0; };
 static void upload_coo(DevCtx &c, DeviceCoo &d, const std::vector<uint32_t> &row, const std::vector<uint32_t> &col, const std::vector<Fr> &val) {
     d.n = val.size();
     d.row.alloc(std::max<size_t>(1, d.n)); d.col.alloc(std::max<size_t>(1, d.n)); d.val.alloc(std::max<size_t>(1, d.n));
@@ -481,7 +480,7 @@ static void upload_coo(DevCtx &c, DeviceCoo &d, const std::vector<uint32_t> &row
     OTTI_HIP(hipMemcpyAsync(d.val.p, val.data(), d.n * sizeof(Fr), hipMemcpyHostToDevice, c.stream));
 }
 // decide once per instance whether the kernels read coefficient codes: worth it when most entries are small integers
-static bool classify_coefficients(DevCtx &c, DeviceCoo coo[3]) {
+bool classify_coefficients(DevCtx &c, DeviceCoo coo[3]) {
     DevBuf<unsigned long long> count(1); unsigned long long n_small = 0; size_t total = 0;
     OTTI_HIP(hipMemsetAsync(count.p, 0, sizeof(unsigned long long), c.stream));
     for (int k = 0; k < 3; k++) {
@@ -493,7 +492,7 @@ static bool classify_coefficients(DevCtx &c, DeviceCoo coo[3]) {
     OTTI_HIP(hipStreamSynchronize(c.stream));
     return total >= 1024 && 2 * n_small >= total;
 }
-static void build_csr_set(DevCtx &c, DeviceCsrSet &d, const DeviceCoo coo[3], bool by_col, size_t rows, bool use_small) {
+void build_csr_set(DevCtx &c, DeviceCsrSet &d, const DeviceCoo coo[3], bool by_col, size_t rows, bool use_small) {
     if (rows + 1 > ((size_t)1 << 31)) throw Error(OTTI_ERR_BAD_ARG, "instance too large for 32-bit indices");
     d.rows = rows; d.use_small = use_small;
     d.avg_row = rows ? (double)(coo[0].n + coo[1].n + coo[2].n) / (3.0 * (double)rows) : 0.0;
@@ -540,11 +539,11 @@ std::shared_ptr<DeviceInstance> upload_instance(const Instance &I) {
     DevCtx &c = DevCtx::get();
     auto d = std::make_shared<DeviceInstance>();
     DeviceCoo coo[3];
-    for (int k = 0; k < 3; k++) upload_coo(c, coo[k], I.M[k].row, I.M[k].col, I.M[k].val);
+    for (int k = 0; k < 3; k++) upload_coo(c, coo[k], I.mat(k).row, I.mat(k).col, I.mat(k).val);
     const bool use_small = classify_coefficients(c, coo);
     build_csr_set(c, d->by_row, coo, false, I.num_cons, use_small);
     build_csr_set(c, d->by_col, coo, true, 2 * I.num_vars, use_small);
-    d->nnz = I.M[0].val.size() + I.M[1].val.size() + I.M[2].val.size();
+    d->nnz = I.nnz[0] + I.nnz[1] + I.nnz[2];
     return d;
 }
 
@@ -558,7 +557,7 @@ std::shared_ptr<DeviceShard> upload_instance_shard(const Instance &I, int rank, 
     // rows r = k (mod g) renumbered r / g, columns untouched; and the entries of columns c = k (mod g) renumbered c / g, rows untouched
     DeviceCoo rows[3], cols[3];
     for (int m = 0; m < 3; m++) {
-        const SparseMat &M = I.M[m];
+        const SparseMat &M = I.mat(m);
         std::vector<uint32_t> rr, rc, cr, cc; std::vector<Fr> rv, cv;
         for (size_t e = 0; e < M.val.size(); e++) {
             if (M.row[e] % g == k) { rr.push_back(M.row[e] / g); rc.push_back(M.col[e]); rv.push_back(M.val[e]); }

@@ -75,7 +75,7 @@ Fr reduce_evals(std::vector<Fr> v, const std::vector<Fr> &ch) {    // bound_poly
 namespace {
 // sizes of the dense representation of I: N operations per matrix, M memory cells
 void decomm_dims(const Instance &I, size_t &N, size_t &M) {
-    size_t nz = 0; for (int k = 0; k < 3; k++) nz = std::max(nz, I.M[k].val.size() + ((I.given_cons < 2 && I.num_cons > I.M[k].val.size()) ? I.num_cons - I.M[k].val.size() : 0));
+    size_t nz = 0; for (int k = 0; k < 3; k++) nz = std::max(nz, I.nnz[k] + ((I.given_cons < 2 && I.num_cons > I.nnz[k]) ? I.num_cons - I.nnz[k] : 0));
     N = next_pow2(std::max<size_t>(nz, 2)); M = (size_t)1 << std::max(ilog2(I.num_cons), ilog2(2 * I.num_vars));
 }
 void check_gens_fit(const Instance &I, const SnarkGens &g, size_t N, size_t M) {
@@ -93,7 +93,7 @@ void decomm_fill_host(DevCtx &c, const Instance &I, DeviceDecomm *dec, EncodeLap
     const size_t N = dec->N, M = dec->M;
     std::vector<uint32_t> addr[2][3], read_ts[2][3], audit[2];
     for (int k = 0; k < 3; k++) {
-        const SparseMat &m = I.M[k];
+        const SparseMat &m = I.mat(k);
         addr[0][k].assign(N, 0); addr[1][k].assign(N, 0);
         for (size_t i = 0; i < m.val.size(); i++) { addr[0][k][i] = m.row[i]; addr[1][k][i] = m.col[i]; }
         if (I.given_cons < 2)                                 // upstream pads 0 / 1 constraints with explicit zero entries (row i, column num_vars)
@@ -119,7 +119,7 @@ void decomm_fill_host(DevCtx &c, const Instance &I, DeviceDecomm *dec, EncodeLap
             dev_u32_to_fr(c, tmp.p, dec->part(2 * side + 1, k), N);
             OTTI_HIP(hipStreamSynchronize(c.stream));     // tmp is reused (the copies come from pageable memory: nothing to overlap with)
         }
-        if (!I.M[k].val.empty()) OTTI_HIP(hipMemcpyAsync(dec->part(4, k), I.M[k].val.data(), I.M[k].val.size() * sizeof(Fr), hipMemcpyHostToDevice, c.stream));
+        if (!I.mat(k).val.empty()) OTTI_HIP(hipMemcpyAsync(dec->part(4, k), I.mat(k).val.data(), I.mat(k).val.size() * sizeof(Fr), hipMemcpyHostToDevice, c.stream));
     }
     for (int side = 0; side < 2; side++) {
         OTTI_HIP(hipMemcpyAsync(tmp.p, audit[side].data(), M * 4, hipMemcpyHostToDevice, c.stream));
@@ -136,7 +136,7 @@ void decomm_fill_device(DevCtx &c, const Instance &I, DeviceDecomm *dec, EncodeL
     std::vector<uint32_t> extra[2][3];                        // upstream pads 0 / 1 constraints with explicit zero entries (row i, column num_vars)
     OTTI_HIP(hipMemsetAsync(dec->comb_ops.p + 12 * N, 0, 4 * N * sizeof(Fr), c.stream));      // values (zero-padded) and the unused sixteenth part
     for (int k = 0; k < 3; k++) {
-        const SparseMat &m = I.M[k]; const size_t nv = m.val.size();
+        const SparseMat &m = I.mat(k); const size_t nv = m.val.size();
         size_t len = nv;
         if (I.given_cons < 2 && I.num_cons > nv) {
             for (size_t i = nv; i < I.num_cons; i++) { extra[0][k].push_back((uint32_t)i); extra[1][k].push_back((uint32_t)I.num_vars); }

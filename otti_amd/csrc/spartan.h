@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 #include <memory>
+#include <mutex>
 #include <stdexcept>
 #include "field.h"
 #include "point.h"
@@ -37,7 +38,18 @@ struct DeviceGens;       // device.h / k_msm.hip
 struct Instance {
     size_t num_cons = 0, num_vars = 0, num_inputs = 0;      // padded cons / vars (powers of two)
     size_t given_cons = 0;                                  // num_cons as passed to Instance::new (SNARK mode: upstream pads 0 / 1 constraints with explicit entries)
-    SparseMat M[3];                                         // A, B, C
+    size_t given_vars = 0;                                  // num_vars as passed (the columns behind the variables are shifted by num_vars - given_vars)
+    size_t nnz[3] = {0, 0, 0};                              // entries of A, B, C: known without the host lists
+    // A, B, C as host lists.  instance_new fills them.  An instance ingested on the device (k_ingest.hip) has `dev` set and the lists EMPTY until a
+    // host consumer asks: mat() downloads the entry lists the device copy keeps (DeviceInstance::ent) exactly once, whichever of any number of
+    // threads asks first; it never reads the file again.  Every reader goes through mat().
+    const SparseMat &mat(int k) const { if (host_lists_pending) std::call_once(host_lists_once, [this] { materialise_host_lists(); }); return M[k]; }
+    mutable SparseMat M[3];                                 // (writers: instance_new, materialise_host_lists)
+    bool host_lists_pending = false;                        // set once, before the instance is shared; never cleared (call_once is the gate)
+    mutable std::once_flag host_lists_once;
+    void materialise_host_lists() const;
+    // how the instance came to be (otti_instance_ingest_info): the circuit file's size and the four laps of a device ingest
+    bool ingested_on_device = false; uint64_t circuit_bytes = 0; double ingest_ms[4] = {0, 0, 0, 0};
     std::shared_ptr<DeviceInstance> dev;                    // uploaded lazily on the first GPU prove
     std::shared_ptr<DeviceShard> shard;                     // uploaded lazily on the first sharded prove
     // Fr tuple evaluation used by the verifier: (A,B,C)(rx, ry)
@@ -46,6 +58,9 @@ struct Instance {
 };
 std::unique_ptr<Instance> instance_new(size_t num_cons, size_t num_vars, size_t num_inputs, const otti_entry *A, size_t nA,
                                        const otti_entry *B, size_t nB, const otti_entry *C, size_t nC);
+// fills I.M from the device's entry lists (set by the device layer; host-only builds have no instance that needs it)
+typedef void (*InstanceHostListsHook)(const Instance &I, SparseMat out[3]);
+extern InstanceHostListsHook g_instance_host_lists_hook;
 
 // ---------------------------------------------------------------------------------------------- generators
 // Every MultiCommitGens upstream derives for this path comes from ONE SHAKE256 stream (label "gens_r1cs_sat"):

@@ -21,7 +21,8 @@ std::unique_ptr<Instance> instance_new(size_t num_cons, size_t num_vars, size_t 
     size_t ncp = num_cons < 2 ? 2 : next_pow2(num_cons);
     if (ncp > ((size_t)1 << 30) || nvp > ((size_t)1 << 30)) throw Error(OTTI_ERR_BAD_ARG, "instance too large for 32-bit indices");
     auto I = std::make_unique<Instance>();
-    I->num_cons = ncp; I->num_vars = nvp; I->num_inputs = num_inputs; I->given_cons = num_cons;
+    I->num_cons = ncp; I->num_vars = nvp; I->num_inputs = num_inputs; I->given_cons = num_cons; I->given_vars = num_vars;
+    I->nnz[0] = nA; I->nnz[1] = nB; I->nnz[2] = nC;
     const otti_entry *src[3] = {A, B, C}; size_t cnt[3] = {nA, nB, nC};
     // validation and conversion to Montgomery form (one field multiplication per entry) in blocks over the host cores; the error a
     // sequential walk would meet first is the one reported
@@ -60,6 +61,14 @@ std::unique_ptr<Instance> instance_new(size_t num_cons, size_t num_vars, size_t 
     return I;
 }
 
+InstanceHostListsHook g_instance_host_lists_hook = nullptr;
+void Instance::materialise_host_lists() const {
+    if (!g_instance_host_lists_hook) throw Error(OTTI_ERR_INTERNAL, "instance without host lists and no device layer to fetch them");
+    SparseMat lists[3];                                      // filled whole before a reader can see any of it: a failed download leaves M empty for the retry
+    g_instance_host_lists_hook(*this, lists);
+    for (int k = 0; k < 3; k++) M[k] = std::move(lists[k]);
+}
+
 std::vector<Fr> eq_evals_host(const Fr *r, size_t ell) {
     std::vector<Fr> ev((size_t)1 << ell);
     ev[0] = fr_one();
@@ -75,7 +84,7 @@ void Instance::evaluate(const std::vector<Fr> &rx, const std::vector<Fr> &ry, Fr
     std::vector<Fr> ex = eq_evals_host(rx.data(), rx.size()), ey = eq_evals_host(ry.data(), ry.size());
     for (int k = 0; k < 3; k++) {
         Fr acc = fr_zero();
-        const SparseMat &m = M[k];
+        const SparseMat &m = mat(k);
         for (size_t i = 0; i < m.val.size(); i++) acc = fr_add(acc, fr_mul(fr_mul(ex[m.row[i]], ey[m.col[i]]), m.val[i]));
         out[k] = acc;
     }
@@ -94,7 +103,7 @@ bool Instance::is_sat(const std::vector<Fr> &vars, const std::vector<Fr> &inputs
     std::vector<Fr> Mz[3];
     for (int k = 0; k < 3; k++) {
         Mz[k].assign(num_cons, fr_zero());
-        const SparseMat &m = M[k];
+        const SparseMat &m = mat(k);
         for (size_t i = 0; i < m.val.size(); i++) Mz[k][m.row[i]] = fr_add(Mz[k][m.row[i]], fr_mul(m.val[i], z[m.col[i]]));
     }
     for (size_t r = 0; r < num_cons; r++) if (!fr_eq(fr_mul(Mz[0][r], Mz[1][r]), Mz[2][r])) return false;

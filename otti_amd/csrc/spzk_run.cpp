@@ -116,6 +116,21 @@ static bool write_file(const RunEnv &E, const char *path, const uint8_t *p, size
 
 // ---- SNARK mode, one role per process.  role 'e': encode, 'p': prove, 'v': verify.  Returns the exit status.
 struct SnarkRoleArgs { char role; std::vector<const char *> files; const char *comm_in, *comm_out, *proof_in, *proof_out, *label; const uint8_t *seed; bool check, verify_comm; };
+// A SERVED request in NIZK mode takes the files to a ready instance in one call (otti_instance_from_zkif, OTTI_INGEST_AUTO: on the device when the
+// circuit's size allows — the worker's runtime is up).  The one-shot keeps the host path (it parses while its HIP runtime comes up), and so does SNARK
+// mode (it needs the host lists at once).  Returns 1: taken; 0: not taken, or the FILES were refused (the three codes a loader gives a file: the
+// caller then goes the host path, which words such a refusal stage by stage exactly as the one-shot does); any other failure — no device, no
+// memory, a HIP error — is the request's failure and comes back as its negative code: nothing is parsed a second time behind it.
+static int served_ingest(const RunEnv &E, bool nizk, const std::string &circuit, const std::string &inputs, const char *witness, otti_instance **inst, otti_r1cs **r) {
+    if (!E.served || !nizk) return 0;
+    const int rc = otti_instance_from_zkif(circuit.c_str(), inputs.c_str(), witness, OTTI_INGEST_AUTO, inst, r);
+    if (rc == OTTI_OK) return 1;
+    return rc == OTTI_ERR_IO || rc == OTTI_ERR_INVALID_INDEX || rc == OTTI_ERR_INVALID_SCALAR ? 0 : rc;
+}
+static const char *ingest_word(const otti_instance *inst) {
+    int32_t on_device = 0;
+    return otti_instance_ingest_info(inst, &on_device, nullptr, nullptr, nullptr) == OTTI_OK && on_device ? "device" : "host";
+}
 static int snark_role(const RunEnv &E, const SnarkRoleArgs &a) {
     int rc; double t0 = now_ms(); Frees fr(E);
     if (a.role == 'v') {                                       // the commitment, the public inputs, the proof: nothing else, and no device
@@ -230,10 +245,14 @@ int spzk_run(int argc, char **argv, const RunEnv &E) {
     const bool verify_only = proof_in != nullptr;
     if (check_only) {                                          // load, Instance::new, upload, check: no generators, no window table
         if (files.size() != 3 || verify_only || proof_out || comm_in || comm_out) return usage(E);
-        otti_r1cs *r = nullptr; int rc = otti_zkif_load(at(E, files[0]).c_str(), at(E, files[1]).c_str(), at(E, files[2]).c_str(), &r); if (rc) return fail(E, "zkif load", rc);
-        fr.add([=] { otti_r1cs_free(r); });
-        otti_instance *inst = nullptr;
-        rc = otti_instance_new(r->num_cons, r->num_vars, r->num_inputs, r->A, r->nA, r->B, r->nB, r->C, r->nC, &inst); if (rc) return fail(E, "Instance::new", rc);
+        otti_r1cs *r = nullptr; otti_instance *inst = nullptr; int rc = 0;
+        const int took = served_ingest(E, nizk, at(E, files[0]), at(E, files[1]), at(E, files[2]).c_str(), &inst, &r);
+        if (took < 0) return fail(E, "zkif ingest", took);
+        if (!took) {
+            rc = otti_zkif_load(at(E, files[0]).c_str(), at(E, files[1]).c_str(), at(E, files[2]).c_str(), &r); if (rc) return fail(E, "zkif load", rc);
+            fr.add([=] { otti_r1cs_free(r); });
+            rc = otti_instance_new(r->num_cons, r->num_vars, r->num_inputs, r->A, r->nA, r->B, r->nB, r->C, r->nC, &inst); if (rc) return fail(E, "Instance::new", rc);
+        } else fr.add([=] { otti_r1cs_free(r); });
         fr.add([=] { otti_instance_free(inst); });
         rc = otti_prepare_device(inst, nullptr); if (rc) return fail(E, "device setup", rc);
         otti_witness *wit = nullptr;
@@ -278,9 +297,14 @@ int spzk_run(int argc, char **argv, const RunEnv &E) {
     }
     double t0 = now_ms();
     otti_r1cs *r = nullptr; int rc;
+    otti_instance *inst = nullptr;
     {
         const std::string f0 = at(E, files[0]), f1 = at(E, files[1]), f2 = at(E, verify_only ? nullptr : files[2]);
-        rc = otti_zkif_load(f0.c_str(), f1.c_str(), verify_only ? nullptr : f2.c_str(), &r); if (rc) return fail(E, "zkif load", rc);
+        const int took = served_ingest(E, nizk, f0, f1, verify_only ? nullptr : f2.c_str(), &inst, &r);
+        if (took < 0) return fail(E, "zkif ingest", took);
+        if (!took) {
+            rc = otti_zkif_load(f0.c_str(), f1.c_str(), verify_only ? nullptr : f2.c_str(), &r); if (rc) return fail(E, "zkif load", rc);
+        }
     }
     fr.add([=] { otti_r1cs_free(r); });
     double t_load = now_ms() - t0; t0 = now_ms();
@@ -290,8 +314,7 @@ int spzk_run(int argc, char **argv, const RunEnv &E) {
     if (nizk) gens_thread = std::thread([&] { gens_rc = E.gens->nizk_gens(r->num_cons, r->num_vars, r->num_inputs, &gens_early); });
     auto gens_rc_wait = [&] { if (gens_thread.joinable()) gens_thread.join(); return gens_rc; };
     struct GensJoiner { std::thread &t; ~GensJoiner() { if (t.joinable()) t.join(); } } gens_joiner{gens_thread};
-    otti_instance *inst = nullptr;
-    rc = otti_instance_new(r->num_cons, r->num_vars, r->num_inputs, r->A, r->nA, r->B, r->nB, r->C, r->nC, &inst); if (rc) return fail(E, "Instance::new", rc);
+    if (!inst) { rc = otti_instance_new(r->num_cons, r->num_vars, r->num_inputs, r->A, r->nA, r->B, r->nB, r->C, r->nC, &inst); if (rc) return fail(E, "Instance::new", rc); }
     fr.add([=] { otti_instance_free(inst); });
     otti_witness *wit = nullptr;                               // --check: the assignment is uploaded once, checked, and proved from HBM
     if (check) {
@@ -379,7 +402,7 @@ int spzk_run(int argc, char **argv, const RunEnv &E) {
         if (f) fclose(f);
     }
     // (no frees: the process ends here and hands everything back at once — releasing the device tables one by one costs milliseconds)
-    if (E.served) fprintf(E.out, "* served: queue %.3f ms, generators %s, table %s\n", E.queue_ms, E.gens->gens_word(), E.gens->table_word());
+    if (E.served) fprintf(E.out, "* served: queue %.3f ms, generators %s, table %s, ingest %s\n", E.queue_ms, E.gens->gens_word(), E.gens->table_word(), ingest_word(inst));
     else fprintf(E.out, "* process start to main() %.0f ms (the dynamic loader mapping the HIP runtime), main() %.3f ms\n", E.t_before_main, now_ms() - t_main0);
     if (rc) { fprintf(E.out, "Verification FAILED (%d: %s)\n", rc, rc == OTTI_ERR_VERIFY_DECOMPRESS ? "DecompressionError" : rc == OTTI_ERR_VERIFY_INTERNAL ? "InternalError" : "malformed proof"); return 1; }
     if (wrc) return 1;

@@ -8,6 +8,7 @@
 // ConstraintSystem{constraints: [BilinearConstraint{linear_combination_a, _b, _c: Variables}]}; Witness{assigned_variables: Variables};
 // Variables{variable_ids: [u64], values: [u8], info}.  Files are concatenations of size-prefixed buffers with identifier "zkif".
 #include "spartan.h"
+#include "zkif.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <fcntl.h>
@@ -210,10 +211,7 @@ void write_header(FILE *f, const std::vector<uint64_t> &inst_ids, const std::vec
 struct IdMap {
     std::vector<uint32_t> col_of;             // 0xffffffff = undeclared
     size_t num_vars = 0, num_inputs = 0;
-    size_t col(uint64_t id) const {
-        if (id >= col_of.size() || col_of[id] == 0xffffffffu) throw Error(OTTI_ERR_INVALID_INDEX, "zkif: constraint references an undeclared variable id");
-        return col_of[id];
-    }
+    // (the lookup of a constraint's id: ColOf below, over the table as a constraint pass is given it; on the device zkif_walk.h zw_col)
     // witness position of an id (its column while it is below num_vars), or SIZE_MAX
     size_t wit_pos(uint64_t id) const { if (id >= col_of.size()) return SIZE_MAX; uint32_t c = col_of[id]; return c < num_vars ? c : SIZE_MAX; }
     void build(const std::vector<uint64_t> &instance_ids, uint64_t free_id) {
@@ -271,7 +269,14 @@ otti_r1cs *otti_r1cs_from(size_t nc, size_t nv, size_t ni, const std::vector<ott
 
 // one linear combination (a Variables table) straight into matrix entries of `row`; no intermediate per-constraint objects, so a
 // 2^24-constraint file costs its own size plus the entry arrays
-static void append_lc(std::vector<otti_entry> &out, const Table &vars, uint64_t row, const IdMap &map) {
+struct ColOf {                                              // the column of a variable id, over IdMap::col_of as a constraint pass is given it (zkif.h)
+    const uint32_t *col_of; size_t n_ids;
+    size_t col(uint64_t id) const {
+        if (id >= n_ids || col_of[id] == 0xffffffffu) throw Error(OTTI_ERR_INVALID_INDEX, "zkif: constraint references an undeclared variable id");
+        return col_of[id];
+    }
+};
+static void append_lc(std::vector<otti_entry> &out, const Table &vars, uint64_t row, const ColOf &map) {
     if (!vars.present) return;
     size_t is, in; vars.vec(0, is, in);
     if (!in) return;
@@ -292,9 +297,11 @@ static void append_lc(std::vector<otti_entry> &out, const Table &vars, uint64_t 
 }
 
 static double zk_now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-otti_r1cs *zkif_load_impl(const char *circuit_path, const char *inputs_path, const char *witness_path) {
+// The frame of both loaders (zkif.h): everything but the pass over the constraints, in the order — and with the OTTI_TRACE laps — the host loader
+// has always had: headers + witness message, id map, message walk, the pass, assignment.
+otti_r1cs *otti::zkif_load_with(const char *circuit_path, const char *inputs_path, const char *witness_path, const ZkifConstraintPass &pass) {
     const bool trace = getenv("OTTI_TRACE") != nullptr; double tt = zk_now();
-    auto lap = [&](const char *what) { if (trace) { double n = zk_now(); fprintf(stderr, "[otti] zkif_load %-28s %.2f ms\n", what, n - tt); tt = n; } };
+    const ZkifLap lap = [&](const char *what) { if (trace) { double n = zk_now(); fprintf(stderr, "[otti] zkif_load %-28s %.2f ms\n", what, n - tt); tt = n; } };
     Messages m;
     FileView circuit(circuit_path);
     parse_headers(circuit, m);
@@ -320,53 +327,22 @@ otti_r1cs *zkif_load_impl(const char *circuit_path, const char *inputs_path, con
     IdMap map; map.build(m.instance.ids, free_id);
     lap("id map");
     if (m.have_witness && m.witness.ids.size() != map.num_vars) throw Error(OTTI_ERR_IO, "zkif: witness does not assign every variable exactly once");
-    // pass 2: constraints of the circuit file.  A quick walk over the messages finds every ConstraintSystem's offset vector; the rows are
-    // then cut into contiguous blocks, one per host thread, each parsed into its own entry lists (a FlatBuffers vector of tables is
-    // random access), and the lists are concatenated in row order — the same entries in the same order as a sequential walk.
-    struct Chunk { Buf b; size_t s, n; uint64_t first_row; };
-    std::vector<Chunk> chunks; uint64_t row = 0;
+    // pass 2: constraints of the circuit file.  A quick walk over the messages finds every ConstraintSystem's offset vector; what becomes of the
+    // rows is the loader's own pass.
+    ZkifCircuit zc; zc.file = circuit.data(); zc.file_bytes = circuit.size();
+    zc.col_of = map.col_of.data(); zc.n_ids = map.col_of.size(); zc.num_vars = map.num_vars; zc.num_inputs = map.num_inputs;
+    uint64_t row = 0;
     for_each_message(circuit, [&](uint8_t type, const Table &msg, const Buf &b) {
         if (type != 2) return;
         size_t s, n; msg.vec(0, s, n); b.chk(s, n * 4);
-        chunks.push_back({b, s, n, row}); row += n;
+        zc.msgs.push_back(ZwMsg{b.p, b.n, s, n, row}); row += n;
     });
+    zc.rows = row;
     lap("message walk");
-    unsigned nt = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-    if (const char *e = getenv("OTTI_PARSE_THREADS")) { int v = atoi(e); if (v >= 1 && v <= 64) nt = (unsigned)v; }
-    if (row < 4096) nt = 1;
-    std::vector<std::vector<otti_entry>> part[3]; for (auto &p : part) p.resize(nt);
-    std::vector<std::exception_ptr> err(nt);
-    auto work = [&](unsigned t) {
-        try {
-            const uint64_t r0 = row * t / nt, r1 = row * (t + 1) / nt;
-            for (auto &v : part) v[t].reserve((size_t)((r1 - r0) * 5 / 4 + 16));
-            for (const Chunk &ch : chunks) {
-                if (ch.first_row + ch.n <= r0 || ch.first_row >= r1) continue;
-                const size_t i0 = r0 > ch.first_row ? (size_t)(r0 - ch.first_row) : 0, i1 = (size_t)std::min<uint64_t>(ch.n, r1 - ch.first_row);
-                for (size_t i = i0; i < i1; i++) {
-                    Table bc; bc.b = &ch.b; bc.pos = ch.s + 4 * i + ch.b.u32(ch.s + 4 * i); bc.present = true; ch.b.chk(bc.pos, 4);
-                    for (int k = 0; k < 3; k++) append_lc(part[k][t], bc.sub(k), ch.first_row + i, map);
-                }
-            }
-        } catch (...) { err[t] = std::current_exception(); }
-    };
-    fan_out(nt, work);
-    for (auto &e : err) if (e) std::rethrow_exception(e);
-    lap("constraints (threads)");
     otti_r1cs *out = (otti_r1cs *)calloc(1, sizeof *out);
     if (!out) throw std::bad_alloc();
     struct Guard { otti_r1cs *r; ~Guard() { if (r) otti_r1cs_free(r); } } guard{out};
-    otti_entry **dst[3] = {&out->A, &out->B, &out->C}; size_t *cnt[3] = {&out->nA, &out->nB, &out->nC};
-    for (int k = 0; k < 3; k++) {                                         // the threads' parts go straight into the arrays the caller will own
-        size_t total = 0; for (auto &v : part[k]) total += v.size();
-        otti_entry *arr = (otti_entry *)malloc(std::max<size_t>(1, total) * sizeof(otti_entry));
-        if (!arr) throw std::bad_alloc();
-        *dst[k] = arr; *cnt[k] = total;
-        std::vector<size_t> at(nt); size_t o = 0; for (unsigned t = 0; t < nt; t++) { at[t] = o; o += part[k][t].size(); }
-        auto cp = [&, k, arr](unsigned t) { if (!part[k][t].empty()) memcpy(arr + at[t], part[k][t].data(), part[k][t].size() * sizeof(otti_entry)); std::vector<otti_entry>().swap(part[k][t]); };
-        fan_out(nt, cp);
-    }
-    lap("concatenate");
+    pass(zc, out, lap);
     out->num_cons = row; out->num_vars = map.num_vars; out->num_inputs = map.num_inputs;
     out->nvars = m.have_witness ? map.num_vars : 0; out->ninputs = map.num_inputs;      // no witness file (verifier): no assignment
     out->vars32 = (uint8_t *)calloc(std::max<size_t>(1, 32 * out->nvars), 1); out->inputs32 = (uint8_t *)calloc(std::max<size_t>(1, 32 * out->ninputs), 1);
@@ -386,6 +362,50 @@ otti_r1cs *zkif_load_impl(const char *circuit_path, const char *inputs_path, con
     lap("assignment");
     guard.r = nullptr;
     return out;
+}
+
+// the host loader's pass: the rows are cut into contiguous blocks, one per host thread, each parsed into its own entry lists (a FlatBuffers
+// vector of tables is random access), and the lists are concatenated in row order — the same entries in the same order as a sequential walk.
+static void host_constraint_pass(const ZkifCircuit &zc, otti_r1cs *out, const ZkifLap &lap) {
+    const ColOf map{zc.col_of, zc.n_ids};
+    const uint64_t row = zc.rows;
+    unsigned nt = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+    if (const char *e = getenv("OTTI_PARSE_THREADS")) { int v = atoi(e); if (v >= 1 && v <= 64) nt = (unsigned)v; }
+    if (row < 4096) nt = 1;
+    std::vector<std::vector<otti_entry>> part[3]; for (auto &p : part) p.resize(nt);
+    std::vector<std::exception_ptr> err(nt);
+    auto work = [&](unsigned t) {
+        try {
+            const uint64_t r0 = row * t / nt, r1 = row * (t + 1) / nt;
+            for (auto &v : part) v[t].reserve((size_t)((r1 - r0) * 5 / 4 + 16));
+            for (const ZwMsg &ch : zc.msgs) {
+                if (ch.first_row + ch.count <= r0 || ch.first_row >= r1) continue;
+                const Buf cb{ch.base, (size_t)ch.size}; const size_t s = (size_t)ch.vec_start;
+                const size_t i0 = r0 > ch.first_row ? (size_t)(r0 - ch.first_row) : 0, i1 = (size_t)std::min<uint64_t>(ch.count, r1 - ch.first_row);
+                for (size_t i = i0; i < i1; i++) {
+                    Table bc; bc.b = &cb; bc.pos = s + 4 * i + cb.u32(s + 4 * i); bc.present = true; cb.chk(bc.pos, 4);
+                    for (int k = 0; k < 3; k++) append_lc(part[k][t], bc.sub(k), ch.first_row + i, map);
+                }
+            }
+        } catch (...) { err[t] = std::current_exception(); }
+    };
+    fan_out(nt, work);
+    for (auto &e : err) if (e) std::rethrow_exception(e);
+    lap("constraints (threads)");
+    otti_entry **dst[3] = {&out->A, &out->B, &out->C}; size_t *cnt[3] = {&out->nA, &out->nB, &out->nC};
+    for (int k = 0; k < 3; k++) {                                         // the threads' parts go straight into the arrays the caller will own
+        size_t total = 0; for (auto &v : part[k]) total += v.size();
+        otti_entry *arr = (otti_entry *)malloc(std::max<size_t>(1, total) * sizeof(otti_entry));
+        if (!arr) throw std::bad_alloc();
+        *dst[k] = arr; *cnt[k] = total;
+        std::vector<size_t> at(nt); size_t o = 0; for (unsigned t = 0; t < nt; t++) { at[t] = o; o += part[k][t].size(); }
+        auto cp = [&, k, arr](unsigned t) { if (!part[k][t].empty()) memcpy(arr + at[t], part[k][t].data(), part[k][t].size() * sizeof(otti_entry)); std::vector<otti_entry>().swap(part[k][t]); };
+        fan_out(nt, cp);
+    }
+    lap("concatenate");
+}
+otti_r1cs *zkif_load_impl(const char *circuit_path, const char *inputs_path, const char *witness_path) {
+    return zkif_load_with(circuit_path, inputs_path, witness_path, host_constraint_pass);
 }
 
 // the public inputs alone (what a SNARK verifier holding the computation commitment needs): the .inp.zkif header's instance values, in
