@@ -43,6 +43,12 @@ extern "C" {
                          stride_bytes: usize, src_on_device: i32, stream: *mut core::ffi::c_void, n_changed: *mut u64, idx: *mut u64,
                          idx_cap: usize) -> i32;
     fn otti_witness_assign_info(wit: *const OttiWitness, calls: *mut u64, changed: *mut u64, resums: *mut u64) -> i32;
+    // .inp.zkif + .wit.zkif to a resident witness of `inst`, equal to otti_zkif_load + otti_witness_upload; mode: 0 auto (the device from
+    // OTTI_INGEST_WIT_MIN_MB MiB of witness file on), 1 host, 2 device (the Witness messages go to HBM as they are in the file and are read
+    // there).  A defective file gets the host pair's code.  inputs_out (optional, an otti_r1cs* to free with otti_r1cs_free): the public inputs.
+    fn otti_witness_from_zkif(inst: *mut OttiInstance, inputs_path: *const c_char, witness_path: *const c_char, mode: i32, out: *mut *mut OttiWitness,
+                              inputs_out: *mut *mut c_void) -> i32;
+    fn otti_witness_ingest_info(wit: *const OttiWitness, on_device: *mut i32, witness_bytes: *mut u64, ms: *mut f64) -> i32;
     // SNARK mode (upstream spartan-zkinterface without --nizk)
     fn otti_snark_gens_new(num_cons: u64, num_vars: u64, num_inputs: u64, num_nz_entries: u64, out: *mut *mut OttiSnarkGens) -> i32;
     fn otti_snark_gens_free(gens: *mut OttiSnarkGens);

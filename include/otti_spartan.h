@@ -412,6 +412,36 @@ int32_t otti_instance_entries(otti_instance *inst, int32_t which /* 0 A, 1 B, 2 
  * take (0 unless on_device); and a device ingest's four laps in ms: host walk + id map, staging + copies, kernels, CSR build.  Any pointer may be NULL. */
 int32_t otti_instance_ingest_info(const otti_instance *inst, int32_t *on_device, uint64_t *circuit_bytes, uint64_t *hbm_entry_bytes,
                                   double ms[4] /* host walk + id map, staging + copies, kernels, CSR build */);
+/* .inp.zkif + .wit.zkif to a resident witness of `inst`, equal in every observable way (z, inputs, small_fraction, proof bytes) to otti_zkif_load on
+ * the instance's three files followed by otti_witness_upload.  It works with every consumer and mutator of a resident witness.
+ *   OTTI_INGEST_HOST:   the host loader's frame over the two files (the circuit's share left out), then the upload path.
+ *   OTTI_INGEST_DEVICE: headers and the inputs file stay on the host, which also locates and checks the ids and values vectors of every Witness
+ *                       message; the messages are staged through the circuit ingest's pinned buffers to HBM as they are in the file, and one kernel,
+ *                       a thread per assigned variable, reads id and value there (elements of any width: narrower ones zero-extended, of wider ones
+ *                       the first 32 bytes, the rest having to be zero), maps the id to its column, refuses a variable assigned twice through a
+ *                       bitmap, tests the value against l, converts it by the upload's rule and writes z.  No 32-byte copy of the assignment is
+ *                       made on the host.  Its own limit: a witness file of 16 GiB and more is OTTI_ERR_BAD_ARG.
+ *   OTTI_INGEST_AUTO:   the device when the witness file has at least OTTI_INGEST_WIT_MIN_MB MiB (read per call; default 10: the smallest size
+ *                       probed at which the device path won, profiles/zkif_witness_ingest.md), else the host.
+ * The id map is rebuilt from these two files alone (the instance ids and free_variable_id of the inputs header, the witness ids); when the resulting
+ * num_vars / num_inputs are not the instance's: OTTI_ERR_BAD_ARG, said behind the checks of the headers, the id map and the number of assigned
+ * variables and before any value is looked at.  Every other defect of the files is reported with the code the host pair (otti_zkif_load +
+ * otti_witness_upload) gives for the same two files beside a clean circuit, the first in the host pair's order: per Witness message in file order
+ * a malformed table or vector (OTTI_ERR_IO), then an element wider than 32 bytes with a non-zero tail (OTTI_ERR_INVALID_SCALAR); the headers'
+ * field_maximum and free_variable_id, the instance ids, a count of assigned variables other than num_vars (OTTI_ERR_IO; an instance id 0
+ * OTTI_ERR_INVALID_INDEX); an inputs file or a witness message without values (OTTI_ERR_IO); the first assigned id that is 0, an instance id
+ * or unknown (OTTI_ERR_INVALID_INDEX); a variable assigned twice (OTTI_ERR_IO); a public input >= l, then a witness value >= l
+ * (OTTI_ERR_INVALID_SCALAR).  A refused z is never visible, and after a device-side refusal the context stays usable.
+ * Before any device is touched: a null inst, path or out, or an unknown mode, is OTTI_ERR_BAD_ARG; a file that cannot be read OTTI_ERR_IO.  Without
+ * a device: OTTI_ERR_NO_DEVICE in every mode (a resident witness lives on one).  On any error *out and *inputs_out are untouched.
+ * *inputs_out (optional): an otti_r1cs with only num_inputs, inputs32, ninputs filled, as otti_zkif_load_inputs gives. */
+int32_t otti_witness_from_zkif(otti_instance *inst, const char *inputs_path, const char *witness_path, int32_t mode, otti_witness **out,
+                               otti_r1cs **inputs_out);
+/* the cut-over OTTI_INGEST_AUTO applies at this moment, in MiB: OTTI_INGEST_WIT_MIN_MB when it is set to a number >= 0, else the default */
+double  otti_witness_ingest_min_mb(void);
+/* how a witness came to be: on_device = 1 when otti_witness_from_zkif read the file on the device; the witness file's size (0 unless it came from
+ * otti_witness_from_zkif); and the device path's three laps in ms: host walk, staging + copies, kernel.  Any pointer but wit may be NULL. */
+int32_t otti_witness_ingest_info(const otti_witness *wit, int32_t *on_device, uint64_t *witness_bytes, double ms[3] /* host walk, staging + copies, kernel */);
 /* synthetic satisfiable R1CS: num_cons = num_vars = n, one non-zero per row per matrix */
 int32_t otti_synth_r1cs(uint64_t n, uint64_t num_inputs, uint64_t seed, otti_r1cs **out);
 /* second distribution of SURVEY 8d ("compiler-like"): 90 % of the witness < 2^64, 1..8 non-zeros per row, small signed coefficients,

@@ -160,6 +160,9 @@ _sig("otti_instance_from_zkif", _i32, ctypes.c_char_p, ctypes.c_char_p, ctypes.c
 _sig("otti_instance_entries", _i32, _vp, _i32, _vp, _sz, ctypes.POINTER(_sz))
 _sig("otti_instance_ingest_info", _i32, _vp, ctypes.POINTER(_i32), ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(ctypes.c_double))
 INGEST_MODES = {"auto": 0, "host": 1, "device": 2}             # OTTI_INGEST_*
+_sig("otti_witness_from_zkif", _i32, _vp, ctypes.c_char_p, ctypes.c_char_p, _i32, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.POINTER(_R1CS)))
+_sig("otti_witness_ingest_min_mb", ctypes.c_double)
+_sig("otti_witness_ingest_info", _i32, _vp, ctypes.POINTER(_i32), ctypes.POINTER(_u64), ctypes.POINTER(ctypes.c_double))
 _sig("otti_k_eq_evals", _i32, _vp, _sz, _vp, _fp)
 _sig("otti_k_fold_top", _i32, _vp, _sz, _vp, _vp, _fp)
 _sig("otti_k_fold_bot", _i32, _vp, _sz, _vp, _vp, _fp)
@@ -559,6 +562,22 @@ class Witness:
         import torch
         fmt, nvars, stride = _tensor_layout(torch, tensor)
         return cls.from_device(inst, tensor.data_ptr(), nvars, fmt, inputs, stride, _torch_stream(torch, tensor, stream))
+
+    @classmethod
+    def from_zkif(cls, inst, inputs, witness, mode="auto"):
+        """otti_witness_from_zkif: the .inp.zkif and .wit.zkif files to a resident witness of ``inst``, equal to zkif_load + upload.  mode "host"
+        parses the two files on the host and uploads; "device" ships the Witness messages to HBM and reads them there; "auto" takes the device
+        from OTTI_INGEST_WIT_MIN_MB MiB of witness file on.  A defective file raises what zkif_load + Witness raise for it.  Returns
+        (Witness, public inputs as an (n, 32) uint8 array)."""
+        h, rp = _vp(), ctypes.POINTER(_R1CS)()
+        _check(lib.otti_witness_from_zkif(inst._h, os.fsencode(inputs), os.fsencode(witness), INGEST_MODES[mode], ctypes.byref(h), ctypes.byref(rp)))
+        return cls._adopt(h), _r1cs_to_py(rp)["inputs"]
+
+    def ingest_info(self):
+        """otti_witness_ingest_info: dict of on_device, witness_bytes and ms (host walk, staging + copies, kernel)"""
+        on, wb, ms = _i32(), _u64(), (ctypes.c_double * 3)()
+        _check(lib.otti_witness_ingest_info(self._h, ctypes.byref(on), ctypes.byref(wb), ms))
+        return dict(on_device=bool(on.value), witness_bytes=wb.value, ms=tuple(ms))
 
     def _source(self, values, fmt, stride_bytes, stream, what):
         """(src, count, fmt, stride_bytes, on_device, stream, keep-alive) of the ``values`` update / assign / diff take"""

@@ -7,11 +7,15 @@ otti_r1cs *zkif_load_impl(const char *circuit_path, const char *inputs_path, con
 void zkif_write_impl(const otti_r1cs *r, const char *circuit_path, const char *inputs_path, const char *witness_path);
 otti_r1cs *zkif_load_inputs_impl(const char *inputs_path);
 namespace otti { otti_r1cs *instance_from_zkif_device(const char *circuit_path, const char *inputs_path, const char *witness_path, std::unique_ptr<Instance> &inst); }   // k_ingest.hip
+#include "zkif.h"
 #include <sys/stat.h>
 #include <unistd.h>
 // otti_instance_from_zkif(OTTI_INGEST_AUTO): the circuit sizes between which the device path is taken (OTTI_INGEST_MIN_MB, OTTI_INGEST_GB override them
 // per call; OTTI_INGEST_GB=0: never).  Where they come from: profiles/zkif_ingest.md.
 constexpr double kIngestMinMB = 15.0;                       // MiB: the smallest probed circuit (2^16 uniform, 15.2 MiB) — the device path's median beat the host path's beyond both spreads at every probed size
+// otti_witness_from_zkif(OTTI_INGEST_AUTO): the witness file's size from which the device path is taken (OTTI_INGEST_WIT_MIN_MB overrides it per call).
+// Where it comes from: profiles/zkif_witness_ingest.md.
+constexpr double kIngestWitMinMB = 10.0;                   // MiB: 2^18 variables (10.0 MiB) — the smallest probed size at which the device path's median beat the host path's beyond both spreads; at 2^16 (2.5 MiB) it did not
 constexpr double kIngestGB = 8.0;                            // image + 40-byte entries + both CSR copies of such a file stay far below one card's HBM
 
 thread_local std::string g_last_error;
@@ -586,6 +590,68 @@ int32_t otti_instance_ingest_info(const otti_instance *inst, int32_t *on_device,
             if (I.ingested_on_device && I.dev) for (int k = 0; k < 3; k++) *hbm_entry_bytes += (uint64_t)I.dev->ent[k].n * 40;
         }
         if (ms) for (int k = 0; k < 4; k++) ms[k] = I.ingest_ms[k];
+        return OTTI_OK;
+    });
+}
+// ---- the inputs and witness files to a resident witness (zkif.h, k_wit_ingest.hip).  The ladder of otti_instance_from_zkif: the arguments, the
+// files' readability, a missing device — said in every mode: a resident witness lives on one —, then the files; *out and *inputs_out are written last.
+static double wit_min_mb() {
+    if (const char *e = getenv("OTTI_INGEST_WIT_MIN_MB")) { char *end = nullptr; const double v = strtod(e, &end); if (end != e && v >= 0) return v; }
+    return kIngestWitMinMB;
+}
+double otti_witness_ingest_min_mb(void) { return wit_min_mb(); }
+int32_t otti_witness_from_zkif(otti_instance *inst, const char *inputs_path, const char *witness_path, int32_t mode, otti_witness **out, otti_r1cs **inputs_out) {
+    return guarded([&] {
+        if (!inst || !inputs_path || !witness_path || !out) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (mode != OTTI_INGEST_AUTO && mode != OTTI_INGEST_HOST && mode != OTTI_INGEST_DEVICE) throw Error(OTTI_ERR_BAD_ARG, "unknown ingest mode");
+        uint64_t witness_bytes = 0;
+        for (const char *path : {inputs_path, witness_path}) {
+            struct stat st;
+            if (access(path, R_OK) != 0 || stat(path, &st) != 0 || !S_ISREG(st.st_mode)) throw Error(OTTI_ERR_IO, std::string("cannot read ") + path);
+            if (path == witness_path) witness_bytes = (uint64_t)st.st_size;
+        }
+        if (otti_device_count() < 1) throw Error(OTTI_ERR_NO_DEVICE, "no device: a resident witness lives on one");
+        const Instance &I = *inst->I;
+        const bool on_device = mode == OTTI_INGEST_DEVICE || (mode == OTTI_INGEST_AUTO && (double)witness_bytes >= wit_min_mb() * 1048576.0);
+        const size_t dims[2] = {I.given_vars, I.num_inputs};
+        std::unique_ptr<DeviceWitness> w; std::vector<uint8_t> inputs32;
+        const auto t0 = std::chrono::steady_clock::now();
+        if (on_device) {
+            zkif_witness_with(inputs_path, witness_path, dims, [&](const ZkifWitness &zw) {
+                const double walk_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+                w = std::make_unique<DeviceWitness>(I, zw);
+                w->file_ms[0] = walk_ms;
+                inputs32 = zw.inputs32;
+            });
+        } else {
+            otti_r1cs *r = zkif_load_assignment(inputs_path, witness_path, dims);
+            struct Guard { otti_r1cs *r; ~Guard() { otti_r1cs_free(r); } } guard{r};
+            std::vector<Fr> inputs = scalars_from_bytes(r->inputs32, r->ninputs);
+            w = std::make_unique<DeviceWitness>(I, WIT_CANONICAL32, r->vars32, r->nvars, 0, false, nullptr, inputs);
+            w->file_bytes = witness_bytes;
+            inputs32.assign(r->inputs32, r->inputs32 + 32 * r->ninputs);
+        }
+        otti_r1cs *io = nullptr;
+        if (inputs_out) {                                       // as otti_zkif_load_inputs gives them
+            io = (otti_r1cs *)calloc(1, sizeof *io);
+            if (!io) throw std::bad_alloc();
+            io->num_inputs = io->ninputs = inputs32.size() / 32;
+            io->vars32 = (uint8_t *)calloc(1, 1); io->inputs32 = (uint8_t *)calloc(std::max<size_t>(1, inputs32.size()), 1);
+            if (!io->vars32 || !io->inputs32) { otti_r1cs_free(io); throw std::bad_alloc(); }
+            if (!inputs32.empty()) memcpy(io->inputs32, inputs32.data(), inputs32.size());
+        }
+        *out = new otti_witness{std::move(w)};
+        if (inputs_out) *inputs_out = io;
+        return OTTI_OK;
+    });
+}
+int32_t otti_witness_ingest_info(const otti_witness *wit, int32_t *on_device, uint64_t *witness_bytes, double ms[3]) {
+    return guarded([&] {
+        if (!wit) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        const DeviceWitness &w = *wit->w;
+        if (on_device) *on_device = w.from_file_on_device ? 1 : 0;
+        if (witness_bytes) *witness_bytes = w.file_bytes;
+        if (ms) for (int k = 0; k < 3; k++) ms[k] = w.file_ms[k];
         return OTTI_OK;
     });
 }

@@ -217,6 +217,13 @@ struct DeviceWitness {
     // is widened on the device).  Validation (InvalidScalar) and the conversion to Montgomery form happen on the device.  producer: the stream
     // whose queued work writes a device source (nullptr: none to wait for).  Returns once the source is free again.
     DeviceWitness(const Instance &I, int format, const void *src, size_t nvars, size_t stride, bool src_on_device, hipStream_t producer, const std::vector<Fr> &inputs);
+    // from the Witness messages of a .wit.zkif as the host walk located them (zkif.h ZkifWitness, k_wit_ingest.hip): the messages go to HBM as they
+    // are in the file and a thread per assigned variable reads, maps, checks and converts its element — the conversion rule above — straight into z.
+    // z, inputs and small_fraction come out as the constructor above leaves them for the host loader's assignment of the same files; a defect
+    // throws what the host pair reports for them (the smallest key), and the fresh z goes with the object.
+    DeviceWitness(const Instance &I, const struct ZkifWitness &zw);
+    bool from_file_on_device = false; uint64_t file_bytes = 0;   // made by the constructor above; the witness file's size (either way through otti_witness_from_zkif)
+    double file_ms[3] = {0, 0, 0};                            // its laps: host walk, staging + copies, kernel
     // straight from the caller's canonical bytes on the host: the same path
     DeviceWitness(const Instance &I, const uint8_t *vars32, size_t nvars, const std::vector<Fr> &inputs) : DeviceWitness(I, WIT_CANONICAL32, vars32, nvars, 0, false, nullptr, inputs) {}
     // variables [first, first + count) replaced likewise.  A scalar >= l throws INVALID_SCALAR and leaves z as it was (the 32-byte formats are
@@ -316,6 +323,9 @@ DotProductProofLog dplog_prove_device(DevCtx &c, const DeviceGens &DG, const Gen
 // Montgomery form to z[dst_off + i]; src is either disjoint from the destination or is the destination itself, packed (conversion in place).
 // Returns the number of non-canonical scalars (stored as zero); n_small: how many are below 2^128.  Synchronises.
 size_t dev_witness_ingest_from(DevCtx &c, int format, const void *src, size_t stride, size_t n, Fr *z, size_t dst_off, size_t *n_small = nullptr);
+// DeviceWitness's constructor from a .wit.zkif (k_wit_ingest.hip): z[col] written for every assigned variable of zw; returns the smallest error key
+// (zkif_wit_walk.h; zw.seed when nothing sorts before it), *n_small as above; ms[1], ms[2]: staging + copies, kernel.  Synchronises.
+uint64_t dev_witness_from_zkif(DevCtx &c, const struct ZkifWitness &zw, Fr *z, size_t *n_small, double ms[3]);
 // DeviceWitness::scatter's two element-wise launches (k_field.hip).  check: conv[i] = element i of src in Montgomery form (the rules of
 // dev_witness_ingest_from, src disjoint from conv or conv itself, packed); *bad_scalars counts those >= l, *bad_indices the i with idx[i] >= V or idx[i] <= idx[i - 1]; writes nothing else;
 // synchronises.  apply (V: the length of z's first half, beyond which nothing is stored): z[idx[i]] = conv[i], and with delta given delta[i] = conv[i] - (what z[idx[i]] held); only queues.

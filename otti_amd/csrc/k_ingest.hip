@@ -17,8 +17,6 @@
 
 namespace otti {
 
-struct IngestMsg { unsigned long long off, size, vec_start, count, first_row; };   // ZwMsg with the body's place in the staged image
-
 // the message that holds row r: the last one that starts at or before it (a message without constraints shares its first row with its successor)
 __device__ __forceinline__ ZwMsg ingest_msg_of(const uint8_t *image, const IngestMsg *msgs, uint32_t n_msgs, uint64_t r) {
     uint32_t lo = 0, hi = n_msgs - 1;
@@ -85,7 +83,7 @@ static void fill_slab(uint8_t *dst, size_t a, size_t b, const std::vector<ZwMsg>
         if (s < t) memcpy(dst + (s - a), msgs[j].base + (s - m0), t - s);
     }
 }
-static void stage_image(DevCtx &c, uint8_t *d_image, size_t image_bytes, const std::vector<ZwMsg> &msgs, const std::vector<IngestMsg> &lay) {
+void ingest_stage_image(DevCtx &c, uint8_t *d_image, size_t image_bytes, const std::vector<ZwMsg> &msgs, const std::vector<IngestMsg> &lay) {
     const size_t n_slabs = (image_bytes + kIngestSlab - 1) / kIngestSlab;
     if (!n_slabs) return;
     unsigned nt = image_bytes < ((size_t)8 << 20) ? 1u : std::max(1u, std::min(kIngestThreads, std::thread::hardware_concurrency()));
@@ -166,7 +164,7 @@ static bool ingest_constraints(const ZkifCircuit &zc, Instance &I, double ms[4])
     DevBuf<IngestMsg> d_msgs(std::max<size_t>(1, lay.size()));
     DevBuf<uint32_t> d_col_of(std::max<size_t>(1, zc.n_ids)), d_cnt(std::max<size_t>(1, 3 * rows));
     DevBuf<unsigned long long> d_err(4);                        // the error key, then the three 64-bit totals
-    stage_image(c, d_image.p, image_bytes, zc.msgs, lay);
+    ingest_stage_image(c, d_image.p, image_bytes, zc.msgs, lay);
     if (!lay.empty()) OTTI_HIP(hipMemcpyAsync(d_msgs.p, lay.data(), lay.size() * sizeof(IngestMsg), hipMemcpyHostToDevice, c.stream));
     if (zc.n_ids) OTTI_HIP(hipMemcpyAsync(d_col_of.p, zc.col_of, zc.n_ids * 4, hipMemcpyHostToDevice, c.stream));
     OTTI_HIP(hipMemsetAsync(d_err.p, 0xff, sizeof(unsigned long long), c.stream));

@@ -33,6 +33,32 @@ template <class Launch> static inline Tallies counted_launch(DevCtx &c, Launch l
     return {h[0], h[1]};
 }
 
+// ------------------------------------------------------------------------------------------------ witness elements
+// (WitFormat: device.h; the loads of k_field.hip's wit_load<F>, or of the zkInterface reader of k_wit_ingest.hip, hand their word to this one rule)
+// THE conversion rule, for every kernel that takes witness elements in: the word wit_load<F> returned -> the Montgomery element.  An integer is
+// always a scalar; a negative one is l - |x| and so never small.  A 32-byte word >= l is refused: stored as zero, and counted as small as well.
+// small: the canonical value is below 2^128 (MONTGOMERY32: judged on fr_to_raw of the word).
+__device__ __forceinline__ bool fr_raw_below_2p128(const Fr &c) { return (c.v[4] | c.v[5] | c.v[6] | c.v[7]) == 0; }
+template <int F> __device__ __forceinline__ Fr wit_convert(Fr raw, bool neg, bool &refused, bool &small) {
+    Fr out; refused = false;
+    if constexpr (F == WIT_I64 || F == WIT_U64) {
+        if (neg) raw = fr_sub(fr_zero(), raw);                                   // l - |x| (on canonical integers the field subtraction is the integer one mod l)
+        small = !neg;
+        out = fr_mul(raw, fr_R2());
+    } else {
+        small = fr_raw_below_2p128(F == WIT_CANONICAL32 ? raw : fr_to_raw(raw));
+        if (!fr_raw_is_canonical(raw.v)) { out = fr_zero(); refused = small = true; }
+        else if constexpr (F == WIT_CANONICAL32) out = fr_mul(raw, fr_R2());
+        else out = raw;
+    }
+    return out;
+}
+// a lane's two tallies summed over its wave and added to counts[0], counts[1]
+__device__ __forceinline__ void wit_tally(unsigned a, unsigned b, unsigned long long *counts) {
+    for (int o = 32; o >= 1; o >>= 1) { a += __shfl_down(a, o); b += __shfl_down(b, o); }
+    if ((threadIdx.x & 63) == 0) { if (a) atomicAdd(&counts[0], (unsigned long long)a); if (b) atomicAdd(&counts[1], (unsigned long long)b); }
+}
+
 // ------------------------------------------------------------------------------------------------ inter-workgroup hand-off
 // Publishing a workgroup's partial result to the LAST workgroup of the same launch.  A per-workgroup agent release fence
 // (buffer_wbl2) serialises on the XCD's L2 and cost ~100 us over a 2048-workgroup grid; instead every handed-off byte is written

@@ -16,6 +16,7 @@
 #include <thread>
 #include <time.h>
 #include <unistd.h>
+#include <sys/stat.h>
 #include <stdlib.h>
 #include <string.h>
 #include <string>
@@ -121,11 +122,27 @@ struct SnarkRoleArgs { char role; std::vector<const char *> files; const char *c
 // mode (it needs the host lists at once).  Returns 1: taken; 0: not taken, or the FILES were refused (the three codes a loader gives a file: the
 // caller then goes the host path, which words such a refusal stage by stage exactly as the one-shot does); any other failure — no device, no
 // memory, a HIP error — is the request's failure and comes back as its negative code: nothing is parsed a second time behind it.
-static int served_ingest(const RunEnv &E, bool nizk, const std::string &circuit, const std::string &inputs, const char *witness, otti_instance **inst, otti_r1cs **r) {
+static int served_ingest(const RunEnv &E, bool nizk, const std::string &circuit, const std::string &inputs, const char *witness, otti_instance **inst, otti_r1cs **r,
+                         otti_witness **wit = nullptr) {
     if (!E.served || !nizk) return 0;
-    const int rc = otti_instance_from_zkif(circuit.c_str(), inputs.c_str(), witness, OTTI_INGEST_AUTO, inst, r);
+    // A prove request (wit given) whose witness file AUTO would read on the device: the circuit without the witness file — the call returns the public
+    // inputs —, then the two files to a resident witness (otti_witness_from_zkif), which the proof is made from.  A refusal of the FILES by either call
+    // — for the second also: files of other dimensions than the circuit's, and a worker without a device, which the host path words as the one-shot
+    // does — leaves nothing behind and goes the host path.
+    // A smaller witness file is parsed with the circuit and uploaded by the proof, as ever (profiles/zkif_witness_ingest.md: why the request looks itself).
+    struct stat st;
+    const bool resident = wit && stat(witness, &st) == 0 && (double)st.st_size >= otti_witness_ingest_min_mb() * 1048576.0;
+    int rc = otti_instance_from_zkif(circuit.c_str(), inputs.c_str(), resident ? nullptr : witness, OTTI_INGEST_AUTO, inst, r);
+    if (rc == OTTI_OK && resident) {
+        rc = otti_witness_from_zkif(*inst, inputs.c_str(), witness, OTTI_INGEST_AUTO, wit, nullptr);
+        if (rc != OTTI_OK) { otti_instance_free(*inst); otti_r1cs_free(*r); *inst = nullptr; *r = nullptr; if (rc == OTTI_ERR_BAD_ARG || rc == OTTI_ERR_NO_DEVICE) rc = OTTI_ERR_IO; }
+    }
     if (rc == OTTI_OK) return 1;
     return rc == OTTI_ERR_IO || rc == OTTI_ERR_INVALID_INDEX || rc == OTTI_ERR_INVALID_SCALAR ? 0 : rc;
+}
+static const char *witness_word(const otti_witness *wit) {
+    int32_t on_device = 0;
+    return wit && otti_witness_ingest_info(wit, &on_device, nullptr, nullptr) == OTTI_OK && on_device ? "device" : "host";
 }
 static const char *ingest_word(const otti_instance *inst) {
     int32_t on_device = 0;
@@ -298,9 +315,10 @@ int spzk_run(int argc, char **argv, const RunEnv &E) {
     double t0 = now_ms();
     otti_r1cs *r = nullptr; int rc;
     otti_instance *inst = nullptr;
+    otti_witness *wit = nullptr;                               // a served prove request: the witness file went straight to HBM; --check: uploaded below; proved from HBM
     {
         const std::string f0 = at(E, files[0]), f1 = at(E, files[1]), f2 = at(E, verify_only ? nullptr : files[2]);
-        const int took = served_ingest(E, nizk, f0, f1, verify_only ? nullptr : f2.c_str(), &inst, &r);
+        const int took = served_ingest(E, nizk, f0, f1, verify_only ? nullptr : f2.c_str(), &inst, &r, verify_only ? nullptr : &wit);
         if (took < 0) return fail(E, "zkif ingest", took);
         if (!took) {
             rc = otti_zkif_load(f0.c_str(), f1.c_str(), verify_only ? nullptr : f2.c_str(), &r); if (rc) return fail(E, "zkif load", rc);
@@ -316,11 +334,13 @@ int spzk_run(int argc, char **argv, const RunEnv &E) {
     struct GensJoiner { std::thread &t; ~GensJoiner() { if (t.joinable()) t.join(); } } gens_joiner{gens_thread};
     if (!inst) { rc = otti_instance_new(r->num_cons, r->num_vars, r->num_inputs, r->A, r->nA, r->B, r->nB, r->C, r->nC, &inst); if (rc) return fail(E, "Instance::new", rc); }
     fr.add([=] { otti_instance_free(inst); });
-    otti_witness *wit = nullptr;                               // --check: the assignment is uploaded once, checked, and proved from HBM
-    if (check) {
+    if (wit) fr.add([=] { otti_witness_free(wit); });
+    if (check) {                                               // --check: the assignment is uploaded once, checked, and proved from HBM
         rc = otti_prepare_device(inst, nullptr); if (rc) return fail(E, "device setup", rc);
-        rc = otti_witness_upload(inst, r->vars32, r->nvars, r->inputs32, r->ninputs, &wit); if (rc) return fail(E, "witness upload", rc);
-        fr.add([=] { otti_witness_free(wit); });
+        if (!wit) {
+            rc = otti_witness_upload(inst, r->vars32, r->nvars, r->inputs32, r->ninputs, &wit); if (rc) return fail(E, "witness upload", rc);
+            fr.add([=] { otti_witness_free(wit); });
+        }
         const int sat = run_check(E, inst, wit, r->num_cons);
         if (sat < 0) return 1;
         if (sat) { fprintf(E.out, "Verification FAILED (unsatisfied assignment)\n"); return 1; }
@@ -402,7 +422,8 @@ int spzk_run(int argc, char **argv, const RunEnv &E) {
         if (f) fclose(f);
     }
     // (no frees: the process ends here and hands everything back at once — releasing the device tables one by one costs milliseconds)
-    if (E.served) fprintf(E.out, "* served: queue %.3f ms, generators %s, table %s, ingest %s\n", E.queue_ms, E.gens->gens_word(), E.gens->table_word(), ingest_word(inst));
+    if (E.served) fprintf(E.out, "* served: queue %.3f ms, generators %s, table %s, witness %s, ingest %s\n", E.queue_ms, E.gens->gens_word(), E.gens->table_word(), witness_word(wit),
+                          ingest_word(inst));
     else fprintf(E.out, "* process start to main() %.0f ms (the dynamic loader mapping the HIP runtime), main() %.3f ms\n", E.t_before_main, now_ms() - t_main0);
     if (rc) { fprintf(E.out, "Verification FAILED (%d: %s)\n", rc, rc == OTTI_ERR_VERIFY_DECOMPRESS ? "DecompressionError" : rc == OTTI_ERR_VERIFY_INTERNAL ? "InternalError" : "malformed proof"); return 1; }
     if (wrc) return 1;

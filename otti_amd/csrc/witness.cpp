@@ -2,6 +2,7 @@
 // assign's dry form, and the derived state a witness may keep — row sums of the commitment, Az / Bz / Cz — which every mutator brings along through
 // ONE ending, z_written.  The provers read wit.z, rows_kept_for and products_kept_for and nothing else of this file.
 #include "device.h"
+#include "zkif.h"
 #include <cstring>
 
 namespace otti {
@@ -60,6 +61,18 @@ DeviceWitness::DeviceWitness(const Instance &I, int format, const void *src, siz
     if (!nvars) OTTI_HIP(hipStreamSynchronize(c.stream));
     if (bad) throw Error(OTTI_ERR_INVALID_SCALAR, "non-canonical scalar in assignment");
     small_fraction = V ? (double)(n_small + (V - nvars)) / (double)V : 0.0;        // the padding zeros count as small
+}
+
+DeviceWitness::DeviceWitness(const Instance &I, const ZkifWitness &zw) : inputs(zw.inputs) {
+    DevCtx &c = DevCtx::get();
+    const size_t V = I.num_vars, nvars = zw.have_witness ? zw.num_vars : 0;
+    if (zw.witness_bytes >= ((size_t)1 << 34)) throw Error(OTTI_ERR_BAD_ARG, "witness file too large for the device ingest (16 GiB)");
+    const std::vector<Fr> tail = set_up(c, I, nvars);
+    size_t n_small = 0;
+    const uint64_t key = dev_witness_from_zkif(c, zw, z.p, &n_small, file_ms);   // synchronises: `tail` is free again; a fresh z is thrown away on a refusal
+    if (key != kZwNoError) zkif_witness_refuse(zw, key);
+    small_fraction = V ? (double)(n_small + (V - nvars)) / (double)V : 0.0;        // the padding zeros count as small
+    from_file_on_device = true; file_bytes = zw.witness_bytes;
 }
 
 // ---- kept rows.  Rows [r0, r1] of z summed over g's table into their slots of rows_kept, by the launch the proof's own commitment would make for

@@ -130,15 +130,17 @@ template <class F> void for_each_message(const FileView &file, F &&fn) {
     if (off != file.size()) throw Error(OTTI_ERR_IO, "zkif: trailing bytes");
 }
 // pass 1: headers and witness only (ConstraintSystem messages are skipped by their size prefix)
+void read_header(const Table &msg, const Buf &b, Messages &m) {
+    VarList iv = read_variables(msg.sub(0));
+    if (!m.have_header || iv.has_vals) m.instance = iv;                   // the .inp.zkif header carries the values
+    m.free_variable_id = std::max(m.free_variable_id, msg.u64f(1, 0));
+    size_t s, n; if (msg.vec(2, s, n)) { b.chk(s, n); m.field_maximum.assign(b.p + s, b.p + s + n); }
+    m.have_header = true;
+}
 void parse_headers(const FileView &file, Messages &m) {
     for_each_message(file, [&](uint8_t type, const Table &msg, const Buf &b) {
-        if (type == 1) {                       // CircuitHeader
-            VarList iv = read_variables(msg.sub(0));
-            if (!m.have_header || iv.has_vals) m.instance = iv;           // the .inp.zkif header carries the values
-            m.free_variable_id = std::max(m.free_variable_id, msg.u64f(1, 0));
-            size_t s, n; if (msg.vec(2, s, n)) { b.chk(s, n); m.field_maximum.assign(b.p + s, b.p + s + n); }
-            m.have_header = true;
-        } else if (type == 3) {                // Witness
+        if (type == 1) read_header(msg, b, m); // CircuitHeader
+        else if (type == 3) {                  // Witness
             VarList w = read_variables(msg.sub(0));
             m.witness.ids.insert(m.witness.ids.end(), w.ids.begin(), w.ids.end());
             m.witness.vals.insert(m.witness.vals.end(), w.vals.begin(), w.vals.end());
@@ -227,6 +229,16 @@ struct IdMap {
         uint32_t k = 0;
         for (uint64_t id = 1; id < free_id; id++) if (!is_inst[id]) col_of[id] = k++;
     }
+    // the same checks, in the same order, and the same dimensions without the table: the instance ids ascending (zkif_wit_walk.h ww_col searches them)
+    std::vector<uint64_t> build_sorted(const std::vector<uint64_t> &instance_ids, uint64_t free_id) {
+        if (free_id > ((uint64_t)1 << 31)) throw Error(OTTI_ERR_BAD_ARG, "zkif: more than 2^31 variable ids");
+        for (auto id : instance_ids) if (id == 0 || id >= free_id) throw Error(OTTI_ERR_INVALID_INDEX, "zkif: instance variable id out of range");
+        std::vector<uint64_t> sorted = instance_ids; std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) throw Error(OTTI_ERR_IO, "zkif: duplicate instance variable id");
+        num_inputs = instance_ids.size();
+        num_vars = free_id > 0 ? (size_t)free_id - 1 - num_inputs : 0;
+        return sorted;
+    }
 };
 
 }  // namespace otti
@@ -296,6 +308,49 @@ static void append_lc(std::vector<otti_entry> &out, const Table &vars, uint64_t 
     }
 }
 
+// ---- the pieces of the frame that the loaders of the assignment alone (zkif.h zkif_load_assignment, zkif_witness_with) share with it
+// one past the largest of n witness ids (0: none)
+static uint64_t witness_id_end(const uint64_t *ids, size_t n) { uint64_t e = 0; for (size_t i = 0; i < n; i++) e = std::max(e, ids[i] + 1); return e; }
+// the headers' checks, and the number of variable ids the files declare
+static uint64_t frame_free_id(const Messages &m, uint64_t witness_end, size_t file_bytes) {
+    if (!m.have_header) throw Error(OTTI_ERR_IO, "zkif: no CircuitHeader message");
+    if (!m.field_maximum.empty()) {
+        static const uint8_t lm1[32] = {0xec, 0xd3, 0xf5, 0x5c, 0x1a, 0x63, 0x12, 0x58, 0xd6, 0x9c, 0xf7, 0xa2, 0xde, 0xf9, 0xde, 0x14,
+                                        0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0x10};
+        std::vector<uint8_t> fm = m.field_maximum; while (!fm.empty() && fm.back() == 0) fm.pop_back();
+        std::vector<uint8_t> want(lm1, lm1 + 32); while (!want.empty() && want.back() == 0) want.pop_back();
+        if (fm != want) throw Error(OTTI_ERR_IO, "zkif: field_maximum is not l-1 for the curve25519 scalar field");
+    }
+    // witness variables: every id in [1, free_variable_id) that is not an instance variable, in increasing order
+    uint64_t free_id = std::max<uint64_t>({m.free_variable_id, (uint64_t)1, witness_end});
+    for (auto id : m.instance.ids) free_id = std::max(free_id, id + 1);
+    // Untrusted header: every variable id a file declares occupies at least eight bytes somewhere in the files (its assignment, or its
+    // uses in constraints), so a free_variable_id beyond that is either garbage or an attempt to make the loader allocate gigabytes.
+    if (free_id > file_bytes / 8 + 2) throw Error(OTTI_ERR_IO, "zkif: free_variable_id is larger than the files can account for");
+    return free_id;
+}
+// the assignment: the public inputs in the instance ids' order, each witness value at its variable's place
+static void frame_assign(const Messages &m, const IdMap &map, bool inputs_file, otti_r1cs *out) {
+    out->nvars = m.have_witness ? map.num_vars : 0; out->ninputs = map.num_inputs;      // no witness file (verifier): no assignment
+    out->vars32 = (uint8_t *)calloc(std::max<size_t>(1, 32 * out->nvars), 1); out->inputs32 = (uint8_t *)calloc(std::max<size_t>(1, 32 * out->ninputs), 1);
+    if (!out->vars32 || !out->inputs32) throw std::bad_alloc();
+    if (m.instance.has_vals) for (size_t i = 0; i < map.num_inputs; i++) memcpy(out->inputs32 + 32 * i, m.instance.vals[i].data(), 32);
+    else if (map.num_inputs && inputs_file) throw Error(OTTI_ERR_IO, "zkif: inputs file carries no instance values");
+    if (m.have_witness) {
+        if (m.witness.ids.size() != m.witness.vals.size()) throw Error(OTTI_ERR_IO, "zkif: witness without values");
+        std::vector<uint8_t> seen(map.num_vars, 0);
+        for (size_t i = 0; i < m.witness.ids.size(); i++) {
+            size_t pos = m.witness.ids[i] == 0 ? SIZE_MAX : map.wit_pos(m.witness.ids[i]);
+            if (pos == SIZE_MAX) throw Error(OTTI_ERR_INVALID_INDEX, "zkif: witness assigns an instance or unknown variable");
+            memcpy(out->vars32 + 32 * pos, m.witness.vals[i].data(), 32); seen[pos] = 1;
+        }
+        for (uint8_t sn : seen) if (!sn) throw Error(OTTI_ERR_IO, "zkif: witness does not assign every variable");
+    }
+}
+static void frame_count(const Messages &m, const IdMap &map) {
+    if (m.have_witness && m.witness.ids.size() != map.num_vars) throw Error(OTTI_ERR_IO, "zkif: witness does not assign every variable exactly once");
+}
+
 static double zk_now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 // The frame of both loaders (zkif.h): everything but the pass over the constraints, in the order — and with the OTTI_TRACE laps — the host loader
 // has always had: headers + witness message, id map, message walk, the pass, assignment.
@@ -308,25 +363,11 @@ otti_r1cs *otti::zkif_load_with(const char *circuit_path, const char *inputs_pat
     size_t file_bytes = circuit.size();
     if (inputs_path) { FileView f(inputs_path); parse_headers(f, m); file_bytes += f.size(); }
     if (witness_path) { FileView f(witness_path); parse_headers(f, m); file_bytes += f.size(); }
-    if (!m.have_header) throw Error(OTTI_ERR_IO, "zkif: no CircuitHeader message");
-    if (!m.field_maximum.empty()) {
-        static const uint8_t lm1[32] = {0xec, 0xd3, 0xf5, 0x5c, 0x1a, 0x63, 0x12, 0x58, 0xd6, 0x9c, 0xf7, 0xa2, 0xde, 0xf9, 0xde, 0x14,
-                                        0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0x10};
-        std::vector<uint8_t> fm = m.field_maximum; while (!fm.empty() && fm.back() == 0) fm.pop_back();
-        std::vector<uint8_t> want(lm1, lm1 + 32); while (!want.empty() && want.back() == 0) want.pop_back();
-        if (fm != want) throw Error(OTTI_ERR_IO, "zkif: field_maximum is not l-1 for the curve25519 scalar field");
-    }
-    // witness variables: every id in [1, free_variable_id) that is not an instance variable, in increasing order
-    uint64_t free_id = std::max<uint64_t>(m.free_variable_id, 1);
-    for (auto id : m.witness.ids) free_id = std::max(free_id, id + 1);
-    for (auto id : m.instance.ids) free_id = std::max(free_id, id + 1);
-    // Untrusted header: every variable id a file declares occupies at least eight bytes somewhere in the files (its assignment, or its
-    // uses in constraints), so a free_variable_id beyond that is either garbage or an attempt to make the loader allocate gigabytes.
-    if (free_id > file_bytes / 8 + 2) throw Error(OTTI_ERR_IO, "zkif: free_variable_id is larger than the files can account for");
+    const uint64_t free_id = frame_free_id(m, witness_id_end(m.witness.ids.data(), m.witness.ids.size()), file_bytes);
     lap("headers + witness message");
     IdMap map; map.build(m.instance.ids, free_id);
     lap("id map");
-    if (m.have_witness && m.witness.ids.size() != map.num_vars) throw Error(OTTI_ERR_IO, "zkif: witness does not assign every variable exactly once");
+    frame_count(m, map);
     // pass 2: constraints of the circuit file.  A quick walk over the messages finds every ConstraintSystem's offset vector; what becomes of the
     // rows is the loader's own pass.
     ZkifCircuit zc; zc.file = circuit.data(); zc.file_bytes = circuit.size();
@@ -344,21 +385,7 @@ otti_r1cs *otti::zkif_load_with(const char *circuit_path, const char *inputs_pat
     struct Guard { otti_r1cs *r; ~Guard() { if (r) otti_r1cs_free(r); } } guard{out};
     pass(zc, out, lap);
     out->num_cons = row; out->num_vars = map.num_vars; out->num_inputs = map.num_inputs;
-    out->nvars = m.have_witness ? map.num_vars : 0; out->ninputs = map.num_inputs;      // no witness file (verifier): no assignment
-    out->vars32 = (uint8_t *)calloc(std::max<size_t>(1, 32 * out->nvars), 1); out->inputs32 = (uint8_t *)calloc(std::max<size_t>(1, 32 * out->ninputs), 1);
-    if (!out->vars32 || !out->inputs32) throw std::bad_alloc();
-    if (m.instance.has_vals) for (size_t i = 0; i < map.num_inputs; i++) memcpy(out->inputs32 + 32 * i, m.instance.vals[i].data(), 32);
-    else if (map.num_inputs && inputs_path) throw Error(OTTI_ERR_IO, "zkif: inputs file carries no instance values");
-    if (m.have_witness) {
-        if (m.witness.ids.size() != m.witness.vals.size()) throw Error(OTTI_ERR_IO, "zkif: witness without values");
-        std::vector<uint8_t> seen(map.num_vars, 0);
-        for (size_t i = 0; i < m.witness.ids.size(); i++) {
-            size_t pos = m.witness.ids[i] == 0 ? SIZE_MAX : map.wit_pos(m.witness.ids[i]);
-            if (pos == SIZE_MAX) throw Error(OTTI_ERR_INVALID_INDEX, "zkif: witness assigns an instance or unknown variable");
-            memcpy(out->vars32 + 32 * pos, m.witness.vals[i].data(), 32); seen[pos] = 1;
-        }
-        for (uint8_t sn : seen) if (!sn) throw Error(OTTI_ERR_IO, "zkif: witness does not assign every variable");
-    }
+    frame_assign(m, map, inputs_path != nullptr, out);
     lap("assignment");
     guard.r = nullptr;
     return out;
@@ -406,6 +433,123 @@ static void host_constraint_pass(const ZkifCircuit &zc, otti_r1cs *out, const Zk
 }
 otti_r1cs *zkif_load_impl(const char *circuit_path, const char *inputs_path, const char *witness_path) {
     return zkif_load_with(circuit_path, inputs_path, witness_path, host_constraint_pass);
+}
+
+// ---- the assignment without a circuit file (zkif.h)
+static void check_want_dims(const IdMap &map, const size_t want_dims[2]) {
+    if (want_dims && (map.num_vars != want_dims[0] || map.num_inputs != want_dims[1]))
+        throw Error(OTTI_ERR_BAD_ARG, "zkif: the inputs and witness files describe an instance of other dimensions");
+}
+otti_r1cs *otti::zkif_load_assignment(const char *inputs_path, const char *witness_path, const size_t want_dims[2]) {
+    Messages m;
+    size_t file_bytes = 0;
+    { FileView f(inputs_path); parse_headers(f, m); file_bytes += f.size(); }
+    { FileView f(witness_path); parse_headers(f, m); file_bytes += f.size(); }
+    const uint64_t free_id = frame_free_id(m, witness_id_end(m.witness.ids.data(), m.witness.ids.size()), file_bytes);
+    IdMap map; map.build(m.instance.ids, free_id);
+    frame_count(m, map);
+    check_want_dims(map, want_dims);
+    otti_r1cs *out = (otti_r1cs *)calloc(1, sizeof *out);
+    if (!out) throw std::bad_alloc();
+    struct Guard { otti_r1cs *r; ~Guard() { if (r) otti_r1cs_free(r); } } guard{out};
+    out->num_vars = map.num_vars; out->num_inputs = map.num_inputs;
+    frame_assign(m, map, true, out);
+    guard.r = nullptr;
+    return out;
+}
+
+[[noreturn]] void otti::zkif_witness_refuse(const ZkifWitness &zw, uint64_t key) {
+    if (key == zw.seed) throw Error(zw.seed_code, zw.seed_what);
+    const int code = ww_key_code(key);
+    throw Error(code, code == OTTI_ERR_INVALID_INDEX ? "zkif: witness assigns an instance or unknown variable"
+                    : code == OTTI_ERR_IO ? "zkif: witness does not assign every variable"
+                    : ww_key_step(key) == WW_MESSAGE ? "zkif: element wider than 32 bytes" : "non-canonical scalar in assignment");
+}
+// one Witness message as read_variables checks it, its values left where they are.  false: it assigns variables and carries no values.
+static bool locate_witness(const Table &msg, const Buf &b, WwMsg &w) {
+    w = WwMsg{b.p, b.n, 0, 0, 0, 0, 0, 0};
+    const Table t = msg.sub(0);
+    if (!t.present) return true;
+    size_t s, n; t.vec(0, s, n);
+    b.chk(s, n * 8);
+    w.ids_start = s; w.count = n;
+    size_t vs, vn;
+    if (t.vec(1, vs, vn) && vn) {
+        if (n == 0 || vn % n) throw Error(OTTI_ERR_IO, "zkif: values length not a multiple of the variable count");
+        b.chk(vs, vn);
+        w.vals_start = vs; w.width = w.stride = vn / n;
+        return true;
+    }
+    return n == 0;
+}
+// the first element of message w (the j-th) with a non-zero byte beyond its 32nd, as a key, or kZwNoError: the reader itself, on an aligned copy of
+// exactly the message's length rounded up to four bytes (what the reader may load)
+static uint64_t first_tail_defect(WwMsg w, size_t j) {
+    std::vector<uint32_t> block((size_t)(w.size + 3) / 4);
+    memcpy(block.data(), w.base, (size_t)w.size);
+    w.base = reinterpret_cast<const uint8_t *>(block.data());
+    for (uint64_t i = 0; i < w.count; i++) {
+        Zw z{w.base, w.size, kZwNoError}; uint64_t id; uint32_t val[8];
+        ww_elem(z, w, j, i, id, val);
+        if (z.err != kZwNoError) return z.err;
+    }
+    return kZwNoError;
+}
+void otti::zkif_witness_with(const char *inputs_path, const char *witness_path, const size_t want_dims[2], const ZkifWitnessPass &pass) {
+    Messages m;
+    ZkifWitness zw;
+    size_t file_bytes = 0;
+    { FileView f(inputs_path); parse_headers(f, m); file_bytes += f.size(); }
+    FileView wf(witness_path);
+    file_bytes += wf.size(); zw.witness_bytes = wf.size();
+    // the host's own first defect: what it is (a key of zkif_wit_walk.h) and what it says
+    auto defer = [&](uint64_t key, const Error &e) { if (key < zw.seed) { zw.seed = key; zw.seed_code = e.code; zw.seed_what = e.what(); } };
+    uint64_t id_end = 0; bool missing_values = false;
+    try {
+        for_each_message(wf, [&](uint8_t type, const Table &msg, const Buf &b) {
+            if (type == 1) { read_header(msg, b, m); return; }
+            if (type != 3) return;
+            if (zw.msgs.size() + 1 >= kWwMaxMessages) throw Error(OTTI_ERR_IO, "zkif: too many Witness messages");
+            WwMsg w;
+            if (!locate_witness(msg, b, w)) { missing_values = true; w.width = w.stride = 0; }
+            w.first = zw.total;
+            if (w.width > kWwMaxWidth) {                         // elements a device thread should not read byte by byte: their tails are read here
+                const uint64_t key = first_tail_defect(w, zw.msgs.size());
+                if (key != kZwNoError) defer(key, Error(OTTI_ERR_INVALID_SCALAR, "zkif: element wider than 32 bytes"));
+                w.width = 32;
+            }
+            for (uint64_t i = 0; i < w.count; i++) { uint64_t id; memcpy(&id, b.p + w.ids_start + 8 * i, 8); id_end = std::max(id_end, id + 1); }
+            zw.msgs.push_back(w); zw.total += w.count; zw.have_witness = true;
+        });
+    } catch (const Error &e) { defer(ww_key_message(zw.msgs.size(), 0, 0), e); }     // behind the tails of the messages before it
+    if (zw.seed == kZwNoError) {
+        try {
+            const uint64_t free_id = frame_free_id(m, id_end, file_bytes);
+            IdMap map; zw.inst_sorted = map.build_sorted(m.instance.ids, free_id);
+            zw.num_vars = map.num_vars; zw.num_inputs = map.num_inputs;
+            if (zw.have_witness && zw.total != map.num_vars) throw Error(OTTI_ERR_IO, "zkif: witness does not assign every variable exactly once");
+            check_want_dims(map, want_dims);
+        } catch (const Error &e) { defer(ww_key(WW_FRAME, 0), e); }
+    }
+    if (zw.seed == kZwNoError) {
+        zw.inputs32.assign(32 * zw.num_inputs, 0);
+        if (m.instance.has_vals) for (size_t i = 0; i < zw.num_inputs; i++) memcpy(zw.inputs32.data() + 32 * i, m.instance.vals[i].data(), 32);
+        else if (zw.num_inputs) defer(ww_key(WW_NO_VALUES, 0), Error(OTTI_ERR_IO, "zkif: inputs file carries no instance values"));
+        if (missing_values) defer(ww_key(WW_NO_VALUES, 1), Error(OTTI_ERR_IO, "zkif: witness without values"));
+    }
+    if (zw.seed == kZwNoError) {
+        zw.inputs.resize(zw.num_inputs);
+        for (size_t i = 0; i < zw.num_inputs; i++)
+            if (!fr_from_bytes(zw.inputs[i], zw.inputs32.data() + 32 * i)) { defer(ww_key(WW_SCALAR, 0), Error(OTTI_ERR_INVALID_SCALAR, "non-canonical scalar in assignment")); break; }
+    }
+    if (ww_key_step(zw.seed) < WW_INDEX) {
+        // The host has refused the files, and of what the values hold only step 1 sorts before that: an element wider than 32 bytes with a non-zero
+        // tail, in a message the walk has accepted.  Such messages are read here, by the reader itself; nothing goes to a device.
+        for (size_t j = 0; j < zw.msgs.size(); j++)
+            if (zw.msgs[j].width > 32) { const uint64_t key = first_tail_defect(zw.msgs[j], j); if (key < zw.seed) zkif_witness_refuse(zw, key); }
+        zkif_witness_refuse(zw, zw.seed);
+    }
+    pass(zw);
 }
 
 // the public inputs alone (what a SNARK verifier holding the computation commitment needs): the .inp.zkif header's instance values, in

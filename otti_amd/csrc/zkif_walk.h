@@ -134,6 +134,18 @@ HD ZwLc zw_lc(Zw &z, const ZwMsg &m, uint64_t i, int k) {
     return lc;
 }
 
+// THE element rule, for coefficients (zw_emit) and assigned values (zkif_wit_walk.h) alike: the w bytes at src as eight little-endian words — a
+// narrower element zero-extended; of a wider one the first 32, any non-zero byte beyond them being the error key_tail.  val comes zeroed.
+HD void zw_value(Zw &z, uint64_t src, uint64_t w, uint64_t key, uint64_t key_tail, uint32_t val[8]) {
+    if (w >= 32) for (int j = 0; j < 8; j++) val[j] = zw_u32(z, src + 4 * j, key);
+    else for (uint64_t b = 0; b < w; b++) val[b >> 2] |= zw_u8(z, src + b, key) << ((unsigned)(b & 3) * 8);
+    if (w > 32) {
+        uint32_t tail = 0;
+        for (uint64_t b = 32; b < w; b++) tail |= zw_u8(z, src + b, key);
+        if (tail) z.fail(key_tail);
+    }
+}
+
 // ---- the two entry points
 // COUNT: entries of (row, matrix) for the three matrices of constraint i
 HD void zw_count(Zw &z, const ZwMsg &m, uint64_t i, uint32_t out[3]) {
@@ -149,14 +161,7 @@ HD bool zw_emit(Zw &z, const ZwMsg &m, uint64_t i, int k, uint64_t e, uint64_t &
     if (e >= lc.count) return false;
     const uint64_t key = zw_key_parse(m.first_row + i, k, 0, 0, 0);    // (cannot fail: zw_lc has checked both vectors whole)
     id = zw_u64(z, lc.ids_start + 8 * e, key);
-    const uint64_t src = lc.vals_start + e * lc.width, w = lc.width;
-    if (w >= 32) for (int j = 0; j < 8; j++) val[j] = zw_u32(z, src + 4 * j, key);
-    else for (uint64_t b = 0; b < w; b++) val[b >> 2] |= zw_u8(z, src + b, key) << ((unsigned)(b & 3) * 8);
-    if (w > 32) {
-        uint32_t tail = 0;
-        for (uint64_t b = 32; b < w; b++) tail |= zw_u8(z, src + b, key);
-        if (tail) z.fail(zw_key_parse(m.first_row + i, k, 1, e, 1));
-    }
+    zw_value(z, lc.vals_start + e * lc.width, lc.width, key, zw_key_parse(m.first_row + i, k, 1, e, 1), val);
     return true;
 }
 // the column of a variable id (zkif.cpp ColOf::col, then instance_new's shift of the columns behind the variables by the padding), or the entry's

@@ -5,7 +5,8 @@
 
 For every size (2^k constraints) and both synthetic distributions (uniform, compiler-like) it writes the zkInterface triple once, then times
 `verify --nizk c i w` as a whole process, 2 warm-ups and 20 requests each way, and splits every request into zkif_load, setup, prove and
-verify from the lines the request itself prints.  The served leg goes smallest size first, so the first request of each larger size is the
+verify from the lines the request itself prints; the last column says where a served request's witness and circuit were read (`witness device|host`,
+`ingest device|host` of its `* served:` line).  The served leg goes smallest size first, so the first request of each larger size is the
 one that replaces the resident window table: its wall time is reported by itself (the rebuild), as are the table's width and bytes.
 The expectation this is written to check: a served request pays no runtime start, so its wall time should be close to the sum of its own
 printed stages.  Output: a markdown report (profiles/spzk_serve.md is one).  The probe process itself opens no GPU."""
@@ -35,6 +36,15 @@ def stages(stdout):
     return out
 
 
+def served_words(stdout):
+    """`witness device|host` and `ingest device|host` of a request's `* served:` line, as "witness/ingest" ("-" for a word the line does not carry:
+    a one-shot has no such line, an older server no `witness` word)"""
+    m = re.search(r"^\* served: (.*)$", stdout, re.M)
+    line = m.group(1) if m else ""
+    w, g = re.search(r"\bwitness (device|host)\b", line), re.search(r"\bingest (device|host)\b", line)
+    return "%s/%s" % (w.group(1) if w else "-", g.group(1) if g else "-")
+
+
 def timed(argv, cwd, env):
     t0 = time.perf_counter()
     r = subprocess.run(argv, cwd=cwd, env=env, capture_output=True, text=True, timeout=600)
@@ -54,7 +64,7 @@ def leg(argv, cwd, env, warmups, requests):
         walls.append(w); parts.append(stages(out))
     med = {k: statistics.median(p[k] for p in parts) for k, _ in STAGES}
     print("[serve_probe] %s %s: median %.1f ms" % (os.path.basename(argv[0]), argv[3], statistics.median(walls)), file=sys.stderr, flush=True)
-    return dict(first_wall=first_wall, first_out=first_out, wall=statistics.median(walls), wall_min=min(walls), wall_max=max(walls), **med)
+    return dict(first_wall=first_wall, first_out=first_out, wall=statistics.median(walls), wall_min=min(walls), wall_max=max(walls), words=served_words(out), **med)
 
 
 def main():
@@ -102,11 +112,11 @@ def main():
             again = leg([SPZK_CLIENT] + argv(name), d, cenv, a.warmups, a.requests) if len(sizes) > 1 else None
             final = srv.status()
         one = {name: leg([SPZK] + argv(name), d, env, a.warmups, a.requests) for _, _, name, _ in cases}
-        say("| circuit | zkif MB | way | wall ms | zkif_load | setup | of it host objects | prove | verify | rest | of it queue |")
-        say("|---|---|---|---|---|---|---|---|---|---|---|")
-        row = lambda label, mb, way, r: say("| %s | %.0f | %s | %.1f (%.1f – %.1f) | %.1f | %.1f | %.1f | %.2f | %.2f | %.1f | %.1f |" % (
+        say("| circuit | zkif MB | way | wall ms | zkif_load | setup | of it host objects | prove | verify | rest | of it queue | witness/ingest |")
+        say("|---|---|---|---|---|---|---|---|---|---|---|---|")
+        row = lambda label, mb, way, r: say("| %s | %.0f | %s | %.1f (%.1f – %.1f) | %.1f | %.1f | %.1f | %.2f | %.2f | %.1f | %.1f | %s |" % (
             label, mb, way, r["wall"], r["wall_min"], r["wall_max"], r["zkif_load"], r["setup"], r["objs"], r["prove"], r["verify"],
-            r["wall"] - r["zkif_load"] - r["setup"] - r["prove"] - r["verify"], r["queue"]))
+            r["wall"] - r["zkif_load"] - r["setup"] - r["prove"] - r["verify"], r["queue"], r["words"]))
         for k, kind, name, mb in cases:
             row("2^%d %s" % (k, kind), mb, "served", served[name]); row("2^%d %s" % (k, kind), mb, "one-shot", one[name])
         if again:
