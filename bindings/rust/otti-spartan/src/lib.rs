@@ -49,6 +49,13 @@ extern "C" {
     fn otti_witness_from_zkif(inst: *mut OttiInstance, inputs_path: *const c_char, witness_path: *const c_char, mode: i32, out: *mut *mut OttiWitness,
                               inputs_out: *mut *mut c_void) -> i32;
     fn otti_witness_ingest_info(wit: *const OttiWitness, on_device: *mut i32, witness_bytes: *mut u64, ms: *mut f64) -> i32;
+    // whether the host entry lists of an instance exist (a device ingest has none until a host consumer downloads them; asking never does) and their size
+    fn otti_instance_host_lists_info(inst: *const OttiInstance, materialised: *mut i32, host_bytes: *mut u64) -> i32;
+    // kernel-level entries (tests): the decommitment fill from one entry list; a rank's share of an entry list (flag, scan, scatter)
+    fn otti_k_decomm_entries(h_row: *const u32, h_col: *const u32, h_val_mont32: *const u8, n: usize, n_ops: usize, pad_to: usize, pad_col: u32,
+                             out_row_u32: *mut u32, out_col_u32: *mut u32, out_row_fr: *mut u8, out_col_fr: *mut u8, out_val_fr: *mut u8, kernel_ms: *mut f32) -> i32;
+    fn otti_k_shard_filter(h_row: *const u32, h_col: *const u32, h_val_mont32: *const u8, n: usize, world: u32, rank: u32, by_col: i32,
+                           out_row: *mut u32, out_col: *mut u32, out_val: *mut u8, out_n: *mut usize, kernel_ms: *mut f32) -> i32;
     // SNARK mode (upstream spartan-zkinterface without --nizk)
     fn otti_snark_gens_new(num_cons: u64, num_vars: u64, num_inputs: u64, num_nz_entries: u64, out: *mut *mut OttiSnarkGens) -> i32;
     fn otti_snark_gens_free(gens: *mut OttiSnarkGens);

@@ -385,8 +385,9 @@ void    otti_r1cs_free(otti_r1cs *r);
  *                       tables there, map variable ids to columns, validate and convert the coefficients and write the entry lists in file order,
  *                       from which both CSR copies are built as for any instance.  Headers, Witness, Command and unknown messages, the .inp.zkif
  *                       and the .wit.zkif stay on the host.  The instance comes back with its device copy made and WITHOUT host lists: the first
- *                       host consumer (otti_instance_is_sat, a verifier without a device evaluation, SNARK encode, a sharded upload,
- *                       otti_instance_entries) downloads them from the device, once, whichever thread asks.  For that the entry lists stay in HBM
+ *                       host consumer (otti_instance_is_sat, a verifier without a device evaluation, otti_instance_entries) downloads them from
+ *                       the device, once, whichever thread asks; SNARK encode / attach and a sharded upload read the lists where they are
+ *                       (otti_instance_host_lists_info tells whether the download has happened).  For that the entry lists stay in HBM
  *                       beside the CSR copies for the life of the instance: 40 bytes per entry (otti_instance_ingest_info: hbm_entry_bytes).
  *                       Without a device: OTTI_ERR_NO_DEVICE.  Its own limits, all OTTI_ERR_BAD_ARG: a circuit file of 16 GiB and more or more
  *                       than 2^30 constraints (said before the file is parsed, so before any defect of it: the host path says "too large"
@@ -412,6 +413,11 @@ int32_t otti_instance_entries(otti_instance *inst, int32_t which /* 0 A, 1 B, 2 
  * take (0 unless on_device); and a device ingest's four laps in ms: host walk + id map, staging + copies, kernels, CSR build.  Any pointer may be NULL. */
 int32_t otti_instance_ingest_info(const otti_instance *inst, int32_t *on_device, uint64_t *circuit_bytes, uint64_t *hbm_entry_bytes,
                                   double ms[4] /* host walk + id map, staging + copies, kernels, CSR build */);
+/* whether the instance's host entry lists exist: materialised = 1 always for otti_instance_new and the host ingest; for a device ingest only once a
+ * host consumer has downloaded them (otti_instance_is_sat, a verifier without a device evaluation, OTTI_DECOMM_HOST=1, otti_instance_entries — SNARK
+ * encode / attach and a sharded upload read the lists in HBM and do not).  host_bytes: their size, 40 bytes per entry, 0 while absent.  Asking never
+ * triggers the download.  Either out pointer may be NULL; a NULL inst is OTTI_ERR_BAD_ARG. */
+int32_t otti_instance_host_lists_info(const otti_instance *inst, int32_t *materialised, uint64_t *host_bytes);
 /* .inp.zkif + .wit.zkif to a resident witness of `inst`, equal in every observable way (z, inputs, small_fraction, proof bytes) to otti_zkif_load on
  * the instance's three files followed by otti_witness_upload.  It works with every consumer and mutator of a resident witness.
  *   OTTI_INGEST_HOST:   the host loader's frame over the two files (the circuit's share left out), then the upload path.
@@ -456,6 +462,18 @@ int32_t otti_k_fr_op(int32_t op, const uint8_t *h_a, const uint8_t *h_b, uint8_t
 /* sparse_mlpoly.rs AddrTimestamps::new for one side of the dense representation: h_addr3 = three lists of N addresses below M (k-major); walking them
    in order over one shared counter array, h_read_ts3[k * N + i] = audit[addr]++ and h_audit[0 .. M) = the counts at the end */
 int32_t otti_k_addr_timestamps(const uint32_t *h_addr3, size_t N, size_t M, uint32_t *h_read_ts3, uint32_t *h_audit, float *kernel_ms);
+/* one matrix of the SNARK decommitment filled from an entry list as the device does it for an instance whose lists are in HBM (a device ingest):
+   position i < n is entry i; n <= i < pad_to the explicit padding (row i, column pad_col, value zero) upstream writes below two constraints
+   (pad_to = n: none); the rest address 0, value zero.  Outputs of N positions each: the addresses as u32, the same as field elements, the values.
+   Before any device is touched: a null pointer (the lists may be NULL when n = 0), N outside 1 .. 2^28, n > N or pad_to > N is OTTI_ERR_BAD_ARG. */
+int32_t otti_k_decomm_entries(const uint32_t *h_row, const uint32_t *h_col, const uint8_t *h_val_mont32, size_t n, size_t N, size_t pad_to, uint32_t pad_col,
+                              uint32_t *out_row_u32, uint32_t *out_col_u32, uint8_t *out_row_fr, uint8_t *out_col_fr, uint8_t *out_val_fr, float *kernel_ms);
+/* rank's share of an entry list as a sharded prover filters a device-ingested instance (flag, scan, scatter): the entries whose row (by_col != 0:
+   column) is rank mod world, in list order, that index divided by world, the other index and the value untouched.  Outputs have room for n entries;
+   *out_n receives the number selected.  kernel_ms includes the read of the count between scan and scatter.  Before any device is touched: a null
+   pointer (lists and outputs may be NULL when n = 0; out_n never), world not a power of two, rank >= world or n >= 2^32 is OTTI_ERR_BAD_ARG. */
+int32_t otti_k_shard_filter(const uint32_t *h_row, const uint32_t *h_col, const uint8_t *h_val_mont32, size_t n, uint32_t world, uint32_t rank, int32_t by_col,
+                            uint32_t *out_row, uint32_t *out_col, uint8_t *out_val, size_t *out_n, float *kernel_ms);
 /* canonical LE <-> Montgomery on the device */
 int32_t otti_k_fr_from_canonical(const uint8_t *h_in, uint8_t *h_out, size_t n);
 int32_t otti_k_fr_to_canonical(const uint8_t *h_in, uint8_t *h_out, size_t n);

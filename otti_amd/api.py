@@ -159,6 +159,9 @@ _sig("otti_instance_device_info", _i32, _vp, _i32, ctypes.POINTER(_DeviceInfo))
 _sig("otti_instance_from_zkif", _i32, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, _i32, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.POINTER(_R1CS)))
 _sig("otti_instance_entries", _i32, _vp, _i32, _vp, _sz, ctypes.POINTER(_sz))
 _sig("otti_instance_ingest_info", _i32, _vp, ctypes.POINTER(_i32), ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(ctypes.c_double))
+_sig("otti_instance_host_lists_info", _i32, _vp, ctypes.POINTER(_i32), ctypes.POINTER(_u64))
+_sig("otti_k_decomm_entries", _i32, _vp, _vp, _vp, _sz, _sz, _sz, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _fp)
+_sig("otti_k_shard_filter", _i32, _vp, _vp, _vp, _sz, ctypes.c_uint32, ctypes.c_uint32, _i32, _vp, _vp, _vp, ctypes.POINTER(_sz), _fp)
 INGEST_MODES = {"auto": 0, "host": 1, "device": 2}             # OTTI_INGEST_*
 _sig("otti_witness_from_zkif", _i32, _vp, ctypes.c_char_p, ctypes.c_char_p, _i32, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.POINTER(_R1CS)))
 _sig("otti_witness_ingest_min_mb", ctypes.c_double)
@@ -337,6 +340,13 @@ class Instance:
         on, cb, hb, ms = _i32(), _u64(), _u64(), (ctypes.c_double * 4)()
         _check(lib.otti_instance_ingest_info(self._h, ctypes.byref(on), ctypes.byref(cb), ctypes.byref(hb), ms))
         return dict(on_device=bool(on.value), circuit_bytes=cb.value, hbm_entry_bytes=hb.value, ms=tuple(ms))
+
+    def host_lists_info(self):
+        """otti_instance_host_lists_info: dict of materialised (the host entry lists exist: always for Instance.new; for a device ingest only once a
+        host consumer has downloaded them) and host_bytes (their size, 0 while absent).  Asking never triggers the download."""
+        m, hb = _i32(), _u64()
+        _check(lib.otti_instance_host_lists_info(self._h, ctypes.byref(m), ctypes.byref(hb)))
+        return dict(materialised=bool(m.value), host_bytes=hb.value)
 
     @property
     def dims(self):
@@ -1102,6 +1112,36 @@ class kernels:
         ts, audit, ms = np.zeros_like(a), np.zeros(int(M), dtype=np.uint32), ctypes.c_float(0)
         _check(lib.otti_k_addr_timestamps(_ptr(a), a.shape[1], int(M), _ptr(ts), _ptr(audit), ctypes.byref(ms)))
         return ts, audit, ms.value
+
+    @staticmethod
+    def decomm_entries(row, col, val, N, pad_to=None, pad_col=0):
+        """otti_k_decomm_entries: one matrix of the SNARK decommitment from an entry list (row, col: uint32; val: (n, 32) Montgomery).  pad_to: the
+        explicit padding's end (None: n, no padding).  Returns (row_u32 (N,), col_u32 (N,), row_fr, col_fr, val_fr ((N, 32) each), kernel ms)"""
+        row, col = np.ascontiguousarray(row, dtype=np.uint32), np.ascontiguousarray(col, dtype=np.uint32)
+        val = _scalars(val, "val") if len(val) else np.zeros((0, 32), dtype=np.uint8)
+        n, N = row.size, int(N)
+        if col.size != n or val.shape[0] != n:
+            raise ValueError("row, col and val: one length")
+        ru, cu = np.zeros(max(N, 0), dtype=np.uint32), np.zeros(max(N, 0), dtype=np.uint32)
+        fr = [np.zeros((max(N, 0), 32), dtype=np.uint8) for _ in range(3)]; ms = ctypes.c_float(0)
+        _check(lib.otti_k_decomm_entries(_ptr(row) if n else None, _ptr(col) if n else None, _ptr(val) if n else None, n, N, n if pad_to is None else int(pad_to), int(pad_col),
+                                         _ptr(ru), _ptr(cu), _ptr(fr[0]), _ptr(fr[1]), _ptr(fr[2]), ctypes.byref(ms)))
+        return ru, cu, fr[0], fr[1], fr[2], ms.value
+
+    @staticmethod
+    def shard_filter(row, col, val, world, rank, by_col=False):
+        """otti_k_shard_filter: rank's share of an entry list, in order, the row (by_col: column) divided by world.  Returns (row, col, val, kernel ms)"""
+        row, col = np.ascontiguousarray(row, dtype=np.uint32), np.ascontiguousarray(col, dtype=np.uint32)
+        val = _scalars(val, "val") if len(val) else np.zeros((0, 32), dtype=np.uint8)
+        n = row.size
+        if col.size != n or val.shape[0] != n:
+            raise ValueError("row, col and val: one length")
+        orow, ocol, oval = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32), np.zeros((n, 32), dtype=np.uint8)
+        cnt, ms = _sz(), ctypes.c_float(0)
+        p = (lambda a: _ptr(a) if n else None)
+        _check(lib.otti_k_shard_filter(p(row), p(col), p(val), n, int(world), int(rank), 1 if by_col else 0, p(orow), p(ocol), p(oval), ctypes.byref(cnt), ctypes.byref(ms)))
+        k = cnt.value
+        return orow[:k].copy(), ocol[:k].copy(), oval[:k].copy(), ms.value
 
     @staticmethod
     def from_canonical(a):

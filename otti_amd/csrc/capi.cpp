@@ -593,6 +593,19 @@ int32_t otti_instance_ingest_info(const otti_instance *inst, int32_t *on_device,
         return OTTI_OK;
     });
 }
+int32_t otti_instance_host_lists_info(const otti_instance *inst, int32_t *materialised, uint64_t *host_bytes) {
+    return guarded([&] {
+        if (!inst) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        const Instance &I = *inst->I;
+        const bool have = I.host_lists_materialised();         // (asks, never downloads)
+        if (materialised) *materialised = have ? 1 : 0;
+        if (host_bytes) {
+            *host_bytes = 0;
+            if (have) for (int k = 0; k < 3; k++) *host_bytes += (uint64_t)I.M[k].val.size() * 40;
+        }
+        return OTTI_OK;
+    });
+}
 // ---- the inputs and witness files to a resident witness (zkif.h, k_wit_ingest.hip).  The ladder of otti_instance_from_zkif: the arguments, the
 // files' readability, a missing device — said in every mode: a resident witness lives on one —, then the files; *out and *inputs_out are written last.
 static double wit_min_mb() {

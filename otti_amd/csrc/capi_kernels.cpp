@@ -85,6 +85,42 @@ int32_t otti_k_addr_timestamps(const uint32_t *h_addr3, size_t N, size_t M, uint
         c.sync(); return OTTI_OK;
     });
 }
+// the decommitment fill from entry lists (snark_prover.cpp decomm_fill_from_entries) on one matrix of a caller's host lists
+int32_t otti_k_decomm_entries(const uint32_t *h_row, const uint32_t *h_col, const uint8_t *h_val_mont32, size_t n, size_t N, size_t pad_to, uint32_t pad_col,
+                              uint32_t *out_row_u32, uint32_t *out_col_u32, uint8_t *out_row_fr, uint8_t *out_col_fr, uint8_t *out_val_fr, float *ms) {
+    return guarded([&] {
+        if ((n && (!h_row || !h_col || !h_val_mont32)) || !out_row_u32 || !out_col_u32 || !out_row_fr || !out_col_fr || !out_val_fr) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (N < 1 || N > ((size_t)1 << 28) || n > N || pad_to > N) throw Error(OTTI_ERR_BAD_ARG, "decommitment fill: N outside 1 .. 2^28, or n or pad_to above N");
+        const size_t len = std::max(n, pad_to);
+        DevCtx &c = DevCtx::get();
+        DevBuf<uint32_t> row(std::max<size_t>(1, n)), col(std::max<size_t>(1, n)), ra(N), ca(N); Staged val(c, h_val_mont32, n); DevBuf<Fr> fr(3 * N);
+        if (n) { OTTI_HIP(hipMemcpyAsync(row.p, h_row, n * 4, hipMemcpyHostToDevice, c.stream)); OTTI_HIP(hipMemcpyAsync(col.p, h_col, n * 4, hipMemcpyHostToDevice, c.stream)); }
+        DecommFill f{}; f.m[0] = DecommFillMat{row.p, col.p, val.d.p, ra.p, ca.p, fr.p, fr.p + N, fr.p + 2 * N, n, len, pad_col};
+        KTimer t(c, ms); dev_decomm_fill(c, f, 1, N); t.stop();
+        OTTI_HIP(hipMemcpyAsync(out_row_u32, ra.p, N * 4, hipMemcpyDeviceToHost, c.stream)); OTTI_HIP(hipMemcpyAsync(out_col_u32, ca.p, N * 4, hipMemcpyDeviceToHost, c.stream));
+        download(c, out_row_fr, fr.p, N); download(c, out_col_fr, fr.p + N, N); download(c, out_val_fr, fr.p + 2 * N, N);
+        c.sync(); return OTTI_OK;
+    });
+}
+// a rank's share of an entry list (k_sparse.hip dev_shard_filter, what upload_instance_shard runs on a device-ingested instance) on a caller's host lists
+int32_t otti_k_shard_filter(const uint32_t *h_row, const uint32_t *h_col, const uint8_t *h_val_mont32, size_t n, uint32_t world, uint32_t rank, int32_t by_col,
+                            uint32_t *out_row, uint32_t *out_col, uint8_t *out_val, size_t *out_n, float *ms) {
+    return guarded([&] {
+        if (!out_n || (n && (!h_row || !h_col || !h_val_mont32 || !out_row || !out_col || !out_val))) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (world < 1 || (world & (world - 1)) || world > (1u << 30) || rank >= world || n >= ((size_t)1 << 32)) throw Error(OTTI_ERR_BAD_ARG, "shard filter: world must be a power of two above the rank, the list below 2^32 entries");
+        DevCtx &c = DevCtx::get();
+        DevBuf<uint32_t> row(std::max<size_t>(1, n)), col(std::max<size_t>(1, n)), flags; Staged val(c, h_val_mont32, n);
+        std::vector<DevBuf<uint32_t>> levels; levels.reserve(4);
+        if (n) { OTTI_HIP(hipMemcpyAsync(row.p, h_row, n * 4, hipMemcpyHostToDevice, c.stream)); OTTI_HIP(hipMemcpyAsync(col.p, h_col, n * 4, hipMemcpyHostToDevice, c.stream)); }
+        DeviceCoo out;
+        KTimer t(c, ms); dev_shard_filter(c, row.p, col.p, val.d.p, n, (int)world, (int)rank, by_col != 0, out, flags, levels); t.stop();   // (the read of the count in between included)
+        if (out.n) {
+            OTTI_HIP(hipMemcpyAsync(out_row, out.row.p, out.n * 4, hipMemcpyDeviceToHost, c.stream)); OTTI_HIP(hipMemcpyAsync(out_col, out.col.p, out.n * 4, hipMemcpyDeviceToHost, c.stream));
+            download(c, out_val, out.val.p, out.n);
+        }
+        c.sync(); *out_n = out.n; return OTTI_OK;
+    });
+}
 int32_t otti_k_fr_from_canonical(const uint8_t *in, uint8_t *out, size_t n) {
     return guarded([&] { DevCtx &c = DevCtx::get(); Staged A(c, in, n); dev_from_canonical(c, A.d.p, A.d.p, n); download(c, out, A.d.p, n); c.sync(); return OTTI_OK; });
 }

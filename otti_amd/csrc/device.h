@@ -62,6 +62,11 @@ bool device_runtime_up();                                   // a device context 
 // low-bit-sharded phase-one tables need it) and, as a second copy, the entries of columns c = k (mod g) (renumbered c / g, rows
 // untouched: compute_eval_table_sparse output lands where the phase-two tables need it).  SURVEY.md 8(e).
 struct DeviceShard { int rank = 0, world = 1; DeviceCsrSet by_row, by_col; };
+// rank's share of an entry list that is in HBM (k_sparse.hip: flag, scan_inplace, scatter): the entries whose row (by_col: column) is rank mod world,
+// in list order, that index divided by world, the other one and the value untouched.  out: n and buffers of max(1, n) elements, no codes.  flags and
+// scan_levels are scratch that grows and may be handed to the next call; the scatter is only queued.
+void dev_shard_filter(DevCtx &c, const uint32_t *row, const uint32_t *col, const Fr *val, size_t n, int world, int rank, bool by_col, DeviceCoo &out,
+                      DevBuf<uint32_t> &flags, std::vector<DevBuf<uint32_t>> &scan_levels);
 
 // fixed-base window table: entry (base b, window w, digit d in 1..E) = d * 2^(c*w) * P[b] in affine Niels form
 struct DeviceGens {

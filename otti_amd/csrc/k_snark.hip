@@ -33,6 +33,29 @@ void dev_u32_to_fr(DevCtx &c, const uint32_t *in, Fr *out, size_t n) {
     if (n) hipLaunchKernelGGL(k_u32_to_fr, grid_for(n), kBlock, 0, c.stream, in, out, n);
 }
 
+// The decommitment's addresses and values straight from entry lists that are in HBM already (a device ingest keeps them: device.h DeviceInstance::ent),
+// one launch for the matrices of f (grid.y): position i < nv is entry i, nv <= i < len the explicit padding upstream writes below two constraints
+// (row i, column pad_col, value zero), the rest address 0 and value zero.  Every element of the five outputs is written: nothing is zeroed beforehand.
+// A streaming pass: 40 bytes read per entry, 104 written per position, the 32-byte elements as two 16-byte accesses (Fr is 16-byte aligned).
+__global__ __launch_bounds__(kBlock) void k_decomm_fill(DecommFill f, size_t N) {
+    const DecommFillMat m = f.m[blockIdx.y];
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < N; i += (size_t)gridDim.x * blockDim.x) {
+        uint32_t r = 0, cl = 0; Fr v = fr_zero();
+        if (i < m.nv) { r = m.row[i]; cl = m.col[i]; v = m.val[i]; }
+        else if (i < m.len) { r = (uint32_t)i; cl = m.pad_col; }
+        m.row_addr[i] = r; m.col_addr[i] = cl;
+        m.row_fr[i] = r ? fr_from_u64((uint64_t)r) : fr_zero();
+        m.col_fr[i] = cl ? fr_from_u64((uint64_t)cl) : fr_zero();
+        m.val_fr[i] = v;
+    }
+}
+void dev_decomm_fill(DevCtx &c, const DecommFill &f, int count, size_t N) {
+    if (count < 1 || count > 3 || !N) throw Error(OTTI_ERR_INTERNAL, "decommitment fill: one to three matrices, at least one position");
+    for (int k = 0; k < count; k++) if (f.m[k].nv > f.m[k].len || f.m[k].len > N) throw Error(OTTI_ERR_INTERNAL, "decommitment fill: lengths out of order");
+    const unsigned gx = (unsigned)std::max<size_t>(1, std::min<size_t>((N + kBlock - 1) / kBlock, (size_t)kMaxBlocks / (size_t)count));   // never a zero grid
+    hipLaunchKernelGGL(k_decomm_fill, dim3(gx, (unsigned)count), kBlock, 0, c.stream, f, N);
+}
+
 // ------------------------------------------------------------------------------------------------ timestamps of the dense representation
 // sparse_mlpoly.rs AddrTimestamps::new on the device (snark_dev.h AddrTs): read_ts of an entry = how many entries with the same address come
 // before it in the walk over the three lists, audit_ts = how many there are.  A stable LSD radix sort (8-bit digits) of the entries' walk

@@ -547,6 +547,40 @@ std::shared_ptr<DeviceInstance> upload_instance(const Instance &I) {
     return d;
 }
 
+// ------------------------------------------------------------------------------------------------ a rank's share of an entry list that is in HBM
+// A stable stream compaction: FLAG the entries whose key (row, or column) is k mod g, scan_inplace the flags, SCATTER every flagged entry to its
+// scanned position with the key renumbered key / g.  g is a power of two: mask and shift.  File order is kept, as the host loop keeps it.  The
+// count comes back with one copy behind the scan, the outputs are allocated to it, and the scatter's positions (1 .. count, less one) lie inside
+// them whatever the lists hold.  A streaming pass of about 100 bytes per entry that stays.
+__global__ __launch_bounds__(kBlock) void k_shard_flag(const uint32_t *key, size_t n, uint32_t mask, uint32_t k, uint32_t *flag) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) flag[i] = (key[i] & mask) == k ? 1u : 0u;
+}
+__global__ __launch_bounds__(kBlock) void k_shard_scatter(const uint32_t *row, const uint32_t *col, const Fr *val, size_t n, uint32_t mask, uint32_t k, int shift, int by_col,
+                                                          const uint32_t *incl, uint32_t *out_row, uint32_t *out_col, Fr *out_val) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const uint32_t r = row[i], cl = col[i];
+        if (((by_col ? cl : r) & mask) != k) continue;
+        const uint32_t p = incl[i] - 1u;                      // this entry's own flag is in the sum: at least 1
+        out_row[p] = by_col ? r : r >> shift; out_col[p] = by_col ? cl >> shift : cl; out_val[p] = val[i];
+    }
+}
+void dev_shard_filter(DevCtx &c, const uint32_t *row, const uint32_t *col, const Fr *val, size_t n, int world, int rank, bool by_col, DeviceCoo &out,
+                      DevBuf<uint32_t> &flags, std::vector<DevBuf<uint32_t>> &scan_levels) {
+    if (world < 1 || (world & (world - 1)) || rank < 0 || rank >= world || n >= ((size_t)1 << 32)) throw Error(OTTI_ERR_BAD_ARG, "shard filter: world must be a power of two above the rank, the list below 2^32 entries");
+    const uint32_t mask = (uint32_t)world - 1u, k = (uint32_t)rank; const int shift = (int)ilog2((size_t)world);
+    uint32_t count = 0;
+    if (n) {
+        if (flags.n < n) { OTTI_HIP(hipStreamSynchronize(c.stream)); flags.alloc(n); }
+        hipLaunchKernelGGL(k_shard_flag, grid_for(n), kBlock, 0, c.stream, by_col ? col : row, n, mask, k, flags.p);
+        scan_inplace(c, flags.p, n, scan_levels);
+        OTTI_HIP(hipMemcpyAsync(&count, flags.p + (n - 1), 4, hipMemcpyDeviceToHost, c.stream));
+        OTTI_HIP(hipStreamSynchronize(c.stream));
+    }
+    out.n = count;                                            // an empty selection: n = 0 with one-element buffers, as upload_coo leaves an empty list
+    out.row.alloc(std::max<size_t>(1, out.n)); out.col.alloc(std::max<size_t>(1, out.n)); out.val.alloc(std::max<size_t>(1, out.n));
+    if (count) hipLaunchKernelGGL(k_shard_scatter, grid_for(n), kBlock, 0, c.stream, row, col, val, n, mask, k, shift, by_col ? 1 : 0, (const uint32_t *)flags.p, out.row.p, out.col.p, out.val.p);
+}
+
 std::shared_ptr<DeviceShard> upload_instance_shard(const Instance &I, int rank, int world) {
     DevCtx &c = DevCtx::get();
     if (world < 1 || (world & (world - 1)) || rank < 0 || rank >= world || (size_t)world > I.num_cons || (size_t)world > 2 * I.num_vars)
@@ -556,7 +590,19 @@ std::shared_ptr<DeviceShard> upload_instance_shard(const Instance &I, int rank, 
     const uint32_t g = (uint32_t)world, k = (uint32_t)rank;
     // rows r = k (mod g) renumbered r / g, columns untouched; and the entries of columns c = k (mod g) renumbered c / g, rows untouched
     DeviceCoo rows[3], cols[3];
-    for (int m = 0; m < 3; m++) {
+    // an instance ingested on the device keeps its entry lists in HBM (DeviceInstance::ent): its share is filtered there, and mat() is never asked
+    const std::shared_ptr<DeviceInstance> di = I.ingested_on_device ? I.dev : nullptr;
+    bool resident = di != nullptr;
+    for (int m = 0; m < 3 && resident; m++) resident = di->ent[m].n == I.nnz[m];
+    if (resident) {
+        DevBuf<uint32_t> flags; std::vector<DevBuf<uint32_t>> scan_levels; scan_levels.reserve(4);
+        for (int m = 0; m < 3; m++) {
+            const DeviceCoo &e = di->ent[m];
+            dev_shard_filter(c, e.row.p, e.col.p, e.val.p, e.n, world, rank, false, rows[m], flags, scan_levels);
+            dev_shard_filter(c, e.row.p, e.col.p, e.val.p, e.n, world, rank, true, cols[m], flags, scan_levels);
+        }
+        OTTI_HIP(hipStreamSynchronize(c.stream));             // the flags and the scan's scratch go out of scope
+    } else for (int m = 0; m < 3; m++) {                      // host lists: the filter as a loop over them, the shares uploaded
         const SparseMat &M = I.mat(m);
         std::vector<uint32_t> rr, rc, cr, cc; std::vector<Fr> rv, cv;
         for (size_t e = 0; e < M.val.size(); e++) {

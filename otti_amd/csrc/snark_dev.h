@@ -41,6 +41,12 @@ unsigned long long dev_pc_tail(DevCtx &c, const PcList &L, int W, size_t len0, s
 
 void dev_gather(DevCtx &c, const Fr *table, const uint32_t *idx, Fr *out, size_t n);
 void dev_u32_to_fr(DevCtx &c, const uint32_t *in, Fr *out, size_t n);        // out[i] = in[i] as a field element (Montgomery form)
+// ---- the decommitment's address and value parts from entry lists in HBM (k_snark.hip k_decomm_fill), `count` matrices in one launch.  Per matrix:
+// nv entries (row, col, val), then the explicit padding (i, pad_col, 0) up to len, then zeros up to N; nv <= len <= N.  Outputs of N elements each:
+// the addresses as u32 and as field elements (Montgomery form), the values.  Only queues.
+struct DecommFillMat { const uint32_t *row, *col; const Fr *val; uint32_t *row_addr, *col_addr; Fr *row_fr, *col_fr, *val_fr; size_t nv, len; uint32_t pad_col; };
+struct DecommFill { DecommFillMat m[3]; };
+void dev_decomm_fill(DevCtx &c, const DecommFill &f, int count, size_t N);
 // ---- sparse_mlpoly.rs AddrTimestamps::new for one side (rows) or both (rows, columns) of the dense representation, in one run of launches.
 // Per side three address lists of N entries with values below M; walking k = 0, 1, 2 and i = 0 .. N - 1 in order over ONE counter array shared by
 // the three lists, read_ts[k][i] = audit[addr[k][i]]++.  Entries at and beyond len[k] (the same on both sides) must be address 0: they are not

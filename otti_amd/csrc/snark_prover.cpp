@@ -163,13 +163,49 @@ void decomm_fill_device(DevCtx &c, const Instance &I, DeviceDecomm *dec, EncodeL
     }
     lap("address / timestamp sort (device)");
 }
+// the same from the entry lists a device ingest keeps in HBM (DeviceInstance::ent): one launch writes addresses, their field elements and the
+// values of all three matrices, padding included — nothing crosses PCIe and Instance::mat() is never asked
+bool decomm_entries_resident(const Instance &I) {
+    // (only a device ingest keeps lists, and its `dev` is set before the instance is shared: no other instance's `dev`, which a prover
+    // thread may be setting right now, is looked at)
+    if (!I.ingested_on_device || !I.dev || I.nnz[0] + I.nnz[1] + I.nnz[2] == 0) return false;
+    for (int k = 0; k < 3; k++) if (I.dev->ent[k].n != I.nnz[k]) return false;
+    return true;
+}
+void decomm_fill_from_entries(DevCtx &c, const Instance &I, DeviceDecomm *dec, EncodeLaps &lap) {
+    const size_t N = dec->N, M = dec->M;
+    const std::shared_ptr<DeviceInstance> d = I.dev;          // (kept alive across the launches)
+    AddrTs a; a.sides = 2; a.N = N; a.M = M;
+    DecommFill f{};
+    OTTI_HIP(hipMemsetAsync(dec->comb_ops.p + 15 * N, 0, N * sizeof(Fr), c.stream));          // the unused sixteenth part
+    for (int k = 0; k < 3; k++) {
+        const size_t nv = I.nnz[k], len = (I.given_cons < 2 && I.num_cons > nv) ? I.num_cons : nv;
+        a.len[k] = (uint32_t)len;
+        f.m[k] = DecommFillMat{d->ent[k].row.p, d->ent[k].col.p, d->ent[k].val.p, dec->row_addr[k].p, dec->col_addr[k].p, dec->part(0, k), dec->part(2, k),
+                               dec->part(4, k), nv, len, (uint32_t)I.num_vars};
+        a.addr[0][k] = dec->row_addr[k].p; a.addr[1][k] = dec->col_addr[k].p;
+        for (int side = 0; side < 2; side++) a.ts_fr[side][k] = dec->part(2 * side + 1, k);
+    }
+    dev_decomm_fill(c, f, 3, N);
+    for (int side = 0; side < 2; side++) a.audit_fr[side] = dec->comb_mem.p + (size_t)side * M;
+    lap("entry lists: upload + expansion");
+    if (lap.on) OTTI_HIP(hipEventRecord(c.ev0, c.stream));
+    dev_addr_timestamps(c, a);                                // returns with the stream idle
+    if (lap.on) {
+        float ms = 0; OTTI_HIP(hipEventRecord(c.ev1, c.stream)); OTTI_HIP(hipEventSynchronize(c.ev1)); OTTI_HIP(hipEventElapsedTime(&ms, c.ev0, c.ev1));
+        fprintf(stderr, "[otti] snark_encode %-34s %.3f ms\n", "dev_addr_timestamps (events)", (double)ms);
+    }
+    lap("address / timestamp sort (device)");
+}
 // MultiSparseMatPolynomialAsDense in HBM: what SNARK::encode keeps as the decommitment and what attach rebuilds
 std::shared_ptr<DeviceDecomm> build_decomm(DevCtx &c, const Instance &I, size_t N, size_t M, EncodeLaps &lap) {
     auto dec = std::make_shared<DeviceDecomm>(); dec->N = N; dec->M = M;
     dec->comb_ops.alloc(16 * N); dec->comb_mem.alloc(2 * M);
     for (int k = 0; k < 3; k++) { dec->row_addr[k].alloc(N); dec->col_addr[k].alloc(N); }
     static const bool host_scans = [] { const char *e = getenv("OTTI_DECOMM_HOST"); return e && e[0] == '1'; }();
-    if (host_scans) decomm_fill_host(c, I, dec.get(), lap); else decomm_fill_device(c, I, dec.get(), lap);
+    if (host_scans) decomm_fill_host(c, I, dec.get(), lap);
+    else if (decomm_entries_resident(I)) decomm_fill_from_entries(c, I, dec.get(), lap);
+    else decomm_fill_device(c, I, dec.get(), lap);
     return dec;
 }
 }  // namespace

@@ -3,6 +3,7 @@
 // Mirrors upstream libspartan's public API for this path [RECALL lib.rs: Instance, VarsAssignment, InputsAssignment,
 // NIZKGens, NIZK::{prove,verify}], reached from `spzk verify --nizk` [REF /root/reference/run.py:58, run.py:100].
 #pragma once
+#include <atomic>
 #include <functional>
 #include <stdint.h>
 #include <stddef.h>
@@ -48,6 +49,8 @@ struct Instance {
     bool host_lists_pending = false;                        // set once, before the instance is shared; never cleared (call_once is the gate)
     mutable std::once_flag host_lists_once;
     void materialise_host_lists() const;
+    mutable std::atomic<bool> host_lists_done{false};       // set behind the download (otti_instance_host_lists_info: asking never triggers it)
+    bool host_lists_materialised() const { return !host_lists_pending || host_lists_done.load(std::memory_order_acquire); }
     // how the instance came to be (otti_instance_ingest_info): the circuit file's size and the four laps of a device ingest
     bool ingested_on_device = false; uint64_t circuit_bytes = 0; double ingest_ms[4] = {0, 0, 0, 0};
     std::shared_ptr<DeviceInstance> dev;                    // uploaded lazily on the first GPU prove

@@ -67,6 +67,7 @@ void Instance::materialise_host_lists() const {
     SparseMat lists[3];                                      // filled whole before a reader can see any of it: a failed download leaves M empty for the retry
     g_instance_host_lists_hook(*this, lists);
     for (int k = 0; k < 3; k++) M[k] = std::move(lists[k]);
+    host_lists_done.store(true, std::memory_order_release);
 }
 
 std::vector<Fr> eq_evals_host(const Fr *r, size_t ell) {

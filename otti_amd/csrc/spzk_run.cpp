@@ -116,21 +116,34 @@ static bool write_file(const RunEnv &E, const char *path, const uint8_t *p, size
 }
 
 // ---- SNARK mode, one role per process.  role 'e': encode, 'p': prove, 'v': verify.  Returns the exit status.
-struct SnarkRoleArgs { char role; std::vector<const char *> files; const char *comm_in, *comm_out, *proof_in, *proof_out, *label; const uint8_t *seed; bool check, verify_comm; };
-// A SERVED request in NIZK mode takes the files to a ready instance in one call (otti_instance_from_zkif, OTTI_INGEST_AUTO: on the device when the
-// circuit's size allows — the worker's runtime is up).  The one-shot keeps the host path (it parses while its HIP runtime comes up), and so does SNARK
-// mode (it needs the host lists at once).  Returns 1: taken; 0: not taken, or the FILES were refused (the three codes a loader gives a file: the
+struct SnarkRoleArgs { char role; std::vector<const char *> files; const char *comm_in, *comm_out, *proof_in, *proof_out, *label; const uint8_t *seed; bool check, verify_comm; double t_main0; };
+// A SERVED request, in NIZK and in SNARK mode alike, takes the files to a ready instance in one call (otti_instance_from_zkif, OTTI_INGEST_AUTO: on the
+// device when the circuit's size allows — the worker's runtime is up).  SNARK encode / attach fill the decommitment from the entry lists the device
+// ingest keeps in HBM (snark_prover.cpp decomm_fill_from_entries): no host lists are made for them.  The one-shot keeps the host path (it parses
+// while its HIP runtime comes up).  After a device ingest the assignment's A, B, C are NULL: only their counts are set.
+// SNARK requests take it from kServedSnarkMinMB MiB of circuit file on only: measured (profiles/snark_zkif_ingest.md, tools/snark_ingest_probe.py), a
+// served `prove --comm-in` of the smallest probed circuit (2^16 uniform, 15.2 MiB) came out slower than the parent's host path at the median (39.7
+// against 20.4 ms: a 22 - 28 ms wait in the ingest's first allocations behind the previous proof's frees, the one profiles/zkif_ingest.md describes),
+// while from the next probed size (2^16 compiler-like, 43.9 MiB) on both requests beat it.  OTTI_INGEST_SNARK_MIN_MB (MiB, read per request)
+// overrides it; with OTTI_INGEST_MIN_MB set and that one not, the general cut-over alone decides.
+// Returns 1: taken; 0: not taken, or the FILES were refused (the three codes a loader gives a file: the
 // caller then goes the host path, which words such a refusal stage by stage exactly as the one-shot does); any other failure — no device, no
 // memory, a HIP error — is the request's failure and comes back as its negative code: nothing is parsed a second time behind it.
+constexpr double kServedSnarkMinMB = 43.0;
+static double served_snark_min_mb() {
+    if (const char *e = getenv("OTTI_INGEST_SNARK_MIN_MB")) { char *end = nullptr; const double v = strtod(e, &end); if (end != e && v >= 0) return v; }
+    return getenv("OTTI_INGEST_MIN_MB") ? 0.0 : kServedSnarkMinMB;
+}
 static int served_ingest(const RunEnv &E, bool nizk, const std::string &circuit, const std::string &inputs, const char *witness, otti_instance **inst, otti_r1cs **r,
                          otti_witness **wit = nullptr) {
-    if (!E.served || !nizk) return 0;
+    if (!E.served) return 0;
+    struct stat st;
+    if (!nizk && (stat(circuit.c_str(), &st) != 0 || (double)st.st_size < served_snark_min_mb() * 1048576.0)) return 0;
     // A prove request (wit given) whose witness file AUTO would read on the device: the circuit without the witness file — the call returns the public
     // inputs —, then the two files to a resident witness (otti_witness_from_zkif), which the proof is made from.  A refusal of the FILES by either call
     // — for the second also: files of other dimensions than the circuit's, and a worker without a device, which the host path words as the one-shot
     // does — leaves nothing behind and goes the host path.
     // A smaller witness file is parsed with the circuit and uploaded by the proof, as ever (profiles/zkif_witness_ingest.md: why the request looks itself).
-    struct stat st;
     const bool resident = wit && stat(witness, &st) == 0 && (double)st.st_size >= otti_witness_ingest_min_mb() * 1048576.0;
     int rc = otti_instance_from_zkif(circuit.c_str(), inputs.c_str(), resident ? nullptr : witness, OTTI_INGEST_AUTO, inst, r);
     if (rc == OTTI_OK && resident) {
@@ -147,6 +160,12 @@ static const char *witness_word(const otti_witness *wit) {
 static const char *ingest_word(const otti_instance *inst) {
     int32_t on_device = 0;
     return otti_instance_ingest_info(inst, &on_device, nullptr, nullptr, nullptr) == OTTI_OK && on_device ? "device" : "host";
+}
+// the one line in which a served request's stdout differs from the one-shot's: how the request was served / what the process's start cost
+static void origin_line(const RunEnv &E, const otti_witness *wit, const otti_instance *inst, double t_main0) {
+    if (E.served) fprintf(E.out, "* served: queue %.3f ms, generators %s, table %s, witness %s, ingest %s\n", E.queue_ms, E.gens->gens_word(), E.gens->table_word(), witness_word(wit),
+                          ingest_word(inst));
+    else fprintf(E.out, "* process start to main() %.0f ms (the dynamic loader mapping the HIP runtime), main() %.3f ms\n", E.t_before_main, now_ms() - t_main0);
 }
 static int snark_role(const RunEnv &E, const SnarkRoleArgs &a) {
     int rc; double t0 = now_ms(); Frees fr(E);
@@ -167,16 +186,20 @@ static int snark_role(const RunEnv &E, const SnarkRoleArgs &a) {
         fprintf(E.out, "Verification successful\n");
         return 0;
     }
-    otti_r1cs *r = nullptr;
+    otti_r1cs *r = nullptr; otti_instance *inst = nullptr;
+    otti_witness *wit = nullptr;                               // a served prove request whose witness file went straight to HBM; --check: uploaded below
     {
         const std::string f0 = at(E, a.files[0]), f1 = at(E, a.files.size() > 1 ? a.files[1] : nullptr), f2 = at(E, a.role == 'p' ? a.files[2] : nullptr);
-        rc = otti_zkif_load(f0.c_str(), a.files.size() > 1 ? f1.c_str() : nullptr, a.role == 'p' ? f2.c_str() : nullptr, &r); if (rc) return fail(E, "zkif load", rc);
+        // (an encode request may name the circuit alone: the one-call ingest wants the inputs file as well, so that one goes the host path)
+        const int took = a.files.size() > 1 ? served_ingest(E, false, f0, f1, a.role == 'p' ? f2.c_str() : nullptr, &inst, &r, a.role == 'p' ? &wit : nullptr) : 0;
+        if (took < 0) return fail(E, "zkif ingest", took);
+        if (!took) { rc = otti_zkif_load(f0.c_str(), a.files.size() > 1 ? f1.c_str() : nullptr, a.role == 'p' ? f2.c_str() : nullptr, &r); if (rc) return fail(E, "zkif load", rc); }
     }
     fr.add([=] { otti_r1cs_free(r); });
     const double t_load = now_ms() - t0; t0 = now_ms();
-    otti_instance *inst = nullptr;
-    rc = otti_instance_new(r->num_cons, r->num_vars, r->num_inputs, r->A, r->nA, r->B, r->nB, r->C, r->nC, &inst); if (rc) return fail(E, "Instance::new", rc);
+    if (!inst) { rc = otti_instance_new(r->num_cons, r->num_vars, r->num_inputs, r->A, r->nA, r->B, r->nB, r->C, r->nC, &inst); if (rc) return fail(E, "Instance::new", rc); }
     fr.add([=] { otti_instance_free(inst); });
+    if (wit) fr.add([=] { otti_witness_free(wit); });
     const uint64_t nnz = std::max<uint64_t>({(uint64_t)r->nA, (uint64_t)r->nB, (uint64_t)r->nC});
     otti_snark_gens *sg = nullptr; rc = E.gens->snark_gens(r->num_cons, r->num_vars, r->num_inputs, nnz, &sg); if (rc) return fail(E, "SNARKGens::new", rc);
     const double t_setup = now_ms() - t0; t0 = now_ms();
@@ -197,16 +220,18 @@ static int snark_role(const RunEnv &E, const SnarkRoleArgs &a) {
         fr.add([=] { otti_comp_comm_free(cc); });
         uint8_t *cb = nullptr; size_t cb_len = 0; rc = otti_comp_comm_bytes(cc, &cb, &cb_len); if (rc) return fail(E, "commitment bytes", rc);
         fprintf(E.out, "* SNARK::encode %.3f ms (computation commitment %zu bytes)\n", now_ms() - t0, cb_len);
+        if (a.role == 'e') origin_line(E, nullptr, inst, a.t_main0);
         if (a.comm_out && !write_file(E, a.comm_out, cb, cb_len)) { if (E.served) otti_buf_free(cb); return 1; }
         if (a.comm_out) fprintf(E.out, "Commitment written to %s (%zu bytes)\n", a.comm_out, cb_len);
         otti_buf_free(cb);
     }
     if (a.role == 'e') return done(E, 0);
     t0 = now_ms();
-    otti_witness *wit = nullptr;
     if (a.check) {
-        rc = otti_witness_upload(inst, r->vars32, r->nvars, r->inputs32, r->ninputs, &wit); if (rc) return fail(E, "witness upload", rc);
-        fr.add([=] { otti_witness_free(wit); });
+        if (!wit) {
+            rc = otti_witness_upload(inst, r->vars32, r->nvars, r->inputs32, r->ninputs, &wit); if (rc) return fail(E, "witness upload", rc);
+            fr.add([=] { otti_witness_free(wit); });
+        }
         const int sat = run_check(E, inst, wit, r->num_cons);
         if (sat < 0) return 1;
         if (sat) { fprintf(E.out, "Not proved (unsatisfied assignment)\n"); return 1; }
@@ -220,6 +245,7 @@ static int snark_role(const RunEnv &E, const SnarkRoleArgs &a) {
     fprintf(E.out, "* SNARK::prove %.3f ms\n  * polycommit %.3f ms\n  * multiply_vec %.3f ms\n  * prove_sc_phase_one %.3f ms\n  * eval_table_sparse %.3f ms\n  * prove_sc_phase_two %.3f ms\n"
            "  * polyeval %.3f ms\n  * R1CSEvalProof: derefs commitment %.3f ms, product circuits %.3f ms, hash layer %.3f ms\n  * len_snark_proof %zu\n",
            now_ms() - t0, st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8], proof_len);
+    origin_line(E, wit, inst, a.t_main0);
     if (!write_file(E, a.proof_out, proof, proof_len)) return 1;
     fprintf(E.out, "Proof written to %s (%zu bytes)\n", a.proof_out, proof_len);
     return done(E, 0);
@@ -307,7 +333,7 @@ int spzk_run(int argc, char **argv, const RunEnv &E) {
     if (!E.served) warm = std::thread([&] { if (!verify_only && otti_device_count() > 0) (void)otti_prepare_device(nullptr, nullptr); });
     struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } joiner{warm};
     if (snark_split) {
-        SnarkRoleArgs a{encode_only ? 'e' : prove_only ? 'p' : 'v', files, comm_in, comm_out, proof_in, proof_out, label, seedp, check, verify_comm};
+        SnarkRoleArgs a{encode_only ? 'e' : prove_only ? 'p' : 'v', files, comm_in, comm_out, proof_in, proof_out, label, seedp, check, verify_comm, t_main0};
         const int status = snark_role(E, a);
         fflush(E.out);
         return status;
@@ -373,6 +399,7 @@ int spzk_run(int argc, char **argv, const RunEnv &E) {
                "  * polyeval %.3f ms\n  * R1CSEvalProof: derefs commitment %.3f ms, product circuits %.3f ms, hash layer %.3f ms\n  * len_snark_proof %zu\n",
                t_prove, st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8], proof_len);
         fprintf(E.out, "* SNARK::verify %.3f ms\n", t_verify);
+        origin_line(E, wit, inst, t_main0);
         int wrc = 0;
         if (proof_out && !rc) { FILE *f = fopen(at(E, proof_out).c_str(), "wb"); if (!f || fwrite(proof, 1, proof_len, f) != proof_len) { fprintf(E.err, "spzk: cannot write %s\n", proof_out); wrc = 1; } if (f) fclose(f); }
         if (!E.served) { otti_buf_free(proof); otti_buf_free(cb); otti_comp_comm_free(vc); otti_comp_comm_free(cc); otti_snark_gens_free(sg); otti_instance_free(inst); otti_r1cs_free(r); }   // served: `fr` does, and the generators are the cache's
@@ -422,9 +449,7 @@ int spzk_run(int argc, char **argv, const RunEnv &E) {
         if (f) fclose(f);
     }
     // (no frees: the process ends here and hands everything back at once — releasing the device tables one by one costs milliseconds)
-    if (E.served) fprintf(E.out, "* served: queue %.3f ms, generators %s, table %s, witness %s, ingest %s\n", E.queue_ms, E.gens->gens_word(), E.gens->table_word(), witness_word(wit),
-                          ingest_word(inst));
-    else fprintf(E.out, "* process start to main() %.0f ms (the dynamic loader mapping the HIP runtime), main() %.3f ms\n", E.t_before_main, now_ms() - t_main0);
+    origin_line(E, wit, inst, t_main0);
     if (rc) { fprintf(E.out, "Verification FAILED (%d: %s)\n", rc, rc == OTTI_ERR_VERIFY_DECOMPRESS ? "DecompressionError" : rc == OTTI_ERR_VERIFY_INTERNAL ? "InternalError" : "malformed proof"); return 1; }
     if (wrc) return 1;
     if (prove_only) { fprintf(E.out, "Proof written to %s (%zu bytes)\n", proof_out, proof_len); return done(E, 0); }
