@@ -459,6 +459,20 @@ int32_t otti_synth_r1cs_compiler_like(uint64_t n, uint64_t num_inputs, uint64_t 
         kernel_ms (optional) receives the HIP-event time of the kernel launches alone. ---- */
 /* Fr/Fp/point self-test kernels: out[i] = a[i] * b[i] etc.  op: 0 mul, 1 add, 2 sub */
 int32_t otti_k_fr_op(int32_t op, const uint8_t *h_a, const uint8_t *h_b, uint8_t *h_out, size_t n, float *kernel_ms);
+/* GF(2^255-19) on the device in one of its three forms (form: 0 the 8-word Fp, 1 nine limbs of 29 bits, 2 ten limbs of 26/25 bits), one case per lane:
+   the very inline functions the MSM kernels call.  Operands: n little-endian 256-bit words each (any value: a loosely reduced element).
+   op: 0 a*b, 1 a^2, 2 a+b, 3 a-b, 4 -a, 5 carry((a-b)+(c+d)) (form 0: the representative below p), 6 unpack(pack(unpack(a))), 7 (a-b)*(c+d),
+   8 (a+a+a)*(b+b), 9 ((a+a)-b)*(c-d), 10 carry((a+a)-b)*((c+c)+d), 11 a^(2^252-3).  Form 1 has no op 1, 9, 11 (OTTI_ERR_BAD_ARG).
+   h_out: n packed results; h_limbs: 10 words per case, the raw limbs (form 0: words) of the result before packing, the rest zero. */
+int32_t otti_k_fp_op(int32_t form, int32_t op, const uint8_t *h_a, const uint8_t *h_b, const uint8_t *h_c, const uint8_t *h_d, size_t n, uint8_t *h_out,
+                     uint32_t *h_limbs, float *kernel_ms);
+/* the point formulas on a caller's operands.  h_P: n points (X, Y, Z, T: 128 bytes; any field elements).  op: 0 p9_madd, 1 p10_madd, 3 the quad-lane mixed
+   addition (h_Q: n Niels entries of 96 bytes; neg != 0: the entry negated as for a negative digit); 2 p10_add, 4 the quad-lane full addition (h_Q: n
+   points); 5 k successive p9_madd of the same entry (k <= 4096).  h_out: n packed points; h_limbs: 4 x 10 words per case, the raw limbs of X, Y, Z, T.
+   op 6: k_encode_points on h_P, on h_P[i] + h_Q[i] with h_Q (may be NULL); h_out: n encodings of 32 bytes.  op 7: k_decode_niels; h_P: n encodings,
+   h_out: n Niels entries, *h_bad: the encodings refused (their entry: the identity's). */
+int32_t otti_k_pt_op(int32_t op, const uint8_t *h_P, const uint8_t *h_Q, int32_t neg, uint32_t k, size_t n, uint8_t *h_out, uint32_t *h_limbs, uint32_t *h_bad,
+                     float *kernel_ms);
 /* sparse_mlpoly.rs AddrTimestamps::new for one side of the dense representation: h_addr3 = three lists of N addresses below M (k-major); walking them
    in order over one shared counter array, h_read_ts3[k * N + i] = audit[addr]++ and h_audit[0 .. M) = the counts at the end */
 int32_t otti_k_addr_timestamps(const uint32_t *h_addr3, size_t N, size_t M, uint32_t *h_read_ts3, uint32_t *h_audit, float *kernel_ms);

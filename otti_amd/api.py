@@ -185,6 +185,8 @@ _sig("otti_k_poly_bound", _i32, _vp, _sz, _sz, _vp, _vp, _fp)
 _sig("otti_k_bullet_round", _i32, _vp, _sz, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _fp)
 _sig("otti_k_bullet_last_fold", _i32, _sz, _vp, _vp, _vp, _vp, _vp)
 _u32 = ctypes.c_uint32
+_sig("otti_k_fp_op", _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _fp)
+_sig("otti_k_pt_op", _i32, _i32, _vp, _vp, _i32, _u32, _sz, _vp, _vp, _vp, _fp)
 _sig("otti_k_pc_round", _i32, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _u32, _u32, _vp, _vp, _fp)
 _sig("otti_k_pc_export", _i32, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp)
 _sig("otti_k_pc_tail", _i32, _vp, _vp, _vp, _vp, _sz, _sz, _u32, _sz, _vp, _vp, _vp, _i32, _vp, _vp)
@@ -1102,6 +1104,58 @@ class kernels:
         out, ms = np.zeros_like(a), ctypes.c_float(0)
         _check(lib.otti_k_fr_op({"mul": 0, "add": 1, "sub": 2}[op], _ptr(a), _ptr(b), _ptr(out), a.shape[0], ctypes.byref(ms)))
         return out, ms.value
+
+    FP_FORMS = ("fp8", "f9", "f10")
+    FP_OPS = ("mul", "sqr", "add", "sub", "neg", "carry", "repack", "mul_sub_add", "mul_3a_2b", "mul_f_e", "mul_carried_f_g", "pow22523")
+    PT_OPS = ("p9_madd", "p10_madd", "p10_add", "q10_madd", "q10_add", "chain", "encode", "decode")
+
+    @staticmethod
+    def _words(a, width, what):
+        a = np.ascontiguousarray(a, dtype=np.uint8)
+        if a.ndim != 2 or a.shape[1] != width:
+            raise ValueError(f"{what}: expected an (n, {width}) uint8 array")
+        return a
+
+    @staticmethod
+    def fp_op(form, op, a, b=None, c=None, d=None):
+        """otti_k_fp_op: GF(2^255-19) in one of the device's forms (FP_FORMS) on (n, 32) uint8 little-endian words; absent operands are zero.
+        Returns (packed results (n, 32) uint8, raw limbs (n, 8 | 9 | 10) uint32).  FP_OPS: a*b, a^2, a+b, a-b, -a, carry((a-b)+(c+d)),
+        unpack(pack(unpack(a))), (a-b)*(c+d), (a+a+a)*(b+b), ((a+a)-b)*(c-d), carry((a+a)-b)*((c+c)+d), a^(2^252-3)."""
+        a = kernels._words(a, 32, "a"); n = a.shape[0]
+        b, c, d = (np.zeros_like(a) if x is None else kernels._words(x, 32, "operand") for x in (b, c, d))
+        if not (b.shape == c.shape == d.shape == a.shape):
+            raise ValueError("operands: one length")
+        f = kernels.FP_FORMS.index(form)
+        out, limbs = np.zeros_like(a), np.zeros((n, 10), dtype=np.uint32)
+        _check(lib.otti_k_fp_op(f, kernels.FP_OPS.index(op), _ptr(a), _ptr(b), _ptr(c), _ptr(d), n, _ptr(out), _ptr(limbs), None))
+        return out, limbs[:, :(8, 9, 10)[f]].copy()
+
+    @staticmethod
+    def pt_op(op, P, Q=None, neg=False, k=1):
+        """otti_k_pt_op (PT_OPS).  The formulas: P (n, 128) points, Q (n, 96) Niels entries (p9_madd, p10_madd, q10_madd, chain: k additions of the
+        same entry) or (n, 128) points (p10_add, q10_add); returns (packed points (n, 128) uint8, raw limbs (n, 4, 9 | 10) uint32).
+        encode: k_encode_points on P, on P[i] + Q[i] with Q; returns (n, 32) encodings.  decode: k_decode_niels on P (n, 32) encodings; returns
+        (Niels entries (n, 96), the number refused)."""
+        o = kernels.PT_OPS.index(op)
+        if op == "decode":
+            P = kernels._words(P, 32, "P"); n = P.shape[0]
+            out, bad = np.zeros((n, 96), dtype=np.uint8), _u32(0)
+            _check(lib.otti_k_pt_op(o, _ptr(P), None, 0, 0, n, _ptr(out), None, ctypes.byref(bad), None))
+            return out, bad.value
+        P = kernels._words(P, 128, "P"); n = P.shape[0]
+        if op == "encode":
+            Q = None if Q is None else kernels._words(Q, 128, "Q")
+            if Q is not None and Q.shape != P.shape:
+                raise ValueError("P and Q: one length")
+            out = np.zeros((n, 32), dtype=np.uint8)
+            _check(lib.otti_k_pt_op(o, _ptr(P), _ptr(Q), 0, 0, n, _ptr(out), None, None, None))
+            return out
+        Q = kernels._words(Q, 128 if op in ("p10_add", "q10_add") else 96, "Q")
+        if Q.shape[0] != n:
+            raise ValueError("P and Q: one length")
+        out, limbs = np.zeros((n, 128), dtype=np.uint8), np.zeros((n, 4, 10), dtype=np.uint32)
+        _check(lib.otti_k_pt_op(o, _ptr(P), _ptr(Q), 1 if neg else 0, int(k), n, _ptr(out), _ptr(limbs), None, None))
+        return out, limbs[:, :, :(9 if op in ("p9_madd", "chain") else 10)].copy()
 
     @staticmethod
     def addr_timestamps(addr3, M):

@@ -68,6 +68,63 @@ int32_t otti_k_fr_op(int32_t op, const uint8_t *a, const uint8_t *b, uint8_t *ou
         download(c, out, O.p, n); c.sync(); return OTTI_OK;
     });
 }
+// GF(2^255-19) in the device's three forms and the point formulas built on them (k_curve_ops.hip), on a caller's operands
+int32_t otti_k_fp_op(int32_t form, int32_t op, const uint8_t *a, const uint8_t *b, const uint8_t *cc, const uint8_t *d, size_t n, uint8_t *out, uint32_t *limbs, float *ms) {
+    return guarded([&] {
+        if (form < FPFORM_FP8 || form > FPFORM_F10 || op < 0 || op >= FPOP_COUNT) throw Error(OTTI_ERR_BAD_ARG, "unknown form or operation");
+        if (form == FPFORM_F9 && (op == FPOP_SQR || op == FPOP_POW22523 || op == FPOP_MUL_F_E)) throw Error(OTTI_ERR_BAD_ARG, "the nine-limb form has no such operation (no square, no power; 2a - b is normalised before it is multiplied)");
+        if (n && (!a || !b || !cc || !d || !out || !limbs)) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (!n) return OTTI_OK;
+        DevCtx &c = DevCtx::get();
+        DevBuf<Fp> in(4 * n), o(n); DevBuf<uint32_t> lm(n * kFpOpLimbStride);
+        const uint8_t *src[4] = {a, b, cc, d};
+        for (int k = 0; k < 4; k++) OTTI_HIP(hipMemcpyAsync(in.p + k * n, src[k], n * sizeof(Fp), hipMemcpyHostToDevice, c.stream));
+        OTTI_HIP(hipMemsetAsync(lm.p, 0, n * kFpOpLimbStride * sizeof(uint32_t), c.stream));
+        KTimer t(c, ms); dev_fp_op(c, form, op, in.p, in.p + n, in.p + 2 * n, in.p + 3 * n, o.p, lm.p, n); t.stop();
+        OTTI_HIP(hipMemcpyAsync(out, o.p, n * sizeof(Fp), hipMemcpyDeviceToHost, c.stream));
+        OTTI_HIP(hipMemcpyAsync(limbs, lm.p, n * kFpOpLimbStride * sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
+        c.sync(); return OTTI_OK;
+    });
+}
+int32_t otti_k_pt_op(int32_t op, const uint8_t *P, const uint8_t *Q, int32_t neg, uint32_t k, size_t n, uint8_t *out, uint32_t *limbs, uint32_t *bad, float *ms) {
+    return guarded([&] {
+        if (op < 0 || op >= PTOP_COUNT) throw Error(OTTI_ERR_BAD_ARG, "unknown operation");
+        if (n && (!P || !out)) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (n > ((size_t)1 << 20) || k > 4096) throw Error(OTTI_ERR_BAD_ARG, "more than 2^20 cases, or a chain of more than 4096 additions");
+        if (bad) *bad = 0;
+        if (!n) return OTTI_OK;
+        DevCtx &c = DevCtx::get();
+        if (op == PTOP_DECODE) {                                   // P: n encodings; out: n Niels entries
+            if (!bad) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+            DevBuf<uint8_t> in(32 * n); DevBuf<Niels> o(n); DevBuf<unsigned> cnt(1);
+            OTTI_HIP(hipMemcpyAsync(in.p, P, 32 * n, hipMemcpyHostToDevice, c.stream));
+            OTTI_HIP(hipMemsetAsync(cnt.p, 0, sizeof(unsigned), c.stream));
+            KTimer t(c, ms); dev_decode_niels(c, in.p, n, o.p, cnt.p); t.stop();
+            OTTI_HIP(hipMemcpyAsync(out, o.p, n * sizeof(Niels), hipMemcpyDeviceToHost, c.stream));
+            OTTI_HIP(hipMemcpyAsync(bad, cnt.p, sizeof(unsigned), hipMemcpyDeviceToHost, c.stream));
+            c.sync(); return OTTI_OK;
+        }
+        DevBuf<Pt> p(n);
+        OTTI_HIP(hipMemcpyAsync(p.p, P, n * sizeof(Pt), hipMemcpyHostToDevice, c.stream));
+        if (op == PTOP_ENCODE) {                                   // Q: n addends, or NULL; out: n encodings
+            DevBuf<Pt> q(n); DevBuf<uint8_t> o(32 * n);
+            if (Q) OTTI_HIP(hipMemcpyAsync(q.p, Q, n * sizeof(Pt), hipMemcpyHostToDevice, c.stream));
+            KTimer t(c, ms); dev_encode_points(c, p.p, n, o.p, Q ? q.p : nullptr); t.stop();
+            OTTI_HIP(hipMemcpyAsync(out, o.p, 32 * n, hipMemcpyDeviceToHost, c.stream));
+            c.sync(); return OTTI_OK;
+        }
+        if (!Q || !limbs) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        const bool q_is_point = op == PTOP_P10_ADD || op == PTOP_Q10_ADD;
+        const size_t qbytes = n * (q_is_point ? sizeof(Pt) : sizeof(Niels)), nl = n * 4 * kFpOpLimbStride;
+        DevBuf<uint8_t> q(qbytes); DevBuf<Pt> o(n); DevBuf<uint32_t> lm(nl);
+        OTTI_HIP(hipMemcpyAsync(q.p, Q, qbytes, hipMemcpyHostToDevice, c.stream));
+        OTTI_HIP(hipMemsetAsync(lm.p, 0, nl * sizeof(uint32_t), c.stream));
+        KTimer t(c, ms); dev_pt_op(c, op, p.p, q.p, neg != 0, k, n, o.p, lm.p); t.stop();
+        OTTI_HIP(hipMemcpyAsync(out, o.p, n * sizeof(Pt), hipMemcpyDeviceToHost, c.stream));
+        OTTI_HIP(hipMemcpyAsync(limbs, lm.p, nl * sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
+        c.sync(); return OTTI_OK;
+    });
+}
 int32_t otti_k_addr_timestamps(const uint32_t *h_addr3, size_t N, size_t M, uint32_t *h_read_ts3, uint32_t *h_audit, float *ms) {
     return guarded([&] {
         if (!h_addr3 || !h_read_ts3 || !h_audit || N < 1 || M < 1 || N > ((size_t)1 << 28) || M > ((size_t)1 << 31)) throw Error(OTTI_ERR_BAD_ARG, "address timestamps: null argument, or N outside 1 .. 2^28, or M outside 1 .. 2^31");

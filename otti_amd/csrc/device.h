@@ -355,6 +355,14 @@ std::shared_ptr<DeviceGens> build_device_gens(const Gens &g, int window_bits);
 
 // ---- element-wise / conversion
 void dev_fr_op(DevCtx &c, int op, const Fr *a, const Fr *b, Fr *out, size_t n);
+// GF(2^255-19) and point formulas on a test's operands (k_curve_ops.hip): the inline functions of field.h / fp9.h / fp10.h, one case per lane (quad
+// forms: four).  limbs: kFpOpLimbStride words per field element (the raw limbs of the unpacked result), four elements per point.  Only queue.
+enum FpForm { FPFORM_FP8 = 0, FPFORM_F9, FPFORM_F10 };
+enum FpOp { FPOP_MUL = 0, FPOP_SQR, FPOP_ADD, FPOP_SUB, FPOP_NEG, FPOP_CARRY, FPOP_REPACK, FPOP_MUL_SUB_ADD, FPOP_MUL_3A_2B, FPOP_MUL_F_E, FPOP_MUL_CARRIED_F_G, FPOP_POW22523, FPOP_COUNT };
+enum PtOp { PTOP_P9_MADD = 0, PTOP_P10_MADD, PTOP_P10_ADD, PTOP_Q10_MADD, PTOP_Q10_ADD, PTOP_P9_CHAIN, PTOP_ENCODE, PTOP_DECODE, PTOP_COUNT };
+constexpr int kFpOpLimbStride = 10;
+void dev_fp_op(DevCtx &c, int form, int op, const Fp *a, const Fp *b, const Fp *cc, const Fp *d, Fp *out, uint32_t *limbs, size_t n);
+void dev_pt_op(DevCtx &c, int op, const Pt *P, const void *Q, bool neg, uint32_t k, size_t n, Pt *out, uint32_t *limbs);
 void dev_from_canonical(DevCtx &c, const Fr *in, Fr *out, size_t n);      // raw LE integer -> Montgomery (must be < l)
 void dev_to_canonical(DevCtx &c, const Fr *in, Fr *out, size_t n);
 void dev_fill_zero(DevCtx &c, Fr *p, size_t n);
@@ -445,7 +453,7 @@ double dev_small_fraction(DevCtx &c, const Fr *z, size_t n);               // sh
 // CALLER has checked that: the kernel takes a term's table column from it); d_s Montgomery.  One workgroup per row; a row without terms is not
 // touched.  Only queues.
 void dev_msm_scatter(DevCtx &c, const DeviceGens &g, const uint64_t *d_idx, const Fr *d_s, size_t count, size_t R, Pt *rows, size_t L);
-void dev_encode_points(DevCtx &c, const Pt *pts, size_t n, uint8_t *d_out32);      // RFC 9496 encodings of n extended points (only queues)
+void dev_encode_points(DevCtx &c, const Pt *pts, size_t n, uint8_t *d_out32, const Pt *addend = nullptr);   // RFC 9496 encodings of n extended points, of pts[i] + addend[i] with an addend (only queues)
 // ---- K9: LZ[j] = sum_i Lv[i] * Z[i*R + j]
 void dev_poly_bound(DevCtx &c, const Fr *Z, size_t L, size_t R, const Fr *Lv, Fr *out, Fr *scratch /* >= 64*R */);
 // chunk sums of the same bound over eq(rest) alone (k_sumcheck.hip): out = (L / m) x R; false (nothing launched) when the geometry does not allow it

@@ -482,10 +482,10 @@ __global__ __launch_bounds__(64) void k_encode_points(const Pt *pts, const Pt *a
     for (int k = 0; k < 8; k++) o[k] = w[k];
     if (host32) { uint32_t *h = (uint32_t *)(host32 + 32 * i); for (int k = 0; k < 8; k++) h[k] = w[k]; }
 }
-void dev_encode_points(DevCtx &c, const Pt *pts, size_t n, uint8_t *d_out32) {
+void dev_encode_points(DevCtx &c, const Pt *pts, size_t n, uint8_t *d_out32, const Pt *addend) {
     if (!n) return;
     KScope ks(c, KC_MSM_FINISH);
-    hipLaunchKernelGGL(k_encode_points, (unsigned)((n + 63) / 64), 64, 0, c.stream, pts, (const Pt *)nullptr, n, d_out32, (uint8_t *)nullptr);
+    hipLaunchKernelGGL(k_encode_points, (unsigned)((n + 63) / 64), 64, 0, c.stream, pts, addend, n, d_out32, (uint8_t *)nullptr);
 }
 // share of the n scalars whose canonical value is below 2^128 (what a compiled circuit's witness is mostly made of)
 __global__ __launch_bounds__(kBlock) void k_count_small(const Fr *z, size_t n, unsigned long long *count) {

@@ -1,15 +1,85 @@
 // Host build of the nine-limb field arithmetic (otti_amd/csrc/fr9.h, fp9.h: the C bodies; the device uses generated asm blocks that
-// tools/limbbench and the GPU parity tests cover) checked against the 8 x u32 arithmetic of field.h / point.h on random and edge inputs.
+// tools/limbbench, the GPU parity tests and tests/test_gpu_curve_arith.py cover) checked against the 8 x u32 arithmetic of field.h / point.h on
+// random inputs and on the edge pool that the device tests use (tests/curve_cases.py).
 // Built and run by tests/test_limb9_host.py (g++, no GPU).
 #include "fr9.h"
 #include "fp9.h"
 #include <stdio.h>
 #include <random>
+#include <vector>
 using namespace otti;
 static std::mt19937_64 rng(20261004);
 static Fr rnd_fr() { Fr t; for (int i = 0; i < 8; i++) t.v[i] = (uint32_t)rng(); t.v[7] &= 0x0fffffffu; uint32_t w[8]; for (int i = 0; i < 8; i++) w[i] = t.v[i]; return fr_cond_sub_l(w, 0); }
 static Fp rnd_fp() { Fp t; for (int i = 0; i < 8; i++) t.v[i] = (uint32_t)rng(); return t; }
 static Fr l_minus(uint32_t k) { Fr a; for (int i = 0; i < 8; i++) a.v[i] = fr_L(i); a.v[0] -= k; return a; }
+// ---- the edge pool of tests/curve_cases.py (limb-boundary and non-canonical 256-bit words) through the plain-C bodies of fp9.h: all pairs for the
+// operations of two operands, the compound shapes whose operands sit at the bounds fp9.h states, and p9_madd (both signs, two in a chain, output bound)
+static Fp raw_pow2(int s) { Fp r = fp_zero(); r.v[s >> 5] = 1u << (s & 31); return r; }
+static Fp raw_sub1(Fp a) { for (int i = 0; i < 8; i++) { if (a.v[i]--) break; } return a; }                 // a - 1 on the raw words (a != 0)
+static Fp raw_add(Fp a, uint32_t k) { uint64_t c = k; for (int i = 0; i < 8; i++) { c += a.v[i]; a.v[i] = (uint32_t)c; c >>= 32; } return a; }
+static std::vector<Fp> edge_pool() {
+    const Fp ones = fp_from_words(~0u, ~0u, ~0u, ~0u, ~0u, ~0u, ~0u, ~0u);
+    Fp p = ones; p.v[0] = 0xffffffedu; p.v[7] = 0x7fffffffu;                                                 // 2^255 - 19
+    Fp two_p = ones; two_p.v[0] = 0xffffffdau;                                                               // 2^256 - 38
+    Fp half = p; half.v[0] = 0xfffffff6u; half.v[7] = 0x3fffffffu;                                           // (p - 1) / 2 = 2^254 - 10
+    std::vector<Fp> v = {fp_zero(), fp_one(), raw_add(fp_zero(), 2), raw_add(fp_zero(), 19), raw_sub1(p), p, raw_add(p, 1), raw_sub1(raw_pow2(255)), raw_pow2(255),
+                         raw_add(raw_pow2(255), 18), two_p, ones, half, fp_D(), fp_2D(), fp_SQRT_M1()};
+    for (int k = 1; k <= 8; k++) { v.push_back(raw_pow2(29 * k)); v.push_back(raw_sub1(raw_pow2(29 * k))); }
+    const int ten[9] = {26, 51, 77, 102, 128, 153, 179, 204, 230};
+    for (int s : ten) { v.push_back(raw_pow2(s)); v.push_back(raw_sub1(raw_pow2(s))); }
+    return v;
+}
+static bool f9_reduced(const F9 &a) {
+    for (int i = 0; i < 8; i++) if (a.v[i] >= (1u << 29) + (i < 2 ? (1u << 18) : 0u)) return false;
+    return a.v[8] < (1u << 23) + 2;
+}
+static bool p9_reduced(const P9 &q) { return f9_reduced(q.X) && f9_reduced(q.Y) && f9_reduced(q.Z) && f9_reduced(q.T); }
+static bool pt_same(const Pt &a, const Pt &b) { return fp_eq(a.X, b.X) && fp_eq(a.Y, b.Y) && fp_eq(a.Z, b.Z) && fp_eq(a.T, b.T); }
+static int edge_pool_checks() {
+    const std::vector<Fp> pool = edge_pool();
+    const size_t n = pool.size();
+    int bad = 0;
+#define ECHECK(cond, what) do { if (!(cond)) { if (bad < 10) printf("FAIL edge pool: %s\n", what); bad++; } } while (0)
+    for (size_t i = 0; i < n; i++) {
+        const Fp a = pool[i]; const F9 a9 = f9_unpack(a);
+        ECHECK(f9_reduced(a9) && fp_eq(f9_pack(a9), a), "unpack / pack");
+        ECHECK(fp_eq(f9_pack(f9_neg(a9)), fp_neg(a)), "neg");
+        for (size_t j = 0; j < n; j++) {
+            const Fp b = pool[j]; const F9 b9 = f9_unpack(b);
+            const F9 m = f9_mul(a9, b9);
+            ECHECK(f9_reduced(m) && fp_eq(f9_pack(m), fp_mul(a, b)), "mul");
+            ECHECK(fp_eq(f9_pack(f9_add(a9, b9)), fp_add(a, b)), "add");
+            ECHECK(fp_eq(f9_pack(f9_sub(a9, b9)), fp_sub(a, b)), "sub");
+            const F9 m32 = f9_mul(f9_add(f9_add(a9, a9), a9), f9_add(b9, b9));                             // fp9.h's 3 * 2^29 x 2^30
+            ECHECK(f9_reduced(m32) && fp_eq(f9_pack(m32), fp_mul(fp_add(fp_add(a, a), a), fp_add(b, b))), "(a+a+a)(b+b)");
+        }
+    }
+    // quadruples and point tuples: every all-equal tuple of the three largest words, then a seeded walk over the pool
+    const size_t big[3] = {11, 7, 4};                                                                    // 2^256 - 1, 2^255 - 1, p - 1
+    std::mt19937_64 pick(20261020);
+    for (int it = 0; it < 4000; it++) {
+        Fp t[7];
+        for (int k = 0; k < 7; k++) t[k] = it < 3 ? pool[big[it]] : ((it & 1) && (pick() & 1) ? pool[big[pick() % 3]] : pool[pick() % n]);
+        const F9 a9 = f9_unpack(t[0]), b9 = f9_unpack(t[1]), c9 = f9_unpack(t[2]), d9 = f9_unpack(t[3]);
+        const F9 eh = f9_mul(f9_sub(a9, b9), f9_add(c9, d9));                                              // the E * H, G * H shapes
+        ECHECK(f9_reduced(eh) && fp_eq(f9_pack(eh), fp_mul(fp_sub(t[0], t[1]), fp_add(t[2], t[3]))), "(a-b)(c+d)");
+        const F9 fg = f9_mul(f9_carry(f9_sub(f9_add(a9, a9), b9)), f9_add(f9_add(c9, c9), d9));            // the normalised F times G
+        ECHECK(f9_reduced(fg) && fp_eq(f9_pack(fg), fp_mul(fp_sub(fp_add(t[0], t[0]), t[1]), fp_add(fp_add(t[2], t[2]), t[3]))), "carry(2a-b)(2c+d)");
+        const F9 cr = f9_carry(f9_add(f9_sub(a9, b9), f9_add(c9, d9)));
+        ECHECK(f9_reduced(cr) && fp_eq(f9_pack(cr), fp_add(fp_sub(t[0], t[1]), fp_add(t[2], t[3]))), "carry((a-b)+(c+d))");
+        Pt P; P.X = t[0]; P.Y = t[1]; P.Z = t[2]; P.T = t[3];
+        Niels nl; nl.yplusx = t[4]; nl.yminusx = t[5]; nl.xy2d = t[6];
+        for (int neg = 0; neg < 2; neg++) {
+            N9 e = n9_unpack(nl); if (neg) e = n9_negate(e);
+            const P9 q1 = p9_madd(p9_unpack(P), e), q2 = p9_madd(q1, e);
+            const Pt w1 = neg ? pt_msub(P, nl) : pt_madd(P, nl), w2 = neg ? pt_msub(w1, nl) : pt_madd(w1, nl);
+            ECHECK(p9_reduced(q1) && p9_reduced(q2), "p9_madd output bound");
+            ECHECK(pt_same(p9_pack(q1), w1) && pt_same(p9_pack(q2), w2), "p9_madd");
+        }
+    }
+#undef ECHECK
+    return bad;
+}
 #define CHECK(cond, what) do { if (!(cond)) { if (bad < 10) printf("FAIL %s at iteration %d\n", what, it); bad++; } } while (0)
 int main(int argc, char **argv) {
     const int iters = argc > 1 ? atoi(argv[1]) : 20000;
@@ -56,6 +126,7 @@ int main(int argc, char **argv) {
         for (int i = 0; i < 8; i++) CHECK(Q.X.v[i] < (1u << 29) + (1u << 18) && Q.Y.v[i] < (1u << 29) + (1u << 18) && Q.Z.v[i] < (1u << 29) + (1u << 18) && Q.T.v[i] < (1u << 29) + (1u << 18), "reduced bound");
         if (it % 61 == 0 || it < 40) { const Pt q = p9_pack(Q); CHECK(fp_eq(q.X, P.X) && fp_eq(q.Y, P.Y) && fp_eq(q.Z, P.Z) && fp_eq(q.T, P.T), "p9_madd"); }
     }
+    bad += edge_pool_checks();
     printf("limb9 check: %d failures\n", bad);
     return bad != 0;
 }

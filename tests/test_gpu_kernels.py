@@ -271,3 +271,85 @@ def test_row_sum_on_device_equals_the_oracles_commitment(rng, n, lgv):
     bad = C.copy(); bad[n - 1, 31] |= 0x80                     # non-canonical field element
     with pytest.raises(oa.ProofVerifyError):
         K.row_sum(bad, s)
+
+
+# ---- the same row sum over points an adversary may send: repeated points, P / -P pairs, the identity's encoding.  Every point is a commitment the
+# oracle forms from a row of integers over its 16 generators (R = 16), so the expected sum is the oracle's commitment to sum_i s[i] * row[i] mod l.
+ROW_SUM_SIZES = [256, 257, 2049, 4097]                         # the smallest the device takes; c = 7; ragged two- and three-way splits
+
+
+class _RowBank:
+    """rows of integers over 16 generators and the oracle's commitments to them, made once: [0] the zero row (the identity), D[i] = (i + 1) P_(i % 16)
+    (4097 distinct points), N[i] = -D[i], and 8 dense random rows"""
+
+    def __init__(self):
+        self.og = orc.OGens(256, 256, 1)
+        assert self.og.R == 16
+        l, n_max = orc.L_ORDER, max(ROW_SUM_SIZES)
+        rnd = np.random.default_rng(20261020)
+        self.rows = [{}] + [{i % 16: i + 1} for i in range(n_max)] + [{i % 16: l - (i + 1)} for i in range(n_max)]
+        self.rows += [{j: v for j, v in enumerate(orc.fr_to_ints(orc.rand_fr(rnd, 16)))} for _ in range(8)]
+        self.zero, self.D, self.N, self.dense = 0, 1, 1 + n_max, 1 + 2 * n_max
+        self.points = orc.commit_rows(self.og, self._dense(self.rows), len(self.rows), 16, orc.fr_from_ints([0] * len(self.rows)))
+        assert eq(self.points[0], np.zeros(32, dtype=np.uint8))
+        assert len({p.tobytes() for p in self.points[self.D:self.N]}) == n_max
+
+    @staticmethod
+    def _dense(rows):
+        return orc.fr_from_ints([r.get(j, 0) for r in rows for j in range(16)])
+
+    def want(self, idx, s):
+        """the oracle's commitment to sum_i s[i] * rows[idx[i]] mod l"""
+        acc = [0] * 16
+        for i, k in zip(idx, s):
+            for j, v in self.rows[i].items():
+                acc[j] = (acc[j] + k * v) % orc.L_ORDER
+        return orc.commit_rows(self.og, orc.fr_from_ints(acc), 1, 16, orc.fr_from_ints([0]))[0]
+
+
+_row_bank = []
+
+
+def row_bank():
+    if not _row_bank:
+        _row_bank.append(_RowBank())
+    return _row_bank[0]
+
+
+@pytest.mark.parametrize("n", ROW_SUM_SIZES)
+def test_row_sum_over_repeated_opposite_and_identity_points(n):
+    B = row_bank(); l = orc.L_ORDER
+    rnd = np.random.default_rng(n)
+    rand = lambda k: orc.fr_to_ints(orc.rand_fr(rnd, k))
+    zeros32 = np.zeros(32, dtype=np.uint8)
+
+    def run(idx, s, what):
+        assert len(idx) == len(s) == n
+        got, want = K.row_sum(B.points[np.asarray(idx)], orc.fr_from_ints(s)), B.want(idx, s)
+        assert eq(got, want), (n, what)
+        return got
+
+    # all points equal
+    run([B.D + 5] * n, rand(n), "all points equal")
+    # P / -P pairs with equal scalars (an odd n ends with the identity's encoding under a scalar of its own): the identity, 32 zero bytes
+    pair_s = rand(n // 2)
+    idx = [x for i in range(n // 2) for x in (B.D + i, B.N + i)] + [B.zero] * (n & 1)
+    s = [x for k in pair_s for x in (k, k)] + [l - 1] * (n & 1)
+    assert eq(run(idx, s, "adjacent P, -P"), zeros32)
+    perm = rnd.permutation(n)
+    assert eq(run([idx[i] for i in perm], [s[i] for i in perm], "shuffled P, -P"), zeros32)
+    # the identity's encoding under non-zero scalars, l - 1 among them, between real terms
+    idx = [B.zero if i % 3 else B.D + i for i in range(n)]
+    s = rand(n)
+    for i in range(1, n, 6):
+        s[i] = l - 1
+    assert all(s[i] for i in range(n))
+    run(idx, s, "identity encodings under non-zero scalars")
+    assert eq(run([B.zero] * n, [l - 1] * n, "only identity encodings"), zeros32)
+    # distinct points, one scalar for all: in every window one bucket takes a whole split
+    distinct = [B.D + i for i in range(n)]
+    run(distinct, rand(1) * n, "distinct points, all scalars equal")
+    for k in (1, l - 1, 2 ** 252):
+        run(distinct, [k] * n, f"all scalars {k}")
+    # few rows, many times each
+    run([B.dense + int(j) for j in rnd.integers(0, 8, size=n)], rand(n), "random rows, repeated")

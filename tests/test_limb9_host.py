@@ -1,6 +1,7 @@
 """The nine-limb field arithmetic of the round-4 kernels (otti_amd/csrc/fr9.h, fp9.h), host build, against the 8 x u32 arithmetic that the
-oracle pins (tests/test_host.py::otti_host_selftest, tests/test_oracle.py).  The device bodies (generated asm) are covered on the GPU by
-tests/test_gpu_kernels.py / test_gpu_parity.py and tools/limbbench."""
+oracle pins (tests/test_host.py::otti_host_selftest, tests/test_oracle.py), on random values and on the edge pool of tests/curve_cases.py (limb
+boundaries, non-canonical words: all pairs, the compound shapes, p9_madd).  The device bodies (generated asm) are covered on the GPU by
+tests/test_gpu_curve_arith.py (the same pool), tests/test_gpu_kernels.py / test_gpu_parity.py and tools/limbbench."""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
