@@ -522,6 +522,14 @@ int32_t otti_k_sc_cubic_fold_round(const uint8_t *h_A, const uint8_t *h_B, const
 /* one round of prove_quad: (e0,e2) of A*B */
 int32_t otti_k_sc_quad_round(const uint8_t *h_A, const uint8_t *h_B, size_t len, uint8_t *h_e2, float *kernel_ms);
 int32_t otti_k_sc_quad_fold_round(const uint8_t *h_A, const uint8_t *h_B, size_t len, const uint8_t *h_r, uint8_t *h_out2, uint8_t *h_e2, float *kernel_ms);
+/* The grid of the round launches above and of the cubic3 ones below, for tests: every launch takes its grid from a plan over the table length and
+   seven capacities of the device — its CUs, then the workgroups resident at once of the cubic3 evaluate, cubic3 fold, quad evaluate, quad fold,
+   four-table evaluate and four-table fold kernels.  otti_k_sc_caps_override puts h_caps7 in the device's place for every later launch of this
+   process (a short table then walks several items per thread, or spreads over up to 2048 workgroups); NULL restores what the device reported.
+   OTTI_ERR_BAD_ARG for a zero among the seven, and while a proof is in flight.  otti_k_sc_plan: the grid and the most items any thread walks
+   that a launch of `kind` (0 .. 5 in the order above) over tables of length len gets under the capacities now in force. */
+int32_t otti_k_sc_caps_override(const uint32_t *h_caps7);
+int32_t otti_k_sc_plan(int32_t kind, size_t len, int32_t armed, uint32_t *workgroups, uint64_t *items_per_thread);
 /* DensePolynomial::commit_inner: L rows of R scalars -> L compressed points C_i = sum_j Z[iR+j] P[j] + blinds[i] P[R+1] */
 /* Self-test of the "armed" launches the provers use for their small sequential rounds (a kernel queued before its challenge is known
  * and released through pinned host memory): the quadratic fold + sums round on the caller's tables (length len, a power of two >= 8),

@@ -174,6 +174,8 @@ _sig("otti_k_sc_cubic_fold_round", _i32, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp,
 _sig("otti_k_sc_quad_round", _i32, _vp, _vp, _sz, _vp, _fp)
 _sig("otti_k_sc_quad_fold_round", _i32, _vp, _vp, _sz, _vp, _vp, _vp, _fp)
 _sig("otti_k_armed_selftest", _i32, _vp, _vp, _sz, _vp, ctypes.c_uint32, _vp, _vp)
+_sig("otti_k_sc_caps_override", _i32, _vp)
+_sig("otti_k_sc_plan", _i32, _i32, _sz, _i32, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(_u64))
 _sig("otti_k_msm_rows", _i32, _vp, _vp, _sz, _sz, _vp, _vp, _fp)
 _sig("otti_k_row_sum", _i32, _vp, _sz, _vp, _vp)
 _sig("otti_k_msm_scatter_rows", _i32, _vp, _sz, _vp, _vp, _sz, _vp, _fp)
@@ -1285,6 +1287,36 @@ class kernels:
         out = np.zeros((2, n // 2, 32), dtype=np.uint8); e = np.zeros((2, 32), dtype=np.uint8); ms = ctypes.c_float(0)
         _check(lib.otti_k_sc_quad_fold_round(_ptr(A), _ptr(B), n, _ptr(r), _ptr(out), _ptr(e), ctypes.byref(ms)))
         return out, e, ms.value
+
+    SC_KINDS = ("cubic3_eval", "cubic3_fold", "quad_eval", "quad_fold", "cubic4_eval", "cubic4_fold")     # sc_plan.h ScKind
+
+    @staticmethod
+    def sc_plan(kind, n, armed=False):
+        """otti_k_sc_plan: (workgroups, the most items a thread walks) of a round launch of ``kind`` (SC_KINDS) over tables of length n, under the
+        capacities now in force (the device's own, or those of an enclosing sc_caps)"""
+        wg, per = ctypes.c_uint32(0), _u64(0)
+        _check(lib.otti_k_sc_plan(kernels.SC_KINDS.index(kind), n, 1 if armed else 0, ctypes.byref(wg), ctypes.byref(per)))
+        return wg.value, per.value
+
+    @staticmethod
+    @contextlib.contextmanager
+    def sc_caps(num_cu, resident):
+        """otti_k_sc_caps_override for the length of a ``with`` block: the round launches inside take their grids from ``num_cu`` CUs and ``resident``
+        workgroups at once (one number for all six kernels, or six by SC_KINDS) in the device's place; the device's own return on the way out"""
+        res = [int(resident)] * 6 if np.isscalar(resident) else [int(x) for x in resident]
+        if len(res) != 6:
+            raise ValueError("resident: one number or six")
+        caps = (ctypes.c_uint32 * 7)(int(num_cu), *res)
+        _check(lib.otti_k_sc_caps_override(caps))
+        try:
+            yield
+        finally:
+            _check(lib.otti_k_sc_caps_override(None))
+
+    @staticmethod
+    def sc_caps_restore():
+        """the device's own capacities again, whatever override stands"""
+        _check(lib.otti_k_sc_caps_override(None))
 
     @staticmethod
     def armed_selftest(A, B, r, hold_us=200):

@@ -297,6 +297,24 @@ int32_t otti_k_sc_quad_fold_round(const uint8_t *A, const uint8_t *B, size_t len
         c.sync(); c.wait_ticket(tk); memcpy(e2, c.h_results, 64); return OTTI_OK;
     });
 }
+// The round launches' grid on demand: capacities in the device's place (num_cu, then resident[] by ScKind), and the plan a launch gets under
+// the capacities in force.  For the tests, which thereby walk many items per thread, or spread over the widest grid, on short tables.
+int32_t otti_k_sc_caps_override(const uint32_t *caps7) {
+    return guarded([&] {
+        if (!caps7) { sc_caps_override(nullptr); return OTTI_OK; }
+        ScCaps caps; caps.num_cu = caps7[0];
+        for (int k = 0; k < kScKinds; k++) caps.resident[k] = caps7[1 + k];
+        sc_caps_override(&caps); return OTTI_OK;
+    });
+}
+int32_t otti_k_sc_plan(int32_t kind, size_t len, int32_t armed, uint32_t *workgroups, uint64_t *items_per_thread) {
+    return guarded([&] {
+        if (kind < 0 || kind >= kScKinds || !workgroups || !items_per_thread) throw Error(OTTI_ERR_BAD_ARG, "unknown kind of round, or null argument");
+        if (!pow2(len) || len < ((kind & 1) ? 4u : 2u)) throw Error(OTTI_ERR_BAD_ARG, "table length must be a power of two >= 2 (>= 4 with a fold)");
+        const ScPlan p = sc_plan((ScKind)kind, len, armed != 0, sc_caps(DevCtx::get()));
+        *workgroups = p.workgroups; *items_per_thread = p.items_per_thread; return OTTI_OK;
+    });
+}
 // Armed launches (device.h): the same fold + sums round three ways on the caller's tables — plain; armed and released by go() after
 // `hold_us` microseconds of the kernel waiting; armed and ABORTED (the tables must come back untouched and the stream must drain),
 // followed by another armed round that must still work.  out2/e2: the plain launch's folded tables and sums, for the caller's oracle.

@@ -423,6 +423,7 @@ unsigned long long dev_sc_quad_fold_eval_armed(DevCtx &c, Fr *A, Fr *B, size_t l
 unsigned long long dev_sc_quad_eval(DevCtx &c, const Fr *A, const Fr *B, size_t len, int slot);
 unsigned long long dev_sc_quad_fold_eval(DevCtx &c, Fr *A, Fr *B, size_t len, const Fr &r, int slot);
 const ScCaps &sc_caps(DevCtx &c);                   // what sc_plan() (sc_plan.h) is told about this device: it sets the grid of every launch above
+void sc_caps_override(const ScCaps *caps);          // tests only: capacities sc_caps() returns in the device's place until nullptr takes them back; refused while a proof is in flight
 void dev_fold_top(DevCtx &c, Fr *Z, size_t len, const Fr &r);
 void dev_fold_bot(DevCtx &c, const Fr *Z, Fr *out, size_t len, const Fr &r);
 void dev_fetch(DevCtx &c, const Fr *src, int slot, size_t n);              // async copy of n elements into h_results[slot..]

@@ -126,7 +126,9 @@ template <uint32_t K> HD Fr9 fr9_sub_kl(const Fr9 &a, const Fr9 &b) {
     return r;
 }
 HD Fr9 fr9_sub2l(const Fr9 &a, const Fr9 &b) { return fr9_sub_kl<2>(a, b); }
-// any normalised value below 2^261 (limb 8 < 2^29)  ->  canonical memory word:  v = low252 + q 2^252 = low252 - q delta (mod l), q < 2^9
+// any normalised value below 2^264 (limb 8 as wide as its 32 bits)  ->  canonical memory word:  v = low252 + q 2^252 = low252 - q delta (mod l), q < 2^12:
+// q delta < 2^137 fits d[0..4], so low252 + l - q delta stays in (0, 2l).  A thread's accumulators after 64 items of the four-table cubic pass 2^261
+// (tests/limb9_check.cpp walks sums up to 4032 l and the limb's ends; tests/test_gpu_sumcheck_walks.py the kernels)
 HD Fr fr9_canon(const Fr9 &a) {
     const uint32_t q = a.v[8] >> 20;
     const uint32_t L[5] = {FR9_L0, FR9_L1, FR9_L2, FR9_L3, FR9_L4};

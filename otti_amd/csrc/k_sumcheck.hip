@@ -1,5 +1,6 @@
 // K2 eq tables, K3/K4/K5/K7 sum-check rounds and folds, K9 DensePolynomial::bound.
 #include "kernels_common.h"
+#include <atomic>
 
 namespace otti {
 
@@ -331,7 +332,22 @@ template <class Kern> static unsigned resident_workgroups(const DevCtx &c, Kern 
     OTTI_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kBlock, 0));
     return (unsigned)std::max(1, per_cu) * (unsigned)std::max(1, c.num_cu);
 }
+// The tests' seam (otti_k_sc_caps_override): capacities that stand in for the device's until they are taken back, so that a short table walks
+// the many-items-per-thread path of a long one or spreads over the widest grid.  Written only while no proof is in flight; never set by the prover.
+static ScCaps g_caps_override;
+static std::atomic<bool> g_caps_overridden{false};
+void sc_caps_override(const ScCaps *caps) {
+    if (ActiveProof::count() != 0) throw Error(OTTI_ERR_BAD_ARG, "the round kernels' capacities cannot change while a proof is in flight");
+    if (!caps) { g_caps_overridden.store(false, std::memory_order_release); return; }
+    bool zero = caps->num_cu == 0;
+    for (int k = 0; k < kScKinds; k++) zero = zero || caps->resident[k] == 0;
+    if (zero) throw Error(OTTI_ERR_BAD_ARG, "a capacity of zero");
+    g_caps_overridden.store(false, std::memory_order_release);
+    g_caps_override = *caps;
+    g_caps_overridden.store(true, std::memory_order_release);
+}
 const ScCaps &sc_caps(DevCtx &c) {
+    if (g_caps_overridden.load(std::memory_order_acquire)) return g_caps_override;
     static std::once_flag once; static ScCaps caps;
     std::call_once(once, [&] {
         caps.num_cu = (unsigned)std::max(1, c.num_cu);

@@ -21,6 +21,7 @@ constexpr int kScKinds = 6;
 // as the partial sums allow, as it has been since the kernels were measured at 2^24.
 constexpr unsigned kScWorkgroupsPerCu = 2;
 constexpr size_t kScWideItems = (size_t)1 << 21;
+// The longest walk the tests pin is 64 items per thread (tests/test_gpu_sumcheck_walks.py): on 256 CUs the plan stays within it for every length up to 2^26.
 
 // what the device says, once per process: its CUs and how many workgroups of each kernel are resident at once (occupancy per CU x CUs)
 struct ScCaps {

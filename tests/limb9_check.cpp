@@ -80,6 +80,52 @@ static int edge_pool_checks() {
 #undef ECHECK
     return bad;
 }
+// ---- fr9_canon above 2^261.  A thread of a round kernel that walks 64 items ends with accumulators of several hundred l (limb 8 beyond 29 bits);
+// fr9_canon takes q = limb 8 >> 20 and stays exact while that limb fits its 32 bits: any normalised value below 2^264.
+// The reference: the limbs' value mod l by Horner over field.h's additions (29 doublings per limb; a limb is a canonical word as it stands).
+static Fr fr9_value_ref(const Fr9 &a) {
+    Fr acc = fr_zero();
+    for (int i = 8; i >= 0; i--) {
+        for (int s = 0; s < 29; s++) acc = fr_add(acc, acc);
+        Fr limb = fr_zero(); limb.v[0] = a.v[i];
+        acc = fr_add(acc, limb);
+    }
+    return acc;
+}
+static int wide_sum_checks() {
+    int bad = 0;
+#define WCHECK(cond, what) do { if (!(cond)) { if (bad < 10) printf("FAIL wide sums: %s\n", what); bad++; } } while (0)
+    // running sums kept as the kernels keep them: normalised items (a product's output form) added without reduction, one carry sweep every fourth item,
+    // fr9_canon(fr9_norm(.)) at the end.  An item is 32 (x + y) < 64 l, so at most 63 of them stay below 4032 l < 2^264; every sum must END in [2^261, 2^264).
+    for (int it = 0; it < 600; it++) {
+        const bool top = it % 4 == 0;                                    // every item at its largest: x = y = l - 1
+        const int count = top ? 9 + it / 4 % 55 : 40 + it % 24;         // 9 .. 63 items of 64 (l - 1): 576 l .. 4032 l; 40 .. 63 random ones: about 32 l each
+        Fr9 acc = fr9_zero(); Fr want = fr_zero();
+        for (int k = 0; k < count; k++) {
+            const Fr x = top ? l_minus(1) : rnd_fr(), y = top ? l_minus(1) : rnd_fr();
+            const Fr9 item = fr9_norm(fr9_add(fr9_unpack5(x), fr9_unpack5(y)));
+            acc = fr9_add(acc, item); want = fr_add(want, fr9_value_ref(item));
+            if ((k & 3) == 3) acc = fr9_norm(acc);
+        }
+        const Fr9 end = fr9_norm(acc);
+        const uint32_t q = end.v[8] >> 20;
+        WCHECK(q >= 512, "a running sum ended below 2^261");            // (limb 8 is 32 bits: below 2^264 by the count above)
+        WCHECK(fr_eq(fr9_value_ref(end), want), "the reference disagrees with itself");
+        WCHECK(fr_eq(fr9_canon(end), want), "fr9_canon of a running sum between 2^261 and 2^264");
+    }
+    // the ends of the range, limb by limb: limb 8 around 2^29 (q = 511, 512), at every bit above it and at 2^32 - 1 (q = 4095), over low limbs of all ones,
+    // all zeros and random bits
+    const uint32_t tops[] = {0x1fffffffu, 0x20000000u, 0x200fffffu, 0x3fffffffu, 0x40000000u, 0x7fffffffu, 0x80000000u, 0xfff00000u, 0xffefffffu, 0xffffffffu};
+    for (uint32_t t8 : tops)
+        for (int low = 0; low < 6; low++) {
+            Fr9 a;
+            for (int i = 0; i < 8; i++) a.v[i] = low == 0 ? FR9_M : low == 1 ? 0u : ((uint32_t)rng() & FR9_M);
+            a.v[8] = t8;
+            WCHECK(fr_eq(fr9_canon(a), fr9_value_ref(a)), "fr9_canon at an end of its range");
+        }
+#undef WCHECK
+    return bad;
+}
 #define CHECK(cond, what) do { if (!(cond)) { if (bad < 10) printf("FAIL %s at iteration %d\n", what, it); bad++; } } while (0)
 int main(int argc, char **argv) {
     const int iters = argc > 1 ? atoi(argv[1]) : 20000;
@@ -127,6 +173,7 @@ int main(int argc, char **argv) {
         if (it % 61 == 0 || it < 40) { const Pt q = p9_pack(Q); CHECK(fp_eq(q.X, P.X) && fp_eq(q.Y, P.Y) && fp_eq(q.Z, P.Z) && fp_eq(q.T, P.T), "p9_madd"); }
     }
     bad += edge_pool_checks();
+    bad += wide_sum_checks();
     printf("limb9 check: %d failures\n", bad);
     return bad != 0;
 }

@@ -73,7 +73,9 @@ def _edge_tables(rng, n, count):
 @pytest.mark.parametrize("n,shift", [(8, 0), (1 << 11, 1), (1 << 15, 2), (1 << 17, 3)])
 def test_round_kernels_on_values_at_the_ends_of_the_field(rng, n, shift):
     """every round kernel of both sum-checks (three- and four-table cubic, quad; plain and fused with the fold) on tables full of l - 1, 0, 1,
-    2^252, limb-boundary values and mixtures — the nine-limb arithmetic's offsets, carries and accumulations at their extremes"""
+    2^252, limb-boundary values and mixtures — the nine-limb arithmetic's offsets and carries within ONE item: at these lengths every thread sums
+    exactly one item, and the pool holds extremes of the integer, not of the stored word.  Sums over several items of a thread, on extremes of the
+    stored word, are in tests/test_gpu_sumcheck_walks.py"""
     l = orc.L_ORDER
     T = _edge_tables(rng, n, 8)
     T = T[shift:] + T[:shift]

@@ -108,13 +108,17 @@ def test_pc_round_shapes(rng, batch, n):
     check_pc_round(*make_batch(kinds, iter(rolled(rng, 2 * n, 3 * len(kinds)))), tau, orc.rand_fr(rng, 1))
 
 
-@pytest.mark.parametrize("fold", [False, True])
-def test_pc_round_at_the_grid_cap(rng, fold):
-    """18 instances with 2^15 items each: 128 workgroups per instance wanted, 2048 / 18 = 113 given — the grid-stride loop runs a second time"""
+@pytest.mark.parametrize("fold,kind", [(False, "random"), (True, "random"), (False, "edge"), (True, "edge")], ids=["False", "True", "False-edge", "True-edge"])
+def test_pc_round_at_the_grid_cap(rng, fold, kind):
+    """18 instances with 2^15 items each: 128 workgroups per instance wanted, 2048 / 18 = 113 given — the grid-stride loop runs a second time, the only
+    place where a thread of k_pc_round adds a second item onto its unswept sums.  edge: the tables of edge_table (values and stored words at the ends
+    of their ranges, a 2^13 block repeated: the stride of 113 * 256 items is no multiple of it, so a thread's two items differ), folded by l - 1"""
     kinds = "pppppppptppppppppt" if fold else "ppt" * 6
     n = 1 << 17 if fold else 1 << 16
-    A, B, C = make_batch(kinds, iter(rolled(rng, n, 3 * len(kinds))))
-    check_pc_round(A, B, C, orc.rand_fr(rng, 15), orc.rand_fr(rng, 1) if fold else None)
+    tables = (edge_table(k, n) for k in range(3 * len(kinds))) if kind == "edge" else iter(rolled(rng, n, 3 * len(kinds)))
+    A, B, C = make_batch(kinds, tables)
+    r = (orc.fr_from_ints([l - 1]) if kind == "edge" else orc.rand_fr(rng, 1)) if fold else None
+    check_pc_round(A, B, C, orc.rand_fr(rng, 15), r)
 
 
 @pytest.mark.parametrize("G", [2, 4])
