@@ -142,7 +142,7 @@ int32_t otti_k_addr_timestamps(const uint32_t *h_addr3, size_t N, size_t M, uint
         c.sync(); return OTTI_OK;
     });
 }
-// the decommitment fill from entry lists (snark_prover.cpp decomm_fill_from_entries) on one matrix of a caller's host lists
+// the decommitment fill from entry lists (snark_encode.cpp decomm_fill_from_entries) on one matrix of a caller's host lists
 int32_t otti_k_decomm_entries(const uint32_t *h_row, const uint32_t *h_col, const uint8_t *h_val_mont32, size_t n, size_t N, size_t pad_to, uint32_t pad_col,
                               uint32_t *out_row_u32, uint32_t *out_col_u32, uint8_t *out_row_fr, uint8_t *out_col_fr, uint8_t *out_val_fr, float *ms) {
     return guarded([&] {
@@ -522,7 +522,7 @@ int32_t otti_k_bullet_last_fold(size_t R, const uint8_t *u, const uint8_t *uinv,
     });
 }
 
-// ---- SNARK mode's kernels (k_snark.hip, snark_dev.h): each entry stages the caller's tables and calls the launch function snark_prover.cpp calls.
+// ---- SNARK mode's kernels (k_snark.hip, snark_dev.h): each entry stages the caller's tables and calls the launch function the prover's sources (snark_encode.cpp, snark_pc.cpp, snark_prover.cpp) call.
 // Lists travel as ONE array: instance y's table at element y * len; third tables only for the instances that have one (has_C[y] != 0), in order.
 int32_t otti_k_pc_round(const uint8_t *A, const uint8_t *B, const uint8_t *C, const uint8_t *has_C, size_t ninst, size_t len, const uint8_t *tau, const uint8_t *r,
                         uint32_t G, uint32_t rk, uint8_t *out, uint8_t *e, float *ms) {

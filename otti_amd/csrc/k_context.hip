@@ -199,7 +199,7 @@ void dev_fr_to_lanes(hipStream_t st, const Fr *d_src, const Fr *factor, unsigned
     hipLaunchKernelGGL(k_fr_to_lanes, (unsigned)((n + 63) / 64), 64, 0, st, d_src, factor ? *factor : fr_zero(), factor ? 1 : 0, d_lanes, n);
 }
 // ONE stream for the process confined to all but a few CUs (hipExtStreamCreateWithCUMask), for chip-filling fixed-base MSM launches that run
-// BESIDE latency-bound rounds: SNARK mode's ahead-of-time derefs rows (snark_prover.cpp), and the witness commitments while several
+// BESIDE latency-bound rounds: SNARK mode's ahead-of-time derefs rows (snark_prover.cpp RowsAhead), and the witness commitments while several
 // proofs are in flight (prover.cpp) — an MSM workgroup holds its CU's registers for the whole launch, and without the mask a round's
 // kernel on another stream waits for one to end (profiles/r3_cumask_probe.txt: 2 ms against 18 us; profiles/r4_inflight_*: rounds
 // of 52-84 us on average with six proofs in flight).  Made on first use and kept: creating a stream while a proof runs stalls launches.

@@ -214,7 +214,7 @@ void dev_addr_timestamps(DevCtx &c, const AddrTs &a) {
 __device__ __forceinline__ Fr hash3(const Fr &addr, const Fr &val, const Fr &ts, const Fr &r, const Fr &r2, const Fr &gamma) {
     return fr_sub(fr_add(fr_add(fr_mul(ts, r2), fr_mul(val, r)), addr), gamma);
 }
-// A rank's residue class of a hashed vector (sharded SNARK::prove, snark_prover.cpp): local element j of a vector of 2 * half_loc elements is
+// A rank's residue class of a hashed vector (sharded SNARK::prove, snark_prover.cpp build_circuits): local element j of a vector of 2 * half_loc elements is
 // global element (j / half_loc) * half_glob + (j % half_loc) * G + rk — the circuit's input is its left half then its right half, and every
 // layer pairs index i with i + (side length) / 2, so both halves keep the elements with i = rk (mod G).  G = 1: the identity.
 struct ShardMap { size_t half_loc, half_glob; uint32_t G, rk; };

@@ -1,4 +1,4 @@
-// Layer plan of the batched product-circuit sum-check (snark_prover.cpp pcbatch_prove): which of a layer's rounds are a launch each, which the
+// Layer plan of the batched product-circuit sum-check (snark_pc.cpp pcbatch_prove): which of a layer's rounds are a launch each, which the
 // persistent tail (k_snark.hip k_pc_tail) plays, which the host; which launches are armed ahead of their challenge; where the layers the host
 // plays alone are exported to.  Pure arithmetic over the layer's shape and the process's knobs — standard library only, so a host compiler
 // can run it without HIP (tests/pc_plan_check.cpp pins the plans of the proofs' layers and the edges of the rule).

@@ -436,9 +436,7 @@ void r1cs_prove_device(Instance &I, DeviceWitness &wit, Gens &g, Transcript &tr,
         static_assert(sizeof(CPoint) == 32, "CPoint is 32 packed bytes");
         if (sh) sh->allgather(c.h_points, Ll * 32, P.comm_vars.data());       // rank order = row-block order
         else for (size_t i = 0; i < Lsz; i++) P.comm_vars[i] = point_at(c, i);
-        tr.append_message("poly_commitment", "poly_commitment_begin", 21);
-        for (auto &cp : P.comm_vars) tr.append_point("poly_commitment_share", cp.b);
-        tr.append_message("poly_commitment", "poly_commitment_end", 19);
+        append_poly_commitment(tr, "poly_commitment", P.comm_vars);
     }
     T.ms[0] = now_ms() - t0;
 

@@ -2,7 +2,7 @@
 // [RECALL upstream src/lib.rs (SNARKGens, SNARK), src/r1csinstance.rs (R1CSCommitment, R1CSEvalProof), src/sparse_mlpoly.rs,
 // src/product_tree.rs, src/sumcheck.rs (SumcheckInstanceProof::prove_cubic_batched); /root/reference/Spartan is an empty submodule].
 // Reached from `spzk verify <files>` WITHOUT --nizk (the reference's run.py passes --nizk, /root/reference/run.py:58,100; BASELINE.json's
-// metric names the SNARK).  Host objects and the verifier live in snark_host.cpp, the GPU prover in snark_prover.cpp, its kernels in
+// metric names the SNARK).  Host objects and the verifier live in snark_host.cpp, the GPU prover in snark_encode.cpp (encode, attach), snark_pc.cpp (product circuits) and snark_prover.cpp (prove), its kernels in
 // k_snark.hip; the R1CS satisfiability proof inside it is the same device code as NIZK mode (prover.cpp r1cs_prove_device).
 #pragma once
 #include "spartan.h"
@@ -16,7 +16,7 @@
 
 namespace otti {
 
-struct DeviceDecomm;                                         // snark_prover.cpp: the dense representation resident in HBM
+struct DeviceDecomm;                                         // snark_prover.h: the dense representation resident in HBM
 
 // lib.rs SNARKGens: gens_r1cs_sat (the NIZK generators) + gens_r1cs_eval = SparseMatPolyCommitmentGens {gens_ops, gens_mem, gens_derefs},
 // three PolyCommitmentGens over ONE SHAKE256 stream (label "gens_r1cs_eval"): a set for m variables is gens_n = P[0 .. R), gens_1.G = P[R],
@@ -60,6 +60,10 @@ struct SnarkProof {
 };
 
 void snark_append_comm(Transcript &tr, const CompComm &c);  // R1CSCommitment::append_to_transcript
+// transcript writers shared by the GPU prover and the host verifier (snark_host.cpp), which must hash identical transcripts
+void append_unipoly(Transcript &tr, const Fr *c, size_t n);             // UniPoly::append_to_transcript
+void append_evals4(Transcript &tr, const Evals4 &e, bool col);          // the four claim_{row,col}_eval_* lines
+Fr reduce_evals(std::vector<Fr> v, const std::vector<Fr> &ch);          // the n-to-1 reduction of claimed evaluations: bound_poly_var_bot, last challenge first
 // host verifier (snark_host.cpp): SNARK::verify
 int snark_verify(const CompComm &comm, const std::vector<Fr> &inputs, const SnarkGens &g, const void *tlabel, size_t tlabel_len, const uint8_t *proof, size_t proof_len);
 // R1CSProof::verify shared with NIZK mode (spartan_host.cpp): returns 0 and the challenges
@@ -129,7 +133,7 @@ private:
 };
 void dotproductlog_verify(const DotProductProofLog &pf, size_t n, const Gens &g, const PcView &v, Transcript &tr, const Fr *a, const CPoint &Cx, const CPoint &Cy, Deferred *later = nullptr);
 
-// GPU (snark_prover.cpp)
+// GPU (snark_encode.cpp: encode, attach; snark_prover.cpp: prove)
 struct SnarkTimings { double ms[10]; };                      // the six R1CSProof stages, [6] derefs commitment, [7] product circuits, [8] hash layer, [9] total
 std::unique_ptr<CompComm> snark_encode_gpu(Instance &inst, SnarkGens &g);
 // The prover's copy of a commitment that came as bytes: rebuilds the decommitment of `inst` in HBM (the same function SNARK::encode uses) and

@@ -1,4 +1,4 @@
-// Device-side interface of SNARK mode's kernels (k_snark.hip) for snark_prover.cpp.
+// Device-side interface of SNARK mode's kernels (k_snark.hip) for snark_encode.cpp, snark_pc.cpp and snark_prover.cpp.
 #pragma once
 #include "device.h"
 #include "pc_plan.h"

@@ -160,13 +160,7 @@ SnarkProof SnarkProof::parse(const uint8_t *p, size_t n) {
 }
 
 // ================================================================================================ verifier
-namespace {
-void append_u64(Transcript &tr, const char *label, uint64_t x) { uint8_t b[8]; for (int i = 0; i < 8; i++) { b[i] = (uint8_t)x; x >>= 8; } tr.append_message(label, b, 8); }
-void append_poly_commitment(Transcript &tr, const char *label, const std::vector<CPoint> &C) {
-    tr.append_message(label, "poly_commitment_begin", 21);
-    for (auto &c : C) tr.append_point("poly_commitment_share", c.b);
-    tr.append_message(label, "poly_commitment_end", 19);
-}
+// the transcript writers the GPU prover shares with this verifier (snark.h; append_poly_commitment: spartan.h)
 void append_unipoly(Transcript &tr, const Fr *c, size_t n) {
     tr.append_message("poly", "UniPoly_begin", 13);
     for (size_t i = 0; i < n; i++) tr.append_scalar("coeff", c[i]);
@@ -183,6 +177,8 @@ Fr reduce_evals(std::vector<Fr> v, const std::vector<Fr> &ch) {
     for (size_t i = ch.size(); i-- > 0;) { size_t h = v.size() / 2; for (size_t k = 0; k < h; k++) v[k] = fr_add(v[2 * k], fr_mul(ch[i], fr_sub(v[2 * k + 1], v[2 * k]))); v.resize(h); }
     return v[0];
 }
+namespace {
+void append_u64(Transcript &tr, const char *label, uint64_t x) { uint8_t b[8]; for (int i = 0; i < 8; i++) { b[i] = (uint8_t)x; x >>= 8; } tr.append_message(label, b, 8); }
 Fr hash3(const Fr &addr, const Fr &val, const Fr &ts, const Fr &r, const Fr &r2, const Fr &gamma) { return fr_sub(fr_add(fr_add(fr_mul(ts, r2), fr_mul(val, r)), addr), gamma); }
 // SumcheckInstanceProof::verify (degree 3, compressed polynomials)
 Fr sc_verify(const std::vector<Fr> &coeffs, Fr e, size_t rounds, Transcript &tr, std::vector<Fr> &r) {

@@ -99,6 +99,12 @@ std::vector<Fr> eq_evals_host(const Fr *r, size_t ell);                  // EqPo
 // ---------------------------------------------------------------------------------------------- proof layout
 typedef uint8_t Cmp[32];
 struct CPoint { uint8_t b[32]; };
+// PolyCommitment::append_to_transcript, for provers and verifiers of both modes alike
+inline void append_poly_commitment(Transcript &tr, const char *label, const std::vector<CPoint> &C) {
+    tr.append_message(label, "poly_commitment_begin", 21);
+    for (auto &p : C) tr.append_point("poly_commitment_share", p.b);
+    tr.append_message(label, "poly_commitment_end", 19);
+}
 // The verifiers' VARIABLE-base sums  sum_i s[i] * decode(C[i])  over the sqrt(V) row commitments of a polynomial commitment
 // (PolyEvalProof::verify: the points come from the proof / the computation commitment, so no table exists for them).  With a device:
 // begin() uploads the compressed points and starts their decompression at once — the commitments are known long before the

@@ -602,9 +602,7 @@ int r1cs_verify_host(const NizkProof &P, size_t N, size_t V, const std::vector<F
         const Fr one = fr_one();
         // R1CSProof::verify
         tr.append_protocol_name("R1CS proof");
-        tr.append_message("poly_commitment", "poly_commitment_begin", 21);
-        for (auto &c : P.comm_vars) tr.append_point("poly_commitment_share", c.b);
-        tr.append_message("poly_commitment", "poly_commitment_end", 19);
+        append_poly_commitment(tr, "poly_commitment", P.comm_vars);
         std::vector<Fr> tau = tr.challenge_vector("challenge_tau", nrx);
         CPoint claim_phase1; pt_encode(claim_phase1.b, commit_scalar_pt(g, g.sc_1, fr_zero(), fr_zero()));
         RowSum rows(P.comm_vars.data(), Lsz);                             // with a device: the row commitments start decompressing now

@@ -119,7 +119,7 @@ static bool write_file(const RunEnv &E, const char *path, const uint8_t *p, size
 struct SnarkRoleArgs { char role; std::vector<const char *> files; const char *comm_in, *comm_out, *proof_in, *proof_out, *label; const uint8_t *seed; bool check, verify_comm; double t_main0; };
 // A SERVED request, in NIZK and in SNARK mode alike, takes the files to a ready instance in one call (otti_instance_from_zkif, OTTI_INGEST_AUTO: on the
 // device when the circuit's size allows — the worker's runtime is up).  SNARK encode / attach fill the decommitment from the entry lists the device
-// ingest keeps in HBM (snark_prover.cpp decomm_fill_from_entries): no host lists are made for them.  The one-shot keeps the host path (it parses
+// ingest keeps in HBM (snark_encode.cpp decomm_fill_from_entries): no host lists are made for them.  The one-shot keeps the host path (it parses
 // while its HIP runtime comes up).  After a device ingest the assignment's A, B, C are NULL: only their counts are set.
 // SNARK requests take it from kServedSnarkMinMB MiB of circuit file on only: measured (profiles/snark_zkif_ingest.md, tools/snark_ingest_probe.py), a
 // served `prove --comm-in` of the smallest probed circuit (2^16 uniform, 15.2 MiB) came out slower than the parent's host path at the median (39.7
