@@ -174,6 +174,28 @@ int32_t otti_nizk_prove_sharded(otti_instance *inst, otti_witness *wit, otti_gen
 /* NIZK::verify(&self, &inst, &inputs, &mut Transcript::new(tlabel), &gens) -> Result<(), ProofVerifyError> */
 int32_t otti_nizk_verify(const otti_instance *inst, const uint8_t *inputs32, size_t ninputs, const otti_gens *gens,
                          const uint8_t *tlabel, size_t tlabel_len, const uint8_t *proof, size_t proof_len);
+/* Many NIZK proofs of ONE instance verified in one call: what a verifier that holds one circuit and a pile of proofs makes, instead of one
+   otti_nizk_verify per caller thread.
+   Verdict rule: results[i] = what otti_nizk_verify returns for (inputs32[i], ninputs[i], proofs[i], proof_lens[i]) with the same instance,
+   generators and label — 0 accepted, otherwise that call's code (a proof that does not parse: OTTI_ERR_MALFORMED_PROOF; rx / ry of other lengths
+   than the instance's: OTTI_ERR_VERIFY_INTERNAL; a wrong count of inputs: OTTI_ERR_INVALID_NUM_INPUTS; an input >= l: OTTI_ERR_INVALID_SCALAR).
+   This is NOT a random-linear-combination batch: every proof goes through the single verifier's own steps, no soundness argument changes and no
+   verdict depends on its neighbours.  What the proofs share is the circuit: with a device and at least 4096 constraints, A, B, C are evaluated at
+   the points of all proofs that parse in one batched pass, one walk over the matrices per four points (otti_k_instance_evaluate is that pass alone).
+   Threading: the call blocks.  Its workers are the library's own: `threads` of them (0: the default, 4; more than 16: OTTI_ERR_BAD_ARG; never more
+   than there are proofs) walk the proofs, each with its own transcript and helper session, so the host cores are shared out by the library; they
+   are joined before the call returns.  threads = 1, or one proof, runs on the calling thread exactly as otti_nizk_verify does.  Several caller
+   threads may call with the same handles at once.
+   HBM: the batched evaluation keeps at most 8 points resident: their eq(ry) tables, 2V * 32 * 8 bytes (512 MB at V = 2^20, padded size), and the
+   two factors of each eq(rx) table (at most 2^12 + 2^13 scalars: 3.1 MB together; the tables themselves, 32 N bytes per point, are never written),
+   plus under 1 MB of partial sums and 96 bytes per proof of results — per calling thread, grow-only and kept across calls.  More proofs run in
+   chunks of 8.  Workers that sum row commitments on the device use their own contexts' buffers, as otti_nizk_verify does.
+   Returns OTTI_OK when the call ran, whatever the verdicts; *n_rejected (may be NULL) = the number of non-zero results, which otti_last_error
+   also names.  OTTI_ERR_BAD_ARG, before anything is touched: a null inst, gens or results; with count > 0 a null inputs32, ninputs, proofs or
+   proof_lens array or a null proofs[i] (inputs32[i] may be NULL where ninputs[i] is 0); threads > 16.  count == 0: OTTI_OK, nothing done. */
+int32_t otti_nizk_verify_many(const otti_instance *inst, const otti_gens *gens, const uint8_t *tlabel, size_t tlabel_len, size_t count,
+                              const uint8_t *const *inputs32, const size_t *ninputs, const uint8_t *const *proofs, const size_t *proof_lens,
+                              uint32_t threads, int32_t *results, size_t *n_rejected /* may be NULL */);
 /* ---- SNARK mode (`spzk verify` without --nizk): upstream lib.rs SNARKGens / ComputationCommitment / SNARK [RECALL].
    otti_snark_encode = SNARK::encode (once per circuit: the commitment to A, B, C — on the GPU); otti_snark_prove = SNARK::prove
    (R1CSProof as in NIZK mode + R1CSEvalProof: memory-checking product circuits, batched cubic sum-checks, three polynomial
@@ -503,6 +525,11 @@ int32_t otti_k_products_patch(otti_instance *inst, const uint8_t *h_z_new, const
                               uint32_t *h_rows, size_t n_rows_cap, uint64_t *n_touched, int32_t *took_full_pass, float *kernel_ms);
 /* compute_eval_table_sparse x3 fused with r_A*A + r_B*B + r_C*C: eq_rx has num_cons entries, out 2*num_vars */
 int32_t otti_k_eval_table_sparse(otti_instance *inst, const uint8_t *h_eq_rx, const uint8_t *h_rABC /* 3 */, uint8_t *h_out, float *kernel_ms);
+/* R1CSInstance::evaluate at K points in one batched pass (the verifier's evaluation in otti_nizk_verify_many; always the many-point kernels, K = 1
+   included).  out32: K x 3 scalars, A, B, C at each point; rx: K x log2(padded num_cons), ry: K x log2(2 * padded num_vars) scalars, conventions of
+   otti_k_eq_evals (Montgomery words in and out, MSB first).  kernel_ms: the eq tables and the evaluation, first launch to last.  HBM as stated
+   at otti_nizk_verify_many.  OTTI_ERR_BAD_ARG for a null inst, or null rx32 / ry32 / out32 with K > 0; OTTI_ERR_NO_DEVICE without a device. */
+int32_t otti_k_instance_evaluate(otti_instance *inst, const uint8_t *rx32, const uint8_t *ry32, size_t K, uint8_t *out32, float *kernel_ms);
 /* which of their variants the three sparse passes above and below (multiply_vec / the satisfiability pass: by_col = 0; eval_table_sparse:
    by_col != 0, rows = 2*num_vars) run on this instance.  quad: a row per four lanes (else per lane); use_small: entries are read through 4-byte
    small-integer codes; n_heavy rows whose longest list exceeds 64 entries go through n_seg segments of 2048.  Makes the device copy of the

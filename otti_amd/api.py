@@ -115,6 +115,8 @@ _sig("otti_shard_allreduce", _i32, _vp, _sz)
 _sig("otti_nizk_prove_sharded", _i32, _vp, _vp, _vp, ctypes.c_char_p, _sz, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_sz),
      ctypes.POINTER(ctypes.c_double))
 _sig("otti_nizk_verify", _i32, _vp, _vp, _sz, _vp, ctypes.c_char_p, _sz, _vp, _sz)
+_sig("otti_nizk_verify_many", _i32, _vp, _vp, ctypes.c_char_p, _sz, _sz, ctypes.POINTER(_vp), ctypes.POINTER(_sz), ctypes.POINTER(_vp), ctypes.POINTER(_sz),
+     ctypes.c_uint32, ctypes.POINTER(_i32), ctypes.POINTER(_sz))
 _sig("otti_prepare_device", _i32, _vp, _vp)
 _sig("otti_snark_gens_new", _i32, _u64, _u64, _u64, _u64, ctypes.POINTER(_vp))
 _sig("otti_snark_gens_free", None, _vp)
@@ -156,6 +158,7 @@ _sig("otti_k_multiply_vec", _i32, _vp, _vp, _vp, _vp, _vp, _fp)
 _sig("otti_k_eval_table_sparse", _i32, _vp, _vp, _vp, _vp, _fp)
 _sig("otti_k_products_patch", _i32, _vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, ctypes.POINTER(_u64), _vp, _sz, ctypes.POINTER(_u64), ctypes.POINTER(_i32), _fp)
 _sig("otti_instance_device_info", _i32, _vp, _i32, ctypes.POINTER(_DeviceInfo))
+_sig("otti_k_instance_evaluate", _i32, _vp, _vp, _vp, _sz, _vp, _fp)
 _sig("otti_instance_from_zkif", _i32, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, _i32, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.POINTER(_R1CS)))
 _sig("otti_instance_entries", _i32, _vp, _i32, _vp, _sz, ctypes.POINTER(_sz))
 _sig("otti_instance_ingest_info", _i32, _vp, ctypes.POINTER(_i32), ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(ctypes.c_double))
@@ -814,6 +817,31 @@ class NIZK:
         buf = np.frombuffer(self.bytes, dtype=np.uint8)
         _check(lib.otti_nizk_verify(inst._h, _ptr(i), i.shape[0], gens._h, label, len(label), _ptr(buf), buf.size))
 
+    @staticmethod
+    def verify_many(inst, proofs, inputs, gens, transcript_label=b"nizk_example", threads=0):
+        """Many proofs of ONE instance in one call (otti_nizk_verify_many): ``proofs`` are NIZK objects or bytes, ``inputs`` one InputsAssignment for
+        all of them or one per proof.  Returns the list of result codes — element i is what ``verify`` on proof i alone would report, 0 = accepted —
+        so a rejected proof raises nothing; only the call's own refusals (bad arguments) raise.  Not a randomised batch: no verdict depends on
+        another proof.  ``threads``: the library's worker threads, 0 = its default, at most 16; the call blocks until all are done."""
+        label = bytes(transcript_label)
+        blobs = [np.frombuffer(bytes(p.bytes if isinstance(p, NIZK) else p), dtype=np.uint8) for p in proofs]
+        n = len(blobs)
+        per = list(inputs) if isinstance(inputs, (list, tuple)) else [inputs] * n
+        if len(per) != n:
+            raise ValueError("verify_many: one InputsAssignment for all proofs, or one per proof")
+        ins = [_scalars(i.assignment, "inputs") for i in per]
+        in_ptrs, in_counts = (_vp * max(1, n))(), (_sz * max(1, n))()
+        pf_ptrs, pf_lens = (_vp * max(1, n))(), (_sz * max(1, n))()
+        empty = np.zeros(1, dtype=np.uint8)
+        for k in range(n):
+            in_ptrs[k], in_counts[k] = _ptr(ins[k]), ins[k].shape[0]
+            pf_ptrs[k], pf_lens[k] = (blobs[k] if blobs[k].size else empty).ctypes.data_as(_vp), blobs[k].size   # an empty proof is a malformed one, not a null pointer
+        results, rejected = (_i32 * max(1, n))(), _sz(0)
+        _check(lib.otti_nizk_verify_many(inst._h, gens._h, label, len(label), n, in_ptrs, in_counts, pf_ptrs, pf_lens, threads, results, ctypes.byref(rejected)))
+        out = [int(results[k]) for k in range(n)]
+        assert rejected.value == sum(1 for r in out if r != 0)
+        return out
+
 
 # ---------------------------------------------------------------------------------------------- SNARK mode (lib.rs SNARKGens / SNARK)
 class SNARKGens:
@@ -1241,6 +1269,19 @@ class kernels:
         assert eq_rx.shape[0] == nc and rABC.shape[0] == 3
         out = np.zeros((2 * nv, 32), dtype=np.uint8); ms = ctypes.c_float(0)
         _check(lib.otti_k_eval_table_sparse(inst._h, _ptr(eq_rx), _ptr(rABC), _ptr(out), ctypes.byref(ms)))
+        return out, ms.value
+
+    @staticmethod
+    def instance_evaluate(inst, rx, ry):
+        """otti_k_instance_evaluate: A, B, C at K points in one batched pass.  rx: (K, log2 num_cons, 32), ry: (K, log2(2 num_vars), 32) Montgomery
+        words (or the same flattened to (K * ell, 32)); returns ((K, 3, 32) Montgomery words, kernel_ms)"""
+        nc, nv, _ = inst.dims
+        nrx, nry = nc.bit_length() - 1, (2 * nv).bit_length() - 1
+        rx = np.ascontiguousarray(rx, dtype=np.uint8).reshape(-1, 32); ry = np.ascontiguousarray(ry, dtype=np.uint8).reshape(-1, 32)
+        k = rx.shape[0] // nrx if nrx else ry.shape[0] // nry
+        assert rx.shape[0] == k * nrx and ry.shape[0] == k * nry
+        out = np.zeros((k, 3, 32), dtype=np.uint8); ms = ctypes.c_float(0)
+        _check(lib.otti_k_instance_evaluate(inst._h, _ptr(rx), _ptr(ry), k, _ptr(out), ctypes.byref(ms)))
         return out, ms.value
 
     @staticmethod

@@ -417,6 +417,26 @@ int32_t otti_nizk_verify(const otti_instance *inst, const uint8_t *inputs32, siz
         return rc;
     });
 }
+int32_t otti_nizk_verify_many(const otti_instance *inst, const otti_gens *gens, const uint8_t *tlabel, size_t tlabel_len, size_t count,
+                              const uint8_t *const *inputs32, const size_t *ninputs, const uint8_t *const *proofs, const size_t *proof_lens,
+                              uint32_t threads, int32_t *results, size_t *n_rejected) {
+    return guarded([&] {
+        if (!inst || !gens || !results) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (threads > kVerifyManyMaxThreads) throw Error(OTTI_ERR_BAD_ARG, "more than 16 worker threads");
+        if (count && (!inputs32 || !ninputs || !proofs || !proof_lens)) throw Error(OTTI_ERR_BAD_ARG, "a null array with count > 0");
+        for (size_t i = 0; i < count; i++) if (!proofs[i] || (ninputs[i] && !inputs32[i])) throw Error(OTTI_ERR_BAD_ARG, "a null proof, or null inputs with a non-zero count");
+        if (n_rejected) *n_rejected = 0;
+        if (!count) return OTTI_OK;
+        std::vector<VerifyItem> items(count);
+        for (size_t i = 0; i < count; i++) items[i] = {inputs32[i], ninputs[i], proofs[i], proof_lens[i]};
+        nizk_verify_many(*inst->I, *gens->g, tlabel, tlabel_len, items.data(), count, threads, results);
+        size_t bad = 0;
+        for (size_t i = 0; i < count; i++) bad += results[i] != OTTI_OK;
+        if (n_rejected) *n_rejected = bad;
+        if (bad) g_last_error = std::to_string(bad) + " of " + std::to_string(count) + " proofs rejected";
+        return OTTI_OK;
+    });
+}
 
 // ------------------------------------------------------------------------------------------------ SNARK mode
 int32_t otti_snark_gens_new(uint64_t nc, uint64_t nv, uint64_t ni, uint64_t nnz, otti_snark_gens **out) {

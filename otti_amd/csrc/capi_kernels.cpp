@@ -232,6 +232,23 @@ int32_t otti_k_eval_table_sparse(otti_instance *inst, const uint8_t *eq_rx, cons
         download(c, out, o.p, 2 * I.num_vars); c.sync(); return OTTI_OK;
     });
 }
+int32_t otti_k_instance_evaluate(otti_instance *inst, const uint8_t *rx32, const uint8_t *ry32, size_t K, uint8_t *out32, float *ms) {
+    return guarded([&] {
+        if (!inst || (K && (!rx32 || !ry32 || !out32))) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (ms) *ms = 0;
+        DevCtx::get();                                             // OTTI_ERR_NO_DEVICE without a device
+        if (!K) return OTTI_OK;
+        Instance &I = *inst->I;
+        const size_t nrx = ilog2(I.num_cons), nry = ilog2(2 * I.num_vars);
+        std::vector<Fr> rx(K * nrx + 1), ry(K * nry + 1);
+        for (size_t i = 0; i < K * nrx; i++) rx[i] = fr_load(rx32 + 32 * i);
+        for (size_t i = 0; i < K * nry; i++) ry[i] = fr_load(ry32 + 32 * i);
+        std::vector<Fr> out(3 * K);
+        instance_evaluate_many(I, rx.data(), nrx, ry.data(), nry, K, reinterpret_cast<Fr (*)[3]>(out.data()), ms);
+        memcpy(out32, out.data(), 3 * K * sizeof(Fr));
+        return OTTI_OK;
+    });
+}
 int32_t otti_instance_device_info(otti_instance *inst, int32_t by_col, otti_device_info *out) {
     return guarded([&] {
         if (!inst || !out) throw Error(OTTI_ERR_BAD_ARG, "null argument");

@@ -182,6 +182,7 @@ struct DevCtx {
     DevCtx() {} DevCtx(const DevCtx &) = delete; DevCtx &operator=(const DevCtx &) = delete;
     struct Scratch *scratch = nullptr;                        // the prover's HBM workspace (prover.cpp); travels with the context
     struct SnarkScratch *snark_scratch = nullptr;             // SNARK mode's per-proof buffers (snark_prover.h), kept across proofs like the above
+    struct EvalManyScratch *eval_many = nullptr;              // the many-point instance evaluation's tables and result memory (prover.cpp), grow-only, kept likewise
     void sync();
     void wait_points(const MsmTicket &ticket);                // results of a dev_msm_rows / dev_bullet_round launch, by the ticket's route (msm_plan.h)
     void encode_pending();
@@ -308,6 +309,22 @@ constexpr int kInstEvalSlot = 16;                            // result slots of 
 void instance_evaluate_begin(Instance &I, const std::vector<Fr> &rx, const std::vector<Fr> &ry);      // queued on the calling thread's stream
 void instance_evaluate_finish(Fr out[3]);                                                              // same thread: waits, reads
 void instance_evaluate_gpu(Instance &I, const std::vector<Fr> &rx, const std::vector<Fr> &ry, Fr out[3]);
+// The same three values at SEVERAL points (the points of many proofs of one instance: verify_many.cpp) with one walk over the matrices per tile of
+// kEvalTile points instead of one per point (k_sparse.hip dev_eval_tile); Az, Bz, Cz are never formed.  begin queues everything on the calling
+// thread's stream and returns; next / finish, on the same thread, wait and copy out[i] = (A, B, C)(rx_i, ry_i), i < the count begin was given.  Result
+// memory is the pass's own (pinned, K x 3 elements): kInstEvalSlot is not touched.  Every proof's rx / ry must have the instance's lengths
+// (OTTI_ERR_VERIFY_INTERNAL otherwise, before anything is queued).
+// HBM: working memory is grow-only, per calling context and kept across calls, as the proof workspace is.  At most kEvalChunk points are resident at
+// a time: their eq(ry) tables, 2V * 32 * kEvalChunk bytes (512 MB at V = 2^20), the factors of their eq(rx) tables (at most 2^12 + 2^13 elements
+// each: 3.1 MB; the tables themselves, 32 N bytes per point, are never written), the workgroups' partial sums (under 1 MB, plus 384 bytes per
+// segment of a long row) and 96 bytes per point of results.  A larger K runs in chunks of kEvalChunk, queued one behind the other.
+constexpr int kEvalTile = 4;                                 // KT: points per walk over the matrices (profiles/verify_many.md)
+constexpr size_t kEvalChunk = 8;                             // points whose eq tables are resident at a time
+void instance_evaluate_many_begin(Instance &I, const std::vector<const NizkProof *> &proofs);
+size_t instance_evaluate_many_next(Fr (*out)[3]);            // same thread: waits for the next tile, copies its values; returns how many points are in `out` by now
+void instance_evaluate_many_finish(Fr (*out)[3]);            // same thread: every tile that is still out
+// the same with host arrays of challenges (rx: K x log2 N, ry: K x log2 2V) and the device time of the pass from first launch to last
+void instance_evaluate_many(Instance &I, const Fr *rx, size_t nrx, const Fr *ry, size_t nry, size_t K, Fr (*out)[3], float *kernel_ms);
 // sh == nullptr (or a world of one): the whole proof on this GPU.  Otherwise this process proves its shard of the SAME proof as the
 // other ranks of sh (collective call: same instance, witness, generators, label and seed on every rank); every rank returns the
 // same bytes, equal to the single-GPU proof.
@@ -368,6 +385,20 @@ void dev_to_canonical(DevCtx &c, const Fr *in, Fr *out, size_t n);
 void dev_fill_zero(DevCtx &c, Fr *p, size_t n);
 // ---- K1 / K6: sparse products.  combine == false: out[k][r] = sum_p val_k[p] * x[idx_k[p]];  true: out[0][r] = sum_k coef[k] * (...)
 void dev_spmv3(DevCtx &c, const DeviceCsrSet &m, const Fr *x, Fr *out0, Fr *out1, Fr *out2, bool combine, const Fr coef[3]);
+// ---- A, B, C at a tile of nt <= kEvalTile points in one walk over the by-row set m (k_sparse.hip; every variant dev_spmv3 has: lane / quad, codes
+// on / off, segmented long lists).  ey_il: the tile's eq(ry) tables interleaved, ey_il[col * kEvalTile + t] (2V * kEvalTile elements);
+// dev_eval_point_y writes point t's table there straight from its two factors (dev_eq_factors: eq(r)[i] = hi[i >> lo_bits] * lo[i & (2^lo_bits - 1)],
+// lo_bits = min(ell, 12)).  eq(rx_t) is read as its FACTORS, interleaved likewise: xlo[j * kEvalTile + t] (2^lo_bits * kEvalTile elements),
+// xhi[h * kEvalTile + t] (2^hi_bits * kEvalTile); dev_eval_point_x puts point t's there.  r: host arrays, ell <= 25; scratch: 4096 + 8192 elements.
+// dev_eval_tile: partial: 3 * kEvalTile * dev_eval_partial_slots(m) elements, seg_partial: 3 * kEvalTile * m.n_seg; out[t * 3 + k] (device memory),
+// t < nt.  Slots t >= nt are neither read nor written.  All only queue.
+struct EvalFactors { int lo_bits, hi_bits; };
+EvalFactors eval_factors(size_t ell);
+struct EvalTables { const Fr *xlo, *xhi, *ey_il; int xlo_bits; };
+size_t dev_eval_partial_slots(const DeviceCsrSet &m);
+void dev_eval_point_x(DevCtx &c, const Fr *r_host, size_t ell, int t, Fr *xlo_il, Fr *xhi_il, Fr *scratch);
+void dev_eval_point_y(DevCtx &c, const Fr *r_host, size_t ell, int t, Fr *ey_il, Fr *scratch);
+void dev_eval_tile(DevCtx &c, const DeviceCsrSet &m, const EvalTables &tab, int nt, Fr *partial, Fr *seg_partial, Fr *out);
 // ---- Instance::is_sat on the device (k_sparse.hip): per constraint row r the three sums of dev_spmv3 and <A_r,z> <B_r,z> == <C_r,z>; Az, Bz, Cz
 // are never written.  dev_sat_pass only queues: bits[r >> 6] bit (r & 63) is set for every FAILING row (all (rows + 63) / 64 words are written: no
 // zeroing beforehand), c.d_counts[0] holds their number.  dev_check_sat runs it into the context's own bitmap, reads the count through the pinned
@@ -403,6 +434,7 @@ void dev_sat_report(DevCtx &c, DeviceInstance &d, const Fr *z, const unsigned lo
 // ---- K2: eq tables.  r is a HOST array (challenges come from the transcript)
 void dev_eq_evals(DevCtx &c, const Fr *r_host, size_t ell, Fr *out, Fr *scratch /* >= 3 * 4096 elements; 5 * 4096 for ell = 25 */);
 void dev_eq_evals2(DevCtx &c, const Fr *r0_host, size_t ell0, Fr *out0, const Fr *r1_host, size_t ell1, Fr *out1, Fr *scratch);   // both in one launch when each has at most 13 variables
+void dev_eq_factors(DevCtx &c, const Fr *r_host, size_t ell, size_t lo_bits, Fr *lo /* 2^lo_bits */, Fr *hi /* 2^(ell - lo_bits) */);   // eq(r)[i] = hi[i >> lo_bits] * lo[i & (2^lo_bits - 1)]: the factors alone, one launch
 // ---- K3/K4/K5/K7: sum-check rounds.  Results land in c.h_results[slot .. slot+k)
 // each returns a ticket: c.wait_ticket(ticket) returns once h_results[slot..] hold that launch's sums (no stream synchronise)
 unsigned long long dev_sc_cubic_eval(DevCtx &c, const Fr *A, const Fr *B, const Fr *C, const Fr *D, size_t len, int slot);

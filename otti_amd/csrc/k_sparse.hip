@@ -112,6 +112,230 @@ void dev_spmv3(DevCtx &c, const DeviceCsrSet &m, const Fr *x, Fr *o0, Fr *o1, Fr
     }
 }
 
+// ------------------------------------------------------------------------------------------------ A, B, C at a tile of points (device.h dev_eval_tile)
+// M_k(rx_t, ry_t) = sum over M_k's entries (r, c, v) of v ex_t[r] ey_t[c] for the nt <= KT points of a tile, in ONE walk over the by-row set: an
+// entry's index, code and — for a wide coefficient — value and shifted unpack are loaded once and applied to the tile's KT values of column c.
+// eq(ry): the tile's tables are stored interleaved, ey_il[col][KT], so one gather of a column brings the values of all KT points in one 32 KT-byte
+// run; k_eval_expand writes them that way straight from the two factors of each table (eq(r)[i] = hi[i >> lo_bits] * lo[i & (2^lo_bits - 1)], as
+// k_eq_expand forms it) — no table is staged and transposed.  eq(rx) is never written out at all: it is needed once per row, point and matrix, and
+// the kernels multiply its two factors, of at most 2^12 and 2^13 elements and interleaved likewise (xlo[j][KT], xhi[h][KT]: they stay in the caches),
+// where a row is finished.  The rows one thread walks share the low factor (eval_row_done), so that costs one product per row, as a table would.
+// (Measured on the way, profiles/verify_many.md: with eq(ry) from its factors as well the walk costs a product more per ENTRY and point, and the
+// compiler-like instance, whose walk the multiplier bounds, took 1.5 x the single evaluations' time; with both tables written out, staged and
+// transposed, the uniform one took 1.25 x.)
+// A row's inner sums are multiplied by ex_t[r] and added to the thread's running totals; Az, Bz, Cz are never written.  The totals are kept for ONE
+// matrix at a time (KT elements: the three matrices are three walks over the rows' pointers), reduced over the workgroup and stored as its partial;
+// k_eval_finish adds the partials up.  Every word is canonical after every step (comment above row_fails), so the sums do not depend on the
+// geometry.  Slots t >= nt of a short tile are neither read nor accumulated: their totals stay zero.
+template <int KT> struct EvalTile { const Fr *xlo, *xhi, *ey_il; int xlo_bits, nt; };
+__device__ __forceinline__ bool eval_row_heavy(const DCsr3 &m, size_t r) {       // the rule of k_spmv3_light: such a row is the segmented path's
+    return max(m.ptr[0][r + 1] - m.ptr[0][r], max(m.ptr[1][r + 1] - m.ptr[1][r], m.ptr[2][r + 1] - m.ptr[2][r])) > (uint32_t)kHeavyRow;
+}
+__device__ __forceinline__ Fr mul9(const Fr &a, const Fr &b) { return fr9_pack_lt2l(fr9_mul(fr9_unpack5(a), fr9_unpack(b))); }   // 32 a b / 2^261 + l < 1.1 l
+// element i of point t's table from its interleaved factors
+template <int KT> __device__ __forceinline__ Fr eval_eq_at(const Fr *lo_il, const Fr *hi_il, int lo_bits, size_t i, int t) {
+    return mul9(hi_il[(i >> lo_bits) * KT + t], lo_il[(i & (((size_t)1 << lo_bits) - 1)) * KT + t]);
+}
+template <bool kSmall, int KT> __device__ __forceinline__ void entry_terms(const DCsr3 &m, int k, uint32_t p, const EvalTile<KT> &T, Fr (&acc)[KT]) {
+    const Fr *xv = T.ey_il + (size_t)m.idx[k][p] * KT;
+    if (kSmall) {
+        const int32_t c = m.small[k][p];
+        if (c != kNotSmall) {
+#pragma unroll
+            for (int t = 0; t < KT; t++) if (t < T.nt) acc[t] = fr_add(acc[t], fr_mul_small(xv[t], c));
+            return;
+        }
+    }
+    const Fr9 v5 = fr9_unpack5(m.val[k][p]);
+#pragma unroll
+    for (int t = 0; t < KT; t++) if (t < T.nt) acc[t] = fr_add(acc[t], fr9_pack_lt2l(fr9_mul(v5, fr9_unpack(xv[t]))));
+}
+template <int KT> __device__ __forceinline__ void eval_zero(Fr (&a)[KT]) {
+#pragma unroll
+    for (int t = 0; t < KT; t++) a[t] = fr_zero();
+}
+// The rows one thread walks lie a multiple of 2^xlo_bits apart (dev_eval_tile checks the launch geometry), so the low factor xlo_t[r & mask] is the
+// SAME for all of them: a row costs one product with the high factor, tot[t] += xhi_t[r >> xlo_bits] * in[t], and the low factor is applied once,
+// to the thread's total (eval_apply_low), before the workgroup adds up.
+template <int KT> __device__ __forceinline__ void eval_row_done(const EvalTile<KT> &T, size_t r, const Fr (&in)[KT], Fr (&tot)[KT]) {
+    const Fr *hi = T.xhi + (r >> T.xlo_bits) * KT;
+#pragma unroll
+    for (int t = 0; t < KT; t++) if (t < T.nt) tot[t] = fr_add(tot[t], mul9(hi[t], in[t]));
+}
+template <int KT> __device__ __forceinline__ void eval_apply_low(const EvalTile<KT> &T, size_t first_row, Fr (&tot)[KT]) {
+    const Fr *lo = T.xlo + (first_row & (((size_t)1 << T.xlo_bits) - 1)) * KT;
+#pragma unroll
+    for (int t = 0; t < KT; t++) if (t < T.nt) tot[t] = mul9(lo[t], tot[t]);
+}
+// a workgroup's totals of matrix k: partial[(workgroup * 3 + k) * KT + t]
+template <int KT> __device__ __forceinline__ void eval_store_partial(Fr (&tot)[KT], Fr *partial, size_t slot, int k) {
+    block_reduce<KT>(tot);
+    if (threadIdx.x == 0)
+#pragma unroll
+        for (int t = 0; t < KT; t++) partial[(slot * 3 + k) * KT + t] = tot[t];
+}
+// row per lane (k_spmv3_light's layout)
+template <bool kSmall, int KT> __global__ __launch_bounds__(kBlock) void k_eval_light(DCsr3 m, size_t rows, EvalTile<KT> T, Fr *partial) {
+    const size_t r0 = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+#pragma unroll 1
+    for (int k = 0; k < 3; k++) {
+        Fr tot[KT]; eval_zero<KT>(tot);
+        for (size_t r = r0; r < rows; r += (size_t)gridDim.x * blockDim.x) {
+            if (eval_row_heavy(m, r)) continue;
+            const uint32_t p0 = m.ptr[k][r], p1 = m.ptr[k][r + 1];
+            if (p0 == p1) continue;
+            Fr in[KT]; eval_zero<KT>(in);
+            for (uint32_t p = p0; p < p1; p++) entry_terms<kSmall, KT>(m, k, p, T, in);
+            eval_row_done<KT>(T, r, in, tot);
+        }
+        eval_apply_low<KT>(T, r0, tot);
+        eval_store_partial<KT>(tot, partial, blockIdx.x, k);
+    }
+}
+// row per quad (k_spmv3_quad's layout and walk): rows are padded to whole waves so that every lane takes part in the shuffles.  After quad_sum all four
+// lanes of a quad hold the row's KT inner sums: lane q of the quad takes point q — one product with the high factor per lane, not KT of them on one
+// lane with three idle — and keeps ONE running total, that of its point.  The totals of a point then sit in the lanes q = t of every quad: they are
+// added up over the wave by shuffles that keep q (offsets 4 .. 32), over the workgroup through LDS.
+template <bool kSmall, int KT> __global__ __launch_bounds__(kBlock) void k_eval_quad(DCsr3 m, size_t rows, EvalTile<KT> T, Fr *partial) {
+    static_assert(KT <= 4, "a quad's four lanes take a point each");
+    __shared__ Fr sm[KT][16];
+    const int q = threadIdx.x & 3, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const size_t r0 = (blockIdx.x * (size_t)blockDim.x + threadIdx.x) >> 2;
+    const bool mine_live = q < T.nt;
+#pragma unroll 1
+    for (int k = 0; k < 3; k++) {
+        Fr tot = fr_zero();
+        for (size_t r = r0; r < ((rows + 63) & ~(size_t)63); r += ((size_t)gridDim.x * blockDim.x) >> 2) {
+            Fr in[KT]; eval_zero<KT>(in);
+            const bool live = r < rows && !eval_row_heavy(m, r);
+            if (live) {
+                const uint32_t p1 = m.ptr[k][r + 1];
+                for (uint32_t p = m.ptr[k][r] + (uint32_t)q; p < p1; p += 4) entry_terms<kSmall, KT>(m, k, p, T, in);
+            }
+#pragma unroll
+            for (int t = 0; t < KT; t++) in[t] = quad_sum(in[t]);          // every lane of the wave takes part
+            Fr mine = in[0];
+#pragma unroll
+            for (int t = 1; t < KT; t++) if (q == t) mine = in[t];
+            if (live && mine_live) tot = fr_add(tot, mul9(T.xhi[(r >> T.xlo_bits) * KT + q], mine));
+        }
+        if (mine_live) tot = mul9(T.xlo[(r0 & (((size_t)1 << T.xlo_bits) - 1)) * KT + q], tot);
+#pragma unroll
+        for (int off = 32; off >= 4; off >>= 1) tot = fr_add(tot, shfl_xor_fr(tot, off));
+        __syncthreads();                                                   // sm may still be read for the matrix before
+        if (lane < KT) sm[lane][wave] = tot;
+        __syncthreads();
+        if (threadIdx.x < KT) {
+            Fr s = sm[threadIdx.x][0];
+            for (int w = 1; w < nw; w++) s = fr_add(s, sm[threadIdx.x][w]);
+            partial[((size_t)blockIdx.x * 3 + k) * KT + threadIdx.x] = s;
+        }
+    }
+}
+// the long lists, segment by segment as k_spmv3_heavy_seg walks them: seg_partial[(segment * 3 + k) * KT + t], raw inner sums
+template <bool kSmall, int KT> __global__ __launch_bounds__(kBlock) void k_eval_heavy_seg(DCsr3 m, const uint32_t *seg_row, const uint32_t *seg_no, EvalTile<KT> T, Fr *seg_partial) {
+    const size_t r = seg_row[blockIdx.x]; const uint32_t sn = seg_no[blockIdx.x];
+#pragma unroll 1
+    for (int k = 0; k < 3; k++) {
+        Fr acc[KT]; eval_zero<KT>(acc);
+        const uint32_t p0 = m.ptr[k][r], p1 = m.ptr[k][r + 1];
+        const uint64_t lo = (uint64_t)p0 + (uint64_t)sn * kHeavySeg;
+        if (lo < p1) {                                              // (the same for every thread of the workgroup)
+            const uint32_t hi = (uint32_t)min((uint64_t)p1, lo + kHeavySeg);
+            for (uint32_t p = (uint32_t)lo + threadIdx.x; p < hi; p += blockDim.x) entry_terms<kSmall, KT>(m, k, p, T, acc);
+        }
+        eval_store_partial<KT>(acc, seg_partial, blockIdx.x, k);
+    }
+}
+// one workgroup per long row adds its segments' sums up, multiplies by ex and stores the row's share as partial slot first_slot + h: the long rows
+// join the workgroups' partials and k_eval_finish sees one list
+template <int KT> __global__ __launch_bounds__(kBlock) void k_eval_heavy_combine(const uint32_t *heavy, const uint32_t *seg_begin, const Fr *seg_partial, EvalTile<KT> T, Fr *partial, size_t first_slot) {
+    const size_t h = blockIdx.x, r = heavy[h];
+#pragma unroll 1
+    for (int k = 0; k < 3; k++) {
+        Fr acc[KT]; eval_zero<KT>(acc);
+        for (uint32_t s = seg_begin[h] + threadIdx.x; s < seg_begin[h + 1]; s += blockDim.x)
+#pragma unroll
+            for (int t = 0; t < KT; t++) acc[t] = fr_add(acc[t], seg_partial[((size_t)s * 3 + k) * KT + t]);
+        block_reduce<KT>(acc);
+        if (threadIdx.x == 0) {
+            Fr tot[KT]; eval_zero<KT>(tot);
+            eval_row_done<KT>(T, r, acc, tot);
+            eval_apply_low<KT>(T, r, tot);
+#pragma unroll
+            for (int t = 0; t < KT; t++) partial[((first_slot + h) * 3 + k) * KT + t] = tot[t];
+        }
+    }
+}
+// the short second launch: workgroup (k, t) adds the n_slots partials of matrix k and point t up; out[t * 3 + k]
+template <int KT> __global__ __launch_bounds__(kBlock) void k_eval_finish(const Fr *partial, size_t n_slots, int nt, Fr *out) {
+    const int k = blockIdx.x % 3, t = blockIdx.x / 3;
+    if (t >= nt) return;
+    Fr acc[1] = {fr_zero()};
+    for (size_t s = threadIdx.x; s < n_slots; s += blockDim.x) acc[0] = fr_add(acc[0], partial[(s * 3 + k) * KT + t]);
+    block_reduce<1>(acc);
+    if (threadIdx.x == 0) out[t * 3 + k] = acc[0];
+}
+// slot t of the interleaved factor tables from one point's factors: lo_il[i][KT] slot t = lo[i], i < n0, and the same for hi
+template <int KT> __global__ __launch_bounds__(kBlock) void k_eval_interleave(const Fr *src0, size_t n0, Fr *dst0, const Fr *src1, size_t n1, Fr *dst1, int t) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n0 + n1; i += (size_t)gridDim.x * blockDim.x) {
+        if (i < n0) dst0[i * KT + t] = src0[i]; else dst1[(i - n0) * KT + t] = src1[i - n0];
+    }
+}
+// slot t of ey_il from one point's factors: ey_il[(h << lo_bits | j)][KT] slot t = hi[h] * lo[j] (k_eq_expand's walk: a thread keeps one lo entry
+// unpacked and walks `per` hi entries; the grid's x is exact, 2^lo_bits / blockDim.x)
+template <int KT> __global__ __launch_bounds__(kBlock) void k_eval_expand(const Fr *__restrict__ hi, const Fr *__restrict__ lo, int lo_bits, Fr *__restrict__ ey_il, int t, size_t n_hi, size_t per) {
+    const size_t j = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (j >= ((size_t)1 << lo_bits)) return;
+    const Fr9 l9 = fr9_unpack(lo[j]);
+    const size_t h0 = (size_t)blockIdx.y * per, h1 = min(n_hi, h0 + per);
+    for (size_t h = h0; h < h1; h++) ey_il[((h << lo_bits) | j) * KT + t] = fr9_pack_lt2l(fr9_mul(fr9_unpack5(hi[h]), l9));
+}
+EvalFactors eval_factors(size_t ell) { EvalFactors f; f.lo_bits = (int)std::min<size_t>(ell, 12); f.hi_bits = (int)ell - f.lo_bits; return f; }
+static void eval_slot_check(int t) { if (t < 0 || t >= kEvalTile) throw Error(OTTI_ERR_INTERNAL, "evaluation tile: a slot outside the tile"); }
+void dev_eval_point_x(DevCtx &c, const Fr *r, size_t ell, int t, Fr *lo_il, Fr *hi_il, Fr *scratch) {
+    eval_slot_check(t);
+    const EvalFactors f = eval_factors(ell);
+    Fr *lo = scratch, *hi = scratch + 4096;
+    dev_eq_factors(c, r, ell, (size_t)f.lo_bits, lo, hi);
+    KScope ks(c, KC_EQ);
+    const size_t n0 = (size_t)1 << f.lo_bits, n1 = (size_t)1 << f.hi_bits;
+    hipLaunchKernelGGL(k_eval_interleave<kEvalTile>, grid_for(n0 + n1), kBlock, 0, c.stream, (const Fr *)lo, n0, lo_il, (const Fr *)hi, n1, hi_il, t);
+}
+void dev_eval_point_y(DevCtx &c, const Fr *r, size_t ell, int t, Fr *ey_il, Fr *scratch) {
+    eval_slot_check(t);
+    const EvalFactors f = eval_factors(ell);
+    Fr *lo = scratch, *hi = scratch + 4096;
+    dev_eq_factors(c, r, ell, (size_t)f.lo_bits, lo, hi);
+    KScope ks(c, KC_EQ);
+    const size_t n_lo = (size_t)1 << f.lo_bits, n_hi = (size_t)1 << f.hi_bits, per = std::min<size_t>(16, std::max<size_t>(1, n_hi / 128));
+    hipLaunchKernelGGL(k_eval_expand<kEvalTile>, dim3((unsigned)((n_lo + kBlock - 1) / kBlock), (unsigned)((n_hi + per - 1) / per)), kBlock, 0, c.stream,
+                       (const Fr *)hi, (const Fr *)lo, f.lo_bits, ey_il, t, n_hi, per);
+}
+size_t dev_eval_partial_slots(const DeviceCsrSet &m) { return (size_t)grid_for(m.quad() ? 4 * m.rows : m.rows) + m.n_heavy; }
+void dev_eval_tile(DevCtx &c, const DeviceCsrSet &m, const EvalTables &tab, int nt, Fr *partial, Fr *seg_partial, Fr *out) {
+    constexpr int KT = kEvalTile;
+    if (nt < 1 || nt > KT) throw Error(OTTI_ERR_INTERNAL, "evaluation tile: 1 .. kEvalTile points");
+    EvalTile<KT> T; T.xlo = tab.xlo; T.xhi = tab.xhi; T.ey_il = tab.ey_il; T.xlo_bits = tab.xlo_bits; T.nt = nt;
+    KScope ks(c, KC_SPMV);
+    const bool quad = m.quad(), sm = m.use_small;      // the layouts dev_spmv3 picks, for its reasons
+    const int grid = grid_for(quad ? 4 * m.rows : m.rows);
+    {   // eval_apply_low's premise: a thread's rows lie a multiple of 2^xlo_bits apart, or it has at most one
+        const size_t stride = ((size_t)grid * kBlock) / (quad ? 4 : 1);
+        if (stride < m.rows && (stride & (((size_t)1 << tab.xlo_bits) - 1)) != 0) throw Error(OTTI_ERR_INTERNAL, "evaluation tile: the launch's row stride splits the low factor");
+    }
+    if (quad && sm) hipLaunchKernelGGL((k_eval_quad<true, KT>), grid, kBlock, 0, c.stream, m.view(), m.rows, T, partial);
+    else if (quad) hipLaunchKernelGGL((k_eval_quad<false, KT>), grid, kBlock, 0, c.stream, m.view(), m.rows, T, partial);
+    else if (sm) hipLaunchKernelGGL((k_eval_light<true, KT>), grid, kBlock, 0, c.stream, m.view(), m.rows, T, partial);
+    else hipLaunchKernelGGL((k_eval_light<false, KT>), grid, kBlock, 0, c.stream, m.view(), m.rows, T, partial);
+    if (m.n_heavy) {
+        if (sm) hipLaunchKernelGGL((k_eval_heavy_seg<true, KT>), (unsigned)m.n_seg, kBlock, 0, c.stream, m.view(), (const uint32_t *)m.seg_row.p, (const uint32_t *)m.seg_no.p, T, seg_partial);
+        else hipLaunchKernelGGL((k_eval_heavy_seg<false, KT>), (unsigned)m.n_seg, kBlock, 0, c.stream, m.view(), (const uint32_t *)m.seg_row.p, (const uint32_t *)m.seg_no.p, T, seg_partial);
+        hipLaunchKernelGGL(k_eval_heavy_combine<KT>, (unsigned)m.n_heavy, kBlock, 0, c.stream, (const uint32_t *)m.heavy.p, (const uint32_t *)m.seg_begin.p, (const Fr *)seg_partial, T, partial, (size_t)grid);
+    }
+    hipLaunchKernelGGL(k_eval_finish<KT>, 3u * KT, kBlock, 0, c.stream, (const Fr *)partial, (size_t)grid + m.n_heavy, nt, out);
+}
+
 // ------------------------------------------------------------------------------------------------ satisfiability pass (Instance::is_sat on the device)
 // Per constraint row r: a = <A_r,z>, b = <B_r,z>, c = <C_r,z> formed exactly as the products above form them, then a b == c in GF(l).  Az, Bz and
 // Cz are never written: a row's only output is bit (r & 63) of bits[r >> 6], set when the row FAILS, and the failing rows are counted in *count.

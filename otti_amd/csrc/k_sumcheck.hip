@@ -81,6 +81,17 @@ void dev_eq_evals(DevCtx &c, const Fr *r, size_t ell, Fr *out, Fr *scratch) {
     hipLaunchKernelGGL(k_eq_expand, dim3((unsigned)(((size_t)1 << lo_bits) / kBlock), (unsigned)((n_hi + per - 1) / per)), kBlock, 0, c.stream, hi, lo, lo_bits, out, n_hi, per);
 }
 
+// the two factors of a table instead of the table: eq(r)[i] = hi[i >> lo_bits] * lo[i & (2^lo_bits - 1)] — lo over the last lo_bits variables of r
+// (1 .. 13), hi over the ell - lo_bits before them (0 .. 13; none: the one-element table {1}) — in one launch, as dev_eq_evals makes them for
+// k_eq_expand.  For kernels that multiply the factors where they need an element (k_sparse.hip k_eval_*).
+void dev_eq_factors(DevCtx &c, const Fr *r, size_t ell, size_t lo_bits, Fr *lo, Fr *hi) {
+    if (lo_bits < 1 || lo_bits > ell || lo_bits > 13 || ell - lo_bits > 13) throw Error(OTTI_ERR_BAD_ARG, "eq factors: 1 .. 13 low variables, at most 13 high ones");
+    const size_t hi_bits = ell - lo_bits;
+    if (!hi_bits) { dev_fill_one(c, hi, 1); KScope ks(c, KC_EQ); launch_eq_tree(c, r, lo_bits, false, lo, nullptr, 0, false, nullptr); return; }
+    KScope ks(c, KC_EQ);
+    launch_eq_tree(c, r + hi_bits, lo_bits, false, lo, r, hi_bits, false, hi);
+}
+
 // ------------------------------------------------------------------------------------------------ K3/K4/K7 sum-check rounds
 __device__ __forceinline__ Pair load_pair(const Fr *T, size_t i, size_t half) { Pair p; p.lo = T[i]; p.hi = T[i + half]; return p; }
 // fold the table of length 4q by r (bound_poly_var_top) for the two entries that form pair i of the folded table

@@ -238,6 +238,116 @@ void instance_evaluate_gpu(Instance &I, const std::vector<Fr> &rx, const std::ve
     instance_evaluate_finish(out);
 }
 
+// The same at several points (device.h): per chunk of kEvalChunk points their eq(ry) tables, written interleaved tile by tile, and the factors of
+// their eq(rx) tables, then one walk over the matrices per tile.  Everything of one call is queued at once: a chunk's launches reuse the tables of
+// the chunk before it in stream order.  Behind every tile its results are copied to pinned memory and an event is recorded, so the caller can
+// collect tile by tile: the first proofs' values are there after one tile's time, not after the whole batch's.
+struct EvalManyScratch {
+    static constexpr size_t kLo = 4096, kHi = 8192, kTiles = (kEvalChunk + kEvalTile - 1) / kEvalTile;   // a table's factors: at most 2^12 and 2^13 elements
+    size_t V2 = 0;
+    DevBuf<Fr> ey_il, xf, eqs, partial, seg_partial, out;     // ey_il: kTiles tables of V2 * kEvalTile; xf: per tile xlo, xhi interleaved over the tile's points
+    Fr *h_out = nullptr; size_t h_cap = 0, pending = 0, done = 0;
+    std::vector<hipEvent_t> tile_done;
+    void reserve(DevCtx &c, size_t v2, size_t slots, size_t segs, size_t K) {
+        if (v2 > V2 || partial.n < 3 * kEvalTile * slots || seg_partial.n < 3 * kEvalTile * segs || out.n < 3 * K || h_cap < 3 * K)
+            OTTI_HIP(hipStreamSynchronize(c.stream));         // nothing queued may still read what is replaced below
+        if (v2 > V2) { ey_il.alloc(kTiles * kEvalTile * v2); V2 = v2; }
+        if (!xf.p) { xf.alloc(kTiles * (kLo + kHi) * kEvalTile); eqs.alloc(kLo + kHi); }
+        if (partial.n < 3 * kEvalTile * slots) partial.alloc(3 * kEvalTile * slots);
+        if (seg_partial.n < 3 * kEvalTile * segs) seg_partial.alloc(3 * kEvalTile * segs);
+        if (out.n < 3 * K) out.alloc(3 * K);
+        if (h_cap < 3 * K) {
+            if (h_out) OTTI_HIP(hipHostFree(h_out));
+            h_out = nullptr; h_cap = 0;
+            OTTI_HIP(hipHostMalloc((void **)&h_out, 3 * K * sizeof(Fr), hipHostMallocDefault)); h_cap = 3 * K;
+        }
+        while (tile_done.size() < (K + kEvalTile - 1) / kEvalTile) { hipEvent_t e; OTTI_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); tile_done.push_back(e); }
+    }
+};
+template <class Rx, class Ry> static void evaluate_many_queue(DevCtx &c, Instance &I, size_t K, Rx rx, Ry ry) {
+    ensure_instance_device(I);
+    const DeviceCsrSet &m = I.dev->by_row;
+    const size_t N = I.num_cons, V2 = 2 * I.num_vars, nrx = ilog2(N), nry = ilog2(V2);
+    if (m.rows != N || nrx < 1 || nry < 1 || nrx > 25 || nry > 25) throw Error(OTTI_ERR_INTERNAL, "the instance's device copy has other dimensions, or an eq table beyond 2^25");
+    if (!c.eval_many) c.eval_many = new EvalManyScratch();
+    EvalManyScratch &S = *c.eval_many;
+    S.pending = S.done = 0;
+    if (!K) return;
+    S.reserve(c, V2, dev_eval_partial_slots(m), m.n_seg, K);
+    constexpr size_t kLo = EvalManyScratch::kLo, kHi = EvalManyScratch::kHi;
+    static_assert(kEvalChunk % kEvalTile == 0, "tiles begin at multiples of kEvalTile in every chunk");
+    auto tables_of = [&](size_t tile) {
+        Fr *x = S.xf.p + tile * (kLo + kHi) * kEvalTile;
+        return EvalTables{x, x + kLo * kEvalTile, S.ey_il.p + tile * kEvalTile * S.V2, eval_factors(nrx).lo_bits};
+    };
+    for (size_t c0 = 0; c0 < K; c0 += kEvalChunk) {
+        const size_t nc = std::min(kEvalChunk, K - c0);
+        for (size_t t0 = 0; t0 < nc; t0 += kEvalTile) {
+            const EvalTables t = tables_of(t0 / kEvalTile);
+            const size_t nt = std::min<size_t>(kEvalTile, nc - t0), first = c0 + t0;
+            for (size_t j = 0; j < nt; j++) {
+                dev_eval_point_x(c, rx(first + j), nrx, (int)j, const_cast<Fr *>(t.xlo), const_cast<Fr *>(t.xhi), S.eqs.p);
+                dev_eval_point_y(c, ry(first + j), nry, (int)j, const_cast<Fr *>(t.ey_il), S.eqs.p);
+            }
+            dev_eval_tile(c, m, t, (int)nt, S.partial.p, S.seg_partial.p, S.out.p + 3 * first);
+            OTTI_HIP(hipMemcpyAsync(S.h_out + 3 * first, S.out.p + 3 * first, 3 * nt * sizeof(Fr), hipMemcpyDeviceToHost, c.stream));
+            OTTI_HIP(hipEventRecord(S.tile_done[first / kEvalTile], c.stream));
+        }
+    }
+    S.pending = K;
+}
+void instance_evaluate_many_begin(Instance &I, const std::vector<const NizkProof *> &proofs) {
+    DevCtx &c = DevCtx::get();
+    const size_t nrx = ilog2(I.num_cons), nry = ilog2(2 * I.num_vars);
+    for (const NizkProof *P : proofs)
+        if (!P || P->rx.size() != nrx || P->ry.size() != nry) throw Error(OTTI_ERR_VERIFY_INTERNAL, "challenge vector lengths do not match the instance");
+    evaluate_many_queue(c, I, proofs.size(), [&](size_t i) { return proofs[i]->rx.data(); }, [&](size_t i) { return proofs[i]->ry.data(); });
+}
+size_t instance_evaluate_many_next(Fr (*out)[3]) {
+    DevCtx &c = DevCtx::get();
+    if (!c.eval_many) throw Error(OTTI_ERR_INTERNAL, "no evaluation was begun on this thread");
+    EvalManyScratch &S = *c.eval_many;
+    if (S.done >= S.pending) return S.pending;
+    OTTI_HIP(hipEventSynchronize(S.tile_done[S.done / kEvalTile]));
+    const size_t n = std::min<size_t>(kEvalTile, S.pending - S.done);
+    for (size_t i = S.done; i < S.done + n; i++) for (int k = 0; k < 3; k++) out[i][k] = S.h_out[3 * i + k];
+    S.done += n;
+    return S.done;
+}
+void instance_evaluate_many_finish(Fr (*out)[3]) {
+    DevCtx &c = DevCtx::get();
+    if (!c.eval_many) throw Error(OTTI_ERR_INTERNAL, "no evaluation was begun on this thread");
+    while (c.eval_many->done < c.eval_many->pending) instance_evaluate_many_next(out);
+    c.eval_many->pending = c.eval_many->done = 0;
+}
+void instance_evaluate_many(Instance &I, const Fr *rx, size_t nrx, const Fr *ry, size_t nry, size_t K, Fr (*out)[3], float *kernel_ms) {
+    DevCtx &c = DevCtx::get();
+    if (((size_t)1 << nrx) != I.num_cons || ((size_t)1 << nry) != 2 * I.num_vars) throw Error(OTTI_ERR_BAD_ARG, "challenge vector lengths do not match the instance");
+    ensure_instance_device(I);
+    if (kernel_ms) OTTI_HIP(hipEventRecord(c.ev0, c.stream));
+    evaluate_many_queue(c, I, K, [&](size_t i) { return rx + i * nrx; }, [&](size_t i) { return ry + i * nry; });
+    if (kernel_ms) OTTI_HIP(hipEventRecord(c.ev1, c.stream));
+    instance_evaluate_many_finish(out);
+    c.sync();
+    if (kernel_ms) OTTI_HIP(hipEventElapsedTime(kernel_ms, c.ev0, c.ev1));
+}
+// verify_many.cpp's hooks (spartan.h).  begin: true when the evaluation is queued on the calling thread; false leaves the caller on the host path.
+// next: the number of points whose values are in `out` by now (one more tile per call), or -1
+static bool inst_eval_many_begin_on_device(const Instance &I, const std::vector<const NizkProof *> &proofs) {
+    static const bool have = [] { int n = 0; return hipGetDeviceCount(&n) == hipSuccess && n > 0; }();
+    if (!have) return false;
+    try { instance_evaluate_many_begin(const_cast<Instance &>(I), proofs); return true; }
+    catch (const Error &) { return false; }
+}
+static long inst_eval_many_next_on_device(Fr (*out)[3]) {
+    try { return (long)instance_evaluate_many_next(out); }
+    catch (const Error &) { return -1; }
+}
+static const bool g_eval_many_hook_registered = [] {
+    g_inst_eval_many_begin_hook = inst_eval_many_begin_on_device; g_inst_eval_many_next_hook = inst_eval_many_next_on_device;
+    return true;
+}();
+
 
 // nizk/mod.rs DotProductProofLog::prove on device vectors: x = LZ (the bound polynomial row, R elements) against a = Rv, over the
 // generators gens_n = P[0..R) / gens_1 of the stream `g` was derived from (PcView: stream indices).  Cx, the bullet-reduction rounds

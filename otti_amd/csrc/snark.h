@@ -87,7 +87,9 @@ struct RowSum {
 };
 // Group equations that do not feed the transcript — most of the verifier's arithmetic: per sum-check round two checks with a
 // variable-base scalar multiplication each — are handed to a few background threads AS THEY ARISE, while the calling thread walks on
-// through the rounds (whose hashed commitments are the sequential path); finish() drains what is left and reports the first failure.
+// through the rounds (whose hashed commitments are the sequential path); finish() drains what is left and reports the first failure — the
+// failing check that was handed over EARLIEST, whichever thread found its failure first: a proof with several defects gets one code, the same in
+// every run and beside any number of other verifiers (verify_many.cpp holds its results against the single verifier's, code for code).
 // Lock-free: the producer fills a slot and bumps `count`; workers claim slots with a compare-exchange on `next`.
 class Deferred {
 public:
@@ -101,7 +103,7 @@ public:
     ~Deferred() { closing_.store(true, std::memory_order_release); for (auto &t : th_) t.join(); }
     void push_back(std::function<void()> f) {
         const size_t c = count_.load(std::memory_order_relaxed);
-        if (c >= kSlots) { run_one(f); return; }                          // (never in practice: two checks per round, at most 2 x 64 rounds + a few)
+        if (c >= kSlots) { run_one(f, kSlots); return; }                          // (never in practice: two checks per round, at most 2 x 64 rounds + a few)
         items_[c] = std::move(f);
         count_.store(c + 1, std::memory_order_release);
     }
@@ -110,22 +112,27 @@ public:
         work(true);
         for (auto &t : th_) t.join();
         th_.clear();
-        if (const int c = code_.load()) throw VerifyFail{c};
+        if (const uint64_t f = first_.load()) throw VerifyFail{(int)(int32_t)(uint32_t)f};
     }
 private:
     static constexpr size_t kSlots = 512;
     std::function<void()> items_[kSlots];
     std::atomic<size_t> count_{0}, next_{0};
     std::atomic<bool> closing_{false};
-    std::atomic<int> code_{0};
+    std::atomic<uint64_t> first_{0};                                      // 0: no failure; else (slot + 1) << 32 | code of the failure in the lowest slot
     std::vector<std::thread> th_;
-    void run_one(const std::function<void()> &f) {
-        try { f(); } catch (const VerifyFail &e) { int z = 0; code_.compare_exchange_strong(z, e.code); } catch (...) { int z = 0; code_.compare_exchange_strong(z, (int)OTTI_ERR_VERIFY_INTERNAL); }
+    void failed(size_t slot, int code) {
+        const uint64_t mine = ((uint64_t)(slot + 1) << 32) | (uint32_t)code;
+        uint64_t cur = first_.load(std::memory_order_relaxed);
+        while ((cur == 0 || mine < cur) && !first_.compare_exchange_weak(cur, mine, std::memory_order_acq_rel)) {}
+    }
+    void run_one(const std::function<void()> &f, size_t slot) {
+        try { f(); } catch (const VerifyFail &e) { failed(slot, e.code); } catch (...) { failed(slot, (int)OTTI_ERR_VERIFY_INTERNAL); }
     }
     void work(bool until_empty) {
         for (;;) {
             size_t i = next_.load(std::memory_order_relaxed);
-            if (i < count_.load(std::memory_order_acquire)) { if (next_.compare_exchange_weak(i, i + 1, std::memory_order_acq_rel)) run_one(items_[i]); continue; }
+            if (i < count_.load(std::memory_order_acquire)) { if (next_.compare_exchange_weak(i, i + 1, std::memory_order_acq_rel)) run_one(items_[i], i); continue; }
             if (until_empty || closing_.load(std::memory_order_acquire)) { if (next_.load() >= count_.load(std::memory_order_acquire)) return; continue; }
             cpu_relax();
         }

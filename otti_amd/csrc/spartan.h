@@ -172,6 +172,30 @@ void sumcheck_round_finish(ZKSumcheckProof &pf, size_t j, const RoundPart1 &p1, 
 typedef std::function<void(Fr out[3])> InstEvalFetch;
 int nizk_verify(const Instance &inst, const std::vector<Fr> &inputs, const Gens &g, const void *tlabel, size_t tlabel_len,
                 const uint8_t *proof, size_t proof_len, const Fr *inst_evals = nullptr, const InstEvalFetch *fetch = nullptr);
+// the same from a parsed proof: everything nizk_verify does behind the count of inputs and NizkProof::parse
+int nizk_verify_parsed(const Instance &inst, const std::vector<Fr> &inputs, const Gens &g, const void *tlabel, size_t tlabel_len,
+                       const NizkProof &P, const Fr *inst_evals = nullptr, const InstEvalFetch *fetch = nullptr);
+
+// ---------------------------------------------------------------------------------------------- many proofs of one instance (verify_many.cpp)
+// results[i] = what nizk_verify returns for item i alone with the same instance, generators and label — NOT a random-linear-combination batch:
+// every proof is verified by the single verifier's own steps, and no verdict depends on its neighbours.  What the items share is the circuit: the
+// points (rx, ry) of all proofs that parse and fit the instance are evaluated in ONE batched pass on the device (hooks below, set by prover.cpp:
+// this file has no HIP in it) when the instance has at least 4096 constraints and a device is present — the rule of the single path; otherwise
+// every worker evaluates on the host as nizk_verify does.  `threads` workers (0: kVerifyManyThreads; at most kVerifyManyMaxThreads; never more
+// than there are proofs to walk) each walk r1cs_verify_host for their share with a Transcript and a SpinPool::Session of their own — the pool's
+// workers() budget shares the helper cores out — and collect their triple once the calling thread, which queued the evaluation before the workers
+// started and collects it tile by tile, has their tile's values: the device time hides behind the host rounds, as it does for one proof.  One worker runs on the calling thread itself,
+// begin / rounds / finish in the single path's order.  An item whose inputs hold a scalar >= l (inputs32 are canonical bytes), whose count of inputs
+// is wrong, whose proof does not parse or whose rx / ry do not fit the instance gets the single path's code for that and takes no part in the
+// evaluation.  An exception in a worker becomes its item's code.  The call blocks; its workers are joined before it returns.
+struct VerifyItem { const uint8_t *inputs32; size_t ninputs; const uint8_t *proof; size_t proof_len; };
+constexpr unsigned kVerifyManyThreads = 4, kVerifyManyMaxThreads = 16;
+typedef bool (*InstEvalManyBeginHook)(const Instance &inst, const std::vector<const NizkProof *> &proofs);   // queues on the calling thread; false: declined
+typedef long (*InstEvalManyNextHook)(Fr (*out)[3]);   // same thread: waits for the next tile of points and copies its values; how many points are in `out` by now, or -1: failed
+extern InstEvalManyBeginHook g_inst_eval_many_begin_hook;
+extern InstEvalManyNextHook g_inst_eval_many_next_hook;
+void nizk_verify_many(const Instance &inst, const Gens &g, const void *tlabel, size_t tlabel_len, const VerifyItem *items, size_t count,
+                      unsigned threads, int32_t *results);
 
 // ---------------------------------------------------------------------------------------------- prover (prover.cpp; GPU)
 struct ProveTimings { double ms[8]; };   // polycommit, multiply_vec, sc_phase_one, eval_table_sparse, sc_phase_two, polyeval, total, (spare)

@@ -667,6 +667,13 @@ int nizk_verify(const Instance &I, const std::vector<Fr> &inputs, const Gens &g,
     try {
         if (inputs.size() != I.num_inputs) return OTTI_ERR_INVALID_NUM_INPUTS;
         NizkProof P = NizkProof::parse(proof, proof_len);
+        return nizk_verify_parsed(I, inputs, g, tlabel, tlabel_len, P, inst_evals_opt, fetch);
+    } catch (const Error &e) { return e.code; }
+}
+int nizk_verify_parsed(const Instance &I, const std::vector<Fr> &inputs, const Gens &g, const void *tlabel, size_t tlabel_len, const NizkProof &P,
+                       const Fr *inst_evals_opt, const InstEvalFetch *fetch) {
+    try {
+        if (inputs.size() != I.num_inputs) return OTTI_ERR_INVALID_NUM_INPUTS;
         size_t N = I.num_cons, V = I.num_vars, nrx = ilog2(N), nry = ilog2(2 * V);
         if (P.rx.size() != nrx || P.ry.size() != nry) return OTTI_ERR_VERIFY_INTERNAL;
         Transcript tr(tlabel, tlabel_len);

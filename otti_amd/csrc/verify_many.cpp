@@ -1,0 +1,114 @@
+// Many NIZK proofs of one instance verified in one call (spartan.h nizk_verify_many).  Host code only: the batched evaluation of A, B, C at the
+// proofs' points is reached through two hooks that prover.cpp sets, so the CPU rebuilds of the host sources compile this file as it is.
+#include "spartan.h"
+#include <atomic>
+#include <condition_variable>
+#include <memory>
+#include <mutex>
+#include <thread>
+
+namespace otti {
+
+InstEvalManyBeginHook g_inst_eval_many_begin_hook = nullptr;
+InstEvalManyNextHook g_inst_eval_many_next_hook = nullptr;
+
+namespace {
+struct Live { size_t item; std::vector<Fr> inputs; NizkProof P; };
+// what the calling thread hands the workers: the evaluation's values, tile by tile as they arrive
+struct Evals {
+    std::mutex mu; std::condition_variable cv;
+    size_t done = 0; bool failed = false;                     // triples of proofs [0, done) hold their values; failed: the rest evaluate on the host
+    std::vector<Fr> triples;                                  // 3 per live proof
+    void publish(size_t d, bool f) { { std::lock_guard<std::mutex> lk(mu); done = d; failed = f; } cv.notify_all(); }
+    bool wait(size_t k) { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return done > k || failed; }); return done > k; }
+};
+int verify_one(const Instance &I, const Gens &g, const void *tlabel, size_t tlabel_len, const Live &L, const InstEvalFetch *fetch) {
+    try { return nizk_verify_parsed(I, L.inputs, g, tlabel, tlabel_len, L.P, nullptr, fetch); }
+    catch (const Error &e) { return e.code; }
+    catch (...) { return OTTI_ERR_INTERNAL; }
+}
+}  // namespace
+
+void nizk_verify_many(const Instance &I, const Gens &g, const void *tlabel, size_t tlabel_len, const VerifyItem *items, size_t count, unsigned threads,
+                      int32_t *results) {
+    if (!count) return;
+    // ---- parse and check, item by item, in the single path's order: the inputs' scalars, their count, the proof's bytes, its challenge lengths
+    const size_t nrx = ilog2(I.num_cons), nry = ilog2(2 * I.num_vars);
+    std::vector<std::unique_ptr<Live>> live; live.reserve(count);
+    for (size_t i = 0; i < count; i++) {
+        const VerifyItem &it = items[i];
+        try {
+            if (!it.proof || (it.ninputs && !it.inputs32)) { results[i] = OTTI_ERR_BAD_ARG; continue; }
+            auto L = std::make_unique<Live>(); L->item = i; L->inputs.resize(it.ninputs);
+            bool canonical = true;
+            for (size_t j = 0; j < it.ninputs && canonical; j++) canonical = fr_from_bytes(L->inputs[j], it.inputs32 + 32 * j);
+            if (!canonical) { results[i] = OTTI_ERR_INVALID_SCALAR; continue; }
+            if (it.ninputs != I.num_inputs) { results[i] = OTTI_ERR_INVALID_NUM_INPUTS; continue; }
+            L->P = NizkProof::parse(it.proof, it.proof_len);
+            if (L->P.rx.size() != nrx || L->P.ry.size() != nry) { results[i] = OTTI_ERR_VERIFY_INTERNAL; continue; }
+            results[i] = OTTI_ERR_INTERNAL;                   // until its worker has written the verdict
+            live.push_back(std::move(L));
+        } catch (const Error &e) { results[i] = e.code; }
+        catch (...) { results[i] = OTTI_ERR_INTERNAL; }
+    }
+    const size_t n = live.size();
+    if (!n) return;
+    // ---- the batched evaluation, queued on this thread before any worker starts
+    bool queued = false;
+    if (I.num_cons >= 4096 && g_inst_eval_many_begin_hook && g_inst_eval_many_next_hook) {
+        std::vector<const NizkProof *> pts(n);
+        for (size_t k = 0; k < n; k++) pts[k] = &live[k]->P;
+        try { queued = g_inst_eval_many_begin_hook(I, pts); } catch (...) { queued = false; }
+    }
+    Evals ev;
+    if (queued) ev.triples.resize(3 * n); else ev.failed = true;
+    auto collect_next = [&] {                                 // on this thread: one more tile's values, published
+        long d = -1;
+        try { d = g_inst_eval_many_next_hook(reinterpret_cast<Fr (*)[3]>(ev.triples.data())); } catch (...) { d = -1; }
+        if (d < 0 || (size_t)d <= ev.done) ev.publish(ev.done, true); else ev.publish((size_t)d, false);
+    };
+    auto fetch_for = [&](size_t k) {
+        return InstEvalFetch([&ev, &live, &I, k](Fr out[3]) {
+            if (ev.wait(k)) { for (int j = 0; j < 3; j++) out[j] = ev.triples[3 * k + j]; return; }
+            I.evaluate(live[k]->P.rx, live[k]->P.ry, out);      // the device let go of the batch: this proof's own host evaluation
+        });
+    };
+    if (!threads) threads = kVerifyManyThreads;
+    const size_t nw = std::min<size_t>({(size_t)threads, (size_t)kVerifyManyMaxThreads, n});
+    if (nw <= 1) {
+        // one worker: the calling thread, in the single path's order — the evaluation is collected where the first proof needs it
+        for (size_t k = 0; k < n; k++) {
+            const InstEvalFetch fetch([&](Fr out[3]) {
+                while (!ev.failed && ev.done <= k) collect_next();
+                if (ev.done > k) { for (int j = 0; j < 3; j++) out[j] = ev.triples[3 * k + j]; return; }
+                I.evaluate(live[k]->P.rx, live[k]->P.ry, out);
+            });
+            results[live[k]->item] = verify_one(I, g, tlabel, tlabel_len, *live[k], queued ? &fetch : nullptr);
+        }
+        while (!ev.failed && ev.done < n) collect_next();     // proofs that failed before their closing step: the queued work still has to drain
+        return;
+    }
+    // ---- workers take the live proofs in order, one at a time; each verdict goes to its own item's slot
+    std::atomic<size_t> next{0};
+    auto work = [&] {
+        for (;;) {
+            const size_t k = next.fetch_add(1, std::memory_order_relaxed);
+            if (k >= n) return;
+            int rc;
+            try {
+                const InstEvalFetch fetch = fetch_for(k);
+                rc = verify_one(I, g, tlabel, tlabel_len, *live[k], queued ? &fetch : nullptr);
+            } catch (...) { rc = OTTI_ERR_INTERNAL; }
+            results[live[k]->item] = rc;
+        }
+    };
+    std::vector<std::thread> th; th.reserve(nw);
+    struct Join { std::vector<std::thread> &th; Evals &ev; ~Join() { if (ev.done * 3 < ev.triples.size() && !ev.failed) ev.publish(ev.done, true); for (auto &t : th) if (t.joinable()) t.join(); } } join{th, ev};
+    for (size_t w = 0; w < nw; w++) {
+        try { th.emplace_back(work); } catch (const std::system_error &) { break; }      // short of threads: those that started share the work
+    }
+    while (!ev.failed && ev.done < n) collect_next();
+    if (th.empty()) work();
+}
+
+}  // namespace otti
