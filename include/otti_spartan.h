@@ -564,6 +564,17 @@ int32_t otti_k_sc_plan(int32_t kind, size_t len, int32_t armed, uint32_t *workgr
  * plain launch's results; any disagreement between the three ways is OTTI_ERR_INTERNAL. */
 int32_t otti_k_armed_selftest(const uint8_t *A, const uint8_t *B, size_t len, const uint8_t *r, uint32_t hold_us, uint8_t *out2, uint8_t *e2);
 int32_t otti_k_msm_rows(otti_gens *gens, const uint8_t *h_Z, size_t L, size_t R, const uint8_t *h_blinds, uint8_t *h_out32, float *kernel_ms);
+/* A general fixed-base MSM job, as the prover's launcher takes it, for kernel-level tests: row i = sum_{j < n_dense} dense[i n_dense + j] P[j]
+   + sum_{e < n_extra} extra_s[i n_extra + e] P[extra_base[e]] over the generators' R + 2 points (n_dense <= R, n_extra <= 8, extra_base[e] < R + 2;
+   scalars Montgomery).  mode: 0 compressed, 1 raw, 2 kept row sums — h_out32 receives 32 compressed bytes per row in every mode.  sparse: -1 decides
+   by the scalars as otti_k_msm_rows does, 0 / 1 force the plain / work-list bulk kernel.  force_bulk: the chip-filling kernel whatever the size.
+   bulk_workgroups: the workgroups a bulk launch aims for (0 = the default the prover uses; 1 makes one workgroup walk a whole row in sub-chunks).
+   plan5 (may be NULL) = {kernel (0 bulk, 1 bulk-sparse, 2 small), chunk, nchunks, fuse, route (0 mail, 1 flag, 2 keep, 3 raw, 4 device-encode,
+   5 host-encode)} of the launch.  OTTI_ERR_BAD_ARG, before a device is touched, for a base beyond the table, n_extra > 8, n_dense > R, no term at
+   all, rows outside 1 .. 65535, more than 512 raw rows, an unknown mode. */
+int32_t otti_k_msm_job(otti_gens *gens, size_t rows, size_t n_dense, const uint8_t *h_dense, size_t n_extra, const uint8_t *h_extra_s,
+                       const uint32_t *h_extra_base, int32_t mode, int32_t sparse, int32_t force_bulk, size_t bulk_workgroups, uint8_t *h_out32,
+                       uint32_t *plan5, float *kernel_ms);
 /* the kernel that patches kept rows, on L identity points: out[i] = compress(sum over {k : idx[k] in [iR, (i+1)R)} s[k] * P[idx[k] - iR]), i < L <= 4096,
    R = the generators' row length; idx strictly ascending below L*R (else OTTI_ERR_INVALID_INDEX), s Montgomery.  A row without terms is the identity. */
 int32_t otti_k_msm_scatter_rows(otti_gens *gens, size_t L, const uint64_t *h_idx, const uint8_t *h_s, size_t count,

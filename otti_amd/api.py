@@ -180,6 +180,7 @@ _sig("otti_k_armed_selftest", _i32, _vp, _vp, _sz, _vp, ctypes.c_uint32, _vp, _v
 _sig("otti_k_sc_caps_override", _i32, _vp)
 _sig("otti_k_sc_plan", _i32, _i32, _sz, _i32, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(_u64))
 _sig("otti_k_msm_rows", _i32, _vp, _vp, _sz, _sz, _vp, _vp, _fp)
+_sig("otti_k_msm_job", _i32, _vp, _sz, _sz, _vp, _sz, _vp, _vp, _i32, _i32, _i32, _sz, _vp, _vp, _fp)
 _sig("otti_k_row_sum", _i32, _vp, _sz, _vp, _vp)
 _sig("otti_k_msm_scatter_rows", _i32, _vp, _sz, _vp, _vp, _sz, _vp, _fp)
 _sig("otti_k_witness_diff", _i32, _vp, _sz, _vp, _i32, _sz, _vp, _vp, _vp, ctypes.POINTER(_u64), ctypes.POINTER(ctypes.c_uint32), _fp)
@@ -1408,6 +1409,26 @@ class kernels:
         out = np.zeros((L, 32), dtype=np.uint8); ms = ctypes.c_float(0)
         _check(lib.otti_k_msm_rows(gens._h, _ptr(Z), L, R, _ptr(blinds), _ptr(out), ctypes.byref(ms)))
         return out, ms.value
+
+    MSM_MODES = ("compressed", "raw", "keep")
+    MSM_KERNELS = ("bulk", "bulk_sparse", "small")
+    MSM_ROUTES = ("mail", "flag", "keep", "raw", "device_encode", "host_encode")
+
+    @staticmethod
+    def msm_job(gens, rows, dense=None, extra_s=None, extra_base=(), mode="compressed", sparse=-1, force_bulk=False, bulk_workgroups=0):
+        """a general fixed-base MSM job through the prover's launcher: ``dense`` (rows * n_dense, 32) Montgomery scalars, dense term j on generator
+        j; ``extra_s`` (rows * n_extra, 32) on the bases ``extra_base``.  Returns (rows compressed points — in every mode —, the plan the launch
+        took: dict(kernel, chunk, nchunks, fuse, route), kernel ms)."""
+        base = np.ascontiguousarray(extra_base, dtype=np.uint32).reshape(-1)
+        n_extra = base.size
+        d = _scalars(dense, "dense") if dense is not None else np.zeros((0, 32), dtype=np.uint8)
+        e = _scalars(extra_s, "extra_s") if extra_s is not None else np.zeros((0, 32), dtype=np.uint8)
+        if rows < 1 or d.shape[0] % rows or e.shape[0] != rows * n_extra:
+            raise ValueError("msm_job: dense is rows * n_dense scalars, extra_s rows * len(extra_base)")
+        out = np.zeros((rows, 32), dtype=np.uint8); plan = np.zeros(5, dtype=np.uint32); ms = ctypes.c_float(0)
+        _check(lib.otti_k_msm_job(gens._h, rows, d.shape[0] // rows, _ptr(d), n_extra, _ptr(e), _ptr(base), kernels.MSM_MODES.index(mode), int(sparse),
+                                  1 if force_bulk else 0, bulk_workgroups, _ptr(out), _ptr(plan), ctypes.byref(ms)))
+        return out, dict(kernel=kernels.MSM_KERNELS[plan[0]], chunk=int(plan[1]), nchunks=int(plan[2]), fuse=int(plan[3]), route=kernels.MSM_ROUTES[plan[4]]), ms.value
 
     # ---- the kernels the prover itself launches (phase one without the eq table, evaluation proof, bullet reduction)
     @staticmethod

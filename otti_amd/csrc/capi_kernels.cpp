@@ -418,6 +418,43 @@ int32_t otti_k_msm_rows(otti_gens *gens, const uint8_t *Z, size_t L, size_t R, c
         c.sync(); memcpy(out32, c.h_points, 32 * L); return OTTI_OK;
     });
 }
+// A general MsmJob through dev_msm_rows (k_msm.hip msm_launch), for the tests: any of the shapes the prover sends (no dense part, up to 8 extras on
+// any base, rows shorter than the table, raw and kept sums, force_bulk) and the plan's seam bulk_workgroups (msm_plan.h).  Row sums come back
+// compressed in every mode; plan5 = {kernel, chunk, nchunks, fuse, route} of the launch, from the launcher's own call of msm_plan().  The
+// arguments are judged on the host, before a device is touched: the kernels take table columns from extra_base.
+int32_t otti_k_msm_job(otti_gens *gens, size_t rows, size_t n_dense, const uint8_t *dense, size_t n_extra, const uint8_t *extra_s, const uint32_t *extra_base,
+                       int32_t mode, int32_t sparse, int32_t force_bulk, size_t bulk_workgroups, uint8_t *out32, uint32_t *plan5, float *ms) {
+    return guarded([&] {
+        if (!gens || !out32 || !rows || rows > 65535) throw Error(OTTI_ERR_BAD_ARG, "null argument, or rows outside 1 .. 65535");
+        Gens &g = *gens->g;
+        if (n_extra > 8) throw Error(OTTI_ERR_BAD_ARG, "more than 8 extra terms");
+        if (n_dense > g.R || n_dense + n_extra == 0) throw Error(OTTI_ERR_BAD_ARG, "more dense terms than generators, or no terms at all");
+        if ((n_dense && !dense) || (n_extra && (!extra_s || !extra_base))) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        for (size_t e = 0; e < n_extra; e++) if (extra_base[e] >= g.R + 2) throw Error(OTTI_ERR_BAD_ARG, "an extra term's base lies beyond the table");
+        if (mode != MSM_COMPRESSED && mode != MSM_RAW && mode != MSM_KEEP) throw Error(OTTI_ERR_BAD_ARG, "unknown mode");
+        if (sparse < -1 || sparse > 1) throw Error(OTTI_ERR_BAD_ARG, "sparse is -1 (decide by the scalars), 0 or 1");
+        if (mode == MSM_RAW && rows > kHostPtsCap) throw Error(OTTI_ERR_BAD_ARG, "more raw rows than the host's point buffer holds");
+        DevCtx &c = DevCtx::get();
+        ensure_gens_device(g);
+        Staged z(c, dense, rows * n_dense), ex(c, extra_s, rows * n_extra);
+        DevBuf<Pt> kept(rows); DevBuf<uint8_t> enc(32 * rows);
+        const bool sp = sparse < 0 ? (n_dense && dev_small_fraction(c, z.d.p, rows * n_dense) > kSparseWitness) : sparse != 0;
+        MsmJob job{.dense = n_dense ? z.d.p : nullptr, .n_dense = n_dense, .rows = rows, .extra_s = n_extra ? ex.d.p : nullptr, .extra_base = extra_base,
+                   .n_extra = n_extra, .mode = mode, .sparse = sp};
+        if (mode == MSM_KEEP) job.keep_dst = kept.p;
+        job.force_bulk = force_bulk != 0;
+        job.bulk_workgroups = bulk_workgroups ? bulk_workgroups : kMsmBulkWorkgroups;
+        const MsmPlan p = dev_msm_plan(c, *g.dev, job);
+        if (plan5) { plan5[0] = (uint32_t)p.kernel; plan5[1] = (uint32_t)p.chunk; plan5[2] = (uint32_t)p.nchunks; plan5[3] = (uint32_t)p.fuse; plan5[4] = (uint32_t)p.route; }
+        KTimer t(c, ms); const MsmTicket tk = dev_msm_rows(c, *g.dev, job); t.stop();
+        c.wait_points(tk);                                        // by the ticket's route: mailed and flagged sums arrive without a stream synchronise
+        if (mode == MSM_COMPRESSED) { memcpy(out32, c.h_points, 32 * rows); c.sync(); return OTTI_OK; }
+        if (mode == MSM_RAW) OTTI_HIP(hipMemcpyAsync(kept.p, c.h_pts, rows * sizeof(Pt), hipMemcpyHostToDevice, c.stream));
+        dev_encode_points(c, kept.p, rows, enc.p);
+        OTTI_HIP(hipMemcpyAsync(out32, enc.p, 32 * rows, hipMemcpyDeviceToHost, c.stream));
+        OTTI_HIP(hipStreamSynchronize(c.stream)); return OTTI_OK;
+    });
+}
 
 // (index, scalar) lists summed into L rows over the generators' table (k_msm.hip k_msm_scatter, the kernel that patches a witness's kept rows),
 // here onto L identity points, which are then compressed.  The index list is judged on the host: the kernel takes table columns from it.

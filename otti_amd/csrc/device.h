@@ -471,10 +471,12 @@ struct MsmJob {
     // compact the non-zero (term, window) pairs into a work list instead of giving every pair a lane.  Results are identical either way.
     bool sparse = false;
     Pt *keep_dst = nullptr; bool force_bulk = false;
+    size_t bulk_workgroups = kMsmBulkWorkgroups;              // msm_plan.h MsmShape: only otti_k_msm_job (the tests) sets another value
 };
 constexpr double kSparseWitness = 0.25;                      // above this share of small scalars a commitment uses the work-list MSM variant
 // returns a ticket: c.wait_points(ticket) returns once the compressed points are in c.h_points
 MsmTicket dev_msm_rows(DevCtx &c, const DeviceGens &g, const MsmJob &job);
+MsmPlan dev_msm_plan(DevCtx &c, const DeviceGens &g, const MsmJob &job);   // the plan dev_msm_rows takes for this job (the same call of msm_plan())
 double dev_small_fraction(DevCtx &c, const Fr *z, size_t n);               // share of scalars below 2^128 (synchronises the stream)
 // MSM_RAW: skip compression; after c.sync() the extended row sums are in c.h_pts[0..rows).
 // MSM_KEEP: no output; the row sums stay on the device in c.msm_keep (to be passed as `addend` of a later launch, which then

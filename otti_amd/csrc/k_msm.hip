@@ -518,6 +518,10 @@ static void msm_report_stamps(DevCtx &c, const unsigned long long *t, const MsmJ
         fprintf(stderr, "[otti] k_msm_small rows=%zu terms=%zu chunks=%zu bullet=%d: scalars %.2f | pairs %.2f | tree %.2f | (others arrive) %.2f | chunk sums %.2f | row tree %.2f | mail %.2f | total %.2f us\n",
                 rows, terms, nchunks, bullet ? 1 : 0, us(0, 1), us(1, 2), us(2, 3), us(3, 4), us(4, 5), us(5, 6), us(6, 7), us(0, 7));
 }
+static MsmPlan msm_plan_of(DevCtx &c, const DeviceGens &g, const MsmJob &j, bool bullet) {
+    return msm_plan({g.c, g.W, j.rows, j.n_dense, j.n_extra, bullet, j.mode, j.addend != nullptr, j.sparse, j.force_bulk, c.msm_mail.host_sum(c), j.bulk_workgroups});
+}
+MsmPlan dev_msm_plan(DevCtx &c, const DeviceGens &g, const MsmJob &job) { return msm_plan_of(c, g, job, false); }
 // One launch in four steps: plan it (msm_plan.h), fill the kernel's arguments from the plan and the job, launch, hand the row sums on by route.
 static MsmTicket msm_launch(DevCtx &c, const DeviceGens &g, const MsmJob &j, const BulletArgs *bul) {
     if (j.n_extra > 8) throw Error(OTTI_ERR_INTERNAL, "msm: too many extra terms");
@@ -526,7 +530,7 @@ static MsmTicket msm_launch(DevCtx &c, const DeviceGens &g, const MsmJob &j, con
     for (size_t i = 0; i < j.n_extra; i++) if (j.extra_base[i] >= g.nbases) throw Error(OTTI_ERR_INTERNAL, "msm: an extra term's base lies beyond the table");
     const size_t rows = j.rows;
     if (!rows) return {};
-    const MsmPlan p = msm_plan({g.c, g.W, rows, j.n_dense, j.n_extra, bul != nullptr, j.mode, j.addend != nullptr, j.sparse, j.force_bulk, c.msm_mail.host_sum(c)});
+    const MsmPlan p = msm_plan_of(c, g, j, bul != nullptr);
     const size_t nchunks = p.nchunks;
     if (p.route == MsmRoute::raw && rows > kHostPtsCap) throw Error(OTTI_ERR_INTERNAL, "msm: too many raw rows");
     MsmArgs A;

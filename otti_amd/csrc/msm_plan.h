@@ -40,6 +40,10 @@ struct MsmShape {
     bool bullet;                                             // a bullet-reduction round (scalars derived in the kernel)
     int mode; bool addend, sparse, force_bulk;
     bool host_sum;                                           // this process's small launches are summed on the host (MsmMailbox::host_sum)
+    // The workgroups a bulk launch aims for.  Every prover call site leaves the default.  ONLY the kernel-level test entry otti_k_msm_job sets
+    // another value (the MSM's counterpart of sc_caps_override): with 1, one workgroup takes min(n_dense, kMsmBulkTerms) terms, so one row of
+    // 2048 terms walks the sub-chunks of k_msm_rows that otherwise need an instance of 2^22 constraints.
+    size_t bulk_workgroups = kMsmBulkWorkgroups;
 };
 struct MsmPlan { MsmKernel kernel; size_t chunk, nchunks; int fuse; MsmRoute route; uint32_t K[9]; };
 
@@ -49,9 +53,9 @@ inline MsmPlan msm_plan(const MsmShape &q) {
     const bool sparse = bulk && q.sparse && q.W <= 32;
     size_t nchunks;
     if (bulk) {
-        // aim for >= 1024 workgroups (4 per CU) but keep at least one term per term lane and at most kMsmMaxChunk per workgroup;
+        // aim for >= bulk_workgroups workgroups (1024, 4 per CU, unless a test says otherwise) but keep at least one term per term lane and at most kMsmMaxChunk per workgroup;
         // the sparse variant keeps a (term, window) work list in LDS: (chunk + extras) * W <= kMsmListCap;  W <= 32 there (5-bit window field)
-        nchunks = std::max<size_t>(1, (kMsmBulkWorkgroups + rows - 1) / rows);
+        nchunks = std::max<size_t>(1, (std::max<size_t>(1, q.bulk_workgroups) + rows - 1) / rows);
         nchunks = std::min(nchunks, std::max<size_t>(1, n_dense / lanes));
         const size_t max_chunk = kMsmBulkTerms;               // both bulk kernels walk their chunk in sub-chunks that fit the LDS
         nchunks = std::max(nchunks, (n_dense + max_chunk - 1) / max_chunk);

@@ -70,7 +70,7 @@ public:
     // share ran at 470 M constraints/s, with one helper each at 730 (tools/inflight_variants.sh, profiles/r4_inflight_variants.txt).
     // The helpers beyond the budget stop spinning (run()).
     int workers() const {
-        const int n = (int)th_.size(), s = cpu_place::sessions().load(std::memory_order_relaxed);
+        const int n = n_helpers_, s = cpu_place::sessions().load(std::memory_order_relaxed);
         if (s <= 1 || fixed_) return n;
         return std::max(0, std::min(n, (int)cores_ / s - 1));
     }
@@ -111,6 +111,7 @@ public:
 private:
     struct alignas(64) Slot { std::atomic<int> state{0}; std::function<void()> fn; };
     std::vector<std::thread> th_;
+    int n_helpers_ = 0;                               // th_.size() once built; set BEFORE the first helper starts: run() asks workers() while th_ may still grow
     std::vector<Slot> slots_;
     std::atomic<bool> quit_{false};
     std::atomic<int> active_{0};
@@ -134,6 +135,7 @@ private:
         if (const char *e = getenv("OTTI_HOST_THREADS")) { int v = atoi(e); if (v >= 1 && v <= 16) n = v - 1; }
         if (const char *e = getenv("OTTI_HOST_THREADS_FIXED")) fixed_ = e[0] == '1';      // keep every helper whatever the number of provers at work
         slots_ = std::vector<Slot>(n > 0 ? n : 1);
+        n_helpers_ = n > 0 ? n : 0; th_.reserve(n_helpers_);
         for (int i = 0; i < n; i++) th_.emplace_back([this, i] { run(i); });
     }
     ~SpinPool() {

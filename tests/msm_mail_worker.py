@@ -1,5 +1,7 @@
-"""Worker of tests/test_gpu_msm_small_mail.py: in a fresh process (OTTI_SMALL_HOST_SUM is read once per process), either
+"""Worker of tests/test_gpu_msm_small_mail.py and tests/test_gpu_msm_edges.py: in a fresh process (OTTI_SMALL_HOST_SUM is read once per process), either
   msm   — one- and two-row fixed-base sums of the latency-bound kind over several row lengths: prints "MSM <L> <lgV> <hex of the points>"
+  edges — tests/test_gpu_msm_edges.py small_sum_lines(): the c = 8 digit rows and the one- and two-row shape jobs through oa.kernels.msm_job
+          (OTTI_MSM_WINDOW=8 comes with the environment): prints "EDGE <name> <fuse> <hex of the points>"
   nizk <lg> — the committed golden NIZK instance of 2^lg constraints: prints "DIGEST <sha256 of the proof>"."""
 import hashlib
 import json
@@ -25,6 +27,10 @@ if sys.argv[1] == "msm":
         Z, bl = orc.rand_fr(rng, L * R), orc.rand_fr(rng, L)
         out, _ = oa.kernels.msm_rows(gens, Z, L, R, bl)
         print("MSM", L, lgV, np.asarray(out).tobytes().hex(), flush=True)
+elif sys.argv[1] == "edges":
+    from test_gpu_msm_edges import small_sum_lines  # noqa: E402
+    for ln in small_sum_lines():
+        print("EDGE", ln, flush=True)
 else:
     n = 1 << int(sys.argv[2])
     g = [x for x in json.load(open(os.path.join(HERE, "golden", "proofs.json"))) if x["n"] == n][0]

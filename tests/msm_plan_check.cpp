@@ -43,8 +43,32 @@ static const Case kCases[] = {
     { 4,    2, 32767, 1, CMP,  F, F, F, F, T,  SMALL,    64, 512, 0, MsmRoute::host_encode},      // 1024 mails > kMsmMailCap: not fused
 };
 
+// The tests' seam (MsmShape::bulk_workgroups, set only by otti_k_msm_job): aiming for ONE workgroup, a row of 2048 terms is one chunk, which the
+// bulk kernels walk in sub-chunks — the walk a default plan reaches only from 2^22 constraints up (the {17, 4096, 4096} case above).
+struct SeamCase { int c; size_t rows, n_dense, n_extra; bool sparse; size_t aim; MsmKernel kernel; size_t chunk, nchunks; };
+static const SeamCase kSeamCases[] = {
+    { 8, 1, 2048, 0, F, 1,    BULK,   2048, 1},
+    { 8, 3, 2048, 8, F, 1,    BULK,   2048, 1},
+    { 8, 1, 2048, 0, T, 1,    SPARSE, 2048, 1},
+    {13, 3, 2048, 1, T, 1,    SPARSE, 2048, 1},
+    { 4, 3, 2048, 0, T, 1,    BULK,   2048, 1},                                                   // W = 64: no work list
+    { 8, 1, 4097, 0, F, 1,    BULK,   2049, 2},                                                   // never more than kMsmBulkTerms per workgroup
+    { 8, 3, 2048, 0, F, 1024, BULK,      8, 256},                                                // the default aim, spelled out: as without the member
+};
+
 int main() {
     int failures = 0;
+    for (const SeamCase &k : kSeamCases) {
+        const int W = 253 / k.c + 1;
+        const MsmPlan p = msm_plan({k.c, W, k.rows, k.n_dense, k.n_extra, false, MSM_COMPRESSED, false, k.sparse, true, true, k.aim});
+        const MsmPlan d = msm_plan({k.c, W, k.rows, k.n_dense, k.n_extra, false, MSM_COMPRESSED, false, k.sparse, true, true});
+        if (p.kernel != k.kernel || p.chunk != k.chunk || p.nchunks != k.nchunks || p.fuse != 0) {
+            failures++;
+            printf("FAIL seam c=%d rows=%zu n_dense=%zu aim=%zu: plan %s chunk %zu x %zu fuse %d, expected %s chunk %zu x %zu\n", k.c, k.rows, k.n_dense, k.aim,
+                   kKernel[(int)p.kernel], p.chunk, p.nchunks, p.fuse, kKernel[(int)k.kernel], k.chunk, k.nchunks);
+        }
+        if (k.aim == kMsmBulkWorkgroups && (d.chunk != p.chunk || d.nchunks != p.nchunks || d.kernel != p.kernel)) { failures++; printf("FAIL the default aim is not kMsmBulkWorkgroups\n"); }
+    }
     for (const Case &k : kCases) {
         const int W = 253 / k.c + 1;
         const MsmPlan p = msm_plan({k.c, W, k.rows, k.n_dense, k.n_extra, k.bullet, k.mode, k.addend, k.sparse, k.force_bulk, k.host_sum});

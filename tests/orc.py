@@ -233,6 +233,31 @@ def commit_rows(gens, Z, L, R, blinds):
     lib.orc_commit_rows(_p(Z), L, R, _p(blinds), gens.pc_n, _p(out)); return out
 
 
+_GE_BYTES = 160                                                    # sizeof(ge_t): four field elements of five 64-bit limbs
+
+
+def decode_points(points32):
+    """(n, 32) compressed points as the oracle's own array of n ge_t, to be handed to msm() many times"""
+    pts = _c(points32); raw = np.zeros(max(1, pts.shape[0]) * _GE_BYTES, dtype=np.uint8)
+    for k in range(pts.shape[0]):
+        if lib.ge_decode(_vp(raw.ctypes.data + _GE_BYTES * k), _p(pts[k])) != 1:
+            raise ValueError(f"point {k} does not decode")
+    return raw
+
+
+def msm(points, scalars):
+    """compress(sum_k scalars[k] * points[k]): points (n, 32) compressed or the array decode_points() made of them; scalars n Python integers
+    (reduced mod l here) or (n, 32) Montgomery bytes.  The oracle's ge_decode / ge_msm / ge_encode, nothing else."""
+    raw = points if points.ndim == 1 else decode_points(points)
+    s = fr_from_ints(list(scalars)) if not isinstance(scalars, np.ndarray) else _c(scalars)
+    n = s.shape[0]
+    assert raw.size >= n * _GE_BYTES
+    acc = np.zeros(_GE_BYTES, dtype=np.uint8); out = np.zeros(32, dtype=np.uint8)
+    lib.ge_msm(_p(acc), _p(s), _p(raw), _sz(n))
+    lib.ge_encode(_p(out), _p(acc))
+    return out
+
+
 def poly_bound(Z, L, R, Lv):
     Z, Lv = _c(Z), _c(Lv); out = np.zeros((R, 32), dtype=np.uint8)
     lib.orc_poly_bound(_p(Z), L, R, _p(Lv), _p(out)); return out

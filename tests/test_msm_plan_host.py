@@ -1,6 +1,7 @@
 """The fixed-base MSM's launch plan (otti_amd/csrc/msm_plan.h: kernel, chunking, fuse and result route of every launch) as a host program:
 the header is standard library only, so the arithmetic that sets the dominant kernel's grid is pinned without a GPU.  The launches
-themselves are covered on the GPU by tests/test_gpu_msm_small_mail.py, test_gpu_witness_rows.py and test_gpu_kernels.py."""
+themselves are covered on the GPU by tests/test_gpu_msm_small_mail.py, test_gpu_witness_rows.py and test_gpu_kernels.py.
+tests/test_gpu_msm_edges.py runs the kernels at these plans, and at the seam's (bulk_workgroups = 1), and asserts the plan each launch took."""
 import os, subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
