@@ -4,7 +4,7 @@
 
 namespace otti {
 
-// ------------------------------------------------------------------------------------------------ K1 / K6 sparse products
+// ------------------------------------------------------------------------------------------------ what every pass over a DCsr3 shares
 // one entry's product.  kSmall: the coefficient is read as a 4-byte code first; only codes that are not small integers touch the 32-byte value
 template <bool kSmall> __device__ __forceinline__ Fr entry_term(const DCsr3 &m, int k, uint32_t p, const Fr *x) {
     const Fr xv = x[m.idx[k][p]];
@@ -16,40 +16,80 @@ __device__ __forceinline__ Fr combine3(const Fr &c0, const Fr &c1, const Fr &c2,
     const Fr9 t = fr9_add(fr9_add(fr9_mul(fr9_unpack5(c0), fr9_unpack(a0)), fr9_mul(fr9_unpack5(c1), fr9_unpack(a1))), fr9_mul(fr9_unpack5(c2), fr9_unpack(a2)));
     return fr9_canon(fr9_norm(t));
 }
-template <bool kSmall> __device__ __forceinline__ Fr row_dot(const DCsr3 &m, int k, const Fr *x, size_t r) {
-    Fr acc = fr_zero();
-    const uint32_t p0 = m.ptr[k][r], p1 = m.ptr[k][r + 1];
-    for (uint32_t p = p0; p < p1; p++) acc = fr_add(acc, entry_term<kSmall>(m, k, p, x));
-    return acc;
+// THE long-row rule: a row (of the by-column set: a column) whose longest list exceeds kHeavyRow belongs to the workgroup-per-row or segmented
+// kernels and to nobody else.  Every kernel, the CSR builder's count and its segment lists ask here, so no row is written twice or not at all.
+__host__ __device__ __forceinline__ bool len_is_heavy(uint32_t longest) { return longest > (uint32_t)kHeavyRow; }
+__device__ __forceinline__ bool row_is_heavy(const DCsr3 &m, size_t r) {
+    return len_is_heavy(max(m.ptr[0][r + 1] - m.ptr[0][r], max(m.ptr[1][r + 1] - m.ptr[1][r], m.ptr[2][r + 1] - m.ptr[2][r])));
 }
+// Long lists (a linear combination over thousands of variables; the constant-1 column of a compiled circuit, which can hold O(N)
+// entries in the transposed copy) are cut into segments of kHeavySeg entries: one workgroup per segment writes the three raw partial
+// sums, then one workgroup per long list adds its segments up and applies the combination.
+constexpr uint32_t kHeavySeg = 2048;
+constexpr uint32_t kWholeList = 0xffffffffu;           // for_entries' segment number: the list is not clipped
+// THE entry walk: f(p) for the entries first, first + step, .. of list k of row r — first = 0, step = 1 for a row per lane; the lane's place in its
+// quad and 4 for a row per quad; threadIdx.x and kBlock for a workgroup per row — or of that list's segment sn alone.  How a row's entries are
+// fetched is decided here and nowhere else.
+template <class F> __device__ __forceinline__ void for_entries(const DCsr3 &m, int k, size_t r, uint32_t first, uint32_t step, uint32_t sn, F f) {
+    uint32_t p = m.ptr[k][r], p1 = m.ptr[k][r + 1];
+    if (sn != kWholeList) {
+        const uint64_t lo = (uint64_t)p + (uint64_t)sn * kHeavySeg;
+        if (lo >= p1) return;                                       // (the same for every thread of the workgroup)
+        p = (uint32_t)lo; p1 = (uint32_t)min((uint64_t)p1, lo + kHeavySeg);
+    }
+    for (p += first; p < p1; p += step) f(p);
+}
+// a[k] = this lane's share (entries q, q + kLanes, ..) of <M_k row r, x>, k = 0, 1, 2: the whole sum for kLanes = 1, to be added up by quad_sum
+// for 4 and by block_reduce for kBlock
+template <bool kSmall, uint32_t kLanes> __device__ __forceinline__ void row_sums(const DCsr3 &m, const Fr *x, size_t r, uint32_t q, Fr (&a)[3], uint32_t sn = kWholeList) {
+    for (int k = 0; k < 3; k++) {
+        a[k] = fr_zero();
+        for_entries(m, k, r, q, kLanes, sn, [&](uint32_t p) { a[k] = fr_add(a[k], entry_term<kSmall>(m, k, p, x)); });
+    }
+}
+__device__ __forceinline__ Fr quad_sum(Fr a) {
+    a = fr_add(a, shfl_xor_fr(a, 1)); a = fr_add(a, shfl_xor_fr(a, 2)); return a;
+}
+// THE segment add-up: one workgroup per long row h adds its segments' partial sums up, K of them per segment (sum j of segment s is
+// partial[s * stride + j]); thread 0 ends up with the totals.  (The constant-1 column of a compiled circuit can have hundreds of segments: one
+// thread walking them alone took ~90 us.)
+template <int K> __device__ __forceinline__ void segment_sums(const uint32_t *seg_begin, size_t h, const Fr *partial, size_t stride, Fr (&acc)[K]) {
+#pragma unroll
+    for (int j = 0; j < K; j++) acc[j] = fr_zero();
+    for (uint32_t s = seg_begin[h] + threadIdx.x; s < seg_begin[h + 1]; s += blockDim.x)
+#pragma unroll
+        for (int j = 0; j < K; j++) acc[j] = fr_add(acc[j], partial[(size_t)s * stride + j]);
+    block_reduce<K>(acc);
+}
+// The launchers' one dispatch: a run-time flag as a compile-time constant (by_flag: the kernels with one template flag), and a set's two —
+// coefficient codes, row per quad — for the row kernels (by_layout).
+template <class F> static inline void by_flag(bool flag, F f) { if (flag) f(std::true_type{}); else f(std::false_type{}); }
+template <class F> static inline void by_layout(const DeviceCsrSet &m, F f) {
+    by_flag(m.use_small, [&](auto small) { by_flag(m.quad(), [&](auto quad) { f(small, quad); }); });
+}
+
+// ------------------------------------------------------------------------------------------------ K1 / K6 sparse products
+// rows up to kHeavyRow entries, a row per lane
 template <bool kSmall> __global__ __launch_bounds__(kBlock) void k_spmv3_light(DCsr3 m, size_t rows, const Fr *x, Fr *o0, Fr *o1, Fr *o2, int combine, Fr c0, Fr c1, Fr c2) {
     for (size_t r = blockIdx.x * (size_t)blockDim.x + threadIdx.x; r < rows; r += (size_t)gridDim.x * blockDim.x) {
-        uint32_t l0 = m.ptr[0][r + 1] - m.ptr[0][r], l1 = m.ptr[1][r + 1] - m.ptr[1][r], l2 = m.ptr[2][r + 1] - m.ptr[2][r];
-        if (max(l0, max(l1, l2)) > (uint32_t)kHeavyRow) continue;
-        Fr a0 = row_dot<kSmall>(m, 0, x, r);
-        Fr a1 = row_dot<kSmall>(m, 1, x, r);
-        Fr a2 = row_dot<kSmall>(m, 2, x, r);
-        if (combine) o0[r] = combine3(c0, c1, c2, a0, a1, a2);
-        else { o0[r] = a0; o1[r] = a1; o2[r] = a2; }
+        if (row_is_heavy(m, r)) continue;
+        Fr a[3];
+        row_sums<kSmall, 1>(m, x, r, 0, a);
+        if (combine) o0[r] = combine3(c0, c1, c2, a[0], a[1], a[2]);
+        else { o0[r] = a[0]; o1[r] = a[1]; o2[r] = a[2]; }
     }
 }
 // The same with FOUR lanes per row (a quad walks its row four entries at a time and adds up by quad shuffles): for matrices with several
 // entries per row the value / index loads of a wave are then 128-byte runs instead of one entry per lane at row-length strides.
-__device__ __forceinline__ Fr quad_sum(Fr a) {
-    a = fr_add(a, shfl_xor_fr(a, 1)); a = fr_add(a, shfl_xor_fr(a, 2)); return a;
-}
+// (Not one body with k_spmv3_light, as k_prod_rows has: merged, three of the four variants took 2 to 6 VGPRs more — profiles/sparse_walk.md.)
 template <bool kSmall> __global__ __launch_bounds__(kBlock) void k_spmv3_quad(DCsr3 m, size_t rows, const Fr *x, Fr *o0, Fr *o1, Fr *o2, int combine, Fr c0, Fr c1, Fr c2) {
-    const int q = threadIdx.x & 3;
+    const uint32_t q = threadIdx.x & 3;
     for (size_t r = (blockIdx.x * (size_t)blockDim.x + threadIdx.x) >> 2; r < ((rows + 63) & ~(size_t)63); r += ((size_t)gridDim.x * blockDim.x) >> 2) {
         Fr a[3] = {fr_zero(), fr_zero(), fr_zero()};
         bool heavy = false;
         if (r < rows) {
-            heavy = max(m.ptr[0][r + 1] - m.ptr[0][r], max(m.ptr[1][r + 1] - m.ptr[1][r], m.ptr[2][r + 1] - m.ptr[2][r])) > (uint32_t)kHeavyRow;
-            if (!heavy)
-                for (int k = 0; k < 3; k++) {
-                    const uint32_t p1 = m.ptr[k][r + 1];
-                    for (uint32_t p = m.ptr[k][r] + (uint32_t)q; p < p1; p += 4) a[k] = fr_add(a[k], entry_term<kSmall>(m, k, p, x));
-                }
+            heavy = row_is_heavy(m, r);
+            if (!heavy) row_sums<kSmall, 4>(m, x, r, q, a);
         }
         for (int k = 0; k < 3; k++) a[k] = quad_sum(a[k]);         // every lane of the wave takes part (rows are padded to whole waves above)
         if (r < rows && !heavy && q == 0) {
@@ -58,37 +98,29 @@ template <bool kSmall> __global__ __launch_bounds__(kBlock) void k_spmv3_quad(DC
         }
     }
 }
-// Long lists (a linear combination over thousands of variables; the constant-1 column of a compiled circuit, which can hold O(N)
-// entries in the transposed copy) are cut into segments of kHeavySeg entries: one workgroup per segment writes the three raw partial
-// sums, then one thread per long list adds its segments up and applies the combination.
-constexpr uint32_t kHeavySeg = 2048;
+// a long row's segment: partial[segment * 3 + k], raw sums
 template <bool kSmall> __global__ __launch_bounds__(kBlock) void k_spmv3_heavy_seg(DCsr3 m, const uint32_t *seg_row, const uint32_t *seg_no, const Fr *x, Fr *partial) {
-    const size_t r = seg_row[blockIdx.x]; const uint32_t sn = seg_no[blockIdx.x];
     Fr acc[3];
-    for (int k = 0; k < 3; k++) {
-        acc[k] = fr_zero();
-        const uint32_t p0 = m.ptr[k][r], p1 = m.ptr[k][r + 1];
-        const uint64_t lo = (uint64_t)p0 + (uint64_t)sn * kHeavySeg;
-        if (lo >= p1) continue;
-        const uint32_t hi = (uint32_t)min((uint64_t)p1, lo + kHeavySeg);
-        for (uint32_t p = (uint32_t)lo + threadIdx.x; p < hi; p += blockDim.x) acc[k] = fr_add(acc[k], entry_term<kSmall>(m, k, p, x));
-    }
+    row_sums<kSmall, kBlock>(m, x, seg_row[blockIdx.x], threadIdx.x, acc, seg_no[blockIdx.x]);
     block_reduce<3>(acc);
     if (threadIdx.x == 0) for (int k = 0; k < 3; k++) partial[(size_t)blockIdx.x * 3 + k] = acc[k];
 }
-// one workgroup per long list: its segments' partial sums are added up across the workgroup (the constant-1 column of a compiled circuit
-// can have hundreds of segments: one thread walking them alone took ~90 us)
 __global__ __launch_bounds__(kBlock) void k_spmv3_heavy_combine(const uint32_t *heavy, const uint32_t *seg_begin, size_t n_heavy, const Fr *partial, Fr *o0, Fr *o1, Fr *o2,
                                                                 int combine, Fr c0, Fr c1, Fr c2) {
-    const size_t h = blockIdx.x;
-    Fr acc[3] = {fr_zero(), fr_zero(), fr_zero()};
-    for (uint32_t s = seg_begin[h] + threadIdx.x; s < seg_begin[h + 1]; s += blockDim.x)
-        for (int k = 0; k < 3; k++) acc[k] = fr_add(acc[k], partial[(size_t)s * 3 + k]);
-    block_reduce<3>(acc);
+    Fr acc[3];
+    segment_sums<3>(seg_begin, blockIdx.x, partial, 3, acc);
     if (threadIdx.x != 0) return;
-    const size_t r = heavy[h];
+    const size_t r = heavy[blockIdx.x];
     if (combine) o0[r] = fr_add(fr_add(fr_mul(c0, acc[0]), fr_mul(c1, acc[1])), fr_mul(c2, acc[2]));
     else { o0[r] = acc[0]; o1[r] = acc[1]; o2[r] = acc[2]; }
+}
+// every long row's segments into the CALLER's context (c.spmv_partial: the matrix object itself is shared by concurrent provers), for
+// k_spmv3_heavy_combine or k_sat_heavy_check behind it
+static void launch_heavy_segments(DevCtx &c, const DeviceCsrSet &m, const Fr *x) {
+    if (c.spmv_partial.n < 3 * m.n_seg) { OTTI_HIP(hipStreamSynchronize(c.stream)); c.spmv_partial.alloc(3 * m.n_seg); }
+    by_flag(m.use_small, [&](auto small) {
+        hipLaunchKernelGGL(k_spmv3_heavy_seg<decltype(small)::value>, (unsigned)m.n_seg, kBlock, 0, c.stream, m.view(), (const uint32_t *)m.seg_row.p, (const uint32_t *)m.seg_no.p, x, c.spmv_partial.p);
+    });
 }
 void dev_spmv3(DevCtx &c, const DeviceCsrSet &m, const Fr *x, Fr *o0, Fr *o1, Fr *o2, bool combine, const Fr coef[3]) {
     Fr z = fr_zero();
@@ -96,20 +128,14 @@ void dev_spmv3(DevCtx &c, const DeviceCsrSet &m, const Fr *x, Fr *o0, Fr *o1, Fr
     KScope ks(c, KC_SPMV);
     // measured on the compiler-like 2^20 instance (4.6 entries per row and matrix): 0.54 -> 0.37 ms; on the uniform one (1 entry) the quad
     // kernel would idle three lanes in four (0.16 -> 0.54 ms)
-    const bool quad = m.quad();
-    const bool sm = m.use_small;
-    if (quad && sm) hipLaunchKernelGGL(k_spmv3_quad<true>, grid_for(4 * m.rows), kBlock, 0, c.stream, m.view(), m.rows, x, o0, o1, o2, (int)combine, c0, c1, c2);
-    else if (quad) hipLaunchKernelGGL(k_spmv3_quad<false>, grid_for(4 * m.rows), kBlock, 0, c.stream, m.view(), m.rows, x, o0, o1, o2, (int)combine, c0, c1, c2);
-    else if (sm) hipLaunchKernelGGL(k_spmv3_light<true>, grid_for(m.rows), kBlock, 0, c.stream, m.view(), m.rows, x, o0, o1, o2, (int)combine, c0, c1, c2);
-    else hipLaunchKernelGGL(k_spmv3_light<false>, grid_for(m.rows), kBlock, 0, c.stream, m.view(), m.rows, x, o0, o1, o2, (int)combine, c0, c1, c2);
-    if (m.n_heavy) {
-        // segment partials are scratch of the CALLER's context: the matrix object itself is shared by concurrent provers
-        if (c.spmv_partial.n < 3 * m.n_seg) { OTTI_HIP(hipStreamSynchronize(c.stream)); c.spmv_partial.alloc(3 * m.n_seg); }
-        if (sm) hipLaunchKernelGGL(k_spmv3_heavy_seg<true>, (unsigned)m.n_seg, kBlock, 0, c.stream, m.view(), (const uint32_t *)m.seg_row.p, (const uint32_t *)m.seg_no.p, x, c.spmv_partial.p);
-        else hipLaunchKernelGGL(k_spmv3_heavy_seg<false>, (unsigned)m.n_seg, kBlock, 0, c.stream, m.view(), (const uint32_t *)m.seg_row.p, (const uint32_t *)m.seg_no.p, x, c.spmv_partial.p);
-        hipLaunchKernelGGL(k_spmv3_heavy_combine, (unsigned)m.n_heavy, kBlock, 0, c.stream, (const uint32_t *)m.heavy.p, (const uint32_t *)m.seg_begin.p, m.n_heavy,
-                           (const Fr *)c.spmv_partial.p, o0, o1, o2, (int)combine, c0, c1, c2);
-    }
+    by_layout(m, [&](auto small, auto quad) {
+        constexpr bool S = decltype(small)::value, Q = decltype(quad)::value;
+        hipLaunchKernelGGL((Q ? k_spmv3_quad<S> : k_spmv3_light<S>), grid_for(Q ? 4 * m.rows : m.rows), kBlock, 0, c.stream, m.view(), m.rows, x, o0, o1, o2, (int)combine, c0, c1, c2);
+    });
+    if (!m.n_heavy) return;
+    launch_heavy_segments(c, m, x);
+    hipLaunchKernelGGL(k_spmv3_heavy_combine, (unsigned)m.n_heavy, kBlock, 0, c.stream, (const uint32_t *)m.heavy.p, (const uint32_t *)m.seg_begin.p, m.n_heavy,
+                       (const Fr *)c.spmv_partial.p, o0, o1, o2, (int)combine, c0, c1, c2);
 }
 
 // ------------------------------------------------------------------------------------------------ A, B, C at a tile of points (device.h dev_eval_tile)
@@ -128,9 +154,6 @@ void dev_spmv3(DevCtx &c, const DeviceCsrSet &m, const Fr *x, Fr *o0, Fr *o1, Fr
 // k_eval_finish adds the partials up.  Every word is canonical after every step (comment above row_fails), so the sums do not depend on the
 // geometry.  Slots t >= nt of a short tile are neither read nor accumulated: their totals stay zero.
 template <int KT> struct EvalTile { const Fr *xlo, *xhi, *ey_il; int xlo_bits, nt; };
-__device__ __forceinline__ bool eval_row_heavy(const DCsr3 &m, size_t r) {       // the rule of k_spmv3_light: such a row is the segmented path's
-    return max(m.ptr[0][r + 1] - m.ptr[0][r], max(m.ptr[1][r + 1] - m.ptr[1][r], m.ptr[2][r + 1] - m.ptr[2][r])) > (uint32_t)kHeavyRow;
-}
 __device__ __forceinline__ Fr mul9(const Fr &a, const Fr &b) { return fr9_pack_lt2l(fr9_mul(fr9_unpack5(a), fr9_unpack(b))); }   // 32 a b / 2^261 + l < 1.1 l
 // element i of point t's table from its interleaved factors
 template <int KT> __device__ __forceinline__ Fr eval_eq_at(const Fr *lo_il, const Fr *hi_il, int lo_bits, size_t i, int t) {
@@ -149,6 +172,10 @@ template <bool kSmall, int KT> __device__ __forceinline__ void entry_terms(const
     const Fr9 v5 = fr9_unpack5(m.val[k][p]);
 #pragma unroll
     for (int t = 0; t < KT; t++) if (t < T.nt) acc[t] = fr_add(acc[t], fr9_pack_lt2l(fr9_mul(v5, fr9_unpack(xv[t]))));
+}
+// row_sums' tile form: this lane's share of list k of row r (or of its segment sn), added to the tile's KT inner sums
+template <bool kSmall, int KT, uint32_t kLanes> __device__ __forceinline__ void row_terms(const DCsr3 &m, int k, size_t r, uint32_t q, const EvalTile<KT> &T, Fr (&acc)[KT], uint32_t sn = kWholeList) {
+    for_entries(m, k, r, q, kLanes, sn, [&](uint32_t p) { entry_terms<kSmall, KT>(m, k, p, T, acc); });
 }
 template <int KT> __device__ __forceinline__ void eval_zero(Fr (&a)[KT]) {
 #pragma unroll
@@ -181,11 +208,9 @@ template <bool kSmall, int KT> __global__ __launch_bounds__(kBlock) void k_eval_
     for (int k = 0; k < 3; k++) {
         Fr tot[KT]; eval_zero<KT>(tot);
         for (size_t r = r0; r < rows; r += (size_t)gridDim.x * blockDim.x) {
-            if (eval_row_heavy(m, r)) continue;
-            const uint32_t p0 = m.ptr[k][r], p1 = m.ptr[k][r + 1];
-            if (p0 == p1) continue;
+            if (row_is_heavy(m, r) || m.ptr[k][r] == m.ptr[k][r + 1]) continue;      // (an empty list: no product with the high factor either)
             Fr in[KT]; eval_zero<KT>(in);
-            for (uint32_t p = p0; p < p1; p++) entry_terms<kSmall, KT>(m, k, p, T, in);
+            row_terms<kSmall, KT, 1>(m, k, r, 0, T, in);
             eval_row_done<KT>(T, r, in, tot);
         }
         eval_apply_low<KT>(T, r0, tot);
@@ -196,6 +221,8 @@ template <bool kSmall, int KT> __global__ __launch_bounds__(kBlock) void k_eval_
 // lanes of a quad hold the row's KT inner sums: lane q of the quad takes point q — one product with the high factor per lane, not KT of them on one
 // lane with three idle — and keeps ONE running total, that of its point.  The totals of a point then sit in the lanes q = t of every quad: they are
 // added up over the wave by shuffles that keep q (offsets 4 .. 32), over the workgroup through LDS.
+// The one kernel that writes for_entries' walk out: through row_terms the codes variant took 124 VGPRs for 115 and the compiler-like 2^20 tile
+// 1.331 ms for 1.313 (profiles/sparse_walk.md).  A change to for_entries is made in this loop as well.
 template <bool kSmall, int KT> __global__ __launch_bounds__(kBlock) void k_eval_quad(DCsr3 m, size_t rows, EvalTile<KT> T, Fr *partial) {
     static_assert(KT <= 4, "a quad's four lanes take a point each");
     __shared__ Fr sm[KT][16];
@@ -207,8 +234,8 @@ template <bool kSmall, int KT> __global__ __launch_bounds__(kBlock) void k_eval_
         Fr tot = fr_zero();
         for (size_t r = r0; r < ((rows + 63) & ~(size_t)63); r += ((size_t)gridDim.x * blockDim.x) >> 2) {
             Fr in[KT]; eval_zero<KT>(in);
-            const bool live = r < rows && !eval_row_heavy(m, r);
-            if (live) {
+            const bool live = r < rows && !row_is_heavy(m, r);
+            if (live) {                                                     // for_entries' walk, written out (above)
                 const uint32_t p1 = m.ptr[k][r + 1];
                 for (uint32_t p = m.ptr[k][r] + (uint32_t)q; p < p1; p += 4) entry_terms<kSmall, KT>(m, k, p, T, in);
             }
@@ -238,12 +265,7 @@ template <bool kSmall, int KT> __global__ __launch_bounds__(kBlock) void k_eval_
 #pragma unroll 1
     for (int k = 0; k < 3; k++) {
         Fr acc[KT]; eval_zero<KT>(acc);
-        const uint32_t p0 = m.ptr[k][r], p1 = m.ptr[k][r + 1];
-        const uint64_t lo = (uint64_t)p0 + (uint64_t)sn * kHeavySeg;
-        if (lo < p1) {                                              // (the same for every thread of the workgroup)
-            const uint32_t hi = (uint32_t)min((uint64_t)p1, lo + kHeavySeg);
-            for (uint32_t p = (uint32_t)lo + threadIdx.x; p < hi; p += blockDim.x) entry_terms<kSmall, KT>(m, k, p, T, acc);
-        }
+        row_terms<kSmall, KT, kBlock>(m, k, r, threadIdx.x, T, acc, sn);
         eval_store_partial<KT>(acc, seg_partial, blockIdx.x, k);
     }
 }
@@ -253,11 +275,8 @@ template <int KT> __global__ __launch_bounds__(kBlock) void k_eval_heavy_combine
     const size_t h = blockIdx.x, r = heavy[h];
 #pragma unroll 1
     for (int k = 0; k < 3; k++) {
-        Fr acc[KT]; eval_zero<KT>(acc);
-        for (uint32_t s = seg_begin[h] + threadIdx.x; s < seg_begin[h + 1]; s += blockDim.x)
-#pragma unroll
-            for (int t = 0; t < KT; t++) acc[t] = fr_add(acc[t], seg_partial[((size_t)s * 3 + k) * KT + t]);
-        block_reduce<KT>(acc);
+        Fr acc[KT];
+        segment_sums<KT>(seg_begin, h, seg_partial + (size_t)k * KT, 3 * KT, acc);
         if (threadIdx.x == 0) {
             Fr tot[KT]; eval_zero<KT>(tot);
             eval_row_done<KT>(T, r, acc, tot);
@@ -318,19 +337,20 @@ void dev_eval_tile(DevCtx &c, const DeviceCsrSet &m, const EvalTables &tab, int 
     if (nt < 1 || nt > KT) throw Error(OTTI_ERR_INTERNAL, "evaluation tile: 1 .. kEvalTile points");
     EvalTile<KT> T; T.xlo = tab.xlo; T.xhi = tab.xhi; T.ey_il = tab.ey_il; T.xlo_bits = tab.xlo_bits; T.nt = nt;
     KScope ks(c, KC_SPMV);
-    const bool quad = m.quad(), sm = m.use_small;      // the layouts dev_spmv3 picks, for its reasons
+    const bool quad = m.quad();                        // the layouts dev_spmv3 picks, for its reasons
     const int grid = grid_for(quad ? 4 * m.rows : m.rows);
     {   // eval_apply_low's premise: a thread's rows lie a multiple of 2^xlo_bits apart, or it has at most one
         const size_t stride = ((size_t)grid * kBlock) / (quad ? 4 : 1);
         if (stride < m.rows && (stride & (((size_t)1 << tab.xlo_bits) - 1)) != 0) throw Error(OTTI_ERR_INTERNAL, "evaluation tile: the launch's row stride splits the low factor");
     }
-    if (quad && sm) hipLaunchKernelGGL((k_eval_quad<true, KT>), grid, kBlock, 0, c.stream, m.view(), m.rows, T, partial);
-    else if (quad) hipLaunchKernelGGL((k_eval_quad<false, KT>), grid, kBlock, 0, c.stream, m.view(), m.rows, T, partial);
-    else if (sm) hipLaunchKernelGGL((k_eval_light<true, KT>), grid, kBlock, 0, c.stream, m.view(), m.rows, T, partial);
-    else hipLaunchKernelGGL((k_eval_light<false, KT>), grid, kBlock, 0, c.stream, m.view(), m.rows, T, partial);
+    by_layout(m, [&](auto small, auto quad) {
+        constexpr bool S = decltype(small)::value, Q = decltype(quad)::value;
+        hipLaunchKernelGGL((Q ? k_eval_quad<S, KT> : k_eval_light<S, KT>), grid, kBlock, 0, c.stream, m.view(), m.rows, T, partial);
+    });
     if (m.n_heavy) {
-        if (sm) hipLaunchKernelGGL((k_eval_heavy_seg<true, KT>), (unsigned)m.n_seg, kBlock, 0, c.stream, m.view(), (const uint32_t *)m.seg_row.p, (const uint32_t *)m.seg_no.p, T, seg_partial);
-        else hipLaunchKernelGGL((k_eval_heavy_seg<false, KT>), (unsigned)m.n_seg, kBlock, 0, c.stream, m.view(), (const uint32_t *)m.seg_row.p, (const uint32_t *)m.seg_no.p, T, seg_partial);
+        by_flag(m.use_small, [&](auto small) {
+            hipLaunchKernelGGL((k_eval_heavy_seg<decltype(small)::value, KT>), (unsigned)m.n_seg, kBlock, 0, c.stream, m.view(), (const uint32_t *)m.seg_row.p, (const uint32_t *)m.seg_no.p, T, seg_partial);
+        });
         hipLaunchKernelGGL(k_eval_heavy_combine<KT>, (unsigned)m.n_heavy, kBlock, 0, c.stream, (const uint32_t *)m.heavy.p, (const uint32_t *)m.seg_begin.p, (const Fr *)seg_partial, T, partial, (size_t)grid);
     }
     hipLaunchKernelGGL(k_eval_finish<KT>, 3u * KT, kBlock, 0, c.stream, (const Fr *)partial, (size_t)grid + m.n_heavy, nt, out);
@@ -340,16 +360,13 @@ void dev_eval_tile(DevCtx &c, const DeviceCsrSet &m, const EvalTables &tab, int 
 // Per constraint row r: a = <A_r,z>, b = <B_r,z>, c = <C_r,z> formed exactly as the products above form them, then a b == c in GF(l).  Az, Bz and
 // Cz are never written: a row's only output is bit (r & 63) of bits[r >> 6], set when the row FAILS, and the failing rows are counted in *count.
 // Forms: z and the coefficients are canonical Montgomery words (< l).  entry_term ends in a conditional subtraction (both of its paths return a
-// word in [0, l)) and fr_add keeps [0, l), so row_dot — and a quad's or a workgroup's sum of such words — is the CANONICAL Montgomery word of the
+// word in [0, l)) and fr_add keeps [0, l), so row_sums — and a quad's or a workgroup's sum of such words — is the CANONICAL Montgomery word of the
 // row sum, never a representative in [l, 2l).  fr_mul(aR, bR) is the canonical word of abR.  Equal field elements are therefore equal words and
 // the comparison is a plain word compare.  The verdict depends on the row alone, so every launch geometry gives the same bitmap and count.
 // Bitmap writes: a wave owns whole 64-row words and lane 0 stores each with one ordinary 8-byte store (every word of the bitmap is written,
 // so it needs no zeroing); only the long rows, judged by a later launch, come in with atomicOr.  The count costs one atomicAdd per wave with
 // failures: at most one per wave of the grid when every row fails.
 __device__ __forceinline__ bool row_fails(const Fr &a, const Fr &b, const Fr &c) { return !fr_eq(fr_mul(a, b), c); }
-__device__ __forceinline__ bool row_is_heavy(const DCsr3 &m, size_t r) {
-    return max(m.ptr[0][r + 1] - m.ptr[0][r], max(m.ptr[1][r + 1] - m.ptr[1][r], m.ptr[2][r + 1] - m.ptr[2][r])) > (uint32_t)kHeavyRow;
-}
 // row per lane (k_spmv3_light's layout): a wave's 64 rows are one word, its verdicts one __ballot
 template <bool kSmall> __global__ __launch_bounds__(kBlock) void k_sat_light(DCsr3 m, size_t rows, const Fr *x, unsigned long long *bits, unsigned long long *count) {
     unsigned long long mine = 0;                                    // failing rows of this wave's words (lane 0)
@@ -357,10 +374,9 @@ template <bool kSmall> __global__ __launch_bounds__(kBlock) void k_sat_light(DCs
     for (size_t r = blockIdx.x * (size_t)blockDim.x + threadIdx.x; r < padded; r += (size_t)gridDim.x * blockDim.x) {
         bool fail = false;
         if (r < rows && !row_is_heavy(m, r)) {
-            const Fr a0 = row_dot<kSmall>(m, 0, x, r);
-            const Fr a1 = row_dot<kSmall>(m, 1, x, r);
-            const Fr a2 = row_dot<kSmall>(m, 2, x, r);
-            fail = row_fails(a0, a1, a2);
+            Fr a[3];
+            row_sums<kSmall, 1>(m, x, r, 0, a);
+            fail = row_fails(a[0], a[1], a[2]);
         }
         const unsigned long long word = (unsigned long long)__ballot(fail);
         if ((threadIdx.x & 63) == 0) { bits[r >> 6] = word; mine += (unsigned long long)__popcll(word); }
@@ -391,11 +407,7 @@ template <bool kSmall> __global__ __launch_bounds__(kBlock) void k_sat_quad(DCsr
         for (int j = 0; j < 4; j++) {
             const size_t r = (w << 6) + (size_t)(16 * j + (lane >> 2));
             Fr a[3] = {fr_zero(), fr_zero(), fr_zero()};
-            if (r < rows && !row_is_heavy(m, r))
-                for (int k = 0; k < 3; k++) {
-                    const uint32_t p1 = m.ptr[k][r + 1];
-                    for (uint32_t p = m.ptr[k][r] + (uint32_t)q; p < p1; p += 4) a[k] = fr_add(a[k], entry_term<kSmall>(m, k, p, x));
-                }
+            if (r < rows && !row_is_heavy(m, r)) row_sums<kSmall, 4>(m, x, r, (uint32_t)q, a);
             for (int k = 0; k < 3; k++) a[k] = quad_sum(a[k]);     // every lane of the wave takes part
             if (q == j) for (int k = 0; k < 3; k++) keep[k] = a[k];
         }
@@ -410,26 +422,18 @@ template <bool kSmall> __global__ __launch_bounds__(kBlock) void k_sat_quad(DCsr
 // the checking form of k_spmv3_heavy_combine: one workgroup per long row adds its segments' partial sums up and sets the row's bit.  Runs after
 // the launch above has stored the row's word (with the bit clear), on the same stream.
 __global__ __launch_bounds__(kBlock) void k_sat_heavy_check(const uint32_t *heavy, const uint32_t *seg_begin, const Fr *partial, unsigned long long *bits, unsigned long long *count) {
-    const size_t h = blockIdx.x;
-    Fr acc[3] = {fr_zero(), fr_zero(), fr_zero()};
-    for (uint32_t s = seg_begin[h] + threadIdx.x; s < seg_begin[h + 1]; s += blockDim.x)
-        for (int k = 0; k < 3; k++) acc[k] = fr_add(acc[k], partial[(size_t)s * 3 + k]);
-    block_reduce<3>(acc);
+    Fr acc[3];
+    segment_sums<3>(seg_begin, blockIdx.x, partial, 3, acc);
     if (threadIdx.x != 0 || !row_fails(acc[0], acc[1], acc[2])) return;
-    const size_t r = heavy[h];
+    const size_t r = heavy[blockIdx.x];
     atomicOr(&bits[r >> 6], 1ull << (r & 63));
     atomicAdd(count, 1ull);
 }
 // The report: one workgroup per listed row recomputes the three sums (a row of any length: the workgroup strides over it) and writes them
 // out of Montgomery form, as canonical integers — little-endian words, i.e. the 32 canonical bytes of each.
 template <bool kSmall> __global__ __launch_bounds__(kBlock) void k_sat_report(DCsr3 m, const uint32_t *row_ids, const Fr *x, Fr *out) {
-    const size_t r = row_ids[blockIdx.x];
     Fr acc[3];
-    for (int k = 0; k < 3; k++) {
-        acc[k] = fr_zero();
-        const uint32_t p1 = m.ptr[k][r + 1];
-        for (uint32_t p = m.ptr[k][r] + threadIdx.x; p < p1; p += blockDim.x) acc[k] = fr_add(acc[k], entry_term<kSmall>(m, k, p, x));
-    }
+    row_sums<kSmall, kBlock>(m, x, row_ids[blockIdx.x], threadIdx.x, acc);
     block_reduce<3>(acc);
     if (threadIdx.x == 0) for (int k = 0; k < 3; k++) out[(size_t)blockIdx.x * 3 + k] = fr_to_raw(acc[k]);
 }
@@ -437,17 +441,13 @@ void dev_sat_pass(DevCtx &c, const DeviceCsrSet &m, const Fr *z, unsigned long l
     unsigned long long *count = c.d_counts.p;
     OTTI_HIP(hipMemsetAsync(count, 0, sizeof(unsigned long long), c.stream));
     KScope ks(c, KC_SAT_CHECK);
-    const bool quad = m.quad(), sm = m.use_small;      // the layouts dev_spmv3 picks, for its reasons
-    if (quad && sm) hipLaunchKernelGGL(k_sat_quad<true>, grid_for(4 * m.rows), kBlock, 0, c.stream, m.view(), m.rows, z, bits, count);
-    else if (quad) hipLaunchKernelGGL(k_sat_quad<false>, grid_for(4 * m.rows), kBlock, 0, c.stream, m.view(), m.rows, z, bits, count);
-    else if (sm) hipLaunchKernelGGL(k_sat_light<true>, grid_for(m.rows), kBlock, 0, c.stream, m.view(), m.rows, z, bits, count);
-    else hipLaunchKernelGGL(k_sat_light<false>, grid_for(m.rows), kBlock, 0, c.stream, m.view(), m.rows, z, bits, count);
-    if (m.n_heavy) {
-        if (c.spmv_partial.n < 3 * m.n_seg) { OTTI_HIP(hipStreamSynchronize(c.stream)); c.spmv_partial.alloc(3 * m.n_seg); }
-        if (sm) hipLaunchKernelGGL(k_spmv3_heavy_seg<true>, (unsigned)m.n_seg, kBlock, 0, c.stream, m.view(), (const uint32_t *)m.seg_row.p, (const uint32_t *)m.seg_no.p, z, c.spmv_partial.p);
-        else hipLaunchKernelGGL(k_spmv3_heavy_seg<false>, (unsigned)m.n_seg, kBlock, 0, c.stream, m.view(), (const uint32_t *)m.seg_row.p, (const uint32_t *)m.seg_no.p, z, c.spmv_partial.p);
-        hipLaunchKernelGGL(k_sat_heavy_check, (unsigned)m.n_heavy, kBlock, 0, c.stream, (const uint32_t *)m.heavy.p, (const uint32_t *)m.seg_begin.p, (const Fr *)c.spmv_partial.p, bits, count);
-    }
+    by_layout(m, [&](auto small, auto quad) {            // the layouts dev_spmv3 picks, for its reasons
+        constexpr bool S = decltype(small)::value, Q = decltype(quad)::value;
+        hipLaunchKernelGGL((Q ? k_sat_quad<S> : k_sat_light<S>), grid_for(Q ? 4 * m.rows : m.rows), kBlock, 0, c.stream, m.view(), m.rows, z, bits, count);
+    });
+    if (!m.n_heavy) return;
+    launch_heavy_segments(c, m, z);
+    hipLaunchKernelGGL(k_sat_heavy_check, (unsigned)m.n_heavy, kBlock, 0, c.stream, (const uint32_t *)m.heavy.p, (const uint32_t *)m.seg_begin.p, (const Fr *)c.spmv_partial.p, bits, count);
 }
 uint64_t dev_sat_count(DevCtx &c) {
     unsigned long long *h = reinterpret_cast<unsigned long long *>(&c.h_results[kSatCountSlot]);
@@ -490,8 +490,7 @@ void dev_sat_report(DevCtx &c, DeviceInstance &d, const Fr *z, const unsigned lo
         for (size_t i = 0; i < n; i++) ids[i] = (uint32_t)rep.rows[i0 + i];
         OTTI_HIP(hipMemcpyAsync(c.sat_rows.p, ids, n * sizeof(uint32_t), hipMemcpyHostToDevice, c.stream));
         if (timed) OTTI_HIP(hipEventRecord(c.ev0, c.stream));
-        if (m.use_small) hipLaunchKernelGGL(k_sat_report<true>, (unsigned)n, kBlock, 0, c.stream, m.view(), (const uint32_t *)c.sat_rows.p, z, c.sat_abc.p);
-        else hipLaunchKernelGGL(k_sat_report<false>, (unsigned)n, kBlock, 0, c.stream, m.view(), (const uint32_t *)c.sat_rows.p, z, c.sat_abc.p);
+        by_flag(m.use_small, [&](auto small) { hipLaunchKernelGGL(k_sat_report<decltype(small)::value>, (unsigned)n, kBlock, 0, c.stream, m.view(), (const uint32_t *)c.sat_rows.p, z, c.sat_abc.p); });
         if (timed) OTTI_HIP(hipEventRecord(c.ev1, c.stream));
         OTTI_HIP(hipMemcpyAsync(rep.abc96.data() + 96 * i0, c.sat_abc.p, 96 * n, hipMemcpyDeviceToHost, c.stream));
         OTTI_HIP(hipStreamSynchronize(c.stream));              // `ids` and the device buffers are reused by the next batch
@@ -503,26 +502,23 @@ void dev_sat_report(DevCtx &c, DeviceInstance &d, const Fr *z, const unsigned lo
 // MARK: the by-column lists of the changed columns set their rows' bits in `touched` (zeroed by the launcher).  Column i of the launch is cols[i], or
 // first + i when there is no list.  A short column goes to one lane, or to a quad where the by-column set has the quad layout (the lanes only store:
 // no shuffle, so a wave needs no padding); a column longer than kHeavyRow is left to k_prod_mark_heavy, where a workgroup strides over it.
+// row_sums' bit-setting form: this lane's share of column j's three lists
+template <uint32_t kLanes> __device__ __forceinline__ void mark_rows(const DCsr3 &m, size_t j, uint32_t q, unsigned long long *touched) {
+    for (int k = 0; k < 3; k++)
+        for_entries(m, k, j, q, kLanes, kWholeList, [&](uint32_t p) { const uint32_t r = m.idx[k][p]; atomicOr(&touched[r >> 6], 1ull << (r & 63)); });
+}
 template <bool kQuad> __global__ __launch_bounds__(kBlock) void k_prod_mark(DCsr3 m, const uint64_t *cols, size_t first, size_t n, unsigned long long *touched) {
     constexpr uint32_t kLanes = kQuad ? 4 : 1;
     const uint32_t q = kQuad ? (threadIdx.x & 3) : 0;
     for (size_t i = (blockIdx.x * (size_t)blockDim.x + threadIdx.x) / kLanes; i < n; i += ((size_t)gridDim.x * blockDim.x) / kLanes) {
         const size_t j = cols ? (size_t)cols[i] : first + i;
-        if (row_is_heavy(m, j)) continue;
-        for (int k = 0; k < 3; k++) {
-            const uint32_t p1 = m.ptr[k][j + 1];
-            for (uint32_t p = m.ptr[k][j] + q; p < p1; p += kLanes) { const uint32_t r = m.idx[k][p]; atomicOr(&touched[r >> 6], 1ull << (r & 63)); }
-        }
+        if (!row_is_heavy(m, j)) mark_rows<kLanes>(m, j, q, touched);
     }
 }
 __global__ __launch_bounds__(kBlock) void k_prod_mark_heavy(DCsr3 m, const uint64_t *cols, size_t first, size_t n, unsigned long long *touched) {
     for (size_t i = blockIdx.x; i < n; i += gridDim.x) {
         const size_t j = cols ? (size_t)cols[i] : first + i;
-        if (!row_is_heavy(m, j)) continue;
-        for (int k = 0; k < 3; k++) {
-            const uint32_t p1 = m.ptr[k][j + 1];
-            for (uint32_t p = m.ptr[k][j] + threadIdx.x; p < p1; p += blockDim.x) { const uint32_t r = m.idx[k][p]; atomicOr(&touched[r >> 6], 1ull << (r & 63)); }
-        }
+        if (row_is_heavy(m, j)) mark_rows<kBlock>(m, j, threadIdx.x, touched);
     }
 }
 // COMPACT: a popcount per word, scanned in place (scan_inplace: inclusive), then every word writes its rows behind those of the words before it
@@ -564,11 +560,7 @@ template <bool kSmall, bool kQuad> __global__ __launch_bounds__(kBlock) void k_p
         const size_t r = i < n ? (size_t)rows[i] : 0;
         const bool live = i < n && !row_is_heavy(m, r);
         Fr a[3] = {fr_zero(), fr_zero(), fr_zero()};
-        if (live)
-            for (int k = 0; k < 3; k++) {
-                const uint32_t p1 = m.ptr[k][r + 1];
-                for (uint32_t p = m.ptr[k][r] + q; p < p1; p += kLanes) a[k] = fr_add(a[k], entry_term<kSmall>(m, k, p, x));
-            }
+        if (live) row_sums<kSmall, kLanes>(m, x, r, q, a);
         if (kQuad) for (int k = 0; k < 3; k++) a[k] = quad_sum(a[k]);
         if (live && q == 0) mine += prod_store_row(r, a[0], a[1], a[2], Az, Bz, Cz, bits);
     }
@@ -581,11 +573,7 @@ template <bool kSmall> __global__ __launch_bounds__(kBlock) void k_prod_rows_hea
         const size_t r = rows[i];
         if (!row_is_heavy(m, r)) continue;                          // (the same for every thread of the workgroup)
         Fr acc[3];
-        for (int k = 0; k < 3; k++) {
-            acc[k] = fr_zero();
-            const uint32_t p1 = m.ptr[k][r + 1];
-            for (uint32_t p = m.ptr[k][r] + threadIdx.x; p < p1; p += blockDim.x) acc[k] = fr_add(acc[k], entry_term<kSmall>(m, k, p, x));
-        }
+        row_sums<kSmall, kBlock>(m, x, r, threadIdx.x, acc);
         block_reduce<3>(acc);
         if (threadIdx.x == 0) { const int d = prod_store_row(r, acc[0], acc[1], acc[2], Az, Bz, Cz, bits); if (d) atomicAdd(count, (unsigned long long)(long long)d); }
     }
@@ -630,8 +618,10 @@ ProductsPatch dev_products_patch(DevCtx &c, const DeviceInstance &d, const Fr *z
         KScope ks(c, KC_SPMV);
         OTTI_HIP(hipMemsetAsync(touched, 0, words * sizeof(unsigned long long), c.stream));
         if (n) {
-            if (bc.quad()) hipLaunchKernelGGL(k_prod_mark<true>, grid_for(4 * n), kBlock, 0, c.stream, bc.view(), d_cols, first, n, touched);
-            else hipLaunchKernelGGL(k_prod_mark<false>, grid_for(n), kBlock, 0, c.stream, bc.view(), d_cols, first, n, touched);
+            by_flag(bc.quad(), [&](auto quad) {
+                constexpr bool Q = decltype(quad)::value;
+                hipLaunchKernelGGL(k_prod_mark<Q>, grid_for(Q ? 4 * n : n), kBlock, 0, c.stream, bc.view(), d_cols, first, n, touched);
+            });
             if (bc.n_heavy) hipLaunchKernelGGL(k_prod_mark_heavy, (unsigned)std::min<size_t>(n, kMaxBlocks), kBlock, 0, c.stream, bc.view(), d_cols, first, n, touched);
         }
         hipLaunchKernelGGL(k_prod_popc, grid_for(words), kBlock, 0, c.stream, (const unsigned long long *)touched, words, c.prod_cnt.p);
@@ -647,16 +637,13 @@ ProductsPatch dev_products_patch(DevCtx &c, const DeviceInstance &d, const Fr *z
     else if (out.n_touched) {
         KScope ks(c, KC_SPMV);
         const size_t nt = out.n_touched; const uint32_t *rows = c.prod_rows.p;
-        const bool quad = br.quad(), sm = br.use_small;             // the layouts dev_spmv3 picks, for its reasons
-        if (quad && sm) hipLaunchKernelGGL((k_prod_rows<true, true>), grid_for(4 * nt), kBlock, 0, c.stream, br.view(), rows, nt, z, Az, Bz, Cz, bits, d_unsat);
-        else if (quad) hipLaunchKernelGGL((k_prod_rows<false, true>), grid_for(4 * nt), kBlock, 0, c.stream, br.view(), rows, nt, z, Az, Bz, Cz, bits, d_unsat);
-        else if (sm) hipLaunchKernelGGL((k_prod_rows<true, false>), grid_for(nt), kBlock, 0, c.stream, br.view(), rows, nt, z, Az, Bz, Cz, bits, d_unsat);
-        else hipLaunchKernelGGL((k_prod_rows<false, false>), grid_for(nt), kBlock, 0, c.stream, br.view(), rows, nt, z, Az, Bz, Cz, bits, d_unsat);
-        if (br.n_heavy) {
-            const unsigned g = (unsigned)std::min<size_t>(nt, kMaxBlocks);
-            if (sm) hipLaunchKernelGGL(k_prod_rows_heavy<true>, g, kBlock, 0, c.stream, br.view(), rows, nt, z, Az, Bz, Cz, bits, d_unsat);
-            else hipLaunchKernelGGL(k_prod_rows_heavy<false>, g, kBlock, 0, c.stream, br.view(), rows, nt, z, Az, Bz, Cz, bits, d_unsat);
-        }
+        by_layout(br, [&](auto small, auto quad) {                  // the layouts dev_spmv3 picks, for its reasons
+            constexpr bool S = decltype(small)::value, Q = decltype(quad)::value;
+            hipLaunchKernelGGL((k_prod_rows<S, Q>), grid_for(Q ? 4 * nt : nt), kBlock, 0, c.stream, br.view(), rows, nt, z, Az, Bz, Cz, bits, d_unsat);
+        });
+        if (br.n_heavy) by_flag(br.use_small, [&](auto small) {
+            hipLaunchKernelGGL(k_prod_rows_heavy<decltype(small)::value>, (unsigned)std::min<size_t>(nt, kMaxBlocks), kBlock, 0, c.stream, br.view(), rows, nt, z, Az, Bz, Cz, bits, d_unsat);
+        });
     }
     OTTI_HIP(hipEventRecord(c.ev1, c.stream));
     OTTI_HIP(hipMemcpyAsync((void *)h_unsat, d_unsat, sizeof(unsigned long long), hipMemcpyDeviceToHost, c.stream));
@@ -693,7 +680,7 @@ __global__ __launch_bounds__(kBlock) void k_coef_codes(const Fr *val, size_t n, 
 // rows whose longest list (over the three matrices) exceeds kHeavyRow
 __global__ __launch_bounds__(kBlock) void k_csr_count_heavy(const uint32_t *p0, const uint32_t *p1, const uint32_t *p2, size_t rows, unsigned *count) {
     for (size_t r = blockIdx.x * (size_t)blockDim.x + threadIdx.x; r < rows; r += (size_t)gridDim.x * blockDim.x)
-        if (max(p0[r + 1] - p0[r], max(p1[r + 1] - p1[r], p2[r + 1] - p2[r])) > (uint32_t)kHeavyRow) atomicAdd(count, 1u);
+        if (len_is_heavy(max(p0[r + 1] - p0[r], max(p1[r + 1] - p1[r], p2[r + 1] - p2[r])))) atomicAdd(count, 1u);
 }
 static void upload_coo(DevCtx &c, DeviceCoo &d, const std::vector<uint32_t> &row, const std::vector<uint32_t> &col, const std::vector<Fr> &val) {
     d.n = val.size();
@@ -749,7 +736,7 @@ void build_csr_set(DevCtx &c, DeviceCsrSet &d, const DeviceCoo coo[3], bool by_c
     for (size_t r = 0; r < rows; r++) {
         uint32_t mx = 0;
         for (int k = 0; k < 3; k++) mx = std::max(mx, ptr[k][r + 1] - ptr[k][r]);
-        if (mx > (uint32_t)kHeavyRow) {
+        if (len_is_heavy(mx)) {
             heavy.push_back((uint32_t)r); seg_begin.push_back((uint32_t)seg_row.size());
             for (uint32_t sn = 0; sn * kHeavySeg < mx; sn++) { seg_row.push_back((uint32_t)r); seg_no.push_back(sn); }
         }
