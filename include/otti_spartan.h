@@ -353,6 +353,33 @@ int32_t otti_witness_assign_info(const otti_witness *wit, uint64_t *calls, uint6
 int32_t otti_witness_set_inputs(otti_instance *inst, otti_witness *wit, const uint8_t *inputs32, size_t ninputs);
 int32_t otti_snark_verify(const otti_comp_comm *comm, const uint8_t *inputs32, size_t ninputs, const otti_snark_gens *gens,
                           const uint8_t *tlabel, size_t tlabel_len, const uint8_t *proof, size_t proof_len);
+/* Many SNARK proofs of ONE computation commitment verified in one call: what a verifier that holds one commitment and a pile of proofs makes,
+   instead of one otti_snark_verify per caller thread.
+   Verdict rule: results[i] = what otti_snark_verify returns for (inputs32[i], ninputs[i], proofs[i], proof_lens[i]) with the same commitment,
+   generators and label — 0 accepted, otherwise that call's code (a proof that does not parse: OTTI_ERR_MALFORMED_PROOF; a wrong count of inputs:
+   OTTI_ERR_INVALID_NUM_INPUTS; an input >= l: OTTI_ERR_INVALID_SCALAR; dimensions that differ from the generators': OTTI_ERR_VERIFY_INTERNAL; a
+   point that does not decode: OTTI_ERR_VERIFY_DECOMPRESS; a proof with several defects gets the single verifier's one code).
+   This is NOT a random-linear-combination batch: every proof goes through the single verifier's own steps, no soundness argument changes and no
+   verdict depends on its neighbours.  What the proofs share is their row sums: the evaluation proof's three variable-base sums (over comm_derefs,
+   comm_ops, comm_mem) are reached by all live proofs together, and with a device every sum of at least 256 points goes there in ONE pass per
+   seam — one decode launch, one sum launch (otti_k_row_sum_many is that pass alone) — with comm_ops and comm_mem decoded once per commitment
+   and kept on the handle until otti_comp_comm_free.  Smaller sums, and all of them without a device or under OTTI_VERIFY_HOST, are summed on
+   the host; the verdicts do not depend on the route.  A proof that fails takes no part in the later passes.
+   Threading: the call blocks.  Its workers are the library's own: `threads` of them, the calling thread included (0: the default, 4; more than
+   16: OTTI_ERR_BAD_ARG; never more than there are proofs), run the proofs' steps; a proof waiting for its sum owns no thread, so the number of
+   threads alive depends on `threads` and not on count.  They are joined before the call returns.  threads = 1, or one proof, runs everything on
+   the calling thread.  Several caller threads may call with the same handles at once.
+   Memory: the call runs in chunks of 16 proofs.  Per chunk, host: the parsed proofs (a few hundred KB each at 2^20 constraints) and two eq
+   tables of at most 2^12 scalars per proof; HBM, on the calling thread's context, grow-only and kept across calls: 160 bytes per comm_derefs point
+   of the chunk, 32 per scalar of every sum of a pass and 128 per (window, split) of a sum — about 25 MB at 2^20 with 8192 rows — plus, per commitment
+   and for its lifetime, 96 bytes per point of comm_ops and comm_mem (about 1 MB at 2^20).  Workers that sum the R1CS part's row commitments on the device
+   use their own contexts' buffers, as otti_snark_verify does.
+   Returns OTTI_OK when the call ran, whatever the verdicts; *n_rejected (may be NULL) = the number of non-zero results, which otti_last_error
+   also names.  OTTI_ERR_BAD_ARG, before anything is touched: a null comm, gens or results; with count > 0 a null inputs32, ninputs, proofs or
+   proof_lens array or a null proofs[i] (inputs32[i] may be NULL where ninputs[i] is 0); threads > 16.  count == 0: OTTI_OK, nothing done. */
+int32_t otti_snark_verify_many(const otti_comp_comm *comm, const otti_snark_gens *gens, const uint8_t *tlabel, size_t tlabel_len, size_t count,
+                               const uint8_t *const *inputs32, const size_t *ninputs, const uint8_t *const *proofs, const size_t *proof_lens,
+                               uint32_t threads, int32_t *results, size_t *n_rejected /* may be NULL */);
 void    otti_buf_free(void *p);
 /* copies the calling thread's last error message (NUL-terminated, truncated to cap) */
 size_t  otti_last_error(char *buf, size_t cap);
@@ -589,6 +616,14 @@ int32_t otti_k_witness_diff(const uint8_t *h_old, size_t n, const void *h_src, i
    out = compress(sum_i s[i] * decompress(C[i])), n >= 256 compressed ristretto255 points, scalars in Montgomery form.  Batch decompression,
    LDS-bucket Pippenger, window recombination on the host.  OTTI_ERR_VERIFY_DECOMPRESS if an encoding does not decode. */
 int32_t otti_k_row_sum(const uint8_t *h_compressed32, size_t n, const uint8_t *h_scalars_mont32, uint8_t *h_out32);
+/* Several such sums in ONE pass (what otti_snark_verify_many sends at each of its three seams): one decode launch over all sets with a counter
+   per set, one sum launch over all jobs.  Set k = points [set_offsets[k], set_offsets[k + 1]) of h_compressed32 (nsets + 1 ascending offsets, counted
+   in points); job j sums set job_set[j] with the next n(job_set[j]) scalars of h_scalars_mont32 — several jobs may name one set.  out32[32 j ..] =
+   the compressed sum and codes[j] = 0, or zeros and codes[j] = OTTI_ERR_VERIFY_DECOMPRESS exactly when job j's set has an encoding that does not
+   decode; the other jobs of the call are unaffected.  Sets of 1 .. 2^20 points (no floor of 256 here).  No host fallback.  OTTI_ERR_BAD_ARG: a
+   null argument, nsets or njobs 0, an empty set or one of more than 2^20 points, a job_set[j] >= nsets. */
+int32_t otti_k_row_sum_many(size_t nsets, const uint8_t *h_compressed32, const size_t *set_offsets, size_t njobs, const uint32_t *job_set,
+                            const uint8_t *h_scalars_mont32, uint8_t *h_out32, int32_t *codes);
 
 /* ---- the kernels the prover actually launches for phase one, the evaluation proof and the bullet reduction (host pointers, as above).
         No reference counterpart beyond the upstream functions named; these exist so that a failing proof points at a kernel. ---- */

@@ -132,6 +132,8 @@ _sig("otti_snark_prove", _i32, _vp, _vp, _vp, _sz, _vp, _sz, _vp, ctypes.c_char_
 _sig("otti_snark_prove_resident", _i32, _vp, _vp, _vp, _vp, ctypes.c_char_p, _sz, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_sz), ctypes.POINTER(ctypes.c_double))
 _sig("otti_snark_prove_sharded", _i32, _vp, _vp, _vp, _vp, ctypes.c_char_p, _sz, _vp, ctypes.POINTER(_vp), ctypes.POINTER(_sz), ctypes.POINTER(ctypes.c_double))
 _sig("otti_snark_verify", _i32, _vp, _vp, _sz, _vp, ctypes.c_char_p, _sz, _vp, _sz)
+_sig("otti_snark_verify_many", _i32, _vp, _vp, ctypes.c_char_p, _sz, _sz, ctypes.POINTER(_vp), ctypes.POINTER(_sz), ctypes.POINTER(_vp), ctypes.POINTER(_sz),
+     ctypes.c_uint32, ctypes.POINTER(_i32), ctypes.POINTER(_sz))
 _sig("otti_zkif_load", _i32, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(ctypes.POINTER(_R1CS)))
 _sig("otti_zkif_write", _i32, ctypes.POINTER(_R1CS), ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p)
 _sig("otti_r1cs_free", None, ctypes.POINTER(_R1CS))
@@ -182,6 +184,7 @@ _sig("otti_k_sc_plan", _i32, _i32, _sz, _i32, ctypes.POINTER(ctypes.c_uint32), c
 _sig("otti_k_msm_rows", _i32, _vp, _vp, _sz, _sz, _vp, _vp, _fp)
 _sig("otti_k_msm_job", _i32, _vp, _sz, _sz, _vp, _sz, _vp, _vp, _i32, _i32, _i32, _sz, _vp, _vp, _fp)
 _sig("otti_k_row_sum", _i32, _vp, _sz, _vp, _vp)
+_sig("otti_k_row_sum_many", _i32, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp)
 _sig("otti_k_msm_scatter_rows", _i32, _vp, _sz, _vp, _vp, _sz, _vp, _fp)
 _sig("otti_k_witness_diff", _i32, _vp, _sz, _vp, _i32, _sz, _vp, _vp, _vp, ctypes.POINTER(_u64), ctypes.POINTER(ctypes.c_uint32), _fp)
 _sig("otti_k_eq_pyramid", _i32, _vp, _sz, _vp)
@@ -959,6 +962,31 @@ class SNARK:
         buf = np.frombuffer(self.bytes, dtype=np.uint8)
         _check(lib.otti_snark_verify(comm._h, _ptr(i), i.shape[0], gens._h, label, len(label), _ptr(buf), buf.size))
 
+    @staticmethod
+    def verify_many(comm, proofs, inputs, gens, transcript_label=b"snark_example", threads=0):
+        """Many proofs of ONE computation commitment in one call (otti_snark_verify_many): ``proofs`` are SNARK objects or bytes, ``inputs`` one
+        InputsAssignment for all of them or one per proof.  Returns the list of result codes — element i is what ``verify`` on proof i alone would
+        report, 0 = accepted — so a rejected proof raises nothing; only the call's own refusals (bad arguments) raise.  Not a randomised batch: no
+        verdict depends on another proof.  ``threads``: the library's worker threads, 0 = its default, at most 16; the call blocks until all are done."""
+        label = bytes(transcript_label)
+        blobs = [np.frombuffer(bytes(p.bytes if isinstance(p, SNARK) else p), dtype=np.uint8) for p in proofs]
+        n = len(blobs)
+        per = list(inputs) if isinstance(inputs, (list, tuple)) else [inputs] * n
+        if len(per) != n:
+            raise ValueError("verify_many: one InputsAssignment for all proofs, or one per proof")
+        ins = [_scalars(i.assignment, "inputs") for i in per]
+        in_ptrs, in_counts = (_vp * max(1, n))(), (_sz * max(1, n))()
+        pf_ptrs, pf_lens = (_vp * max(1, n))(), (_sz * max(1, n))()
+        empty = np.zeros(1, dtype=np.uint8)
+        for k in range(n):
+            in_ptrs[k], in_counts[k] = _ptr(ins[k]), ins[k].shape[0]
+            pf_ptrs[k], pf_lens[k] = (blobs[k] if blobs[k].size else empty).ctypes.data_as(_vp), blobs[k].size   # an empty proof is a malformed one, not a null pointer
+        results, rejected = (_i32 * max(1, n))(), _sz(0)
+        _check(lib.otti_snark_verify_many(comm._h, gens._h, label, len(label), n, in_ptrs, in_counts, pf_ptrs, pf_lens, threads, results, ctypes.byref(rejected)))
+        out = [int(results[k]) for k in range(n)]
+        assert rejected.value == sum(1 for r in out if r != 0)
+        return out
+
 
 def shard_init(segment_name, rank, world):
     """Join the node-local exchange of a sharded proof (collective; ``segment_name`` must be fresh and the same on every rank)."""
@@ -1376,6 +1404,23 @@ class kernels:
         out = np.zeros(32, dtype=np.uint8)
         _check(lib.otti_k_row_sum(_ptr(C), C.shape[0], _ptr(s), _ptr(out)))
         return out
+
+    @staticmethod
+    def row_sum_many(sets, jobs):
+        """several such sums in one pass: ``sets`` = arrays of compressed points, ``jobs`` = [(set index, Montgomery scalars)]; returns
+        (sums (njobs, 32) uint8, codes [int]) — a job whose set has an undecodable point carries OTTI_ERR_VERIFY_DECOMPRESS and zeros"""
+        cs = [np.ascontiguousarray(c, dtype=np.uint8).reshape(-1, 32) for c in sets]
+        off = np.zeros(len(cs) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([c.shape[0] for c in cs])
+        comp = np.ascontiguousarray(np.concatenate(cs) if cs else np.zeros((1, 32), dtype=np.uint8))
+        js = np.ascontiguousarray([k for k, _ in jobs], dtype=np.uint32)
+        ss = [_scalars(s, "s") for _, s in jobs]
+        for (k, _), s in zip(jobs, ss):
+            assert not 0 <= k < len(cs) or s.shape[0] == cs[k].shape[0]
+        sc = np.ascontiguousarray(np.concatenate(ss) if ss else np.zeros((1, 32), dtype=np.uint8))
+        out = np.zeros((max(1, len(jobs)), 32), dtype=np.uint8); codes = (_i32 * max(1, len(jobs)))()
+        _check(lib.otti_k_row_sum_many(len(cs), _ptr(comp), _ptr(off), len(jobs), _ptr(js), _ptr(sc), _ptr(out), codes))
+        return out[:len(jobs)], [int(codes[j]) for j in range(len(jobs))]
 
     @staticmethod
     def msm_scatter_rows(gens, L, idx, s):

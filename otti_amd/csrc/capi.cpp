@@ -532,6 +532,31 @@ int32_t otti_snark_verify(const otti_comp_comm *comm, const uint8_t *inputs32, s
         return rc;
     });
 }
+// Many SNARK proofs of ONE computation commitment in one call (snark.h snark_verify_many; the contract: include/otti_spartan.h).
+// Bounds per chunk of kSnarkVerifyManyChunk = 16 proofs.  Host: the parsed proofs and, per proof, the eq tables of the evaluation proof whose
+// row sum is out (at most 2 x 2^12 scalars).  HBM, on the calling thread's context, grow-only and kept across calls: 160 bytes per comm_derefs
+// point of the chunk, 32 per scalar of every sum of a pass, 128 per (window, split) of a job — 25 MB at 2^20 constraints with 8192 rows — and, once
+// per commitment and for its lifetime, 96 bytes per point of comm_ops and comm_mem (1 MB at 2^20).  Threads: `threads` - 1 beside the caller.
+int32_t otti_snark_verify_many(const otti_comp_comm *comm, const otti_snark_gens *gens, const uint8_t *tlabel, size_t tlabel_len, size_t count,
+                               const uint8_t *const *inputs32, const size_t *ninputs, const uint8_t *const *proofs, const size_t *proof_lens,
+                               uint32_t threads, int32_t *results, size_t *n_rejected) {
+    return guarded([&] {
+        if (!comm || !gens || !results) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (threads > kVerifyManyMaxThreads) throw Error(OTTI_ERR_BAD_ARG, "more than 16 worker threads");
+        if (count && (!inputs32 || !ninputs || !proofs || !proof_lens)) throw Error(OTTI_ERR_BAD_ARG, "a null array with count > 0");
+        for (size_t i = 0; i < count; i++) if (!proofs[i] || (ninputs[i] && !inputs32[i])) throw Error(OTTI_ERR_BAD_ARG, "a null proof, or null inputs with a non-zero count");
+        if (n_rejected) *n_rejected = 0;
+        if (!count) return OTTI_OK;
+        std::vector<VerifyItem> items(count);
+        for (size_t i = 0; i < count; i++) items[i] = {inputs32[i], ninputs[i], proofs[i], proof_lens[i]};
+        snark_verify_many(*comm->c, *gens->g, tlabel, tlabel_len, items.data(), count, threads, results);
+        size_t bad = 0;
+        for (size_t i = 0; i < count; i++) bad += results[i] != OTTI_OK;
+        if (n_rejected) *n_rejected = bad;
+        if (bad) g_last_error = std::to_string(bad) + " of " + std::to_string(count) + " proofs rejected";
+        return OTTI_OK;
+    });
+}
 
 // ------------------------------------------------------------------------------------------------ zkInterface / synthetic
 int32_t otti_zkif_load(const char *c, const char *i, const char *w, otti_r1cs **out) {

@@ -406,6 +406,29 @@ int32_t otti_k_row_sum(const uint8_t *compressed32, size_t n, const uint8_t *sca
         pt_encode(out32, sum); return OTTI_OK;
     });
 }
+// Several such sums in one pass (device.h dev_row_sums_many: k_decode_niels_sets, k_msm_var_many).  Set k: points [set_offsets[k], set_offsets[k + 1])
+// of compressed32 (nsets + 1 ascending offsets, in points); job j sums set job_set[j] with the next (that set's n) scalars of scalars_mont32.  No host
+// fallback.  The arguments are judged before a device is touched.
+int32_t otti_k_row_sum_many(size_t nsets, const uint8_t *compressed32, const size_t *set_offsets, size_t njobs, const uint32_t *job_set,
+                            const uint8_t *scalars_mont32, uint8_t *out32, int32_t *codes) {
+    return guarded([&] {
+        if (!compressed32 || !set_offsets || !job_set || !scalars_mont32 || !out32 || !codes || !nsets || !njobs) throw Error(OTTI_ERR_BAD_ARG, "null argument, no sets or no jobs");
+        std::vector<RowSumSetIn> sets(nsets); std::vector<RowSumJobIn> jobs(njobs);
+        for (size_t k = 0; k < nsets; k++) {
+            if (set_offsets[k + 1] <= set_offsets[k] || set_offsets[k + 1] - set_offsets[k] > kRowSumMaxPoints) throw Error(OTTI_ERR_BAD_ARG, "an empty set, or one of more than 2^20 points");
+            sets[k].comp32 = compressed32 + 32 * set_offsets[k]; sets[k].n = set_offsets[k + 1] - set_offsets[k];
+        }
+        size_t total = 0;
+        for (size_t j = 0; j < njobs; j++) { if (job_set[j] >= nsets) throw Error(OTTI_ERR_BAD_ARG, "a job names a set that is not there"); total += sets[job_set[j]].n; }
+        std::vector<Fr> s(total); memcpy(s.data(), scalars_mont32, 32 * total);
+        total = 0;
+        for (size_t j = 0; j < njobs; j++) { jobs[j].set = job_set[j]; jobs[j].scalars = s.data() + total; total += sets[job_set[j]].n; }
+        std::vector<RowSumOut> res(njobs);
+        dev_row_sums_many(DevCtx::get(), sets.data(), nsets, jobs.data(), njobs, res.data());
+        for (size_t j = 0; j < njobs; j++) { codes[j] = res[j].code; if (res[j].code) memset(out32 + 32 * j, 0, 32); else pt_encode(out32 + 32 * j, res[j].sum); }
+        return OTTI_OK;
+    });
+}
 int32_t otti_k_msm_rows(otti_gens *gens, const uint8_t *Z, size_t L, size_t R, const uint8_t *blinds, uint8_t *out32, float *ms) {
     return guarded([&] {
         DevCtx &c = DevCtx::get(); Gens &g = *gens->g;

@@ -156,6 +156,7 @@ struct DevCtx {
     void reset_arrival_counters();                            // after an aborted or timed-out launch: a grid may have left them non-zero (stream must be idle)
     hipEvent_t ev_order = nullptr;                            // orders a caller's stream (otti_kd_*) against this context's own
     std::vector<struct RowSumSlot *> row_slots;               // the verifier's variable-base sums in flight on this context (prover.cpp), buffers kept across proofs
+    struct RowSumManyScratch *row_many = nullptr;             // dev_row_sums_many's working memory (k_msm.hip), grow-only, kept across calls
     TailMailbox tail_mail;
     // ---- host waits on device mail (waits.cpp).  The one guarded spin: polls arrived() until it holds; while it does not, fails the way lim says
     // (an armed launch that gave up; a time limit counted from t0, with release-or-drain) and ends in fail(), which throws
@@ -515,6 +516,22 @@ MsmTicket dev_bullet_round(DevCtx &c, const DeviceGens &g, const BulletRound &ro
 // combines (253 doublings: a sequential chain a host core runs 30 x faster than a GPU lane).  Returns the window width c it used.
 void dev_decode_niels(DevCtx &c, const uint8_t *compressed_dev, size_t n, Niels *out, unsigned *bad);
 int dev_msm_var(DevCtx &c, const Niels *pts, const Fr *scalars, size_t n, Pt *out, size_t out_cap, int *n_windows, int *n_splits);
+// ---- several such sums in one pass (k_msm.hip k_decode_niels_sets, k_msm_var_many): what the staged SNARK verifier (snark_verify_many.cpp) sends
+// for all its live proofs at one of its three seams.  A set is n compressed points in HOST memory, decoded in the pass with a counter of its own,
+// or — `decoded` given — n points already in HBM in the form the sums read (a commitment's, decoded once: dev_decode_set), with what that decode
+// found.  A job is a set and n scalars (host, Montgomery); several jobs may name one set, and sets of different n share the launch: every job
+// takes the c, W and splits dev_msm_var takes for its n.  Queues one upload each of points, scalars and tables, one decode launch (counted under
+// `decode`), one sum launch (`msm_var`) and the copies back on c.stream, waits, and recombines each job's windows on the host as the single
+// row sum does: out[j] = {0, the sum} or {OTTI_ERR_VERIFY_DECOMPRESS} exactly when job j's set has a point that does not decode — its neighbours
+// are untouched.  OTTI_ERR_BAD_ARG (nothing queued): no sets or jobs, a set of fewer than 1 or more than kRowSumMaxPoints points, a job naming no set.
+// HBM: grow-only per context, 160 bytes per point to decode, 32 per scalar, 128 per (window, split) — at most 51 * ceil(n / 2048) per job.
+constexpr size_t kRowSumMaxPoints = (size_t)1 << 20;
+struct RowSumSetIn { const uint8_t *comp32 = nullptr; size_t n = 0; const Niels *decoded = nullptr; bool decoded_bad = false; };
+struct RowSumJobIn { size_t set = 0; const Fr *scalars = nullptr; };
+struct RowSumOut { int code = 0; Pt sum; };
+void dev_row_sums_many(DevCtx &c, const RowSumSetIn *sets, size_t nsets, const RowSumJobIn *jobs, size_t njobs, RowSumOut *out);
+struct DecodedSet { DevBuf<Niels> pts; size_t n = 0; bool bad = false; };      // bad: some encoding did not decode (the identity stands in its place)
+void dev_decode_set(DevCtx &c, const uint8_t *comp32, size_t n, DecodedSet &out);   // host bytes -> HBM; synchronises
 double dev_madd_peak(DevCtx &c);                                          // mixed point additions per second, whole chip (the MSM's ALU roof)
 // v[i] (times *factor when given: a device-resident scalar is not needed, it travels by value) as 8 u32 limbs widened to u64 lanes, on `st`
 void dev_fr_to_lanes(hipStream_t st, const Fr *d_src, const Fr *factor, unsigned long long *d_lanes, size_t n);

@@ -665,12 +665,14 @@ std::shared_ptr<DeviceGens> build_device_gens(const Gens &g, int c) {
 // window recombination (a dependent chain: ~25 us on a host core against ~300 us on a GPU lane).
 constexpr int kVarChunk = 2048, kVarMaxBuckets = kBlock;        // one bucket per thread at most: c <= 9
 struct VarMsmArgs { const Niels *pts; const Fr *sc; uint32_t n, chunk; int c, W, splits; uint32_t K[9]; Pt *out; };
-__global__ __launch_bounds__(kBlock) void k_msm_var(VarMsmArgs A) {
+// One workgroup's share, (window w, split `split`) of the sum A describes: the body of k_msm_var and of k_msm_var_many below.  The whole
+// workgroup enters it or none of it does (barriers).
+__device__ __forceinline__ void msm_var_block(const VarMsmArgs &A, const int w, const uint32_t split) {
     __shared__ uint16_t s_key[kVarChunk], s_list[kVarChunk];        // per point: (|digit| - 1) | sign << 15, 0xffff for a zero digit; point indices sorted by bucket
     __shared__ uint32_t s_start[kVarMaxBuckets + 1], s_fill[kVarMaxBuckets];
     __shared__ P10 s_bkt[kVarMaxBuckets];
-    const int w = blockIdx.x, tid = threadIdx.x;
-    const uint32_t i0 = blockIdx.y * A.chunk, n_here = min(A.chunk, A.n - i0), nb = 1u << (A.c - 1);
+    const int tid = threadIdx.x;
+    const uint32_t i0 = split * A.chunk, n_here = min(A.chunk, A.n - i0), nb = 1u << (A.c - 1);
     for (uint32_t b = tid; b <= nb; b += kBlock) { s_start[b] = 0; if (b < nb) s_fill[b] = 0; }
     __syncthreads();
     // The TOP window holds only the 253 - c (W - 1) leading bits of a scalar (often a single one) plus the recoding carry: few digit
@@ -731,39 +733,159 @@ __global__ __launch_bounds__(kBlock) void k_msm_var(VarMsmArgs A) {
         if ((uint32_t)tid < sft) s_bkt[(uint32_t)tid * m] = p10_add(s_bkt[(uint32_t)tid * m], s_bkt[((uint32_t)tid + sft) * m], d2);
         __syncthreads();
     }
-    if (tid == 0) A.out[(size_t)w * A.splits + blockIdx.y] = p10_pack(s_bkt[0]);
+    if (tid == 0) A.out[(size_t)w * A.splits + split] = p10_pack(s_bkt[0]);
+}
+__global__ __launch_bounds__(kBlock) void k_msm_var(VarMsmArgs A) { msm_var_block(A, (int)blockIdx.x, blockIdx.y); }
+// Several sums in one launch.  jobs: a table in device memory, one VarMsmArgs per sum, each with the c, W, splits and chunk var_msm_shape takes
+// for its own n (a launch with one job writes what k_msm_var writes); several jobs may read the same points with different scalars.  The grid
+// is (max W) x (all jobs' splits): first[j] = the first blockIdx.y of job j (njobs + 1 entries, ascending), searched by every workgroup;
+// a workgroup beyond its job's windows leaves before it touches LDS.
+__global__ __launch_bounds__(kBlock) void k_msm_var_many(const VarMsmArgs *jobs, const uint32_t *first, uint32_t njobs) {
+    uint32_t lo = 0, hi = njobs;                                       // the last j with first[j] <= blockIdx.y
+    while (hi - lo > 1) { const uint32_t mid = (lo + hi) / 2; if (first[mid] <= blockIdx.y) lo = mid; else hi = mid; }
+    if ((int)blockIdx.x >= jobs[lo].W) return;
+    const VarMsmArgs A = jobs[lo];
+    msm_var_block(A, (int)blockIdx.x, blockIdx.y - first[lo]);
+}
+// the shape of one sum over n points: splits of at most kVarChunk points, ~8 points per bucket (2^(c-1) buckets for `chunk` points)
+static void var_msm_shape(VarMsmArgs &A, size_t n) {
+    const size_t splits = (n + kVarChunk - 1) / kVarChunk, chunk = (n + splits - 1) / splits;
+    int lg = 0; while (((size_t)1 << lg) < chunk) lg++;
+    A.c = std::max(5, std::min(9, lg - 2));
+    A.W = 253 / A.c + 1; A.splits = (int)splits; A.n = (uint32_t)n; A.chunk = (uint32_t)chunk;
+    msm_recoding_constant(A.K, A.c, A.W);
 }
 int dev_msm_var(DevCtx &c, const Niels *pts, const Fr *scalars, size_t n, Pt *out, size_t out_cap, int *n_windows, int *n_splits) {
     if (!n || n > ((size_t)1 << 24)) throw Error(OTTI_ERR_INTERNAL, "msm_var: bad size");
     VarMsmArgs A;
-    const size_t splits = (n + kVarChunk - 1) / kVarChunk, chunk = (n + splits - 1) / splits;
-    int lg = 0; while (((size_t)1 << lg) < chunk) lg++;
-    A.c = std::max(5, std::min(9, lg - 2));                    // ~8 points per bucket: 2^(c-1) buckets for `chunk` points
-    A.W = 253 / A.c + 1; A.splits = (int)splits; A.pts = pts; A.sc = scalars; A.n = (uint32_t)n; A.chunk = (uint32_t)chunk; A.out = out;
-    if ((size_t)A.W * splits > out_cap) throw Error(OTTI_ERR_INTERNAL, "msm_var: result buffer too small");
-    msm_recoding_constant(A.K, A.c, A.W);
+    var_msm_shape(A, n);
+    A.pts = pts; A.sc = scalars; A.out = out;
+    if ((size_t)A.W * A.splits > out_cap) throw Error(OTTI_ERR_INTERNAL, "msm_var: result buffer too small");
     KScope ks(c, KC_MSM_VAR);
-    hipLaunchKernelGGL(k_msm_var, dim3((unsigned)A.W, (unsigned)splits), kBlock, 0, c.stream, A);
+    hipLaunchKernelGGL(k_msm_var, dim3((unsigned)A.W, (unsigned)A.splits), kBlock, 0, c.stream, A);
     if (n_windows) *n_windows = A.W;
-    if (n_splits) *n_splits = (int)splits;
+    if (n_splits) *n_splits = A.splits;
     return A.c;
 }
 // RFC 9496 4.3.1 Decode, one lane per point, straight into the affine Niels form the mixed addition reads (Z = 1 after Decode)
-__global__ __launch_bounds__(64) void k_decode_niels(const uint8_t *in, size_t n, Niels *out, unsigned *bad) {
-    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (i >= n) return;
+__device__ __forceinline__ bool decode_niels_one(const uint8_t *in, size_t i, Niels *out) {      // false: the encoding does not decode (the identity is stored)
     uint8_t b[32];
     const uint32_t *src = reinterpret_cast<const uint32_t *>(in + 32 * i);
     for (int k = 0; k < 8; k++) { const uint32_t x = src[k]; b[4 * k] = (uint8_t)x; b[4 * k + 1] = (uint8_t)(x >> 8); b[4 * k + 2] = (uint8_t)(x >> 16); b[4 * k + 3] = (uint8_t)(x >> 24); }
     Pt p;
-    if (!pt_decode(p, b)) { atomicAdd(bad, 1u); out[i] = niels_identity(); return; }
+    if (!pt_decode(p, b)) { out[i] = niels_identity(); return false; }
     Niels nl; nl.yplusx = fp_add(p.Y, p.X); nl.yminusx = fp_sub(p.Y, p.X); nl.xy2d = fp_mul(p.T, fp_2D());
     out[i] = nl;
+    return true;
+}
+__global__ __launch_bounds__(64) void k_decode_niels(const uint8_t *in, size_t n, Niels *out, unsigned *bad) {
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (!decode_niels_one(in, i, out)) atomicAdd(bad, 1u);
+}
+// the same over several sets that lie one behind the other (set k: points [off[k], off[k + 1]), nsets + 1 offsets, ascending), a counter per set
+__global__ __launch_bounds__(64) void k_decode_niels_sets(const uint8_t *in, const uint32_t *off, uint32_t nsets, Niels *out, unsigned *bad) {
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= off[nsets]) return;
+    if (decode_niels_one(in, i, out)) return;
+    uint32_t lo = 0, hi = nsets;                                       // the last k with off[k] <= i
+    while (hi - lo > 1) { const uint32_t mid = (lo + hi) / 2; if (off[mid] <= i) lo = mid; else hi = mid; }
+    atomicAdd(&bad[lo], 1u);
 }
 void dev_decode_niels(DevCtx &c, const uint8_t *compressed_dev, size_t n, Niels *out, unsigned *bad) {
     if (!n) return;
     KScope ks(c, KC_DECODE);
     hipLaunchKernelGGL(k_decode_niels, (unsigned)((n + 63) / 64), 64, 0, c.stream, compressed_dev, n, out, bad);
+}
+void dev_decode_set(DevCtx &c, const uint8_t *comp32, size_t n, DecodedSet &out) {
+    if (!n || n > kRowSumMaxPoints) throw Error(OTTI_ERR_BAD_ARG, "decode: a set of no points or of more than 2^20");
+    DevBuf<uint8_t> comp(32 * n); DevBuf<unsigned> bad(1);
+    out.pts.alloc(n); out.n = n;
+    OTTI_HIP(hipMemcpyAsync(comp.p, comp32, 32 * n, hipMemcpyHostToDevice, c.stream));
+    OTTI_HIP(hipMemsetAsync(bad.p, 0, sizeof(unsigned), c.stream));
+    dev_decode_niels(c, comp.p, n, out.pts.p, bad.p);
+    unsigned h_bad = 0;
+    OTTI_HIP(hipMemcpyAsync(&h_bad, bad.p, sizeof h_bad, hipMemcpyDeviceToHost, c.stream));
+    OTTI_HIP(hipStreamSynchronize(c.stream));
+    out.bad = h_bad != 0;
+}
+// Grow-only working memory of dev_row_sums_many, per context, kept across calls as the row-sum slots are.
+struct RowSumManyScratch { DevBuf<uint8_t> comp; DevBuf<Niels> pts; DevBuf<Fr> sc; DevBuf<Pt> out; DevBuf<unsigned> bad; DevBuf<uint32_t> tab; DevBuf<VarMsmArgs> jobs; };
+template <class T> static void grow(DevBuf<T> &b, size_t n) { if (b.n < n) b.alloc(n + n / 4); }
+void dev_row_sums_many(DevCtx &c, const RowSumSetIn *sets, size_t nsets, const RowSumJobIn *jobs, size_t njobs, RowSumOut *out) {
+    if (!sets || !jobs || !out || !nsets || !njobs) throw Error(OTTI_ERR_BAD_ARG, "row sums: no sets or no jobs");
+    // ---- the sets that still have to be decoded lie one behind the other in one buffer; off[k]: the first point of the k-th of them
+    std::vector<uint32_t> tab, set_slot(nsets, 0);                     // tab = off[0 .. n_comp] || first[0 .. njobs]
+    size_t total_pts = 0;
+    for (size_t k = 0; k < nsets; k++) {
+        const RowSumSetIn &S = sets[k];
+        if (S.n < 1 || S.n > kRowSumMaxPoints || (!S.decoded && !S.comp32)) throw Error(OTTI_ERR_BAD_ARG, "row sums: an empty set, or one of more than 2^20 points");
+        if (S.decoded) continue;
+        set_slot[k] = (uint32_t)tab.size(); tab.push_back((uint32_t)total_pts); total_pts += S.n;
+    }
+    const size_t n_comp = tab.size();
+    tab.push_back((uint32_t)total_pts);
+    if (total_pts >> 31) throw Error(OTTI_ERR_INTERNAL, "row sums: too many points in one pass");
+    size_t total_sc = 0;
+    for (size_t j = 0; j < njobs; j++) {
+        if (jobs[j].set >= nsets || !jobs[j].scalars) throw Error(OTTI_ERR_BAD_ARG, "row sums: a job names no set, or has no scalars");
+        total_sc += sets[jobs[j].set].n;
+    }
+    if (!c.row_many) c.row_many = new RowSumManyScratch();
+    RowSumManyScratch &S = *c.row_many;
+    grow(S.comp, 32 * total_pts); grow(S.pts, total_pts); grow(S.sc, total_sc); grow(S.bad, n_comp); grow(S.jobs, njobs);
+    // ---- the job table: every job's shape is the one dev_msm_var takes for its n; results one behind the other, (window, split) within a job
+    std::vector<VarMsmArgs> tbl(njobs);
+    std::vector<size_t> out_off(njobs);
+    size_t sc_off = 0, total_out = 0, total_y = 0; int max_W = 0;
+    for (size_t j = 0; j < njobs; j++) {
+        const RowSumSetIn &set = sets[jobs[j].set]; VarMsmArgs &A = tbl[j];
+        var_msm_shape(A, set.n);
+        A.pts = set.decoded ? set.decoded : S.pts.p + tab[set_slot[jobs[j].set]];
+        A.sc = S.sc.p + sc_off; sc_off += set.n;
+        out_off[j] = total_out; total_out += (size_t)A.W * A.splits;
+        tab.push_back((uint32_t)total_y); total_y += (size_t)A.splits;
+        max_W = std::max(max_W, A.W);
+    }
+    tab.push_back((uint32_t)total_y);
+    if (total_y > 65535) throw Error(OTTI_ERR_INTERNAL, "row sums: too many splits in one pass");
+    grow(S.out, total_out); grow(S.tab, tab.size());
+    for (size_t j = 0; j < njobs; j++) tbl[j].out = S.out.p + out_off[j];
+    // ---- queue: compressed points, decode, scalars and tables, the sums, the copies back
+    std::vector<uint8_t> comp(32 * total_pts); std::vector<Fr> sc(total_sc);
+    for (size_t k = 0; k < nsets; k++) if (!sets[k].decoded) memcpy(comp.data() + 32 * (size_t)tab[set_slot[k]], sets[k].comp32, 32 * sets[k].n);
+    sc_off = 0;
+    for (size_t j = 0; j < njobs; j++) { const size_t n = sets[jobs[j].set].n; memcpy(sc.data() + sc_off, jobs[j].scalars, n * sizeof(Fr)); sc_off += n; }
+    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{c.stream};   // the copies read this frame's vectors: nothing queued outlives it, also on a throw
+    OTTI_HIP(hipMemcpyAsync(S.tab.p, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c.stream));
+    if (total_pts) {
+        OTTI_HIP(hipMemcpyAsync(S.comp.p, comp.data(), comp.size(), hipMemcpyHostToDevice, c.stream));
+        OTTI_HIP(hipMemsetAsync(S.bad.p, 0, n_comp * sizeof(unsigned), c.stream));
+        KScope ks(c, KC_DECODE);
+        hipLaunchKernelGGL(k_decode_niels_sets, (unsigned)((total_pts + 63) / 64), 64, 0, c.stream, (const uint8_t *)S.comp.p, (const uint32_t *)S.tab.p, (uint32_t)n_comp, S.pts.p, S.bad.p);
+    }
+    OTTI_HIP(hipMemcpyAsync(S.sc.p, sc.data(), total_sc * sizeof(Fr), hipMemcpyHostToDevice, c.stream));
+    OTTI_HIP(hipMemcpyAsync(S.jobs.p, tbl.data(), njobs * sizeof(VarMsmArgs), hipMemcpyHostToDevice, c.stream));
+    {
+        KScope ks(c, KC_MSM_VAR);
+        hipLaunchKernelGGL(k_msm_var_many, dim3((unsigned)max_W, (unsigned)total_y), kBlock, 0, c.stream, (const VarMsmArgs *)S.jobs.p, (const uint32_t *)(S.tab.p + n_comp + 1), (uint32_t)njobs);
+    }
+    std::vector<Pt> part(total_out); std::vector<unsigned> bad(std::max<size_t>(1, n_comp), 0);
+    OTTI_HIP(hipMemcpyAsync(part.data(), S.out.p, total_out * sizeof(Pt), hipMemcpyDeviceToHost, c.stream));
+    if (n_comp) OTTI_HIP(hipMemcpyAsync(bad.data(), S.bad.p, n_comp * sizeof(unsigned), hipMemcpyDeviceToHost, c.stream));
+    OTTI_HIP(hipStreamSynchronize(c.stream));
+    // ---- per job: sum_w 2^(c w) * (sum over splits), Horner from the top window, c doublings per step
+    for (size_t j = 0; j < njobs; j++) {
+        const RowSumSetIn &set = sets[jobs[j].set]; const VarMsmArgs &A = tbl[j];
+        if (set.decoded ? set.decoded_bad : bad[set_slot[jobs[j].set]] != 0) { out[j].code = OTTI_ERR_VERIFY_DECOMPRESS; out[j].sum = pt_identity(); continue; }
+        const Pt *p = part.data() + out_off[j];
+        Pt acc = pt_identity();
+        for (int w = A.W - 1; w >= 0; w--) {
+            if (w != A.W - 1) for (int k = 0; k < A.c; k++) acc = pt_dbl(acc);
+            for (int sp = 0; sp < A.splits; sp++) acc = pt_add(acc, p[(size_t)w * A.splits + sp]);
+        }
+        out[j].code = 0; out[j].sum = acc;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ the ALU roof of the MSM, measured

@@ -9,6 +9,7 @@
 #include "device.h"
 #include "pool.h"
 #include "shard.h"
+#include "snark.h"
 #include <chrono>
 #include <cstring>
 #include <mutex>
@@ -133,7 +134,48 @@ static int row_sum_finish_on_device(RowSumJob *job, const Fr *s, Pt &out) {
         return 0;
     } catch (const Error &) { (void)hipStreamSynchronize(c.stream); return -1; }     // the caller falls back to the host cores
 }
+// snark_verify_many's seam (snark.h g_row_sums_many_hook): the sums all live proofs name at one of their three steps, in one dev_row_sums_many
+// pass on the calling thread's context.  Requests over the commitment's own points share ONE set, decoded once per commitment and kept on it.
+struct RowSumsCache { DecodedSet ops, mem; };
+static std::shared_ptr<RowSumsCache> row_sums_cache(DevCtx &c, const CompComm &comm) {
+    std::lock_guard<std::mutex> lk(comm.row_cache_mu);
+    if (!comm.row_cache) {
+        auto rc = std::make_shared<RowSumsCache>();
+        if (comm.comm_ops.size() >= kRowSumDeviceMin) dev_decode_set(c, comm.comm_ops[0].b, comm.comm_ops.size(), rc->ops);
+        if (comm.comm_mem.size() >= kRowSumDeviceMin) dev_decode_set(c, comm.comm_mem[0].b, comm.comm_mem.size(), rc->mem);
+        comm.row_cache = rc;
+    }
+    return comm.row_cache;
+}
+static bool row_sums_many_on_device(const CompComm &comm, const RowRequest *req, size_t n, RowAnswer *ans) {
+    try {
+        DevCtx &c = DevCtx::get();
+        for (size_t i = 0; i < n; i++) if (req[i].n < 1 || req[i].n > kRowSumMaxPoints) return false;
+        std::vector<RowSumSetIn> sets; std::vector<RowSumJobIn> jobs(n);
+        std::shared_ptr<RowSumsCache> cache;                         // held for the pass: the commitment may go while another caller's pass reads it
+        long ops_set = -1, mem_set = -1;
+        for (size_t i = 0; i < n; i++) {
+            const bool is_ops = req[i].C == comm.comm_ops.data() && req[i].n == comm.comm_ops.size(), is_mem = req[i].C == comm.comm_mem.data() && req[i].n == comm.comm_mem.size();
+            long &shared = is_ops ? ops_set : mem_set;
+            if ((is_ops || is_mem) && shared < 0) {
+                if (!cache) cache = row_sums_cache(c, comm);
+                const DecodedSet &d = is_ops ? cache->ops : cache->mem;
+                if (d.n != req[i].n) return false;
+                RowSumSetIn s; s.n = d.n; s.decoded = d.pts.p; s.decoded_bad = d.bad;
+                shared = (long)sets.size(); sets.push_back(s);
+            }
+            if (is_ops || is_mem) jobs[i].set = (size_t)shared;
+            else { RowSumSetIn s; s.comp32 = req[i].C[0].b; s.n = req[i].n; jobs[i].set = sets.size(); sets.push_back(s); }
+            jobs[i].scalars = req[i].s;
+        }
+        std::vector<RowSumOut> out(n);
+        dev_row_sums_many(c, sets.data(), sets.size(), jobs.data(), n, out.data());
+        for (size_t i = 0; i < n; i++) { ans[i].code = out[i].code; ans[i].sum = out[i].sum; }
+        return true;
+    } catch (const Error &) { return false; }
+}
 static const bool g_hook_registered = [] {
+    g_row_sums_many_hook = row_sums_many_on_device;
     g_fixed_base_msm_hook = fixed_base_msm_on_device; g_row_sum_begin_hook = row_sum_begin_on_device; g_row_sum_finish_hook = row_sum_finish_on_device;
     return true;
 }();

@@ -13,10 +13,14 @@
 #include <functional>
 #include <thread>
 #include <atomic>
+#include <chrono>
+#include <memory>
+#include <mutex>
 
 namespace otti {
 
 struct DeviceDecomm;                                         // snark_prover.h: the dense representation resident in HBM
+struct RowSumsCache;                                         // prover.cpp: a commitment's points decoded in HBM (snark_verify_many)
 
 // lib.rs SNARKGens: gens_r1cs_sat (the NIZK generators) + gens_r1cs_eval = SparseMatPolyCommitmentGens {gens_ops, gens_mem, gens_derefs},
 // three PolyCommitmentGens over ONE SHAKE256 stream (label "gens_r1cs_eval"): a set for m variables is gens_n = P[0 .. R), gens_1.G = P[R],
@@ -35,6 +39,9 @@ struct CompComm {
     size_t batch_size = 3, num_ops = 0, num_mem_cells = 0;   // SparseMatPolyCommitment
     std::vector<CPoint> comm_ops, comm_mem;
     std::shared_ptr<DeviceDecomm> dec;                       // prover side only
+    // verifier side: comm_ops and comm_mem decoded in HBM for snark_verify_many's passes, built once by whichever thread first needs them
+    // (under row_cache_mu), shared read-only, freed with the commitment
+    mutable std::shared_ptr<RowSumsCache> row_cache; mutable std::mutex row_cache_mu;
     std::vector<uint8_t> serialize() const;                  // bincode
     static std::unique_ptr<CompComm> parse(const uint8_t *p, size_t n);
 };
@@ -93,10 +100,13 @@ struct RowSum {
 // Lock-free: the producer fills a slot and bumps `count`; workers claim slots with a compare-exchange on `next`.
 class Deferred {
 public:
-    Deferred() {
+    // workers < 0: the default rule below.  0: no threads at all — everything handed over runs in finish(), on the thread that calls it (a proof
+    // parked between the steps of snark_verify_many owns no thread); the failure reported is the same either way.
+    explicit Deferred(int workers = -1) {
         const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
         unsigned nw = hw >= 12 ? 6 : hw >= 6 ? hw - 3 : 0;                // beside the caller and its spinning helpers (pool.h)
         if (const char *e = getenv("OTTI_VERIFY_THREADS")) { int v = atoi(e); if (v >= 0 && v <= 32) nw = (unsigned)v; }
+        if (workers >= 0) nw = (unsigned)workers;
         try { for (unsigned i = 0; i < nw; i++) th_.emplace_back([this] { work(false); }); } catch (const std::system_error &) {}
     }
     Deferred(const Deferred &) = delete; Deferred &operator=(const Deferred &) = delete;
@@ -139,6 +149,62 @@ private:
     }
 };
 void dotproductlog_verify(const DotProductProofLog &pf, size_t n, const Gens &g, const PcView &v, Transcript &tr, const Fr *a, const CPoint &Cx, const CPoint &Cy, Deferred *later = nullptr);
+// RowSum's host path alone: decompression and Pippenger on the host cores.  wide: striped over up to 16 threads of its own (the single verifier);
+// otherwise on the calling thread alone (snark_verify_many's workers are the parallelism there).  Throws VerifyFail{OTTI_ERR_VERIFY_DECOMPRESS}.
+Pt row_sum_on_host(const CPoint *C, size_t n, const Fr *s, bool wide);
+
+// R1CSEvalProof::verify as a resumable walk.  Its three variable-base row sums (PolyEvalProof::verify's C_LZ of the derefs, ops and mem
+// evaluation proofs, in that order) are the seams: a step ends by NAMING its sum (points and scalars, both alive until the next step has begun) and
+// the next step begins with the answer — the point, or the decompress failure, which it throws where RowSum::finish would have.  Between steps
+// the object owns no thread when made with deferred_threads = 0 (its group equations then run inside after_mem).  Every step throws VerifyFail; after
+// a throw the object is only good for destruction.  evalproof_verify below is begin .. after_mem in sequence with RowSum answering.
+struct RowRequest { const CPoint *C = nullptr; size_t n = 0; const Fr *s = nullptr; };
+struct RowAnswer { int code = 0; Pt sum; };
+class EvalProofVerifier {
+public:
+    EvalProofVerifier(const EvalProof &E, const CompComm &c, const std::vector<Fr> &rx, const std::vector<Fr> &ry, const Fr evals[3], const SnarkGens &g, Transcript &tr,
+                      int deferred_threads = -1);
+    RowRequest begin();                                      // step 0: the product-layer and layered sum-check walk; names the sum over comm_derefs
+    RowRequest after_derefs(const RowAnswer &a);             // step 1: names the sum over comm_ops
+    RowRequest after_ops(const RowAnswer &a);                // step 2: names the sum over comm_mem
+    void after_mem(const RowAnswer &a);                      // step 3: the hash layer's closing checks and every deferred group equation
+private:
+    const EvalProof &E; const CompComm &c; const SnarkGens &g; Transcript &tr;
+    Deferred later;
+    Fr evals[3]; size_t nm = 0;
+    std::vector<Fr> rxe, rye, r_mem_check, claims_ops, claims_dotp, rand_ops, claims_mem, rand_mem;
+    // the evaluation proof whose row sum is out
+    const DotProductProofLog *pe_pf = nullptr; const PcSet *pe_set = nullptr; std::vector<Fr> Lv, Rv; CPoint C_Zr;
+    bool trace; std::chrono::steady_clock::time_point t_lap, t_sum;
+    void lap(const char *what);
+    RowRequest polyeval_begin(const DotProductProofLog &pf, const PcSet &s, const std::vector<Fr> &r, const Fr &Zr, const std::vector<CPoint> &comm);
+    void polyeval_end(const RowAnswer &a);
+    Fr joint(std::vector<Fr> ev, const char *label_evals, const char *label_ch, const char *label_joint, const std::vector<Fr> &rand, std::vector<Fr> &r_joint);
+};
+void evalproof_verify(const EvalProof &E, const CompComm &c, const std::vector<Fr> &rx, const std::vector<Fr> &ry, const Fr evals[3], const SnarkGens &g, Transcript &tr);
+
+// ---------------------------------------------------------------------------------------------- many proofs of one commitment (snark_verify_many.cpp)
+// results[i] = what snark_verify returns for item i alone with the same commitment, generators and label (an input >= l: OTTI_ERR_INVALID_SCALAR, as
+// the C entry reports it) — NOT a random-linear-combination batch: every proof walks the single verifier's own steps and no verdict depends on its
+// neighbours.  What the proofs share is their three row sums: all live proofs reach each seam of EvalProofVerifier together, and the calling thread
+// sends the sums of one seam to the device in ONE pass (hook below, set by prover.cpp: that file has no HIP in it) — comm_ops and comm_mem, the same
+// points for every proof, decoded once per commitment and kept on it.  Sums under kRowSumDeviceMin points, and all of them without a hook, when it
+// declines or throws, or under OTTI_VERIFY_HOST, are summed on the host by the workers; the verdicts do not depend on the route.
+// `threads` workers (0: kSnarkVerifyManyThreads; at most kVerifyManyMaxThreads; never more than there are proofs) run step 0 (everything snark_verify
+// does before the evaluation proof, r1cs_verify_host with its own row sum included) and then each next step of every proof still alive; with one
+// worker everything runs on the calling thread.  A proof parked between steps owns no thread: the threads alive depend on `threads`, not on count.
+// Live proofs are bounded: the call runs in chunks of kSnarkVerifyManyChunk items (OTTI_SNARK_VERIFY_CHUNK overrides it, for the tests).
+// Per chunk, host: the parsed proofs (a few hundred KB each at 2^20) and per proof two eq tables of at most 2^12 scalars; HBM, on the calling
+// thread's context, grow-only: 160 bytes per comm_derefs point (chunk * L_derefs of them), 32 per scalar of every sum, 128 per (window, split)
+// of a sum — about 25 MB at 2^20 (8192 rows) with 16 proofs — plus, once per commitment and for its lifetime, 96 bytes per point of comm_ops and comm_mem.
+constexpr unsigned kSnarkVerifyManyThreads = 4;
+constexpr size_t kSnarkVerifyManyChunk = 16, kRowSumDeviceMin = 256;
+// req[i].C == comm.comm_ops.data() / comm.comm_mem.data(): the commitment's own points (cached); anything else: that request's own set.
+// Runs on the calling thread's context; false: declined, nothing answered.
+typedef bool (*RowSumsManyHook)(const CompComm &comm, const RowRequest *req, size_t n, RowAnswer *ans);
+extern RowSumsManyHook g_row_sums_many_hook;
+void snark_verify_many(const CompComm &comm, const SnarkGens &g, const void *tlabel, size_t tlabel_len, const VerifyItem *items, size_t count, unsigned threads,
+                       int32_t *results);
 
 // GPU (snark_encode.cpp: encode, attach; snark_prover.cpp: prove)
 struct SnarkTimings { double ms[10]; };                      // the six R1CSProof stages, [6] derefs commitment, [7] product circuits, [8] hash layer, [9] total

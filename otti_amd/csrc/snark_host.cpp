@@ -225,22 +225,6 @@ void pcbatch_verify(const ProductCircuitEvalProofBatched &pf, const std::vector<
     }
     claims_out = claims;
 }
-// PolyEvalProof::verify_plain: the commitment opens to Zr (blind zero) at r
-void polyeval_verify_plain(const DotProductProofLog &pf, const PcSet &s, const Gens &g, const std::vector<Fr> &r, const Fr &Zr, const std::vector<CPoint> &comm, RowSum &rows, Transcript &tr,
-                           Deferred &later) {
-    require(r.size() == s.num_vars && comm.size() == s.L && rows.n == s.L && rows.C == comm.data() && pf.L_vec.size() == ilog2(s.R));
-    const auto t_b = std::chrono::steady_clock::now();
-    CPoint C_Zr; { Term t = {s.g1, Zr}; g.commit_terms_c(C_Zr.b, &t, 1); }
-    if (getenv("OTTI_TRACE")) fprintf(stderr, "[otti]   polyeval_verify_plain: C_Zr %.3f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_b).count());
-    tr.append_protocol_name("polynomial evaluation proof");
-    const size_t lv = s.num_vars / 2;
-    std::vector<Fr> Lv = eq_evals_host(r.data(), lv), Rv = eq_evals_host(r.data() + lv, s.num_vars - lv);
-    static const bool trace = getenv("OTTI_TRACE") != nullptr; const auto t_a = std::chrono::steady_clock::now();
-    CPoint C_LZ; pt_encode(C_LZ.b, rows.finish(Lv.data()));
-    if (trace) fprintf(stderr, "[otti]   polyeval_verify_plain: C_Zr + eq tables + row sum %.3f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_a).count());
-    const PcView pv = {s.h_n, s.g1, s.h1, s.R};
-    dotproductlog_verify(pf, s.R, g, pv, tr, Rv.data(), C_LZ, C_Zr, &later);
-}
 // HashLayerProof::verify_helper
 void hash_verify_helper(const std::vector<Fr> &rand_mem, const Evals4 &claims, const Fr ops_val[3], const Fr ops_addr[3], const Fr read_ts[3], const Fr &audit_ts,
                         const std::vector<Fr> &r, const Fr &r_hash, const Fr &gamma) {
@@ -257,23 +241,59 @@ void hash_verify_helper(const std::vector<Fr> &rand_mem, const Evals4 &claims, c
     }
     require(fr_eq(hash3(init_addr, init_val, audit_ts, r_hash, r2, gamma), claims.audit));
 }
-// R1CSEvalProof::verify
-void evalproof_verify(const EvalProof &E, const CompComm &c, const std::vector<Fr> &rx, const std::vector<Fr> &ry, const Fr evals[3], const SnarkGens &g, Transcript &tr) {
-    const bool trace = getenv("OTTI_TRACE") != nullptr; auto t_lap = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) { if (!trace) return; const auto t = std::chrono::steady_clock::now(); fprintf(stderr, "[otti] evalproof_verify %-32s %.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_lap).count()); t_lap = t; };
-    tr.append_protocol_name("Sparse polynomial evaluation proof");
-    // the three polynomial commitments whose rows the closing evaluation proofs sum are known now: with a device they decompress while
-    // the host verifies the layered sum-checks
-    RowSum rows_derefs(E.comm_derefs.data(), E.comm_derefs.size()), rows_ops(c.comm_ops.data(), c.comm_ops.size()), rows_mem(c.comm_mem.data(), c.comm_mem.size());
-    Deferred later;                                                   // the closing group equations of the three evaluation proofs run beside the rest
-    const size_t nm = std::max(rx.size(), ry.size()), N = c.num_ops, M = c.num_mem_cells;
-    std::vector<Fr> rxe(nm - rx.size(), fr_zero()), rye(nm - ry.size(), fr_zero());     // equalize: zeros in FRONT of the shorter point
+}  // namespace
+
+// ================================================================================================ R1CSEvalProof::verify in four steps (snark.h)
+EvalProofVerifier::EvalProofVerifier(const EvalProof &E_, const CompComm &c_, const std::vector<Fr> &rx, const std::vector<Fr> &ry, const Fr evals_[3], const SnarkGens &g_, Transcript &tr_,
+                                     int deferred_threads)
+    : E(E_), c(c_), g(g_), tr(tr_), later(deferred_threads), trace(getenv("OTTI_TRACE") != nullptr), t_lap(std::chrono::steady_clock::now()) {
+    for (int k = 0; k < 3; k++) evals[k] = evals_[k];
+    nm = std::max(rx.size(), ry.size());
+    rxe.assign(nm - rx.size(), fr_zero()); rye.assign(nm - ry.size(), fr_zero());       // equalize: zeros in FRONT of the shorter point
     rxe.insert(rxe.end(), rx.begin(), rx.end()); rye.insert(rye.end(), ry.begin(), ry.end());
+}
+void EvalProofVerifier::lap(const char *what) {
+    if (!trace) return;
+    const auto t = std::chrono::steady_clock::now(); fprintf(stderr, "[otti] evalproof_verify %-32s %.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_lap).count()); t_lap = t;
+}
+// PolyEvalProof::verify_plain (the commitment opens to Zr, blind zero, at r) up to its row sum, which it names
+RowRequest EvalProofVerifier::polyeval_begin(const DotProductProofLog &pf, const PcSet &s, const std::vector<Fr> &r, const Fr &Zr, const std::vector<CPoint> &comm) {
+    const Gens &gg = *g.eval;
+    require(r.size() == s.num_vars && comm.size() == s.L && pf.L_vec.size() == ilog2(s.R));
+    const auto t_b = std::chrono::steady_clock::now();
+    { Term t = {s.g1, Zr}; gg.commit_terms_c(C_Zr.b, &t, 1); }
+    if (trace) fprintf(stderr, "[otti]   polyeval_verify_plain: C_Zr %.3f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_b).count());
+    tr.append_protocol_name("polynomial evaluation proof");
+    const size_t lv = s.num_vars / 2;
+    Lv = eq_evals_host(r.data(), lv); Rv = eq_evals_host(r.data() + lv, s.num_vars - lv);
+    pe_pf = &pf; pe_set = &s; t_sum = std::chrono::steady_clock::now();
+    return {comm.data(), comm.size(), Lv.data()};
+}
+// ... and from the sum on: throws where RowSum::finish would have
+void EvalProofVerifier::polyeval_end(const RowAnswer &a) {
+    if (a.code) throw VerifyFail{a.code};
+    CPoint C_LZ; pt_encode(C_LZ.b, a.sum);
+    if (trace) fprintf(stderr, "[otti]   polyeval_verify_plain: C_Zr + eq tables + row sum %.3f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_sum).count());
+    const PcSet &s = *pe_set; const PcView pv = {s.h_n, s.g1, s.h1, s.R};
+    dotproductlog_verify(*pe_pf, s.R, *g.eval, pv, tr, Rv.data(), C_LZ, C_Zr, &later);
+}
+Fr EvalProofVerifier::joint(std::vector<Fr> ev, const char *label_evals, const char *label_ch, const char *label_joint, const std::vector<Fr> &rand, std::vector<Fr> &r_joint) {
+    tr.append_scalars(label_evals, ev.data(), ev.size());
+    std::vector<Fr> ch = tr.challenge_vector(label_ch, ilog2(ev.size()));
+    const Fr j = reduce_evals(ev, ch);
+    r_joint = ch; r_joint.insert(r_joint.end(), rand.begin(), rand.end());
+    tr.append_scalar(label_joint, j);
+    return j;
+}
+// step 0: the layered sum-checks, up to the row sum of the derefs evaluation proof
+RowRequest EvalProofVerifier::begin() {
+    tr.append_protocol_name("Sparse polynomial evaluation proof");
+    const size_t N = c.num_ops, M = c.num_mem_cells;
     require(((size_t)1 << nm) == M && N >= 2 && N == next_pow2(N));
     tr.append_message("derefs_commitment", "begin_derefs_commitment", 23);
     append_poly_commitment(tr, "comm_poly_row_col_ops_val", E.comm_derefs);
     tr.append_message("derefs_commitment", "end_derefs_commitment", 21);
-    std::vector<Fr> r_mem_check = tr.challenge_vector("challenge_r_hash", 2);
+    r_mem_check = tr.challenge_vector("challenge_r_hash", 2);
     tr.append_protocol_name("Sparse polynomial evaluation proof");
     // ---- ProductLayerProof::verify
     tr.append_protocol_name("Sparse polynomial product layer proof");
@@ -290,7 +310,7 @@ void evalproof_verify(const EvalProof &E, const CompComm &c, const std::vector<F
         tr.append_scalar("claim_eval_dotp_left", E.dotp_left[k]); tr.append_scalar("claim_eval_dotp_right", E.dotp_right[k]);
         claims_dotp_circuit.push_back(E.dotp_left[k]); claims_dotp_circuit.push_back(E.dotp_right[k]);
     }
-    std::vector<Fr> claims_prod(12), claims_ops, claims_dotp, rand_ops, claims_mem, none, rand_mem;
+    std::vector<Fr> claims_prod(12), none;
     for (int k = 0; k < 3; k++) { claims_prod[k] = E.eval_row.read[k]; claims_prod[3 + k] = E.eval_row.write[k]; claims_prod[6 + k] = E.eval_col.read[k]; claims_prod[9 + k] = E.eval_col.write[k]; }
     lap("commitments appended, jobs begun");
     pcbatch_verify(E.proof_ops, claims_prod, claims_dotp_circuit, N, tr, claims_ops, claims_dotp, rand_ops);
@@ -300,44 +320,58 @@ void evalproof_verify(const EvalProof &E, const CompComm &c, const std::vector<F
     require(claims_dotp.size() == 9 && rand_mem.size() == nm);
     // ---- HashLayerProof::verify
     tr.append_protocol_name("Sparse polynomial hash layer proof");
-    auto joint = [&](std::vector<Fr> ev, const char *label_evals, const char *label_ch, const char *label_joint, const std::vector<Fr> &rand, std::vector<Fr> &r_joint) {
-        tr.append_scalars(label_evals, ev.data(), ev.size());
-        std::vector<Fr> ch = tr.challenge_vector(label_ch, ilog2(ev.size()));
-        const Fr j = reduce_evals(ev, ch);
-        r_joint = ch; r_joint.insert(r_joint.end(), rand.begin(), rand.end());
-        tr.append_scalar(label_joint, j);
-        return j;
-    };
-    {   // DerefsEvalProof::verify
-        tr.append_protocol_name("Derefs evaluation proof");
-        std::vector<Fr> ev(8, fr_zero()), rj;
-        for (int k = 0; k < 3; k++) { ev[k] = E.h_deref_row[k]; ev[3 + k] = E.h_deref_col[k]; }
-        const Fr j = joint(ev, "evals_ops_val", "challenge_combine_n_to_one", "joint_claim_eval", rand_ops, rj);
-        polyeval_verify_plain(E.pe_derefs, g.derefs, *g.eval, rj, j, E.comm_derefs, rows_derefs, tr, later);
-        lap("polyeval derefs");
-    }
+    // DerefsEvalProof::verify
+    tr.append_protocol_name("Derefs evaluation proof");
+    std::vector<Fr> ev(8, fr_zero()), rj;
+    for (int k = 0; k < 3; k++) { ev[k] = E.h_deref_row[k]; ev[3 + k] = E.h_deref_col[k]; }
+    const Fr j = joint(ev, "evals_ops_val", "challenge_combine_n_to_one", "joint_claim_eval", rand_ops, rj);
+    return polyeval_begin(E.pe_derefs, g.derefs, rj, j, E.comm_derefs);
+}
+// step 1: from the derefs sum to the row sum over comm_ops
+RowRequest EvalProofVerifier::after_derefs(const RowAnswer &a) {
+    polyeval_end(a);
+    lap("polyeval derefs");
     for (int k = 0; k < 3; k++) require(fr_eq(claims_dotp[3 * k], E.h_deref_row[k]) && fr_eq(claims_dotp[3 * k + 1], E.h_deref_col[k]) && fr_eq(claims_dotp[3 * k + 2], E.h_val[k]));
-    {
-        std::vector<Fr> ev(16, fr_zero()), rj;
-        for (int k = 0; k < 3; k++) { ev[k] = E.h_row_addr[k]; ev[3 + k] = E.h_row_read_ts[k]; ev[6 + k] = E.h_col_addr[k]; ev[9 + k] = E.h_col_read_ts[k]; ev[12 + k] = E.h_val[k]; }
-        const Fr j = joint(ev, "claim_evals_ops", "challenge_combine_n_to_one", "joint_claim_eval_ops", rand_ops, rj);
-        polyeval_verify_plain(E.pe_ops, g.ops, *g.eval, rj, j, c.comm_ops, rows_ops, tr, later);
-        lap("polyeval ops");
-    }
-    {
-        std::vector<Fr> rj;
-        const Fr j = joint({E.h_row_audit, E.h_col_audit}, "claim_evals_mem", "challenge_combine_two_to_one", "joint_claim_eval_mem", rand_mem, rj);
-        polyeval_verify_plain(E.pe_mem, g.mem, *g.eval, rj, j, c.comm_mem, rows_mem, tr, later);
-        lap("polyeval mem");
-    }
-    Evals4 crow, ccol;                                                // the product layer's claims at (rand_mem, rand_ops)
+    std::vector<Fr> ev(16, fr_zero()), rj;
+    for (int k = 0; k < 3; k++) { ev[k] = E.h_row_addr[k]; ev[3 + k] = E.h_row_read_ts[k]; ev[6 + k] = E.h_col_addr[k]; ev[9 + k] = E.h_col_read_ts[k]; ev[12 + k] = E.h_val[k]; }
+    const Fr j = joint(ev, "claim_evals_ops", "challenge_combine_n_to_one", "joint_claim_eval_ops", rand_ops, rj);
+    return polyeval_begin(E.pe_ops, g.ops, rj, j, c.comm_ops);
+}
+// step 2: from the ops sum to the row sum over comm_mem
+RowRequest EvalProofVerifier::after_ops(const RowAnswer &a) {
+    polyeval_end(a);
+    lap("polyeval ops");
+    std::vector<Fr> rj;
+    const Fr j = joint({E.h_row_audit, E.h_col_audit}, "claim_evals_mem", "challenge_combine_two_to_one", "joint_claim_eval_mem", rand_mem, rj);
+    return polyeval_begin(E.pe_mem, g.mem, rj, j, c.comm_mem);
+}
+// step 3: from the mem sum to the end, the deferred group equations included
+void EvalProofVerifier::after_mem(const RowAnswer &a) {
+    polyeval_end(a);
+    lap("polyeval mem");
+    Evals4 crow, ccol;                                              // the product layer's claims at (rand_mem, rand_ops)
     crow.init = claims_mem[0]; crow.audit = claims_mem[1]; ccol.init = claims_mem[2]; ccol.audit = claims_mem[3];
     for (int k = 0; k < 3; k++) { crow.read[k] = claims_ops[k]; crow.write[k] = claims_ops[3 + k]; ccol.read[k] = claims_ops[6 + k]; ccol.write[k] = claims_ops[9 + k]; }
     hash_verify_helper(rand_mem, crow, E.h_deref_row, E.h_row_addr, E.h_row_read_ts, E.h_row_audit, rxe, r_mem_check[0], r_mem_check[1]);
     hash_verify_helper(rand_mem, ccol, E.h_deref_col, E.h_col_addr, E.h_col_read_ts, E.h_col_audit, rye, r_mem_check[0], r_mem_check[1]);
     later.finish();
 }
-}  // namespace
+// the four steps in sequence with RowSum answering: the single verifier.  The three polynomial commitments whose rows the closing evaluation
+// proofs sum are known at the start: with a device they decompress while the host verifies the layered sum-checks
+static RowAnswer answer_from(RowSum &rows, const RowRequest &q) {
+    require(rows.n == q.n && rows.C == q.C);
+    RowAnswer a; a.sum = pt_identity();
+    try { a.sum = rows.finish(q.s); } catch (const VerifyFail &f) { a.code = f.code; }
+    return a;
+}
+void evalproof_verify(const EvalProof &E, const CompComm &c, const std::vector<Fr> &rx, const std::vector<Fr> &ry, const Fr evals[3], const SnarkGens &g, Transcript &tr) {
+    RowSum rows_derefs(E.comm_derefs.data(), E.comm_derefs.size()), rows_ops(c.comm_ops.data(), c.comm_ops.size()), rows_mem(c.comm_mem.data(), c.comm_mem.size());
+    EvalProofVerifier v(E, c, rx, ry, evals, g, tr);                  // its closing group equations run beside the rest (Deferred's own threads)
+    RowRequest q = v.begin();
+    q = v.after_derefs(answer_from(rows_derefs, q));
+    q = v.after_ops(answer_from(rows_ops, q));
+    v.after_mem(answer_from(rows_mem, q));
+}
 
 void snark_append_comm(Transcript &tr, const CompComm &c) {          // R1CSCommitment / SparseMatPolyCommitment::append_to_transcript
     append_u64(tr, "num_cons", c.num_cons); append_u64(tr, "num_vars", c.num_vars); append_u64(tr, "num_inputs", c.num_inputs);

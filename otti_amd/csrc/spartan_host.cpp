@@ -421,7 +421,11 @@ Pt RowSum::finish(const Fr *s) {
         lap.dev = false;
         if (rc == OTTI_ERR_VERIFY_DECOMPRESS) throw VerifyFail{rc};
     }
+    return row_sum_on_host(C, n, s, true);
+}
+Pt row_sum_on_host(const CPoint *C, size_t n, const Fr *s, bool wide) {
     std::vector<Pt> Cs(n);
+    if (!wide) { for (size_t i = 0; i < n; i++) Cs[i] = dec(C[i]); return host_msm(s, Cs.data(), n); }
     {   // decompression of the row commitments (an inverse square root each), striped over the host cores
         const size_t nt = std::min<size_t>({n / 64 + 1, (size_t)16, (size_t)std::max(1u, std::thread::hardware_concurrency())});
         std::vector<int> bad(nt, 0); std::vector<std::thread> th;
