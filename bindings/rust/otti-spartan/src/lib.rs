@@ -18,6 +18,20 @@ pub enum OttiGens {}
 pub enum OttiSnarkGens {}
 pub enum OttiCompComm {}
 pub enum OttiWitness {}
+/// what otti_nizk_prove_many reports about its front half (otti_prove_many_info)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct OttiProveManyInfo {
+    pub chunks: u32,
+    pub product_tiles: u32,
+    pub row_jobs: u32,
+    pub workers: u32,
+    pub rows_from_front: u32,
+    pub products_from_front: u32,
+    pub front_failed: u32,
+    pub row_kernel: [i32; 4],
+    pub front_ms: [f64; 3],
+}
 
 extern "C" {
     fn otti_instance_new(num_cons: u64, num_vars: u64, num_inputs: u64, a: *const OttiEntry, na: usize, b: *const OttiEntry, nb: usize,
@@ -49,6 +63,12 @@ extern "C" {
     fn otti_witness_from_zkif(inst: *mut OttiInstance, inputs_path: *const c_char, witness_path: *const c_char, mode: i32, out: *mut *mut OttiWitness,
                               inputs_out: *mut *mut c_void) -> i32;
     fn otti_witness_ingest_info(wit: *const OttiWitness, on_device: *mut i32, witness_bytes: *mut u64, ms: *mut f64) -> i32;
+    // many resident witnesses of one instance proved in one call: results[i], proofs[i] (otti_buf_free) and proof_lens[i] are what
+    // otti_nizk_prove_resident gives for wits[i] and seeds32[i] alone; the witness-only work of the proofs is formed for the batch in joint passes and
+    // the library's own `threads` workers (0: four; at most 16; the calling thread counts) run the rest.  The handles are only read.
+    fn otti_nizk_prove_many(inst: *mut OttiInstance, wits: *const *mut OttiWitness, count: usize, gens: *mut OttiGens, tlabel: *const u8, tlabel_len: usize,
+                            seeds32: *const *const u8, threads: u32, proofs: *mut *mut u8, proof_lens: *mut usize, results: *mut i32,
+                            n_failed: *mut usize, stage_ms: *mut f64, info: *mut OttiProveManyInfo) -> i32;
     // whether the host entry lists of an instance exist (a device ingest has none until a host consumer downloads them; asking never does) and their size
     fn otti_instance_host_lists_info(inst: *const OttiInstance, materialised: *mut i32, host_bytes: *mut u64) -> i32;
     // kernel-level entries (tests): the decommitment fill from one entry list; a rank's share of an entry list (flag, scan, scatter)

@@ -196,6 +196,50 @@ int32_t otti_nizk_verify(const otti_instance *inst, const uint8_t *inputs32, siz
 int32_t otti_nizk_verify_many(const otti_instance *inst, const otti_gens *gens, const uint8_t *tlabel, size_t tlabel_len, size_t count,
                               const uint8_t *const *inputs32, const size_t *ninputs, const uint8_t *const *proofs, const size_t *proof_lens,
                               uint32_t threads, int32_t *results, size_t *n_rejected /* may be NULL */);
+/* Many resident witnesses of ONE instance proved in one call: the prover's counterpart of otti_nizk_verify_many.  results[i], proofs[i] and
+   proof_lens[i] are exactly what otti_nizk_prove_resident(inst, wits[i], gens, tlabel, tlabel_len, seeds32[i], ..) returns — with a seed, the same
+   bytes; seeds32 NULL, or seeds32[i] NULL: OS entropy.  Each proof is freed with otti_buf_free; a failed item has proofs[i] = NULL, proof_lens[i] = 0.
+   What the proofs share: everything a proof computes before its first challenge depends on the witness alone — the unblinded row sums of its
+   commitment and Az, Bz, Cz.  The calling thread forms both for chunks of at most 16 witnesses in joint passes (the FRONT HALF): ONE fixed-base
+   MSM launch over the rows of all witnesses of a chunk that do not keep rows (one per MSM variant; a joint launch may be a chip-filling one
+   where each single launch is a small one), and one walk over A, B, C per four witnesses that do not keep products
+   (otti_k_multiply_vec_many is that walk alone, otti_k_prove_front the front half alone).  A chunk in which fewer than two witnesses lack a
+   thing gets no joint pass for it.  The sequential halves then run on the library's own workers.
+   Where the joint passes run follows from measurements (profiles/prove_many.md): up to 2^16 padded variables — beyond, a proof's own launches
+   hide behind its tape draws and the joint ones cost more wall time than they save — and, for the products, only where the matrices have the
+   row-per-quad layout of a compiled circuit (three entries per row and matrix on average, or more).  Elsewhere each proof forms the thing
+   itself, as a single proof does; OTTI_PROVE_MANY_RULE=0, read per call, sets this rule aside (measurements, tests).
+   Per-item failures do not affect other items: a witness uploaded for other dimensions gives OTTI_ERR_INVALID_NUM_VARS, a wrong input count
+   OTTI_ERR_INVALID_NUM_INPUTS.  Returns OTTI_OK when the call ran; *n_failed (may be NULL) = the number of non-zero results, which
+   otti_last_error also names.
+   Refusals before anything is touched (outputs stay as they were), in this order: OTTI_ERR_BAD_ARG for a null inst or gens; a null proofs,
+   proof_lens or results; with count > 0 a null wits or wits[i]; threads > 16; generators made for another size; then OTTI_ERR_NO_DEVICE.
+   count == 0: OTTI_OK, nothing done.
+   Handles: the call only reads them — a witness's z, kept rows, kept products and counters are as before.  One handle may appear several times.
+   Several caller threads may call with the same handles at once.
+   Threads: `threads` counts the calling thread (0: the default, 4, as otti_nizk_verify_many — six and eight were faster in the median but
+   showed outliers of several times the median where a process opens four hardware queues, profiles/prove_many.md; never more than count).  threads = 1 or count = 1
+   runs everything on the calling thread.  Workers lease pooled device contexts and are joined before the call returns; a worker starts a proof
+   once the launches that write its front buffers have completed, so the first proofs run while later tiles are still summed.
+   HBM: the front half's buffers live on the calling thread's context, grow-only, kept across calls and reused chunk by chunk: 96 N bytes per
+   witness lacking products, 128 L + 32 V per witness lacking rows, one tile of 256 V bytes.  OTTI_PROVE_MANY_GB (read per call; default 8; 0: no
+   front half) bounds them by cutting chunks shorter; OTTI_PROVE_MANY_FRONT=0 switches the front half off (A/B runs).  A front half that cannot
+   get its memory is no error: the chunk's proofs form their own rows and products (info.front_failed counts such chunks).  Bytes never depend on
+   any of this.
+   stage_ms[8 i ..] (count * 8 doubles, may be NULL): proof i's own stages as otti_nizk_prove_resident reports them; [0] excludes the front half,
+   whose device-event times info.front_ms holds. */
+typedef struct {
+    uint32_t chunks, product_tiles, row_jobs, workers;
+    uint32_t rows_from_front, products_from_front;   /* witnesses whose proof read the front half's rows / products */
+    uint32_t front_failed;                           /* chunks whose front half gave up (proofs then formed their own) */
+    int32_t  row_kernel[4];                          /* MsmKernel of the first four row jobs (0 bulk, 1 bulk-sparse, 2 small), -1 unused */
+    double   front_ms[3];                            /* staging + interleave, row sums, products: device-event time */
+} otti_prove_many_info;
+int32_t otti_nizk_prove_many(otti_instance *inst, otti_witness *const *wits, size_t count, otti_gens *gens,
+                             const uint8_t *tlabel, size_t tlabel_len,
+                             const uint8_t *const *seeds32 /* NULL, or seeds32[i] NULL: OS entropy */, uint32_t threads,
+                             uint8_t **proofs, size_t *proof_lens, int32_t *results, size_t *n_failed /* may be NULL */,
+                             double *stage_ms /* count * 8, may be NULL */, otti_prove_many_info *info /* may be NULL */);
 /* ---- SNARK mode (`spzk verify` without --nizk): upstream lib.rs SNARKGens / ComputationCommitment / SNARK [RECALL].
    otti_snark_encode = SNARK::encode (once per circuit: the commitment to A, B, C — on the GPU); otti_snark_prove = SNARK::prove
    (R1CSProof as in NIZK mode + R1CSEvalProof: memory-checking product circuits, batched cubic sum-checks, three polynomial
@@ -542,6 +586,16 @@ int32_t otti_k_fr_from_canonical(const uint8_t *h_in, uint8_t *h_out, size_t n);
 int32_t otti_k_fr_to_canonical(const uint8_t *h_in, uint8_t *h_out, size_t n);
 /* R1CSInstance::multiply_vec: z has 2*num_vars entries; outputs num_cons entries each */
 int32_t otti_k_multiply_vec(otti_instance *inst, const uint8_t *h_z, uint8_t *h_Az, uint8_t *h_Bz, uint8_t *h_Cz, float *kernel_ms);
+/* the same for K vectors through the many-vector kernels (one walk over the matrices per tile of four vectors, K = 1 included): h_zs[k] has
+   2*num_vars entries; outputs K * num_cons entries each, vector k's at [k * num_cons ..), bit for bit what otti_k_multiply_vec gives for it.
+   kernel_ms includes putting a tile's vectors side by side.  OTTI_ERR_BAD_ARG: a null argument or K = 0. */
+int32_t otti_k_multiply_vec_many(otti_instance *inst, const uint8_t *const *h_zs, size_t K, uint8_t *h_Az, uint8_t *h_Bz, uint8_t *h_Cz, float *kernel_ms);
+/* otti_nizk_prove_many's front half alone on K staged vectors (plan, budget and switches as there; small_flags[k] != 0: vector k's rows are
+   summed by the MSM variant for small scalars).  h_rows32: K * L * 32 bytes, the compressed UNBLINDED row sums of vector k's variables at
+   [k * L * 32 ..); h_Az, h_Bz, h_Cz: K * num_cons entries each.  What the plan leaves to a single proof is formed as that proof forms it, so the
+   outputs are whole; info (may be NULL) says what ran jointly.  OTTI_ERR_BAD_ARG: a null argument, K = 0, generators made for another size. */
+int32_t otti_k_prove_front(otti_instance *inst, otti_gens *gens, const uint8_t *const *h_zs, const int32_t *small_flags, size_t K, uint8_t *h_rows32,
+                           uint8_t *h_Az, uint8_t *h_Bz, uint8_t *h_Cz, otti_prove_many_info *info, float *kernel_ms);
 /* the patch of kept products on a caller's host state.  h_cols: ncols strictly ascending z indices below 2 * padded num_vars (else
    OTTI_ERR_INVALID_INDEX, judged on the host before anything is staged), or NULL with the range [first, first + count); the io vectors are N
    Montgomery elements each, io_bits ceil(N / 64) words, *io_unsat the count that goes with them: they are patched for z = h_z_new exactly as a

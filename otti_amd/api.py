@@ -117,6 +117,21 @@ _sig("otti_nizk_prove_sharded", _i32, _vp, _vp, _vp, ctypes.c_char_p, _sz, _vp, 
 _sig("otti_nizk_verify", _i32, _vp, _vp, _sz, _vp, ctypes.c_char_p, _sz, _vp, _sz)
 _sig("otti_nizk_verify_many", _i32, _vp, _vp, ctypes.c_char_p, _sz, _sz, ctypes.POINTER(_vp), ctypes.POINTER(_sz), ctypes.POINTER(_vp), ctypes.POINTER(_sz),
      ctypes.c_uint32, ctypes.POINTER(_i32), ctypes.POINTER(_sz))
+class _ProveManyInfo(ctypes.Structure):
+    _fields_ = [("chunks", ctypes.c_uint32), ("product_tiles", ctypes.c_uint32), ("row_jobs", ctypes.c_uint32), ("workers", ctypes.c_uint32),
+                ("rows_from_front", ctypes.c_uint32), ("products_from_front", ctypes.c_uint32), ("front_failed", ctypes.c_uint32),
+                ("row_kernel", _i32 * 4), ("front_ms", ctypes.c_double * 3)]
+
+    def as_dict(self):
+        names = ("bulk", "bulk_sparse", "small")
+        d = {k: int(getattr(self, k)) for k in ("chunks", "product_tiles", "row_jobs", "workers", "rows_from_front", "products_from_front", "front_failed")}
+        d["row_kernel"] = [names[k] for k in self.row_kernel if k >= 0]
+        d["front_ms"] = dict(zip(("staging", "row_sums", "products"), self.front_ms))
+        return d
+
+
+_sig("otti_nizk_prove_many", _i32, _vp, ctypes.POINTER(_vp), _sz, _vp, ctypes.c_char_p, _sz, ctypes.POINTER(_vp), ctypes.c_uint32,
+     ctypes.POINTER(_vp), ctypes.POINTER(_sz), ctypes.POINTER(_i32), ctypes.POINTER(_sz), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_ProveManyInfo))
 _sig("otti_prepare_device", _i32, _vp, _vp)
 _sig("otti_snark_gens_new", _i32, _u64, _u64, _u64, _u64, ctypes.POINTER(_vp))
 _sig("otti_snark_gens_free", None, _vp)
@@ -157,6 +172,8 @@ _sig("otti_k_fr_from_canonical", _i32, _vp, _vp, _sz)
 _sig("otti_k_addr_timestamps", _i32, _vp, _sz, _sz, _vp, _vp, _fp)
 _sig("otti_k_fr_to_canonical", _i32, _vp, _vp, _sz)
 _sig("otti_k_multiply_vec", _i32, _vp, _vp, _vp, _vp, _vp, _fp)
+_sig("otti_k_multiply_vec_many", _i32, _vp, ctypes.POINTER(_vp), _sz, _vp, _vp, _vp, _fp)
+_sig("otti_k_prove_front", _i32, _vp, _vp, ctypes.POINTER(_vp), _vp, _sz, _vp, _vp, _vp, _vp, ctypes.POINTER(_ProveManyInfo), _fp)
 _sig("otti_k_eval_table_sparse", _i32, _vp, _vp, _vp, _vp, _fp)
 _sig("otti_k_products_patch", _i32, _vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp, ctypes.POINTER(_u64), _vp, _sz, ctypes.POINTER(_u64), ctypes.POINTER(_i32), _fp)
 _sig("otti_instance_device_info", _i32, _vp, _i32, ctypes.POINTER(_DeviceInfo))
@@ -806,6 +823,39 @@ class NIZK:
         return cls(cls._take(p, n), dict(zip(STAGES, ms)))
 
     @classmethod
+    def prove_many(cls, inst, witnesses, gens, transcript_label=b"nizk_example", seeds=None, threads=0, details=False):
+        """Many resident witnesses of ONE instance proved in one call (otti_nizk_prove_many): the witness-only work of the proofs — commitment row
+        sums, Az, Bz, Cz — is formed for the batch in joint passes, the library's own ``threads`` workers (0 = its default, 4; at most 16; the
+        calling thread counts) run the rest.  ``seeds``: None, or one 32-byte seed or None per witness.  Returns a list of NIZK objects — element k
+        has the bytes ``prove(inst, witnesses[k], .., seed=seeds[k])`` gives — with None where an item failed, which raises nothing; only the call's
+        own refusals raise.  ``details=True``: (proofs, result codes, info dict) as well.  The handles are only read; one may appear several times."""
+        label = bytes(transcript_label)
+        wits = list(witnesses)
+        n = len(wits)
+        per = list(seeds) if seeds is not None else [None] * n
+        if len(per) != n:
+            raise ValueError("prove_many: one seed (or None) per witness")
+        hs, sd = (_vp * max(1, n))(), (_vp * max(1, n))()
+        keep = [_seed(x) for x in per]                            # the seed buffers live until the call returns
+        for k in range(n):
+            hs[k], sd[k] = wits[k]._h, keep[k]
+        pf, lens, res = (_vp * max(1, n))(), (_sz * max(1, n))(), (_i32 * max(1, n))()
+        failed, ms, info = _sz(0), (ctypes.c_double * (8 * max(1, n)))(), _ProveManyInfo()
+        _check(lib.otti_nizk_prove_many(inst._h, hs, n, gens._h, label, len(label), sd, threads, pf, lens, res, ctypes.byref(failed), ms, ctypes.byref(info)))
+        out = []
+        for k in range(n):
+            if res[k] == 0:
+                data = ctypes.string_at(pf[k], lens[k])
+                lib.otti_buf_free(pf[k])
+                out.append(cls(data, dict(zip(STAGES, ms[8 * k:8 * k + 8]))))
+            else:
+                assert not pf[k]
+                out.append(None)
+        codes = [int(res[k]) for k in range(n)]
+        assert failed.value == sum(1 for r in codes if r != 0)
+        return (out, codes, info.as_dict()) if details else out
+
+    @classmethod
     def prove_sharded(cls, inst, witness, gens, transcript_label=b"nizk_example", seed=None):
         """This rank's part of ONE proof spread over the GPUs of a node (collective over the ranks of ``shard_init``; every rank
         passes the same instance, resident witness, generators, label and 32-byte seed and gets the same proof bytes back)."""
@@ -1273,6 +1323,31 @@ class kernels:
         o = [np.zeros((nc, 32), dtype=np.uint8) for _ in range(3)]; ms = ctypes.c_float(0)
         _check(lib.otti_k_multiply_vec(inst._h, _ptr(z), _ptr(o[0]), _ptr(o[1]), _ptr(o[2]), ctypes.byref(ms)))
         return o[0], o[1], o[2], ms.value
+
+    @staticmethod
+    def multiply_vec_many(inst, zs):
+        """otti_k_multiply_vec_many: Az, Bz, Cz of the K vectors ``zs`` through the many-vector kernels, a tile of four per walk over the matrices.
+        Returns ((K, N, 32) Az, Bz, Cz, kernel ms)."""
+        zs = [np.ascontiguousarray(_scalars(z, "z")) for z in zs]; nc, nv, _ = inst.dims; K = len(zs)
+        assert K and all(z.shape[0] == 2 * nv for z in zs)
+        ptrs = (_vp * K)(*[_ptr(z) for z in zs])
+        o = [np.zeros((K, nc, 32), dtype=np.uint8) for _ in range(3)]; ms = ctypes.c_float(0)
+        _check(lib.otti_k_multiply_vec_many(inst._h, ptrs, K, _ptr(o[0]), _ptr(o[1]), _ptr(o[2]), ctypes.byref(ms)))
+        return o[0], o[1], o[2], ms.value
+
+    @staticmethod
+    def prove_front(inst, gens, zs, small_flags):
+        """otti_k_prove_front: prove_many's front half alone on the K staged vectors ``zs``.  Returns ((K, L, 32) compressed unblinded row sums,
+        (K, N, 32) Az, Bz, Cz, info dict, ms)."""
+        zs = [np.ascontiguousarray(_scalars(z, "z")) for z in zs]; nc, nv, _ = inst.dims; K = len(zs)
+        assert K and all(z.shape[0] == 2 * nv for z in zs) and len(small_flags) == K
+        ell = nv.bit_length() - 1; L = 1 << (ell // 2)
+        ptrs = (_vp * K)(*[_ptr(z) for z in zs])
+        flags = np.ascontiguousarray([1 if f else 0 for f in small_flags], dtype=np.int32)
+        rows = np.zeros((K, L, 32), dtype=np.uint8)
+        o = [np.zeros((K, nc, 32), dtype=np.uint8) for _ in range(3)]; ms = ctypes.c_float(0); info = _ProveManyInfo()
+        _check(lib.otti_k_prove_front(inst._h, gens._h, ptrs, _ptr(flags), K, _ptr(rows), _ptr(o[0]), _ptr(o[1]), _ptr(o[2]), ctypes.byref(info), ctypes.byref(ms)))
+        return rows, o[0], o[1], o[2], info.as_dict(), ms.value
 
     @staticmethod
     def products_patch(inst, z_new, Az, Bz, Cz, bits, n_unsat, cols=None, first=0, count=0):

@@ -437,6 +437,38 @@ int32_t otti_nizk_verify_many(const otti_instance *inst, const otti_gens *gens, 
         return OTTI_OK;
     });
 }
+// Many resident witnesses of ONE instance in one call (device.h nizk_prove_many; the contract: include/otti_spartan.h).  Everything the arguments
+// alone say is said before the handles are looked into, the generators' size before a device is asked for, and no output is written before that.
+int32_t otti_nizk_prove_many(otti_instance *inst, otti_witness *const *wits, size_t count, otti_gens *gens, const uint8_t *tlabel, size_t tlabel_len,
+                             const uint8_t *const *seeds32, uint32_t threads, uint8_t **proofs, size_t *proof_lens, int32_t *results, size_t *n_failed,
+                             double *stage_ms, otti_prove_many_info *info) {
+    return guarded([&] {
+        if (!inst || !gens) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (!proofs || !proof_lens || !results) throw Error(OTTI_ERR_BAD_ARG, "a null output array");
+        if (count && !wits) throw Error(OTTI_ERR_BAD_ARG, "a null witness array with count > 0");
+        for (size_t i = 0; i < count; i++) if (!wits[i]) throw Error(OTTI_ERR_BAD_ARG, "a null witness handle");
+        if (threads > kProveManyMaxThreads) throw Error(OTTI_ERR_BAD_ARG, "more than 16 worker threads");
+        if (!count) { if (n_failed) *n_failed = 0; return OTTI_OK; }
+        Instance &I = *inst->I; Gens &g = *gens->g;
+        {   const size_t ell = ilog2(I.num_vars);
+            if (g.num_vars_padded != I.num_vars || g.R != ((size_t)1 << (ell - ell / 2))) throw Error(OTTI_ERR_BAD_ARG, "generators were made for a different instance size"); }
+        if (otti_device_count() < 1) throw Error(OTTI_ERR_NO_DEVICE, "no device");
+        std::vector<ProveManyItem> items(count);
+        for (size_t i = 0; i < count; i++) items[i] = {wits[i]->w.get(), seeds32 ? seeds32[i] : nullptr};
+        std::vector<std::vector<uint8_t>> pf(count); std::vector<ProveTimings> tm(count);
+        otti_prove_many_info inf{};
+        nizk_prove_many(I, g, tlabel, tlabel_len, items.data(), count, threads, pf.data(), results, tm.data(), inf);
+        size_t bad = 0;
+        for (size_t i = 0; i < count; i++) {
+            if (results[i] == OTTI_OK) proofs[i] = to_malloc(pf[i], &proof_lens[i]); else { proofs[i] = nullptr; proof_lens[i] = 0; bad++; }
+            if (stage_ms) memcpy(stage_ms + 8 * i, tm[i].ms, sizeof tm[i].ms);
+        }
+        if (n_failed) *n_failed = bad;
+        if (info) *info = inf;
+        if (bad) g_last_error = std::to_string(bad) + " of " + std::to_string(count) + " proofs failed";
+        return OTTI_OK;
+    });
+}
 
 // ------------------------------------------------------------------------------------------------ SNARK mode
 int32_t otti_snark_gens_new(uint64_t nc, uint64_t nv, uint64_t ni, uint64_t nnz, otti_snark_gens **out) {

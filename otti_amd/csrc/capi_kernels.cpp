@@ -192,6 +192,55 @@ int32_t otti_k_multiply_vec(otti_instance *inst, const uint8_t *z, uint8_t *Az, 
         download(c, Az, a.p, I.num_cons); download(c, Bz, b.p, I.num_cons); download(c, Cz, d.p, I.num_cons); c.sync(); return OTTI_OK;
     });
 }
+// K staged vectors, one buffer each (what a batch of resident witnesses looks like to the many-vector kernels)
+struct StagedMany {
+    std::vector<std::unique_ptr<Staged>> v; std::vector<const Fr *> p;
+    StagedMany(DevCtx &c, const uint8_t *const *hs, size_t K, size_t n) { for (size_t k = 0; k < K; k++) { v.push_back(std::make_unique<Staged>(c, hs[k], n)); p.push_back(v.back()->d.p); } }
+};
+// dev_spmv3_many on K staged vectors, tile by tile through one interleaved table (k_sparse.hip): always the many-vector kernels, K = 1 included
+int32_t otti_k_multiply_vec_many(otti_instance *inst, const uint8_t *const *h_zs, size_t K, uint8_t *Az, uint8_t *Bz, uint8_t *Cz, float *ms) {
+    return guarded([&] {
+        if (!inst || !h_zs || !K || !Az || !Bz || !Cz) throw Error(OTTI_ERR_BAD_ARG, "null argument, or no vectors");
+        for (size_t k = 0; k < K; k++) if (!h_zs[k]) throw Error(OTTI_ERR_BAD_ARG, "a null vector");
+        DevCtx &c = DevCtx::get(); Instance &I = *inst->I; ensure_instance_device(I);
+        const size_t N = I.num_cons, V2 = 2 * I.num_vars; const DeviceCsrSet &m = I.dev->by_row;
+        StagedMany Z(c, h_zs, K, V2);
+        DevBuf<Fr> z_il(kEvalTile * V2), o[3] = {DevBuf<Fr>(K * N), DevBuf<Fr>(K * N), DevBuf<Fr>(K * N)}, seg(std::max<size_t>(1, 3 * kEvalTile * m.n_seg));
+        KTimer t(c, ms);
+        for (size_t k0 = 0; k0 < K; k0 += kEvalTile) {
+            const int nt = (int)std::min<size_t>(kEvalTile, K - k0);
+            SpmvManyOut out{};
+            for (int a = 0; a < nt; a++) { dev_interleave_slot(c, Z.p[k0 + a], V2, z_il.p, a); for (int j = 0; j < 3; j++) out.o[j][a] = o[j].p + (k0 + a) * N; }
+            dev_spmv3_many(c, m, z_il.p, nt, out, seg.p);
+        }
+        t.stop();
+        download(c, Az, o[0].p, K * N); download(c, Bz, o[1].p, K * N); download(c, Cz, o[2].p, K * N); c.sync(); return OTTI_OK;
+    });
+}
+// nizk_prove_many's front half alone (prove_many.cpp prove_front_staged): the joint row jobs and tiles the plan cuts for K witnesses that keep nothing
+int32_t otti_k_prove_front(otti_instance *inst, otti_gens *gens, const uint8_t *const *h_zs, const int32_t *small_flags, size_t K, uint8_t *h_rows32,
+                           uint8_t *Az, uint8_t *Bz, uint8_t *Cz, otti_prove_many_info *info, float *ms) {
+    return guarded([&] {
+        if (!inst || !gens || !h_zs || !small_flags || !K || !h_rows32 || !Az || !Bz || !Cz) throw Error(OTTI_ERR_BAD_ARG, "null argument, or no vectors");
+        for (size_t k = 0; k < K; k++) if (!h_zs[k]) throw Error(OTTI_ERR_BAD_ARG, "a null vector");
+        Instance &I = *inst->I; Gens &g = *gens->g;
+        {   const size_t ell = ilog2(I.num_vars);
+            if (g.num_vars_padded != I.num_vars || g.R != ((size_t)1 << (ell - ell / 2))) throw Error(OTTI_ERR_BAD_ARG, "generators were made for a different instance size"); }
+        DevCtx &c = DevCtx::get(); ensure_device_objects(I, g);
+        const size_t N = I.num_cons, V = I.num_vars, L = V / g.R;
+        StagedMany Z(c, h_zs, K, 2 * V);
+        DevBuf<Pt> rows(K * L); DevBuf<uint8_t> enc(32 * K * L);
+        DevBuf<Fr> o[3] = {DevBuf<Fr>(K * N), DevBuf<Fr>(K * N), DevBuf<Fr>(K * N)};
+        Fr *const abc[3] = {o[0].p, o[1].p, o[2].p};
+        otti_prove_many_info inf{};
+        KTimer t(c, ms); prove_front_staged(I, g, Z.p.data(), small_flags, K, rows.p, abc, inf); t.stop();
+        dev_encode_points(c, rows.p, K * L, enc.p);
+        OTTI_HIP(hipMemcpyAsync(h_rows32, enc.p, 32 * K * L, hipMemcpyDeviceToHost, c.stream));
+        download(c, Az, o[0].p, K * N); download(c, Bz, o[1].p, K * N); download(c, Cz, o[2].p, K * N); c.sync();
+        if (info) *info = inf;
+        return OTTI_OK;
+    });
+}
 // the kept-products step of DeviceWitness::z_written (witness.cpp) on a caller's host state: the same dev_products_patch, so a wrong patch points at a kernel and not at a proof
 int32_t otti_k_products_patch(otti_instance *inst, const uint8_t *h_z_new, const uint64_t *h_cols, size_t ncols, size_t first, size_t count,
                               uint8_t *io_Az, uint8_t *io_Bz, uint8_t *io_Cz, uint64_t *io_bits, uint64_t *io_unsat,

@@ -184,6 +184,7 @@ struct DevCtx {
     struct Scratch *scratch = nullptr;                        // the prover's HBM workspace (prover.cpp); travels with the context
     struct SnarkScratch *snark_scratch = nullptr;             // SNARK mode's per-proof buffers (snark_prover.h), kept across proofs like the above
     struct EvalManyScratch *eval_many = nullptr;              // the many-point instance evaluation's tables and result memory (prover.cpp), grow-only, kept likewise
+    struct ProveManyScratch *prove_many = nullptr;            // nizk_prove_many's front-half buffers (prove_many.cpp), grow-only, kept likewise
     void sync();
     void wait_points(const MsmTicket &ticket);                // results of a dev_msm_rows / dev_bullet_round launch, by the ticket's route (msm_plan.h)
     void encode_pending();
@@ -330,13 +331,30 @@ void instance_evaluate_many(Instance &I, const Fr *rx, size_t nrx, const Fr *ry,
 // other ranks of sh (collective call: same instance, witness, generators, label and seed on every rank); every rank returns the
 // same bytes, equal to the single-GPU proof.
 class ShardComm;
+struct ProveFront;
 std::vector<uint8_t> nizk_prove_resident(Instance &I, DeviceWitness &wit, Gens &g, const void *tlabel, size_t tlabel_len, const uint8_t *seed32,
-                                         ProveTimings *tm, ShardComm *sh = nullptr);
+                                         ProveTimings *tm, ShardComm *sh = nullptr, const ProveFront *front = nullptr);
+// ---- many witnesses of one instance proved in one call (prove_many.cpp; the contract: include/otti_spartan.h otti_nizk_prove_many).  Everything a
+// proof computes before its first challenge depends on the witness alone: the calling thread forms it for the whole batch in joint passes (the front
+// half: prove_many_plan.h says which) on its own stream, and `threads` workers, the calling thread among them, run the sequential halves.
+// results[i], proofs[i], tm[i] are what nizk_prove_resident gives for item i alone.  The handles are only read.
+struct ProveManyItem { DeviceWitness *wit; const uint8_t *seed32; };
+constexpr unsigned kProveManyThreads = 4, kProveManyMaxThreads = 16;      // the default is verify_many's: a process here opens four hardware queues
+void nizk_prove_many(Instance &I, Gens &g, const void *tlabel, size_t tlabel_len, const ProveManyItem *items, size_t count, unsigned threads,
+                     std::vector<uint8_t> *proofs, int32_t *results, ProveTimings *tm /* count, may be null */, otti_prove_many_info &info);
+// the front half alone on staged vectors (otti_k_prove_front): zs[k] 2V elements in HBM, small[k] the MSM variant of vector k; rows: K * L points,
+// abc[j]: K * N elements.  Synchronises.
+void prove_front_staged(Instance &I, Gens &g, const Fr *const *zs, const int32_t *small, size_t K, Pt *rows, Fr *const abc[3], otti_prove_many_info &info);
 // hooks: called on the proving thread the moment the first (rx) / second (ry) sum-check's challenges are complete — SNARK mode starts the
 // work that depends on them alone (the two halves of the dereferenced polynomial and their commitment rows) on another stream while the
 // R1CS proof goes on through its latency-bound rounds
 struct R1csHooks { std::function<void(const std::vector<Fr> &)> on_rx, on_ry; std::function<void()> on_idle; };   // on_idle: from here on the proof is short rounds only (the chip is idle between them)
-void r1cs_prove_device(Instance &I, DeviceWitness &wit, Gens &g, Transcript &tr, RandomTape &tape, NizkProof &P, ProveTimings &T, ShardComm *sh, const R1csHooks *hooks = nullptr);
+// What somebody else has formed of a proof's witness-only work, resident and complete before the proof starts (prove_many.cpp: the front half of a
+// batch): the L unblinded row sums of the commitment over the proof's generators, and Az, Bz, Cz (N canonical Montgomery words each, bit for bit
+// what dev_spmv3 writes).  A null member: the proof has its own way to that thing, as ever.  Read only; an unsharded proof alone looks at it.
+struct ProveFront { const Pt *rows = nullptr; const Fr *abc[3] = {nullptr, nullptr, nullptr}; };
+void r1cs_prove_device(Instance &I, DeviceWitness &wit, Gens &g, Transcript &tr, RandomTape &tape, NizkProof &P, ProveTimings &T, ShardComm *sh, const R1csHooks *hooks = nullptr,
+                       const ProveFront *front = nullptr);
 std::shared_ptr<DeviceShard> upload_instance_shard(const Instance &I, int rank, int world);
 // DotProductProofLog::prove on the device (prover.cpp): generator stream indices of (gens_n.h, gens_1.G[0], gens_1.h) and the row length
 struct PeBufs { Fr *LZ, *Rv, *a, *s, *b2, *s2, *rows, *extras; };      // R elements each (rows: 2 R, extras: 4 (log2 R + 1))
@@ -400,6 +418,13 @@ size_t dev_eval_partial_slots(const DeviceCsrSet &m);
 void dev_eval_point_x(DevCtx &c, const Fr *r_host, size_t ell, int t, Fr *xlo_il, Fr *xhi_il, Fr *scratch);
 void dev_eval_point_y(DevCtx &c, const Fr *r_host, size_t ell, int t, Fr *ey_il, Fr *scratch);
 void dev_eval_tile(DevCtx &c, const DeviceCsrSet &m, const EvalTables &tab, int nt, Fr *partial, Fr *seg_partial, Fr *out);
+// ---- dev_spmv3 for a tile of nt <= kEvalTile vectors in ONE walk over the by-row set (k_sparse.hip k_spmv3_many_*: every variant dev_spmv3 has).
+// z_il: the tile's vectors interleaved, z_il[col * kEvalTile + t] over all 2V columns (dev_interleave_slot writes vector t there), so one gather of a
+// column brings all the tile's values in one 128-byte run.  out.o[k][t]: matrix k's product with vector t, rows elements, canonical words bit for
+// bit as dev_spmv3 writes them; slots t >= nt are neither read nor written.  seg_partial: 3 * kEvalTile * m.n_seg elements.  Both only queue.
+struct SpmvManyOut { Fr *o[3][4]; };
+void dev_interleave_slot(DevCtx &c, const Fr *src, size_t n, Fr *dst_il, int t);
+void dev_spmv3_many(DevCtx &c, const DeviceCsrSet &m, const Fr *z_il, int nt, const SpmvManyOut &out, Fr *seg_partial);
 // ---- Instance::is_sat on the device (k_sparse.hip): per constraint row r the three sums of dev_spmv3 and <A_r,z> <B_r,z> == <C_r,z>; Az, Bz, Cz
 // are never written.  dev_sat_pass only queues: bits[r >> 6] bit (r & 63) is set for every FAILING row (all (rows + 63) / 64 words are written: no
 // zeroing beforehand), c.d_counts[0] holds their number.  dev_check_sat runs it into the context's own bitmap, reads the count through the pinned

@@ -356,6 +356,93 @@ void dev_eval_tile(DevCtx &c, const DeviceCsrSet &m, const EvalTables &tab, int 
     hipLaunchKernelGGL(k_eval_finish<KT>, 3u * KT, kBlock, 0, c.stream, (const Fr *)partial, (size_t)grid + m.n_heavy, nt, out);
 }
 
+// ------------------------------------------------------------------------------------------------ multiply_vec for a tile of vectors (device.h dev_spmv3_many)
+// Az, Bz, Cz of the nt <= KT vectors of a tile in ONE walk over the by-row set: the k_spmv3_* kernels with entry_terms / row_terms as their inner step
+// and the tile's interleaved vectors, z_il[col][KT], in ey_il's place — an entry's index, code and value are loaded once for the KT witnesses.  One
+// matrix at a time, as k_eval_light walks (KT accumulators live, not 3 KT).  Every partial sum is the canonical word (comment above row_fails), so the
+// words stored are those dev_spmv3 stores for each vector alone, whatever the geometry.  Slots t >= nt are neither read nor written.
+static_assert(kEvalTile == 4, "SpmvManyOut (device.h) holds a tile of four vectors");
+template <int KT> __device__ __forceinline__ EvalTile<KT> vec_tile(const Fr *z_il, int nt) { EvalTile<KT> T; T.xlo = T.xhi = nullptr; T.ey_il = z_il; T.xlo_bits = 0; T.nt = nt; return T; }
+// row per lane (k_spmv3_light's layout)
+template <bool kSmall, int KT> __global__ __launch_bounds__(kBlock) void k_spmv3_many_light(DCsr3 m, size_t rows, const Fr *z_il, int nt, SpmvManyOut O) {
+    const EvalTile<KT> T = vec_tile<KT>(z_il, nt);
+    for (size_t r = blockIdx.x * (size_t)blockDim.x + threadIdx.x; r < rows; r += (size_t)gridDim.x * blockDim.x) {
+        if (row_is_heavy(m, r)) continue;
+#pragma unroll 1
+        for (int k = 0; k < 3; k++) {
+            Fr acc[KT]; eval_zero<KT>(acc);
+            row_terms<kSmall, KT, 1>(m, k, r, 0, T, acc);
+#pragma unroll
+            for (int t = 0; t < KT; t++) if (t < nt) O.o[k][t][r] = acc[t];
+        }
+    }
+}
+// row per quad (k_spmv3_quad's layout, walk and padding to whole waves).  After quad_sum all four lanes of a quad hold the row's KT sums: lane q
+// stores vector q's, so a row's KT stores leave from four lanes at once.
+template <bool kSmall, int KT> __global__ __launch_bounds__(kBlock) void k_spmv3_many_quad(DCsr3 m, size_t rows, const Fr *z_il, int nt, SpmvManyOut O) {
+    static_assert(KT <= 4, "a quad's four lanes take a vector each");
+    const EvalTile<KT> T = vec_tile<KT>(z_il, nt);
+    const uint32_t q = threadIdx.x & 3;
+    for (size_t r = (blockIdx.x * (size_t)blockDim.x + threadIdx.x) >> 2; r < ((rows + 63) & ~(size_t)63); r += ((size_t)gridDim.x * blockDim.x) >> 2) {
+        const bool live = r < rows && !row_is_heavy(m, r);
+#pragma unroll 1
+        for (int k = 0; k < 3; k++) {
+            Fr acc[KT]; eval_zero<KT>(acc);
+            if (live) row_terms<kSmall, KT, 4>(m, k, r, q, T, acc);
+#pragma unroll
+            for (int t = 0; t < KT; t++) acc[t] = quad_sum(acc[t]);       // every lane of the wave takes part
+            Fr mine = acc[0]; Fr *dst = O.o[k][0];
+#pragma unroll
+            for (int t = 1; t < KT; t++) if (q == (uint32_t)t) { mine = acc[t]; dst = O.o[k][t]; }
+            if (live && (int)q < nt) dst[r] = mine;
+        }
+    }
+}
+// a long row's segment, as k_eval_heavy_seg walks it: seg_partial[(segment * 3 + k) * KT + t], raw sums
+template <bool kSmall, int KT> __global__ __launch_bounds__(kBlock) void k_spmv3_many_heavy_seg(DCsr3 m, const uint32_t *seg_row, const uint32_t *seg_no, const Fr *z_il, int nt, Fr *seg_partial) {
+    const EvalTile<KT> T = vec_tile<KT>(z_il, nt);
+    const size_t r = seg_row[blockIdx.x]; const uint32_t sn = seg_no[blockIdx.x];
+#pragma unroll 1
+    for (int k = 0; k < 3; k++) {
+        Fr acc[KT]; eval_zero<KT>(acc);
+        row_terms<kSmall, KT, kBlock>(m, k, r, threadIdx.x, T, acc, sn);
+        eval_store_partial<KT>(acc, seg_partial, blockIdx.x, k);
+    }
+}
+// one workgroup per long row adds its segments' sums up and stores the row's KT x 3 words
+template <int KT> __global__ __launch_bounds__(kBlock) void k_spmv3_many_heavy_combine(const uint32_t *heavy, const uint32_t *seg_begin, const Fr *seg_partial, int nt, SpmvManyOut O) {
+    const size_t h = blockIdx.x, r = heavy[h];
+#pragma unroll 1
+    for (int k = 0; k < 3; k++) {
+        Fr acc[KT];
+        segment_sums<KT>(seg_begin, h, seg_partial + (size_t)k * KT, 3 * KT, acc);
+        if (threadIdx.x == 0)
+#pragma unroll
+            for (int t = 0; t < KT; t++) if (t < nt) O.o[k][t][r] = acc[t];
+    }
+}
+void dev_interleave_slot(DevCtx &c, const Fr *src, size_t n, Fr *dst_il, int t) {
+    eval_slot_check(t);
+    KScope ks(c, KC_SPMV);                                    // the tile's cost beside K single passes includes putting its vectors side by side
+    hipLaunchKernelGGL(k_eval_interleave<kEvalTile>, grid_for(n), kBlock, 0, c.stream, src, n, dst_il, (const Fr *)nullptr, (size_t)0, (Fr *)nullptr, t);
+}
+void dev_spmv3_many(DevCtx &c, const DeviceCsrSet &m, const Fr *z_il, int nt, const SpmvManyOut &out, Fr *seg_partial) {
+    constexpr int KT = kEvalTile;
+    if (nt < 1 || nt > KT) throw Error(OTTI_ERR_INTERNAL, "vector tile: 1 .. kEvalTile vectors");
+    for (int k = 0; k < 3; k++) for (int t = 0; t < nt; t++) if (!out.o[k][t]) throw Error(OTTI_ERR_INTERNAL, "vector tile: a live slot without an output");
+    if (m.n_heavy && !seg_partial) throw Error(OTTI_ERR_INTERNAL, "vector tile: long rows without segment memory");
+    KScope ks(c, KC_SPMV);
+    by_layout(m, [&](auto small, auto quad) {                 // the layouts dev_spmv3 picks, for its reasons
+        constexpr bool S = decltype(small)::value, Q = decltype(quad)::value;
+        hipLaunchKernelGGL((Q ? k_spmv3_many_quad<S, KT> : k_spmv3_many_light<S, KT>), grid_for(Q ? 4 * m.rows : m.rows), kBlock, 0, c.stream, m.view(), m.rows, z_il, nt, out);
+    });
+    if (!m.n_heavy) return;
+    by_flag(m.use_small, [&](auto small) {
+        hipLaunchKernelGGL((k_spmv3_many_heavy_seg<decltype(small)::value, KT>), (unsigned)m.n_seg, kBlock, 0, c.stream, m.view(), (const uint32_t *)m.seg_row.p, (const uint32_t *)m.seg_no.p, z_il, nt, seg_partial);
+    });
+    hipLaunchKernelGGL(k_spmv3_many_heavy_combine<KT>, (unsigned)m.n_heavy, kBlock, 0, c.stream, (const uint32_t *)m.heavy.p, (const uint32_t *)m.seg_begin.p, (const Fr *)seg_partial, nt, out);
+}
+
 // ------------------------------------------------------------------------------------------------ satisfiability pass (Instance::is_sat on the device)
 // Per constraint row r: a = <A_r,z>, b = <B_r,z>, c = <C_r,z> formed exactly as the products above form them, then a b == c in GF(l).  Az, Bz and
 // Cz are never written: a row's only output is bit (r & 63) of bits[r >> 6], set when the row FAILS, and the failing rows are counted in *count.

@@ -498,7 +498,20 @@ static void host_fold_top(std::vector<Fr> &t, const Fr &r) {
 
 // R1CSProof::prove on the device.  The transcript already carries the caller's protocol name (NIZK / SNARK) and whatever that caller
 // appends before the satisfiability proof; P receives the proof and the challenges (rx, ry); T.ms[0..5] the stage times.
-void r1cs_prove_device(Instance &I, DeviceWitness &wit, Gens &g, Transcript &tr, RandomTape &tape, NizkProof &P, ProveTimings &T, ShardComm *sh, const R1csHooks *hooks) {
+// The two hand-over points of a proof's witness-only work: where the unblinded row sums / Az, Bz, Cz already are — kept with the witness (device.h
+// DeviceWitness) or formed by a batch's front half (ProveFront) — or nullptr / false: this proof forms them.  A sharded proof asks neither.
+static const Pt *rows_formed(const DeviceWitness &wit, const Gens &g, const ProveFront *front) {
+    if (wit.rows_kept_for(g)) return wit.rows_kept.p;
+    return front ? front->rows : nullptr;
+}
+static bool products_formed(const DeviceWitness &wit, const Instance &I, const ProveFront *front, const Fr *abc[3]) {
+    if (wit.products_kept_for(I)) { for (int k = 0; k < 3; k++) abc[k] = wit.prod_abc[k].p; return true; }
+    if (!front || !front->abc[0]) return false;
+    for (int k = 0; k < 3; k++) abc[k] = front->abc[k];
+    return true;
+}
+void r1cs_prove_device(Instance &I, DeviceWitness &wit, Gens &g, Transcript &tr, RandomTape &tape, NizkProof &P, ProveTimings &T, ShardComm *sh, const R1csHooks *hooks,
+                       const ProveFront *front) {
     DevCtx &c = DevCtx::get();
     ensure_device_objects(I, g);
     const DeviceInstance &DI = *I.dev; const DeviceGens &DG = *g.dev;
@@ -532,8 +545,9 @@ void r1cs_prove_device(Instance &I, DeviceWitness &wit, Gens &g, Transcript &tr,
     // ---- polycommit: DensePolynomial::commit (K8).  The witness terms of every row are summed first (no host input needed);
     // meanwhile the host draws the whole random tape (its label sequence is known in advance); the blind terms are added last.
     t0 = now_ms();
-    // (a witness that keeps its rows for these points has them already: DeviceWitness::rows_kept; a sharded proof sums its block as ever)
-    const bool rows_kept = !sh && wit.rows_kept_for(g);
+    // (a witness that keeps its rows for these points has them already: DeviceWitness::rows_kept — or a batch's front half has summed them; a
+    // sharded proof sums its block as ever)
+    const Pt *rows_kept = sh ? nullptr : rows_formed(wit, g, front);
     if (!rows_kept) {
         // several proofs in flight in this process: the chip-filling launch goes to the process's CU-masked stream, so that the other
         // proofs' rounds (tens of workgroups each) find CUs whose registers no MSM workgroup holds; ordered against this context's
@@ -572,13 +586,14 @@ void r1cs_prove_device(Instance &I, DeviceWitness &wit, Gens &g, Transcript &tr,
     OTTI_HIP(hipMemcpyAsync(S.blinds.p, blinds_vars.data() + rk * Ll, Ll * sizeof(Fr), hipMemcpyHostToDevice, c.stream));
     {
         uint32_t hbase = g.pc_n.h;
-        dev_msm_rows(c, DG, {.rows = Ll, .extra_s = S.blinds.p, .extra_base = &hbase, .n_extra = 1, .addend = rows_kept ? wit.rows_kept.p : c.msm_keep.p});
+        dev_msm_rows(c, DG, {.rows = Ll, .extra_s = S.blinds.p, .extra_base = &hbase, .n_extra = 1, .addend = rows_kept ? rows_kept : c.msm_keep.p});
         // Az, Bz, Cz do not depend on the transcript: queue them behind the commitment so that they run while the host hashes it
         OTTI_HIP(hipEventRecord(c.ev0, c.stream));
-        // (a witness that keeps its products for this instance has them already, DeviceWitness::prod_abc: copies, since the tables are folded in place;
-        // a sharded proof's rows are renumbered per rank and formed as ever)
-        if (!sh && wit.products_kept_for(I))
-            for (int k = 0; k < 3; k++) OTTI_HIP(hipMemcpyAsync(S.T[1 + k].p, wit.prod_abc[k].p, N * sizeof(Fr), hipMemcpyDeviceToDevice, c.stream));
+        // (a witness that keeps its products for this instance has them already, DeviceWitness::prod_abc, as has a proof behind a batch's front
+        // half: copies, since the tables are folded in place; a sharded proof's rows are renumbered per rank and formed as ever)
+        const Fr *abc[3];
+        if (!sh && products_formed(wit, I, front, abc))
+            for (int k = 0; k < 3; k++) OTTI_HIP(hipMemcpyAsync(S.T[1 + k].p, abc[k], N * sizeof(Fr), hipMemcpyDeviceToDevice, c.stream));
         else dev_spmv3(c, rows_set, wit.z.p, S.T[1].p, S.T[2].p, S.T[3].p, false, nullptr);
         // ... and so do the blinding commitments of every sum-check round (tape-only): one batched launch for both sum-checks
         { RandomTape::Cursor c1(tape, off_sc1), c2(tape, off_sc2); sumcheck_draw_tape(early1, c1, nrx, 4); sumcheck_draw_tape(early2, c2, nry, 3); }
@@ -835,7 +850,7 @@ void r1cs_prove_device(Instance &I, DeviceWitness &wit, Gens &g, Transcript &tr,
 }
 
 std::vector<uint8_t> nizk_prove_resident(Instance &I, DeviceWitness &wit, Gens &g, const void *tlabel, size_t tlabel_len, const uint8_t *seed32,
-                                         ProveTimings *tm, ShardComm *sh) {
+                                         ProveTimings *tm, ShardComm *sh, const ProveFront *front) {
     DevCtx &c = DevCtx::get();
     ActiveProof active;
     SpinPool::Session pool_session;                               // helper threads spin for the duration of this proof
@@ -844,7 +859,7 @@ std::vector<uint8_t> nizk_prove_resident(Instance &I, DeviceWitness &wit, Gens &
     RandomTape tape(seed32);
     NizkProof P;
     tr.append_protocol_name("Spartan NIZK proof");
-    r1cs_prove_device(I, wit, g, tr, tape, P, T, sh);
+    r1cs_prove_device(I, wit, g, tr, tape, P, T, sh, nullptr, front);
     std::vector<uint8_t> out = P.serialize();
     T.ms[6] = now_ms() - t_start;
     OTTI_HIP(hipStreamSynchronize(c.stream));                    // already drained: every result above was waited for
