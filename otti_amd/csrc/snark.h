@@ -6,7 +6,7 @@
 // k_snark.hip; the R1CS satisfiability proof inside it is the same device code as NIZK mode (prover.cpp r1cs_prove_device).
 #pragma once
 #include "spartan.h"
-#include "cpu_relax.h"
+#include "verify.h"
 #include <algorithm>
 #include <vector>
 #include <system_error>
@@ -73,86 +73,6 @@ void append_evals4(Transcript &tr, const Evals4 &e, bool col);          // the f
 Fr reduce_evals(std::vector<Fr> v, const std::vector<Fr> &ch);          // the n-to-1 reduction of claimed evaluations: bound_poly_var_bot, last challenge first
 // host verifier (snark_host.cpp): SNARK::verify
 int snark_verify(const CompComm &comm, const std::vector<Fr> &inputs, const SnarkGens &g, const void *tlabel, size_t tlabel_len, const uint8_t *proof, size_t proof_len);
-// R1CSProof::verify shared with NIZK mode (spartan_host.cpp): returns 0 and the challenges
-int r1cs_verify_host(const NizkProof &P, size_t N, size_t V, const std::vector<Fr> &inputs, const Fr inst_evals[3], const Gens &g, Transcript &tr,
-                     std::vector<Fr> &rx, std::vector<Fr> &ry, const InstEvalFetch *fetch = nullptr);
-
-// verifier building blocks shared with NIZK mode (spartan_host.cpp)
-struct VerifyFail { int code; };
-Pt dec(const CPoint &c);                                     // throws VerifyFail{OTTI_ERR_VERIFY_DECOMPRESS}
-void require(bool ok);                                       // throws VerifyFail{OTTI_ERR_VERIFY_INTERNAL}
-Pt host_msm_wide(const Fr *sc, const Pt *pts, size_t n);
-// sum_i s[i] * decode(C[i]) over the row commitments of a polynomial commitment (PolyEvalProof::verify's C_LZ).  Construct it as soon as
-// the commitments are known (with a device their decompression starts right away, spartan.h RowSumBeginHook), call finish() when the
-// scalars are; without a device, or when it declines, both steps run on the host cores inside finish().  Throws VerifyFail.
-struct RowSum {
-    RowSumJob *job = nullptr; const CPoint *C; size_t n;
-    RowSum(const CPoint *C_, size_t n_);
-    RowSum(const RowSum &) = delete; RowSum &operator=(const RowSum &) = delete;
-    ~RowSum();
-    Pt finish(const Fr *s);
-};
-// Group equations that do not feed the transcript — most of the verifier's arithmetic: per sum-check round two checks with a
-// variable-base scalar multiplication each — are handed to a few background threads AS THEY ARISE, while the calling thread walks on
-// through the rounds (whose hashed commitments are the sequential path); finish() drains what is left and reports the first failure — the
-// failing check that was handed over EARLIEST, whichever thread found its failure first: a proof with several defects gets one code, the same in
-// every run and beside any number of other verifiers (verify_many.cpp holds its results against the single verifier's, code for code).
-// Lock-free: the producer fills a slot and bumps `count`; workers claim slots with a compare-exchange on `next`.
-class Deferred {
-public:
-    // workers < 0: the default rule below.  0: no threads at all — everything handed over runs in finish(), on the thread that calls it (a proof
-    // parked between the steps of snark_verify_many owns no thread); the failure reported is the same either way.
-    explicit Deferred(int workers = -1) {
-        const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-        unsigned nw = hw >= 12 ? 6 : hw >= 6 ? hw - 3 : 0;                // beside the caller and its spinning helpers (pool.h)
-        if (const char *e = getenv("OTTI_VERIFY_THREADS")) { int v = atoi(e); if (v >= 0 && v <= 32) nw = (unsigned)v; }
-        if (workers >= 0) nw = (unsigned)workers;
-        try { for (unsigned i = 0; i < nw; i++) th_.emplace_back([this] { work(false); }); } catch (const std::system_error &) {}
-    }
-    Deferred(const Deferred &) = delete; Deferred &operator=(const Deferred &) = delete;
-    ~Deferred() { closing_.store(true, std::memory_order_release); for (auto &t : th_) t.join(); }
-    void push_back(std::function<void()> f) {
-        const size_t c = count_.load(std::memory_order_relaxed);
-        if (c >= kSlots) { run_one(f, kSlots); return; }                          // (never in practice: two checks per round, at most 2 x 64 rounds + a few)
-        items_[c] = std::move(f);
-        count_.store(c + 1, std::memory_order_release);
-    }
-    void finish() {                                                       // throws VerifyFail
-        closing_.store(true, std::memory_order_release);
-        work(true);
-        for (auto &t : th_) t.join();
-        th_.clear();
-        if (const uint64_t f = first_.load()) throw VerifyFail{(int)(int32_t)(uint32_t)f};
-    }
-private:
-    static constexpr size_t kSlots = 512;
-    std::function<void()> items_[kSlots];
-    std::atomic<size_t> count_{0}, next_{0};
-    std::atomic<bool> closing_{false};
-    std::atomic<uint64_t> first_{0};                                      // 0: no failure; else (slot + 1) << 32 | code of the failure in the lowest slot
-    std::vector<std::thread> th_;
-    void failed(size_t slot, int code) {
-        const uint64_t mine = ((uint64_t)(slot + 1) << 32) | (uint32_t)code;
-        uint64_t cur = first_.load(std::memory_order_relaxed);
-        while ((cur == 0 || mine < cur) && !first_.compare_exchange_weak(cur, mine, std::memory_order_acq_rel)) {}
-    }
-    void run_one(const std::function<void()> &f, size_t slot) {
-        try { f(); } catch (const VerifyFail &e) { failed(slot, e.code); } catch (...) { failed(slot, (int)OTTI_ERR_VERIFY_INTERNAL); }
-    }
-    void work(bool until_empty) {
-        for (;;) {
-            size_t i = next_.load(std::memory_order_relaxed);
-            if (i < count_.load(std::memory_order_acquire)) { if (next_.compare_exchange_weak(i, i + 1, std::memory_order_acq_rel)) run_one(items_[i], i); continue; }
-            if (until_empty || closing_.load(std::memory_order_acquire)) { if (next_.load() >= count_.load(std::memory_order_acquire)) return; continue; }
-            cpu_relax();
-        }
-    }
-};
-void dotproductlog_verify(const DotProductProofLog &pf, size_t n, const Gens &g, const PcView &v, Transcript &tr, const Fr *a, const CPoint &Cx, const CPoint &Cy, Deferred *later = nullptr);
-// RowSum's host path alone: decompression and Pippenger on the host cores.  wide: striped over up to 16 threads of its own (the single verifier);
-// otherwise on the calling thread alone (snark_verify_many's workers are the parallelism there).  Throws VerifyFail{OTTI_ERR_VERIFY_DECOMPRESS}.
-Pt row_sum_on_host(const CPoint *C, size_t n, const Fr *s, bool wide);
-
 // R1CSEvalProof::verify as a resumable walk.  Its three variable-base row sums (PolyEvalProof::verify's C_LZ of the derefs, ops and mem
 // evaluation proofs, in that order) are the seams: a step ends by NAMING its sum (points and scalars, both alive until the next step has begun) and
 // the next step begins with the answer — the point, or the decompress failure, which it throws where RowSum::finish would have.  Between steps

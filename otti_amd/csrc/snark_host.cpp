@@ -35,130 +35,6 @@ std::unique_ptr<SnarkGens> snark_gens_new(size_t num_cons, size_t num_vars, size
     return g;
 }
 
-// ================================================================================================ wire forms (bincode)
-namespace {
-struct Writer {
-    std::vector<uint8_t> b;
-    void raw(const void *p, size_t n) { const uint8_t *q = (const uint8_t *)p; b.insert(b.end(), q, q + n); }
-    void u64(uint64_t x) { uint8_t t[8]; for (int i = 0; i < 8; i++) { t[i] = (uint8_t)x; x >>= 8; } raw(t, 8); }
-    void pt(const CPoint &c) { raw(c.b, 32); }
-    void fr(const Fr &x) { raw(x.v, 32); }                      // upstream serialises Scalar's Montgomery limbs
-    void pts(const std::vector<CPoint> &v) { u64(v.size()); for (auto &c : v) pt(c); }
-    void frs(const Fr *v, size_t n) { u64(n); for (size_t i = 0; i < n; i++) fr(v[i]); }
-    void frs(const std::vector<Fr> &v) { frs(v.data(), v.size()); }
-    void evals4(const Evals4 &e) { fr(e.init); frs(e.read, 3); frs(e.write, 3); fr(e.audit); }
-    void batch(const ProductCircuitEvalProofBatched &p) {
-        u64(p.layers.size());
-        for (auto &L : p.layers) { u64(L.coeffs.size() / 3); for (size_t j = 0; j < L.coeffs.size() / 3; j++) frs(&L.coeffs[3 * j], 3); frs(L.left); frs(L.right); }
-        frs(p.dotp_left); frs(p.dotp_right); frs(p.dotp_weight);
-    }
-    void dplog(const DotProductProofLog &d) { pts(d.L_vec); pts(d.R_vec); pt(d.delta); pt(d.beta); fr(d.z1); fr(d.z2); }
-    void sc(const ZKSumcheckProof &s) {
-        pts(s.comm_polys); pts(s.comm_evals); u64(s.proofs.size());
-        for (auto &d : s.proofs) { pt(d.delta); pt(d.beta); frs(d.z); fr(d.z_delta); fr(d.z_beta); }
-    }
-};
-struct Reader {
-    const uint8_t *p; size_t n, pos = 0;
-    void need(size_t k) { if (pos + k > n) throw Error(OTTI_ERR_MALFORMED_PROOF, "proof truncated"); }
-    uint64_t u64() { need(8); uint64_t x = 0; for (int i = 7; i >= 0; i--) x = (x << 8) | p[pos + i]; pos += 8; return x; }
-    CPoint pt() { need(32); CPoint c; memcpy(c.b, p + pos, 32); pos += 32; return c; }
-    Fr fr() { need(32); Fr x; memcpy(x.v, p + pos, 32); pos += 32; if (!fr_raw_is_canonical(x.v)) throw Error(OTTI_ERR_MALFORMED_PROOF, "scalar out of range"); return x; }
-    size_t len(size_t max) { uint64_t k = u64(); if (k > max) throw Error(OTTI_ERR_MALFORMED_PROOF, "vector length out of range"); return (size_t)k; }
-    std::vector<CPoint> pts(size_t max) { size_t k = len(max); std::vector<CPoint> v(k); for (auto &c : v) c = pt(); return v; }
-    std::vector<Fr> frs(size_t max) { size_t k = len(max); std::vector<Fr> v(k); for (auto &x : v) x = fr(); return v; }
-    void frs_fixed(Fr *v, size_t k) { if (u64() != k) throw Error(OTTI_ERR_MALFORMED_PROOF, "vector length"); for (size_t i = 0; i < k; i++) v[i] = fr(); }
-    void evals4(Evals4 &e) { e.init = fr(); frs_fixed(e.read, 3); frs_fixed(e.write, 3); e.audit = fr(); }
-    ProductCircuitEvalProofBatched batch() {
-        ProductCircuitEvalProofBatched p; p.layers.resize(len(64));
-        for (auto &L : p.layers) {
-            size_t rounds = len(64); L.coeffs.resize(3 * rounds);
-            for (size_t j = 0; j < rounds; j++) frs_fixed(&L.coeffs[3 * j], 3);
-            L.left = frs(64); L.right = frs(64);
-            if (L.left.size() != L.right.size()) throw Error(OTTI_ERR_MALFORMED_PROOF, "layer claims");
-        }
-        p.dotp_left = frs(64); p.dotp_right = frs(64); p.dotp_weight = frs(64);
-        if (p.dotp_left.size() != p.dotp_right.size() || p.dotp_left.size() != p.dotp_weight.size()) throw Error(OTTI_ERR_MALFORMED_PROOF, "dot-product claims");
-        return p;
-    }
-    DotProductProofLog dplog() {
-        DotProductProofLog d; d.L_vec = pts(64); d.R_vec = pts(64); d.delta = pt(); d.beta = pt(); d.z1 = fr(); d.z2 = fr();
-        if (d.L_vec.size() != d.R_vec.size()) throw Error(OTTI_ERR_MALFORMED_PROOF, "bullet reduction vectors");
-        return d;
-    }
-    ZKSumcheckProof sc() {
-        ZKSumcheckProof s; s.comm_polys = pts(64); s.comm_evals = pts(64); size_t k = len(64); s.proofs.resize(k);
-        for (auto &d : s.proofs) { d.delta = pt(); d.beta = pt(); d.z = frs(4); d.z_delta = fr(); d.z_beta = fr(); }
-        return s;
-    }
-};
-void write_r1cs(Writer &w, const NizkProof &P) {                 // R1CSProof's fields, as NizkProof::serialize writes them (without rx, ry)
-    w.pts(P.comm_vars); w.sc(P.sc1);
-    for (int i = 0; i < 4; i++) w.pt(P.claims_phase2[i]);
-    w.pt(P.pok.alpha); w.fr(P.pok.z1); w.fr(P.pok.z2);
-    w.pt(P.prod.alpha); w.pt(P.prod.beta); w.pt(P.prod.delta); for (int i = 0; i < 5; i++) w.fr(P.prod.z[i]);
-    w.pt(P.eq1.alpha); w.fr(P.eq1.z);
-    w.sc(P.sc2);
-    w.pt(P.comm_vars_at_ry);
-    w.dplog(P.polyeval);
-    w.pt(P.eq2.alpha); w.fr(P.eq2.z);
-}
-void read_r1cs(Reader &r, NizkProof &P) {
-    P.comm_vars = r.pts((size_t)1 << 20); P.sc1 = r.sc();
-    for (int i = 0; i < 4; i++) P.claims_phase2[i] = r.pt();
-    P.pok.alpha = r.pt(); P.pok.z1 = r.fr(); P.pok.z2 = r.fr();
-    P.prod.alpha = r.pt(); P.prod.beta = r.pt(); P.prod.delta = r.pt(); for (int i = 0; i < 5; i++) P.prod.z[i] = r.fr();
-    P.eq1.alpha = r.pt(); P.eq1.z = r.fr();
-    P.sc2 = r.sc();
-    P.comm_vars_at_ry = r.pt();
-    P.polyeval = r.dplog();
-    P.eq2.alpha = r.pt(); P.eq2.z = r.fr();
-}
-}  // namespace
-
-std::vector<uint8_t> CompComm::serialize() const {
-    Writer w;
-    w.u64(num_cons); w.u64(num_vars); w.u64(num_inputs); w.u64(batch_size); w.u64(num_ops); w.u64(num_mem_cells);
-    w.pts(comm_ops); w.pts(comm_mem);
-    return std::move(w.b);
-}
-std::unique_ptr<CompComm> CompComm::parse(const uint8_t *p, size_t n) {
-    Reader r{p, n}; auto c = std::make_unique<CompComm>();
-    c->num_cons = r.u64(); c->num_vars = r.u64(); c->num_inputs = r.u64(); c->batch_size = r.u64(); c->num_ops = r.u64(); c->num_mem_cells = r.u64();
-    c->comm_ops = r.pts((size_t)1 << 24); c->comm_mem = r.pts((size_t)1 << 24);
-    if (r.pos != n || c->batch_size != 3) throw Error(OTTI_ERR_MALFORMED_PROOF, "malformed computation commitment");
-    return c;
-}
-std::vector<uint8_t> SnarkProof::serialize() const {
-    Writer w;
-    write_r1cs(w, r1cs);
-    for (int k = 0; k < 3; k++) w.fr(inst_evals[k]);
-    const EvalProof &E = eval;
-    w.pts(E.comm_derefs);
-    w.evals4(E.eval_row); w.evals4(E.eval_col); w.frs(E.dotp_left, 3); w.frs(E.dotp_right, 3);
-    w.batch(E.proof_mem); w.batch(E.proof_ops);
-    w.frs(E.h_row_addr, 3); w.frs(E.h_row_read_ts, 3); w.fr(E.h_row_audit);
-    w.frs(E.h_col_addr, 3); w.frs(E.h_col_read_ts, 3); w.fr(E.h_col_audit);
-    w.frs(E.h_val, 3); w.frs(E.h_deref_row, 3); w.frs(E.h_deref_col, 3);
-    w.dplog(E.pe_ops); w.dplog(E.pe_mem); w.dplog(E.pe_derefs);
-    return std::move(w.b);
-}
-SnarkProof SnarkProof::parse(const uint8_t *p, size_t n) {
-    Reader r{p, n}; SnarkProof S;
-    read_r1cs(r, S.r1cs);
-    for (int k = 0; k < 3; k++) S.inst_evals[k] = r.fr();
-    EvalProof &E = S.eval;
-    E.comm_derefs = r.pts((size_t)1 << 24);
-    r.evals4(E.eval_row); r.evals4(E.eval_col); r.frs_fixed(E.dotp_left, 3); r.frs_fixed(E.dotp_right, 3);
-    E.proof_mem = r.batch(); E.proof_ops = r.batch();
-    r.frs_fixed(E.h_row_addr, 3); r.frs_fixed(E.h_row_read_ts, 3); E.h_row_audit = r.fr();
-    r.frs_fixed(E.h_col_addr, 3); r.frs_fixed(E.h_col_read_ts, 3); E.h_col_audit = r.fr();
-    r.frs_fixed(E.h_val, 3); r.frs_fixed(E.h_deref_row, 3); r.frs_fixed(E.h_deref_col, 3);
-    E.pe_ops = r.dplog(); E.pe_mem = r.dplog(); E.pe_derefs = r.dplog();
-    if (r.pos != n) throw Error(OTTI_ERR_MALFORMED_PROOF, "trailing bytes after proof");
-    return S;
-}
-
 // ================================================================================================ verifier
 // the transcript writers the GPU prover shares with this verifier (snark.h; append_poly_commitment: spartan.h)
 void append_unipoly(Transcript &tr, const Fr *c, size_t n) {

@@ -66,12 +66,8 @@ void snark_verify_many(const CompComm &comm, const SnarkGens &g, const void *tla
         for (size_t i = c0; i < c1; i++) {
             const VerifyItem &it = items[i];
             try {
-                if (!it.proof || (it.ninputs && !it.inputs32)) { results[i] = OTTI_ERR_BAD_ARG; continue; }
-                auto L = std::make_unique<Live>(); L->item = i; L->inputs.resize(it.ninputs);
-                bool canonical = true;
-                for (size_t j = 0; j < it.ninputs && canonical; j++) canonical = fr_from_bytes(L->inputs[j], it.inputs32 + 32 * j);
-                if (!canonical) { results[i] = OTTI_ERR_INVALID_SCALAR; continue; }
-                if (it.ninputs != comm.num_inputs) { results[i] = OTTI_ERR_INVALID_NUM_INPUTS; continue; }
+                auto L = std::make_unique<Live>(); L->item = i;
+                if (int rc = item_inputs(it, comm.num_inputs, L->inputs)) { results[i] = rc; continue; }
                 if (comm.num_cons != g.num_cons || comm.num_vars != g.num_vars) { results[i] = OTTI_ERR_VERIFY_INTERNAL; continue; }
                 L->S = SnarkProof::parse(it.proof, it.proof_len);
                 results[i] = OTTI_ERR_INTERNAL;               // until a step has written the verdict

@@ -1,7 +1,8 @@
 // Host-side objects of the proving path: instance building, generator derivation, proof (de)serialisation, sigma protocols,
 // verifier, synthetic instances.  See spartan.h for what each piece replaces upstream.
 #include "spartan.h"
-#include "snark.h"
+#include "verify.h"
+#include "hostpar.h"
 #include "pool.h"
 #include <algorithm>
 #include <chrono>
@@ -45,10 +46,7 @@ std::unique_ptr<Instance> instance_new(size_t num_cons, size_t num_vars, size_t 
                 m.row[i] = (uint32_t)e.row; m.col[i] = (uint32_t)col; m.val[i] = v;
             }
         };
-        std::vector<std::thread> th;
-        for (unsigned t = 1; t < nt; t++) th.emplace_back(work, t);
-        work(0);
-        for (auto &x : th) x.join();
+        fan_out(nt, work);
         for (unsigned t = 0; t < nt; t++) if (bad_at[t] != SIZE_MAX) {
             const otti_entry &e = src[k][bad_at[t]];
             if (e.row >= num_cons) throw Error(OTTI_ERR_INVALID_INDEX, "row index out of range");
@@ -123,10 +121,7 @@ std::vector<Pt> derive_generators(const char *label, size_t count) {
     std::vector<Pt> out(count);
     const unsigned nt = count < 64 ? 1u : std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
     auto work = [&](unsigned t) { for (size_t i = count * t / nt; i < count * (t + 1) / nt; i++) out[i] = pt_from_uniform_bytes(&u[64 * i]); };
-    std::vector<std::thread> th;
-    for (unsigned t = 1; t < nt; t++) th.emplace_back(work, t);
-    work(0);
-    for (auto &x : th) x.join();
+    fan_out(nt, work);
     return out;
 }
 
@@ -151,11 +146,8 @@ std::unique_ptr<Gens> gens_new(size_t num_cons, size_t num_vars, size_t num_inpu
         g->small_slot[idx] = (int)g->small_tables.size();
         g->small_tables.emplace_back(); uniq.push_back(idx);
     }
-    {   // the host window tables of these (up to seven) points are independent builds
-        std::vector<std::thread> th;
-        for (size_t idx : uniq) { Gens *gp = g.get(); th.emplace_back([gp, idx] { gp->small_tables[gp->small_slot[idx]].build(gp->P[idx]); }); }
-        for (auto &x : th) x.join();
-    }
+    // the host window tables of these (up to seven) points are independent builds
+    fan_out((unsigned)uniq.size(), [&](unsigned t) { const size_t idx = uniq[t]; g->small_tables[g->small_slot[idx]].build(g->P[idx]); });
     return g;
 }
 
@@ -324,72 +316,8 @@ void sumcheck_round_finish(ZKSumcheckProof &pf, size_t j, const RoundPart1 &p1, 
     st.claim = eval; st.comm_claim = comm_eval; pf.comm_evals[j] = comm_eval;
 }
 
-// ================================================================================================ bincode layout
-namespace {
-struct Writer {
-    std::vector<uint8_t> b;
-    void raw(const void *p, size_t n) { const uint8_t *q = (const uint8_t *)p; b.insert(b.end(), q, q + n); }
-    void u64(uint64_t x) { uint8_t t[8]; for (int i = 0; i < 8; i++) { t[i] = (uint8_t)x; x >>= 8; } raw(t, 8); }
-    void pt(const CPoint &c) { raw(c.b, 32); }
-    void fr(const Fr &x) { raw(x.v, 32); }                      // upstream serialises Scalar's Montgomery limbs
-    void pts(const std::vector<CPoint> &v) { u64(v.size()); for (auto &c : v) pt(c); }
-    void frs(const std::vector<Fr> &v) { u64(v.size()); for (auto &x : v) fr(x); }
-    void sc(const ZKSumcheckProof &s) {
-        pts(s.comm_polys); pts(s.comm_evals); u64(s.proofs.size());
-        for (auto &d : s.proofs) { pt(d.delta); pt(d.beta); frs(d.z); fr(d.z_delta); fr(d.z_beta); }
-    }
-};
-struct Reader {
-    const uint8_t *p; size_t n, pos = 0;
-    void need(size_t k) { if (pos + k > n) throw Error(OTTI_ERR_MALFORMED_PROOF, "proof truncated"); }
-    uint64_t u64() { need(8); uint64_t x = 0; for (int i = 7; i >= 0; i--) x = (x << 8) | p[pos + i]; pos += 8; return x; }
-    CPoint pt() { need(32); CPoint c; memcpy(c.b, p + pos, 32); pos += 32; return c; }
-    Fr fr() { need(32); Fr x; memcpy(x.v, p + pos, 32); pos += 32; if (!fr_raw_is_canonical(x.v)) throw Error(OTTI_ERR_MALFORMED_PROOF, "scalar out of range"); return x; }
-    size_t len(size_t max) { uint64_t k = u64(); if (k > max) throw Error(OTTI_ERR_MALFORMED_PROOF, "vector length out of range"); return (size_t)k; }
-    std::vector<CPoint> pts(size_t max) { size_t k = len(max); std::vector<CPoint> v(k); for (auto &c : v) c = pt(); return v; }
-    std::vector<Fr> frs(size_t max) { size_t k = len(max); std::vector<Fr> v(k); for (auto &x : v) x = fr(); return v; }
-    ZKSumcheckProof sc() {
-        ZKSumcheckProof s; s.comm_polys = pts(64); s.comm_evals = pts(64); size_t k = len(64); s.proofs.resize(k);
-        for (auto &d : s.proofs) { d.delta = pt(); d.beta = pt(); d.z = frs(4); d.z_delta = fr(); d.z_beta = fr(); }
-        return s;
-    }
-};
-}  // namespace
-
-std::vector<uint8_t> NizkProof::serialize() const {
-    Writer w;
-    w.pts(comm_vars); w.sc(sc1);
-    for (int i = 0; i < 4; i++) w.pt(claims_phase2[i]);
-    w.pt(pok.alpha); w.fr(pok.z1); w.fr(pok.z2);
-    w.pt(prod.alpha); w.pt(prod.beta); w.pt(prod.delta); for (int i = 0; i < 5; i++) w.fr(prod.z[i]);
-    w.pt(eq1.alpha); w.fr(eq1.z);
-    w.sc(sc2);
-    w.pt(comm_vars_at_ry);
-    w.pts(polyeval.L_vec); w.pts(polyeval.R_vec); w.pt(polyeval.delta); w.pt(polyeval.beta); w.fr(polyeval.z1); w.fr(polyeval.z2);
-    w.pt(eq2.alpha); w.fr(eq2.z);
-    w.frs(rx); w.frs(ry);
-    return std::move(w.b);
-}
-
-NizkProof NizkProof::parse(const uint8_t *p, size_t n) {
-    Reader r{p, n}; NizkProof P;
-    P.comm_vars = r.pts((size_t)1 << 20); P.sc1 = r.sc();
-    for (int i = 0; i < 4; i++) P.claims_phase2[i] = r.pt();
-    P.pok.alpha = r.pt(); P.pok.z1 = r.fr(); P.pok.z2 = r.fr();
-    P.prod.alpha = r.pt(); P.prod.beta = r.pt(); P.prod.delta = r.pt(); for (int i = 0; i < 5; i++) P.prod.z[i] = r.fr();
-    P.eq1.alpha = r.pt(); P.eq1.z = r.fr();
-    P.sc2 = r.sc();
-    P.comm_vars_at_ry = r.pt();
-    P.polyeval.L_vec = r.pts(64); P.polyeval.R_vec = r.pts(64); P.polyeval.delta = r.pt(); P.polyeval.beta = r.pt();
-    P.polyeval.z1 = r.fr(); P.polyeval.z2 = r.fr();
-    P.eq2.alpha = r.pt(); P.eq2.z = r.fr();
-    P.rx = r.frs(64); P.ry = r.frs(64);
-    if (r.pos != n) throw Error(OTTI_ERR_MALFORMED_PROOF, "trailing bytes after proof");
-    return P;
-}
-
 // ================================================================================================ verifier
-// (external linkage: snark_host.cpp builds SNARK::verify from the same pieces; declared in snark.h)
+// (the pieces other files build their verifiers from are declared in verify.h)
 Pt dec(const CPoint &c) { Pt p; if (!pt_decode_fast(p, c.b)) throw VerifyFail{OTTI_ERR_VERIFY_DECOMPRESS}; return p; }
 void require(bool ok) { if (!ok) throw VerifyFail{OTTI_ERR_VERIFY_INTERNAL}; }
 Pt commit_scalar_pt(const Gens &g, const GensView &g1, const Fr &x, const Fr &blind) { return g.commit_generic(&x, 1, blind, g1); }
@@ -399,11 +327,8 @@ Pt commit_scalar_pt(const Gens &g, const GensView &g1, const Fr &x, const Fr &bl
 Pt host_msm_wide(const Fr *sc, const Pt *pts, size_t n) {
     const size_t nt = std::min<size_t>({n / 128, (size_t)16, (size_t)std::max(1u, std::thread::hardware_concurrency())});
     if (nt < 2) return host_msm(sc, pts, n);
-    std::vector<Pt> part(nt); std::vector<std::thread> th;
-    auto work = [&](size_t t) { size_t lo = n * t / nt, hi = n * (t + 1) / nt; part[t] = host_msm(sc + lo, pts + lo, hi - lo); };
-    for (size_t t = 1; t < nt; t++) th.emplace_back(work, t);
-    work(0);
-    for (auto &x : th) x.join();
+    std::vector<Pt> part(nt);
+    fan_out((unsigned)nt, [&](size_t t) { size_t lo = n * t / nt, hi = n * (t + 1) / nt; part[t] = host_msm(sc + lo, pts + lo, hi - lo); });
     Pt acc = part[0]; for (size_t t = 1; t < nt; t++) acc = pt_add(acc, part[t]);
     return acc;
 }
@@ -428,11 +353,8 @@ Pt row_sum_on_host(const CPoint *C, size_t n, const Fr *s, bool wide) {
     if (!wide) { for (size_t i = 0; i < n; i++) Cs[i] = dec(C[i]); return host_msm(s, Cs.data(), n); }
     {   // decompression of the row commitments (an inverse square root each), striped over the host cores
         const size_t nt = std::min<size_t>({n / 64 + 1, (size_t)16, (size_t)std::max(1u, std::thread::hardware_concurrency())});
-        std::vector<int> bad(nt, 0); std::vector<std::thread> th;
-        auto work = [&](size_t t) { try { for (size_t i = t; i < n; i += nt) Cs[i] = dec(C[i]); } catch (const VerifyFail &f) { bad[t] = f.code; } };
-        for (size_t t = 1; t < nt; t++) th.emplace_back(work, t);
-        work(0);
-        for (auto &x : th) x.join();
+        std::vector<int> bad(nt, 0);
+        fan_out((unsigned)nt, [&](size_t t) { try { for (size_t i = t; i < n; i += nt) Cs[i] = dec(C[i]); } catch (const VerifyFail &f) { bad[t] = f.code; } });
         for (int b : bad) if (b) throw VerifyFail{b};
     }
     return host_msm_wide(s, Cs.data(), n);
@@ -697,13 +619,7 @@ int nizk_verify_parsed(const Instance &I, const std::vector<Fr> &inputs, const G
 // f(i) for i in [0, n) on the host's cores (every index independent: the result does not depend on the split); large instances only
 template <class F> static void host_par_for(size_t n, F &&f) {
     unsigned nt = n < ((size_t)1 << 16) ? 1u : std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-    std::vector<std::thread> th;
-    auto run = [&](unsigned t) { for (size_t i = n * t / nt, e = n * (t + 1) / nt; i < e; i++) f(i); };
-    unsigned started = 1;
-    for (; started < nt; started++) { try { th.emplace_back(run, started); } catch (const std::system_error &) { break; } }
-    run(0);
-    for (unsigned t = started; t < nt; t++) run(t);
-    for (auto &x : th) x.join();
+    fan_out(nt, [&](unsigned t) { for (size_t i = n * t / nt, e = n * (t + 1) / nt; i < e; i++) f(i); });
 }
 
 void synth_r1cs(size_t n, size_t ni, uint64_t seed, std::vector<otti_entry> &A, std::vector<otti_entry> &B, std::vector<otti_entry> &C,

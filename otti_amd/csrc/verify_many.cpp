@@ -1,6 +1,7 @@
 // Many NIZK proofs of one instance verified in one call (spartan.h nizk_verify_many).  Host code only: the batched evaluation of A, B, C at the
 // proofs' points is reached through two hooks that prover.cpp sets, so the CPU rebuilds of the host sources compile this file as it is.
 #include "spartan.h"
+#include "verify.h"
 #include <atomic>
 #include <condition_variable>
 #include <memory>
@@ -38,12 +39,8 @@ void nizk_verify_many(const Instance &I, const Gens &g, const void *tlabel, size
     for (size_t i = 0; i < count; i++) {
         const VerifyItem &it = items[i];
         try {
-            if (!it.proof || (it.ninputs && !it.inputs32)) { results[i] = OTTI_ERR_BAD_ARG; continue; }
-            auto L = std::make_unique<Live>(); L->item = i; L->inputs.resize(it.ninputs);
-            bool canonical = true;
-            for (size_t j = 0; j < it.ninputs && canonical; j++) canonical = fr_from_bytes(L->inputs[j], it.inputs32 + 32 * j);
-            if (!canonical) { results[i] = OTTI_ERR_INVALID_SCALAR; continue; }
-            if (it.ninputs != I.num_inputs) { results[i] = OTTI_ERR_INVALID_NUM_INPUTS; continue; }
+            auto L = std::make_unique<Live>(); L->item = i;
+            if (int rc = item_inputs(it, I.num_inputs, L->inputs)) { results[i] = rc; continue; }
             L->P = NizkProof::parse(it.proof, it.proof_len);
             if (L->P.rx.size() != nrx || L->P.ry.size() != nry) { results[i] = OTTI_ERR_VERIFY_INTERNAL; continue; }
             results[i] = OTTI_ERR_INTERNAL;                   // until its worker has written the verdict

@@ -9,6 +9,7 @@
 // Variables{variable_ids: [u64], values: [u8], info}.  Files are concatenations of size-prefixed buffers with identifier "zkif".
 #include "spartan.h"
 #include "zkif.h"
+#include "hostpar.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <fcntl.h>
@@ -254,19 +255,6 @@ static uint8_t *copy_bytes(const std::vector<uint8_t> &v) {
     uint8_t *p = (uint8_t *)malloc(std::max<size_t>(1, v.size()));
     if (!v.empty()) memcpy(p, v.data(), v.size());
     return p;
-}
-
-// run f(0 .. nt) on nt threads (the caller's included).  A thread that cannot be started (EAGAIN under a pids cgroup or
-// RLIMIT_NPROC) must not unwind through joinable std::threads (std::terminate): the shares that found no thread run here instead.
-template <class F> static void fan_out(unsigned nt, F &&f) {
-    std::vector<std::thread> th; th.reserve(nt);
-    unsigned started = 1;
-    for (; started < nt; started++) {
-        try { th.emplace_back(f, started); } catch (const std::system_error &) { break; }
-    }
-    f(0u);
-    for (unsigned t = started; t < nt; t++) f(t);
-    for (auto &x : th) x.join();
 }
 
 otti_r1cs *otti_r1cs_from(size_t nc, size_t nv, size_t ni, const std::vector<otti_entry> &A, const std::vector<otti_entry> &B,

@@ -1,8 +1,8 @@
 """A proof's field map and its substitutes: where every point, scalar and vector count of a NIZK proof, a SNARK proof and a computation commitment
 sits in the wire form, and the one-field-at-a-time replacements the verifier tests apply there.  Pure Python: no library, no GPU.
 
-The wire forms are bincode, as the product's own writers emit them (NizkProof::serialize in spartan_host.cpp, SnarkProof::serialize and
-CompComm::serialize in snark_host.cpp): a vector is a u64 count followed by its elements, a point is its 32-byte ristretto255 encoding, a scalar the
+The wire forms are bincode, as the product's own writers emit them (NizkProof::serialize, SnarkProof::serialize and CompComm::serialize in
+wire.cpp): a vector is a u64 count followed by its elements, a point is its 32-byte ristretto255 encoding, a scalar the
 32 bytes of its Montgomery limbs (x * 2^256 mod l), little endian.  nizk(b), snark(b) and commitment(b) return [(name, offset, kind)] in wire
 order, kind in "pt", "fr", "len" (a vector's count) and, in a commitment only, "u64" (its six dimensions); each walk must end at len(b).  Names
 follow the structs: sc1.proofs[3].z[2], prod.delta, polyeval.L[0], proof_ops.layers[2].coeffs[1][0], h_row_read_ts[1], pe_mem.z2; a vector's count
@@ -246,6 +246,52 @@ def steering(blob, fields):
     for fs in groups.values():
         picks += [(f, ONE_PER_FIELD[f[2]]) for f in _ends(fs)]
     return Corpus(blob, fields, picks)
+
+
+# ------------------------------------------------------------------------------------------------ balanced counts
+# Changing ONE count breaks the framing: every later field is read from the wrong place and the parser refuses the bytes.  A verifier also requires
+# certain vectors to agree in length, and that is only reached by bytes that are well framed: here one vector loses its last element and another of
+# the same set gains one (a copy of its own last element; 32 zero bytes, a valid point and a valid scalar, where it was empty), each with its count.
+def agreeing_vectors(fields):
+    """the sets of counted vectors a verifier requires to be equally long, by name: a sum-check's comm_polys / comm_evals / proofs, the L / R of
+    every log dot-product proof, each product-circuit layer's left / right, a batched proof's dotp_left / dotp_right / dotp_weight"""
+    lens = {name[:-4] for name, _, kind in fields if kind == "len"}
+    sets = [[sc + ".comm_polys", sc + ".comm_evals", sc + ".proofs"] for sc in ("sc1", "sc2")]
+    sets += [[d + ".L", d + ".R"] for d in ("polyeval", "pe_ops", "pe_mem", "pe_derefs") if d + ".L" in lens]
+    for b in ("proof_mem", "proof_ops"):
+        layers = sorted(n for n in lens if re.fullmatch(re.escape(b) + r"\.layers\[\d+\]\.left", n))
+        sets += [[n, n[:-4] + "right"] for n in sorted(layers, key=_indices)]
+        if b + ".dotp_left" in lens:
+            sets.append([b + ".dotp_left", b + ".dotp_right", b + ".dotp_weight"])
+    assert all(v in lens for s in sets for v in s), sets
+    return sets
+
+
+def _resize(blob, fields, vec, delta):
+    """the edits [(offset, bytes removed, bytes put there)] that give vector `vec` one element more (delta = 1) or take its last (delta = -1)"""
+    count_at = next(off for name, off, _ in fields if name == vec + ".len")
+    n = int.from_bytes(blob[count_at:count_at + 8], "little")
+    assert n + delta >= 0, vec
+    spans = [(off, off + (8 if kind in ("len", "u64") else 32)) for name, off, kind in fields if name.startswith(vec + "[%d]" % (n - 1))] if n else []
+    start, end = (min(s for s, _ in spans), max(e for _, e in spans)) if n else (count_at + 8, count_at + 8)
+    body = (end, 0, blob[start:end] if n else IDENTITY) if delta > 0 else (start, end - start, b"")
+    return [(count_at, 8, (n + delta).to_bytes(8, "little")), body]
+
+
+def balanced(blob, fields):
+    """[(name, bytes)], name "a -> b": within every set of agreeing_vectors, vector a shorter by one and the next of its set (the first again behind
+    the last) longer by one, nothing else changed; a move out of an empty vector does not exist and is left out"""
+    out = []
+    for vecs in agreeing_vectors(fields):
+        for k, a in enumerate(vecs):
+            b = vecs[(k + 1) % len(vecs)]
+            if value(blob, fields, a + ".len") == 0:
+                continue
+            m = blob
+            for off, cut, put in sorted(_resize(blob, fields, a, -1) + _resize(blob, fields, b, 1), reverse=True):
+                m = m[:off] + put + m[off + cut:]
+            out.append(("%s -> %s" % (a, b), m))
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ the verdict rule

@@ -2,7 +2,7 @@
 // the pool).  Compiles the product's host sources directly (no HIP, no device code) and feeds them mutated .zkif files and proofs.
 // usage: san_harness <circuit.zkif> <inputs.zkif> <witness.zkif> <proof.bin> <label> <workdir> <iterations> [<snark_comm.bin> <snark_proof.bin> <nnz>]
 // (with the last three: SNARK::verify of the given and of mutated proofs as well).  The same source builds with -fsanitize=thread (make tsan): the
-// verifiers hand their group equations to background threads through lock-free slots (snark.h Deferred), which is what that build checks.
+// verifiers hand their group equations to background threads through lock-free slots (verify.h Deferred), which is what that build checks.
 #include "../../otti_amd/csrc/spartan.h"
 #include "../../otti_amd/csrc/snark.h"
 #include <stdio.h>

@@ -18,6 +18,7 @@
 #include <vector>
 
 using namespace otti;
+extern "C" void otti_r1cs_free(otti_r1cs *r) { if (!r) return; free(r->A); free(r->B); free(r->C); free(r->vars32); free(r->inputs32); free(r); }   // zkif.cpp's, unused here
 
 static std::vector<uint8_t> slurp(const char *p) {
     FILE *f = fopen(p, "rb"); if (!f) { perror(p); exit(2); }

@@ -305,7 +305,7 @@ def test_host_parsers_under_address_and_ub_sanitizers(tmp_path):
 
 def test_host_verifiers_under_thread_sanitizer(tmp_path):
     """NIZK::verify and SNARK::verify hand their group equations, the decompression of the sum-check commitments and the split
-    multiplication tables to background threads through lock-free slots (snark.h Deferred, spartan_host.cpp PreDecoded) while the calling
+    multiplication tables to background threads through lock-free slots (verify.h Deferred, spartan_host.cpp PreDecoded) while the calling
     thread and its spinning helpers walk the rounds: the same harness built with -fsanitize=thread must see no data race."""
     import subprocess
     san = os.path.join(os.path.dirname(os.path.abspath(__file__)), "san")

@@ -10,7 +10,7 @@ the end, so it reports DECOMPRESS (-11) for a point that the oracle, walking in 
 changed transcript has already failed (-10).  On these two corpora that is the case for 37 NIZK and 25 SNARK point fields; the test asks that the
 product say -11 or -10, and -11 wherever the oracle does.  Neither verifier is to be changed to make these agree.
 
-The product's codes are taken three times — with the default background threads of snark.h Deferred, with none (OTTI_VERIFY_THREADS=0: every
+The product's codes are taken three times — with the default background threads of verify.h Deferred, with none (OTTI_VERIFY_THREADS=0: every
 deferred equation runs inside finish()) and with six — and once more through each batched verifier; all must be equal, code for code.  Each module
 fixture prints its corpus size, the skipped substitutes (equal to the original: at most 1 %) and the seconds taken."""
 import collections
@@ -224,6 +224,46 @@ def test_snark_verify_many_gives_the_single_codes(snark_run, monkeypatch):
     print("snark_verify_many, chunk 4: %d items in %.1f s" % (len(blobs), time.time() - t0))
     bad = snark_run.many_differences(got, order)
     assert not bad, "\n".join(bad[:40])
+
+
+# ------------------------------------------------------------------------------------------------ counts that disagree in well-framed bytes
+# The product's code for every move of proof_fields.balanced, by the member the move is in — recorded from the verifiers as they stood before the
+# wire code was gathered into wire.cpp, and the same since: a refusal either belongs to the parser (MALFORMED) or to the verifier (VERIFY_INTERNAL),
+# and callers see which.  The two modes differ on polyeval: SnarkProof::parse refuses an L / R of different lengths, NizkProof::parse does not and
+# the verifier rejects it.  The sum-checks' three vectors are the verifier's to compare in both modes; everything of the evaluation proof is refused
+# at parse.  The oracle's parser is stricter (every one of these is MALFORMED to it), so only its refusal is asserted, not its code.
+BALANCED_CODES = {
+    "nizk": {"sc1": pf.VERIFY_INTERNAL, "sc2": pf.VERIFY_INTERNAL, "polyeval": pf.VERIFY_INTERNAL},
+    "snark": {"sc1": pf.VERIFY_INTERNAL, "sc2": pf.VERIFY_INTERNAL, "polyeval": pf.MALFORMED, "pe_ops": pf.MALFORMED, "pe_mem": pf.MALFORMED,
+              "pe_derefs": pf.MALFORMED, "proof_mem": pf.MALFORMED, "proof_ops": pf.MALFORMED},
+}
+# nizk: 2 sum-checks x 3 moves + 2 of polyeval.  snark (n = 16: five mem layers, four ops layers; proof_mem has no dot-product claims to move):
+# 6 + 2 x 4 log dot-product proofs + 2 x (5 + 4) layers + 3 of proof_ops' dot-product claims
+BALANCED_MOVES = {"nizk": 8, "snark": 35}
+
+
+def test_balanced_counts_get_the_recorded_codes(run, request, monkeypatch):
+    """one vector shorter and its neighbour longer, bytes well framed (proof_fields.balanced): the single verifier with its default threads, with
+    OTTI_VERIFY_THREADS 0 and 6, and the batched verifier all give the table's code; the oracle refuses every one"""
+    mode = request.node.callspec.params["run"]
+    case, table = run.case, BALANCED_CODES[mode]
+    moves = pf.balanced(run.proof, case.fields(run.proof))
+    assert len(moves) == BALANCED_MOVES[mode] and {name.split(".")[0] for name, _ in moves} == set(table)
+    for name, blob in moves:
+        case.fields(blob)                                                                 # raises unless the walk ends at len(blob): well framed
+    want = [table[name.split(".")[0]] for name, _ in moves]
+    names = [name for name, _ in moves]
+    blobs = [blob for _, blob in moves]
+    assert list(zip(names, [case.product(b) for b in blobs])) == list(zip(names, want))
+    for threads in ("0", "6"):
+        monkeypatch.setenv("OTTI_VERIFY_THREADS", threads)
+        assert list(zip(names, [case.product(b) for b in blobs])) == list(zip(names, want)), threads
+    monkeypatch.delenv("OTTI_VERIFY_THREADS")
+    for threads in (0, 1):
+        got = case.product_many([run.proof] + blobs + [run.proof], threads)
+        assert list(zip(names, got[1:-1])) == list(zip(names, want)) and got[0] == got[-1] == 0, threads
+    refused = [case.oracle(b) for b in blobs]
+    assert all(refused), list(zip(names, refused))
 
 
 # ------------------------------------------------------------------------------------------------ the statement outside the proof

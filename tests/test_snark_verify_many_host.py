@@ -9,13 +9,12 @@ import threading
 
 import pytest
 
+import host_build
 import otti_amd as oa
 import orc
 import snark_verify_many_cases as sm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "otti_amd", "csrc")
-HOST_SOURCES = ["hash.cpp", "hostfast.cpp", "hostifma.cpp", "hostgroup.cpp", "spartan_host.cpp", "snark_host.cpp", "verify_many.cpp", "snark_verify_many.cpp"]
 LABEL = b"many"
 
 
@@ -88,10 +87,7 @@ def test_new_entries_are_exported_and_bound():
 
 
 def _build_check(tmp_path, name, sanitize):
-    exe = tmp_path / name
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", *sanitize, "-march=x86-64-v3", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas",
-                    os.path.join(ROOT, "tests", "snark_verify_many_check.cpp"), *[os.path.join(SRC, s) for s in HOST_SOURCES], "-o", str(exe), "-lpthread"], check=True)
-    return exe
+    return host_build.build_check(tmp_path, "snark_verify_many_check.cpp", name, sanitize, extra=["verify_many.cpp", "snark_verify_many.cpp"])
 
 
 def _check_files(tmp_path, n):
@@ -112,7 +108,7 @@ WANT_LINE = re.compile(r"14 items \(6 accepted\), steps, workers 1 2 4, both ord
 
 
 def test_staged_verifier_under_address_and_ub_sanitizers(tmp_path):
-    exe = _build_check(tmp_path, "snark_verify_many_asan", ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan"])
+    exe = _build_check(tmp_path, "snark_verify_many_asan", host_build.ASAN_UBSAN)
     r = subprocess.run([str(exe), *_check_files(tmp_path, 200)], capture_output=True, text=True, timeout=600,
                        env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1"))
     tail = r.stdout[-2000:] + r.stderr[-4000:]
@@ -124,7 +120,7 @@ def test_staged_verifier_under_thread_sanitizer(tmp_path):
     """workers parked between the passes, their spinning helpers and the deferred group equations of several proofs at once: no data race.  (gcc 11's
     libtsan does not intercept pthread_cond_clockwait, which the helper pool's wait_for uses: its sleeping helpers are reported as "double lock of a
     mutex", the known false positive tests/test_host.py names; the run goes on past it and everything else must be clean.)"""
-    exe = _build_check(tmp_path, "snark_verify_many_tsan", ["-fsanitize=thread"])
+    exe = _build_check(tmp_path, "snark_verify_many_tsan", host_build.TSAN)
     r = subprocess.run([str(exe), *_check_files(tmp_path, 200)], capture_output=True, text=True, timeout=900,
                        env=dict(os.environ, OTTI_HOST_THREADS="3", TSAN_OPTIONS="halt_on_error=0"))
     tail = r.stdout[-2000:] + r.stderr[-4000:]

@@ -4,7 +4,7 @@ requests with the one-shot's own failure, the request's working directory, malfo
 Server and one-shot run with no device visible (HIP_VISIBLE_DEVICES empty), so both sides of every comparison behave alike on any machine.
 A served request's stdout is compared with the one-shot's line by line after replacing the numbers of milliseconds, the one line that
 differs by design (`* process start to main()` / `* served:`) and the CODE in a last line `Verification FAILED (<code>: <name>)`: the verifier hands
-its group equations to background threads and reports whichever failed first in time (snark.h Deferred), so a damaged proof is rejected as -10 or
+its group equations to background threads and reports whichever failed first in time (verify.h Deferred), so a damaged proof is rejected as -10 or
 as -11 from one run of the same process to the next; that the line is there, and the status, are compared."""
 import os
 import re

@@ -6,19 +6,14 @@ import os
 import re
 import subprocess
 
+import host_build
 import zkif_ingest_cases as zc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "otti_amd", "csrc")
-HOST_SOURCES = ["hash.cpp", "hostfast.cpp", "hostifma.cpp", "hostgroup.cpp", "spartan_host.cpp", "snark_host.cpp", "zkif.cpp"]   # as tests/san/Makefile
 N_MUTANTS = 1500
 
 
 def test_walker_agrees_with_the_host_loader_under_sanitizers(tmp_path):
-    exe = tmp_path / "zkif_walk_check"
-    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan",
-                    "-march=x86-64-v3", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", os.path.join(ROOT, "tests", "zkif_walk_check.cpp"),
-                    *[os.path.join(SRC, s) for s in HOST_SOURCES], "-o", str(exe), "-lpthread"], check=True)
+    exe = host_build.build_check(tmp_path, "zkif_walk_check.cpp", "zkif_walk_check", host_build.ASAN_UBSAN)
     d = str(tmp_path)
     lines = []
     for name, n, ni, compiler in (("uniform48", 48, 3, False), ("uniform1000", 1000, 10, False), ("compiler200", 200, 3, True)):
