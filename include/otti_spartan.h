@@ -196,6 +196,51 @@ int32_t otti_nizk_verify(const otti_instance *inst, const uint8_t *inputs32, siz
 int32_t otti_nizk_verify_many(const otti_instance *inst, const otti_gens *gens, const uint8_t *tlabel, size_t tlabel_len, size_t count,
                               const uint8_t *const *inputs32, const size_t *ninputs, const uint8_t *const *proofs, const size_t *proof_lens,
                               uint32_t threads, int32_t *results, size_t *n_rejected /* may be NULL */);
+/* Many NIZK proofs of ONE instance verified as ONE randomised batch: the group equations that feed nothing hashed — two per sum-check round, the
+   six sigma equations and the closing equation of the log dot-product proof with its fixed-base sum over the R generators — are not checked
+   proof by proof but collected as term lists  sum_j s_j P_j = identity  and summed, for all proofs at once, in one multi-scalar multiplication
+   (otti_k_batch_sum is the device pass alone).  What is hashed stays per proof: the transcript, the combinations inside the rounds, the row sum.
+   Verdict rule: results[i] = what otti_nizk_verify returns for item i alone with the same instance, generators and label, code for code, with ONE
+   exception: a proof that otti_nizk_verify rejects is accepted with probability at most 2^-120 over the library's own randomness (the bound is
+   1 / l < 2^-252 per call: each equation of each proof has a weight of its own, a full scalar, so no two defects can cancel).  A valid proof is
+   never rejected.  seed32: NULL = OS entropy.  A caller's seed exists only so that tests can repeat a run: a seed the prover could know or guess
+   FORFEITS SOUNDNESS — never pass one in production.
+   How verdicts are reached: a proof that fails on its walk (a scalar check, a point that does not decode on the hashed path) has that code; if
+   the one sum over all other proofs is the identity, all of them are accepted; if not, one localisation pass forms each proof's own sum over the
+   points already decoded, and only the proofs whose sum is not the identity, or that hold an undecodable point, are run through the single
+   verifier for their code (so are proofs whose rx / ry differ from the transcript's challenges).  A batch with a bad proof therefore costs one
+   more sum and one single verification per culprit.
+   Refusals, their order, count == 0, threads (0: the default, 8; more than 16: OTTI_ERR_BAD_ARG), *n_rejected and the otti_last_error wording
+   are otti_nizk_verify_many's.  The workers own no background threads.  Several caller threads may call with the same handles at once.
+   Where the sum runs: on the device when one is present (the proofs' distinct points go up once, one decode launch, one sum launch; the
+   generators take part as a set decoded once per generators handle and kept on it), on the host cores otherwise or under OTTI_VERIFY_HOST.
+   Decided from tools/verify_batch_probe.py on an MI355X (profiles/verify_batch.md has the tables): the default is EIGHT workers — never slower
+   than four beyond the spread, faster from 16 proofs on, and steady, where eight of otti_nizk_verify_many's workers are erratic; the sum runs on
+   the device at EVERY size (its launches take 0.24 - 0.30 ms from 260 points to 13 000, the host cores 1 - 10 ms; OTTI_VERIFY_BATCH_SUM=host,
+   read per call, forces the host: measurements, tests); and a call with FEWER THAN THREE live proofs of an instance of at least 2^16 padded
+   constraints takes otti_nizk_verify_many's path (faster there by 0.2 - 0.3 ms, while at 2^12 the batch is faster by as much;
+   info.routed_to_many = 1; OTTI_VERIFY_BATCH_RULE=0, read per call, sets this routing aside).  Against
+   otti_nizk_verify_many with its four workers the batch is level at 4 proofs, 1.4 - 2.0 x faster at 16 and 2.0 - 3.5 x at 64; a batch with one
+   bad proof costs 2 - 6 ms more than a good one.
+   HBM: per calling thread, grow-only and kept across calls: 128 bytes per distinct point (about 25 per sum-check round and proof), 32 per
+   scalar (twice when a localisation pass runs), 128 per (window, split) of a job; per generators handle 96 bytes per generator.
+   info (may be NULL) is filled whenever the call ran. */
+typedef struct {
+    uint32_t live;                  /* proofs that parsed and fit the instance */
+    uint32_t equations, points;     /* group equations collected; distinct points sent to the sum (over all proofs that reached it) */
+    uint32_t gen_slots;             /* generator slots that carry a merged scalar */
+    uint32_t on_device;             /* 1: the sum ran on the device, 0: on the host cores */
+    uint32_t accepted_first_pass;   /* 1: the one sum was the identity and every proof in it was accepted */
+    uint32_t localise_passes;       /* 0 or 1 */
+    uint32_t singles_rerun;         /* proofs run through the single verifier for their code */
+    uint32_t workers;
+    uint32_t routed_to_many;        /* 1: fewer than three live proofs of a large instance, verified on otti_nizk_verify_many's path; the sum's counters stay 0 */
+    double sum_ms;                  /* device-event time of the sum's launches, both passes (0 on the host) */
+} otti_verify_batch_info;
+int32_t otti_nizk_verify_batch(const otti_instance *inst, const otti_gens *gens, const uint8_t *tlabel, size_t tlabel_len, size_t count,
+                               const uint8_t *const *inputs32, const size_t *ninputs, const uint8_t *const *proofs, const size_t *proof_lens,
+                               uint32_t threads, const uint8_t *seed32 /* may be NULL */, int32_t *results, size_t *n_rejected /* may be NULL */,
+                               otti_verify_batch_info *info /* may be NULL */);
 /* Many resident witnesses of ONE instance proved in one call: the prover's counterpart of otti_nizk_verify_many.  results[i], proofs[i] and
    proof_lens[i] are exactly what otti_nizk_prove_resident(inst, wits[i], gens, tlabel, tlabel_len, seeds32[i], ..) returns — with a seed, the same
    bytes; seeds32 NULL, or seeds32[i] NULL: OS entropy.  Each proof is freed with otti_buf_free; a failed item has proofs[i] = NULL, proof_lens[i] = 0.
@@ -644,6 +689,14 @@ int32_t otti_k_sc_plan(int32_t kind, size_t len, int32_t armed, uint32_t *workgr
  * plain, armed + released after hold_us microseconds, and armed + aborted.  out2 (len/2 + len/2 elements) and e2 (2 elements) are the
  * plain launch's results; any disagreement between the three ways is OTTI_ERR_INTERNAL. */
 int32_t otti_k_armed_selftest(const uint8_t *A, const uint8_t *B, size_t len, const uint8_t *r, uint32_t hold_us, uint8_t *out2, uint8_t *e2);
+/* The device pass of otti_nizk_verify_batch alone (dev_batch_sum: one k_decode_niels_sets launch, one k_msm_var_many launch).  Set k: points
+   [set_offsets[k], set_offsets[k + 1]) of h_compressed32 (nsets + 1 ascending offsets from 0, in points).  With nsets >= 2 the LAST set plays the
+   generators: it is decoded ahead, as a generators handle's set is, and takes part resident; a job may name it only alone.  Job j sums the
+   job_nsets[j] consecutive sets from job_first_set[j] on with the next (those sets' points) scalars of h_scalars_mont32; jobs may overlap.
+   codes[j] = 0 and out32 + 32 j the encoded sum, or OTTI_ERR_VERIFY_DECOMPRESS (32 zero bytes) exactly when one of the job's sets holds a point
+   that does not decode.  kernel_ms (may be NULL): device-event time of the two launches.  No host fallback. */
+int32_t otti_k_batch_sum(size_t nsets, const uint8_t *h_compressed32, const size_t *set_offsets, size_t njobs, const uint32_t *job_first_set,
+                         const uint32_t *job_nsets, const uint8_t *h_scalars_mont32, uint8_t *out32, int32_t *codes, float *kernel_ms);
 int32_t otti_k_msm_rows(otti_gens *gens, const uint8_t *h_Z, size_t L, size_t R, const uint8_t *h_blinds, uint8_t *h_out32, float *kernel_ms);
 /* A general fixed-base MSM job, as the prover's launcher takes it, for kernel-level tests: row i = sum_{j < n_dense} dense[i n_dense + j] P[j]
    + sum_{e < n_extra} extra_s[i n_extra + e] P[extra_base[e]] over the generators' R + 2 points (n_dense <= R, n_extra <= 8, extra_base[e] < R + 2;

@@ -117,6 +117,11 @@ _sig("otti_nizk_prove_sharded", _i32, _vp, _vp, _vp, ctypes.c_char_p, _sz, _vp, 
 _sig("otti_nizk_verify", _i32, _vp, _vp, _sz, _vp, ctypes.c_char_p, _sz, _vp, _sz)
 _sig("otti_nizk_verify_many", _i32, _vp, _vp, ctypes.c_char_p, _sz, _sz, ctypes.POINTER(_vp), ctypes.POINTER(_sz), ctypes.POINTER(_vp), ctypes.POINTER(_sz),
      ctypes.c_uint32, ctypes.POINTER(_i32), ctypes.POINTER(_sz))
+class _VerifyBatchInfo(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_uint32) for k in ("live", "equations", "points", "gen_slots", "on_device", "accepted_first_pass", "localise_passes", "singles_rerun",
+                                               "workers", "routed_to_many")] + [("sum_ms", ctypes.c_double)]
+_sig("otti_nizk_verify_batch", _i32, _vp, _vp, ctypes.c_char_p, _sz, _sz, ctypes.POINTER(_vp), ctypes.POINTER(_sz), ctypes.POINTER(_vp), ctypes.POINTER(_sz),
+     ctypes.c_uint32, _vp, ctypes.POINTER(_i32), ctypes.POINTER(_sz), ctypes.POINTER(_VerifyBatchInfo))
 class _ProveManyInfo(ctypes.Structure):
     _fields_ = [("chunks", ctypes.c_uint32), ("product_tiles", ctypes.c_uint32), ("row_jobs", ctypes.c_uint32), ("workers", ctypes.c_uint32),
                 ("rows_from_front", ctypes.c_uint32), ("products_from_front", ctypes.c_uint32), ("front_failed", ctypes.c_uint32),
@@ -202,6 +207,7 @@ _sig("otti_k_msm_rows", _i32, _vp, _vp, _sz, _sz, _vp, _vp, _fp)
 _sig("otti_k_msm_job", _i32, _vp, _sz, _sz, _vp, _sz, _vp, _vp, _i32, _i32, _i32, _sz, _vp, _vp, _fp)
 _sig("otti_k_row_sum", _i32, _vp, _sz, _vp, _vp)
 _sig("otti_k_row_sum_many", _i32, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp)
+_sig("otti_k_batch_sum", _i32, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp)
 _sig("otti_k_msm_scatter_rows", _i32, _vp, _sz, _vp, _vp, _sz, _vp, _fp)
 _sig("otti_k_witness_diff", _i32, _vp, _sz, _vp, _i32, _sz, _vp, _vp, _vp, ctypes.POINTER(_u64), ctypes.POINTER(ctypes.c_uint32), _fp)
 _sig("otti_k_eq_pyramid", _i32, _vp, _sz, _vp)
@@ -896,6 +902,34 @@ class NIZK:
         assert rejected.value == sum(1 for r in out if r != 0)
         return out
 
+    @staticmethod
+    def verify_batch(inst, proofs, inputs, gens, transcript_label=b"nizk_example", threads=0, seed=None, details=False):
+        """Many proofs of ONE instance as one randomised batch (otti_nizk_verify_batch): the arguments and the returned list of codes are
+        ``verify_many``'s — element i is what ``verify`` on proof i alone would report, except that a proof it rejects is accepted with
+        probability at most 2^-120 over the library's randomness.  ``seed`` (32 bytes) repeats a run in tests; a seed the prover could know
+        forfeits soundness, so leave it None.  ``details=True`` returns (codes, info dict: the otti_verify_batch_info counters)."""
+        label = bytes(transcript_label)
+        blobs = [np.frombuffer(bytes(p.bytes if isinstance(p, NIZK) else p), dtype=np.uint8) for p in proofs]
+        n = len(blobs)
+        per = list(inputs) if isinstance(inputs, (list, tuple)) else [inputs] * n
+        if len(per) != n:
+            raise ValueError("verify_batch: one InputsAssignment for all proofs, or one per proof")
+        ins = [_scalars(i.assignment, "inputs") for i in per]
+        in_ptrs, in_counts = (_vp * max(1, n))(), (_sz * max(1, n))()
+        pf_ptrs, pf_lens = (_vp * max(1, n))(), (_sz * max(1, n))()
+        empty = np.zeros(1, dtype=np.uint8)
+        for k in range(n):
+            in_ptrs[k], in_counts[k] = _ptr(ins[k]), ins[k].shape[0]
+            pf_ptrs[k], pf_lens[k] = (blobs[k] if blobs[k].size else empty).ctypes.data_as(_vp), blobs[k].size
+        results, rejected, info = (_i32 * max(1, n))(), _sz(0), _VerifyBatchInfo()
+        _check(lib.otti_nizk_verify_batch(inst._h, gens._h, label, len(label), n, in_ptrs, in_counts, pf_ptrs, pf_lens, threads, _seed(seed), results,
+                                          ctypes.byref(rejected), ctypes.byref(info)))
+        out = [int(results[k]) for k in range(n)]
+        assert rejected.value == sum(1 for r in out if r != 0)
+        if not details:
+            return out
+        return out, {k: getattr(info, k) for k, _ in _VerifyBatchInfo._fields_ }
+
 
 # ---------------------------------------------------------------------------------------------- SNARK mode (lib.rs SNARKGens / SNARK)
 class SNARKGens:
@@ -1496,6 +1530,24 @@ class kernels:
         out = np.zeros((max(1, len(jobs)), 32), dtype=np.uint8); codes = (_i32 * max(1, len(jobs)))()
         _check(lib.otti_k_row_sum_many(len(cs), _ptr(comp), _ptr(off), len(jobs), _ptr(js), _ptr(sc), _ptr(out), codes))
         return out[:len(jobs)], [int(codes[j]) for j in range(len(jobs))]
+
+    @staticmethod
+    def batch_sum(sets, jobs):
+        """the batch verifier's device pass alone (otti_k_batch_sum): ``sets`` = arrays of compressed points, lying one behind the other; with two
+        sets or more the last one is decoded ahead and resident, as the generators are.  ``jobs`` = [(first set, number of sets, Montgomery
+        scalars for those sets' points)].  Returns (sums (njobs, 32) uint8, codes [int], device-event ms of the launches)"""
+        cs = [np.ascontiguousarray(c, dtype=np.uint8).reshape(-1, 32) for c in sets]
+        off = np.zeros(len(cs) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([c.shape[0] for c in cs])
+        comp = np.ascontiguousarray(np.concatenate(cs) if cs else np.zeros((1, 32), dtype=np.uint8))
+        first = np.ascontiguousarray([f for f, _, _ in jobs], dtype=np.uint32); count = np.ascontiguousarray([c for _, c, _ in jobs], dtype=np.uint32)
+        ss = [_scalars(s, "s") for _, _, s in jobs]
+        for (f, c, _), s in zip(jobs, ss):
+            assert not (c >= 1 and 0 <= f and f + c <= len(cs)) or s.shape[0] == int(off[f + c] - off[f])
+        sc = np.ascontiguousarray(np.concatenate(ss) if ss else np.zeros((1, 32), dtype=np.uint8))
+        out = np.zeros((max(1, len(jobs)), 32), dtype=np.uint8); codes = (_i32 * max(1, len(jobs)))(); ms = ctypes.c_float(0)
+        _check(lib.otti_k_batch_sum(len(cs), _ptr(comp), _ptr(off), len(jobs), _ptr(first), _ptr(count), _ptr(sc), _ptr(out), codes, ctypes.byref(ms)))
+        return out[:len(jobs)], [int(codes[j]) for j in range(len(jobs))], float(ms.value)
 
     @staticmethod
     def msm_scatter_rows(gens, L, idx, s):

@@ -437,6 +437,27 @@ int32_t otti_nizk_verify_many(const otti_instance *inst, const otti_gens *gens, 
         return OTTI_OK;
     });
 }
+int32_t otti_nizk_verify_batch(const otti_instance *inst, const otti_gens *gens, const uint8_t *tlabel, size_t tlabel_len, size_t count,
+                               const uint8_t *const *inputs32, const size_t *ninputs, const uint8_t *const *proofs, const size_t *proof_lens,
+                               uint32_t threads, const uint8_t *seed32, int32_t *results, size_t *n_rejected, otti_verify_batch_info *info) {
+    return guarded([&] {
+        if (!inst || !gens || !results) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (threads > kVerifyManyMaxThreads) throw Error(OTTI_ERR_BAD_ARG, "more than 16 worker threads");
+        if (count && (!inputs32 || !ninputs || !proofs || !proof_lens)) throw Error(OTTI_ERR_BAD_ARG, "a null array with count > 0");
+        for (size_t i = 0; i < count; i++) if (!proofs[i] || (ninputs[i] && !inputs32[i])) throw Error(OTTI_ERR_BAD_ARG, "a null proof, or null inputs with a non-zero count");
+        if (n_rejected) *n_rejected = 0;
+        if (info) memset(info, 0, sizeof *info);
+        if (!count) return OTTI_OK;
+        std::vector<VerifyItem> items(count);
+        for (size_t i = 0; i < count; i++) items[i] = {inputs32[i], ninputs[i], proofs[i], proof_lens[i]};
+        nizk_verify_batch(*inst->I, *gens->g, tlabel, tlabel_len, items.data(), count, threads, seed32, results, info);
+        size_t bad = 0;
+        for (size_t i = 0; i < count; i++) bad += results[i] != OTTI_OK;
+        if (n_rejected) *n_rejected = bad;
+        if (bad) g_last_error = std::to_string(bad) + " of " + std::to_string(count) + " proofs rejected";
+        return OTTI_OK;
+    });
+}
 // Many resident witnesses of ONE instance in one call (device.h nizk_prove_many; the contract: include/otti_spartan.h).  Everything the arguments
 // alone say is said before the handles are looked into, the generators' size before a device is asked for, and no output is written before that.
 int32_t otti_nizk_prove_many(otti_instance *inst, otti_witness *const *wits, size_t count, otti_gens *gens, const uint8_t *tlabel, size_t tlabel_len,

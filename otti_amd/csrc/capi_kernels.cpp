@@ -478,6 +478,35 @@ int32_t otti_k_row_sum_many(size_t nsets, const uint8_t *compressed32, const siz
         return OTTI_OK;
     });
 }
+// The batch verifier's device pass alone (device.h dev_batch_sum).  With two sets or more the last one stands in for the generators: decoded ahead
+// (dev_decode_set), resident for the pass.  The arguments are judged before a device is touched.
+int32_t otti_k_batch_sum(size_t nsets, const uint8_t *compressed32, const size_t *set_offsets, size_t njobs, const uint32_t *job_first_set,
+                         const uint32_t *job_nsets, const uint8_t *scalars_mont32, uint8_t *out32, int32_t *codes, float *kernel_ms) {
+    return guarded([&] {
+        if (!compressed32 || !set_offsets || !job_first_set || !job_nsets || !scalars_mont32 || !out32 || !codes || !nsets || !njobs) throw Error(OTTI_ERR_BAD_ARG, "null argument, no sets or no jobs");
+        if (set_offsets[0] != 0) throw Error(OTTI_ERR_BAD_ARG, "the offsets do not start at 0");
+        for (size_t k = 0; k < nsets; k++)
+            if (set_offsets[k + 1] <= set_offsets[k] || set_offsets[k + 1] - set_offsets[k] > kRowSumMaxPoints) throw Error(OTTI_ERR_BAD_ARG, "an empty set, or one of more than 2^20 points");
+        const size_t up = nsets >= 2 ? nsets - 1 : nsets, ngens = nsets >= 2 ? set_offsets[nsets] - set_offsets[up] : 0;      // `up` sets go up in the pass
+        std::vector<BatchSumJobIn> jobs(njobs); size_t total = 0;
+        for (size_t j = 0; j < njobs; j++) {
+            const size_t f = job_first_set[j], c = job_nsets[j];
+            if (!c || f + c > nsets || (f + c == nsets && nsets >= 2 && c != 1)) throw Error(OTTI_ERR_BAD_ARG, "a job names sets that are not there, or the last set with others");
+            jobs[j].first_set = f; jobs[j].nsets = c; total += set_offsets[f + c] - set_offsets[f];
+        }
+        std::vector<Fr> s(total); memcpy(s.data(), scalars_mont32, 32 * total);
+        total = 0;
+        for (size_t j = 0; j < njobs; j++) { jobs[j].scalars = s.data() + total; total += set_offsets[jobs[j].first_set + jobs[j].nsets] - set_offsets[jobs[j].first_set]; }
+        DevCtx &c = DevCtx::get();
+        DecodedSet last;
+        if (ngens) dev_decode_set(c, compressed32 + 32 * set_offsets[up], ngens, last);
+        BatchSumIn in; in.comp32 = compressed32; in.set_off = set_offsets; in.nsets = up; in.gens = ngens ? last.pts.p : nullptr; in.ngens = ngens; in.gens_bad = last.bad;
+        std::vector<RowSumOut> res(njobs);
+        dev_batch_sum(c, in, jobs.data(), njobs, res.data(), kernel_ms);
+        for (size_t j = 0; j < njobs; j++) { codes[j] = res[j].code; if (res[j].code) memset(out32 + 32 * j, 0, 32); else pt_encode(out32 + 32 * j, res[j].sum); }
+        return OTTI_OK;
+    });
+}
 int32_t otti_k_msm_rows(otti_gens *gens, const uint8_t *Z, size_t L, size_t R, const uint8_t *blinds, uint8_t *out32, float *ms) {
     return guarded([&] {
         DevCtx &c = DevCtx::get(); Gens &g = *gens->g;

@@ -156,6 +156,7 @@ struct DevCtx {
     void reset_arrival_counters();                            // after an aborted or timed-out launch: a grid may have left them non-zero (stream must be idle)
     hipEvent_t ev_order = nullptr;                            // orders a caller's stream (otti_kd_*) against this context's own
     std::vector<struct RowSumSlot *> row_slots;               // the verifier's variable-base sums in flight on this context (prover.cpp), buffers kept across proofs
+    struct BatchSumScratch *batch_sum = nullptr;              // dev_batch_sum's working memory and what its last decoding pass left resident (k_msm.hip), grow-only
     struct RowSumManyScratch *row_many = nullptr;             // dev_row_sums_many's working memory (k_msm.hip), grow-only, kept across calls
     TailMailbox tail_mail;
     // ---- host waits on device mail (waits.cpp).  The one guarded spin: polls arrived() until it holds; while it does not, fails the way lim says
@@ -555,6 +556,21 @@ struct RowSumSetIn { const uint8_t *comp32 = nullptr; size_t n = 0; const Niels 
 struct RowSumJobIn { size_t set = 0; const Fr *scalars = nullptr; };
 struct RowSumOut { int code = 0; Pt sum; };
 void dev_row_sums_many(DevCtx &c, const RowSumSetIn *sets, size_t nsets, const RowSumJobIn *jobs, size_t njobs, RowSumOut *out);
+// ---- the weighted sum of a batch of proofs' group equations (verify_batch.cpp; the same two kernels): nsets sets of compressed points in HOST
+// memory, one behind the other (set k: points [set_off[k], set_off[k + 1]), nsets + 1 ascending offsets from 0) — one set per proof — go up once and
+// are decoded by ONE launch with a counter per set; the generators take part as one more set, index nsets, already in HBM in the form the sums read
+// (decoded once per generators handle).  A job sums `nsets` CONSECUTIVE sets from first_set on — they are contiguous in HBM, so a job over all of
+// them is the whole batch's sum and a job over one set is one proof's — or the generator set alone (first_set == in.nsets, nsets == 1), with one
+// scalar per point (host, Montgomery); jobs may overlap and name a set several times.  ONE k_msm_var_many launch forms all jobs' sums; out[j] is
+// {0, the sum} or {OTTI_ERR_VERIFY_DECOMPRESS} exactly when one of job j's sets holds a point that does not decode.  reuse: a second pass over the
+// sets the context's LAST pass decoded (the same offsets, or OTTI_ERR_INTERNAL): nothing goes up or is decoded again, and a job over uploaded sets
+// may leave scalars null to take those its points got from the first job of that pass, if that job spanned all sets — the localisation pass sends
+// only the generator scalars.  ms (may be null): device-event time of the launches.  Waits; recombines the windows on the host as the row sums do.
+// HBM: grow-only per context, 32 + 96 bytes per point, 32 per scalar (twice for a second pass), 128 per (window, split) — at most 51 * ceil(n / 2048) per job.
+struct BatchSumIn { const uint8_t *comp32 = nullptr; const size_t *set_off = nullptr; size_t nsets = 0; const Niels *gens = nullptr; size_t ngens = 0; bool gens_bad = false, reuse = false; };
+struct BatchSumJobIn { size_t first_set = 0, nsets = 1; const Fr *scalars = nullptr; };
+void dev_batch_sum(DevCtx &c, const BatchSumIn &in, const BatchSumJobIn *jobs, size_t njobs, RowSumOut *out, float *ms);
+const unsigned *dev_batch_sum_bad(DevCtx &c);                              // per set of the last decoding pass: how many of its points did not decode
 struct DecodedSet { DevBuf<Niels> pts; size_t n = 0; bool bad = false; };      // bad: some encoding did not decode (the identity stands in its place)
 void dev_decode_set(DevCtx &c, const uint8_t *comp32, size_t n, DecodedSet &out);   // host bytes -> HBM; synchronises
 double dev_madd_peak(DevCtx &c);                                          // mixed point additions per second, whole chip (the MSM's ALU roof)

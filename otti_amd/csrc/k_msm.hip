@@ -887,6 +887,99 @@ void dev_row_sums_many(DevCtx &c, const RowSumSetIn *sets, size_t nsets, const R
         out[j].code = 0; out[j].sum = acc;
     }
 }
+// The weighted sum of a batch of proofs' group equations (device.h dev_batch_sum).  The sets lie one behind the other in S.pts as they do in the
+// upload, so a job over consecutive sets reads one contiguous run of points: the first pass's job spans them all, the localisation pass's jobs take
+// one set each, and both are plain VarMsmArgs for k_msm_var_many — no kernel of its own.
+struct BatchSumScratch {
+    DevBuf<uint8_t> comp; DevBuf<Niels> pts; DevBuf<Fr> sc, sc_again; DevBuf<Pt> out; DevBuf<unsigned> bad; DevBuf<uint32_t> tab; DevBuf<VarMsmArgs> jobs;
+    std::vector<uint32_t> off; std::vector<unsigned> h_bad; bool point_scalars = false;      // what the last decoding pass left resident
+};
+void dev_batch_sum(DevCtx &c, const BatchSumIn &in, const BatchSumJobIn *jobs, size_t njobs, RowSumOut *out, float *ms) {
+    if (!jobs || !out || !njobs || !in.nsets || !in.set_off || (!in.reuse && !in.comp32)) throw Error(OTTI_ERR_BAD_ARG, "batch sum: no sets or no jobs");
+    if (!c.batch_sum) c.batch_sum = new BatchSumScratch();
+    BatchSumScratch &S = *c.batch_sum;
+    const size_t nsets = in.nsets, total_pts = in.set_off[nsets];
+    for (size_t k = 0; k < nsets; k++) if (in.set_off[k + 1] <= in.set_off[k]) throw Error(OTTI_ERR_BAD_ARG, "batch sum: an empty set");
+    if (in.set_off[0] != 0 || total_pts > ((size_t)1 << 24)) throw Error(OTTI_ERR_BAD_ARG, "batch sum: offsets that do not start at 0, or more than 2^24 points");
+    if (in.gens ? (in.ngens < 1 || in.ngens > kRowSumMaxPoints) : in.ngens != 0) throw Error(OTTI_ERR_BAD_ARG, "batch sum: a generator set of no points or of more than 2^20");
+    if (in.reuse) {
+        bool same = S.off.size() == nsets + 1;
+        for (size_t k = 0; same && k <= nsets; k++) same = S.off[k] == (uint32_t)in.set_off[k];
+        if (!same) throw Error(OTTI_ERR_INTERNAL, "batch sum: the sets of a second pass are not those the context holds");
+    }
+    // ---- the job table: every job's shape is the one dev_msm_var takes for its n; results one behind the other, (window, split) within a job
+    std::vector<VarMsmArgs> tbl(njobs); std::vector<size_t> out_off(njobs), sc_at(njobs, SIZE_MAX);
+    std::vector<uint32_t> first(njobs + 1);
+    size_t total_sc = 0, total_out = 0, total_y = 0; int max_W = 0;
+    for (size_t j = 0; j < njobs; j++) {
+        const BatchSumJobIn &J = jobs[j]; const bool on_gens = J.first_set == nsets;
+        if (on_gens ? (!in.gens || J.nsets != 1) : (J.nsets < 1 || J.first_set + J.nsets > nsets)) throw Error(OTTI_ERR_BAD_ARG, "batch sum: a job names sets that are not there");
+        if (!J.scalars && (on_gens || !in.reuse || !S.point_scalars)) throw Error(OTTI_ERR_BAD_ARG, "batch sum: a job without scalars where none are resident");
+        const size_t n = on_gens ? in.ngens : in.set_off[J.first_set + J.nsets] - in.set_off[J.first_set];
+        var_msm_shape(tbl[j], n);
+        if (J.scalars) { sc_at[j] = total_sc; total_sc += n; }
+        out_off[j] = total_out; total_out += (size_t)tbl[j].W * tbl[j].splits;
+        first[j] = (uint32_t)total_y; total_y += (size_t)tbl[j].splits;
+        max_W = std::max(max_W, tbl[j].W);
+    }
+    first[njobs] = (uint32_t)total_y;
+    if (total_y > 65535) throw Error(OTTI_ERR_INTERNAL, "batch sum: too many splits in one pass");
+    DevBuf<Fr> &SC = in.reuse ? S.sc_again : S.sc;                        // a second pass leaves the first one's point scalars where they are
+    if (!in.reuse) { grow(S.comp, 32 * total_pts); grow(S.pts, total_pts); grow(S.bad, nsets); }
+    grow(SC, std::max<size_t>(1, total_sc)); grow(S.out, total_out); grow(S.jobs, njobs); grow(S.tab, nsets + 1 + njobs + 1);
+    for (size_t j = 0; j < njobs; j++) {
+        const BatchSumJobIn &J = jobs[j]; VarMsmArgs &A = tbl[j];
+        A.pts = J.first_set == nsets ? in.gens : S.pts.p + in.set_off[J.first_set];
+        A.sc = J.scalars ? SC.p + sc_at[j] : S.sc.p + in.set_off[J.first_set];
+        A.out = S.out.p + out_off[j];
+    }
+    std::vector<Fr> sc(total_sc);
+    for (size_t j = 0; j < njobs; j++) if (jobs[j].scalars) memcpy(sc.data() + sc_at[j], jobs[j].scalars, (size_t)tbl[j].n * sizeof(Fr));
+    std::vector<uint32_t> tab(nsets + 1);
+    for (size_t k = 0; k <= nsets; k++) tab[k] = (uint32_t)in.set_off[k];
+    tab.insert(tab.end(), first.begin(), first.end());
+    // ---- queue: compressed points, decode, scalars and tables, the sums, the copies back
+    struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{c.stream};   // the copies read this frame's vectors: nothing queued outlives it, also on a throw
+    OTTI_HIP(hipMemcpyAsync(S.tab.p, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c.stream));
+    if (total_sc) OTTI_HIP(hipMemcpyAsync(SC.p, sc.data(), total_sc * sizeof(Fr), hipMemcpyHostToDevice, c.stream));
+    OTTI_HIP(hipMemcpyAsync(S.jobs.p, tbl.data(), njobs * sizeof(VarMsmArgs), hipMemcpyHostToDevice, c.stream));
+    if (!in.reuse) {
+        S.off.clear(); S.point_scalars = false;                          // until this pass has run: a throw below leaves nothing a second pass could take
+        OTTI_HIP(hipMemcpyAsync(S.comp.p, in.comp32, 32 * total_pts, hipMemcpyHostToDevice, c.stream));
+        OTTI_HIP(hipMemsetAsync(S.bad.p, 0, nsets * sizeof(unsigned), c.stream));
+    }
+    if (ms) OTTI_HIP(hipEventRecord(c.ev0, c.stream));
+    if (!in.reuse) {
+        KScope ks(c, KC_DECODE);
+        hipLaunchKernelGGL(k_decode_niels_sets, (unsigned)((total_pts + 63) / 64), 64, 0, c.stream, (const uint8_t *)S.comp.p, (const uint32_t *)S.tab.p, (uint32_t)nsets, S.pts.p, S.bad.p);
+    }
+    {
+        KScope ks(c, KC_MSM_VAR);
+        hipLaunchKernelGGL(k_msm_var_many, dim3((unsigned)max_W, (unsigned)total_y), kBlock, 0, c.stream, (const VarMsmArgs *)S.jobs.p, (const uint32_t *)(S.tab.p + nsets + 1), (uint32_t)njobs);
+    }
+    if (ms) OTTI_HIP(hipEventRecord(c.ev1, c.stream));
+    std::vector<Pt> part(total_out); std::vector<unsigned> bad(nsets, 0);
+    OTTI_HIP(hipMemcpyAsync(part.data(), S.out.p, total_out * sizeof(Pt), hipMemcpyDeviceToHost, c.stream));
+    if (!in.reuse) OTTI_HIP(hipMemcpyAsync(bad.data(), S.bad.p, nsets * sizeof(unsigned), hipMemcpyDeviceToHost, c.stream));
+    OTTI_HIP(hipStreamSynchronize(c.stream));
+    if (ms) OTTI_HIP(hipEventElapsedTime(ms, c.ev0, c.ev1));
+    if (!in.reuse) { S.h_bad = bad; S.off.assign(tab.begin(), tab.begin() + nsets + 1); S.point_scalars = jobs[0].scalars && jobs[0].first_set == 0 && jobs[0].nsets == nsets; }
+    // ---- per job: sum_w 2^(c w) * (sum over splits), Horner from the top window, c doublings per step
+    for (size_t j = 0; j < njobs; j++) {
+        const BatchSumJobIn &J = jobs[j]; const VarMsmArgs &A = tbl[j];
+        bool undecodable = J.first_set == nsets ? in.gens_bad : false;
+        if (J.first_set != nsets) for (size_t k = J.first_set; k < J.first_set + J.nsets; k++) undecodable |= S.h_bad[k] != 0;
+        if (undecodable) { out[j].code = OTTI_ERR_VERIFY_DECOMPRESS; out[j].sum = pt_identity(); continue; }
+        const Pt *p = part.data() + out_off[j];
+        Pt acc = pt_identity();
+        for (int w = A.W - 1; w >= 0; w--) {
+            if (w != A.W - 1) for (int k = 0; k < A.c; k++) acc = pt_dbl(acc);
+            for (int sp = 0; sp < A.splits; sp++) acc = pt_add(acc, p[(size_t)w * A.splits + sp]);
+        }
+        out[j].code = 0; out[j].sum = acc;
+    }
+}
+const unsigned *dev_batch_sum_bad(DevCtx &c) { return c.batch_sum ? c.batch_sum->h_bad.data() : nullptr; }
 
 // ------------------------------------------------------------------------------------------------ the ALU roof of the MSM, measured
 // Whole-chip throughput of the mixed point addition the bulk MSM is made of (p9_madd of fp9.h — the form the bulk kernel uses —, operands in registers, every CU busy): what

@@ -144,7 +144,7 @@ void nizk_prove_many(Instance &I, Gens &g, const void *tlabel, size_t tlabel_len
 
     // ---- what the calling thread hands the workers.  A worker starts proof i only after the launches that write i's front buffers have COMPLETED:
     // the calling thread synchronises with the event behind the step and then publishes the item under the mutex (a host publish behind an event
-    // synchronise, as verify_many.cpp's Evals::publish does it), so the worker's stream needs no event of another context to wait on.  With one
+    // synchronise, as verify.h's ManyEvals::publish does it), so the worker's stream needs no event of another context to wait on.  With one
     // thread everything is on one stream, whose order does the same.
     struct Shared {
         std::mutex mu; std::condition_variable cv;

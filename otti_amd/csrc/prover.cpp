@@ -10,6 +10,7 @@
 #include "pool.h"
 #include "shard.h"
 #include "snark.h"
+#include "hostpar.h"
 #include <chrono>
 #include <cstring>
 #include <mutex>
@@ -174,8 +175,55 @@ static bool row_sums_many_on_device(const CompComm &comm, const RowRequest *req,
         return true;
     } catch (const Error &) { return false; }
 }
+// nizk_verify_batch's sum (spartan.h g_batch_sum_hook) on the calling thread's context: the proofs' distinct points as sets one behind the other,
+// the generators as a set decoded once per handle and kept on it.  First pass: one job over all sets and one over the generators with the merged
+// scalars.  Localisation: one job per set over what the first pass left decoded, and one per proof on the generator set.
+struct GensDecoded { DecodedSet set; };
+static std::shared_ptr<GensDecoded> gens_decoded(DevCtx &c, const Gens &g) {
+    std::lock_guard<std::mutex> lk(device_objects_mu());
+    if (!g.decoded) {
+        std::vector<uint8_t> comp(32 * g.P.size());
+        const unsigned nt = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+        fan_out(nt, [&](unsigned t) { for (size_t i = t; i < g.P.size(); i += nt) pt_encode(&comp[32 * i], g.P[i]); });
+        auto d = std::make_shared<GensDecoded>();
+        dev_decode_set(c, comp.data(), g.P.size(), d->set);
+        g.decoded = d;
+    }
+    return g.decoded;
+}
+static bool batch_sum_on_device(const Gens &g, const BatchSumSet *sets, size_t nsets, const Fr *gen_total, size_t ngens, bool localise, Pt *sums, uint8_t *set_bad, double *ms) {
+    try {
+        if (!nsets || ngens != g.P.size() || ngens > kRowSumMaxPoints) return false;
+        DevCtx &c = DevCtx::get();
+        std::shared_ptr<GensDecoded> gd = gens_decoded(c, g);            // held for the pass
+        if (gd->set.bad || gd->set.n != ngens) return false;
+        std::vector<size_t> off(nsets + 1, 0);
+        for (size_t k = 0; k < nsets; k++) off[k + 1] = off[k] + sets[k].n;
+        BatchSumIn in; in.set_off = off.data(); in.nsets = nsets; in.gens = gd->set.pts.p; in.ngens = ngens; in.reuse = localise;
+        std::vector<uint8_t> comp; std::vector<Fr> sc; std::vector<BatchSumJobIn> jobs; float t = 0;
+        if (!localise) {
+            comp.resize(32 * off[nsets]); sc.resize(off[nsets]);
+            for (size_t k = 0; k < nsets; k++) { memcpy(&comp[32 * off[k]], sets[k].comp32, 32 * sets[k].n); memcpy(&sc[off[k]], sets[k].scalars, sets[k].n * sizeof(Fr)); }
+            in.comp32 = comp.data();
+            jobs = {{0, nsets, sc.data()}, {nsets, 1, gen_total}};
+            RowSumOut out[2];
+            dev_batch_sum(c, in, jobs.data(), 2, out, &t);
+            const unsigned *bad = dev_batch_sum_bad(c);
+            for (size_t k = 0; k < nsets; k++) set_bad[k] = bad[k] != 0;
+            sums[0] = pt_add(out[0].sum, out[1].sum);
+        } else {
+            for (size_t k = 0; k < nsets; k++) jobs.push_back({k, 1, nullptr});
+            for (size_t k = 0; k < nsets; k++) jobs.push_back({nsets, 1, sets[k].gen_scalars});
+            std::vector<RowSumOut> out(2 * nsets);
+            dev_batch_sum(c, in, jobs.data(), jobs.size(), out.data(), &t);
+            for (size_t k = 0; k < nsets; k++) { set_bad[k] = out[k].code != 0; sums[k] = pt_add(out[k].sum, out[nsets + k].sum); }
+        }
+        if (ms) *ms = t;
+        return true;
+    } catch (const Error &) { return false; }
+}
 static const bool g_hook_registered = [] {
-    g_row_sums_many_hook = row_sums_many_on_device;
+    g_row_sums_many_hook = row_sums_many_on_device; g_batch_sum_hook = batch_sum_on_device;
     g_fixed_base_msm_hook = fixed_base_msm_on_device; g_row_sum_begin_hook = row_sum_begin_on_device; g_row_sum_finish_hook = row_sum_finish_on_device;
     return true;
 }();

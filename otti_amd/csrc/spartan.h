@@ -80,6 +80,7 @@ struct Gens {
     std::vector<int> small_slot;                            // P index -> slot in small_tables, or -1
     std::vector<FixedBaseTable> small_tables;               // host tables for P[0..4], P[R], P[R+1]
     std::shared_ptr<DeviceGens> dev;                        // device window table, built lazily
+    mutable std::shared_ptr<struct GensDecoded> decoded;    // P in the form the variable-base sums read, in HBM (prover.cpp batch_sum_on_device): made once, kept
     Pt commit_terms(const Term *t, size_t n) const;         // host, fixed-base tables only
     PtFe commit_terms_fe(const Term *t, size_t n) const;    // the same, staying in the five-limb form of the sequential path (hostfast.h)
     void commit_terms_c(uint8_t out[32], const Term *t, size_t n) const { Pt p = commit_terms(t, n); pt_encode(out, p); }
@@ -196,6 +197,30 @@ extern InstEvalManyBeginHook g_inst_eval_many_begin_hook;
 extern InstEvalManyNextHook g_inst_eval_many_next_hook;
 void nizk_verify_many(const Instance &inst, const Gens &g, const void *tlabel, size_t tlabel_len, const VerifyItem *items, size_t count,
                       unsigned threads, int32_t *results);
+
+// ---------------------------------------------------------------------------------------------- many proofs as one randomised batch (verify_batch.cpp)
+// results[i] = what nizk_verify returns for item i alone, except that a proof the single verifier rejects is accepted with probability at most
+// 2^-120 over the weights (drawn from a RandomTape: seed32, or OS entropy when null).  Item checks, parsing and the joint evaluation of A, B, C are
+// nizk_verify_many's.  The workers (no background threads) walk the live proofs with a collecting sink (verify.h TermSink): the transcript, the
+// hashed combinations and the row sum C_LZ run as ever, every group equation that feeds nothing hashed is stated as a term list instead of checked.
+// A proof that fails on its walk is settled with that code; one whose rx / ry differ from the transcript's goes to the single verifier, whose
+// failure order decides its code.  The calling thread gives every equation of every other proof a weight of its own and forms ONE sum: the
+// identity accepts them all; otherwise one localisation pass forms each proof's own sum and only the proofs whose sum is not the identity, or
+// whose points hold one that does not decode, are run through nizk_verify_parsed for their code.  The sum runs on the device through the hook
+// below (prover.cpp sets it) — at every size: its launches take 0.24 - 0.30 ms whatever the batch, the host cores 1 - 10 ms — and on the host cores
+// without a device, when it declines, under OTTI_VERIFY_HOST or under OTTI_VERIFY_BATCH_SUM=host (read per call: measurements, tests).
+struct BatchSumSet { const uint8_t *comp32; size_t n; const Fr *scalars; const Fr *gen_scalars; };   // one proof: n distinct points and their scalars; its own generator scalars (ngens)
+// localise false: sums[0] = sum over all sets + <gen_total, P>, set_bad[k] = set k holds a point that does not decode (it still contributes whatever
+// the decode left).  localise true — the same thread, the same sets, right after: sums[k] = set k's own sum + <its gen_scalars, P>.  false: declined.
+typedef bool (*BatchSumHook)(const Gens &g, const BatchSumSet *sets, size_t nsets, const Fr *gen_total, size_t ngens, bool localise, Pt *sums, uint8_t *set_bad, double *ms);
+extern BatchSumHook g_batch_sum_hook;
+// Both from profiles/verify_batch.md: eight workers are never slower than four beyond the spread and faster from K = 16 on (a worker owns no
+// background threads, so eight are steady where eight of nizk_verify_many's are erratic); fewer than three live proofs of an instance of 2^16
+// padded constraints or more take nizk_verify_many's path (faster there by 0.2 - 0.3 ms; at 2^12 the batch is, by as much).
+constexpr unsigned kVerifyBatchThreads = 8, kVerifyBatchMinLive = 3;
+constexpr size_t kVerifyBatchRouteMinCons = (size_t)1 << 16;
+void nizk_verify_batch(const Instance &inst, const Gens &g, const void *tlabel, size_t tlabel_len, const VerifyItem *items, size_t count,
+                       unsigned threads, const uint8_t *seed32, int32_t *results, otti_verify_batch_info *info);
 
 // ---------------------------------------------------------------------------------------------- prover (prover.cpp; GPU)
 struct ProveTimings { double ms[8]; };   // polycommit, multiply_vec, sc_phase_one, eval_table_sparse, sc_phase_two, polyeval, total, (spare)

@@ -320,6 +320,7 @@ void sumcheck_round_finish(ZKSumcheckProof &pf, size_t j, const RoundPart1 &p1, 
 // (the pieces other files build their verifiers from are declared in verify.h)
 Pt dec(const CPoint &c) { Pt p; if (!pt_decode_fast(p, c.b)) throw VerifyFail{OTTI_ERR_VERIFY_DECOMPRESS}; return p; }
 void require(bool ok) { if (!ok) throw VerifyFail{OTTI_ERR_VERIFY_INTERNAL}; }
+static inline Fr kMinusOne() { return fr_neg(fr_one()); }
 Pt commit_scalar_pt(const Gens &g, const GensView &g1, const Fr &x, const Fr &blind) { return g.commit_generic(&x, 1, blind, g1); }
 // Group equations that do not feed the transcript (most of the verifier's work: two scalar multiplications and a small MSM per
 // sum-check round) are collected here and checked at the end, spread over the host cores.  Each entry throws VerifyFail on failure.
@@ -366,6 +367,10 @@ void knowledge_verify(const KnowledgeProof &pf, const Gens &g, Transcript &tr, c
     tr.append_point("C", C.b); tr.append_point("alpha", pf.alpha.b);
     Fr c = tr.challenge_scalar("c");
     const KnowledgeProof *p = &pf; const Gens *gp = &g;
+    if (TermSink *t = later.sink) {                                       // z1 G + z2 h - c C - alpha
+        t->gen(pf.z1, g.sc_1.G[0]); t->gen(pf.z2, g.sc_1.h); t->point(fr_neg(c), C); t->point(kMinusOne(), pf.alpha); t->close();
+        return;
+    }
     later.push_back([=] { require(pt_eq(commit_scalar_pt(*gp, gp->sc_1, p->z1, p->z2), pt_add(host_scalarmul(dec(C), c), dec(p->alpha)))); });
 }
 void equality_verify(const EqualityProof &pf, const Gens &g, Transcript &tr, const CPoint &C1, const CPoint &C2, Deferred &later) {
@@ -373,6 +378,10 @@ void equality_verify(const EqualityProof &pf, const Gens &g, Transcript &tr, con
     tr.append_point("C1", C1.b); tr.append_point("C2", C2.b); tr.append_point("alpha", pf.alpha.b);
     Fr c = tr.challenge_scalar("c");
     const EqualityProof *p = &pf; const Gens *gp = &g;
+    if (TermSink *t = later.sink) {                                       // z h - c C1 + c C2 - alpha
+        t->gen(pf.z, g.sc_1.h); t->point(fr_neg(c), C1); t->point(c, C2); t->point(kMinusOne(), pf.alpha); t->close();
+        return;
+    }
     later.push_back([=] { require(pt_eq(host_scalarmul(gp->P[gp->sc_1.h], p->z), pt_add(host_scalarmul(pt_sub(dec(C1), dec(C2)), c), dec(p->alpha)))); });
 }
 bool product_check(const CPoint &P, const Pt &X, const Fr &c, const Pt &G, const Pt &h, const Fr &z1, const Fr &z2) {
@@ -386,6 +395,13 @@ void product_verify(const ProductProof &pf, const Gens &g, Transcript &tr, const
     tr.append_point("alpha", pf.alpha.b); tr.append_point("beta", pf.beta.b); tr.append_point("delta", pf.delta.b);
     Fr c = tr.challenge_scalar("c");
     const ProductProof *p = &pf; const Gens *gp = &g;
+    if (TermSink *t = later.sink) {                                       // product_check's  P + c X - z1 G - z2 h, three times; the third has G = X
+        const uint32_t G = g.sc_1.G[0], h = g.sc_1.h;
+        t->point(fr_one(), pf.alpha); t->point(c, X); t->gen(fr_neg(pf.z[0]), G); t->gen(fr_neg(pf.z[1]), h); t->close();
+        t->point(fr_one(), pf.beta); t->point(c, Y); t->gen(fr_neg(pf.z[2]), G); t->gen(fr_neg(pf.z[3]), h); t->close();
+        t->point(fr_one(), pf.delta); t->point(c, Z); t->point(fr_neg(pf.z[2]), X); t->gen(fr_neg(pf.z[4]), h); t->close();
+        return;
+    }
     later.push_back([=] { const Pt &G = gp->P[gp->sc_1.G[0]], &h = gp->P[gp->sc_1.h]; require(product_check(p->alpha, dec(X), c, G, h, p->z[0], p->z[1])); });
     later.push_back([=] { const Pt &G = gp->P[gp->sc_1.G[0]], &h = gp->P[gp->sc_1.h]; require(product_check(p->beta, dec(Y), c, G, h, p->z[2], p->z[3])); });
     later.push_back([=] { const Pt &h = gp->P[gp->sc_1.h]; require(product_check(p->delta, dec(Z), c, dec(X), h, p->z[2], p->z[4])); });
@@ -400,6 +416,13 @@ void dotproduct_verify(const DotProductProof &pf, const Gens &g, const GensView 
     Fr c = tr.challenge_scalar("c");
     Fr za = fr_zero(); for (size_t i = 0; i < n; i++) za = fr_add(za, fr_mul(pf.z[i], a[i]));
     const DotProductProof *p = &pf; const Gens *gp = &g; const GensView *gv = &gn;       // all outlive the deferred run (owned by nizk_verify's frame)
+    if (TermSink *t = later.sink) {                                       // c Cx + delta - <z, G> - z_delta h;  c Cy + beta - <z, a> G_1 - z_beta h_1
+        t->point(c, Cx); t->point(fr_one(), pf.delta);
+        for (size_t i = 0; i < n; i++) t->gen(fr_neg(pf.z[i]), gn.G[i]);
+        t->gen(fr_neg(pf.z_delta), gn.h); t->close();
+        t->point(c, Cy); t->point(fr_one(), pf.beta); t->gen(fr_neg(za), g.sc_1.G[0]); t->gen(fr_neg(pf.z_beta), g.sc_1.h); t->close();
+        return;
+    }
     later.push_back([=] { require(pt_eq(pt_add(host_scalarmul(dec(Cx), c), dec(p->delta)), gp->commit_generic(p->z.data(), n, p->z_delta, *gv))); });
     later.push_back([=] { require(pt_eq(pt_add(host_scalarmul(dec(Cy), c), dec(p->beta)), commit_scalar_pt(*gp, gp->sc_1, za, p->z_beta))); });
 }
@@ -481,9 +504,20 @@ void dotproductlog_verify(const DotProductProofLog &pf, size_t n, const Gens &g,
     for (size_t i = 0; i < lg; i++) { ch[i] = fr_sqr(ch[i]); chi[i] = fr_sqr(chi[i]); }
     std::vector<Fr> s(n); s[0] = allinv;
     for (size_t i = 1; i < n; i++) { size_t lg_i = ilog2(i + 1) - 1; size_t k = (size_t)1 << lg_i; s[i] = fr_mul(s[i - k], ch[(lg - 1) - lg_i]); }
+    Fr a_hat = fr_zero(); for (size_t i = 0; i < n; i++) a_hat = fr_add(a_hat, fr_mul(a[i], s[i]));
+    if (TermSink *t = later ? later->sink : nullptr) {
+        // the closing equation as terms, g_hat never summed:  c a_hat (sum ch_i L_i + sum chi_i R_i + Cx + Cy) + a_hat beta + delta
+        //                                                      - z1 sum s_i P_i - z1 a_hat G_1 - z2 h_1
+        const Fr ca = fr_mul(c, a_hat), mz1 = fr_neg(pf.z1);
+        for (size_t i = 0; i < lg; i++) { t->point(fr_mul(ca, ch[i]), pf.L_vec[i]); t->point(fr_mul(ca, chi[i]), pf.R_vec[i]); }
+        t->point(ca, Cx); t->point(ca, Cy); t->point(a_hat, pf.beta); t->point(fr_one(), pf.delta);
+        for (size_t i = 0; i < n; i++) t->gen(fr_mul(mz1, s[i]), (uint32_t)i);
+        t->gen(fr_mul(mz1, a_hat), v.g1); t->gen(fr_neg(pf.z2), v.h1); t->close();
+        lap("challenges, s, closing terms");
+        return;
+    }
     Pt g_hat;
     if (!(g_fixed_base_msm_hook && g_fixed_base_msm_hook(g, s.data(), n, g_hat))) g_hat = host_msm_wide(s.data(), g.P.data(), n);
-    Fr a_hat = fr_zero(); for (size_t i = 0; i < n; i++) a_hat = fr_add(a_hat, fr_mul(a[i], s[i]));
     lap("challenges, s, g_hat");
     const DotProductProofLog *p = &pf; const Gens *gp = &g;
     // the closing equation  ((Gamma_hat c + beta) a_hat + delta == (g_hat + a_hat G) z1 + z2 h)  as FOUR deferred jobs: the two halves of
@@ -520,7 +554,7 @@ void dotproductlog_verify(const DotProductProofLog &pf, size_t n, const Gens &g,
 }
 // R1CSProof::verify: `tr` already carries the caller's protocol name (NIZK / SNARK); returns the challenges the transcript produced
 int r1cs_verify_host(const NizkProof &P, size_t N, size_t V, const std::vector<Fr> &inputs, const Fr inst_evals_given[3], const Gens &g, Transcript &tr,
-                     std::vector<Fr> &rx, std::vector<Fr> &ry, const InstEvalFetch *fetch) {
+                     std::vector<Fr> &rx, std::vector<Fr> &ry, const InstEvalFetch *fetch, TermSink *sink) {
     try {
         const size_t nrx = ilog2(N), nry = ilog2(2 * V);
         size_t ell = ilog2(V), Lsz = (size_t)1 << (ell / 2), Rsz = (size_t)1 << (ell - ell / 2);
@@ -533,11 +567,11 @@ int r1cs_verify_host(const NizkProof &P, size_t N, size_t V, const std::vector<F
         CPoint claim_phase1; pt_encode(claim_phase1.b, commit_scalar_pt(g, g.sc_1, fr_zero(), fr_zero()));
         RowSum rows(P.comm_vars.data(), Lsz);                             // with a device: the row commitments start decompressing now
         PreDecoded pre1, pre2;                                            // declared before `later`: its workers fill them, so they must be destroyed after it
-        Deferred later;                                                   // P, g and the CPoints it captures live until run_deferred below
+        Deferred later(sink);                                             // P, g and the CPoints it captures live until run_deferred below
         SpinPool::Session pool_session;
         const bool trace = getenv("OTTI_TRACE") != nullptr; auto t_lap = std::chrono::steady_clock::now();
         auto lap = [&](const char *what) { if (!trace) return; const auto t = std::chrono::steady_clock::now(); fprintf(stderr, "[otti] r1cs_verify %-28s %.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_lap).count()); t_lap = t; };
-        if (P.sc1.comm_evals.size() == nrx && P.sc2.comm_evals.size() == nry) { pre1.start(P.sc1.comm_evals, later); pre2.start(P.sc2.comm_evals, later); }
+        if (!sink && P.sc1.comm_evals.size() == nrx && P.sc2.comm_evals.size() == nry) { pre1.start(P.sc1.comm_evals, later); pre2.start(P.sc2.comm_evals, later); }
         CPoint comm_post1 = sumcheck_verify(P.sc1, claim_phase1, nrx, 3, g, g.sc_4, tr, rx, later, pre1.src ? &pre1 : nullptr);
         lap("sum-check one");
         const CPoint &cAz = P.claims_phase2[0], &cBz = P.claims_phase2[1], &cCz = P.claims_phase2[2], &cPr = P.claims_phase2[3];

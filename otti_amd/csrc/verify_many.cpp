@@ -3,9 +3,7 @@
 #include "spartan.h"
 #include "verify.h"
 #include <atomic>
-#include <condition_variable>
 #include <memory>
-#include <mutex>
 #include <thread>
 
 namespace otti {
@@ -15,14 +13,6 @@ InstEvalManyNextHook g_inst_eval_many_next_hook = nullptr;
 
 namespace {
 struct Live { size_t item; std::vector<Fr> inputs; NizkProof P; };
-// what the calling thread hands the workers: the evaluation's values, tile by tile as they arrive
-struct Evals {
-    std::mutex mu; std::condition_variable cv;
-    size_t done = 0; bool failed = false;                     // triples of proofs [0, done) hold their values; failed: the rest evaluate on the host
-    std::vector<Fr> triples;                                  // 3 per live proof
-    void publish(size_t d, bool f) { { std::lock_guard<std::mutex> lk(mu); done = d; failed = f; } cv.notify_all(); }
-    bool wait(size_t k) { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return done > k || failed; }); return done > k; }
-};
 int verify_one(const Instance &I, const Gens &g, const void *tlabel, size_t tlabel_len, const Live &L, const InstEvalFetch *fetch) {
     try { return nizk_verify_parsed(I, L.inputs, g, tlabel, tlabel_len, L.P, nullptr, fetch); }
     catch (const Error &e) { return e.code; }
@@ -50,39 +40,20 @@ void nizk_verify_many(const Instance &I, const Gens &g, const void *tlabel, size
     }
     const size_t n = live.size();
     if (!n) return;
-    // ---- the batched evaluation, queued on this thread before any worker starts
-    bool queued = false;
-    if (I.num_cons >= 4096 && g_inst_eval_many_begin_hook && g_inst_eval_many_next_hook) {
-        std::vector<const NizkProof *> pts(n);
-        for (size_t k = 0; k < n; k++) pts[k] = &live[k]->P;
-        try { queued = g_inst_eval_many_begin_hook(I, pts); } catch (...) { queued = false; }
-    }
-    Evals ev;
-    if (queued) ev.triples.resize(3 * n); else ev.failed = true;
-    auto collect_next = [&] {                                 // on this thread: one more tile's values, published
-        long d = -1;
-        try { d = g_inst_eval_many_next_hook(reinterpret_cast<Fr (*)[3]>(ev.triples.data())); } catch (...) { d = -1; }
-        if (d < 0 || (size_t)d <= ev.done) ev.publish(ev.done, true); else ev.publish((size_t)d, false);
-    };
-    auto fetch_for = [&](size_t k) {
-        return InstEvalFetch([&ev, &live, &I, k](Fr out[3]) {
-            if (ev.wait(k)) { for (int j = 0; j < 3; j++) out[j] = ev.triples[3 * k + j]; return; }
-            I.evaluate(live[k]->P.rx, live[k]->P.ry, out);      // the device let go of the batch: this proof's own host evaluation
-        });
-    };
+    // ---- the batched evaluation, queued on this thread before any worker starts (verify.h ManyEvals)
+    std::vector<const NizkProof *> pts(n);
+    for (size_t k = 0; k < n; k++) pts[k] = &live[k]->P;
+    ManyEvals ev(I, std::move(pts));
+    const bool queued = ev.queued;
     if (!threads) threads = kVerifyManyThreads;
     const size_t nw = std::min<size_t>({(size_t)threads, (size_t)kVerifyManyMaxThreads, n});
     if (nw <= 1) {
         // one worker: the calling thread, in the single path's order — the evaluation is collected where the first proof needs it
         for (size_t k = 0; k < n; k++) {
-            const InstEvalFetch fetch([&](Fr out[3]) {
-                while (!ev.failed && ev.done <= k) collect_next();
-                if (ev.done > k) { for (int j = 0; j < 3; j++) out[j] = ev.triples[3 * k + j]; return; }
-                I.evaluate(live[k]->P.rx, live[k]->P.ry, out);
-            });
+            const InstEvalFetch fetch([&ev, k](Fr out[3]) { ev.fetch_on_caller(k, out); });
             results[live[k]->item] = verify_one(I, g, tlabel, tlabel_len, *live[k], queued ? &fetch : nullptr);
         }
-        while (!ev.failed && ev.done < n) collect_next();     // proofs that failed before their closing step: the queued work still has to drain
+        ev.collect_rest();
         return;
     }
     // ---- workers take the live proofs in order, one at a time; each verdict goes to its own item's slot
@@ -93,18 +64,18 @@ void nizk_verify_many(const Instance &I, const Gens &g, const void *tlabel, size
             if (k >= n) return;
             int rc;
             try {
-                const InstEvalFetch fetch = fetch_for(k);
+                const InstEvalFetch fetch([&ev, k](Fr out[3]) { ev.fetch_on_worker(k, out); });
                 rc = verify_one(I, g, tlabel, tlabel_len, *live[k], queued ? &fetch : nullptr);
             } catch (...) { rc = OTTI_ERR_INTERNAL; }
             results[live[k]->item] = rc;
         }
     };
     std::vector<std::thread> th; th.reserve(nw);
-    struct Join { std::vector<std::thread> &th; Evals &ev; ~Join() { if (ev.done * 3 < ev.triples.size() && !ev.failed) ev.publish(ev.done, true); for (auto &t : th) if (t.joinable()) t.join(); } } join{th, ev};
+    struct Join { std::vector<std::thread> &th; ManyEvals &ev; ~Join() { ev.let_go(); for (auto &t : th) if (t.joinable()) t.join(); } } join{th, ev};
     for (size_t w = 0; w < nw; w++) {
         try { th.emplace_back(work); } catch (const std::system_error &) { break; }      // short of threads: those that started share the work
     }
-    while (!ev.failed && ev.done < n) collect_next();
+    ev.collect_rest();
     if (th.empty()) work();
 }
 
