@@ -1,5 +1,6 @@
 // The group equations of a batch of proofs as one weighted sum (verify_batch.cpp): every check the verifier does not hash has the form
-// sum_j s_j * P_j = identity, stated as a list of terms — a scalar with either a point, named by its 32-byte encoding, or a generator slot.  An
+// sum_j s_j * P_j = identity, stated as a list of terms — a scalar with either a point, named by its 32-byte encoding, or a generator slot.  The
+// verifiers state each equation as such a list and nothing else: the single verifier sums it (verify.h term_sum), the batch collects it.  An
 // equation that fails leaves an error point E != identity; under independent uniform weights w the weighted sum  sum_k w_k E_k  is the identity
 // with probability 1 / l only, whatever the E_k are: two defects cannot cancel unless they share a weight, which is why every equation of every
 // proof has its own.  This header does the scalar side of that — it multiplies the weights in, merges the terms that name the same point
@@ -18,12 +19,15 @@ namespace otti {
 
 typedef std::array<uint8_t, 32> BtKey;
 struct BtTerm { Fr s; int32_t gen; BtKey key; };            // gen >= 0: generator slot `gen`; gen < 0: the point whose encoding is `key`
+inline BtTerm bt_point(const Fr &s, const uint8_t enc[32]) { BtTerm t; t.s = s; t.gen = -1; memcpy(t.key.data(), enc, 32); return t; }
+inline BtTerm bt_gen(const Fr &s, uint32_t slot) { BtTerm t; t.s = s; t.gen = (int32_t)slot; t.key.fill(0); return t; }
 // one proof's equations in the order they arose: equation k is terms [eq[k], eq[k + 1])
 struct BtEquations {
     std::vector<BtTerm> terms; std::vector<uint32_t> eq{0};
-    void point(const Fr &s, const uint8_t enc[32]) { BtTerm t; t.s = s; t.gen = -1; memcpy(t.key.data(), enc, 32); terms.push_back(t); }
-    void gen(const Fr &s, uint32_t slot) { BtTerm t; t.s = s; t.gen = (int32_t)slot; t.key.fill(0); terms.push_back(t); }
+    void point(const Fr &s, const uint8_t enc[32]) { terms.push_back(bt_point(s, enc)); }
+    void gen(const Fr &s, uint32_t slot) { terms.push_back(bt_gen(s, slot)); }
     void close() { eq.push_back((uint32_t)terms.size()); }   // the terms since the last close() are one equation (an empty one holds trivially)
+    void equation(const std::vector<BtTerm> &e) { terms.insert(terms.end(), e.begin(), e.end()); close(); }
     size_t count() const { return eq.size() - 1; }
 };
 // one proof's equations under their weights: a scalar per distinct point, in the order of first appearance, and a scalar per generator slot

@@ -201,8 +201,8 @@ void nizk_verify_many(const Instance &inst, const Gens &g, const void *tlabel, s
 // ---------------------------------------------------------------------------------------------- many proofs as one randomised batch (verify_batch.cpp)
 // results[i] = what nizk_verify returns for item i alone, except that a proof the single verifier rejects is accepted with probability at most
 // 2^-120 over the weights (drawn from a RandomTape: seed32, or OS entropy when null).  Item checks, parsing and the joint evaluation of A, B, C are
-// nizk_verify_many's.  The workers (no background threads) walk the live proofs with a collecting sink (verify.h TermSink): the transcript, the
-// hashed combinations and the row sum C_LZ run as ever, every group equation that feeds nothing hashed is stated as a term list instead of checked.
+// nizk_verify_many's.  The workers (no background threads) walk the live proofs with a collecting sink (verify.h Deferred::equation): the transcript, the
+// hashed combinations and the row sum C_LZ run as ever, every group equation that feeds nothing hashed is appended as its term list instead of run.
 // A proof that fails on its walk is settled with that code; one whose rx / ry differ from the transcript's goes to the single verifier, whose
 // failure order decides its code.  The calling thread gives every equation of every other proof a weight of its own and forms ONE sum: the
 // identity accepts them all; otherwise one localisation pass forms each proof's own sum and only the proofs whose sum is not the identity, or

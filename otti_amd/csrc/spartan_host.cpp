@@ -321,9 +321,8 @@ void sumcheck_round_finish(ZKSumcheckProof &pf, size_t j, const RoundPart1 &p1, 
 Pt dec(const CPoint &c) { Pt p; if (!pt_decode_fast(p, c.b)) throw VerifyFail{OTTI_ERR_VERIFY_DECOMPRESS}; return p; }
 void require(bool ok) { if (!ok) throw VerifyFail{OTTI_ERR_VERIFY_INTERNAL}; }
 static inline Fr kMinusOne() { return fr_neg(fr_one()); }
-Pt commit_scalar_pt(const Gens &g, const GensView &g1, const Fr &x, const Fr &blind) { return g.commit_generic(&x, 1, blind, g1); }
-// Group equations that do not feed the transcript (most of the verifier's work: two scalar multiplications and a small MSM per
-// sum-check round) are collected here and checked at the end, spread over the host cores.  Each entry throws VerifyFail on failure.
+// a commitment the sequential path hashes or multiplies on (r1cs_verify_host)
+static Pt commit_scalar_pt(const Gens &g, const GensView &g1, const Fr &x, const Fr &blind) { return g.commit_generic(&x, 1, blind, g1); }
 // a sum over many points, split over the host cores (the verifier's two sqrt(V)-sized multi-scalar multiplications)
 Pt host_msm_wide(const Fr *sc, const Pt *pts, size_t n) {
     const size_t nt = std::min<size_t>({n / 128, (size_t)16, (size_t)std::max(1u, std::thread::hardware_concurrency())});
@@ -360,51 +359,38 @@ Pt row_sum_on_host(const CPoint *C, size_t n, const Fr *s, bool wide) {
     }
     return host_msm_wide(s, Cs.data(), n);
 }
-void run_deferred(Deferred &d) { d.finish(); }
+Pt term_sum(const BtTerm *t, size_t n, const Gens &g) {
+    std::vector<Fr> s(n); std::vector<Pt> P(n);
+    for (size_t i = 0; i < n; i++) {
+        s[i] = t[i].s;
+        if (t[i].gen < 0) { if (!pt_decode_fast(P[i], t[i].key.data())) throw VerifyFail{OTTI_ERR_VERIFY_DECOMPRESS}; }
+        else { require((size_t)t[i].gen < g.P.size()); P[i] = g.P[t[i].gen]; }
+    }
+    return host_msm(s.data(), P.data(), n);
+}
 
 void knowledge_verify(const KnowledgeProof &pf, const Gens &g, Transcript &tr, const CPoint &C, Deferred &later) {
     tr.append_protocol_name("knowledge proof");
     tr.append_point("C", C.b); tr.append_point("alpha", pf.alpha.b);
     Fr c = tr.challenge_scalar("c");
-    const KnowledgeProof *p = &pf; const Gens *gp = &g;
-    if (TermSink *t = later.sink) {                                       // z1 G + z2 h - c C - alpha
-        t->gen(pf.z1, g.sc_1.G[0]); t->gen(pf.z2, g.sc_1.h); t->point(fr_neg(c), C); t->point(kMinusOne(), pf.alpha); t->close();
-        return;
-    }
-    later.push_back([=] { require(pt_eq(commit_scalar_pt(*gp, gp->sc_1, p->z1, p->z2), pt_add(host_scalarmul(dec(C), c), dec(p->alpha)))); });
+    later.equation(g, {term(pf.z1, g.sc_1.G[0]), term(pf.z2, g.sc_1.h), term(fr_neg(c), C), term(kMinusOne(), pf.alpha)});   // z1 G + z2 h - c C - alpha
 }
 void equality_verify(const EqualityProof &pf, const Gens &g, Transcript &tr, const CPoint &C1, const CPoint &C2, Deferred &later) {
     tr.append_protocol_name("equality proof");
     tr.append_point("C1", C1.b); tr.append_point("C2", C2.b); tr.append_point("alpha", pf.alpha.b);
     Fr c = tr.challenge_scalar("c");
-    const EqualityProof *p = &pf; const Gens *gp = &g;
-    if (TermSink *t = later.sink) {                                       // z h - c C1 + c C2 - alpha
-        t->gen(pf.z, g.sc_1.h); t->point(fr_neg(c), C1); t->point(c, C2); t->point(kMinusOne(), pf.alpha); t->close();
-        return;
-    }
-    later.push_back([=] { require(pt_eq(host_scalarmul(gp->P[gp->sc_1.h], p->z), pt_add(host_scalarmul(pt_sub(dec(C1), dec(C2)), c), dec(p->alpha)))); });
-}
-bool product_check(const CPoint &P, const Pt &X, const Fr &c, const Pt &G, const Pt &h, const Fr &z1, const Fr &z2) {
-    Pt lhs = pt_add(dec(P), host_scalarmul(X, c));
-    Pt rhs = pt_add(host_scalarmul(G, z1), host_scalarmul(h, z2));
-    return pt_eq(lhs, rhs);
+    later.equation(g, {term(pf.z, g.sc_1.h), term(fr_neg(c), C1), term(c, C2), term(kMinusOne(), pf.alpha)});                  // z h - c C1 + c C2 - alpha
 }
 void product_verify(const ProductProof &pf, const Gens &g, Transcript &tr, const CPoint &X, const CPoint &Y, const CPoint &Z, Deferred &later) {
     tr.append_protocol_name("product proof");
     tr.append_point("X", X.b); tr.append_point("Y", Y.b); tr.append_point("Z", Z.b);
     tr.append_point("alpha", pf.alpha.b); tr.append_point("beta", pf.beta.b); tr.append_point("delta", pf.delta.b);
     Fr c = tr.challenge_scalar("c");
-    const ProductProof *p = &pf; const Gens *gp = &g;
-    if (TermSink *t = later.sink) {                                       // product_check's  P + c X - z1 G - z2 h, three times; the third has G = X
-        const uint32_t G = g.sc_1.G[0], h = g.sc_1.h;
-        t->point(fr_one(), pf.alpha); t->point(c, X); t->gen(fr_neg(pf.z[0]), G); t->gen(fr_neg(pf.z[1]), h); t->close();
-        t->point(fr_one(), pf.beta); t->point(c, Y); t->gen(fr_neg(pf.z[2]), G); t->gen(fr_neg(pf.z[3]), h); t->close();
-        t->point(fr_one(), pf.delta); t->point(c, Z); t->point(fr_neg(pf.z[2]), X); t->gen(fr_neg(pf.z[4]), h); t->close();
-        return;
-    }
-    later.push_back([=] { const Pt &G = gp->P[gp->sc_1.G[0]], &h = gp->P[gp->sc_1.h]; require(product_check(p->alpha, dec(X), c, G, h, p->z[0], p->z[1])); });
-    later.push_back([=] { const Pt &G = gp->P[gp->sc_1.G[0]], &h = gp->P[gp->sc_1.h]; require(product_check(p->beta, dec(Y), c, G, h, p->z[2], p->z[3])); });
-    later.push_back([=] { const Pt &h = gp->P[gp->sc_1.h]; require(product_check(p->delta, dec(Z), c, dec(X), h, p->z[2], p->z[4])); });
+    // P + c X - z1 G - z2 h, three times; the third has G = X
+    const uint32_t G = g.sc_1.G[0], h = g.sc_1.h; const Fr one = fr_one();
+    later.equation(g, {term(one, pf.alpha), term(c, X), term(fr_neg(pf.z[0]), G), term(fr_neg(pf.z[1]), h)});
+    later.equation(g, {term(one, pf.beta), term(c, Y), term(fr_neg(pf.z[2]), G), term(fr_neg(pf.z[3]), h)});
+    later.equation(g, {term(one, pf.delta), term(c, Z), term(fr_neg(pf.z[2]), X), term(fr_neg(pf.z[4]), h)});
 }
 void dotproduct_verify(const DotProductProof &pf, const Gens &g, const GensView &gn, Transcript &tr, const Fr *a, size_t n,
                        const CPoint &Cx, const CPoint &Cy, Deferred &later) {
@@ -415,16 +401,12 @@ void dotproduct_verify(const DotProductProof &pf, const Gens &g, const GensView 
     tr.append_point("delta", pf.delta.b); tr.append_point("beta", pf.beta.b);
     Fr c = tr.challenge_scalar("c");
     Fr za = fr_zero(); for (size_t i = 0; i < n; i++) za = fr_add(za, fr_mul(pf.z[i], a[i]));
-    const DotProductProof *p = &pf; const Gens *gp = &g; const GensView *gv = &gn;       // all outlive the deferred run (owned by nizk_verify's frame)
-    if (TermSink *t = later.sink) {                                       // c Cx + delta - <z, G> - z_delta h;  c Cy + beta - <z, a> G_1 - z_beta h_1
-        t->point(c, Cx); t->point(fr_one(), pf.delta);
-        for (size_t i = 0; i < n; i++) t->gen(fr_neg(pf.z[i]), gn.G[i]);
-        t->gen(fr_neg(pf.z_delta), gn.h); t->close();
-        t->point(c, Cy); t->point(fr_one(), pf.beta); t->gen(fr_neg(za), g.sc_1.G[0]); t->gen(fr_neg(pf.z_beta), g.sc_1.h); t->close();
-        return;
-    }
-    later.push_back([=] { require(pt_eq(pt_add(host_scalarmul(dec(Cx), c), dec(p->delta)), gp->commit_generic(p->z.data(), n, p->z_delta, *gv))); });
-    later.push_back([=] { require(pt_eq(pt_add(host_scalarmul(dec(Cy), c), dec(p->beta)), commit_scalar_pt(*gp, gp->sc_1, za, p->z_beta))); });
+    // c Cx + delta - <z, G> - z_delta h;  c Cy + beta - <z, a> G_1 - z_beta h_1
+    std::vector<BtTerm> e = {term(c, Cx), term(fr_one(), pf.delta)};
+    for (size_t i = 0; i < n; i++) e.push_back(term(fr_neg(pf.z[i]), gn.G[i]));
+    e.push_back(term(fr_neg(pf.z_delta), gn.h));
+    later.equation(g, std::move(e));
+    later.equation(g, {term(c, Cy), term(fr_one(), pf.beta), term(fr_neg(za), g.sc_1.G[0]), term(fr_neg(pf.z_beta), g.sc_1.h)});
 }
 // The commitments a sum-check's rounds decompress ON the sequential path (comm_evals: each one is combined with a challenge and the
 // result is hashed before the next round can start) are decompressed ahead of it by the background threads, one per task; the round
@@ -477,8 +459,8 @@ CPoint sumcheck_verify(const ZKSumcheckProof &pf, const CPoint &comm_claim, size
 // takes the sum from one small MSM launch instead of a host Pippenger over n points.  Without it (no device, no table) nothing changes.
 FixedBaseMsmHook g_fixed_base_msm_hook = nullptr;
 // BulletReductionProof::verify + the closing equation of DotProductProofLog::verify.  The transcript part (the round challenges, then c)
-// and the fixed-base sum g_hat (device, when the prover's table is resident) run on the calling thread; Gamma_hat — a variable-base sum
-// over the 2 log n proof points — and the closing group equation feed nothing that is hashed, so with `later` they become one more
+// and the fixed-base part of the closing equation (device, when the prover's table is resident) run on the calling thread; the rest of that
+// equation — a variable-base sum over the 2 log n + 4 proof points — feeds nothing that is hashed, so with `later` it becomes one more
 // deferred check (spartan.h verifiers: SNARK mode has three of these proofs in a row).
 void dotproductlog_verify(const DotProductProofLog &pf, size_t n, const Gens &g, const PcView &v, Transcript &tr, const Fr *a, const CPoint &Cx, const CPoint &Cy, Deferred *later) {
     require(v.R == n && g.P.size() >= n + 2);
@@ -505,56 +487,45 @@ void dotproductlog_verify(const DotProductProofLog &pf, size_t n, const Gens &g,
     std::vector<Fr> s(n); s[0] = allinv;
     for (size_t i = 1; i < n; i++) { size_t lg_i = ilog2(i + 1) - 1; size_t k = (size_t)1 << lg_i; s[i] = fr_mul(s[i - k], ch[(lg - 1) - lg_i]); }
     Fr a_hat = fr_zero(); for (size_t i = 0; i < n; i++) a_hat = fr_add(a_hat, fr_mul(a[i], s[i]));
-    if (TermSink *t = later ? later->sink : nullptr) {
-        // the closing equation as terms, g_hat never summed:  c a_hat (sum ch_i L_i + sum chi_i R_i + Cx + Cy) + a_hat beta + delta
-        //                                                      - z1 sum s_i P_i - z1 a_hat G_1 - z2 h_1
-        const Fr ca = fr_mul(c, a_hat), mz1 = fr_neg(pf.z1);
-        for (size_t i = 0; i < lg; i++) { t->point(fr_mul(ca, ch[i]), pf.L_vec[i]); t->point(fr_mul(ca, chi[i]), pf.R_vec[i]); }
-        t->point(ca, Cx); t->point(ca, Cy); t->point(a_hat, pf.beta); t->point(fr_one(), pf.delta);
-        for (size_t i = 0; i < n; i++) t->gen(fr_mul(mz1, s[i]), (uint32_t)i);
-        t->gen(fr_mul(mz1, a_hat), v.g1); t->gen(fr_neg(pf.z2), v.h1); t->close();
-        lap("challenges, s, closing terms");
-        return;
-    }
+    // the closing equation:  c a_hat (sum ch_i L_i + sum chi_i R_i + Cx + Cy) + a_hat beta + delta - z1 sum s_i P_i - z1 a_hat G_1 - z2 h_1
+    const bool collect = later && later->sink;
+    const Fr ca = fr_mul(c, a_hat), mz1 = fr_neg(pf.z1);
+    std::vector<BtTerm> e; e.reserve(2 * lg + 6 + (collect ? n : 0));
+    for (size_t i = 0; i < lg; i++) { e.push_back(term(fr_mul(ca, ch[i]), pf.L_vec[i])); e.push_back(term(fr_mul(ca, chi[i]), pf.R_vec[i])); }
+    e.push_back(term(ca, Cx)); e.push_back(term(ca, Cy)); e.push_back(term(a_hat, pf.beta)); e.push_back(term(fr_one(), pf.delta));
+    const size_t np = e.size();                                           // 2 lg + 4 point terms, then the generator terms, then G_1 and h_1
+    // The generator terms  -z1 s_i P_i  are written out only for a collector.  Run, they are  -z1 g_hat  with  g_hat = sum s_i P_i  taken below:
+    // n products by -z1 on this thread, which is the sequential path, measured 0.2 - 0.35 ms on a SNARK verification (three of these proofs).
+    if (collect) for (size_t i = 0; i < n; i++) e.push_back(term(fr_mul(mz1, s[i]), (uint32_t)i));
+    e.push_back(term(fr_mul(mz1, a_hat), v.g1)); e.push_back(term(fr_neg(pf.z2), v.h1));
+    if (collect) { later->sink->equation(e); lap("challenges, s, closing terms"); return; }
+    // Summed in three parts.  g_hat on this thread: a fixed-base sum, from the device when the prover's table is resident (the hook is not
+    // called from a worker).  The point terms in two halves, G_1 and h_1 with the second, as two deferred jobs side by side; a third job
+    // scales g_hat, waits for them (jobs are claimed in order, so the two are under way or done when it starts) and tests the whole sum.
     Pt g_hat;
     if (!(g_fixed_base_msm_hook && g_fixed_base_msm_hook(g, s.data(), n, g_hat))) g_hat = host_msm_wide(s.data(), g.P.data(), n);
     lap("challenges, s, g_hat");
-    const DotProductProofLog *p = &pf; const Gens *gp = &g;
-    // the closing equation  ((Gamma_hat c + beta) a_hat + delta == (g_hat + a_hat G) z1 + z2 h)  as FOUR deferred jobs: the two halves of
-    // Gamma_hat (log n decompressions and a small variable-base sum each) and the right-hand side run side by side on the workers, the
-    // fourth job waits for them (jobs are claimed in order, so the three are under way or done when it starts) and finishes the chain.
-    struct Closing { Pt half[2], rhs; std::atomic<int> done{0}, ok{0}; };
+    struct Closing { Pt half[2]; std::atomic<int> done{0}, ok{0}; };
     struct Arrive { Closing &c; bool good = false; ~Arrive() { if (good) c.ok.fetch_add(1, std::memory_order_release); c.done.fetch_add(1, std::memory_order_release); } };
     auto st = std::make_shared<Closing>();
-    auto half = [=](int which) {
-        Arrive arr{*st};
-        std::vector<Pt> pts(lg + 1); std::vector<Fr> sc(which ? chi : ch);
-        for (size_t i = 0; i < lg; i++) pts[i] = dec(which ? p->R_vec[i] : p->L_vec[i]);
-        if (which == 0) { sc.push_back(fr_one()); pts[lg] = pt_add(dec(Cx), dec(Cy)); }
-        st->half[which] = host_msm(sc.data(), pts.data(), sc.size());
-        arr.good = true;
-    };
-    auto right = [=] {
-        Arrive arr{*st};
-        st->rhs = pt_add(host_scalarmul(pt_add(g_hat, host_scalarmul(gp->P[v.g1], a_hat)), p->z1), host_scalarmul(gp->P[v.h1], p->z2));
-        arr.good = true;
-    };
-    auto closing = [=] {
-        while (st->done.load(std::memory_order_acquire) < 3) {
+    auto hand = [&](std::function<void()> job) { if (later) later->push_back(std::move(job)); else job(); };
+    for (int which = 0; which < 2; which++) {
+        std::vector<BtTerm> t(e.begin() + which * (np / 2), which ? e.end() : e.begin() + np / 2);
+        hand([st, which, gp = &g, t = std::move(t)] { Arrive arr{*st}; st->half[which] = term_sum(t.data(), t.size(), *gp); arr.good = true; });
+    }
+    hand([st, g_hat, mz1] {
+        const Pt g_part = host_scalarmul(g_hat, mz1);
+        while (st->done.load(std::memory_order_acquire) < 2) {
             cpu_relax();
         }
-        if (st->ok.load(std::memory_order_acquire) < 3) return;            // the job that failed has reported why
-        const Pt Gamma_hat = pt_add(st->half[0], st->half[1]);
-        const Pt lhs = pt_add(host_scalarmul(pt_add(host_scalarmul(Gamma_hat, c), dec(p->beta)), a_hat), dec(p->delta));
-        require(pt_eq(lhs, st->rhs));
-    };
-    if (later) { later->push_back([=] { half(0); }); later->push_back([=] { half(1); }); later->push_back(right); later->push_back(closing); }
-    else { half(0); half(1); right(); closing(); }
+        if (st->ok.load(std::memory_order_acquire) < 2) return;            // the job that failed has reported why
+        require_identity(pt_add(pt_add(st->half[0], st->half[1]), g_part));
+    });
     lap(later ? "closing equation (deferred)" : "Gamma_hat, closing equation");
 }
 // R1CSProof::verify: `tr` already carries the caller's protocol name (NIZK / SNARK); returns the challenges the transcript produced
 int r1cs_verify_host(const NizkProof &P, size_t N, size_t V, const std::vector<Fr> &inputs, const Fr inst_evals_given[3], const Gens &g, Transcript &tr,
-                     std::vector<Fr> &rx, std::vector<Fr> &ry, const InstEvalFetch *fetch, TermSink *sink) {
+                     std::vector<Fr> &rx, std::vector<Fr> &ry, const InstEvalFetch *fetch, BtEquations *sink) {
     try {
         const size_t nrx = ilog2(N), nry = ilog2(2 * V);
         size_t ell = ilog2(V), Lsz = (size_t)1 << (ell / 2), Rsz = (size_t)1 << (ell - ell / 2);
@@ -567,7 +538,7 @@ int r1cs_verify_host(const NizkProof &P, size_t N, size_t V, const std::vector<F
         CPoint claim_phase1; pt_encode(claim_phase1.b, commit_scalar_pt(g, g.sc_1, fr_zero(), fr_zero()));
         RowSum rows(P.comm_vars.data(), Lsz);                             // with a device: the row commitments start decompressing now
         PreDecoded pre1, pre2;                                            // declared before `later`: its workers fill them, so they must be destroyed after it
-        Deferred later(sink);                                             // P, g and the CPoints it captures live until run_deferred below
+        Deferred later(sink);
         SpinPool::Session pool_session;
         const bool trace = getenv("OTTI_TRACE") != nullptr; auto t_lap = std::chrono::steady_clock::now();
         auto lap = [&](const char *what) { if (!trace) return; const auto t = std::chrono::steady_clock::now(); fprintf(stderr, "[otti] r1cs_verify %-28s %.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_lap).count()); t_lap = t; };
@@ -615,7 +586,7 @@ int r1cs_verify_host(const NizkProof &P, size_t N, size_t V, const std::vector<F
         CPoint expected2; pt_encode(expected2.b, host_scalarmul(comm_eval_Z, comb));
         equality_verify(P.eq2, g, tr, expected2, comm_post2, later);
         lap("log dot-product proof + rest");
-        run_deferred(later);
+        later.finish();
         lap("deferred group equations");
         return OTTI_OK;
     } catch (const VerifyFail &f) { return f.code; }

@@ -1,5 +1,5 @@
-// The host verifiers' toolkit, defined in spartan_host.cpp: what NIZK::verify, SNARK::verify (snark_host.cpp) and the two batched verifiers
-// (verify_many.cpp, snark_verify_many.cpp) are all built from.
+// The host verifiers' toolkit, defined in spartan_host.cpp: what NIZK::verify, SNARK::verify (snark_host.cpp) and the batched verifiers
+// (verify_many.cpp, verify_batch.cpp, snark_verify_many.cpp) are all built from.
 #pragma once
 #include "spartan.h"
 #include "cpu_relax.h"
@@ -8,6 +8,7 @@
 #include <atomic>
 #include <condition_variable>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <system_error>
 #include <thread>
@@ -29,15 +30,18 @@ struct RowSum {
     ~RowSum();
     Pt finish(const Fr *s);
 };
-// The same equations stated instead of run: each site that hands a check to Deferred below also knows it as a term list  sum_j s_j P_j = identity
-// (batch_terms.h), and a Deferred built over a TermSink takes that list and no closure — nothing is decoded, multiplied or compared on the walk.
-// verify_batch.cpp sums the lists of many proofs under random weights in one multi-scalar multiplication.
-struct TermSink : BtEquations {
-    using BtEquations::point;
-    void point(const Fr &s, const CPoint &c) { BtEquations::point(s, c.b); }
-};
+// A group equation that feeds nothing hashed is stated ONCE, as a term list  sum_j s_j P_j = identity  (batch_terms.h): a scalar with a point, named
+// by its 32-byte encoding, or with a generator slot of g.P.  Deferred::equation below either runs the list (term_sum, then the identity test) or,
+// built over a BtEquations, appends it and runs nothing — verify_batch.cpp sums the lists of many proofs under random weights in one
+// multi-scalar multiplication.  A list owns its encodings: nothing it names has to outlive the site that stated it.
+inline BtTerm term(const Fr &s, const CPoint &c) { return bt_point(s, c.b); }
+inline BtTerm term(const Fr &s, uint32_t slot) { return bt_gen(s, slot); }
+// the sum of n terms, in one host_msm.  Throws VerifyFail: OTTI_ERR_VERIFY_DECOMPRESS for an encoding that does not decode,
+// OTTI_ERR_VERIFY_INTERNAL for a slot past g.P
+Pt term_sum(const BtTerm *t, size_t n, const Gens &g);
+inline void require_identity(const Pt &sum) { require(pt_eq(sum, pt_identity())); }
 // Group equations that do not feed the transcript — most of the verifier's arithmetic: per sum-check round two checks with a
-// variable-base scalar multiplication each — are handed to a few background threads AS THEY ARISE, while the calling thread walks on
+// small multi-scalar multiplication each — are handed to a few background threads AS THEY ARISE, while the calling thread walks on
 // through the rounds (whose hashed commitments are the sequential path); finish() drains what is left and reports the first failure — the
 // failing check that was handed over EARLIEST, whichever thread found its failure first: a proof with several defects gets one code, the same in
 // every run and beside any number of other verifiers (verify_many.cpp holds its results against the single verifier's, code for code).
@@ -53,11 +57,16 @@ public:
         if (workers >= 0) nw = (unsigned)workers;
         try { for (unsigned i = 0; i < nw; i++) th_.emplace_back([this] { work(false); }); } catch (const std::system_error &) {}
     }
-    // collecting: no threads, no closures — the sites state their checks to `s` (nullptr: the default rule above, as Deferred())
-    explicit Deferred(TermSink *s) : Deferred(s ? 0 : -1) { sink = s; }
-    TermSink *sink = nullptr;
+    // collecting: no threads, and equation() appends to `s` instead of running (nullptr: the default rule above, as Deferred())
+    explicit Deferred(BtEquations *s) : Deferred(s ? 0 : -1) { sink = s; }
+    BtEquations *sink = nullptr;
     Deferred(const Deferred &) = delete; Deferred &operator=(const Deferred &) = delete;
     ~Deferred() { closing_.store(true, std::memory_order_release); for (auto &t : th_) t.join(); }
+    // one group equation, one slot: the job owns the list
+    void equation(const Gens &g, std::vector<BtTerm> e) {
+        if (sink) { sink->equation(e); return; }
+        push_back([gp = &g, e = std::move(e)] { require_identity(term_sum(e.data(), e.size(), *gp)); });
+    }
     void push_back(std::function<void()> f) {
         const size_t c = count_.load(std::memory_order_relaxed);
         if (c >= kSlots) { run_one(f, kSlots); return; }                          // (never in practice: two checks per round, at most 2 x 64 rounds + a few)
@@ -95,6 +104,11 @@ private:
         }
     }
 };
+// the sigma protocols' verifiers (nizk/mod.rs): the transcript part runs, the group equations go to `later`
+void knowledge_verify(const KnowledgeProof &pf, const Gens &g, Transcript &tr, const CPoint &C, Deferred &later);
+void equality_verify(const EqualityProof &pf, const Gens &g, Transcript &tr, const CPoint &C1, const CPoint &C2, Deferred &later);
+void product_verify(const ProductProof &pf, const Gens &g, Transcript &tr, const CPoint &X, const CPoint &Y, const CPoint &Z, Deferred &later);
+void dotproduct_verify(const DotProductProof &pf, const Gens &g, const GensView &gn, Transcript &tr, const Fr *a, size_t n, const CPoint &Cx, const CPoint &Cy, Deferred &later);
 void dotproductlog_verify(const DotProductProofLog &pf, size_t n, const Gens &g, const PcView &v, Transcript &tr, const Fr *a, const CPoint &Cx, const CPoint &Cy, Deferred *later = nullptr);
 // RowSum's host path alone: decompression and Pippenger on the host cores.  wide: striped over up to 16 threads of its own (the single verifier);
 // otherwise on the calling thread alone (snark_verify_many's workers are the parallelism there).  Throws VerifyFail{OTTI_ERR_VERIFY_DECOMPRESS}.
@@ -103,7 +117,7 @@ Pt row_sum_on_host(const CPoint *C, size_t n, const Fr *s, bool wide);
 // R1CSProof::verify, shared by both modes: `tr` already carries the caller's protocol name; returns 0 and the challenges the transcript produced.
 // sink: the group equations that feed nothing hashed are stated to it as term lists and NOT checked here (0 then says: the walk met no failure).
 int r1cs_verify_host(const NizkProof &P, size_t N, size_t V, const std::vector<Fr> &inputs, const Fr inst_evals[3], const Gens &g, Transcript &tr,
-                     std::vector<Fr> &rx, std::vector<Fr> &ry, const InstEvalFetch *fetch = nullptr, TermSink *sink = nullptr);
+                     std::vector<Fr> &rx, std::vector<Fr> &ry, const InstEvalFetch *fetch = nullptr, BtEquations *sink = nullptr);
 
 // What both batched verifiers check of an item before they parse its proof, in the single path's order: the arguments, the inputs' scalars
 // (inputs32 are canonical bytes: a scalar >= l is OTTI_ERR_INVALID_SCALAR, as the C entry reports it), their count.  0: `inputs` is filled.
@@ -113,6 +127,27 @@ inline int item_inputs(const VerifyItem &it, size_t num_inputs, std::vector<Fr> 
     for (size_t j = 0; j < it.ninputs; j++) if (!fr_from_bytes(inputs[j], it.inputs32 + 32 * j)) return OTTI_ERR_INVALID_SCALAR;
     if (it.ninputs != num_inputs) return OTTI_ERR_INVALID_NUM_INPUTS;
     return OTTI_OK;
+}
+// How both batched NIZK verifiers open: parse and check, item by item, in the single path's order — the inputs' scalars, their count, the proof's
+// bytes, its challenge lengths.  An item that fails has its code in results[]; the others come back live (Live: LiveProof or a struct derived
+// from it), in the items' order, with OTTI_ERR_INTERNAL as their result until they are settled.
+struct LiveProof { size_t item; std::vector<Fr> inputs; NizkProof P; };
+template <class Live> std::vector<std::unique_ptr<Live>> parse_items(const Instance &I, const VerifyItem *items, size_t count, int32_t *results) {
+    const size_t nrx = ilog2(I.num_cons), nry = ilog2(2 * I.num_vars);
+    std::vector<std::unique_ptr<Live>> live; live.reserve(count);
+    for (size_t i = 0; i < count; i++) {
+        const VerifyItem &it = items[i];
+        try {
+            auto L = std::make_unique<Live>(); L->item = i;
+            if (int rc = item_inputs(it, I.num_inputs, L->inputs)) { results[i] = rc; continue; }
+            L->P = NizkProof::parse(it.proof, it.proof_len);
+            if (L->P.rx.size() != nrx || L->P.ry.size() != nry) { results[i] = OTTI_ERR_VERIFY_INTERNAL; continue; }
+            results[i] = OTTI_ERR_INTERNAL;
+            live.push_back(std::move(L));
+        } catch (const Error &e) { results[i] = e.code; }
+        catch (...) { results[i] = OTTI_ERR_INTERNAL; }
+    }
+    return live;
 }
 
 // The evaluation of A, B, C at the points of many proofs of one instance, as both batched NIZK verifiers use it (verify_many.cpp, verify_batch.cpp):
@@ -145,5 +180,31 @@ struct ManyEvals {
         if (done > k) take(k, out); else on_host(k, out);
     }
 };
+// walk(k, fetch) for every proof k of `ev`, each once; fetch is null where nothing was queued.  Up to nw workers take the proofs in order by an atomic
+// counter while the calling thread, which constructed `ev`, collects its tiles; short of threads, those that started share the work.  nw <= 1:
+// the calling thread alone, in the single path's order — the evaluation is collected where the first proof needs it.  walk must not throw.
+template <class Walk> void walk_proofs(ManyEvals &ev, size_t nw, Walk &&walk) {
+    const size_t n = ev.pts.size();
+    if (nw <= 1) {
+        for (size_t k = 0; k < n; k++) {
+            const InstEvalFetch fetch([&ev, k](Fr out[3]) { ev.fetch_on_caller(k, out); });
+            walk(k, ev.queued ? &fetch : nullptr);
+        }
+        ev.collect_rest();
+        return;
+    }
+    std::atomic<size_t> next{0};
+    auto work = [&] {
+        for (size_t k; (k = next.fetch_add(1, std::memory_order_relaxed)) < n;) {
+            const InstEvalFetch fetch([&ev, k](Fr out[3]) { ev.fetch_on_worker(k, out); });
+            walk(k, ev.queued ? &fetch : nullptr);
+        }
+    };
+    std::vector<std::thread> th; th.reserve(nw);
+    struct Join { std::vector<std::thread> &th; ManyEvals &ev; ~Join() { ev.let_go(); for (auto &t : th) if (t.joinable()) t.join(); } } join{th, ev};
+    for (size_t w = 0; w < nw; w++) { try { th.emplace_back(work); } catch (const std::system_error &) { break; } }
+    ev.collect_rest();
+    if (th.empty()) work();
+}
 
 }  // namespace otti

@@ -2,6 +2,7 @@
 // A, B, C and the device's sum are reached through hooks that prover.cpp sets, so the CPU rebuilds of the host sources compile this file as it is.
 #include "spartan.h"
 #include "verify.h"
+#include "hostpar.h"
 #include <atomic>
 #include <memory>
 #include <thread>
@@ -12,9 +13,8 @@ BatchSumHook g_batch_sum_hook = nullptr;
 
 namespace {
 enum State { kWalk, kCollected, kSettled, kSingle };            // kSingle: the single verifier decides (rx / ry differ, or the proof's own sum fails)
-struct Live {
-    size_t item; std::vector<Fr> inputs; NizkProof P;
-    TermSink sink; BtWeighted weighed; State state = kWalk;
+struct Live : LiveProof {
+    BtEquations sink; BtWeighted weighed; State state = kWalk;
     Fr evals[3]; bool have_evals = false;                       // A, B, C at the proof's point, once its walk has fetched them
 };
 // the walk of nizk_verify_parsed with the collecting sink: the code the walk itself met, or 0 with L.state set
@@ -43,11 +43,7 @@ struct HostSum {
         pts.resize(n); bad.assign(n, 0);
         const unsigned nt = (unsigned)std::min<size_t>({n, (size_t)16, (size_t)std::max(1u, std::thread::hardware_concurrency())});
         std::atomic<size_t> next{0};
-        auto work = [&] { for (size_t k; (k = next.fetch_add(1)) < n;) { pts[k].resize(sets[k].n); for (size_t i = 0; i < sets[k].n; i++) if (!pt_decode_fast(pts[k][i], sets[k].comp32 + 32 * i)) { pts[k][i] = pt_identity(); bad[k] = 1; } } };
-        std::vector<std::thread> th;
-        for (unsigned t = 1; t < nt; t++) { try { th.emplace_back(work); } catch (const std::system_error &) { break; } }
-        work();
-        for (auto &t : th) t.join();
+        fan_out(nt, [&](unsigned) { for (size_t k; (k = next.fetch_add(1)) < n;) { pts[k].resize(sets[k].n); for (size_t i = 0; i < sets[k].n; i++) if (!pt_decode_fast(pts[k][i], sets[k].comp32 + 32 * i)) { pts[k][i] = pt_identity(); bad[k] = 1; } } });
     }
     Pt over_gens(const Fr *s, size_t ngens) const { return host_msm_wide(s, g.P.data(), ngens); }
     Pt all(const BatchSumSet *sets, size_t n, const Fr *gen_total, size_t ngens) const {
@@ -65,21 +61,7 @@ void nizk_verify_batch(const Instance &I, const Gens &g, const void *tlabel, siz
     otti_verify_batch_info inf; memset(&inf, 0, sizeof inf);
     struct Report { otti_verify_batch_info *to, &from; ~Report() { if (to) *to = from; } } report{info, inf};
     if (!count) return;
-    // ---- parse and check, item by item, in the single path's order (nizk_verify_many's)
-    const size_t nrx = ilog2(I.num_cons), nry = ilog2(2 * I.num_vars);
-    std::vector<std::unique_ptr<Live>> live; live.reserve(count);
-    for (size_t i = 0; i < count; i++) {
-        const VerifyItem &it = items[i];
-        try {
-            auto L = std::make_unique<Live>(); L->item = i;
-            if (int rc = item_inputs(it, I.num_inputs, L->inputs)) { results[i] = rc; continue; }
-            L->P = NizkProof::parse(it.proof, it.proof_len);
-            if (L->P.rx.size() != nrx || L->P.ry.size() != nry) { results[i] = OTTI_ERR_VERIFY_INTERNAL; continue; }
-            results[i] = OTTI_ERR_INTERNAL;                   // until it is settled
-            live.push_back(std::move(L));
-        } catch (const Error &e) { results[i] = e.code; }
-        catch (...) { results[i] = OTTI_ERR_INTERNAL; }
-    }
+    const auto live = parse_items<Live>(I, items, count, results);
     const size_t n = live.size();
     inf.live = (uint32_t)n;
     if (!n) return;
@@ -97,40 +79,15 @@ void nizk_verify_batch(const Instance &I, const Gens &g, const void *tlabel, siz
     std::vector<const NizkProof *> pts(n);
     for (size_t k = 0; k < n; k++) pts[k] = &live[k]->P;
     ManyEvals ev(I, std::move(pts));
-    const bool queued = ev.queued;
     if (!threads) threads = kVerifyBatchThreads;
     const size_t nw = std::min<size_t>({(size_t)threads, (size_t)kVerifyManyMaxThreads, n});
     inf.workers = (uint32_t)nw;
-    auto walk = [&](size_t k, const InstEvalFetch &fetch) {
+    walk_proofs(ev, nw, [&](size_t k, const InstEvalFetch *fetch) {
         Live &L = *live[k];
         int rc;
-        try { rc = walk_one(I, g, tlabel, tlabel_len, L, queued ? &fetch : nullptr); } catch (...) { rc = OTTI_ERR_INTERNAL; }
+        try { rc = walk_one(I, g, tlabel, tlabel_len, L, fetch); } catch (...) { rc = OTTI_ERR_INTERNAL; }
         if (rc) { L.state = kSettled; results[L.item] = rc; }
-    };
-    if (nw <= 1) {
-        for (size_t k = 0; k < n; k++) {
-            const InstEvalFetch fetch([&ev, k](Fr out[3]) { ev.fetch_on_caller(k, out); });
-            walk(k, fetch);
-        }
-        ev.collect_rest();
-    } else {
-        std::atomic<size_t> next{0};
-        auto work = [&] {
-            for (;;) {
-                const size_t k = next.fetch_add(1, std::memory_order_relaxed);
-                if (k >= n) return;
-                const InstEvalFetch fetch([&ev, k](Fr out[3]) { ev.fetch_on_worker(k, out); });
-                walk(k, fetch);
-            }
-        };
-        std::vector<std::thread> th; th.reserve(nw);
-        {
-            struct Join { std::vector<std::thread> &th; ManyEvals &ev; ~Join() { ev.let_go(); for (auto &t : th) if (t.joinable()) t.join(); } } join{th, ev};
-            for (size_t w = 0; w < nw; w++) { try { th.emplace_back(work); } catch (const std::system_error &) { break; } }
-            ev.collect_rest();
-            if (th.empty()) work();
-        }
-    }
+    });
     // ---- every equation of every collected proof under a weight of its own; the generator terms of all proofs folded into one scalar per slot
     const size_t ngens = g.P.size();
     RandomTape tape(seed32);
