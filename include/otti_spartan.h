@@ -761,6 +761,14 @@ int32_t otti_k_bullet_last_fold(size_t R, const uint8_t *h_u, const uint8_t *h_u
    sharded layer); h_tau holds log2(G * len / 2) variables (len / 4 with a fold). */
 int32_t otti_k_pc_round(const uint8_t *h_A, const uint8_t *h_B, const uint8_t *h_C, const uint8_t *h_has_C, size_t ninst, size_t len, const uint8_t *h_tau,
                         const uint8_t *h_r, uint32_t G, uint32_t rk, uint8_t *h_out, uint8_t *h_e, float *kernel_ms);
+/* The grid of otti_k_pc_round, otti_k_dot_many and otti_k_sum3, for tests: min(ceil(items / 256), max_blocks / ninst) workgroups per instance (at
+   least one), max_blocks = 2048 on the device's own account; beyond that a thread walks several items.  otti_k_pc_grid_cap_override puts
+   *h_max_blocks in the place of the 2048 for every later launch of this process (a short table then walks many items per thread); NULL or 0
+   restores the device's own.  OTTI_ERR_BAD_ARG above 2048, and while a proof is in flight.  otti_k_pc_plan: the workgroups per instance and the
+   most items any thread walks that a launch over ninst (1 .. 64) instances of `items` items gets under the cap now in force (items = len / 2 for
+   otti_k_pc_round, len / 4 with a fold, n for the other two). */
+int32_t otti_k_pc_grid_cap_override(const uint32_t *h_max_blocks);
+int32_t otti_k_pc_plan(size_t ninst, size_t items, uint32_t *workgroups, uint64_t *items_per_thread);
 /* the hand-over of a batch's tables to the host (folded by h_fold_r first unless NULL): h_out[(3 y + t) * n_out ..) = table t of instance y
    (n_out = len, or len / 2 with a fold; the place of an absent third table is zero) */
 int32_t otti_k_pc_export(const uint8_t *h_A, const uint8_t *h_B, const uint8_t *h_C, const uint8_t *h_has_C, size_t ninst, size_t len, const uint8_t *h_fold_r, uint8_t *h_out);

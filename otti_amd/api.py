@@ -225,6 +225,8 @@ _sig("otti_k_pc_tail", _i32, _vp, _vp, _vp, _vp, _sz, _sz, _u32, _sz, _vp, _vp, 
 _sig("otti_k_prod_layer", _i32, _vp, _vp, _sz, _sz, _vp, _vp, _fp)
 _sig("otti_k_hash_mem", _i32, _vp, _vp, _sz, _vp, _vp, _u32, _u32, _vp, _vp, _fp)
 _sig("otti_k_hash_ops", _i32, _vp, _vp, _vp, _sz, _vp, _vp, _u32, _u32, _vp, _vp, _fp)
+_sig("otti_k_pc_grid_cap_override", _i32, _vp)
+_sig("otti_k_pc_plan", _i32, _sz, _sz, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(_u64))
 _sig("otti_k_dot_many", _i32, _vp, _vp, _sz, _sz, _vp, _fp)
 _sig("otti_k_sum3", _i32, _vp, _vp, _vp, _sz, _sz, _vp, _fp)
 _sig("otti_k_poly_bound_chunks", _i32, _vp, _sz, _sz, _vp, _sz, _vp, ctypes.POINTER(_i32), _fp)
@@ -1693,6 +1695,31 @@ class kernels:
             o = out.reshape(2 * ninst + nc, h, 32); k = iter(range(2 * ninst, 2 * ninst + nc))
             folded = ([o[y] for y in range(ninst)], [o[ninst + y] for y in range(ninst)], [o[next(k)] if has_c[y] else None for y in range(ninst)])
         return e, folded, ms.value
+
+    @staticmethod
+    def pc_plan(ninst, items):
+        """otti_k_pc_plan: (workgroups per instance, the most items a thread walks) of a launch of pc_round, dot_many or sum3 over ``ninst`` instances
+        of ``items`` items (pc_round: n / 2, with a fold n / 4; the others: n), under the block cap now in force (the device's own 2048, or that of
+        an enclosing pc_grid_cap)"""
+        wg, per = ctypes.c_uint32(0), _u64(0)
+        _check(lib.otti_k_pc_plan(ninst, items, ctypes.byref(wg), ctypes.byref(per)))
+        return wg.value, per.value
+
+    @staticmethod
+    @contextlib.contextmanager
+    def pc_grid_cap(max_blocks):
+        """otti_k_pc_grid_cap_override for the length of a ``with`` block: the launches inside share ``max_blocks`` workgroups among their instances
+        in the place of the device's own 2048 (``ninst`` of them: one workgroup per instance); the device's own return on the way out"""
+        _check(lib.otti_k_pc_grid_cap_override(ctypes.byref(ctypes.c_uint32(int(max_blocks)))))
+        try:
+            yield
+        finally:
+            _check(lib.otti_k_pc_grid_cap_override(None))
+
+    @staticmethod
+    def pc_grid_cap_restore():
+        """the device's own block cap again, whatever override stands"""
+        _check(lib.otti_k_pc_grid_cap_override(None))
 
     @staticmethod
     def pc_export(A, B, C, fold_r=None):

@@ -700,6 +700,19 @@ int32_t otti_k_pc_round(const uint8_t *A, const uint8_t *B, const uint8_t *C, co
         c.sync(); c.wait_ticket(tk); memcpy(e, &c.h_results[kSumSlot], 96 * ninst); return OTTI_OK;
     });
 }
+// The batched launches' grid on demand (k_snark.hip pc_grid): a block cap in the device's place, and the plan a launch over ninst instances of
+// `items` items gets under the cap in force.  For the tests, which thereby walk many items per thread on short tables.
+int32_t otti_k_pc_grid_cap_override(const uint32_t *max_blocks) {
+    return guarded([&] { pc_grid_cap_override(max_blocks ? *max_blocks : 0u); return OTTI_OK; });
+}
+int32_t otti_k_pc_plan(size_t ninst, size_t items, uint32_t *workgroups, uint64_t *items_per_thread) {
+    return guarded([&] {
+        if (!workgroups || !items_per_thread) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (ninst < 1 || ninst > 64 || items < 1) throw Error(OTTI_ERR_BAD_ARG, "1 .. 64 instances of at least one item");
+        const PcGrid g = pc_grid(items, (int)ninst);
+        *workgroups = g.workgroups; *items_per_thread = g.items_per_thread; return OTTI_OK;
+    });
+}
 int32_t otti_k_pc_export(const uint8_t *A, const uint8_t *B, const uint8_t *C, const uint8_t *has_C, size_t ninst, size_t len, const uint8_t *fold_r, uint8_t *out) {
     return guarded([&] {
         check_pc_list(A, B, C, has_C, ninst, len);

@@ -126,10 +126,10 @@ template <uint32_t K> HD Fr9 fr9_sub_kl(const Fr9 &a, const Fr9 &b) {
     return r;
 }
 HD Fr9 fr9_sub2l(const Fr9 &a, const Fr9 &b) { return fr9_sub_kl<2>(a, b); }
-// any normalised value below 2^264 (limb 8 as wide as its 32 bits)  ->  canonical memory word:  v = low252 + q 2^252 = low252 - q delta (mod l), q < 2^12:
-// q delta < 2^137 fits d[0..4], so low252 + l - q delta stays in (0, 2l).  A thread's accumulators after 64 items of the four-table cubic pass 2^261
-// (tests/limb9_check.cpp walks sums up to 4032 l and the limb's ends; tests/test_gpu_sumcheck_walks.py the kernels)
-HD Fr fr9_canon(const Fr9 &a) {
+// any normalised value below 2^264 (limb 8 as wide as its 32 bits)  ->  the same value mod l, normalised, in (0, 2l):  v = low252 + q 2^252 =
+// low252 - q delta (mod l), q < 2^12: q delta < 2^137 fits d[0..4], so low252 + l - q delta stays in (0, 2l).  What a running sum goes on from
+// once its limb 8 has grown (pc_accum9.h), and the first half of fr9_canon
+HD Fr9 fr9_fold_top(const Fr9 &a) {
     const uint32_t q = a.v[8] >> 20;
     const uint32_t L[5] = {FR9_L0, FR9_L1, FR9_L2, FR9_L3, FR9_L4};
     uint32_t d[6]; uint64_t acc = 0;
@@ -140,8 +140,11 @@ HD Fr fr9_canon(const Fr9 &a) {
 #pragma unroll
     for (int i = 0; i < 8; i++) r.v[i] = a.v[i] + fr9_kl_limb(1, i) - (i < 6 ? d[i] : 0u);
     r.v[8] = (a.v[8] & 0xfffffu) + fr9_kl_limb(1, 8);
-    return fr9_pack_lt2l(fr9_norm(r));
+    return fr9_norm(r);
 }
+// any normalised value below 2^264  ->  canonical memory word.  A thread's accumulators after 64 items of the four-table cubic pass 2^261
+// (tests/limb9_check.cpp walks sums up to 4032 l and the limb's ends; tests/test_gpu_sumcheck_walks.py the kernels)
+HD Fr fr9_canon(const Fr9 &a) { return fr9_pack_lt2l(fr9_fold_top(a)); }
 // limbs of 32 x, normalised (x normalised, x < 2^256)
 HD Fr9 fr9_shl5(const Fr9 &a) {
     Fr9 r;

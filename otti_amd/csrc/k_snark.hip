@@ -270,7 +270,21 @@ template <int K> __global__ __launch_bounds__(kBlock) void k_reduce_many(const F
     block_reduce<K>(acc);
     if (threadIdx.x == 0) for (int k = 0; k < K; k++) out[(size_t)blockIdx.x * K + k] = acc[k];
 }
-static inline int many_grid(size_t n, int ninst) { return (int)std::max<size_t>(1, std::min<size_t>((n + kBlock - 1) / kBlock, std::max<size_t>(1, (size_t)kMaxBlocks / (size_t)ninst))); }
+// The grid of the launches over a batch (pc_plan.h pc_round_grid) under the block cap in force: the device's own, kMaxBlocks, or what the tests put
+// in its place (otti_k_pc_grid_cap_override) so that short tables walk the many-items-per-thread path of long ones.  Never above kMaxBlocks (the
+// partial sums' buffers are sized by it); written only while no proof is in flight; never set by the prover.
+static_assert(kPcThreads == kBlock && kPcMaxBlocks == kMaxBlocks, "pc_plan.h restates device.h");
+static std::atomic<unsigned> g_pc_grid_cap{0};                // 0: the device's own
+void pc_grid_cap_override(unsigned max_blocks) {
+    if (ActiveProof::count() != 0) throw Error(OTTI_ERR_BAD_ARG, "the batched launches' block cap cannot change while a proof is in flight");
+    if (max_blocks > (unsigned)kMaxBlocks) throw Error(OTTI_ERR_BAD_ARG, "a block cap above the device's own (kMaxBlocks): the partial sums' buffers end there");
+    g_pc_grid_cap.store(max_blocks, std::memory_order_release);
+}
+PcGrid pc_grid(size_t items, int ninst) {
+    const unsigned cap = g_pc_grid_cap.load(std::memory_order_acquire);
+    return pc_round_grid(items, ninst, cap ? cap : (unsigned)kMaxBlocks);
+}
+static inline int many_grid(size_t n, int ninst) { return (int)pc_grid(n, ninst).workgroups; }
 // ---- a round of the batched cubic sum-check as ONE launch (fold by the previous challenge + the sums of this round at the points 0, 2, 3
 // of the variable being bound), results mailed to the host by the last workgroup (finish_in_kernel of k_sumcheck.hip, here for every
 // instance of the batch at once).
@@ -310,30 +324,8 @@ __device__ __forceinline__ void finish_many(Fr (&acc)[3], const Mailbox &mb, con
     __syncthreads();
     if (threadIdx.x == 0) __hip_atomic_store(mb.host_flag, mb.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
-// ---- nine-limb forms (fr9.h).  Product-circuit instance (third table = the shared eq table, never stored): per item
-//   Q(0) += (E a_lo) b_lo,  Q(1) += (E a_hi) b_hi,  Q_inf += (E a_hi - E a_lo)(b_hi - b_lo)
-// — the quadratic's values at 0, 1 and its leading coefficient, in FIVE products (E a_lo and E a_hi serve two sums each; six when E multiplied
-// the three products a b); finish_many turns the totals into the values at 0, 2, 3.  E goes in times 2^10: E a_* then carries the factor 32
-// the second product needs.  a_*, b_* normalised below 2.2 l; e10 normalised below 2^10 l.
-__device__ __forceinline__ void abe_accum9(Fr9 (&acc)[3], const Fr9 &a_lo, const Fr9 &a_hi, const Fr9 &b_lo, const Fr9 &b_hi, const Fr9 &e10) {
-    const Fr9 u = fr9_mul(e10, a_lo), v = fr9_mul(e10, a_hi);                               // 2^10 l * 2.2 l / 2^261 + l < 5.4 l
-    const Fr9 dv = fr9_norm(fr9_sub_kl<8>(v, u)), db = fr9_sub_kl<4>(b_hi, b_lo);           // < 13.4 l; < 6.2 l (loose)
-    acc[0] = fr9_add(acc[0], fr9_mul(u, b_lo));                                             // 5.4 * 2.2 / 2^9 + 1 < 1.1 l
-    acc[1] = fr9_add(acc[1], fr9_mul(v, b_hi));
-    acc[2] = fr9_add(acc[2], fr9_mul(dv, db));                                              // 13.4 * 6.2 / 2^9 + 1 < 1.2 l
-}
-// Dot-product triple (three real tables): the cubic's values at 0, 2, 3 as they stand.  a_* plain, b_*5 and c_*5 times 32.
-__device__ __forceinline__ void abc_accum9(Fr9 (&acc)[3], const Fr9 &a_lo, const Fr9 &a_hi, const Fr9 &b_lo5, const Fr9 &b_hi5, const Fr9 &c_lo5, const Fr9 &c_hi5) {
-    acc[0] = fr9_add(acc[0], fr9_mul(fr9_mul(a_lo, b_lo5), c_lo5));
-    // point 2: x = 2 a_hi - a_lo + 4l (carried down), y5, z5 = 2 X_hi5 - X_lo5 + 128 l (limbs < 2^31): values 8.4 l, 270 l: products < 5.5 l, < 3.9 l
-    const Fr9 x2 = fr9_norm(fr9_sub_kl<4>(fr9_add(a_hi, a_hi), a_lo));
-    const Fr9 y2 = fr9_sub_kl<128>(fr9_add(b_hi5, b_hi5), b_lo5), z2 = fr9_sub_kl<128>(fr9_add(c_hi5, c_hi5), c_lo5);
-    acc[1] = fr9_add(acc[1], fr9_mul(fr9_mul(x2, y2), z2));
-    // point 3: X_3 = X_2 + (X_hi - X_lo): carried down on every side (their limbs would reach 3.5 * 2^30)
-    const Fr9 x3 = fr9_norm(fr9_add(x2, fr9_sub_kl<4>(a_hi, a_lo)));
-    const Fr9 y3 = fr9_norm(fr9_add(y2, fr9_sub_kl<128>(b_hi5, b_lo5))), z3 = fr9_norm(fr9_add(z2, fr9_sub_kl<128>(c_hi5, c_lo5)));
-    acc[2] = fr9_add(acc[2], fr9_mul(fr9_mul(x3, y3), z3));          // values 14.6 l, 469 l: 14.6 * 469 / 512 + 1 = 14.4 l, then 14.4 * 469 / 512 + 1 = 14.2 l
-}
+// ---- nine-limb forms (fr9.h).  What an item adds to a thread's three sums — abe_accum9 for a product-circuit instance, abc_accum9 for a dot-product
+// triple — and the sweep / fold step after it, pc_acc_step, with the walk bound kPcWalkMax: pc_accum9.h, where a host compiler reads them too.
 // kFold: the tables have 4q entries and are folded by r to 2q (pairs (i, i + q)); otherwise they have 2q entries as they are
 template <bool kFold> __global__ __launch_bounds__(kBlock) void k_pc_round(PcList L, size_t q, Fr r, EqSrc E, Mailbox mb, Armed go) {
     if (kFold && go.want) { Fr v[1]; if (!armed_fetch<1>(go, v)) return; r = v[0]; }
@@ -364,7 +356,7 @@ template <bool kFold> __global__ __launch_bounds__(kBlock) void k_pc_round(PcLis
             } else { c_lo5 = fr9_unpack5(C[i]); c_hi5 = fr9_unpack5(C[i + q]); }
             abc_accum9(acc, a_lo, a_hi, fr9_shl5(b_lo), fr9_shl5(b_hi), c_lo5, c_hi5);
         } else abe_accum9(acc, a_lo, a_hi, b_lo, b_hi, eq_s_at<10>(E, i));
-        if ((++n & 3u) == 0) acc9_carry(acc);
+        pc_acc_step(acc, n);
     }
     Fr tot[3]; acc9_canon<3>(tot, acc);
     finish_many(tot, mb, L);
@@ -373,15 +365,24 @@ static Mailbox pc_mailbox(DevCtx &c, int slot, int nblocks) {
     if ((size_t)nblocks * 3 > c.partials.n) throw Error(OTTI_ERR_INTERNAL, "round partials exceed the context's buffer");
     return c.next_mailbox(slot);
 }
+// The walk k_pc_round can take.  Its sums are folded back every kPcWalkMax items (pc_accum9.h), so no length overflows them; what is left is the
+// 32-bit item count, which may even wrap (kPcWalkMax divides 2^32).  The refusal below therefore cannot be reached — a walk of 2^32 items needs
+// tables of 2^40 elements under a cap of one block — and no test shows it; it stands for the day the step changes.
+constexpr size_t kPcWalkLimit = (size_t)1 << 32;
+static int pc_round_blocks(size_t items, int ninst) {
+    const PcGrid g = pc_grid(items, ninst);
+    if (g.items_per_thread > kPcWalkLimit) throw Error(OTTI_ERR_INTERNAL, "a thread of the batched round kernel would walk more items than its sums can take");
+    return (int)g.workgroups;
+}
 unsigned long long dev_pc_eval(DevCtx &c, const PcList &L, size_t len, const EqSrc &E, int slot) {
-    const size_t half = len / 2; const int g = many_grid(half, L.n); Mailbox mb = pc_mailbox(c, slot, g * L.n);
+    const size_t half = len / 2; const int g = pc_round_blocks(half, L.n); Mailbox mb = pc_mailbox(c, slot, g * L.n);
     KScope ks(c, KC_PC_ROUND);
     hipLaunchKernelGGL(k_pc_round<false>, dim3((unsigned)g, (unsigned)L.n), kBlock, 0, c.stream, L, half, fr_zero(), E, mb, Armed{nullptr, nullptr, 0});
     return mb.seq;
 }
 unsigned long long dev_pc_fold_eval(DevCtx &c, const PcList &L, size_t len, const Fr *r, const EqSrc &E, int slot) {
     if (len < 4) throw Error(OTTI_ERR_INTERNAL, "fold_eval needs len >= 4");
-    const size_t q = len / 4; const int g = many_grid(q, L.n); Mailbox mb = pc_mailbox(c, slot, g * L.n);
+    const size_t q = len / 4; const int g = pc_round_blocks(q, L.n); Mailbox mb = pc_mailbox(c, slot, g * L.n);
     const Armed go = r ? Armed{nullptr, nullptr, 0} : c.arm();
     KScope ks(c, KC_PC_ROUND);
     hipLaunchKernelGGL(k_pc_round<true>, dim3((unsigned)g, (unsigned)L.n), kBlock, 0, c.stream, L, q, r ? *r : fr_zero(), E, mb, go);
@@ -490,7 +491,7 @@ __global__ __launch_bounds__(kTailThreads) void k_pc_tail(TailArgs a) {
         const uint32_t half = L / 2;
         // ---- this round's sums: S_t = sum over pairs of (A_t B_t C_t), t in {0, 2, 3}
         // nine limbs (fr9.h): the first table plain, the other two times 32 — each of the two products then has exactly one operand carrying the
-        // radix correction (abc_accum9 above has the bounds; here every operand comes canonical out of the LDS)
+        // radix correction (abc_accum9 of pc_accum9.h has the bounds; here every operand comes canonical out of the LDS)
         Fr9 acc9 = fr9_zero(); unsigned n_acc = 0;
         if (grp < ngrp)
             for (uint32_t p = (uint32_t)grp * 64 + lane; p < half; p += (uint32_t)ngrp * 64) {

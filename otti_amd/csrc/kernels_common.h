@@ -5,6 +5,7 @@
 #include "fp10.h"
 #include "fp9.h"
 #include "fr9.h"
+#include "pc_accum9.h"
 #include "pool.h"
 #include <stdio.h>
 #include <stdlib.h>
@@ -314,15 +315,7 @@ __device__ __forceinline__ void quadratic_to_023(Fr (&q)[3]) {
     const Fr s3 = fr_sub(fr_add(fr_add(t2, t), fr_add(fr_dbl(q[2]), q[2])), fr_dbl(q[0]));
     q[1] = s2; q[2] = s3;
 }
-// a thread's running sums (limbs grow by < 2^29 per item: carried down every fourth item) -> canonical words
-__device__ __forceinline__ void acc9_carry(Fr9 (&acc)[3]) {
-#pragma unroll
-    for (int k = 0; k < 3; k++) acc[k] = fr9_norm(acc[k]);
-}
-template <int K> __device__ __forceinline__ void acc9_canon(Fr (&out)[K], const Fr9 (&acc)[K]) {
-#pragma unroll
-    for (int k = 0; k < K; k++) out[k] = fr9_canon(fr9_norm(acc[k]));
-}
+// (a thread's running sums, acc9_carry and acc9_canon: pc_accum9.h)
 // bound_poly_var_top of (x0, x2) by r (r5 = 32 r): the folded element, normalised and below 2.2 l, and its canonical word for the table
 __device__ __forceinline__ Fr9 fold9(const Fr &x0, const Fr &x2, const Fr9 &r5, Fr &word) {
     const Fr9 a = fr9_unpack(x0);

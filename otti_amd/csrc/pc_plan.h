@@ -16,6 +16,20 @@ constexpr int kPcPreExportEnd = 7400;                        // pre-exported hos
 constexpr int kHashEvalSlot = kPcPreExportEnd;               // result slots of the hash layer's 21 evaluations (clear of the round sums and the exported tails)
 static_assert(kPcTailSlot < kPcPreExportEnd && kPcPreExportEnd <= kHashEvalSlot, "pre-exported layers would reach into the hash layer's ahead-of-time results");
 
+// Grid of a launch over a batch of instances (k_snark.hip: the round kernel k_pc_round — items = pairs of a table's elements, quads with a fold —
+// and the evaluations' k_dot_many, k_sum3 — items = elements): a thread per item up to max_blocks workgroups over ALL instances, the same number
+// for each.  Beyond that the grid does not grow with the tables, the walk does: 18 instances of 2^19 items run on 113 workgroups each, 19 items
+// per thread, and the 2^25 items per instance the library accepts are 1160.  k_pc_round takes any walk (pc_accum9.h kPcWalkMax: it folds its
+// sums back every 256 items); the other two add canonical values.
+constexpr int kPcThreads = 256;                              // threads per workgroup (device.h kBlock)
+constexpr int kPcMaxBlocks = 2048;                           // the device's own max_blocks (device.h kMaxBlocks): 8 workgroups per CU of 256
+struct PcGrid { unsigned workgroups; size_t items_per_thread; };   // per instance; the most items any thread walks
+inline PcGrid pc_round_grid(size_t items, int ninst, size_t max_blocks) {
+    const size_t per_inst = std::max<size_t>(1, max_blocks / (size_t)std::max(1, ninst));
+    const size_t g = std::max<size_t>(1, std::min<size_t>((items + kPcThreads - 1) / kPcThreads, per_inst));
+    return {(unsigned)g, (items + g * kPcThreads - 1) / (g * kPcThreads)};
+}
+
 // What the rule reads besides a layer's shape: the OTTI_PC_* switches (read once per process) and what the device and the process's state allow
 // (per call).  The defaults are a 256-CU device's, with the AVX-512 IFMA host tail.
 struct PcKnobs {

@@ -8,7 +8,11 @@ namespace otti {
 constexpr int kMaxInst = 20;                                  // 12 product circuits + 6 dot-product halves in the largest batch
 // Places in the pinned result buffer (c.h_results) and scratch sizes that the prover and the kernel-level test entries must agree on
 constexpr int kSumSlot = 64;                                  // where a round's sums land (kPcTailSlot, where a layer's exported tables start: pc_plan.h)
-constexpr size_t kSnarkPartials = (size_t)3 * kMaxBlocks + 64;   // dev_dot_many / dev_sum3 scratch: 3 sums x at most kMaxBlocks workgroups per launch (k_snark.hip many_grid)
+constexpr size_t kSnarkPartials = (size_t)3 * kMaxBlocks + 64;   // dev_dot_many / dev_sum3 scratch: 3 sums x at most kMaxBlocks workgroups per launch (pc_plan.h pc_round_grid)
+// The grid of k_pc_round, k_dot_many and k_sum3 over `ninst` instances of `items` items (pc_plan.h pc_round_grid) under the block cap in force,
+// and the tests' seam in it: max_blocks in the place of kMaxBlocks for every later launch (0: the device's own again; never above kMaxBlocks)
+PcGrid pc_grid(size_t items, int ninst);
+void pc_grid_cap_override(unsigned max_blocks);
 struct AbcList { const Fr *A[kMaxInst], *B[kMaxInst], *C[kMaxInst]; int n; };
 struct PtrList { Fr *p[64]; int n; };
 struct LayerList { const Fr *in_left[16], *in_right[16]; Fr *out_left[16], *out_right[16]; int n; };

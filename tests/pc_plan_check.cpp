@@ -55,6 +55,33 @@ static const PreCase kPreCases[] = {
     {12,  7, 18, 7, {128, 164, 236, 380, 668, 1244, 2396}, 5852},
 };
 
+// The grid of a launch over a batch (pc_round_grid): workgroups per instance and the most items a thread walks, on both sides of the cap
+struct GridCase { size_t items; int ninst; size_t max_blocks; unsigned workgroups; size_t walk; };
+static const GridCase kGridCases[] = {
+    // items                   ninst  cap   workgroups walk
+    {1,                           1, 2048,     1,    1},
+    {256,                         1, 2048,     1,    1},
+    {257,                         1, 2048,     2,    1},
+    {(size_t)2048 * 256,          1, 2048,  2048,    1},      // the last length with a thread per item
+    {(size_t)2048 * 256 + 1,      1, 2048,  2048,    2},
+    {(size_t)1 << 25,             1, 2048,  2048,   64},
+    {(size_t)113 * 256,          18, 2048,   113,    1},      // 2048 / 18 = 113 workgroups per instance
+    {(size_t)113 * 256 + 1,      18, 2048,   113,    2},
+    {(size_t)1 << 15,            18, 2048,   113,    2},      // tests/test_gpu_snark_kernels.py test_pc_round_at_the_grid_cap
+    {(size_t)1 << 19,            18, 2048,   113,   19},      // the operations circuits' input layer of a 2^20 proof: 18.1 items per thread
+    {(size_t)1 << 25,            18, 2048,   113, 1160},      // the longest tables the library accepts: far beyond kPcWalkMax
+    {(size_t)102 * 256,          20, 2048,   102,    1},      // 2048 / 20 = 102
+    {(size_t)102 * 256 + 1,      20, 2048,   102,    2},
+    {(size_t)1 << 19,            20, 2048,   102,   21},
+    {(size_t)256 * 64,           18,   18,     1,   64},      // the tests' seam: one workgroup per instance ...
+    {(size_t)1 << 18,             3,    3,     1, 1024},
+    {2048,                        2,    6,     3,    3},      // ... three, ragged: walks of 3 / 2 and 6 / 5
+    {4096,                        2,    6,     3,    6},
+    {(size_t)1 << 19,             1,    3,     3,  683},
+    {(size_t)1 << 12,            18,    1,     1,   16},      // a cap below the instances still gives each its workgroup
+    {5,                          64, 2048,     1,    1},
+};
+
 static int failures = 0;
 #define EXPECT(cond, ...) do { if (!(cond)) { failures++; printf("FAIL " __VA_ARGS__); printf("\n"); } } while (0)
 
@@ -137,6 +164,21 @@ int main() {
                     }
                     EXPECT(end == at && end <= (size_t)kPcPreExportEnd, "pre-export ni %d nl %zu lgt %zu: ends at %zu", ni, nl, lgt, end);
                 }
-    printf("%zu plans checked, %zu pre-exports, %zu swept, %d failures\n", sizeof kCases / sizeof kCases[0], sizeof kPreCases / sizeof kPreCases[0], swept, failures);
+    for (const GridCase &k : kGridCases) {
+        const PcGrid g = pc_round_grid(k.items, k.ninst, k.max_blocks);
+        EXPECT(g.workgroups == k.workgroups && g.items_per_thread == k.walk, "grid of %zu items x %d under %zu blocks: %u workgroups, walk %zu; expected %u, %zu", k.items, k.ninst, k.max_blocks, g.workgroups, g.items_per_thread, k.workgroups, k.walk);
+    }
+    // whatever the shape: every item has a thread's pass, no pass is wholly idle, and the grid stays within the cap (the partial sums' buffers)
+    for (int ninst : {1, 4, 12, 18, 20, 64})
+        for (size_t cap : {(size_t)1, (size_t)18, (size_t)54, (size_t)2048})
+            for (size_t items : {(size_t)1, (size_t)255, (size_t)256, (size_t)257, (size_t)28928, (size_t)28929, (size_t)1 << 19, ((size_t)1 << 19) + 1, (size_t)1 << 25}) {
+                const PcGrid g = pc_round_grid(items, ninst, cap);
+                const size_t threads = (size_t)g.workgroups * kPcThreads;
+                swept++;
+                EXPECT(g.workgroups >= 1 && ((size_t)g.workgroups * ninst <= cap || g.workgroups == 1), "grid of %zu x %d under %zu: %u workgroups", items, ninst, cap, g.workgroups);
+                EXPECT(g.items_per_thread * threads >= items && (g.items_per_thread - 1) * threads < items, "grid of %zu x %d under %zu: walk %zu on %zu threads", items, ninst, cap, g.items_per_thread, threads);
+                EXPECT((size_t)(g.workgroups - 1) * kPcThreads < items, "grid of %zu x %d under %zu: an idle workgroup among %u", items, ninst, cap, g.workgroups);
+            }
+    printf("%zu plans checked, %zu pre-exports, %zu grids, %zu swept, %d failures\n", sizeof kCases / sizeof kCases[0], sizeof kPreCases / sizeof kPreCases[0], sizeof kGridCases / sizeof kGridCases[0], swept, failures);
     return failures ? 1 : 0;
 }

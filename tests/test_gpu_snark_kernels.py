@@ -110,8 +110,8 @@ def test_pc_round_shapes(rng, batch, n):
 
 @pytest.mark.parametrize("fold,kind", [(False, "random"), (True, "random"), (False, "edge"), (True, "edge")], ids=["False", "True", "False-edge", "True-edge"])
 def test_pc_round_at_the_grid_cap(rng, fold, kind):
-    """18 instances with 2^15 items each: 128 workgroups per instance wanted, 2048 / 18 = 113 given — the grid-stride loop runs a second time, the only
-    place where a thread of k_pc_round adds a second item onto its unswept sums.  edge: the tables of edge_table (values and stored words at the ends
+    """18 instances with 2^15 items each: 128 workgroups per instance wanted, 2048 / 18 = 113 given — the grid-stride loop runs a second time under the
+    library's own block cap (walks of 2 .. 1024 items, with the sweep and the fold of pc_acc_step: tests/test_gpu_pc_round_walks.py).  edge: the tables of edge_table (values and stored words at the ends
     of their ranges, a 2^13 block repeated: the stride of 113 * 256 items is no multiple of it, so a thread's two items differ), folded by l - 1"""
     kinds = "pppppppptppppppppt" if fold else "ppt" * 6
     n = 1 << 17 if fold else 1 << 16

@@ -11,4 +11,4 @@ def test_layer_plans_of_the_proofs_and_what_the_tail_kernel_relies_on(tmp_path):
     subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "otti_amd", "csrc"), os.path.join(ROOT, "tests", "pc_plan_check.cpp"), "-o", str(exe)], check=True)
     r = subprocess.run([str(exe)], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
-    assert "19 plans checked, 3 pre-exports" in r.stdout and "0 failures" in r.stdout
+    assert "19 plans checked, 3 pre-exports, 21 grids" in r.stdout and "0 failures" in r.stdout

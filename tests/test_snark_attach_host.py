@@ -48,11 +48,12 @@ def _spzk(*args):
 def test_new_symbols_are_exported():
     for name in ("otti_comp_comm_attach", "otti_comp_comm_dims", "otti_k_addr_timestamps", "otti_snark_gens_points", "otti_zkif_load_inputs",
                  "otti_k_pc_round", "otti_k_pc_export", "otti_k_pc_tail", "otti_k_prod_layer", "otti_k_hash_mem", "otti_k_hash_ops", "otti_k_dot_many",
-                 "otti_k_sum3", "otti_k_poly_bound_chunks"):
+                 "otti_k_sum3", "otti_k_poly_bound_chunks", "otti_k_pc_grid_cap_override", "otti_k_pc_plan"):
         assert hasattr(oa.lib, name), name
     header = open(os.path.join(os.path.dirname(HERE), "include", "otti_spartan.h")).read()
-    for name in ("pc_round", "pc_export", "pc_tail", "prod_layer", "hash_mem", "hash_ops", "dot_many", "sum3", "poly_bound_chunks"):
+    for name in ("pc_round", "pc_export", "pc_tail", "prod_layer", "hash_mem", "hash_ops", "dot_many", "sum3", "poly_bound_chunks", "pc_plan"):
         assert callable(getattr(oa.kernels, name)) and f"int32_t otti_k_{name}(" in header, name
+    assert callable(oa.kernels.pc_grid_cap) and callable(oa.kernels.pc_grid_cap_restore) and "int32_t otti_k_pc_grid_cap_override(" in header
     assert callable(oa.ComputationCommitment.attach) and callable(oa.kernels.addr_timestamps)
 
 
