@@ -604,6 +604,16 @@ int32_t otti_k_fr_op(int32_t op, const uint8_t *h_a, const uint8_t *h_b, uint8_t
    h_out: n packed results; h_limbs: 10 words per case, the raw limbs (form 0: words) of the result before packing, the rest zero. */
 int32_t otti_k_fp_op(int32_t form, int32_t op, const uint8_t *h_a, const uint8_t *h_b, const uint8_t *h_c, const uint8_t *h_d, size_t n, uint8_t *h_out,
                      uint32_t *h_limbs, float *kernel_ms);
+/* GF(l) in the device's nine limbs of 29 bits (Montgomery radix 2^261), one case per lane: the very inline functions the sum-check, eq-table and sparse
+   kernels call.  An operand is n 32-byte words (any 256-bit value, little-endian) or n x 9 raw uint32 limbs, as the operation demands:
+   words in, limbs out: 0 unpack, 1 unpack5 (limbs of 32 a), 2 unpack10 (limbs of 1024 a; a < 2^253);
+   limbs in, limbs out: 3 mul(a, b) = a b / 2^261 mod l, 4 mul(a, a) with the same registers as both inputs, 5 add, 6 norm (one carry sweep),
+   7 .. 11 a - b + K l for K = 2, 4, 8, 16, 128, 12 fold_top, 13 shl5;  limbs in, word out: 14 pack_lt2l, 15 pack_lt3l, 16 canon;
+   words in, word and limbs out: 17 pack_lt2l(mul(unpack5(a), unpack(b))), 18 the fold a + c (b - a) of the round kernels (c unpacked times 32): the
+   stored word and the limbs handed on.  Operands an operation does not read are ignored but must not be NULL; the output it does not produce is
+   zero.  Nothing checks an operation's precondition (fr9.h): that is the caller's.  Before any device work: an unknown op, a null pointer with n > 0
+   or n > 2^24 is OTTI_ERR_BAD_ARG; n = 0 returns at once. */
+int32_t otti_k_fr9_op(int32_t op, const void *h_a, const void *h_b, const void *h_c, size_t n, uint8_t *h_words, uint32_t *h_limbs, float *kernel_ms);
 /* the point formulas on a caller's operands.  h_P: n points (X, Y, Z, T: 128 bytes; any field elements).  op: 0 p9_madd, 1 p10_madd, 3 the quad-lane mixed
    addition (h_Q: n Niels entries of 96 bytes; neg != 0: the entry negated as for a negative digit); 2 p10_add, 4 the quad-lane full addition (h_Q: n
    points); 5 k successive p9_madd of the same entry (k <= 4096).  h_out: n packed points; h_limbs: 4 x 10 words per case, the raw limbs of X, Y, Z, T.

@@ -218,6 +218,7 @@ _sig("otti_k_bullet_round", _i32, _vp, _sz, _i32, _vp, _vp, _vp, _vp, _vp, _vp, 
 _sig("otti_k_bullet_last_fold", _i32, _sz, _vp, _vp, _vp, _vp, _vp)
 _u32 = ctypes.c_uint32
 _sig("otti_k_fp_op", _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _fp)
+_sig("otti_k_fr9_op", _i32, _i32, _vp, _vp, _vp, _sz, _vp, _vp, _fp)
 _sig("otti_k_pt_op", _i32, _i32, _vp, _vp, _i32, _u32, _sz, _vp, _vp, _vp, _fp)
 _sig("otti_k_pc_round", _i32, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _u32, _u32, _vp, _vp, _fp)
 _sig("otti_k_pc_export", _i32, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp)
@@ -1274,6 +1275,37 @@ class kernels:
         out, limbs = np.zeros_like(a), np.zeros((n, 10), dtype=np.uint32)
         _check(lib.otti_k_fp_op(f, kernels.FP_OPS.index(op), _ptr(a), _ptr(b), _ptr(c), _ptr(d), n, _ptr(out), _ptr(limbs), None))
         return out, limbs[:, :(8, 9, 10)[f]].copy()
+
+    FR9_OPS = ("unpack", "unpack5", "unpack10", "mul", "mul_self", "add", "norm", "sub_kl2", "sub_kl4", "sub_kl8", "sub_kl16", "sub_kl128", "fold_top",
+               "shl5", "pack_lt2l", "pack_lt3l", "canon", "mul9", "fold9")
+    FR9_WORDS_IN = {"unpack": 1, "unpack5": 1, "unpack10": 1, "mul9": 2, "fold9": 3}      # operands that are 32-byte words; every other operand: nine limbs
+    FR9_LIMBS_IN = {"mul": 2, "add": 2, "sub_kl2": 2, "sub_kl4": 2, "sub_kl8": 2, "sub_kl16": 2, "sub_kl128": 2}   # (the other limb operations: one)
+
+    @staticmethod
+    def fr9_op(op, a, b=None, c=None):
+        """otti_k_fr9_op: GF(l) in nine limbs of 29 bits (fr9.h; fold9 of the round kernels), the very inline functions the hot kernels call.  An
+        operand is (n, 32) uint8 (a little-endian word) or (n, 9) uint32 (raw limbs), as the operation demands (FR9_WORDS_IN; the rest take limbs);
+        every operand the operation reads must be given, none that it does not.  Returns (words (n, 32) uint8, limbs (n, 9) uint32); the output an
+        operation does not produce is zero.  No precondition is checked here."""
+        o = kernels.FR9_OPS.index(op)
+        nw = kernels.FR9_WORDS_IN.get(op, 0)
+        need = nw if nw else kernels.FR9_LIMBS_IN.get(op, 1)
+        given = [x for x in (a, b, c) if x is not None]
+        if len(given) != need or any(x is None for x in (a, b, c)[:need]):
+            raise ValueError(f"{op}: takes {need} operand(s)")
+        if nw:
+            given = [kernels._words(x, 32, "operand") for x in given]
+        else:
+            given = [np.ascontiguousarray(x, dtype=np.uint32) for x in given]
+            if any(x.ndim != 2 or x.shape[1] != 9 for x in given):
+                raise ValueError("operand: expected an (n, 9) uint32 array of limbs")
+        n = given[0].shape[0]
+        if any(x.shape != given[0].shape for x in given):
+            raise ValueError("operands: one length")
+        given += [given[0]] * (3 - need)                              # never read: the entry only wants no null pointer
+        out, limbs = np.zeros((n, 32), dtype=np.uint8), np.zeros((n, 9), dtype=np.uint32)
+        _check(lib.otti_k_fr9_op(o, _ptr(given[0]), _ptr(given[1]), _ptr(given[2]), n, _ptr(out), _ptr(limbs), None))
+        return out, limbs
 
     @staticmethod
     def pt_op(op, P, Q=None, neg=False, k=1):

@@ -86,6 +86,28 @@ int32_t otti_k_fp_op(int32_t form, int32_t op, const uint8_t *a, const uint8_t *
         c.sync(); return OTTI_OK;
     });
 }
+// GF(l) in nine limbs (fr9.h, fold9) on a caller's operands: words or raw limbs in, as the operation demands (device.h Fr9Op)
+int32_t otti_k_fr9_op(int32_t op, const void *a, const void *b, const void *cc, size_t n, uint8_t *out, uint32_t *limbs, float *ms) {
+    return guarded([&] {
+        if (op < 0 || op >= FR9OP_COUNT) throw Error(OTTI_ERR_BAD_ARG, "unknown operation");
+        if (n && (!a || !b || !cc || !out || !limbs)) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (n > ((size_t)1 << 24)) throw Error(OTTI_ERR_BAD_ARG, "more than 2^24 cases");
+        if (!n) return OTTI_OK;
+        DevCtx &c = DevCtx::get();
+        const int nw = fr9_op_words_in(op), nl = fr9_op_limbs_in(op);
+        const size_t lbytes = n * kFr9OpLimbs * sizeof(uint32_t);
+        DevBuf<Fr> w(3 * n), o(n); DevBuf<uint32_t> l(2 * n * kFr9OpLimbs), lm(n * kFr9OpLimbs);
+        const void *src[3] = {a, b, cc};
+        for (int k = 0; k < nw; k++) OTTI_HIP(hipMemcpyAsync(w.p + k * n, src[k], n * sizeof(Fr), hipMemcpyHostToDevice, c.stream));
+        for (int k = 0; k < nl; k++) OTTI_HIP(hipMemcpyAsync(l.p + k * n * kFr9OpLimbs, src[k], lbytes, hipMemcpyHostToDevice, c.stream));
+        OTTI_HIP(hipMemsetAsync(o.p, 0, n * sizeof(Fr), c.stream));
+        OTTI_HIP(hipMemsetAsync(lm.p, 0, lbytes, c.stream));
+        KTimer t(c, ms); dev_fr9_op(c, op, w.p, w.p + n, w.p + 2 * n, l.p, l.p + n * kFr9OpLimbs, o.p, lm.p, n); t.stop();
+        OTTI_HIP(hipMemcpyAsync(out, o.p, n * sizeof(Fr), hipMemcpyDeviceToHost, c.stream));
+        OTTI_HIP(hipMemcpyAsync(limbs, lm.p, lbytes, hipMemcpyDeviceToHost, c.stream));
+        c.sync(); return OTTI_OK;
+    });
+}
 int32_t otti_k_pt_op(int32_t op, const uint8_t *P, const uint8_t *Q, int32_t neg, uint32_t k, size_t n, uint8_t *out, uint32_t *limbs, uint32_t *bad, float *ms) {
     return guarded([&] {
         if (op < 0 || op >= PTOP_COUNT) throw Error(OTTI_ERR_BAD_ARG, "unknown operation");

@@ -400,6 +400,17 @@ enum PtOp { PTOP_P9_MADD = 0, PTOP_P10_MADD, PTOP_P10_ADD, PTOP_Q10_MADD, PTOP_Q
 constexpr int kFpOpLimbStride = 10;
 void dev_fp_op(DevCtx &c, int form, int op, const Fp *a, const Fp *b, const Fp *cc, const Fp *d, Fp *out, uint32_t *limbs, size_t n);
 void dev_pt_op(DevCtx &c, int op, const Pt *P, const void *Q, bool neg, uint32_t k, size_t n, Pt *out, uint32_t *limbs);
+// GF(l) in nine limbs on a test's operands (k_curve_ops.hip): the inline functions of fr9.h and fold9 of kernels_common.h, one case per lane.  An
+// operation reads 32-byte words (aw, bw, cw) or raw limbs (al, bl: kFr9OpLimbs words per case), whichever fr9_op_words_in / fr9_op_limbs_in say,
+// and writes a word, limbs, or both; the output it does not produce is left alone.  Only queues.
+enum Fr9Op { FR9OP_UNPACK = 0, FR9OP_UNPACK5, FR9OP_UNPACK10, FR9OP_MUL, FR9OP_MUL_SELF, FR9OP_ADD, FR9OP_NORM, FR9OP_SUB_KL2, FR9OP_SUB_KL4, FR9OP_SUB_KL8,
+             FR9OP_SUB_KL16, FR9OP_SUB_KL128, FR9OP_FOLD_TOP, FR9OP_SHL5, FR9OP_PACK_LT2L, FR9OP_PACK_LT3L, FR9OP_CANON, FR9OP_MUL9, FR9OP_FOLD9, FR9OP_COUNT };
+constexpr int kFr9OpLimbs = 9;
+constexpr int fr9_op_words_in(int op) { return op <= FR9OP_UNPACK10 ? 1 : op == FR9OP_MUL9 ? 2 : op == FR9OP_FOLD9 ? 3 : 0; }
+constexpr int fr9_op_limbs_in(int op) {
+    return fr9_op_words_in(op) ? 0 : (op == FR9OP_MUL || op == FR9OP_ADD || (op >= FR9OP_SUB_KL2 && op <= FR9OP_SUB_KL128)) ? 2 : 1;
+}
+void dev_fr9_op(DevCtx &c, int op, const Fr *aw, const Fr *bw, const Fr *cw, const uint32_t *al, const uint32_t *bl, Fr *out, uint32_t *limbs, size_t n);
 void dev_from_canonical(DevCtx &c, const Fr *in, Fr *out, size_t n);      // raw LE integer -> Montgomery (must be < l)
 void dev_to_canonical(DevCtx &c, const Fr *in, Fr *out, size_t n);
 void dev_fill_zero(DevCtx &c, Fr *p, size_t n);

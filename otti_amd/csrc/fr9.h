@@ -14,8 +14,12 @@
 // fr9_shl5 for computed ones.
 //
 // Bounds.  "normalised": limbs 0..7 < 2^29, limb 8 whatever the value needs (< 2^29 for every value below 2^261).  "loose": any limbs
-// for which the column sums of the product stay below 2^64: 9 * max(a_i) * max(b_j) + 6 * 2^58 < 2^64, e.g. one operand normalised and the
-// other with limbs < 2^31.9, or both < 2^30.3.  Value bound of a product: a * b / 2^261 + l; every caller states what it relies on.
+// for which the column sums of the product stay below 2^64.  A column holds at most nine a_i * b_j, the quotient digits (< 2^29) times limbs of
+// l (together at most (2^29 - 1) * S, S = 2 L0 + L1 + L2 + L3 + L4 + L8) and a carry-in below 2^36:
+//     9 * max(a_i) * max(b_j) + (2^29 - 1) * S + 2^36 < 2^64,
+// i.e. one operand with all nine limbs < 2^29 and the other with limbs <= 3597011027 (2^31.74), or both with limbs <= 1389651246 (2^30.37);
+// tests/scalar_cases.py derives the two integers and runs the product at them.  (2^31.9 beside a normalised operand does NOT fit: column 8 of
+// nine limbs 2^29 - 1 times nine limbs 2^31.9 passes 2^64.)  Value bound of a product: a * b / 2^261 + l; every caller states what it relies on.
 //
 // Restates, for this path, upstream libspartan `src/scalar/ristretto255.rs::Scalar::{mul, add, sub}` (montgomery_reduce is its
 // reduction; /root/reference/Spartan is an empty submodule: .gitmodules:4-6); checked against the CPU oracle (fr.c) by the parity tests.

@@ -1,6 +1,7 @@
-// Test-only launches over GF(2^255-19) (otti_k_fp_op, otti_k_pt_op): the inline functions of field.h, fp9.h and fp10.h that the MSM kernels are
-// made of, one case per lane (the quad forms: one case per four lanes), on operands a test chooses.  Nothing is restated here: every operation is
-// a call of the function the hot kernels call, so what these launches return is what k_msm.hip computes on the same operands.
+// Test-only launches over GF(2^255-19) (otti_k_fp_op, otti_k_pt_op) and over GF(l) in nine limbs (otti_k_fr9_op): the inline functions of field.h,
+// fp9.h, fp10.h and fr9.h that the MSM, sum-check, eq-table and sparse kernels are made of, one case per lane (the quad forms: one case per four
+// lanes), on operands a test chooses.  Nothing is restated here: every operation is a call of the function the hot kernels call, so what these
+// launches return is what k_msm.hip, k_sumcheck.hip and k_sparse.hip compute on the same operands.
 #include "kernels_common.h"
 
 namespace otti {
@@ -122,6 +123,46 @@ void dev_pt_op(DevCtx &c, int op, const Pt *P, const void *Q, bool neg, uint32_t
     const size_t lanes = (op == PTOP_Q10_MADD || op == PTOP_Q10_ADD) ? 4 * n : n;
     KScope ks(c, KC_OTHER);
     hipLaunchKernelGGL(k_pt_op, (unsigned)((lanes + kBlock - 1) / kBlock), kBlock, 0, c.stream, op, P, Q, neg ? 1 : 0, k, n, out, limbs);
+}
+
+// ------------------------------------------------------------------------------------------------ GF(l), nine limbs of 29 bits
+__device__ __forceinline__ Fr9 fr9_op_load(const uint32_t *l, size_t i) { Fr9 r; for (int k = 0; k < kFr9OpLimbs; k++) r.v[k] = l[i * kFr9OpLimbs + k]; return r; }
+// out[i]: the word an operation produces; limbs[i * kFr9OpLimbs ..): the limbs it produces (device.h Fr9Op: which operands it reads)
+__global__ __launch_bounds__(kBlock) void k_fr9_op(int op, const Fr *aw, const Fr *bw, const Fr *cw, const uint32_t *al, const uint32_t *bl, Fr *out, uint32_t *limbs, size_t n) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        Fr9 x = fr9_zero(), y = fr9_zero(), r = fr9_zero();
+        if (fr9_op_limbs_in(op) >= 1) x = fr9_op_load(al, i);
+        if (fr9_op_limbs_in(op) >= 2) y = fr9_op_load(bl, i);
+        Fr w = fr_zero(); bool has_word = false, has_limbs = true;
+        switch (op) {
+        case FR9OP_UNPACK: r = fr9_unpack(aw[i]); break;
+        case FR9OP_UNPACK5: r = fr9_unpack5(aw[i]); break;
+        case FR9OP_UNPACK10: r = fr9_unpack_s<10>(aw[i]); break;
+        case FR9OP_MUL: r = fr9_mul(x, y); break;
+        case FR9OP_MUL_SELF: r = fr9_mul(x, x); break;
+        case FR9OP_ADD: r = fr9_add(x, y); break;
+        case FR9OP_NORM: r = fr9_norm(x); break;
+        case FR9OP_SUB_KL2: r = fr9_sub_kl<2>(x, y); break;
+        case FR9OP_SUB_KL4: r = fr9_sub_kl<4>(x, y); break;
+        case FR9OP_SUB_KL8: r = fr9_sub_kl<8>(x, y); break;
+        case FR9OP_SUB_KL16: r = fr9_sub_kl<16>(x, y); break;
+        case FR9OP_SUB_KL128: r = fr9_sub_kl<128>(x, y); break;
+        case FR9OP_FOLD_TOP: r = fr9_fold_top(x); break;
+        case FR9OP_SHL5: r = fr9_shl5(x); break;
+        case FR9OP_PACK_LT2L: w = fr9_pack_lt2l(x); has_word = true; has_limbs = false; break;
+        case FR9OP_PACK_LT3L: w = fr9_pack_lt3l(x); has_word = true; has_limbs = false; break;
+        case FR9OP_CANON: w = fr9_canon(x); has_word = true; has_limbs = false; break;
+        case FR9OP_MUL9: r = fr9_mul(fr9_unpack5(aw[i]), fr9_unpack(bw[i])); w = fr9_pack_lt2l(r); has_word = true; break;
+        default: r = fold9(aw[i], bw[i], fr9_unpack5(cw[i]), w); has_word = true; break;                  // FR9OP_FOLD9
+        }
+        if (has_word) out[i] = w;
+        if (has_limbs) for (int k = 0; k < kFr9OpLimbs; k++) limbs[i * kFr9OpLimbs + k] = r.v[k];
+    }
+}
+void dev_fr9_op(DevCtx &c, int op, const Fr *aw, const Fr *bw, const Fr *cw, const uint32_t *al, const uint32_t *bl, Fr *out, uint32_t *limbs, size_t n) {
+    if (!n) return;
+    KScope ks(c, KC_OTHER);
+    hipLaunchKernelGGL(k_fr9_op, grid_for(n), kBlock, 0, c.stream, op, aw, bw, cw, al, bl, out, limbs, n);
 }
 
 }  // namespace otti

@@ -1,10 +1,12 @@
-// Host build of the nine-limb field arithmetic (otti_amd/csrc/fr9.h, fp9.h: the C bodies; the device uses generated asm blocks that
-// tools/limbbench, the GPU parity tests and tests/test_gpu_curve_arith.py cover) checked against the 8 x u32 arithmetic of field.h / point.h on
-// random inputs and on the edge pool that the device tests use (tests/curve_cases.py).
-// Built and run by tests/test_limb9_host.py (g++, no GPU).
+// Host build of the nine-limb field arithmetic (otti_amd/csrc/fr9.h, fp9.h: the C bodies; the device uses generated asm blocks, which
+// tests/test_gpu_scalar_arith.py (GF(l)) and tests/test_gpu_curve_arith.py (GF(2^255-19)) run on the same pools) checked against the 8 x u32
+// arithmetic of field.h / point.h on random inputs and on the edge pool of tests/curve_cases.py, and, given a case file as second argument,
+// against the plain-integer reference of tests/scalar_cases.py on its pool (limb for limb).
+// Built and run by tests/test_limb9_host.py and tests/test_scalar_cases_host.py (g++, no GPU): limb9_check [iterations [case file]].
 #include "fr9.h"
 #include "fp9.h"
 #include <stdio.h>
+#include <string.h>
 #include <random>
 #include <vector>
 using namespace otti;
@@ -126,10 +128,71 @@ static int wide_sum_checks() {
 #undef WCHECK
     return bad;
 }
+// ---- the case file of tests/scalar_cases.py (write_case_file): per line an operation of otti_k_fr9_op, its operands and the word and / or limbs the
+// plain-integer reference expects; the plain-C bodies of fr9.h must return exactly those.  The pool is stated once, in scalar_cases.py.
+static bool read_u32s(FILE *f, uint32_t *p, int n) { for (int i = 0; i < n; i++) if (fscanf(f, "%x", &p[i]) != 1) return false; return true; }
+static Fr9 fold9_host(const Fr &x0, const Fr &x2, const Fr9 &r5, Fr &word) {      // fold9 of kernels_common.h (a device-only header), as test "fold" above
+    const Fr9 a = fr9_unpack(x0);
+    const Fr9 s = fr9_norm(fr9_add(a, fr9_mul(r5, fr9_sub_kl<2>(fr9_unpack(x2), a))));
+    word = fr9_pack_lt3l(s);
+    return s;
+}
+static int scalar_case_file(const char *path) {
+    static const char *names[] = {"unpack", "unpack5", "unpack10", "mul", "mul_self", "add", "norm", "sub_kl2", "sub_kl4", "sub_kl8", "sub_kl16", "sub_kl128",
+                                  "fold_top", "shl5", "pack_lt2l", "pack_lt3l", "canon", "mul9", "fold9"};
+    enum { UNPACK, UNPACK5, UNPACK10, MUL, MUL_SELF, ADD, NORM, SUB2, SUB4, SUB8, SUB16, SUB128, FOLD_TOP, SHL5, PACK2, PACK3, CANON, MUL9, FOLD9, NOPS };
+    FILE *f = fopen(path, "r");
+    if (!f) { printf("FAIL case file: cannot open %s\n", path); return 1; }
+    int bad = 0; long line = 0, per_op[NOPS] = {0}; char name[32];
+    while (fscanf(f, "%31s", name) == 1) {
+        line++;
+        int op = 0; while (op < NOPS && strcmp(name, names[op])) op++;
+        if (op == NOPS) { printf("FAIL case file: unknown operation %s at line %ld\n", name, line); bad++; break; }
+        const int nw = op <= UNPACK10 ? 1 : op == MUL9 ? 2 : op == FOLD9 ? 3 : 0;
+        const int nl = nw ? 0 : (op == MUL || op == ADD || (op >= SUB2 && op <= SUB128)) ? 2 : 1;
+        const bool has_word = op >= PACK2, has_limbs = op < PACK2 || op >= MUL9;
+        Fr w[3], want_w = fr_zero(), got_w = fr_zero(); Fr9 x[2], want_l = fr9_zero(), got_l = fr9_zero();
+        bool ok = true;
+        for (int k = 0; k < nw; k++) ok = ok && read_u32s(f, w[k].v, 8);
+        for (int k = 0; k < nl; k++) ok = ok && read_u32s(f, x[k].v, 9);
+        if (has_word) ok = ok && read_u32s(f, want_w.v, 8);
+        if (has_limbs) ok = ok && read_u32s(f, want_l.v, 9);
+        if (!ok) { printf("FAIL case file: short line %ld (%s)\n", line, name); bad++; break; }
+        switch (op) {
+        case UNPACK: got_l = fr9_unpack(w[0]); break;
+        case UNPACK5: got_l = fr9_unpack5(w[0]); break;
+        case UNPACK10: got_l = fr9_unpack_s<10>(w[0]); break;
+        case MUL: got_l = fr9_mul(x[0], x[1]); break;
+        case MUL_SELF: got_l = fr9_mul(x[0], x[0]); break;
+        case ADD: got_l = fr9_add(x[0], x[1]); break;
+        case NORM: got_l = fr9_norm(x[0]); break;
+        case SUB2: got_l = fr9_sub_kl<2>(x[0], x[1]); break;
+        case SUB4: got_l = fr9_sub_kl<4>(x[0], x[1]); break;
+        case SUB8: got_l = fr9_sub_kl<8>(x[0], x[1]); break;
+        case SUB16: got_l = fr9_sub_kl<16>(x[0], x[1]); break;
+        case SUB128: got_l = fr9_sub_kl<128>(x[0], x[1]); break;
+        case FOLD_TOP: got_l = fr9_fold_top(x[0]); break;
+        case SHL5: got_l = fr9_shl5(x[0]); break;
+        case PACK2: got_w = fr9_pack_lt2l(x[0]); break;
+        case PACK3: got_w = fr9_pack_lt3l(x[0]); break;
+        case CANON: got_w = fr9_canon(x[0]); break;
+        case MUL9: got_l = fr9_mul(fr9_unpack5(w[0]), fr9_unpack(w[1])); got_w = fr9_pack_lt2l(got_l); break;
+        default: got_l = fold9_host(w[0], w[1], fr9_unpack5(w[2]), got_w); break;
+        }
+        bool same = fr_eq(got_w, want_w);
+        for (int i = 0; i < 9; i++) same = same && got_l.v[i] == want_l.v[i];
+        if (!same) { if (bad < 10) printf("FAIL case file: %s, case %ld of the operation (line %ld)\n", name, per_op[op], line); bad++; }
+        per_op[op]++;
+    }
+    fclose(f);
+    for (int op = 0; op < NOPS; op++) if (!per_op[op] && !bad) { printf("FAIL case file: no case of %s\n", names[op]); bad++; }
+    printf("case file: %ld cases\n", line);
+    return bad;
+}
 #define CHECK(cond, what) do { if (!(cond)) { if (bad < 10) printf("FAIL %s at iteration %d\n", what, it); bad++; } } while (0)
 int main(int argc, char **argv) {
     const int iters = argc > 1 ? atoi(argv[1]) : 20000;
-    int bad = 0;
+    int bad = argc > 2 ? scalar_case_file(argv[2]) : 0;
     for (int it = 0; it < iters; it++) {
         Fr a = rnd_fr(), b = rnd_fr(), c = rnd_fr();
         if (it == 0) a = fr_zero();

@@ -29,16 +29,7 @@ def test_fr_ops(rng, n):
         assert orc.fr_to_ints(out) == [f(x, y) % orc.L_ORDER for x, y in zip(xa, xb)], op
 
 
-def test_fr_edge_values():
-    l = orc.L_ORDER
-    vals = [0, 1, 2, l - 1, l - 2, (l - 1) // 2, 2 ** 252, 2 ** 128, 2 ** 32 - 1, 2 ** 64 - 1]
-    a = orc.fr_from_ints([x for x in vals for _ in vals]); b = orc.fr_from_ints([y for _ in vals for y in vals])
-    xa, xb = orc.fr_to_ints(a), orc.fr_to_ints(b)
-    for op, f in (("mul", lambda x, y: x * y), ("add", lambda x, y: x + y), ("sub", lambda x, y: x - y)):
-        out, _ = K.fr_op(op, a, b)
-        assert orc.fr_to_ints(out) == [f(x, y) % l for x, y in zip(xa, xb)]
-
-
+# (edge values, all pairs: tests/test_gpu_scalar_arith.py::test_eight_word_ops_on_all_pairs_of_the_canonical_pool)
 def test_canonical_roundtrip(rng):
     a = orc.rand_fr(rng, 500)
     canon = K.to_canonical(a)

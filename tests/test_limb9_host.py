@@ -1,7 +1,9 @@
 """The nine-limb field arithmetic of the round-4 kernels (otti_amd/csrc/fr9.h, fp9.h), host build, against the 8 x u32 arithmetic that the
 oracle pins (tests/test_host.py::otti_host_selftest, tests/test_oracle.py), on random values and on the edge pool of tests/curve_cases.py (limb
-boundaries, non-canonical words: all pairs, the compound shapes, p9_madd).  The device bodies (generated asm) are covered on the GPU by
-tests/test_gpu_curve_arith.py (the same pool), tests/test_gpu_kernels.py / test_gpu_parity.py and tools/limbbench."""
+boundaries, non-canonical words: all pairs, the compound shapes, p9_madd).  That pool is GF(2^255-19)'s: the device bodies of fp9.h (generated
+asm) run on it in tests/test_gpu_curve_arith.py.  GF(l)'s pool is tests/scalar_cases.py: the C bodies of fr9.h run on it in
+tests/test_scalar_cases_host.py (this program, given the case file), the device bodies (fr9_mul's generated asm among them) in
+tests/test_gpu_scalar_arith.py; tests/test_gpu_kernels.py / test_gpu_parity.py see them only through whole kernels on stored words."""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
