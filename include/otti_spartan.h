@@ -469,6 +469,37 @@ int32_t otti_snark_verify(const otti_comp_comm *comm, const uint8_t *inputs32, s
 int32_t otti_snark_verify_many(const otti_comp_comm *comm, const otti_snark_gens *gens, const uint8_t *tlabel, size_t tlabel_len, size_t count,
                                const uint8_t *const *inputs32, const size_t *ninputs, const uint8_t *const *proofs, const size_t *proof_lens,
                                uint32_t threads, int32_t *results, size_t *n_rejected /* may be NULL */);
+/* Many SNARK proofs of ONE computation commitment verified as ONE randomised batch.  The staging is otti_snark_verify_many's: chunks of 16, the
+   four-step walk, one device pass per row-sum seam, parked proofs that own no thread.  What differs: the group equations that feed nothing
+   hashed — the sat proof's two per round, its sigma equations, and the FOUR log dot-product closing equations (one over the sat generators, three
+   over the evaluation generators, each with a fixed-base sum over up to 8192 of them) — are not checked proof by proof but collected as term
+   lists and summed, for all proofs of a chunk at once, in one multi-scalar multiplication.  A closing equation's n generator scalars are a
+   product form, s[i] = c * prod over the set bits t of i of f[t]: the verifier states lg n + 1 scalars and the device expands them where the sum
+   reads them (otti_k_gen_runs is that expansion alone), so they never exist on the host.  What is hashed stays per proof: the transcript, the
+   sat rounds' combinations, the four row sums, the product-circuit walk.
+   Verdict rule: results[i] = what otti_snark_verify returns for item i alone with the same commitment, generators and label, code for code, with
+   ONE exception: a proof that otti_snark_verify rejects is accepted with probability at most 2^-120 over the library's own randomness (each
+   equation of each proof has a weight of its own, a full scalar, so no two defects can cancel).  A valid proof is never rejected.  seed32: NULL =
+   OS entropy.  A caller's seed exists only so that tests can repeat a run: a seed the prover could know or guess FORFEITS SOUNDNESS — never pass
+   one in production.
+   How verdicts are reached: a proof that fails on its walk before the evaluation proof has that code; one that fails inside it is run through
+   the single verifier, which checks the sat equations first; if a chunk's one sum over all other proofs is the identity, all of them are
+   accepted; if not, one localisation pass forms each proof's own sum over the points already decoded, and only the proofs whose sum is not the
+   identity, or that hold an undecodable point, are run through the single verifier for their code.
+   Refusals, their order, count == 0, threads (0: the default, 8; more than 16: OTTI_ERR_BAD_ARG), *n_rejected and the otti_last_error wording are
+   otti_snark_verify_many's.  Several caller threads may call with the same handles at once.
+   Where the sum runs: on the device when one is present (each generators handle decoded once and kept on it), on the host cores otherwise, under
+   OTTI_VERIFY_HOST or under OTTI_VERIFY_BATCH_SUM=host (read per call: measurements, tests); the verdicts do not depend on the route.
+   info (may be NULL) is filled whenever the call ran: its counters add up over the chunks, gen_slots counts the slots of both handles,
+   accepted_first_pass says that every chunk's sum was the identity, routed_to_many stays 0.
+   Decided from tools/snark_verify_batch_probe.py on an MI355X (profiles/snark_verify_batch.md has the tables, 2^12, 2^16 and 2^20, 2 to 64 proofs):
+   the default is EIGHT workers (level with four up to 4 proofs, faster from 8 on); there is NO routing rule, because the batch is ahead of
+   otti_snark_verify_many with its four workers in every row, 2 proofs included (at 16 proofs 0.40 - 0.55 of its time); the sum runs on the device
+   at every size (0.26 - 0.66 ms per pass).  A batch of 2 - 4 proofs with a bad one among them is slower than otti_snark_verify_many by 2.5 - 6 ms. */
+int32_t otti_snark_verify_batch(const otti_comp_comm *comm, const otti_snark_gens *gens, const uint8_t *tlabel, size_t tlabel_len, size_t count,
+                                const uint8_t *const *inputs32, const size_t *ninputs, const uint8_t *const *proofs, const size_t *proof_lens,
+                                uint32_t threads, const uint8_t *seed32 /* may be NULL */, int32_t *results, size_t *n_rejected /* may be NULL */,
+                                otti_verify_batch_info *info /* may be NULL */);
 void    otti_buf_free(void *p);
 /* copies the calling thread's last error message (NUL-terminated, truncated to cap) */
 size_t  otti_last_error(char *buf, size_t cap);
@@ -707,6 +738,14 @@ int32_t otti_k_armed_selftest(const uint8_t *A, const uint8_t *B, size_t len, co
    that does not decode.  kernel_ms (may be NULL): device-event time of the two launches.  No host fallback. */
 int32_t otti_k_batch_sum(size_t nsets, const uint8_t *h_compressed32, const size_t *set_offsets, size_t njobs, const uint32_t *job_first_set,
                          const uint32_t *job_nsets, const uint8_t *h_scalars_mont32, uint8_t *out32, int32_t *codes, float *kernel_ms);
+/* The expansion of product-form generator runs alone (one k_gen_runs launch, one thread per (job, slot)): job j is a vector of job_n[j] scalars,
+   out[j][i] = base[j][i] + sum over the runs r of job j with i < 2^lg_r of  c_r * prod_{t < lg_r, bit t of i set} f_r[t]  (bit 0 the least
+   significant).  A job with job_has_base[j] != 0 takes the next job_n[j] words of h_base_mont32, otherwise zeros.  Run r belongs to job
+   run_job[r] (ascending), has run_lg[r] <= 20 factors — the next of h_factors_mont32 — with 2^lg <= job_n, and the coefficient h_run_c_mont32[r].
+   h_out_mont32 takes the jobs' vectors one behind the other.  All scalars are 32-byte Montgomery words.  kernel_ms (may be NULL): device-event
+   time of the tables' upload and the launch.  No host fallback.  OTTI_ERR_BAD_ARG before a device is touched for anything the above excludes. */
+int32_t otti_k_gen_runs(size_t njobs, const size_t *job_n, const uint8_t *job_has_base, const uint8_t *h_base_mont32, size_t nruns, const uint32_t *run_job,
+                        const uint32_t *run_lg, const uint8_t *h_run_c_mont32, const uint8_t *h_factors_mont32, uint8_t *h_out_mont32, float *kernel_ms);
 int32_t otti_k_msm_rows(otti_gens *gens, const uint8_t *h_Z, size_t L, size_t R, const uint8_t *h_blinds, uint8_t *h_out32, float *kernel_ms);
 /* A general fixed-base MSM job, as the prover's launcher takes it, for kernel-level tests: row i = sum_{j < n_dense} dense[i n_dense + j] P[j]
    + sum_{e < n_extra} extra_s[i n_extra + e] P[extra_base[e]] over the generators' R + 2 points (n_dense <= R, n_extra <= 8, extra_base[e] < R + 2;

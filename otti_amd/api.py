@@ -154,6 +154,8 @@ _sig("otti_snark_prove_sharded", _i32, _vp, _vp, _vp, _vp, ctypes.c_char_p, _sz,
 _sig("otti_snark_verify", _i32, _vp, _vp, _sz, _vp, ctypes.c_char_p, _sz, _vp, _sz)
 _sig("otti_snark_verify_many", _i32, _vp, _vp, ctypes.c_char_p, _sz, _sz, ctypes.POINTER(_vp), ctypes.POINTER(_sz), ctypes.POINTER(_vp), ctypes.POINTER(_sz),
      ctypes.c_uint32, ctypes.POINTER(_i32), ctypes.POINTER(_sz))
+_sig("otti_snark_verify_batch", _i32, _vp, _vp, ctypes.c_char_p, _sz, _sz, ctypes.POINTER(_vp), ctypes.POINTER(_sz), ctypes.POINTER(_vp), ctypes.POINTER(_sz),
+     ctypes.c_uint32, _vp, ctypes.POINTER(_i32), ctypes.POINTER(_sz), ctypes.POINTER(_VerifyBatchInfo))
 _sig("otti_zkif_load", _i32, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(ctypes.POINTER(_R1CS)))
 _sig("otti_zkif_write", _i32, ctypes.POINTER(_R1CS), ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p)
 _sig("otti_r1cs_free", None, ctypes.POINTER(_R1CS))
@@ -208,6 +210,7 @@ _sig("otti_k_msm_job", _i32, _vp, _sz, _sz, _vp, _sz, _vp, _vp, _i32, _i32, _i32
 _sig("otti_k_row_sum", _i32, _vp, _sz, _vp, _vp)
 _sig("otti_k_row_sum_many", _i32, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp)
 _sig("otti_k_batch_sum", _i32, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp)
+_sig("otti_k_gen_runs", _i32, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp)
 _sig("otti_k_msm_scatter_rows", _i32, _vp, _sz, _vp, _vp, _sz, _vp, _fp)
 _sig("otti_k_witness_diff", _i32, _vp, _sz, _vp, _i32, _sz, _vp, _vp, _vp, ctypes.POINTER(_u64), ctypes.POINTER(ctypes.c_uint32), _fp)
 _sig("otti_k_eq_pyramid", _i32, _vp, _sz, _vp)
@@ -1074,6 +1077,34 @@ class SNARK:
         assert rejected.value == sum(1 for r in out if r != 0)
         return out
 
+    @staticmethod
+    def verify_batch(comm, proofs, inputs, gens, transcript_label=b"snark_example", threads=0, seed=None, details=False):
+        """Many proofs of ONE computation commitment as one randomised batch (otti_snark_verify_batch): the arguments and the returned list of
+        codes are ``verify_many``'s — element i is what ``verify`` on proof i alone would report, except that a proof it rejects is accepted with
+        probability at most 2^-120 over the library's randomness.  ``seed`` (32 bytes) repeats a run in tests; a seed the prover could know
+        forfeits soundness, so leave it None.  ``details=True`` returns (codes, info dict: the otti_verify_batch_info counters)."""
+        label = bytes(transcript_label)
+        blobs = [np.frombuffer(bytes(p.bytes if isinstance(p, SNARK) else p), dtype=np.uint8) for p in proofs]
+        n = len(blobs)
+        per = list(inputs) if isinstance(inputs, (list, tuple)) else [inputs] * n
+        if len(per) != n:
+            raise ValueError("verify_batch: one InputsAssignment for all proofs, or one per proof")
+        ins = [_scalars(i.assignment, "inputs") for i in per]
+        in_ptrs, in_counts = (_vp * max(1, n))(), (_sz * max(1, n))()
+        pf_ptrs, pf_lens = (_vp * max(1, n))(), (_sz * max(1, n))()
+        empty = np.zeros(1, dtype=np.uint8)
+        for k in range(n):
+            in_ptrs[k], in_counts[k] = _ptr(ins[k]), ins[k].shape[0]
+            pf_ptrs[k], pf_lens[k] = (blobs[k] if blobs[k].size else empty).ctypes.data_as(_vp), blobs[k].size
+        results, rejected, info = (_i32 * max(1, n))(), _sz(0), _VerifyBatchInfo()
+        _check(lib.otti_snark_verify_batch(comm._h, gens._h, label, len(label), n, in_ptrs, in_counts, pf_ptrs, pf_lens, threads, _seed(seed), results,
+                                           ctypes.byref(rejected), ctypes.byref(info)))
+        out = [int(results[k]) for k in range(n)]
+        assert rejected.value == sum(1 for r in out if r != 0)
+        if not details:
+            return out
+        return out, {k: getattr(info, k) for k, _ in _VerifyBatchInfo._fields_}
+
 
 def shard_init(segment_name, rank, world):
     """Join the node-local exchange of a sharded proof (collective; ``segment_name`` must be fresh and the same on every rank)."""
@@ -1582,6 +1613,30 @@ class kernels:
         out = np.zeros((max(1, len(jobs)), 32), dtype=np.uint8); codes = (_i32 * max(1, len(jobs)))(); ms = ctypes.c_float(0)
         _check(lib.otti_k_batch_sum(len(cs), _ptr(comp), _ptr(off), len(jobs), _ptr(first), _ptr(count), _ptr(sc), _ptr(out), codes, ctypes.byref(ms)))
         return out[:len(jobs)], [int(codes[j]) for j in range(len(jobs))], float(ms.value)
+
+    @staticmethod
+    def gen_runs(jobs):
+        """the expansion of product-form generator runs alone (otti_k_gen_runs): ``jobs`` = [(n, base, runs)] with ``base`` n Montgomery scalars
+        or None and ``runs`` = [(coefficient, factors)], Montgomery, a run of lg factors covering slots [0, 2^lg) of its job.  Returns (one
+        (n, 32) Montgomery array per job: base[i] + sum of c * prod of the factors at the set bits of i, device-event ms)"""
+        ns = np.ascontiguousarray([n for n, _, _ in jobs], dtype=np.uint64)
+        has = np.ascontiguousarray([b is not None for _, b, _ in jobs], dtype=np.uint8)
+        bs = [_scalars(b, "base") for _, b, _ in jobs if b is not None]
+        for n, b, _ in jobs:
+            assert b is None or _scalars(b, "base").shape[0] == n
+        base = np.ascontiguousarray(np.concatenate(bs)) if bs else None
+        rj, rl, rc, rf = [], [], [], []
+        for j, (_, _, runs) in enumerate(jobs):
+            for c, f in runs:
+                f = _scalars(f, "factors") if len(f) else np.zeros((0, 32), dtype=np.uint8)
+                rj.append(j); rl.append(f.shape[0]); rc.append(_scalars(c, "c").reshape(1, 32)); rf.append(f)
+        run_job = np.ascontiguousarray(rj, dtype=np.uint32); run_lg = np.ascontiguousarray(rl, dtype=np.uint32)
+        cs = np.ascontiguousarray(np.concatenate(rc)) if rc else None
+        fs = np.ascontiguousarray(np.concatenate(rf)) if rf else None
+        out = np.zeros((max(1, int(ns.sum())), 32), dtype=np.uint8); ms = ctypes.c_float(0)
+        _check(lib.otti_k_gen_runs(len(jobs), _ptr(ns), _ptr(has), _ptr(base), len(rj), _ptr(run_job), _ptr(run_lg), _ptr(cs), _ptr(fs), _ptr(out), ctypes.byref(ms)))
+        cut = np.cumsum(ns).astype(np.int64)[:-1]
+        return np.split(out[:int(ns.sum())], cut), float(ms.value)
 
     @staticmethod
     def msm_scatter_rows(gens, L, idx, s):

@@ -610,6 +610,29 @@ int32_t otti_snark_verify_many(const otti_comp_comm *comm, const otti_snark_gens
         return OTTI_OK;
     });
 }
+// The same proofs as one randomised batch (snark.h snark_verify_batch; the contract: include/otti_spartan.h).  Refusals, their order and count == 0
+// are otti_snark_verify_many's; the bounds per chunk are its too, plus per collected proof a dense scalar per generator of either handle.
+int32_t otti_snark_verify_batch(const otti_comp_comm *comm, const otti_snark_gens *gens, const uint8_t *tlabel, size_t tlabel_len, size_t count,
+                                const uint8_t *const *inputs32, const size_t *ninputs, const uint8_t *const *proofs, const size_t *proof_lens,
+                                uint32_t threads, const uint8_t *seed32, int32_t *results, size_t *n_rejected, otti_verify_batch_info *info) {
+    return guarded([&] {
+        if (!comm || !gens || !results) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        if (threads > kVerifyManyMaxThreads) throw Error(OTTI_ERR_BAD_ARG, "more than 16 worker threads");
+        if (count && (!inputs32 || !ninputs || !proofs || !proof_lens)) throw Error(OTTI_ERR_BAD_ARG, "a null array with count > 0");
+        for (size_t i = 0; i < count; i++) if (!proofs[i] || (ninputs[i] && !inputs32[i])) throw Error(OTTI_ERR_BAD_ARG, "a null proof, or null inputs with a non-zero count");
+        if (n_rejected) *n_rejected = 0;
+        if (info) memset(info, 0, sizeof *info);
+        if (!count) return OTTI_OK;
+        std::vector<VerifyItem> items(count);
+        for (size_t i = 0; i < count; i++) items[i] = {inputs32[i], ninputs[i], proofs[i], proof_lens[i]};
+        snark_verify_batch(*comm->c, *gens->g, tlabel, tlabel_len, items.data(), count, threads, seed32, results, info);
+        size_t bad = 0;
+        for (size_t i = 0; i < count; i++) bad += results[i] != OTTI_OK;
+        if (n_rejected) *n_rejected = bad;
+        if (bad) g_last_error = std::to_string(bad) + " of " + std::to_string(count) + " proofs rejected";
+        return OTTI_OK;
+    });
+}
 
 // ------------------------------------------------------------------------------------------------ zkInterface / synthetic
 int32_t otti_zkif_load(const char *c, const char *i, const char *w, otti_r1cs **out) {

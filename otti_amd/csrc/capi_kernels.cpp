@@ -529,6 +529,47 @@ int32_t otti_k_batch_sum(size_t nsets, const uint8_t *compressed32, const size_t
         return OTTI_OK;
     });
 }
+// The expansion of product-form generator runs alone (device.h dev_gen_runs: one k_gen_runs launch).  Job j has job_n[j] slots; its base, when
+// job_has_base[j], is the next job_n[j] words of base_mont32; run r belongs to job run_job[r] (ascending), has run_lg[r] factors — the next of
+// factors_mont32 — and the coefficient run_c_mont32[r].  out_mont32 takes the jobs' vectors one behind the other.  No host fallback.  The arguments
+// are judged before a device is touched.
+int32_t otti_k_gen_runs(size_t njobs, const size_t *job_n, const uint8_t *job_has_base, const uint8_t *base_mont32, size_t nruns, const uint32_t *run_job,
+                        const uint32_t *run_lg, const uint8_t *run_c_mont32, const uint8_t *factors_mont32, uint8_t *out_mont32, float *kernel_ms) {
+    return guarded([&] {
+        if (!njobs || !job_n || !job_has_base || !out_mont32 || (nruns && (!run_job || !run_lg || !run_c_mont32))) throw Error(OTTI_ERR_BAD_ARG, "null argument, or no jobs");
+        size_t total = 0, nbase = 0, nfac = 0;
+        for (size_t j = 0; j < njobs; j++) {
+            if (job_n[j] < 1 || job_n[j] > kRowSumMaxPoints) throw Error(OTTI_ERR_BAD_ARG, "a job of no slots, or of more than 2^20");
+            total += job_n[j]; if (job_has_base[j]) nbase += job_n[j];
+        }
+        if (nbase && !base_mont32) throw Error(OTTI_ERR_BAD_ARG, "a job has a base and there is none");
+        for (size_t r = 0; r < nruns; r++) {
+            if (run_job[r] >= njobs || (r && run_job[r] < run_job[r - 1])) throw Error(OTTI_ERR_BAD_ARG, "a run names a job that is not there, or the runs are not sorted by job");
+            if (run_lg[r] > kGenRunMaxLg || ((size_t)1 << run_lg[r]) > job_n[run_job[r]]) throw Error(OTTI_ERR_BAD_ARG, "a run of more slots than its job has");
+            nfac += run_lg[r];
+        }
+        if (nfac && !factors_mont32) throw Error(OTTI_ERR_BAD_ARG, "runs with factors and there are none");
+        std::vector<Fr> base(nbase), fac(nfac); std::vector<GenRunIn> runs(nruns); std::vector<GenRunsJobIn> jobs(njobs);
+        if (nbase) memcpy(base.data(), base_mont32, 32 * nbase);
+        if (nfac) memcpy(fac.data(), factors_mont32, 32 * nfac);
+        nfac = 0;
+        for (size_t r = 0; r < nruns; r++) { memcpy(&runs[r].c, run_c_mont32 + 32 * r, 32); runs[r].lg = run_lg[r]; runs[r].f = fac.data() + nfac; nfac += run_lg[r]; }
+        DevCtx &c = DevCtx::get();
+        DevBuf<Fr> out(total); GenRunsStaging keep;
+        size_t at = 0, r = 0; nbase = 0;
+        for (size_t j = 0; j < njobs; j++) {
+            jobs[j].n = job_n[j]; jobs[j].out_dev = out.p + at; at += job_n[j];
+            if (job_has_base[j]) { jobs[j].base = base.data() + nbase; nbase += job_n[j]; }
+            jobs[j].runs = runs.data() + r;
+            while (r < nruns && run_job[r] == j) { r++; jobs[j].nruns++; }
+        }
+        struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } } drain{c.stream};
+        { KTimer t(c, kernel_ms); dev_gen_runs(c, jobs.data(), njobs, keep); t.stop(); }
+        OTTI_HIP(hipMemcpyAsync(out_mont32, out.p, 32 * total, hipMemcpyDeviceToHost, c.stream));
+        OTTI_HIP(hipStreamSynchronize(c.stream));
+        return OTTI_OK;
+    });
+}
 int32_t otti_k_msm_rows(otti_gens *gens, const uint8_t *Z, size_t L, size_t R, const uint8_t *blinds, uint8_t *out32, float *ms) {
     return guarded([&] {
         DevCtx &c = DevCtx::get(); Gens &g = *gens->g;

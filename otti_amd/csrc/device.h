@@ -578,8 +578,29 @@ void dev_row_sums_many(DevCtx &c, const RowSumSetIn *sets, size_t nsets, const R
 // may leave scalars null to take those its points got from the first job of that pass, if that job spanned all sets — the localisation pass sends
 // only the generator scalars.  ms (may be null): device-event time of the launches.  Waits; recombines the windows on the host as the row sums do.
 // HBM: grow-only per context, 32 + 96 bytes per point, 32 per scalar (twice for a second pass), 128 per (window, split) — at most 51 * ceil(n / 2048) per job.
-struct BatchSumIn { const uint8_t *comp32 = nullptr; const size_t *set_off = nullptr; size_t nsets = 0; const Niels *gens = nullptr; size_t ngens = 0; bool gens_bad = false, reuse = false; };
-struct BatchSumJobIn { size_t first_set = 0, nsets = 1; const Fr *scalars = nullptr; };
+// A SNARK batch has two generator handles: a second resident set, gens2, is set index nsets + 1.  A job on a generator set carries either host
+// scalars, as above, or — scalars null — {base, runs}: its scalars are formed in HBM by k_gen_runs, launched on the same stream just ahead of the
+// sums, straight into the slice the job's sum reads: sc[i] = base[i] + sum over the runs r with i < 2^lg_r of c_r * prod_{bit t of i set} f_r[t].
+// base: n dense scalars (host, Montgomery) or null for zeros.  A run of more slots than its set has points is OTTI_ERR_BAD_ARG.
+struct GenRunIn { Fr c; uint32_t lg = 0; const Fr *f = nullptr; };         // host: coefficient, lg factors (Montgomery)
+struct BatchSumIn {
+    const uint8_t *comp32 = nullptr; const size_t *set_off = nullptr; size_t nsets = 0; const Niels *gens = nullptr; size_t ngens = 0; bool gens_bad = false, reuse = false;
+    const Niels *gens2 = nullptr; size_t ngens2 = 0; bool gens2_bad = false;
+};
+struct BatchSumJobIn { size_t first_set = 0, nsets = 1; const Fr *scalars = nullptr; const Fr *base = nullptr; const GenRunIn *runs = nullptr; size_t nruns = 0; };
+// The expansion alone (k_msm.hip k_gen_runs, one thread per (job, slot), the runs' factors staged in LDS a tile at a time, no atomics): job j writes
+// n scalars to out_dev, which is device memory.  Queues the tables' upload and the launch on c.stream and returns; `keep` holds the host and
+// device staging, so it must live until the stream has drained.  Throws OTTI_ERR_BAD_ARG before anything is queued: no jobs, a job of no slots or
+// more than kRowSumMaxPoints, a run with 2^lg > n or without its factors.
+constexpr uint32_t kGenRunMaxLg = 20, kGenRunTile = 8;
+struct GenRunsJobIn { size_t n = 0; const Fr *base = nullptr; const GenRunIn *runs = nullptr; size_t nruns = 0; Fr *out_dev = nullptr; };
+struct GenRunDev { Fr c; uint32_t lg, f_off, job, pad; };
+struct GenRunsJobDev { Fr *out; const Fr *base; uint32_t n, run_first, run_count, pad; };
+struct GenRunsStaging {
+    DevBuf<Fr> base, fac; DevBuf<GenRunDev> runs; DevBuf<GenRunsJobDev> jobs; DevBuf<uint32_t> first;
+    std::vector<Fr> h_base, h_fac; std::vector<GenRunDev> h_runs; std::vector<GenRunsJobDev> h_jobs; std::vector<uint32_t> h_first;
+};
+void dev_gen_runs(DevCtx &c, const GenRunsJobIn *jobs, size_t njobs, GenRunsStaging &keep);
 void dev_batch_sum(DevCtx &c, const BatchSumIn &in, const BatchSumJobIn *jobs, size_t njobs, RowSumOut *out, float *ms);
 const unsigned *dev_batch_sum_bad(DevCtx &c);                              // per set of the last decoding pass: how many of its points did not decode
 struct DecodedSet { DevBuf<Niels> pts; size_t n = 0; bool bad = false; };      // bad: some encoding did not decode (the identity stands in its place)

@@ -1,5 +1,6 @@
 // K8 fixed-base MSM over the generator window table (commitments, bullet-reduction rounds), the table build, K10 bookkeeping.
 #include "kernels_common.h"
+#include "fr9.h"
 
 namespace otti {
 
@@ -747,6 +748,85 @@ __global__ __launch_bounds__(kBlock) void k_msm_var_many(const VarMsmArgs *jobs,
     const VarMsmArgs A = jobs[lo];
     msm_var_block(A, (int)blockIdx.x, blockIdx.y - first[lo]);
 }
+template <class T> static void grow(DevBuf<T> &b, size_t n) { if (b.n < n) b.alloc(n + n / 4); }
+// The generator scalars of a batch of SNARK proofs, formed where the sums read them (device.h dev_gen_runs).  The closing equation of a log
+// dot-product proof names its n generators with  s[i] = c * prod_{bit t of i set} f[t]: lg n + 1 scalars per proof come up instead of n, and one
+// thread per (job, slot) multiplies its own product out — at most lg n field products, no thread waits for another, no atomics: a slot belongs to
+// one thread.  A workgroup is kBlock consecutive slots of one job (first[j]: job j's first blockIdx.x, searched as k_msm_var_many does).  The
+// job's runs go through LDS kGenRunTile at a time: coefficient, lg and factors are the same for every slot, so a tile is loaded once per
+// workgroup and read as broadcasts.  The multiplications are uniform — a clear bit multiplies by one — so a wave never splits on the bits of i;
+// a run shorter than the job's vector leaves the slots past its 2^lg alone.
+// Arithmetic: the nine-limb product (fr9.h; 58 VGPRs against 73 with the eight-word one, profiles/snark_verify_batch.md), one conversion at the end
+// of a run.  fr9_mul(a, b) = a b 2^-261, so the factors are staged as limbs of 32 f (fr9_unpack5, as is the one a clear bit multiplies by) and a
+// product stays in the memory format.  Bounds: p starts as the limbs of a canonical c < l; a staged factor is normalised with value < 32 l, so
+// p' < p * 32 l / 2^261 + l < 2 l whenever p < 2 l (64 l^2 < 2^510): every p is normalised and below 2 l, which fr9_mul and fr9_pack_lt2l ask for.
+__global__ __launch_bounds__(kBlock) void k_gen_runs(const GenRunsJobDev *jobs, const uint32_t *first, uint32_t njobs, const GenRunDev *runs, const Fr *fac) {
+    __shared__ Fr s_c[kGenRunTile]; __shared__ Fr9 s_f[kGenRunTile][kGenRunMaxLg];
+    __shared__ uint32_t s_lg[kGenRunTile];
+    uint32_t lo = 0, hi = njobs;                                       // the last j with first[j] <= blockIdx.x
+    while (hi - lo > 1) { const uint32_t mid = (lo + hi) / 2; if (first[mid] <= blockIdx.x) lo = mid; else hi = mid; }
+    const GenRunsJobDev J = jobs[lo];
+    const uint32_t tid = threadIdx.x, i = (blockIdx.x - first[lo]) * kBlock + tid;
+    const bool mine = i < J.n;
+    Fr acc = (mine && J.base) ? J.base[i] : fr_zero();
+    const Fr9 one = fr9_unpack5(fr_one());
+    for (uint32_t r0 = 0; r0 < J.run_count; r0 += kGenRunTile) {
+        const uint32_t nr = min(kGenRunTile, J.run_count - r0);
+        __syncthreads();                                               // the tile before this one has been read by everyone
+        for (uint32_t k = tid; k < nr * (kGenRunMaxLg + 1); k += kBlock) {
+            const uint32_t r = k / (kGenRunMaxLg + 1), t = k % (kGenRunMaxLg + 1);
+            const GenRunDev &R = runs[J.run_first + r0 + r];
+            if (t == kGenRunMaxLg) { s_c[r] = R.c; s_lg[r] = R.lg; }
+            else if (t < R.lg) s_f[r][t] = fr9_unpack5(fac[R.f_off + t]);
+        }
+        __syncthreads();
+        for (uint32_t r = 0; r < nr; r++) {
+            const uint32_t lg = s_lg[r];
+            if (!mine || (i >> lg) != 0) continue;
+            Fr9 p = fr9_unpack(s_c[r]);
+            for (uint32_t t = 0; t < lg; t++) {
+                const Fr9 f = s_f[r][t];
+                Fr9 m;
+                for (int k = 0; k < 9; k++) m.v[k] = ((i >> t) & 1u) ? f.v[k] : one.v[k];
+                p = fr9_mul(p, m);
+            }
+            acc = fr_add(acc, fr9_pack_lt2l(p));
+        }
+    }
+    if (mine) J.out[i] = acc;
+}
+void dev_gen_runs(DevCtx &c, const GenRunsJobIn *jobs, size_t njobs, GenRunsStaging &K) {
+    if (!jobs || !njobs) throw Error(OTTI_ERR_BAD_ARG, "gen runs: no jobs");
+    K.h_base.clear(); K.h_fac.clear(); K.h_runs.clear(); K.h_jobs.assign(njobs, GenRunsJobDev()); K.h_first.assign(njobs + 1, 0);
+    std::vector<size_t> base_at(njobs, SIZE_MAX);
+    size_t blocks = 0;
+    for (size_t j = 0; j < njobs; j++) {
+        const GenRunsJobIn &J = jobs[j];
+        if (J.n < 1 || J.n > kRowSumMaxPoints || !J.out_dev || (J.nruns && !J.runs)) throw Error(OTTI_ERR_BAD_ARG, "gen runs: a job of no slots, of more than 2^20, or without its output or runs");
+        K.h_first[j] = (uint32_t)blocks; blocks += (J.n + kBlock - 1) / kBlock;
+        GenRunsJobDev &D = K.h_jobs[j];
+        D.out = J.out_dev; D.base = nullptr; D.n = (uint32_t)J.n; D.run_first = (uint32_t)K.h_runs.size(); D.run_count = (uint32_t)J.nruns; D.pad = 0;
+        if (J.base) { base_at[j] = K.h_base.size(); K.h_base.insert(K.h_base.end(), J.base, J.base + J.n); }
+        for (size_t r = 0; r < J.nruns; r++) {
+            const GenRunIn &R = J.runs[r];
+            if (R.lg > kGenRunMaxLg || ((size_t)1 << R.lg) > J.n || (R.lg && !R.f)) throw Error(OTTI_ERR_BAD_ARG, "gen runs: a run of more slots than its job has, or without its factors");
+            GenRunDev d; d.c = R.c; d.lg = R.lg; d.f_off = (uint32_t)K.h_fac.size(); d.job = (uint32_t)j; d.pad = 0;
+            K.h_runs.push_back(d); K.h_fac.insert(K.h_fac.end(), R.f, R.f + R.lg);
+        }
+    }
+    K.h_first[njobs] = (uint32_t)blocks;
+    if (blocks >= ((size_t)1 << 31) || K.h_fac.size() >= ((size_t)1 << 31)) throw Error(OTTI_ERR_INTERNAL, "gen runs: too many slots or factors in one pass");
+    grow(K.base, std::max<size_t>(1, K.h_base.size())); grow(K.fac, std::max<size_t>(1, K.h_fac.size())); grow(K.runs, std::max<size_t>(1, K.h_runs.size()));
+    grow(K.jobs, njobs); grow(K.first, njobs + 1);
+    for (size_t j = 0; j < njobs; j++) if (base_at[j] != SIZE_MAX) K.h_jobs[j].base = K.base.p + base_at[j];
+    if (!K.h_base.empty()) OTTI_HIP(hipMemcpyAsync(K.base.p, K.h_base.data(), K.h_base.size() * sizeof(Fr), hipMemcpyHostToDevice, c.stream));
+    if (!K.h_fac.empty()) OTTI_HIP(hipMemcpyAsync(K.fac.p, K.h_fac.data(), K.h_fac.size() * sizeof(Fr), hipMemcpyHostToDevice, c.stream));
+    if (!K.h_runs.empty()) OTTI_HIP(hipMemcpyAsync(K.runs.p, K.h_runs.data(), K.h_runs.size() * sizeof(GenRunDev), hipMemcpyHostToDevice, c.stream));
+    OTTI_HIP(hipMemcpyAsync(K.jobs.p, K.h_jobs.data(), njobs * sizeof(GenRunsJobDev), hipMemcpyHostToDevice, c.stream));
+    OTTI_HIP(hipMemcpyAsync(K.first.p, K.h_first.data(), (njobs + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c.stream));
+    KScope ks(c, KC_MSM_VAR);
+    hipLaunchKernelGGL(k_gen_runs, (unsigned)blocks, kBlock, 0, c.stream, (const GenRunsJobDev *)K.jobs.p, (const uint32_t *)K.first.p, (uint32_t)njobs, (const GenRunDev *)K.runs.p, (const Fr *)K.fac.p);
+}
 // the shape of one sum over n points: splits of at most kVarChunk points, ~8 points per bucket (2^(c-1) buckets for `chunk` points)
 static void var_msm_shape(VarMsmArgs &A, size_t n) {
     const size_t splits = (n + kVarChunk - 1) / kVarChunk, chunk = (n + splits - 1) / splits;
@@ -811,7 +891,6 @@ void dev_decode_set(DevCtx &c, const uint8_t *comp32, size_t n, DecodedSet &out)
 }
 // Grow-only working memory of dev_row_sums_many, per context, kept across calls as the row-sum slots are.
 struct RowSumManyScratch { DevBuf<uint8_t> comp; DevBuf<Niels> pts; DevBuf<Fr> sc; DevBuf<Pt> out; DevBuf<unsigned> bad; DevBuf<uint32_t> tab; DevBuf<VarMsmArgs> jobs; };
-template <class T> static void grow(DevBuf<T> &b, size_t n) { if (b.n < n) b.alloc(n + n / 4); }
 void dev_row_sums_many(DevCtx &c, const RowSumSetIn *sets, size_t nsets, const RowSumJobIn *jobs, size_t njobs, RowSumOut *out) {
     if (!sets || !jobs || !out || !nsets || !njobs) throw Error(OTTI_ERR_BAD_ARG, "row sums: no sets or no jobs");
     // ---- the sets that still have to be decoded lie one behind the other in one buffer; off[k]: the first point of the k-th of them
@@ -893,6 +972,7 @@ void dev_row_sums_many(DevCtx &c, const RowSumSetIn *sets, size_t nsets, const R
 struct BatchSumScratch {
     DevBuf<uint8_t> comp; DevBuf<Niels> pts; DevBuf<Fr> sc, sc_again; DevBuf<Pt> out; DevBuf<unsigned> bad; DevBuf<uint32_t> tab; DevBuf<VarMsmArgs> jobs;
     std::vector<uint32_t> off; std::vector<unsigned> h_bad; bool point_scalars = false;      // what the last decoding pass left resident
+    GenRunsStaging gen;                                                   // jobs whose scalars k_gen_runs forms
 };
 void dev_batch_sum(DevCtx &c, const BatchSumIn &in, const BatchSumJobIn *jobs, size_t njobs, RowSumOut *out, float *ms) {
     if (!jobs || !out || !njobs || !in.nsets || !in.set_off || (!in.reuse && !in.comp32)) throw Error(OTTI_ERR_BAD_ARG, "batch sum: no sets or no jobs");
@@ -902,6 +982,7 @@ void dev_batch_sum(DevCtx &c, const BatchSumIn &in, const BatchSumJobIn *jobs, s
     for (size_t k = 0; k < nsets; k++) if (in.set_off[k + 1] <= in.set_off[k]) throw Error(OTTI_ERR_BAD_ARG, "batch sum: an empty set");
     if (in.set_off[0] != 0 || total_pts > ((size_t)1 << 24)) throw Error(OTTI_ERR_BAD_ARG, "batch sum: offsets that do not start at 0, or more than 2^24 points");
     if (in.gens ? (in.ngens < 1 || in.ngens > kRowSumMaxPoints) : in.ngens != 0) throw Error(OTTI_ERR_BAD_ARG, "batch sum: a generator set of no points or of more than 2^20");
+    if (in.gens2 ? (!in.gens || in.ngens2 < 1 || in.ngens2 > kRowSumMaxPoints) : in.ngens2 != 0) throw Error(OTTI_ERR_BAD_ARG, "batch sum: a second generator set without a first, of no points or of more than 2^20");
     if (in.reuse) {
         bool same = S.off.size() == nsets + 1;
         for (size_t k = 0; same && k <= nsets; k++) same = S.off[k] == (uint32_t)in.set_off[k];
@@ -910,14 +991,18 @@ void dev_batch_sum(DevCtx &c, const BatchSumIn &in, const BatchSumJobIn *jobs, s
     // ---- the job table: every job's shape is the one dev_msm_var takes for its n; results one behind the other, (window, split) within a job
     std::vector<VarMsmArgs> tbl(njobs); std::vector<size_t> out_off(njobs), sc_at(njobs, SIZE_MAX);
     std::vector<uint32_t> first(njobs + 1);
-    size_t total_sc = 0, total_out = 0, total_y = 0; int max_W = 0;
+    std::vector<GenRunsJobIn> gen_jobs; std::vector<size_t> gen_of;
+    size_t total_sc = 0, total_exp = 0, total_out = 0, total_y = 0; int max_W = 0;
     for (size_t j = 0; j < njobs; j++) {
-        const BatchSumJobIn &J = jobs[j]; const bool on_gens = J.first_set == nsets;
-        if (on_gens ? (!in.gens || J.nsets != 1) : (J.nsets < 1 || J.first_set + J.nsets > nsets)) throw Error(OTTI_ERR_BAD_ARG, "batch sum: a job names sets that are not there");
-        if (!J.scalars && (on_gens || !in.reuse || !S.point_scalars)) throw Error(OTTI_ERR_BAD_ARG, "batch sum: a job without scalars where none are resident");
-        const size_t n = on_gens ? in.ngens : in.set_off[J.first_set + J.nsets] - in.set_off[J.first_set];
+        const BatchSumJobIn &J = jobs[j]; const bool on_gens2 = J.first_set == nsets + 1, on_gens = J.first_set == nsets || on_gens2;
+        if (on_gens ? (!(on_gens2 ? in.gens2 : in.gens) || J.nsets != 1) : (J.nsets < 1 || J.first_set + J.nsets > nsets)) throw Error(OTTI_ERR_BAD_ARG, "batch sum: a job names sets that are not there");
+        const bool expand = on_gens && !J.scalars && (J.base || J.nruns);                     // its scalars are formed in HBM
+        if (!J.scalars && !expand && (on_gens || !in.reuse || !S.point_scalars)) throw Error(OTTI_ERR_BAD_ARG, "batch sum: a job without scalars where none are resident");
+        const size_t n = on_gens2 ? in.ngens2 : on_gens ? in.ngens : in.set_off[J.first_set + J.nsets] - in.set_off[J.first_set];
         var_msm_shape(tbl[j], n);
         if (J.scalars) { sc_at[j] = total_sc; total_sc += n; }
+        if (expand) { sc_at[j] = total_exp; total_exp += n; }                                 // behind the host scalars: nothing goes up for these
+        if (expand) { GenRunsJobIn G; G.n = n; G.base = J.base; G.runs = J.runs; G.nruns = J.nruns; gen_jobs.push_back(G); gen_of.push_back(j); }
         out_off[j] = total_out; total_out += (size_t)tbl[j].W * tbl[j].splits;
         first[j] = (uint32_t)total_y; total_y += (size_t)tbl[j].splits;
         max_W = std::max(max_W, tbl[j].W);
@@ -926,13 +1011,15 @@ void dev_batch_sum(DevCtx &c, const BatchSumIn &in, const BatchSumJobIn *jobs, s
     if (total_y > 65535) throw Error(OTTI_ERR_INTERNAL, "batch sum: too many splits in one pass");
     DevBuf<Fr> &SC = in.reuse ? S.sc_again : S.sc;                        // a second pass leaves the first one's point scalars where they are
     if (!in.reuse) { grow(S.comp, 32 * total_pts); grow(S.pts, total_pts); grow(S.bad, nsets); }
-    grow(SC, std::max<size_t>(1, total_sc)); grow(S.out, total_out); grow(S.jobs, njobs); grow(S.tab, nsets + 1 + njobs + 1);
+    for (size_t j : gen_of) sc_at[j] += total_sc;
+    grow(SC, std::max<size_t>(1, total_sc + total_exp)); grow(S.out, total_out); grow(S.jobs, njobs); grow(S.tab, nsets + 1 + njobs + 1);
     for (size_t j = 0; j < njobs; j++) {
         const BatchSumJobIn &J = jobs[j]; VarMsmArgs &A = tbl[j];
-        A.pts = J.first_set == nsets ? in.gens : S.pts.p + in.set_off[J.first_set];
-        A.sc = J.scalars ? SC.p + sc_at[j] : S.sc.p + in.set_off[J.first_set];
+        A.pts = J.first_set == nsets + 1 ? in.gens2 : J.first_set == nsets ? in.gens : S.pts.p + in.set_off[J.first_set];
+        A.sc = sc_at[j] != SIZE_MAX ? SC.p + sc_at[j] : S.sc.p + in.set_off[J.first_set];
         A.out = S.out.p + out_off[j];
     }
+    for (size_t k = 0; k < gen_jobs.size(); k++) gen_jobs[k].out_dev = SC.p + sc_at[gen_of[k]];
     std::vector<Fr> sc(total_sc);
     for (size_t j = 0; j < njobs; j++) if (jobs[j].scalars) memcpy(sc.data() + sc_at[j], jobs[j].scalars, (size_t)tbl[j].n * sizeof(Fr));
     std::vector<uint32_t> tab(nsets + 1);
@@ -953,6 +1040,7 @@ void dev_batch_sum(DevCtx &c, const BatchSumIn &in, const BatchSumJobIn *jobs, s
         KScope ks(c, KC_DECODE);
         hipLaunchKernelGGL(k_decode_niels_sets, (unsigned)((total_pts + 63) / 64), 64, 0, c.stream, (const uint8_t *)S.comp.p, (const uint32_t *)S.tab.p, (uint32_t)nsets, S.pts.p, S.bad.p);
     }
+    if (!gen_jobs.empty()) dev_gen_runs(c, gen_jobs.data(), gen_jobs.size(), S.gen);     // after the host scalars' copy, which leaves these slices alone; ahead of the sums
     {
         KScope ks(c, KC_MSM_VAR);
         hipLaunchKernelGGL(k_msm_var_many, dim3((unsigned)max_W, (unsigned)total_y), kBlock, 0, c.stream, (const VarMsmArgs *)S.jobs.p, (const uint32_t *)(S.tab.p + nsets + 1), (uint32_t)njobs);
@@ -967,8 +1055,8 @@ void dev_batch_sum(DevCtx &c, const BatchSumIn &in, const BatchSumJobIn *jobs, s
     // ---- per job: sum_w 2^(c w) * (sum over splits), Horner from the top window, c doublings per step
     for (size_t j = 0; j < njobs; j++) {
         const BatchSumJobIn &J = jobs[j]; const VarMsmArgs &A = tbl[j];
-        bool undecodable = J.first_set == nsets ? in.gens_bad : false;
-        if (J.first_set != nsets) for (size_t k = J.first_set; k < J.first_set + J.nsets; k++) undecodable |= S.h_bad[k] != 0;
+        bool undecodable = J.first_set == nsets ? in.gens_bad : J.first_set == nsets + 1 ? in.gens2_bad : false;
+        if (J.first_set < nsets) for (size_t k = J.first_set; k < J.first_set + J.nsets; k++) undecodable |= S.h_bad[k] != 0;
         if (undecodable) { out[j].code = OTTI_ERR_VERIFY_DECOMPRESS; out[j].sum = pt_identity(); continue; }
         const Pt *p = part.data() + out_off[j];
         Pt acc = pt_identity();

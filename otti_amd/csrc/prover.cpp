@@ -222,8 +222,55 @@ static bool batch_sum_on_device(const Gens &g, const BatchSumSet *sets, size_t n
         return true;
     } catch (const Error &) { return false; }
 }
+// snark_verify_batch's sum (snark.h g_snark_batch_sum_hook): the same passes over two generator handles, each decoded once and kept on its handle.
+// No generator scalar goes up written out: a handle's job carries the folded explicit terms as its base and the proofs' product-form runs, and
+// k_gen_runs forms the scalars in HBM ahead of the sums.
+static bool snark_batch_sum_on_device(const Gens *const g[2], const SnarkBatchSet *sets, size_t nsets, const BatchGenSide total[2], bool localise, Pt *sums, uint8_t *set_bad, double *ms) {
+    try {
+        if (!nsets) return false;
+        for (int h = 0; h < 2; h++) if (g[h]->P.size() > kRowSumMaxPoints) return false;
+        DevCtx &c = DevCtx::get();
+        std::shared_ptr<GensDecoded> gd[2] = {gens_decoded(c, *g[0]), gens_decoded(c, *g[1])};      // held for the pass
+        for (int h = 0; h < 2; h++) if (gd[h]->set.bad || gd[h]->set.n != g[h]->P.size()) return false;
+        std::vector<size_t> off(nsets + 1, 0);
+        for (size_t k = 0; k < nsets; k++) off[k + 1] = off[k] + sets[k].n;
+        BatchSumIn in; in.set_off = off.data(); in.nsets = nsets; in.reuse = localise;
+        in.gens = gd[0]->set.pts.p; in.ngens = gd[0]->set.n; in.gens2 = gd[1]->set.pts.p; in.ngens2 = gd[1]->set.n;
+        std::vector<std::vector<GenRunIn>> runs;                          // per generator job, in the jobs' order
+        auto side = [&](const BatchGenSide &s, size_t set) {
+            runs.emplace_back(s.nruns);
+            for (size_t r = 0; r < s.nruns; r++) { GenRunIn &R = runs.back()[r]; R.c = s.runs[r]->c; R.lg = (uint32_t)s.runs[r]->lg(); R.f = s.runs[r]->f.data(); }
+            BatchSumJobIn J; J.first_set = set; J.nsets = 1; J.base = s.base; J.nruns = s.nruns;
+            return J;
+        };
+        std::vector<uint8_t> comp; std::vector<Fr> sc; std::vector<BatchSumJobIn> jobs; float t = 0;
+        const size_t first_gen = localise ? nsets : 1, ngen = localise ? 2 * nsets : 2;
+        runs.reserve(ngen);
+        if (!localise) {
+            comp.resize(32 * off[nsets]); sc.resize(off[nsets]);
+            for (size_t k = 0; k < nsets; k++) { memcpy(&comp[32 * off[k]], sets[k].comp32, 32 * sets[k].n); memcpy(&sc[off[k]], sets[k].scalars, sets[k].n * sizeof(Fr)); }
+            in.comp32 = comp.data();
+            BatchSumJobIn all; all.first_set = 0; all.nsets = nsets; all.scalars = sc.data();
+            jobs = {all, side(total[0], nsets), side(total[1], nsets + 1)};
+        } else {
+            for (size_t k = 0; k < nsets; k++) { BatchSumJobIn J; J.first_set = k; J.nsets = 1; jobs.push_back(J); }
+            for (size_t k = 0; k < nsets; k++) for (int h = 0; h < 2; h++) jobs.push_back(side(sets[k].gen[h], nsets + h));
+        }
+        for (size_t j = 0; j < ngen; j++) jobs[first_gen + j].runs = runs[j].data();
+        std::vector<RowSumOut> out(jobs.size());
+        dev_batch_sum(c, in, jobs.data(), jobs.size(), out.data(), &t);
+        if (!localise) {
+            const unsigned *bad = dev_batch_sum_bad(c);
+            for (size_t k = 0; k < nsets; k++) set_bad[k] = bad[k] != 0;
+            sums[0] = pt_add(out[0].sum, pt_add(out[1].sum, out[2].sum));
+        } else
+            for (size_t k = 0; k < nsets; k++) { set_bad[k] = out[k].code != 0; sums[k] = pt_add(out[k].sum, pt_add(out[nsets + 2 * k].sum, out[nsets + 2 * k + 1].sum)); }
+        if (ms) *ms = t;
+        return true;
+    } catch (const Error &) { return false; }
+}
 static const bool g_hook_registered = [] {
-    g_row_sums_many_hook = row_sums_many_on_device; g_batch_sum_hook = batch_sum_on_device;
+    g_row_sums_many_hook = row_sums_many_on_device; g_batch_sum_hook = batch_sum_on_device; g_snark_batch_sum_hook = snark_batch_sum_on_device;
     g_fixed_base_msm_hook = fixed_base_msm_on_device; g_row_sum_begin_hook = row_sum_begin_on_device; g_row_sum_finish_hook = row_sum_finish_on_device;
     return true;
 }();

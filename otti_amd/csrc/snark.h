@@ -83,7 +83,7 @@ struct RowAnswer { int code = 0; Pt sum; };
 class EvalProofVerifier {
 public:
     EvalProofVerifier(const EvalProof &E, const CompComm &c, const std::vector<Fr> &rx, const std::vector<Fr> &ry, const Fr evals[3], const SnarkGens &g, Transcript &tr,
-                      int deferred_threads = -1);
+                      int deferred_threads = -1, BtEquations *sink = nullptr);   // sink: the group equations over g.eval are stated to it and not run (no threads then)
     RowRequest begin();                                      // step 0: the product-layer and layered sum-check walk; names the sum over comm_derefs
     RowRequest after_derefs(const RowAnswer &a);             // step 1: names the sum over comm_ops
     RowRequest after_ops(const RowAnswer &a);                // step 2: names the sum over comm_mem
@@ -94,7 +94,7 @@ private:
     Fr evals[3]; size_t nm = 0;
     std::vector<Fr> rxe, rye, r_mem_check, claims_ops, claims_dotp, rand_ops, claims_mem, rand_mem;
     // the evaluation proof whose row sum is out
-    const DotProductProofLog *pe_pf = nullptr; const PcSet *pe_set = nullptr; std::vector<Fr> Lv, Rv; CPoint C_Zr;
+    const DotProductProofLog *pe_pf = nullptr; const PcSet *pe_set = nullptr; std::vector<Fr> Lv, Rv, Rpt; CPoint C_Zr;   // Rpt: the point Rv is the eq table of
     bool trace; std::chrono::steady_clock::time_point t_lap, t_sum;
     void lap(const char *what);
     RowRequest polyeval_begin(const DotProductProofLog &pf, const PcSet &s, const std::vector<Fr> &r, const Fr &Zr, const std::vector<CPoint> &comm);
@@ -125,6 +125,40 @@ typedef bool (*RowSumsManyHook)(const CompComm &comm, const RowRequest *req, siz
 extern RowSumsManyHook g_row_sums_many_hook;
 void snark_verify_many(const CompComm &comm, const SnarkGens &g, const void *tlabel, size_t tlabel_len, const VerifyItem *items, size_t count, unsigned threads,
                        int32_t *results);
+// The staging itself — chunks, the four-step walk, one device pass per seam, parked proofs that own no thread — for both callers.  With chunk_end the
+// proofs state their group equations instead of running them: sat holds those over g.sat (r1cs_verify_host), eval those over g.eval (the three
+// closing equations of EvalProofVerifier); generator slots are per handle, so the lists stay apart.  Both sinks take product-form runs.
+// After a chunk's last step chunk_end gets, on the calling thread, every proof of the chunk whose verdict the walk has not written: walk_code 0 — it
+// walked to the end —, or the code it met inside the evaluation proof (the single verifier runs the sat equations before that: it decides).
+struct SnarkCollected { size_t item = 0; BtEquations sat, eval; int walk_code = OTTI_ERR_INTERNAL; bool settled = false; };
+typedef std::function<void(std::vector<SnarkCollected *> &)> SnarkChunkEnd;
+void snark_verify_staged(const CompComm &comm, const SnarkGens &g, const void *tlabel, size_t tlabel_len, const VerifyItem *items, size_t count, unsigned threads,
+                         int32_t *results, const SnarkChunkEnd *chunk_end);
+
+// ---------------------------------------------------------------------------------------------- many proofs as one randomised batch (snark_verify_batch.cpp)
+// results[i] = what snark_verify returns for item i alone, except that a proof the single verifier rejects is accepted with probability at most
+// 2^-120 over the weights (drawn from a RandomTape: seed32, or OS entropy when null).  Item checks, parsing, chunks, the four-step walk and its one
+// device pass per seam are snark_verify_many's (snark_verify_staged).  What is hashed stays per proof: the transcript, the sat rounds' combinations,
+// the four row sums, the product-circuit walk.  Every group equation that feeds nothing hashed — the sat proof's two per round, the sigma
+// equations, the four log dot-product closing equations — is stated to a collecting sink; a closing equation's n generator terms are ONE
+// product-form run (batch_terms.h), so the n scalars s never exist on the host.  After a chunk's last step every equation of every collected
+// proof gets a weight of its own and ONE sum is formed over the proofs' points and both generator handles: the identity accepts them all; otherwise
+// one localisation pass forms each proof's own sum, and only the proofs whose sum is not the identity, or whose points hold one that does not
+// decode, are run through snark_verify for their code.  A proof that fails on its walk before the evaluation proof is settled with that code;
+// one that fails inside it goes to snark_verify too, which runs the sat equations first.  The sum runs on the device through the hook below
+// (prover.cpp sets it: the runs are expanded there, k_msm.hip k_gen_runs) and on the host cores (bt_run_expand) without a device, when it
+// declines, under OTTI_VERIFY_HOST or under OTTI_VERIFY_BATCH_SUM=host (read per call: measurements, tests).  OTTI_VERIFY_BATCH_RUNS=0 (read per
+// call: measurements) collects without runs: every closing equation's n generator terms are written out on the worker, as for NIZK's batch.
+// A handle's side of a sum: a dense scalar per slot of g.P (null: none) plus product-form runs over its first slots.
+struct BatchGenSide { const Fr *base; const BtRun *const *runs; size_t nruns; };
+struct SnarkBatchSet { const uint8_t *comp32; size_t n; const Fr *scalars; BatchGenSide gen[2]; };    // one proof: n points and scalars; its own sides over g.sat, g.eval
+// localise false: sums[0] = sum over all sets + both handles under total[]; set_bad[k] = set k holds a point that does not decode.  localise true — the
+// same thread, the same sets, right after: sums[k] = set k's own sum + both handles under its gen[].  false: declined.
+typedef bool (*SnarkBatchSumHook)(const Gens *const g[2], const SnarkBatchSet *sets, size_t nsets, const BatchGenSide total[2], bool localise, Pt *sums, uint8_t *set_bad, double *ms);
+extern SnarkBatchSumHook g_snark_batch_sum_hook;
+constexpr unsigned kSnarkVerifyBatchThreads = 8;            // profiles/snark_verify_batch.md: level with four up to 4 proofs, faster from 8 on, at 2^12, 2^16 and 2^20
+void snark_verify_batch(const CompComm &comm, const SnarkGens &g, const void *tlabel, size_t tlabel_len, const VerifyItem *items, size_t count, unsigned threads,
+                        const uint8_t *seed32, int32_t *results, otti_verify_batch_info *info);
 
 // GPU (snark_encode.cpp: encode, attach; snark_prover.cpp: prove)
 struct SnarkTimings { double ms[10]; };                      // the six R1CSProof stages, [6] derefs commitment, [7] product circuits, [8] hash layer, [9] total

@@ -121,8 +121,9 @@ void hash_verify_helper(const std::vector<Fr> &rand_mem, const Evals4 &claims, c
 
 // ================================================================================================ R1CSEvalProof::verify in four steps (snark.h)
 EvalProofVerifier::EvalProofVerifier(const EvalProof &E_, const CompComm &c_, const std::vector<Fr> &rx, const std::vector<Fr> &ry, const Fr evals_[3], const SnarkGens &g_, Transcript &tr_,
-                                     int deferred_threads)
-    : E(E_), c(c_), g(g_), tr(tr_), later(deferred_threads), trace(getenv("OTTI_TRACE") != nullptr), t_lap(std::chrono::steady_clock::now()) {
+                                     int deferred_threads, BtEquations *sink)
+    : E(E_), c(c_), g(g_), tr(tr_), later(sink ? 0 : deferred_threads), trace(getenv("OTTI_TRACE") != nullptr), t_lap(std::chrono::steady_clock::now()) {
+    later.sink = sink;
     for (int k = 0; k < 3; k++) evals[k] = evals_[k];
     nm = std::max(rx.size(), ry.size());
     rxe.assign(nm - rx.size(), fr_zero()); rye.assign(nm - ry.size(), fr_zero());       // equalize: zeros in FRONT of the shorter point
@@ -141,7 +142,7 @@ RowRequest EvalProofVerifier::polyeval_begin(const DotProductProofLog &pf, const
     if (trace) fprintf(stderr, "[otti]   polyeval_verify_plain: C_Zr %.3f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_b).count());
     tr.append_protocol_name("polynomial evaluation proof");
     const size_t lv = s.num_vars / 2;
-    Lv = eq_evals_host(r.data(), lv); Rv = eq_evals_host(r.data() + lv, s.num_vars - lv);
+    Lv = eq_evals_host(r.data(), lv); Rv = eq_evals_host(r.data() + lv, s.num_vars - lv); Rpt.assign(r.begin() + lv, r.end());
     pe_pf = &pf; pe_set = &s; t_sum = std::chrono::steady_clock::now();
     return {comm.data(), comm.size(), Lv.data()};
 }
@@ -151,7 +152,7 @@ void EvalProofVerifier::polyeval_end(const RowAnswer &a) {
     CPoint C_LZ; pt_encode(C_LZ.b, a.sum);
     if (trace) fprintf(stderr, "[otti]   polyeval_verify_plain: C_Zr + eq tables + row sum %.3f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_sum).count());
     const PcSet &s = *pe_set; const PcView pv = {s.h_n, s.g1, s.h1, s.R};
-    dotproductlog_verify(*pe_pf, s.R, *g.eval, pv, tr, Rv.data(), C_LZ, C_Zr, &later);
+    dotproductlog_verify(*pe_pf, s.R, *g.eval, pv, tr, Rv.data(), C_LZ, C_Zr, &later, Rpt.data());
 }
 Fr EvalProofVerifier::joint(std::vector<Fr> ev, const char *label_evals, const char *label_ch, const char *label_joint, const std::vector<Fr> &rand, std::vector<Fr> &r_joint) {
     tr.append_scalars(label_evals, ev.data(), ev.size());

@@ -1,4 +1,5 @@
-// Many SNARK proofs of one computation commitment verified in one call (snark.h snark_verify_many).  Host code only: the batched row sums are
+// Many SNARK proofs of one computation commitment verified in one call (snark.h snark_verify_many), and the staging it shares with the randomised
+// batch (snark_verify_staged; snark_verify_batch.cpp).  Host code only: the batched row sums are
 // reached through one hook that prover.cpp sets, so the CPU rebuilds of the host sources compile this file as it is.
 #include "snark.h"
 #include <atomic>
@@ -17,6 +18,7 @@ struct Live {
     size_t item = 0; std::vector<Fr> inputs; SnarkProof S; std::vector<Fr> rx, ry;
     std::unique_ptr<Transcript> tr; std::unique_ptr<EvalProofVerifier> v;
     RowRequest req; RowAnswer ans; bool host_sum = true, alive = true;
+    SnarkCollected col;                                       // snark_verify_batch: the group equations this walk stated instead of running
 };
 // The call's own threads: `extra` of them beside the calling thread, started once and parked on a condition variable between the phases;
 // run(n, f) shares f(0 .. n) out among them and the caller and returns when all are done.  f does not throw.
@@ -54,8 +56,19 @@ size_t chunk_size() {
 
 void snark_verify_many(const CompComm &comm, const SnarkGens &g, const void *tlabel, size_t tlabel_len, const VerifyItem *items, size_t count, unsigned threads,
                        int32_t *results) {
+    snark_verify_staged(comm, g, tlabel, tlabel_len, items, count, threads, results, nullptr);
+}
+// The staging both callers share.  chunk_end == null: every proof runs its own group equations (snark_verify_many).  Otherwise (snark_verify_batch)
+// a proof states them to two collecting sinks, one per generator handle, and the proofs of a chunk that walked to the end without a failure are
+// handed to chunk_end on the calling thread, which owes their results; a proof that fails inside the evaluation proof is handed over too, marked,
+// because the single verifier would have reported a failing sat equation first.
+void snark_verify_staged(const CompComm &comm, const SnarkGens &g, const void *tlabel, size_t tlabel_len, const VerifyItem *items, size_t count, unsigned threads,
+                         int32_t *results, const SnarkChunkEnd *chunk_end) {
     if (!count) return;
     if (!threads) threads = kSnarkVerifyManyThreads;
+    const bool collect = chunk_end != nullptr;
+    const char *runs_env = collect ? getenv("OTTI_VERIFY_BATCH_RUNS") : nullptr;  // "0", read per collecting call: the closing equations' generator terms written out (measurements)
+    const bool take_runs = !(runs_env && !strcmp(runs_env, "0"));
     const size_t chunk = chunk_size(), nw = std::min<size_t>({(size_t)threads, (size_t)kVerifyManyMaxThreads, count, chunk});
     Crew crew(nw - 1);
     const bool host_only = !g_row_sums_many_hook || getenv("OTTI_VERIFY_HOST") != nullptr;
@@ -77,18 +90,26 @@ void snark_verify_many(const CompComm &comm, const SnarkGens &g, const void *tla
         }
         // ---- one step of one proof; a failure is the proof's verdict and takes it out of the later passes
         auto step = [&](Live &L, int stage) {
-            auto leave = [&](int code) { results[L.item] = code; L.alive = false; L.v.reset(); L.tr.reset(); };
+            bool in_eval = false;                             // a failure from here on came after r1cs_verify_host would have run its deferred equations
+            auto leave = [&](int code) {
+                L.alive = false; L.v.reset(); L.tr.reset();
+                if (collect && (code == OTTI_OK || in_eval)) { L.col.walk_code = code; return; }      // chunk_end settles it
+                results[L.item] = code; L.col.settled = true;
+            };
             try {
                 if (stage == 0) {                             // everything snark_verify does before the evaluation proof, then its step 0
                     L.tr = std::make_unique<Transcript>(tlabel, tlabel_len);
                     L.tr->append_protocol_name("Spartan SNARK proof");
                     snark_append_comm(*L.tr, comm);
-                    if (int rc = r1cs_verify_host(L.S.r1cs, comm.num_cons, comm.num_vars, L.inputs, L.S.inst_evals, *g.sat, *L.tr, L.rx, L.ry)) { leave(rc); return; }
+                    if (collect) { L.col.item = L.item; L.col.sat.accept_runs = L.col.eval.accept_runs = take_runs; }
+                    if (int rc = r1cs_verify_host(L.S.r1cs, comm.num_cons, comm.num_vars, L.inputs, L.S.inst_evals, *g.sat, *L.tr, L.rx, L.ry, nullptr, collect ? &L.col.sat : nullptr)) { leave(rc); return; }
+                    in_eval = true;
                     L.tr->append_scalar("Ar_claim", L.S.inst_evals[0]); L.tr->append_scalar("Br_claim", L.S.inst_evals[1]); L.tr->append_scalar("Cr_claim", L.S.inst_evals[2]);
-                    L.v = std::make_unique<EvalProofVerifier>(L.S.eval, comm, L.rx, L.ry, L.S.inst_evals, g, *L.tr, 0);
+                    L.v = std::make_unique<EvalProofVerifier>(L.S.eval, comm, L.rx, L.ry, L.S.inst_evals, g, *L.tr, 0, collect ? &L.col.eval : nullptr);
                     L.req = L.v->begin();
                     return;
                 }
+                in_eval = true;
                 if (L.host_sum) {                             // the route does not change the verdict: the same sum, or the same failure
                     L.ans = RowAnswer();
                     try { L.ans.sum = row_sum_on_host(L.req.C, L.req.n, L.req.s, false); } catch (const VerifyFail &f) { L.ans.code = f.code; }
@@ -118,6 +139,11 @@ void snark_verify_many(const CompComm &comm, const SnarkGens &g, const void *tla
             std::vector<Live *> next;
             for (Live *L : now) if (L->alive) next.push_back(L);
             now.swap(next);
+        }
+        if (collect) {
+            std::vector<SnarkCollected *> done;
+            for (auto &L : live) if (!L->col.settled) done.push_back(&L->col);
+            if (!done.empty()) (*chunk_end)(done);
         }
     }
 }

@@ -454,6 +454,14 @@ CPoint sumcheck_verify(const ZKSumcheckProof &pf, const CPoint &comm_claim, size
     }
     return pf.comm_evals[num_rounds - 1];
 }
+// <eq table of r, s> without either vector.  The table is most-significant-bit first (eq_evals_host: a[i] = prod_j (bit lg - 1 - j of i ? r_j : 1 - r_j)),
+// and bit t of i gives s[i] the squared challenge lg - 1 - t: coordinate j and challenge j meet in the same bit, so the sum over i factors into
+// allinv * prod_j ((1 - r_j) + r_j ch2_j).  ch2: the squared challenges.
+Fr dotproductlog_a_hat(const Fr *r, const Fr *ch2, size_t lg, const Fr &allinv) {
+    Fr p = allinv; const Fr one = fr_one();
+    for (size_t j = 0; j < lg; j++) p = fr_mul(p, fr_add(fr_sub(one, r[j]), fr_mul(r[j], ch2[j])));
+    return p;
+}
 // g_hat = <s, gens_n.G> is a FIXED-base sum over the first n generators of the stream: when the prover's window table of that stream is
 // already resident (prove and verify in one process, as `spzk verify` runs them), the device side registers this hook and the verifier
 // takes the sum from one small MSM launch instead of a host Pippenger over n points.  Without it (no device, no table) nothing changes.
@@ -462,7 +470,10 @@ FixedBaseMsmHook g_fixed_base_msm_hook = nullptr;
 // and the fixed-base part of the closing equation (device, when the prover's table is resident) run on the calling thread; the rest of that
 // equation — a variable-base sum over the 2 log n + 4 proof points — feeds nothing that is hashed, so with `later` it becomes one more
 // deferred check (spartan.h verifiers: SNARK mode has three of these proofs in a row).
-void dotproductlog_verify(const DotProductProofLog &pf, size_t n, const Gens &g, const PcView &v, Transcript &tr, const Fr *a, const CPoint &Cx, const CPoint &Cy, Deferred *later) {
+// a_point (may be null): a is the eq table of these lg n coordinates (eq_evals_host) — a collecting call whose sink takes product-form runs
+// (batch_terms.h accept_runs) then never forms s: the generator terms are one run, and  a_hat = <a, s>  is a product of lg n two-term factors.
+void dotproductlog_verify(const DotProductProofLog &pf, size_t n, const Gens &g, const PcView &v, Transcript &tr, const Fr *a, const CPoint &Cx, const CPoint &Cy, Deferred *later,
+                          const Fr *a_point) {
     require(v.R == n && g.P.size() >= n + 2);
     static const bool trace = getenv("OTTI_TRACE") != nullptr; auto t_lap = std::chrono::steady_clock::now();
     auto lap = [&](const char *what) { if (!trace) return; const auto t = std::chrono::steady_clock::now(); fprintf(stderr, "[otti]   dotproductlog_verify n=%zu %-22s %.3f ms\n", n, what, std::chrono::duration<double, std::milli>(t - t_lap).count()); t_lap = t; };
@@ -484,19 +495,26 @@ void dotproductlog_verify(const DotProductProofLog &pf, size_t n, const Gens &g,
         for (size_t i = lg; i-- > 0;) { chi[i] = fr_mul(suf, pre[i]); suf = fr_mul(suf, ch[i]); }
     }
     for (size_t i = 0; i < lg; i++) { ch[i] = fr_sqr(ch[i]); chi[i] = fr_sqr(chi[i]); }
-    std::vector<Fr> s(n); s[0] = allinv;
-    for (size_t i = 1; i < n; i++) { size_t lg_i = ilog2(i + 1) - 1; size_t k = (size_t)1 << lg_i; s[i] = fr_mul(s[i - k], ch[(lg - 1) - lg_i]); }
-    Fr a_hat = fr_zero(); for (size_t i = 0; i < n; i++) a_hat = fr_add(a_hat, fr_mul(a[i], s[i]));
+    const bool collect = later && later->sink, as_run = collect && later->sink->accept_runs;
+    // s[i] = allinv * prod over the set bits t of i of ch[lg - 1 - t] (squared): written out unless a run stands for it and a_hat has its closed form
+    std::vector<Fr> s; Fr a_hat;
+    if (as_run && a_point) a_hat = dotproductlog_a_hat(a_point, ch.data(), lg, allinv);
+    else {
+        s.resize(n); s[0] = allinv;
+        for (size_t i = 1; i < n; i++) { size_t lg_i = ilog2(i + 1) - 1; size_t k = (size_t)1 << lg_i; s[i] = fr_mul(s[i - k], ch[(lg - 1) - lg_i]); }
+        a_hat = fr_zero(); for (size_t i = 0; i < n; i++) a_hat = fr_add(a_hat, fr_mul(a[i], s[i]));
+    }
     // the closing equation:  c a_hat (sum ch_i L_i + sum chi_i R_i + Cx + Cy) + a_hat beta + delta - z1 sum s_i P_i - z1 a_hat G_1 - z2 h_1
-    const bool collect = later && later->sink;
     const Fr ca = fr_mul(c, a_hat), mz1 = fr_neg(pf.z1);
-    std::vector<BtTerm> e; e.reserve(2 * lg + 6 + (collect ? n : 0));
+    std::vector<BtTerm> e; e.reserve(2 * lg + 6 + (collect && !as_run ? n : 0));
     for (size_t i = 0; i < lg; i++) { e.push_back(term(fr_mul(ca, ch[i]), pf.L_vec[i])); e.push_back(term(fr_mul(ca, chi[i]), pf.R_vec[i])); }
     e.push_back(term(ca, Cx)); e.push_back(term(ca, Cy)); e.push_back(term(a_hat, pf.beta)); e.push_back(term(fr_one(), pf.delta));
     const size_t np = e.size();                                           // 2 lg + 4 point terms, then the generator terms, then G_1 and h_1
     // The generator terms  -z1 s_i P_i  are written out only for a collector.  Run, they are  -z1 g_hat  with  g_hat = sum s_i P_i  taken below:
     // n products by -z1 on this thread, which is the sequential path, measured 0.2 - 0.35 ms on a SNARK verification (three of these proofs).
-    if (collect) for (size_t i = 0; i < n; i++) e.push_back(term(fr_mul(mz1, s[i]), (uint32_t)i));
+    // A collector that takes runs gets them as ONE: coefficient -z1 allinv, factor t the squared challenge lg - 1 - t — the recurrence above, unrolled.
+    if (as_run) { std::vector<Fr> f(lg); for (size_t t = 0; t < lg; t++) f[t] = ch[(lg - 1) - t]; later->sink->run(fr_mul(mz1, allinv), f.data(), lg); }
+    else if (collect) for (size_t i = 0; i < n; i++) e.push_back(term(fr_mul(mz1, s[i]), (uint32_t)i));
     e.push_back(term(fr_mul(mz1, a_hat), v.g1)); e.push_back(term(fr_neg(pf.z2), v.h1));
     if (collect) { later->sink->equation(e); lap("challenges, s, closing terms"); return; }
     // Summed in three parts.  g_hat on this thread: a fixed-base sum, from the device when the prover's table is resident (the hook is not
@@ -569,7 +587,7 @@ int r1cs_verify_host(const NizkProof &P, size_t N, size_t V, const std::vector<F
             lap("C_LZ");
             require(P.polyeval.L_vec.size() == ilog2(Rsz));
             const PcView pv = {g.pc_n.h, g.pc_1.G[0], g.pc_1.h, Rsz};
-            dotproductlog_verify(P.polyeval, Rsz, g, pv, tr, Rv.data(), C_LZ, P.comm_vars_at_ry, &later);
+            dotproductlog_verify(P.polyeval, Rsz, g, pv, tr, Rv.data(), C_LZ, P.comm_vars_at_ry, &later, ry.data() + 1 + lv);
         }
         // SparsePolynomial over (1, inputs) evaluated at ry[1..], MSB-first index bits
         Fr poly_input_eval = fr_zero();

@@ -109,7 +109,10 @@ void knowledge_verify(const KnowledgeProof &pf, const Gens &g, Transcript &tr, c
 void equality_verify(const EqualityProof &pf, const Gens &g, Transcript &tr, const CPoint &C1, const CPoint &C2, Deferred &later);
 void product_verify(const ProductProof &pf, const Gens &g, Transcript &tr, const CPoint &X, const CPoint &Y, const CPoint &Z, Deferred &later);
 void dotproduct_verify(const DotProductProof &pf, const Gens &g, const GensView &gn, Transcript &tr, const Fr *a, size_t n, const CPoint &Cx, const CPoint &Cy, Deferred &later);
-void dotproductlog_verify(const DotProductProofLog &pf, size_t n, const Gens &g, const PcView &v, Transcript &tr, const Fr *a, const CPoint &Cx, const CPoint &Cy, Deferred *later = nullptr);
+// a_point: the lg n coordinates `a` is the eq table of, when it is one (a collector that takes runs then needs neither `a` nor the n scalars s)
+void dotproductlog_verify(const DotProductProofLog &pf, size_t n, const Gens &g, const PcView &v, Transcript &tr, const Fr *a, const CPoint &Cx, const CPoint &Cy, Deferred *later = nullptr,
+                          const Fr *a_point = nullptr);
+Fr dotproductlog_a_hat(const Fr *r, const Fr *ch2, size_t lg, const Fr &allinv);     // <eq_evals_host(r, lg), s> in closed form: ch2 the squared challenges, allinv = s[0]
 // RowSum's host path alone: decompression and Pippenger on the host cores.  wide: striped over up to 16 threads of its own (the single verifier);
 // otherwise on the calling thread alone (snark_verify_many's workers are the parallelism there).  Throws VerifyFail{OTTI_ERR_VERIFY_DECOMPRESS}.
 Pt row_sum_on_host(const CPoint *C, size_t n, const Fr *s, bool wide);
