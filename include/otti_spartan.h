@@ -587,6 +587,43 @@ int32_t otti_instance_ingest_info(const otti_instance *inst, int32_t *on_device,
  * encode / attach and a sharded upload read the lists in HBM and do not).  host_bytes: their size, 40 bytes per entry, 0 while absent.  Asking never
  * triggers the download.  Either out pointer may be NULL; a NULL inst is OTTI_ERR_BAD_ARG. */
 int32_t otti_instance_host_lists_info(const otti_instance *inst, int32_t *materialised, uint64_t *host_bytes);
+/* ---- an instance from where matrices live as arrays: rows, columns and coefficients of A, B and C, in device memory (a circuit generator's
+ * output) or host memory (a compiler's arrays: 16 to 24 bytes per entry with integer coefficients cross PCIe, against otti_entry's 48).
+ * The instance is exactly the one otti_instance_new makes from the same triples in the same order: the same padded dimensions, the same shift
+ * of columns >= num_vars by the padding, the same entries in caller order (explicit zeros and duplicates kept as otti_instance_new keeps them),
+ * the same otti_instance_device_info on both CSR copies, so every NIZK proof and every SNARK computation commitment from it is byte-identical.
+ * Coefficients come in the witness formats (OTTI_WIT_*) and become field elements by the witness rule: a negative I64 is l - |x|, INT64_MIN included.
+ * Validation runs on the device, in one pass, and reports what otti_instance_new's sequential walk over A, then B, then C meets first, within one
+ * entry the row before the column before the scalar, with otti_instance_new's code and otti_last_error wording: OTTI_ERR_INVALID_INDEX for
+ * row >= num_cons or col >= num_vars + 1 + num_inputs (a negative index of a signed format is out of range; a 64-bit index is compared in 64 bits
+ * before it is narrowed: 2^32 + 3 is never the index 3), OTTI_ERR_INVALID_SCALAR for a CANONICAL32 / MONTGOMERY32 coefficient whose raw value is
+ * >= l (the integer formats cannot fail it).  Then no instance is returned, *out is untouched, everything allocated is released and the context
+ * stays usable.
+ * Argument errors are reported before any device is touched: OTTI_ERR_BAD_ARG for a null mats or out, a null array with a non-zero n, an
+ * unknown index or coefficient format, a non-zero val_stride_bytes below the element size or not a multiple of 8, an array (device or host:
+ * host arrays are staged as they are) not aligned to its element — 4 or 8 bytes for indices, 8 for every coefficient format —, n >= 2^32, and
+ * padded dimensions above 2^30; then OTTI_ERR_NO_DEVICE.
+ * src_on_device = 1: the arrays are in HBM; stream as for otti_witness_from_device (the ingest is ordered behind an event recorded on it; NULL
+ * names no stream to wait for).  src_on_device = 0: host memory, copied to HBM as it is; the same kernel reads it there.
+ * Returns after the ingest has finished: the sources are free again.
+ * The result is a device-ingested instance (see otti_instance_from_zkif, OTTI_INGEST_DEVICE): its device copy is made, its entry lists stay in
+ * HBM, and the host lists are downloaded by the first host consumer (otti_instance_host_lists_info: materialised = 0 until then).
+ * otti_instance_ingest_info reports on_device = 1, the source bytes read (two indices and one coefficient per entry) as circuit_bytes and the
+ * laps ms[0] = 0, ms[1] = staging, ms[2] = kernel, ms[3] = CSR build. */
+enum { OTTI_IDX_U32 = 0, OTTI_IDX_I32 = 1, OTTI_IDX_U64 = 2, OTTI_IDX_I64 = 3 };
+typedef struct {
+    const void *row, *col;       /* n indices each, packed, in index_format */
+    const void *val;             /* n coefficients in val_format (OTTI_WIT_*), val_stride_bytes apart (0 = packed) */
+    size_t n; int32_t index_format, val_format; size_t val_stride_bytes;
+} otti_coo;
+int32_t otti_instance_from_coo(uint64_t num_cons, uint64_t num_vars, uint64_t num_inputs, const otti_coo mats[3] /* A, B, C */,
+                               int32_t src_on_device, void *stream, otti_instance **out);
+/* the entry lists a device-ingested instance keeps in HBM, matrix `which` (0 A, 1 B, 2 C): n stored rows (u32), n padded columns (u32: a column
+ * >= num_vars moved up by the padding) and n Montgomery values (32 bytes each, usable with otti_kd_*), in caller order.  An instance that keeps
+ * no lists (otti_instance_new, the host ingest), and an empty matrix, answer n = 0 with NULL pointers.  The pointers are valid for the life of
+ * the instance.  Any out pointer may be NULL; a NULL inst or another `which` is OTTI_ERR_BAD_ARG.  Touches no device. */
+int32_t otti_instance_device_entries(const otti_instance *inst, int32_t which, const void **d_row, const void **d_col,
+                                     const void **d_val, size_t *n);
 /* .inp.zkif + .wit.zkif to a resident witness of `inst`, equal in every observable way (z, inputs, small_fraction, proof bytes) to otti_zkif_load on
  * the instance's three files followed by otti_witness_upload.  It works with every consumer and mutator of a resident witness.
  *   OTTI_INGEST_HOST:   the host loader's frame over the two files (the circuit's share left out), then the upload path.

@@ -189,6 +189,13 @@ _sig("otti_instance_from_zkif", _i32, ctypes.c_char_p, ctypes.c_char_p, ctypes.c
 _sig("otti_instance_entries", _i32, _vp, _i32, _vp, _sz, ctypes.POINTER(_sz))
 _sig("otti_instance_ingest_info", _i32, _vp, ctypes.POINTER(_i32), ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(ctypes.c_double))
 _sig("otti_instance_host_lists_info", _i32, _vp, ctypes.POINTER(_i32), ctypes.POINTER(_u64))
+class _Coo(ctypes.Structure):                                  # otti_coo
+    _fields_ = [("row", _vp), ("col", _vp), ("val", _vp), ("n", _sz), ("index_format", _i32), ("val_format", _i32), ("val_stride_bytes", _sz)]
+
+
+IDX_U32, IDX_I32, IDX_U64, IDX_I64 = 0, 1, 2, 3                # OTTI_IDX_*
+_sig("otti_instance_from_coo", _i32, _u64, _u64, _u64, ctypes.POINTER(_Coo), _i32, _vp, ctypes.POINTER(_vp))
+_sig("otti_instance_device_entries", _i32, _vp, _i32, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_sz))
 _sig("otti_k_decomm_entries", _i32, _vp, _vp, _vp, _sz, _sz, _sz, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _fp)
 _sig("otti_k_shard_filter", _i32, _vp, _vp, _vp, _sz, ctypes.c_uint32, ctypes.c_uint32, _i32, _vp, _vp, _vp, ctypes.POINTER(_sz), _fp)
 INGEST_MODES = {"auto": 0, "host": 1, "device": 2}             # OTTI_INGEST_*
@@ -366,6 +373,39 @@ class Instance:
         assignment = _r1cs_to_py(rp)
         assignment.update(A=None, B=None, C=None, **counts)
         return cls(h, None), assignment
+
+    @classmethod
+    def from_coo(cls, num_cons, num_vars, num_inputs, A, B, C, stream=None, montgomery=False):
+        """otti_instance_from_coo: the instance Instance.new makes from the same triples, from three arrays per matrix.  A, B, C: (rows, cols, vals)
+        of numpy arrays or torch tensors.  rows / cols: int32, int64 (numpy also uint32, uint64), one dtype per matrix, made contiguous.  vals:
+        int64 (negative: l - |x|) or uint64 numbers, or a uint8 array of shape (n, 32) of canonical scalars (``montgomery=True``: of Montgomery
+        words); its stride along dimension 0 is passed on, so a strided view is read where it is.  Either all nine arrays live on the GPU or none
+        does.  For GPU tensors ``stream`` defaults to torch's current stream (Witness.from_tensor's rule); torch has to be imported before
+        otti_amd.  Validation runs on the device and raises what Instance.new raises for the same triples.  Nothing is kept
+        alive once the call has returned."""
+        mats = [tuple(m) for m in (A, B, C)]
+        if any(len(m) != 3 for m in mats):
+            raise ValueError("each matrix is (rows, cols, vals)")
+        flat = [a for m in mats for a in m]
+        torch = sys.modules.get("torch")
+        on_gpu = [torch is not None and isinstance(a, torch.Tensor) and a.is_cuda for a in flat]
+        if any(on_gpu) and not all(on_gpu):
+            raise SpartanError(-21, "from_coo: either all nine arrays live on the GPU or none does")
+        if all(on_gpu):
+            coo, keep, producer = _coo_device(torch, mats, stream, montgomery)
+        else:
+            coo, keep, producer = _coo_host(torch, mats, montgomery), mats, None   # (mats: the contiguous forms the pointers go into)
+        h = _vp()
+        _check(lib.otti_instance_from_coo(num_cons, num_vars, num_inputs, coo, 1 if all(on_gpu) else 0, producer, ctypes.byref(h)))
+        del keep
+        return cls(h, None)
+
+    def device_entries(self, which):
+        """otti_instance_device_entries: (ptr_row, ptr_col, ptr_val, n) of the entry lists a device-ingested instance keeps in HBM — u32 rows, u32
+        padded columns, Montgomery values, caller order; (0, 0, 0, 0) for an instance that keeps none.  Valid while the instance lives."""
+        r, c, v, n = _vp(), _vp(), _vp(), _sz()
+        _check(lib.otti_instance_device_entries(self._h, which, ctypes.byref(r), ctypes.byref(c), ctypes.byref(v), ctypes.byref(n)))
+        return r.value or 0, c.value or 0, v.value or 0, n.value
 
     def entries(self, which):
         """otti_instance_entries: the entries of A (0), B (1) or C (2) as the caller's — unpadded columns, canonical values, caller / file order"""
@@ -568,6 +608,69 @@ def _torch_stream(torch, t, stream):
         cur.synchronize()
         return None
     return cur.cuda_stream
+
+
+_NP_INDEX = {np.dtype(np.uint32): IDX_U32, np.dtype(np.int32): IDX_I32, np.dtype(np.uint64): IDX_U64, np.dtype(np.int64): IDX_I64}
+
+
+def _coo_val_format(is_int64, is_uint64, is_bytes32, montgomery):
+    if is_int64 or is_uint64:
+        if montgomery:
+            raise ValueError("montgomery=True goes with (n, 32) uint8 coefficients")
+        return WIT_I64 if is_int64 else WIT_U64
+    if is_bytes32:
+        return WIT_MONTGOMERY32 if montgomery else WIT_CANONICAL32
+    raise ValueError("coefficients: expected 1-D int64 / uint64 or uint8 of shape (n, 32)")
+
+
+def _coo_host(torch, mats, montgomery):
+    """Instance.from_coo's otti_coo[3] over host arrays (numpy, or torch tensors on the CPU, whose memory numpy views)"""
+    coo = (_Coo * 3)()
+    for k, m in enumerate(mats):
+        rows, cols, vals = (a.numpy() if torch is not None and isinstance(a, torch.Tensor) else np.asarray(a) for a in m)
+        if rows.dtype != cols.dtype or rows.dtype not in _NP_INDEX or rows.ndim != 1 or cols.ndim != 1:
+            raise ValueError("rows and cols: two 1-D arrays of one dtype among int32, int64, uint32, uint64")
+        rows, cols = np.ascontiguousarray(rows), np.ascontiguousarray(cols)
+        fmt = _coo_val_format(vals.dtype == np.int64 and vals.ndim == 1, vals.dtype == np.uint64 and vals.ndim == 1,
+                              vals.dtype == np.uint8 and vals.ndim == 2 and vals.shape[1] == 32, montgomery)
+        n = vals.shape[0]
+        if rows.shape[0] != n or cols.shape[0] != n:
+            raise ValueError("rows, cols and vals of one matrix have one length")
+        eb = 8 if fmt in (WIT_I64, WIT_U64) else 32
+        if n > 1 and (vals.strides[0] < eb or (vals.ndim == 2 and vals.strides[1] != 1)):
+            vals = np.ascontiguousarray(vals)                 # (a reversed or overlapping view; an odd stride is the library's to refuse)
+        coo[k] = _Coo(_ptr(rows), _ptr(cols), _ptr(vals), n, _NP_INDEX[rows.dtype], fmt, vals.strides[0] if n > 1 else 0)
+        mats[k] = (rows, cols, vals)                           # alive until the call has returned
+    return coo
+
+
+def _coo_device(torch, mats, stream, montgomery):
+    """Instance.from_coo's otti_coo[3] over GPU tensors, the tensors it points into and the stream to order the ingest after"""
+    index = {torch.int32: IDX_I32, torch.int64: IDX_I64}
+    for name, fmt in (("uint32", IDX_U32), ("uint64", IDX_U64)):
+        if hasattr(torch, name):
+            index[getattr(torch, name)] = fmt
+    coo, keep, copied = (_Coo * 3)(), [], False
+    for k, (rows, cols, vals) in enumerate(mats):
+        if rows.dtype != cols.dtype or rows.dtype not in index or rows.dim() != 1 or cols.dim() != 1:
+            raise ValueError("rows and cols: two 1-D tensors of one dtype among int32, int64")
+        fmt = _coo_val_format(vals.dtype == torch.int64 and vals.dim() == 1, getattr(torch, "uint64", None) == vals.dtype and vals.dim() == 1,
+                              vals.dtype == torch.uint8 and vals.dim() == 2 and vals.shape[1] == 32, montgomery)
+        n = vals.shape[0]
+        if rows.shape[0] != n or cols.shape[0] != n:
+            raise ValueError("rows, cols and vals of one matrix have one length")
+        eb = 8 if fmt in (WIT_I64, WIT_U64) else 32
+        fixed = [rows.contiguous(), cols.contiguous(), vals]
+        if n > 1 and (vals.stride(0) * vals.element_size() < eb or (vals.dim() == 2 and vals.stride(1) != 1)):
+            fixed[2] = vals.contiguous()
+        copied = copied or any(a is not b for a, b in zip(fixed, (rows, cols, vals)))
+        rows, cols, vals = fixed
+        keep.append(fixed)
+        p = lambda t: t.data_ptr() if t.numel() else None
+        coo[k] = _Coo(p(rows), p(cols), p(vals), n, index[rows.dtype], fmt, vals.stride(0) * vals.element_size() if n > 1 else 0)
+    if copied:                                                 # a contiguous copy was queued on torch's current stream, whichever stream the caller names
+        torch.cuda.current_stream(mats[0][2].device).synchronize()
+    return coo, keep, _torch_stream(torch, mats[0][2], stream)
 
 
 class Witness:

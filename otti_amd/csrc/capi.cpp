@@ -8,6 +8,7 @@ void zkif_write_impl(const otti_r1cs *r, const char *circuit_path, const char *i
 otti_r1cs *zkif_load_inputs_impl(const char *inputs_path);
 namespace otti { otti_r1cs *instance_from_zkif_device(const char *circuit_path, const char *inputs_path, const char *witness_path, std::unique_ptr<Instance> &inst); }   // k_ingest.hip
 #include "zkif.h"
+#include "coo_walk.h"
 #include <sys/stat.h>
 #include <unistd.h>
 // otti_instance_from_zkif(OTTI_INGEST_AUTO): the circuit sizes between which the device path is taken (OTTI_INGEST_MIN_MB, OTTI_INGEST_GB override them
@@ -724,6 +725,43 @@ int32_t otti_instance_host_lists_info(const otti_instance *inst, int32_t *materi
             *host_bytes = 0;
             if (have) for (int k = 0; k < 3; k++) *host_bytes += (uint64_t)I.M[k].val.size() * 40;
         }
+        return OTTI_OK;
+    });
+}
+// ---- row / column / coefficient arrays to a ready instance (device.h instance_from_coo, k_coo_ingest.hip).  Everything the arguments alone say is
+// said before a device is asked for, in the witness section's terms (check_wit_source); *out is written last.
+int32_t otti_instance_from_coo(uint64_t num_cons, uint64_t num_vars, uint64_t num_inputs, const otti_coo mats[3], int32_t src_on_device, void *stream,
+                               otti_instance **out) {
+    return guarded([&] {
+        if (!mats || !out) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        CooSource src[3];
+        for (int k = 0; k < 3; k++) {
+            const otti_coo &m = mats[k];
+            if (m.index_format < OTTI_IDX_U32 || m.index_format > OTTI_IDX_I64) throw Error(OTTI_ERR_BAD_ARG, "unknown index format");
+            // (a host source is staged as it is, so it has to sit on its element's grid as a device source has to)
+            check_wit_source(m.val, m.n, m.val_format, m.val_stride_bytes, true);
+            if ((!m.row || !m.col) && m.n) throw Error(OTTI_ERR_BAD_ARG, "null index array with a non-zero count");
+            const size_t ib = coo_index_bytes(m.index_format);
+            if (((uintptr_t)m.row | (uintptr_t)m.col) & (ib - 1)) throw Error(OTTI_ERR_BAD_ARG, "an index array must be aligned to its element");
+            if ((uint64_t)m.n >= kCooMaxEntries) throw Error(OTTI_ERR_BAD_ARG, "a matrix with 2^32 entries or more");
+            src[k] = CooSource{m.row, m.col, m.val, m.n, m.index_format, m.val_format, m.val_stride_bytes ? m.val_stride_bytes : wit_elem_bytes(m.val_format)};
+        }
+        // instance_new's limit on the padded dimensions, which are powers of two: said on the given ones
+        if (num_cons > ((uint64_t)1 << 30) || num_vars > ((uint64_t)1 << 30) || num_inputs >= ((uint64_t)1 << 30))
+            throw Error(OTTI_ERR_BAD_ARG, "instance too large for 32-bit indices");
+        if (otti_device_count() < 1) throw Error(OTTI_ERR_NO_DEVICE, "no device: the arrays are ingested on one");
+        return adopt(out, instance_from_coo(num_cons, num_vars, num_inputs, src, src_on_device != 0, (hipStream_t)stream));
+    });
+}
+int32_t otti_instance_device_entries(const otti_instance *inst, int32_t which, const void **d_row, const void **d_col, const void **d_val, size_t *n) {
+    return guarded([&] {
+        if (!inst || which < 0 || which > 2) throw Error(OTTI_ERR_BAD_ARG, "null argument, or a matrix other than 0 (A), 1 (B), 2 (C)");
+        const std::shared_ptr<DeviceInstance> d = inst->I->dev;
+        const DeviceCoo *e = d && d->ent[which].n ? &d->ent[which] : nullptr;
+        if (d_row) *d_row = e ? e->row.p : nullptr;
+        if (d_col) *d_col = e ? e->col.p : nullptr;
+        if (d_val) *d_val = e ? e->val.p : nullptr;
+        if (n) *n = e ? e->n : 0;
         return OTTI_OK;
     });
 }

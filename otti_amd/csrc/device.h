@@ -57,7 +57,22 @@ struct DeviceInstance { DeviceCsrSet by_row, by_col; size_t nnz = 0; DeviceCoo e
 struct DevCtx;
 bool classify_coefficients(DevCtx &c, DeviceCoo coo[3]);
 void build_csr_set(DevCtx &c, DeviceCsrSet &d, const DeviceCoo coo[3], bool by_col, size_t rows, bool use_small);
-bool device_runtime_up();                                   // a device context exists in this process already (k_context.hip): asking never brings one up
+// The tail of every device ingest (k_ingest.hip: zkInterface bytes; k_coo_ingest.hip: row / column / coefficient arrays), behind a clean pass that
+// left the validated lists in d->ent in caller order: the size check, classify_coefficients, both CSR copies, the codes released, and I's fields —
+// dimensions, counts, host_lists_pending, ingested_on_device, source_bytes as circuit_bytes, lap 3 (from t0, a reading of ingest_now, to the end
+// of the CSR build) and the device copy itself.
+struct IngestDims { size_t ncp, nvp, num_inputs, given_cons, given_vars; };
+double ingest_now();                                        // ms on the steady clock
+void finish_device_ingest(DevCtx &c, Instance &I, const std::shared_ptr<DeviceInstance> &d, const IngestDims &dims, uint64_t source_bytes, double t0);
+// A, B or C as three arrays (= otti_coo of the C ABI): n indices each in row and col (CooIdxFormat, coo_walk.h), n coefficients in val (WitFormat),
+// val_stride bytes apart (never 0 here)
+struct CooSource { const void *row, *col, *val; size_t n; int index_format, val_format; size_t val_stride; };
+// otti_instance_from_coo behind its argument checks (k_coo_ingest.hip): the arrays, in HBM (then ordered behind `producer`'s queued work, nullptr:
+// none to wait for) or on the host (then staged as they are), to the instance instance_new makes from the same triples.  The first defect in
+// instance_new's order is thrown with its code and wording; everything allocated is released and the context stays usable.  Returns when the
+// sources are free again.
+std::unique_ptr<Instance> instance_from_coo(size_t num_cons, size_t num_vars, size_t num_inputs, const CooSource mats[3], bool src_on_device, hipStream_t producer);
+bool device_runtime_up();                                  // a device context exists in this process already (k_context.hip): asking never brings one up
 // Rank k of g holds the constraint rows r = k (mod g) (renumbered r / g, columns untouched: multiply_vec output lands where the
 // low-bit-sharded phase-one tables need it) and, as a second copy, the entries of columns c = k (mod g) (renumbered c / g, rows
 // untouched: compute_eval_table_sparse output lands where the phase-two tables need it).  SURVEY.md 8(e).

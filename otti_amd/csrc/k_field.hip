@@ -30,25 +30,8 @@ void dev_fetch(DevCtx &c, const Fr *src, int slot, size_t n) { OTTI_HIP(hipMemcp
 // all 32 bytes of its own element before it stores them).  Integers are loaded as one 8-byte word and widened; the 32-byte formats as two
 // 16-byte loads when base and stride allow it (wide), else as four 8-byte ones.
 // counts[0]: non-canonical scalars (upstream: R1CSError::InvalidScalar); counts[1]: scalars below 2^128 (their share picks the commitment's MSM variant)
-typedef uint32_t wit_u32x4 __attribute__((ext_vector_type(4)));
-template <int F> __device__ __forceinline__ Fr wit_load(const unsigned char *p, bool wide, bool &neg) {
-    Fr raw; neg = false;
-    if constexpr (F == WIT_I64 || F == WIT_U64) {
-        unsigned long long x = *reinterpret_cast<const unsigned long long *>(p);
-        if (F == WIT_I64 && (long long)x < 0) { neg = true; x = 0ull - x; }      // |INT64_MIN| = 2^63 comes out of the wrap-around as it should
-        raw = fr_zero(); raw.v[0] = (uint32_t)x; raw.v[1] = (uint32_t)(x >> 32);
-    } else if (wide) {
-        const wit_u32x4 lo = *reinterpret_cast<const wit_u32x4 *>(p), hi = *reinterpret_cast<const wit_u32x4 *>(p + 16);
-        for (int k = 0; k < 4; k++) { raw.v[k] = lo[k]; raw.v[4 + k] = hi[k]; }
-    } else {
-        for (int k = 0; k < 4; k++) {
-            const unsigned long long w = *reinterpret_cast<const unsigned long long *>(p + 8 * k);
-            raw.v[2 * k] = (uint32_t)w; raw.v[2 * k + 1] = (uint32_t)(w >> 32);
-        }
-    }
-    return raw;
-}
-// (the conversion rule wit_convert<F> and the tally wit_tally: kernels_common.h — k_wit_ingest.hip applies the same rule to the elements of a .wit.zkif)
+// (the load wit_load<F>, the conversion rule wit_convert<F> and the tally wit_tally: kernels_common.h — k_wit_ingest.hip applies the same rule to the
+// elements of a .wit.zkif, k_coo_ingest.hip load and rule to the coefficients of a matrix)
 template <int F> __global__ __launch_bounds__(kBlock) void k_witness_ingest_from(const unsigned char *src, size_t stride, size_t n, Fr *z, size_t dst_off,
                                                                                unsigned long long *counts) {
     unsigned bad = 0, nsmall = 0;

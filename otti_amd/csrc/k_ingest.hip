@@ -125,7 +125,7 @@ void ingest_stage_image(DevCtx &c, uint8_t *d_image, size_t image_bytes, const s
     OTTI_HIP(se);
 }
 
-static double ingest_now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+double ingest_now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // Instance::mat() of an instance made here: the entry lists the device copy keeps, as instance_new would have left them on the host
 // (the caller hands over local lists and takes them only when all of this has succeeded)
@@ -208,19 +208,24 @@ static bool ingest_constraints(const ZkifCircuit &zc, Instance &I, double ms[4])
     t1 = ingest_now(); ms[2] = t1 - t0; t0 = t1;
     if (err != kZwNoError && !(err >> 63)) refuse(err);
     if (err != kZwNoError) return true;                       // a coefficient >= l and no parse error: the caller's, behind the frame
-    if (nvp > ((size_t)1 << 30)) throw Error(OTTI_ERR_BAD_ARG, "instance too large for 32-bit indices");
     d_image.release(); d_cnt.release(); d_col_of.release(); d_msgs.release();
-    const bool use_small = classify_coefficients(c, coo);
-    build_csr_set(c, d->by_row, coo, false, ncp, use_small);
-    build_csr_set(c, d->by_col, coo, true, 2 * nvp, use_small);
-    for (int k = 0; k < 3; k++) coo[k].code.release();        // the codes have gone into the CSR copies; row, col, val stay (device.h DeviceInstance::ent)
-    d->nnz = (size_t)totals[0] + totals[1] + totals[2];
-    ms[3] = ingest_now() - t0;
-    I.num_cons = ncp; I.num_vars = nvp; I.num_inputs = zc.num_inputs; I.given_cons = rows; I.given_vars = zc.num_vars;
-    for (int k = 0; k < 3; k++) I.nnz[k] = totals[k];
-    I.host_lists_pending = true; I.ingested_on_device = true; I.circuit_bytes = zc.file_bytes;
-    I.dev = d;
+    finish_device_ingest(c, I, d, IngestDims{ncp, nvp, zc.num_inputs, rows, zc.num_vars}, zc.file_bytes, t0);
     return false;
+}
+// the tail of every device ingest (device.h): the lists of d->ent, validated and in caller order, to a ready instance
+void finish_device_ingest(DevCtx &c, Instance &I, const std::shared_ptr<DeviceInstance> &d, const IngestDims &dims, uint64_t source_bytes, double t0) {
+    if (dims.nvp > ((size_t)1 << 30)) throw Error(OTTI_ERR_BAD_ARG, "instance too large for 32-bit indices");
+    DeviceCoo *coo = d->ent;
+    const bool use_small = classify_coefficients(c, coo);
+    build_csr_set(c, d->by_row, coo, false, dims.ncp, use_small);
+    build_csr_set(c, d->by_col, coo, true, 2 * dims.nvp, use_small);
+    for (int k = 0; k < 3; k++) coo[k].code.release();        // the codes have gone into the CSR copies; row, col, val stay (device.h DeviceInstance::ent)
+    d->nnz = coo[0].n + coo[1].n + coo[2].n;
+    I.ingest_ms[3] = ingest_now() - t0;
+    I.num_cons = dims.ncp; I.num_vars = dims.nvp; I.num_inputs = dims.num_inputs; I.given_cons = dims.given_cons; I.given_vars = dims.given_vars;
+    for (int k = 0; k < 3; k++) I.nnz[k] = coo[k].n;
+    I.host_lists_pending = true; I.ingested_on_device = true; I.circuit_bytes = source_bytes;
+    I.dev = d;
 }
 static const bool g_host_lists_hook_set = (g_instance_host_lists_hook = host_lists_from_device, true);   // (the pointer itself is constant-initialised: no order to mind)
 

@@ -35,7 +35,27 @@ template <class Launch> static inline Tallies counted_launch(DevCtx &c, Launch l
 }
 
 // ------------------------------------------------------------------------------------------------ witness elements
-// (WitFormat: device.h; the loads of k_field.hip's wit_load<F>, or of the zkInterface reader of k_wit_ingest.hip, hand their word to this one rule)
+// (WitFormat: device.h; the loads of wit_load<F>, or of the zkInterface reader of k_wit_ingest.hip, hand their word to this one rule)
+// The load: an element of format F at p.  Integers are one 8-byte word, widened; the 32-byte formats two 16-byte loads when base and stride allow
+// it (wide), else four 8-byte ones.
+typedef uint32_t wit_u32x4 __attribute__((ext_vector_type(4)));
+template <int F> __device__ __forceinline__ Fr wit_load(const unsigned char *p, bool wide, bool &neg) {
+    Fr raw; neg = false;
+    if constexpr (F == WIT_I64 || F == WIT_U64) {
+        unsigned long long x = *reinterpret_cast<const unsigned long long *>(p);
+        if (F == WIT_I64 && (long long)x < 0) { neg = true; x = 0ull - x; }      // |INT64_MIN| = 2^63 comes out of the wrap-around as it should
+        raw = fr_zero(); raw.v[0] = (uint32_t)x; raw.v[1] = (uint32_t)(x >> 32);
+    } else if (wide) {
+        const wit_u32x4 lo = *reinterpret_cast<const wit_u32x4 *>(p), hi = *reinterpret_cast<const wit_u32x4 *>(p + 16);
+        for (int k = 0; k < 4; k++) { raw.v[k] = lo[k]; raw.v[4 + k] = hi[k]; }
+    } else {
+        for (int k = 0; k < 4; k++) {
+            const unsigned long long w = *reinterpret_cast<const unsigned long long *>(p + 8 * k);
+            raw.v[2 * k] = (uint32_t)w; raw.v[2 * k + 1] = (uint32_t)(w >> 32);
+        }
+    }
+    return raw;
+}
 // THE conversion rule, for every kernel that takes witness elements in: the word wit_load<F> returned -> the Montgomery element.  An integer is
 // always a scalar; a negative one is l - |x| and so never small.  A 32-byte word >= l is refused: stored as zero, and counted as small as well.
 // small: the canonical value is below 2^128 (MONTGOMERY32: judged on fr_to_raw of the word).
