@@ -13,6 +13,15 @@ pub struct OttiEntry {
     pub col: u64,
     pub val: [u8; 32],
 }
+/// new coefficients of one matrix for otti_instance_set_values (otti_coo_values): n elements in val_format (OTTI_WIT_*), val_stride_bytes apart (0: packed)
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct OttiCooValues {
+    pub val: *const c_void,
+    pub n: usize,
+    pub val_format: i32,
+    pub val_stride_bytes: usize,
+}
 pub enum OttiInstance {}
 pub enum OttiGens {}
 pub enum OttiSnarkGens {}
@@ -84,6 +93,11 @@ extern "C" {
     fn otti_comp_comm_from_bytes(buf: *const u8, len: usize, out: *mut *mut OttiCompComm) -> i32;
     fn otti_comp_comm_free(comm: *mut OttiCompComm);
     fn otti_comp_comm_attach(comm: *mut OttiCompComm, inst: *mut OttiInstance, gens: *mut OttiSnarkGens, flags: u32) -> i32;
+    // new coefficients for a live instance in place (vals: 3 x OttiCooValues, A, B, C; val null with n 0: the matrix stays), its generation and
+    // slot maps, and a computation commitment with its decommitment brought to the instance's current coefficients
+    fn otti_instance_set_values(inst: *mut OttiInstance, vals: *const OttiCooValues, src_on_device: i32, stream: *mut c_void) -> i32;
+    fn otti_instance_values_info(inst: *const OttiInstance, generation: *mut u64, slots_resident: *mut i32, slot_bytes: *mut u64, ms: *mut f64) -> i32;
+    fn otti_comp_comm_revalue(comm: *mut OttiCompComm, inst: *mut OttiInstance, gens: *mut OttiSnarkGens) -> i32;
     fn otti_comp_comm_dims(comm: *const OttiCompComm, num_cons: *mut u64, num_vars: *mut u64, num_inputs: *mut u64, num_ops: *mut u64, has_decommitment: *mut i32) -> i32;
     fn otti_snark_prove(inst: *mut OttiInstance, comm: *mut OttiCompComm, vars32: *const u8, nvars: usize, inputs32: *const u8, ninputs: usize,
                         gens: *mut OttiSnarkGens, tlabel: *const u8, tlabel_len: usize, seed32: *const u8, flags: u32, proof: *mut *mut u8,

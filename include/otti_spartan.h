@@ -624,6 +624,50 @@ int32_t otti_instance_from_coo(uint64_t num_cons, uint64_t num_vars, uint64_t nu
  * the instance.  Any out pointer may be NULL; a NULL inst or another `which` is OTTI_ERR_BAD_ARG.  Touches no device. */
 int32_t otti_instance_device_entries(const otti_instance *inst, int32_t which, const void **d_row, const void **d_col,
                                      const void **d_val, size_t *n);
+/* ---- new coefficients for a live instance, in place: the structure (rows, columns, counts, padded dimensions) stays and every entry of the
+ * matrices named gets a new coefficient.  For a caller that emits the same structure with new coefficients per dataset.
+ * vals[k] (k = 0 A, 1 B, 2 C): val == NULL (then n must be 0) leaves matrix k as it is.  Otherwise n must equal the matrix's entry count
+ * (OTTI_ERR_BAD_ARG), and element i replaces the coefficient of entry i in the order the instance was given its entries (otti_instance_entries
+ * order).  Formats (OTTI_WIT_*, a negative I64 is l - |x|), strides, alignment rules, src_on_device, the stream wait and "returns when the
+ * sources are free again" are exactly those of otti_instance_from_coo.
+ * Errors: a refused coefficient (a CANONICAL32 / MONTGOMERY32 value >= l) is reported as otti_instance_new would report it on the new triples:
+ * the first defect walking A, then B, then C, OTTI_ERR_INVALID_SCALAR with its wording.  Argument errors (a null inst or vals, a null val with a
+ * non-zero n, an unknown format, a bad stride or alignment, a wrong n) come before OTTI_ERR_NO_DEVICE, which is reported when the call needs a
+ * device — the instance keeps its lists in HBM, or src_on_device = 1 — and there is none.  ALL OR NOTHING: after any error the instance is bit
+ * for bit what it was (everything is converted and validated into staging first, then placed).
+ * On success the instance is the one otti_instance_from_coo or otti_instance_new would make from the old rows and columns with the new
+ * coefficients: entries, proofs, the verifiers' evaluate and SNARK commitments are identical, and the sparse-kernel variant is decided again by
+ * the same rule, so otti_instance_device_info equals the fresh instance's in both directions of a codes / no-codes flip.
+ * An instance that keeps its entry lists in HBM (otti_instance_from_coo, otti_instance_from_zkif with OTTI_INGEST_DEVICE) is revalued there by two
+ * streaming kernels.  Its first call also builds the slot maps (where each entry sits in the by-row and the by-column copy: 8 bytes per entry,
+ * kept for the life of the instance; an instance that is never revalued pays nothing); later calls only convert and place.  The convert pass's
+ * list of small-integer codes (4 bytes per entry of every matrix ever replaced) is kept with the instance likewise, so a later call allocates
+ * nothing but the new value list.  The d_val pointer of
+ * otti_instance_device_entries changes with every successful call (the staging list becomes the list).  Host lists that were never downloaded
+ * stay so (otti_instance_host_lists_info); downloaded ones are refreshed inside the call.
+ * Any other instance (otti_instance_new, the host ingest) takes the plain route: converted on the host, the device copy dropped and rebuilt
+ * lazily, as after otti_instance_new.  Slow and correct; with host sources it needs no device.
+ * Every instance carries a coefficient GENERATION: 0 at creation, +1 per successful call.  State derived from the coefficients follows it:
+ *  - a witness's kept products (otti_witness_keep_products) made at another generation are stale: proofs form their own, mutators do not patch
+ *    them, otti_witness_products_info says kept = 0, otti_witness_check_sat runs its pass, and otti_witness_keep_products recomputes.  Kept rows
+ *    do not depend on the instance and stay.
+ *  - a computation commitment records the generation its decommitment was last built (encode, attach) or revalued from; otti_snark_prove* refuses
+ *    a commitment whose recorded generation differs from the instance's, with OTTI_ERR_BAD_ARG, before any device work.
+ *  - the sharded copy is dropped and rebuilt by the next sharded proof.
+ * The caller's rule: no other call on this instance may be in flight, and proofs made before the call remain proofs about the old instance. */
+typedef struct { const void *val; size_t n; int32_t val_format; size_t val_stride_bytes; } otti_coo_values;
+int32_t otti_instance_set_values(otti_instance *inst, const otti_coo_values vals[3] /* A, B, C */, int32_t src_on_device, void *stream);
+/* the generation, whether the slot maps exist and their size (8 bytes per entry, 0 while absent), and the last successful call's laps:
+ * ms[0] staging, ms[1] convert + validate, ms[2] place (the plain route: everything in ms[1]).  Any out pointer may be NULL.  Touches no device. */
+int32_t otti_instance_values_info(const otti_instance *inst, uint64_t *generation, int32_t *slots_resident, uint64_t *slot_bytes,
+                                  double ms[3] /* staging, convert+validate, place */);
+/* A computation commitment WITH its decommitment (from otti_snark_encode, or completed by otti_comp_comm_attach) brought to the instance's current
+ * coefficients without encoding again.  Of the 16 N + 2 M committed elements only the 3 N values of A, B, C depend on the coefficients: they are
+ * written again (from the lists in HBM when the instance keeps them, else from the host lists) and only the rows of comm_ops that meet them are
+ * summed again; addresses, timestamps and comm_mem are untouched.  Afterwards otti_comp_comm_bytes equals a fresh otti_snark_encode of the
+ * revalued instance and otti_snark_prove* accepts the pair.  OTTI_ERR_BAD_ARG: a null argument, a commitment without decommitment, and the
+ * dimensions and generators otti_comp_comm_attach checks — all before the device is touched. */
+int32_t otti_comp_comm_revalue(otti_comp_comm *comm, otti_instance *inst, otti_snark_gens *gens);
 /* .inp.zkif + .wit.zkif to a resident witness of `inst`, equal in every observable way (z, inputs, small_fraction, proof bytes) to otti_zkif_load on
  * the instance's three files followed by otti_witness_upload.  It works with every consumer and mutator of a resident witness.
  *   OTTI_INGEST_HOST:   the host loader's frame over the two files (the circuit's share left out), then the upload path.
@@ -740,6 +784,10 @@ int32_t otti_k_instance_evaluate(otti_instance *inst, const uint8_t *rx32, const
    instance as those entries do, if it is not there yet, and launches nothing else. */
 typedef struct { uint64_t rows, entries[3], n_heavy, n_seg; int32_t use_small, quad; } otti_device_info;
 int32_t otti_instance_device_info(otti_instance *inst, int32_t by_col, otti_device_info *out);
+/* the last successful otti_instance_set_values of an instance that keeps its lists in HBM, by HIP events: ms[0] the convert launches, ms[1] the
+   place launches (the first call: the fills that record the slot maps), over all matrices of the call; zeros before any call and on the plain
+   route.  Touches no device. */
+int32_t otti_k_instance_values_kernel_ms(const otti_instance *inst, float ms[2]);
 /* EqPolynomial::evals */
 int32_t otti_k_eq_evals(const uint8_t *h_r, size_t ell, uint8_t *h_out, float *kernel_ms);
 /* DensePolynomial::bound_poly_var_top / _bot (in place on a staged copy; out has len/2 entries) */

@@ -196,6 +196,14 @@ class _Coo(ctypes.Structure):                                  # otti_coo
 IDX_U32, IDX_I32, IDX_U64, IDX_I64 = 0, 1, 2, 3                # OTTI_IDX_*
 _sig("otti_instance_from_coo", _i32, _u64, _u64, _u64, ctypes.POINTER(_Coo), _i32, _vp, ctypes.POINTER(_vp))
 _sig("otti_instance_device_entries", _i32, _vp, _i32, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_sz))
+class _CooValues(ctypes.Structure):                            # otti_coo_values
+    _fields_ = [("val", _vp), ("n", _sz), ("val_format", _i32), ("val_stride_bytes", _sz)]
+
+
+_sig("otti_instance_set_values", _i32, _vp, ctypes.POINTER(_CooValues), _i32, _vp)
+_sig("otti_instance_values_info", _i32, _vp, ctypes.POINTER(_u64), ctypes.POINTER(_i32), ctypes.POINTER(_u64), ctypes.POINTER(ctypes.c_double))
+_sig("otti_k_instance_values_kernel_ms", _i32, _vp, _fp)
+_sig("otti_comp_comm_revalue", _i32, _vp, _vp, _vp)
 _sig("otti_k_decomm_entries", _i32, _vp, _vp, _vp, _sz, _sz, _sz, ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _fp)
 _sig("otti_k_shard_filter", _i32, _vp, _vp, _vp, _sz, ctypes.c_uint32, ctypes.c_uint32, _i32, _vp, _vp, _vp, ctypes.POINTER(_sz), _fp)
 INGEST_MODES = {"auto": 0, "host": 1, "device": 2}             # OTTI_INGEST_*
@@ -399,6 +407,63 @@ class Instance:
         _check(lib.otti_instance_from_coo(num_cons, num_vars, num_inputs, coo, 1 if all(on_gpu) else 0, producer, ctypes.byref(h)))
         del keep
         return cls(h, None)
+
+    def set_values(self, A=None, B=None, C=None, stream=None, montgomery=False):
+        """otti_instance_set_values: new coefficients for the entries of A, B, C in place (None: that matrix stays).  Each is what from_coo takes
+        as vals — 1-D int64 / uint64 or uint8 of shape (n, 32), numpy or torch, strided views read where they are — with one element per entry
+        in ``entries`` order.  Either every array given lives on the GPU or none does; ``stream`` as in from_coo.  A coefficient >= l raises
+        what Instance.new raises for the new triples and leaves the instance as it was.  Returns self."""
+        given = [v for v in (A, B, C) if v is not None]
+        torch = sys.modules.get("torch")
+        on_gpu = [torch is not None and isinstance(v, torch.Tensor) and v.is_cuda for v in given]
+        if any(on_gpu) and not all(on_gpu):
+            raise SpartanError(-21, "set_values: either every array lives on the GPU or none does")
+        dev = bool(on_gpu) and all(on_gpu)
+        vals, keep, copied = (_CooValues * 3)(), [], False
+        for k, v in enumerate((A, B, C)):
+            if v is None:
+                vals[k] = _CooValues(None, 0, WIT_CANONICAL32, 0)
+                continue
+            if dev:
+                fmt = _coo_val_format(v.dtype == torch.int64 and v.dim() == 1, getattr(torch, "uint64", None) == v.dtype and v.dim() == 1,
+                                      v.dtype == torch.uint8 and v.dim() == 2 and v.shape[1] == 32, montgomery)
+                eb = 8 if fmt in (WIT_I64, WIT_U64) else 32
+                n = v.shape[0]
+                if n > 1 and (v.stride(0) * v.element_size() < eb or (v.dim() == 2 and v.stride(1) != 1)):
+                    v, copied = v.contiguous(), True
+                vals[k] = _CooValues(v.data_ptr() if v.numel() else None, n, fmt, v.stride(0) * v.element_size() if n > 1 else 0)
+            else:
+                v = v.numpy() if torch is not None and isinstance(v, torch.Tensor) else np.asarray(v)
+                fmt = _coo_val_format(v.dtype == np.int64 and v.ndim == 1, v.dtype == np.uint64 and v.ndim == 1,
+                                      v.dtype == np.uint8 and v.ndim == 2 and v.shape[1] == 32, montgomery)
+                eb = 8 if fmt in (WIT_I64, WIT_U64) else 32
+                n = v.shape[0]
+                if n > 1 and (v.strides[0] < eb or (v.ndim == 2 and v.strides[1] != 1)):
+                    v = np.ascontiguousarray(v)
+                vals[k] = _CooValues(_ptr(v), n, fmt, v.strides[0] if n > 1 else 0)
+            keep.append(v)                                     # alive until the call has returned
+        producer = None
+        if dev:
+            if copied:                                         # a contiguous copy was queued on torch's current stream, whichever stream the caller names
+                torch.cuda.current_stream(keep[0].device).synchronize()
+            producer = _torch_stream(torch, keep[0], stream)
+        _check(lib.otti_instance_set_values(self._h, vals, 1 if dev else 0, producer))
+        del keep
+        return self
+
+    def values_info(self):
+        """otti_instance_values_info: dict of generation (0 at creation, +1 per successful set_values), slots_resident and slot_bytes (the slot
+        maps the first set_values of a device-ingested instance builds: 8 bytes per entry) and ms (staging, convert + validate, place) of the
+        last call"""
+        g, sr, sb, ms = _u64(), _i32(), _u64(), (ctypes.c_double * 3)()
+        _check(lib.otti_instance_values_info(self._h, ctypes.byref(g), ctypes.byref(sr), ctypes.byref(sb), ms))
+        return dict(generation=g.value, slots_resident=bool(sr.value), slot_bytes=sb.value, ms=tuple(ms))
+
+    def values_kernel_ms(self):
+        """otti_k_instance_values_kernel_ms: (convert, place) launches of the last set_values by HIP events, ms"""
+        ms = (ctypes.c_float * 2)()
+        _check(lib.otti_k_instance_values_kernel_ms(self._h, ms))
+        return ms[0], ms[1]
 
     def device_entries(self, which):
         """otti_instance_device_entries: (ptr_row, ptr_col, ptr_val, n) of the entry lists a device-ingested instance keeps in HBM — u32 rows, u32
@@ -1097,6 +1162,12 @@ class ComputationCommitment:
         """Rebuild the decommitment of ``inst`` on the device.  ``verify``: also recompute both commitments and compare them with the
         stored points (raises SpartanError, code -21, on a difference); without it the caller is trusted beyond the dimensions."""
         _check(lib.otti_comp_comm_attach(self._h, inst._h, gens._h, 1 if verify else 0))
+        return self
+
+    def revalue(self, inst, gens):
+        """otti_comp_comm_revalue: this commitment (with its decommitment) brought to ``inst``'s current coefficients after Instance.set_values:
+        only the values and the commitment rows that hold them are computed again; ``bytes`` then equals a fresh encode's."""
+        _check(lib.otti_comp_comm_revalue(self._h, inst._h, gens._h))
         return self
 
     def _dims(self):

@@ -315,7 +315,7 @@ int32_t otti_witness_drop_products(otti_witness *wit) { return witness_read(wit,
 int32_t otti_witness_products_info(const otti_witness *wit, int32_t *kept, size_t *n_rows, const void **d_Az, const void **d_Bz, const void **d_Cz,
                                    uint64_t *n_unsat, uint64_t *patches, uint64_t *rows_recomputed, uint64_t *full_passes) {
     return witness_read(wit, [&](const DeviceWitness &w) {
-        if (kept) *kept = w.prod_inst ? 1 : 0;
+        if (kept) *kept = w.products_live() ? 1 : 0;                 // (products of an earlier coefficient generation are not kept: device.h prod_gen)
         if (n_rows) *n_rows = w.prod_abc[0].n;
         if (d_Az) *d_Az = w.prod_abc[0].p;
         if (d_Bz) *d_Bz = w.prod_abc[1].p;
@@ -763,6 +763,43 @@ int32_t otti_instance_device_entries(const otti_instance *inst, int32_t which, c
         if (d_val) *d_val = e ? e->val.p : nullptr;
         if (n) *n = e ? e->n : 0;
         return OTTI_OK;
+    });
+}
+// ---- new coefficients for a live instance (device.h instance_set_values, k_revalue.hip).  Everything the arguments alone say — the counts against
+// the instance's included — is said before a device is asked for; a device is asked for only when the call needs one.
+int32_t otti_instance_set_values(otti_instance *inst, const otti_coo_values vals[3], int32_t src_on_device, void *stream) {
+    return guarded([&] {
+        if (!inst || !vals) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        Instance &I = *inst->I;
+        ValuesSource src[3];
+        for (int k = 0; k < 3; k++) {
+            const otti_coo_values &m = vals[k];
+            check_wit_source(m.val, m.n, m.val_format, m.val_stride_bytes, true);
+            if (m.val && m.n != I.nnz[k]) throw Error(OTTI_ERR_BAD_ARG, "set_values: a matrix's count differs from its number of entries");
+            src[k] = ValuesSource{m.val, m.n, m.val_format, m.val_stride_bytes ? m.val_stride_bytes : wit_elem_bytes(m.val_format)};
+        }
+        if ((src_on_device || instance_values_on_device(I)) && otti_device_count() < 1) throw Error(OTTI_ERR_NO_DEVICE, "no device: the coefficients are replaced on one");
+        instance_set_values(I, src, src_on_device != 0, (hipStream_t)stream);
+        return OTTI_OK;
+    });
+}
+int32_t otti_instance_values_info(const otti_instance *inst, uint64_t *generation, int32_t *slots_resident, uint64_t *slot_bytes, double ms[3]) {
+    return guarded([&] {
+        if (!inst) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        const Instance &I = *inst->I;
+        const std::shared_ptr<DeviceInstance> d = I.dev;
+        const bool slots = d && d->slots_resident;
+        if (generation) *generation = I.value_gen;
+        if (slots_resident) *slots_resident = slots ? 1 : 0;
+        if (slot_bytes) { *slot_bytes = 0; if (slots) for (int k = 0; k < 3; k++) *slot_bytes += (uint64_t)d->ent[k].n * 8; }
+        if (ms) for (int k = 0; k < 3; k++) ms[k] = I.values_ms[k];
+        return OTTI_OK;
+    });
+}
+int32_t otti_comp_comm_revalue(otti_comp_comm *comm, otti_instance *inst, otti_snark_gens *gens) {
+    return guarded([&] {
+        if (!comm || !inst || !gens) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        snark_revalue_gpu(*inst->I, *comm->c, *gens->g); return OTTI_OK;
     });
 }
 // ---- the inputs and witness files to a resident witness (zkif.h, k_wit_ingest.hip).  The ladder of otti_instance_from_zkif: the arguments, the

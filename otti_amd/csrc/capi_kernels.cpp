@@ -330,6 +330,14 @@ int32_t otti_instance_device_info(otti_instance *inst, int32_t by_col, otti_devi
         return OTTI_OK;
     });
 }
+int32_t otti_k_instance_values_kernel_ms(const otti_instance *inst, float ms[2]) {
+    return guarded([&] {
+        if (!inst || !ms) throw Error(OTTI_ERR_BAD_ARG, "null argument");
+        const std::shared_ptr<DeviceInstance> d = inst->I->dev;
+        for (int k = 0; k < 2; k++) ms[k] = d && d->slots_resident ? d->values_kernel_ms[k] : 0.0f;
+        return OTTI_OK;
+    });
+}
 int32_t otti_k_eq_evals(const uint8_t *r, size_t ell, uint8_t *out, float *ms) {
     return guarded([&] {
         if (ell > 25) throw Error(OTTI_ERR_BAD_ARG, "ell > 25");

@@ -53,7 +53,17 @@ struct DeviceCoo { DevBuf<uint32_t> row, col; DevBuf<Fr> val; DevBuf<int32_t> co
 // ent[k]: the entry lists themselves, KEPT beside the CSR copies by a device ingest (k_ingest.hip) and by nothing else — they are what
 // Instance::mat() downloads when a host consumer asks for the lists.  Their cost: 40 bytes of HBM per entry (row 4, col 4, val 32) for as long as
 // the instance lives; otti_instance_ingest_info reports it.  An instance uploaded from host lists keeps none (ent[k].n = 0, no buffers).
-struct DeviceInstance { DeviceCsrSet by_row, by_col; size_t nnz = 0; DeviceCoo ent[3]; };
+// slot_row[k], slot_col[k]: where entry i of ent[k] sits in by_row / by_col (its position in idx / val / small of that copy) — made by the first
+// otti_instance_set_values of the instance and by nothing else (k_revalue.hip), kept for its life: 8 bytes per entry.  n_small[k]: how many of
+// ent[k]'s coefficients have a small-integer code, counted then as well, so that the codes rule can be applied again when one matrix changes.
+struct DeviceInstance {
+    DeviceCsrSet by_row, by_col; size_t nnz = 0; DeviceCoo ent[3];
+    DevBuf<uint32_t> slot_row[3], slot_col[3]; bool slots_resident = false; unsigned long long n_small[3] = {0, 0, 0};
+    // set_values' scratch that does not become part of the instance, kept from the first call on so that later calls allocate the staging value
+    // list alone: the convert pass's code lists (4 bytes per entry of every matrix ever replaced) and its four words (error key, three small counts)
+    DevBuf<int32_t> values_code[3]; DevBuf<unsigned long long> values_words;
+    float values_kernel_ms[2] = {0, 0};                      // the last set_values' convert and place launches by HIP events (all matrices of the call)
+};
 struct DevCtx;
 bool classify_coefficients(DevCtx &c, DeviceCoo coo[3]);
 void build_csr_set(DevCtx &c, DeviceCsrSet &d, const DeviceCoo coo[3], bool by_col, size_t rows, bool use_small);
@@ -72,6 +82,15 @@ struct CooSource { const void *row, *col, *val; size_t n; int index_format, val_
 // instance_new's order is thrown with its code and wording; everything allocated is released and the context stays usable.  Returns when the
 // sources are free again.
 std::unique_ptr<Instance> instance_from_coo(size_t num_cons, size_t num_vars, size_t num_inputs, const CooSource mats[3], bool src_on_device, hipStream_t producer);
+// otti_instance_set_values behind its argument checks — the counts against I.nnz among them: capi.cpp — (k_revalue.hip): new coefficients for the entries of a live instance, in the order the
+// entries were given.  An instance that keeps its lists in HBM (ent) is revalued there: a convert pass into staging lists (values, codes, the small
+// count, one atomicMin error word), then — only behind a clean word — a place pass through the slot maps into both CSR copies, the staging list
+// swapped in as ent[k].val, the codes rule applied again (small[] allocated or released as the variant flips), materialised host lists refreshed.
+// Any other instance takes instance_set_values_host (a device source is downloaded first).  A refusal throws what instance_new would on the new
+// triples and leaves the instance bit for bit as it was.  Both routes drop `shard` and bump I.value_gen.  Returns when the sources are free again.
+// true: the instance keeps lists in HBM, i.e. the call takes the device route and needs a device
+bool instance_values_on_device(const Instance &I);
+void instance_set_values(Instance &I, const ValuesSource vals[3], bool src_on_device, hipStream_t producer);
 bool device_runtime_up();                                  // a device context exists in this process already (k_context.hip): asking never brings one up
 // Rank k of g holds the constraint rows r = k (mod g) (renumbered r / g, columns untouched: multiply_vec output lands where the
 // low-bit-sharded phase-one tables need it) and, as a second copy, the entries of columns c = k (mod g) (renumbered c / g, rows
@@ -295,7 +314,11 @@ struct DeviceWitness {
     Instance *prod_inst = nullptr;                            // whose matrices they were formed with
     uint64_t prod_unsat = 0;                                  // host copy of *prod_unsat_dev
     unsigned long long prod_patches = 0, prod_rows_recomputed = 0, prod_full_passes = 0;   // since keep_products: patches that recomputed listed rows, those rows, full passes (the first included)
-    bool products_kept_for(const Instance &I) const { return prod_inst == &I && prod_abc[0].p; }
+    // The sums hold the instance's COEFFICIENTS as well: prod_gen is the instance's generation (Instance::value_gen) they were formed at, and
+    // products of another generation are stale — not kept for any reader, not patched by any mutator, recomputed by the next keep_products.
+    uint64_t prod_gen = 0;
+    bool products_live() const { return prod_inst && prod_abc[0].p && prod_gen == prod_inst->value_gen; }
+    bool products_kept_for(const Instance &I) const { return prod_inst == &I && products_live(); }
     void keep_products(Instance &I);                          // one full pass now; again for the same instance: nothing
     void drop_products();
     static void check_range(size_t V, size_t first, size_t count);   // INVALID_NUM_VARS unless [first, first + count) lies within V variables

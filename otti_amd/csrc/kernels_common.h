@@ -56,24 +56,7 @@ template <int F> __device__ __forceinline__ Fr wit_load(const unsigned char *p, 
     }
     return raw;
 }
-// THE conversion rule, for every kernel that takes witness elements in: the word wit_load<F> returned -> the Montgomery element.  An integer is
-// always a scalar; a negative one is l - |x| and so never small.  A 32-byte word >= l is refused: stored as zero, and counted as small as well.
-// small: the canonical value is below 2^128 (MONTGOMERY32: judged on fr_to_raw of the word).
-__device__ __forceinline__ bool fr_raw_below_2p128(const Fr &c) { return (c.v[4] | c.v[5] | c.v[6] | c.v[7]) == 0; }
-template <int F> __device__ __forceinline__ Fr wit_convert(Fr raw, bool neg, bool &refused, bool &small) {
-    Fr out; refused = false;
-    if constexpr (F == WIT_I64 || F == WIT_U64) {
-        if (neg) raw = fr_sub(fr_zero(), raw);                                   // l - |x| (on canonical integers the field subtraction is the integer one mod l)
-        small = !neg;
-        out = fr_mul(raw, fr_R2());
-    } else {
-        small = fr_raw_below_2p128(F == WIT_CANONICAL32 ? raw : fr_to_raw(raw));
-        if (!fr_raw_is_canonical(raw.v)) { out = fr_zero(); refused = small = true; }
-        else if constexpr (F == WIT_CANONICAL32) out = fr_mul(raw, fr_R2());
-        else out = raw;
-    }
-    return out;
-}
+// (THE conversion rule, wit_convert<F>: the word wit_load<F> returned -> the Montgomery element, lives in spartan.h, where the host reads it too)
 // a lane's two tallies summed over its wave and added to counts[0], counts[1]
 __device__ __forceinline__ void wit_tally(unsigned a, unsigned b, unsigned long long *counts) {
     for (int o = 32; o >= 1; o >>= 1) { a += __shfl_down(a, o); b += __shfl_down(b, o); }

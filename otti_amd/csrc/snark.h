@@ -39,6 +39,7 @@ struct CompComm {
     size_t batch_size = 3, num_ops = 0, num_mem_cells = 0;   // SparseMatPolyCommitment
     std::vector<CPoint> comm_ops, comm_mem;
     std::shared_ptr<DeviceDecomm> dec;                       // prover side only
+    uint64_t dec_gen = 0;                                    // the instance's coefficient generation (Instance::value_gen) dec was last built (encode, attach) or revalued from
     // verifier side: comm_ops and comm_mem decoded in HBM for snark_verify_many's passes, built once by whichever thread first needs them
     // (under row_cache_mu), shared read-only, freed with the commitment
     mutable std::shared_ptr<RowSumsCache> row_cache; mutable std::mutex row_cache_mu;
@@ -168,6 +169,18 @@ std::unique_ptr<CompComm> snark_encode_gpu(Instance &inst, SnarkGens &g);
 // difference: Error(OTTI_ERR_BAD_ARG), comm stays as it was).  Dimensions are checked before the device is touched; a commitment that
 // already has its decommitment is left alone.
 void snark_attach_gpu(Instance &inst, CompComm &comm, SnarkGens &g, bool verify);
+// otti_comp_comm_revalue: a commitment with its decommitment brought to the instance's CURRENT coefficients (otti_instance_set_values) without a new
+// encode.  Of the 16 N + 2 M committed elements only the 3 N values of comb_ops hold coefficients: dec->part(4, k) is written again — from the lists
+// the instance keeps in HBM when it keeps them, else from the host lists, upstream's zero padding kept — and the rows of comm_ops that meet them
+// (value_rows.h comm_value_rows) are summed again with the bulk MSM; addresses, timestamps, comb_mem and comm_mem stay, row_cache is dropped, the
+// instance's generation recorded.  comm.serialize() then equals a fresh encode's of the revalued instance.  Checks as attach: the dimensions and
+// the generators, before the device is touched; a commitment without decommitment is BAD_ARG.
+void snark_revalue_gpu(Instance &inst, CompComm &comm, SnarkGens &g);
+// SNARK::prove's refusal of a commitment whose decommitment predates the instance's coefficients (BAD_ARG), before any device work
+inline void check_comm_generation(const Instance &inst, const CompComm &comm) {
+    if (comm.dec && comm.dec_gen != inst.value_gen)
+        throw Error(OTTI_ERR_BAD_ARG, "the computation commitment predates the instance's coefficients (otti_instance_set_values): otti_comp_comm_revalue brings it up to date");
+}
 std::vector<uint8_t> snark_prove_gpu(Instance &inst, CompComm &comm, const uint8_t *vars32, size_t nvars, const std::vector<Fr> &inputs, SnarkGens &g,
                                      const void *tlabel, size_t tlabel_len, const uint8_t *seed32, SnarkTimings *tm);
 struct DeviceWitness;                                        // device.h: the assignment resident in HBM (otti_witness_upload)

@@ -1,6 +1,7 @@
 // SNARK::encode and attach on the MI355X: the dense representation of A, B, C (addresses, timestamps, values: 16 N + 2 M field elements)
 // built in HBM and committed with the bulk MSM.  Follows upstream libspartan src/r1csinstance.rs, src/sparse_mlpoly.rs; see snark.h.
 #include "snark_prover.h"
+#include "value_rows.h"
 #include <thread>
 
 namespace otti {
@@ -146,7 +147,7 @@ std::unique_ptr<CompComm> snark_encode_gpu(Instance &I, SnarkGens &g) {
     lap("commit comb_ops (+ window table)");
     cc->comm_mem = commit_poly(c, *g.eval, dec->comb_mem.p, g.mem);
     lap("commit comb_mem");
-    cc->dec = dec;
+    cc->dec = dec; cc->dec_gen = I.value_gen;
     return cc;
 }
 
@@ -165,7 +166,40 @@ void snark_attach_gpu(Instance &I, CompComm &cc, SnarkGens &g, bool verify) {
         if (!same_points(commit_poly(c, *g.eval, dec->comb_mem.p, g.mem), cc.comm_mem)) throw Error(OTTI_ERR_BAD_ARG, "attach: comm_mem recomputed from this instance differs from the stored commitment");
         lap("verify comm_mem");
     }
-    cc.dec = dec;
+    cc.dec = dec; cc.dec_gen = I.value_gen;
+}
+
+void snark_revalue_gpu(Instance &I, CompComm &cc, SnarkGens &g) {
+    size_t N, M; decomm_dims(I, N, M);
+    if (!cc.dec) throw Error(OTTI_ERR_BAD_ARG, "revalue: this computation commitment carries no decommitment (encode it, or attach the instance first)");
+    if (I.num_cons != cc.num_cons || I.num_vars != cc.num_vars || I.num_inputs != cc.num_inputs || N != cc.num_ops || M != cc.num_mem_cells || cc.dec->N != N || cc.dec->M != M)
+        throw Error(OTTI_ERR_BAD_ARG, "the computation commitment was made for an instance of other dimensions");
+    check_gens_fit(I, g, N, M);
+    if (cc.comm_ops.size() != g.ops.L) throw Error(OTTI_ERR_BAD_ARG, "the computation commitment was made for other generators");
+    DevCtx &c = DevCtx::get();
+    EncodeLaps lap(c);
+    DeviceDecomm &dec = *cc.dec;
+    // ---- the values alone: entries [0, nnz) of part(4, k); what lies behind them is upstream's zero padding and stays
+    const bool resident = decomm_entries_resident(I);
+    const std::shared_ptr<DeviceInstance> d = resident ? I.dev : nullptr;
+    for (int k = 0; k < 3; k++) {
+        if (!I.nnz[k]) continue;
+        if (resident) OTTI_HIP(hipMemcpyAsync(dec.part(4, k), d->ent[k].val.p, I.nnz[k] * sizeof(Fr), hipMemcpyDeviceToDevice, c.stream));
+        else OTTI_HIP(hipMemcpyAsync(dec.part(4, k), I.mat(k).val.data(), I.nnz[k] * sizeof(Fr), hipMemcpyHostToDevice, c.stream));
+    }
+    lap("revalue: values into comb_ops");
+    // ---- the rows of comm_ops that meet them, as one block of independent row sums
+    const ValueRows vr = comm_value_rows(N, g.ops.L, g.ops.R);
+    const size_t rows = vr.r1 - vr.r0;
+    ensure_gens_device(*g.eval);
+    const Fr *Z = dec.comb_ops.p + vr.r0 * g.ops.R;
+    const bool sparse = dev_small_fraction(c, Z, rows * g.ops.R) > kSparseWitness;
+    dev_msm_rows(c, *g.eval->dev, {.dense = Z, .n_dense = g.ops.R, .rows = rows, .sparse = sparse});
+    c.sync();
+    memcpy(cc.comm_ops[vr.r0].b, c.h_points, 32 * rows);
+    lap("revalue: value rows of comm_ops");
+    { std::lock_guard<std::mutex> lk(cc.row_cache_mu); cc.row_cache.reset(); }
+    cc.dec_gen = I.value_gen;
 }
 
 }  // namespace otti

@@ -424,11 +424,13 @@ std::vector<uint8_t> snark_prove_resident_once(Instance &I, CompComm &comm, Devi
 std::vector<uint8_t> snark_prove_gpu(Instance &I, CompComm &comm, const uint8_t *vars32, size_t nvars, const std::vector<Fr> &inputs, SnarkGens &g,
                                      const void *tlabel, size_t tlabel_len, const uint8_t *seed32, SnarkTimings *tm) {
     if (I.num_cons != comm.num_cons || I.num_vars != comm.num_vars || I.num_inputs != comm.num_inputs) throw Error(OTTI_ERR_BAD_ARG, "commitment belongs to another instance");
+    check_comm_generation(I, comm);
     DeviceWitness wit(I, vars32, nvars, inputs);                 // uploaded (and checked for canonical scalars) inside the call
     return snark_prove_resident(I, comm, wit, g, tlabel, tlabel_len, seed32, tm);
 }
 std::vector<uint8_t> snark_prove_resident(Instance &I, CompComm &comm, DeviceWitness &wit, SnarkGens &g, const void *tlabel, size_t tlabel_len,
                                           const uint8_t *seed32, SnarkTimings *tm, ShardComm *sh) {
+    check_comm_generation(I, comm);                           // before any device work
     // (sharded: every rank of a node sees the same device conditions or none does — a rank that alone repeated its proof would leave the
     // others waiting in the exchange — so the persistent tail, which can time out, is not used at all there)
     if (sh) return snark_prove_resident_once(I, comm, wit, g, tlabel, tlabel_len, seed32, tm, sh);

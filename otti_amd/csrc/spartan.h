@@ -55,12 +55,42 @@ struct Instance {
     bool ingested_on_device = false; uint64_t circuit_bytes = 0; double ingest_ms[4] = {0, 0, 0, 0};
     std::shared_ptr<DeviceInstance> dev;                    // uploaded lazily on the first GPU prove
     std::shared_ptr<DeviceShard> shard;                     // uploaded lazily on the first sharded prove
+    // the coefficient generation (otti_instance_set_values): 0 at creation, +1 per successful replacement.  What was derived from the coefficients
+    // and lives outside the instance — a witness's kept products, a computation commitment's decommitment — records the generation it was made at
+    uint64_t value_gen = 0;
+    double values_ms[3] = {0, 0, 0};                        // the last replacement's laps: staging, convert + validate, place
     // Fr tuple evaluation used by the verifier: (A,B,C)(rx, ry)
     void evaluate(const std::vector<Fr> &rx, const std::vector<Fr> &ry, Fr out[3]) const;
     bool is_sat(const std::vector<Fr> &vars_padded, const std::vector<Fr> &inputs) const;
 };
 std::unique_ptr<Instance> instance_new(size_t num_cons, size_t num_vars, size_t num_inputs, const otti_entry *A, size_t nA,
                                        const otti_entry *B, size_t nB, const otti_entry *C, size_t nC);
+// THE conversion rule, for every kernel and every host loop that takes witness elements or coefficients in (F: OTTI_WIT_*): the raw word — a
+// 32-byte format's eight words as they are, an integer's magnitude in words 0 and 1 with neg saying it was below zero — -> the Montgomery element.
+// An integer is always a scalar; a negative one is l - |x| and so never small.  A 32-byte word >= l is refused: stored as zero, and counted as
+// small as well.  small: the canonical value is below 2^128 (MONTGOMERY32: judged on fr_to_raw of the word).
+HD bool fr_raw_below_2p128(const Fr &c) { return (c.v[4] | c.v[5] | c.v[6] | c.v[7]) == 0; }
+template <int F> HD Fr wit_convert(Fr raw, bool neg, bool &refused, bool &small) {
+    Fr out; refused = false;
+    if constexpr (F == OTTI_WIT_I64 || F == OTTI_WIT_U64) {
+        if (neg) raw = fr_sub(fr_zero(), raw);                                   // l - |x| (on canonical integers the field subtraction is the integer one mod l)
+        small = !neg;
+        out = fr_mul(raw, fr_R2());
+    } else {
+        small = fr_raw_below_2p128(F == OTTI_WIT_CANONICAL32 ? raw : fr_to_raw(raw));
+        if (!fr_raw_is_canonical(raw.v)) { out = fr_zero(); refused = small = true; }
+        else if constexpr (F == OTTI_WIT_CANONICAL32) out = fr_mul(raw, fr_R2());
+        else out = raw;
+    }
+    return out;
+}
+// New coefficients for a matrix of a live instance (= otti_coo_values of the C ABI): n elements in val_format (OTTI_WIT_*), val_stride bytes apart
+// (never 0 here); val == nullptr: the matrix stays as it is.  instance_set_values_host is the plain route, for an instance whose lists are on the
+// host (instance_new, the host zkif load): host arrays converted by the witness rule (a negative I64 is l - |x|), the first refused coefficient in
+// the order A, B, C thrown as instance_new throws it with the instance untouched, then M[k].val replaced, dev and shard dropped (rebuilt lazily)
+// and the generation bumped.  Nothing in it needs a device.
+struct ValuesSource { const void *val; size_t n; int val_format; size_t val_stride; };
+void instance_set_values_host(Instance &I, const ValuesSource vals[3]);
 // fills I.M from the device's entry lists (set by the device layer; host-only builds have no instance that needs it)
 typedef void (*InstanceHostListsHook)(const Instance &I, SparseMat out[3]);
 extern InstanceHostListsHook g_instance_host_lists_hook;

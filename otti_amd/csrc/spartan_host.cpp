@@ -59,6 +59,40 @@ std::unique_ptr<Instance> instance_new(size_t num_cons, size_t num_vars, size_t 
     return I;
 }
 
+// otti_instance_set_values on host lists (spartan.h): everything is converted into lists of its own first, so a refusal leaves I as it was.
+// The element's raw word is read as kernels_common.h wit_load reads it and handed to the one conversion rule, wit_convert.
+template <int F> static void convert_values_host(const ValuesSource &s, std::vector<Fr> &out) {
+    const uint8_t *p = static_cast<const uint8_t *>(s.val);
+    for (size_t i = 0; i < s.n; i++, p += s.val_stride) {
+        Fr raw = fr_zero(); bool neg = false, refused, small;
+        if (F == OTTI_WIT_I64 || F == OTTI_WIT_U64) {
+            uint64_t x; memcpy(&x, p, 8);
+            if (F == OTTI_WIT_I64 && (int64_t)x < 0) { neg = true; x = 0ull - x; }
+            raw.v[0] = (uint32_t)x; raw.v[1] = (uint32_t)(x >> 32);
+        } else memcpy(raw.v, p, 32);
+        out[i] = wit_convert<F>(raw, neg, refused, small);
+        if (refused) throw Error(OTTI_ERR_INVALID_SCALAR, "non-canonical scalar in matrix");
+    }
+}
+void instance_set_values_host(Instance &I, const ValuesSource vals[3]) {
+    std::vector<Fr> fresh[3];
+    for (int k = 0; k < 3; k++) {
+        const ValuesSource &s = vals[k];
+        if (!s.val) continue;
+        fresh[k].resize(s.n);
+        switch (s.val_format) {
+        case OTTI_WIT_CANONICAL32: convert_values_host<OTTI_WIT_CANONICAL32>(s, fresh[k]); break;
+        case OTTI_WIT_MONTGOMERY32: convert_values_host<OTTI_WIT_MONTGOMERY32>(s, fresh[k]); break;
+        case OTTI_WIT_I64: convert_values_host<OTTI_WIT_I64>(s, fresh[k]); break;
+        case OTTI_WIT_U64: convert_values_host<OTTI_WIT_U64>(s, fresh[k]); break;
+        default: throw Error(OTTI_ERR_BAD_ARG, "unknown coefficient format");
+        }
+    }
+    for (int k = 0; k < 3; k++) if (vals[k].val) { (void)I.mat(k); I.M[k].val = std::move(fresh[k]); }
+    I.dev.reset(); I.shard.reset();
+    I.value_gen++;
+}
+
 InstanceHostListsHook g_instance_host_lists_hook = nullptr;
 void Instance::materialise_host_lists() const {
     if (!g_instance_host_lists_hook) throw Error(OTTI_ERR_INTERNAL, "instance without host lists and no device layer to fetch them");

@@ -114,7 +114,7 @@ void DeviceWitness::z_written(DevCtx &c, const Written &w, RowsPlan rows) {
         if (w.vars) small_fraction = dev_small_fraction(c, z.p, z.n / 2);        // the padding zeros count as small
         if (rows.how == RowsPlan::RESUM) sum_rows_into(c, *this, *rows_gens, rows.r0, rows.r1, false);
         rows_ok = true;
-        if (prod_inst) p = dev_products_patch(c, *prod_inst->dev, z.p, w.d_idx, w.n, w.first, w.count, prod_abc[0].p, prod_abc[1].p, prod_abc[2].p, prod_bits.p, prod_unsat_dev.p);
+        if (products_live()) p = dev_products_patch(c, *prod_inst->dev, z.p, w.d_idx, w.n, w.first, w.count, prod_abc[0].p, prod_abc[1].p, prod_abc[2].p, prod_bits.p, prod_unsat_dev.p);
         products_ok = true;
     } catch (...) {
         (void)hipStreamSynchronize(c.stream);
@@ -127,7 +127,7 @@ void DeviceWitness::z_written(DevCtx &c, const Written &w, RowsPlan rows) {
         rows_patched += touched; terms_patched += w.n;
     }
     if (rows.how == RowsPlan::RESUM) rows_resummed += rows.r1 - rows.r0 + 1;
-    if (prod_inst) {
+    if (products_live()) {
         prod_unsat = p.n_unsat;
         if (p.full) prod_full_passes++;
         else if (p.n_touched) { prod_patches++; prod_rows_recomputed += p.n_touched; }
@@ -213,7 +213,7 @@ size_t DeviceWitness::assign(size_t first, int format, const void *src, size_t c
     }
     DevBuf<uint64_t> idx; DevBuf<Fr> delta;
     if (rows.how == RowsPlan::PATCH) { idx.alloc(n_changed); delta.alloc(n_changed); }
-    else if (prod_inst) idx.alloc(n_changed);                     // kept products are patched by the list of changed columns, whatever becomes of kept rows
+    else if (products_live()) idx.alloc(n_changed);                     // kept products are patched by the list of changed columns, whatever becomes of kept rows
     dev_witness_diff_apply(c, format, s.p, s.stride, count, z.p + first, first, n_changed, idx.p, delta.p, true);
     z_written(c, {.d_idx = idx.p, .n = n_changed, .delta = delta.p, .counted = true}, rows);
     if (rows.how == RowsPlan::RESUM) assign_resums++;
@@ -258,7 +258,7 @@ void DeviceWitness::keep_products(Instance &I) {
     try {
         for (int k = 0; k < 3; k++) prod_abc[k].alloc(N);
         prod_bits.alloc((N + 63) >> 6); prod_unsat_dev.alloc(1);
-        prod_inst = &I;
+        prod_inst = &I; prod_gen = I.value_gen;
         dev_products_full(c, *I.dev, z.p, prod_abc[0].p, prod_abc[1].p, prod_abc[2].p, prod_bits.p, prod_unsat_dev.p);
         unsigned long long n = 0;
         OTTI_HIP(hipMemcpyAsync(&n, prod_unsat_dev.p, sizeof n, hipMemcpyDeviceToHost, c.stream));
@@ -269,7 +269,7 @@ void DeviceWitness::keep_products(Instance &I) {
 void DeviceWitness::drop_products() {
     for (int k = 0; k < 3; k++) prod_abc[k].release();
     prod_bits.release(); prod_unsat_dev.release();
-    prod_inst = nullptr; prod_unsat = 0; prod_patches = prod_rows_recomputed = prod_full_passes = 0;
+    prod_inst = nullptr; prod_gen = 0; prod_unsat = 0; prod_patches = prod_rows_recomputed = prod_full_passes = 0;
 }
 bool DeviceWitness::rows_kept_for(const Gens &g) const { return rows_kept.p && rows_R == g.R && rows_stream && !strcmp(rows_stream, g.stream); }
 void DeviceWitness::keep_rows(Gens &g) {
